@@ -20,14 +20,23 @@ target; "bf16" = plain bf16 storage / MFMA (faster, far outside the tolerance - 
 "fp32" = exact fp32 MFMAs.
 
 `value` is measured with ONE batch in flight (--streams 1: BASELINE's "bs=8" read strictly; ms_per_step is then the latency of a
-step).  `multi_stream` repeats the measurement with --multi-streams S (default 3) engine handles per GPU, each with its own HIP
+step).  With --full, `multi_stream` repeats the measurement with --multi-streams S (default 3) engine handles per GPU, each with its own HIP
 stream, hipGraph and camera group, taking the K timed steps round-robin - the reference's deployment shape (one inference engine
 per camera group sharing the GPU, main.py:1236-1291); every step is still one full bs-8 pass.
 
 --collate at N = 1: the RCCL collate step runs on a world-size-1 `nccl` group exactly as it does at N > 1 (same all_gather_into_tensor
-over the zero-copy view of the result block, ordered behind the forward by the engine's event), `value` includes it and `collate` reports its cost per step.
+over the zero-copy view of the result block, ordered behind the forward by the engine's event), `value` includes it; with --full,
+`collate` reports its cost per step.
 
-Prints ONE JSON line on rank 0 with the contract fields plus:
+A plain run sets up, warms up, times the K steps and prints ONE JSON line on rank 0 with the contract fields (metric, value, unit,
+higher_is_better, dtype, ms_per_step = milliseconds of one timed step, ...).  --dump-outputs DIR then also writes what the last timed
+step computed - the [n, Q, 6] result block a caller receives (rank 0's all-gathered block when the collate step runs) as labels.npy,
+scores.npy and boxes.npy, and with --workload two_stage the step's Stage-2 classifier input as crops.npy - all float32.
+
+--full adds every side measurement below (each can still be switched off by its --no-* option), as extra fields of the same line:
+  collate      - the same K steps without the collate step (N > 1 or --collate): the all-gather's cost per step
+  multi_stream - see above; bf16_engine - the plain-bf16 engine, one batch in flight
+  p50_ms_per_frame_bs1 / p99_ms_per_frame_bs1 - synchronous bs-1 latency on the engine of `value`
   roofline     - MFMA roofline of the dominant kernel family (conv_igemm), from HIP-event timings of every launch on the
                  engine's stream (rtd_profile) and the algorithmic FLOPs per launch
   cpu_baseline - the CPU oracle (oracle/rtdetr_oracle.py, fp32 eager PyTorch) timed on this box's host cores on a bounded
@@ -69,6 +78,25 @@ def csrc_sha() -> str:
     return h.hexdigest()[:16]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def write_outputs(d: str, arrays: dict) -> None:
+    """--dump-outputs: each array as d/<name>.npy (float32).  Should they exceed DUMP_LIMIT_BYTES together, every array larger than
+    an equal share keeps a fixed, seeded sample of its flattened elements (in index order) instead."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(1, len(arrays))
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float32)
+        if total > DUMP_LIMIT_BYTES and a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(d, f"{name}.npy"), a)
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -90,11 +118,20 @@ def parse_args(argv=None):
     ap.add_argument("--no-detect-host", action="store_true", help="skip the detect_host_ms measurement (RTDETRDetector.detect on host frames)")
     ap.add_argument("--no-mfma-probe", action="store_true", help="skip the sustained-MFMA-rate probe (roofline.sustained_mfma)")
     ap.add_argument("--collate", action="store_true", help="N = 1: run the RCCL collate step on a world-size-1 nccl group (always on at N > 1)")
-    ap.add_argument("--profile-out", default="")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (collate cost, roofline / per-kernel profile, MFMA probe, bs-1 latency, multi_stream, "
+                         "bf16_engine, detect_host_ms, CPU baselines); a plain run times the K steps only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write what the last timed step computed as DIR/<name>.npy (float32)")
+    ap.add_argument("--profile-out", default="", help="--full: the per-launch rtd_profile records as JSON")
     ap.add_argument("--opt", action="append", default=[], help="rtd_debug_option name=value (A/B runs)")
     ap.add_argument("--launch-selftest", action="store_true",
                     help="CPU-only: form the world (gloo), all-gather the rank ids, print them as JSON - tests the self-launch path")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.profile_out and not args.full:
+        ap.error("--profile-out needs --full (the per-kernel profile is a side measurement)")
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def self_launch(args) -> int:
@@ -149,7 +186,7 @@ def bench_crop_step(batch: int, size: int, seed: int = 5000, n_crops: int = 16):
     def run(engine, frames, stream):
         engine.signal_stream(stream.cuda_stream)          # Stage 2 after Stage 1
         with torch.cuda.stream(stream):
-            batcher.preprocess_batch(frames, rects)
+            return batcher.preprocess_batch(frames, rects)
 
     info = {"crops_per_step": n_crops, "crop_sides": "rng.integers(64, 512)", "classifier_input": [n_crops, 3, batcher.input_size, batcher.input_size],
             "timed": "detect + crop/resize/normalise batch (one asynchronous launch on a torch-owned stream ordered after the forward); classifier forward EXCLUDED (EVA02 out of scope)"}
@@ -187,7 +224,7 @@ def main():
 
     from telescope_cam_detection_amd import _capi
     from telescope_cam_detection_amd.arch import ARCHS
-    from telescope_cam_detection_amd.shard import collate_after
+    from telescope_cam_detection_amd.shard import DevBlock, collate_after
     from telescope_cam_detection_amd.synth import noise_frame
     from telescope_cam_detection_amd.weights import fold_weights, pack_blob, synth_weights
 
@@ -208,8 +245,9 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
 
-    def measure(precision: str, S: int, crops=None, collate=collate):
-        """K timed steps round-robin over S engine handles of `precision`; returns (elapsed seconds, handles, their frames)."""
+    def measure(precision: str, S: int, crops=None, collate=collate, outputs=None):
+        """K timed steps round-robin over S engine handles of `precision`; returns (elapsed seconds, handles, their frames).
+        `outputs` (a dict): filled with what the last timed step computed, as host float32 arrays."""
         prec = _capi.precision_code(precision)
         # several handles per GPU run the throughput profile (rtd_config.profile); a lone handle the latency profile
         prof_mode = _capi.PROFILE_THROUGHPUT if (S > 1 and not args.latency_profile) else _capi.PROFILE_LATENCY
@@ -222,12 +260,13 @@ def main():
         # inside the library and are ordered against these through the library's events (shard.collate_after)
         streams = [torch.cuda.Stream(device=torch.device("cuda", local_rank)) for e in engs]
         gathered = [torch.empty(world * B * Q * 6, dtype=torch.float32, device="cuda") for _ in range(S)] if collate else None
+        crops_out = [None] * S
 
         def step(k):
             si = k % S
             engs[si].infer_async_prepared(prepared[si])
             if crops is not None:
-                crops(engs[si], frames_of[si], streams[si])
+                crops_out[si] = crops(engs[si], frames_of[si], streams[si])
             if collate:
                 collate_after(engs[si], gathered[si], streams[si])   # all-gather ordered after this engine's forward, next forward after it
 
@@ -243,6 +282,19 @@ def main():
             t = torch.tensor([el], dtype=torch.float64, device="cuda")
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
+        if outputs is not None:
+            # the last timed step ran on handle (K - 1) % S: its result block (the all-gathered blocks of every rank when the collate
+            # step runs - what rank 0's web server receives) and its Stage-2 classifier input; the fence above has drained every stream
+            si = (args.steps - 1) % S
+            if collate:
+                block = gathered[si]
+            else:
+                ptr, n = engs[si].result_block()
+                block = torch.as_tensor(DevBlock(ptr, n), device=torch.device("cuda", local_rank))
+            rows = block.reshape(-1, Q, 6).cpu().numpy().astype(np.float32)
+            outputs.update(labels=rows[..., 0], scores=rows[..., 1], boxes=rows[..., 2:6])
+            if crops_out[si] is not None:
+                outputs["crops"] = crops_out[si].cpu().numpy().astype(np.float32)
         return el, engs, frames_of
 
     crops_fn, crop_info = None, None
@@ -250,7 +302,10 @@ def main():
         crops_fn, crop_info = bench_crop_step(B, H, seed=5000 + rank)
 
     S = max(1, args.streams)
-    elapsed, engs, frames_of = measure(args.precision, S, crops_fn)
+    outputs = {} if (args.dump_outputs and rank == 0) else None
+    elapsed, engs, frames_of = measure(args.precision, S, crops_fn, outputs=outputs)
+    if outputs is not None:
+        write_outputs(args.dump_outputs, outputs)
     eng, frames = engs[0], frames_of[0]
     fps = world * B * args.steps / elapsed
     out = {
@@ -267,7 +322,7 @@ def main():
                               "fp32": "exact fp32 MFMAs"}[args.precision]},
         "rccl_ranks": rccl_ranks,
     }
-    if collate:
+    if collate and args.full:
         # the same K steps without the collate step: the all-gather's cost per step at THIS world size (world size 1: RCCL's launch + local copy)
         for e in engs:
             e.close()
@@ -284,7 +339,8 @@ def main():
     if args.arch in CANON_GFLOP_PER_FRAME and H == 640:
         out["mfma_frac_whole_model"] = round(CANON_GFLOP_PER_FRAME[args.arch] * fps / world / (MFMA_PEAK_TFLOPS[args.precision] * 1e3), 4)
 
-    if rank == 0:
+    # ---- everything below is a side measurement of --full; a plain run closes its handles and prints the line ----
+    if rank == 0 and args.full:
         # ---- per-kernel HIP-event profile on the engine's stream -> roofline of the dominant kernel ----
         print(f"[bench] {fps:.1f} frames/s; profiling kernels ...", file=sys.stderr, flush=True)
         prof = eng.profile(B, reps=5)
@@ -390,14 +446,14 @@ def main():
 
     # ---- several batches in flight (same engine), and the plain-bf16 engine for comparison: extra lines, never `value` ----
     MS = args.multi_streams
-    if MS > 1 and MS != S and args.workload == "detect":
+    if args.full and MS > 1 and MS != S and args.workload == "detect":
         el, es, _ = measure(args.precision, MS)
         out["multi_stream"] = {"value": round(world * B * args.steps / el, 2), "unit": "frames/s", "streams_per_gpu": MS,
                                "ms_per_step": round(1000.0 * el / args.steps, 4),
                                "note": f"same K steps round-robin over {MS} throughput-profile handles ({MS} bs-{B} batches in flight)"}
         for e in es:
             e.close()
-    if args.precision == "f16x3" and not args.no_bf16_line and args.workload == "detect" and world == 1:
+    if args.full and args.precision == "f16x3" and not args.no_bf16_line and args.workload == "detect" and world == 1:
         el, es, _ = measure("bf16", 1)
         out["bf16_engine"] = {"value": round(world * B * args.steps / el, 2), "unit": "frames/s", "streams_per_gpu": 1,
                               "ms_per_step": round(1000.0 * el / args.steps, 4),
@@ -405,7 +461,7 @@ def main():
         for e in es:
             e.close()
 
-    if rank == 0 and world == 1 and not args.no_detect_host and args.workload == "detect" and args.precision == "f16x3" and not args.opt:
+    if args.full and rank == 0 and world == 1 and not args.no_detect_host and args.workload == "detect" and args.precision == "f16x3" and not args.opt:
         # ---- the call the product makes: RTDETRDetector.detect(host frame), protocol of the reference's tests/test_inference.py:63-115 ----
         print("[bench] detect() on host frames ...", file=sys.stderr, flush=True)
         import logging
@@ -435,7 +491,7 @@ def main():
 
     if rank == 0:
         # ---- CPU baseline: the oracle on this box's host cores, bounded sample ----
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             from oracle import rtdetr_oracle as orc
             # the box's CPU share, not the host's core count (oversubscribed OpenMP spin-waits look like a hang)
             cores = min(len(os.sched_getaffinity(0)), int(os.environ.get("RTD_CPU_THREADS", "16")))

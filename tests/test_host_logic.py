@@ -176,6 +176,33 @@ def test_bench_self_launch_forms_a_world_of_two_on_gloo():
     assert out["world"] == 2 and out["ranks"] == [0, 1] and out["gpus"] == 2
 
 
+def test_bench_options_and_output_dump(tmp_path, monkeypatch):
+    """a plain bench.py run leaves the side measurements to --full; --dump-outputs writes float32 .npy files, and outputs that exceed the
+    size limit together keep the same seeded sample of their elements on every run"""
+    import bench
+    a = bench.parse_args(["--gpus", "1", "--steps", "5", "--warmup", "2"])
+    assert a.full is False and a.dump_outputs == "" and a.steps == 5 and a.warmup == 2
+    a = bench.parse_args(["--full", "--dump-outputs", str(tmp_path), "--profile-out", "p.json"])
+    assert a.full is True and a.dump_outputs == str(tmp_path)
+    for bad in (["--profile-out", "p.json"], ["--steps", "0"]):
+        with pytest.raises(SystemExit):
+            bench.parse_args(bad)
+    small = np.arange(24, dtype=np.float64).reshape(2, 3, 4)
+    big = np.random.default_rng(3).standard_normal((64, 1000))
+    bench.write_outputs(str(tmp_path / "a"), {"small": small, "big": big})
+    assert np.load(tmp_path / "a" / "small.npy").dtype == np.float32
+    np.testing.assert_array_equal(np.load(tmp_path / "a" / "big.npy"), big.astype(np.float32))
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 100_000)
+    for d in ("b", "c"):
+        bench.write_outputs(str(tmp_path / d), {"small": small, "big": big})
+    s = np.load(tmp_path / "b" / "small.npy")
+    np.testing.assert_array_equal(s, small.astype(np.float32))                   # under its share: whole
+    b = np.load(tmp_path / "b" / "big.npy")
+    assert b.dtype == np.float32 and b.ndim == 1 and s.nbytes + b.nbytes <= 100_000 and b.size == 50_000 // 4
+    np.testing.assert_array_equal(b, np.load(tmp_path / "c" / "big.npy"))
+    assert np.isin(b, big.astype(np.float32)).all()
+
+
 class _FakeEngine:
     """stands in for _capi.Engine on a box without a GPU: records what the detector asks for"""
     max_batch, num_queries = 4, 5

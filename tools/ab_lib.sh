@@ -4,7 +4,7 @@
 # the current build, alternating, bench.py's `value` and the conv family's per-step time.
 #   cp telescope_cam_detection_amd/lib/libmi355rtdetr.so tools/_bin/lib_old.so   (before rebuilding)
 #   /usr/local/graft/bin/gpurun --timeout 900 -- 'bash tools/ab_lib.sh [extra bench.py flags]'
-B="--steps 100 --warmup 10 --multi-streams 0 --no-bf16-line --no-cpu-baseline --no-latency --no-detect-host"
+B="--full --steps 100 --warmup 10 --multi-streams 0 --no-bf16-line --no-cpu-baseline --no-latency --no-detect-host"
 for rep in 1 2 3; do
   for which in old new; do
     if [ $which = old ]; then export RTD_LIB_PATH=$PWD/tools/_bin/lib_old.so; else unset RTD_LIB_PATH; fi

@@ -4,7 +4,7 @@ opt=$1; shift
 vals=()
 while [ $# -gt 0 ] && [ "$1" != "--" ]; do vals+=("$1"); shift; done
 [ "$1" = "--" ] && shift
-B="--steps 200 --warmup 20 --multi-streams 0 --no-bf16-line --no-cpu-baseline --no-latency --no-detect-host --no-mfma-probe"
+B="--full --steps 200 --warmup 20 --multi-streams 0 --no-bf16-line --no-cpu-baseline --no-latency --no-detect-host --no-mfma-probe"
 for rep in 1 2 3; do
   for v in "${vals[@]}"; do
     timeout -k 10 300 python bench.py $B --opt $opt=$v "$@" 2>/dev/null | tail -1 > /tmp/ab.json || exit 1

@@ -5,7 +5,7 @@
 export TMPDIR=/tmp
 O=gpurun_out/ab_rocprof
 mkdir -p $O
-PROF="--steps 20 --warmup 3 --streams 1 --multi-streams 0 --no-bf16-line --no-cpu-baseline --no-latency --no-detect-host --no-mfma-probe --opt side_stream=0"
+PROF="--full --steps 20 --warmup 3 --streams 1 --multi-streams 0 --no-bf16-line --no-cpu-baseline --no-latency --no-detect-host --no-mfma-probe --opt side_stream=0"
 for rep in 1 2; do
   for which in old new; do
     if [ $which = old ]; then export RTD_LIB_PATH=$PWD/tools/_bin/lib_old.so; else unset RTD_LIB_PATH; fi
