@@ -37,8 +37,7 @@ int rtd_profile(rtd_handle h, int32_t n, int32_t reps, rtd_layer_time* out, int3
  * Conv dispatch, bf16 / fp32 operands (csrc/common.h ConvOpts; one tile family since round 5):
  *   conv_mode [0]   0 auto | 1 register-staged fallback kernel only | 3, 4 wave-specialised LDS-DMA tile with 4 / 2 stages everywhere |
  *                   10 128 x 64 tile everywhere
- *   ws2_min_blocks [257], ws64_max_blocks [160], glds_min_blocks [4], glds_min_n [128], reg_epilogue [1], prefetch [1],
- *   glds_drop [0: timing-only probes, results wrong when set]
+ *   ws2_min_blocks [257], ws64_max_blocks [160], glds_min_blocks [4], glds_min_n [128], reg_epilogue [1], prefetch [1]
  *   conv_reg [3] (pair operands too): bit 0 direct 3x3 kernels for the narrow stem / stage-0 layers, bit 1 the 64-channel pair kernel
  * Conv dispatch, pair operands (RTD_PREC_F16X3): split_ws2_min_blocks [257] | split_ws64_max_blocks [160] |
  *   split_flex [1: flexible tile heights on grids of <= split_flex_small_max [200] tiles], split_flex_min_nk [4] |

@@ -129,7 +129,7 @@ inline void rtd_launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, unsigned
 struct ConvOpts {
   // ---- bf16 / fp32 operands
   int conv_mode = 0;          // 0 auto; test / A-B modes: 1 = register-staged fallback kernel only, 3 / 4 = wave-specialised tile with 4 / 2 stages
-                              // everywhere, 7 = 256-pixel tile, 8 = A-stationary kernel, 9 = streaming kernels on any grid, 10 = 128 x 64 tile
+                              // everywhere, 10 = 128 x 64 tile everywhere
   int glds_min_blocks = 4;    // bf16: smallest grid of 128 x 128 tiles the LDS-DMA kernels take (fp32: 512, fixed)
   int glds_min_n = 128;       // bf16: smallest Cout the LDS-DMA kernels take (64 measured slower on the stage-0 reduce convs: 45 vs 42 us)
   int ws2_min_blocks = 257;   // grids that do not fit one block per CU run the 2-stage kernel at 2 blocks per CU
@@ -137,7 +137,6 @@ struct ConvOpts {
   int reg_epilogue = 1;       // residual-free bf16 tiles finish in registers
   int conv_reg = 3;           // direct 3x3 kernels for the narrow layers (bit 1: the 64-channel pair kernel)
   int prefetch = 1;           // 0 = launches ignore ConvArgs::pf
-  int glds_drop = 0;          // timing-only probes (results wrong): 1 = x descriptor has 0 records, 2 = w, 4 = no DMA at all, 32 = block stamps
   // ---- pair (F16X2) operands
   int split_ws2_min_blocks = 257;
   int split_ws64_max_blocks = 160;

@@ -57,7 +57,7 @@ struct ConvK {
   // ldx2, x2_bstride count bf16 ELEMENTS (twice the channels); y_split / res_split = the output / residual is a F16X2 tensor, its
   // ldy / y_bstride (ldr / r_bstride) count channels as for fp32 and addresses go through split_off()
   int split = 0, y_split = 0, res_split = 0;
-  int raw = 0;           // two-pass split-K: the tile kernels write bare fp32 partial sums (no bias) to slice `s` of ConvG::slab
+  int raw = 0;           // two-pass split-K: the tile kernels write bare fp32 partial sums (no bias) to slice `s` of ConvWorkspace::slab
 };
 
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
@@ -78,7 +78,7 @@ __device__ __forceinline__ void prefetch_share(const ConvK& a, unsigned block, u
 
 // the activation is a kernel argument: the epilogue loops are instantiated once per activation (dispatch_act) so that the
 // choice costs one scalar branch per block - as a per-element switch (8 scalar branches around each of a thread's 32-64 outputs)
-// it was 4.5 us of a 20 us launch (s_memtime stamps, tools/conv_stamps.py)
+// it was 4.5 us of a 20 us launch (in-kernel s_memtime stamps, EXPERIMENTS.md "Timing probes")
 template <int A> struct ActC { static constexpr int value = A; };
 template <int ACT> __device__ __forceinline__ float act_c(float v) {
   if (ACT == ACT_RELU) return fmaxf(v, 0.f);
@@ -341,7 +341,7 @@ __global__ __launch_bounds__(256) void conv_igemm_kernel(const ConvK a) {
 
 // (image, row, column) of an output pixel, walked 32 pixels at a time: the loaders of the tile kernels need it for every 32nd row of their
 // tile, and a division by a run-time extent is ~35 instructions with quarter-rate multiplies - seven rows' worth was 5000 cycles before a
-// block's first DMA (stamps of conv_igemm_wsq_kernel: first barrier passed at 4944 cycles with the DMA switched off).
+// block's first DMA (stamps of conv_igemm_wsq_kernel: first barrier passed at 4944 cycles with the DMA switched off, EXPERIMENTS.md "Timing probes").
 struct PixWalk { int b, oy, ox; };
 __device__ __forceinline__ void pix_init(const ConvK& a, int m, PixWalk& p) {
   p.b = m / a.OHW;
@@ -359,11 +359,136 @@ struct ConvG {
   ConvK k;
   unsigned x_bytes, w_bytes;   // extents of the two buffers from their base pointers (buffer descriptors)
   unsigned x2_bytes;           // extent of the second input
-  unsigned y_bytes;            // extent of the output (A-stationary kernel: buffer stores), 0 = not provided
-  int probe;                   // timing-only probes (results wrong): bit 2 = issue no DMA at all; bit 5 = block stamps into `slab`
   int splitk;                  // pair kernels, two-pass split-K: the grid is splitk x tiles (1 = off), see launch_conv_split
-  float* slab;                 // diagnostics (probe bit 5): [blocks][8] stamps
 };
+
+// XCD-aware bijective block order: the dispatcher deals block ids round-robin to the 8 XCDs, so consecutive tiles go to consecutive
+// blocks of ONE XCD (neighbouring pixel tiles share halo rows in its L2)
+__device__ __forceinline__ int xcd_tile_order() {
+  const int nwg = gridDim.x, bid = blockIdx.x;
+  const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
+  return (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
+}
+
+// two-pass split-K (g.splitk = S > 1): the grid is S x tiles, slice-major; slice sl multiplies the channel groups [sl, sl + 1) Cin / S of every
+// tap and writes bare partial sums to its slab slice (ConvK::raw, set up by the host); k_splitk_reduce finishes the layer.  Returns the
+// block's slice and turns `wg` into its tile.
+__device__ __forceinline__ int split_k_slice(const ConvG& g, int& wg) {
+  int sl = 0;
+  if (g.splitk > 1) { const int tiles = (int)gridDim.x / g.splitk; sl = wg / tiles; wg -= sl * tiles; }
+  return sl;
+}
+
+// ---- the loader role of every LDS-DMA tile kernel (waves 4-7 of the block) ------------------------------------------------------
+// Per K-step a loader wave stages 8 rows of each of the NAI = ceil(BM / 32) 32-row pixel pieces and of the NBI 32-row filter pieces:
+// stage buffer = [32 NAI pixel rows | 32 NBI filter rows] x 128 bytes, one `buffer_load_dwordx4 ... lds` per piece (pixel pieces first),
+// source-side swizzle (lane chunk ^ (row >> 1) & 7).  Pixel rows past BM or M and taps outside the image get the out-of-range offset
+// 0x80000000: the DMA writes zeros.  Dual input: K columns from k2_start on are channels of x2 at the output pixel (a 1x1 tap of another
+// tensor; rows past M keep the out-of-range bit).  x_up2: a 1x1 over a nearest-upsampled x reads pixel (oy / 2, ox / 2) of the half-size x.
+// K walk (a template choice: offered both at run time, hipcc merges the two mirror-image counters by selecting a POINTER to kh / kw / c0
+// and keeps them in scratch memory - the loaders then run a scratch round trip per K-step and every layer is 40-60 % slower):
+//  * taps outer (bf16 / fp32 operands): BK-wide column chunks of the tap-major filter in order;
+//  * channel groups outer, taps inner (pair operands; the filter keeps its tap-major layout, only the walk changes).  With taps outer a pixel's
+//    128-byte group slice is re-read by the nine taps eight K-steps apart - 8 MB of other slices per XCD in between, more than its L2
+//    holds: the 3x3 layers at 80^2 fetched their input 4-6 times from beyond L2.  Every pair tile kernel walks K this way and issues the
+//    three products in one order, so an output's bits do not depend on which of them ran it.  `c0` = first channel (split-K slice).
+// STAGES - 1 tiles in flight; per K-step: wait for tile ks (counted vmcnt, PPT = NAI + NBI DMAs per tile) | barrier | issue tile ks + STAGES - 1.
+template <int ES, int STAGES, int BM, int NBI, bool GROUPS_OUTER>
+__device__ __forceinline__ void tile_loader(const ConvG& g, char* smem, int w4, int lane, int m0, int n0, int nk, int c0) {
+  const ConvK& a = g.k;
+  constexpr int NAI = (BM + 31) / 32, AROWS = 32 * NAI, PPT = NAI + NBI;
+  constexpr int BK = 128 / ES;                    // elements per 128-byte row
+  constexpr int STAGE = (AROWS + 32 * NBI) * 128;
+  constexpr int AHEAD = STAGES - 1;
+  static_assert(STAGES >= 2 && STAGES <= 4, "counted waits below assume 1..3 tiles ahead");
+  static_assert(NAI <= 8, "a2_off");
+  const int lrow = w4 * 8 + (lane >> 3);
+  const int chunk = (lane & 7) ^ ((w4 * 4 + (lane >> 4)) & 7);
+  int a_off[NAI], a_iy0[NAI], a_ix0[NAI], b_off[NBI];
+  unsigned a2_off[8];   // fixed extent: with a dependent extent hipcc (ROCm 7.2) silently drops the HOST stub of every kernel instantiation
+  PixWalk pw;
+  pix_init(a, m0 + lrow, pw);
+  const int dq32 = 32 / a.OW, dr32 = 32 - dq32 * a.OW;
+#pragma unroll
+  for (int i = 0; i < NAI; ++i) {
+    const int row = i * 32 + lrow;
+    const int m = m0 + row;
+    a2_off[i] = 0x80000000u;
+    const int b = pw.b, oy = pw.oy, ox = pw.ox, r = oy * a.OW + ox;
+    pix_step32(a, dq32, dr32, pw);
+    if (m < a.M && row < BM) {
+      a_iy0[i] = oy * a.stride - a.pad;
+      a_ix0[i] = ox * a.stride - a.pad;
+      a_off[i] = (int)(((long long)b * a.x_bstride + ((long long)a_iy0[i] * a.W + a_ix0[i]) * a.ldx) * ES) + chunk * 16;
+      if (a.x_up2) a_off[i] = (int)(((long long)b * a.x_bstride + ((long long)(oy >> 1) * (a.W >> 1) + (ox >> 1)) * a.ldx) * ES) + chunk * 16;
+      if (a.x2) a2_off[i] = (unsigned)(((long long)b * a.x2_bstride + (long long)r * a.ldx2) * ES) + chunk * 16;
+    } else {
+      a_iy0[i] = -(1 << 28);
+      a_ix0[i] = -(1 << 28);
+      a_off[i] = 0;
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NBI; ++i) b_off[i] = (n0 + i * 32 + lrow) * a.Kpad * ES + chunk * 16;
+  const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, g.x_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rx2 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x2 ? a.x2 : a.x), 0, a.x2 ? g.x2_bytes : 0u, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, g.w_bytes, 0x00020000);
+  const int nk_main = a.x2 ? a.k2_start / BK : nk;   // (channel groups outer) K-steps before the x2 columns
+  int ksi = 0, k0 = 0, kh = 0, kw = 0;
+  auto issue = [&](int buf) __attribute__((always_inline)) {      // (called twice: left to the inliner's budget, its captures live in scratch)
+    char* sa = smem + buf * STAGE + w4 * 1024;
+    int kf;                                                   // filter column of this K-step (elements)
+    bool second;
+    if constexpr (GROUPS_OUTER) {
+      second = ksi >= nk_main;
+      kf = second ? a.k2_start + (ksi - nk_main) * BK : (kh * a.KW + kw) * a.Cin + c0;
+    } else {
+      second = a.x2 && k0 >= a.k2_start;
+      kf = k0;
+    }
+    if (second) {
+      const unsigned d2 = (unsigned)((kf - a.k2_start) * ES);
+#pragma unroll
+      for (int i = 0; i < NAI; ++i)
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx2, (lds_ptr_t)(sa + i * 4096), 16, a2_off[i] + ((a2_off[i] >> 31) ? 0u : d2), 0, 0, 0);
+    } else {
+      const int delta = ((kh * a.W + kw) * (int)a.ldx + c0) * ES;
+#pragma unroll
+      for (int i = 0; i < NAI; ++i) {
+        const int iy = a_iy0[i] + kh, ix = a_ix0[i] + kw;
+        const bool ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
+        const unsigned vo = ok ? (unsigned)(a_off[i] + delta) : 0x80000000u;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(sa + i * 4096), 16, vo, 0, 0, 0);
+      }
+    }
+#pragma unroll
+    for (int i = 0; i < NBI; ++i)
+      __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(sa + AROWS * 128 + i * 4096), 16, (unsigned)(b_off[i] + kf * ES), 0, 0, 0);
+    if constexpr (GROUPS_OUTER) {
+      ++ksi;
+      if (++kw == a.KW) {
+        kw = 0;
+        if (++kh == a.KH) { kh = 0; c0 += BK; }
+      }
+    } else {
+      k0 += BK;
+      c0 += BK;
+      if (c0 >= a.Cin) {
+        c0 = 0;
+        if (++kw == a.KW) { kw = 0; ++kh; }
+      }
+    }
+  };
+  for (int t = 0; t < AHEAD && t < nk; ++t) issue(t);
+  for (int ks = 0; ks < nk; ++ks) {
+    const int younger = nk - 1 - ks;
+    if (STAGES == 4 && younger >= 2) wait_vmcnt<2 * PPT>();
+    else if (STAGES >= 3 && younger >= 1) wait_vmcnt<PPT>();
+    else wait_vmcnt<0>();
+    __builtin_amdgcn_s_barrier();
+    if (ks + AHEAD < nk) issue((ks + AHEAD) % STAGES);
+  }
+}
 
 __device__ __forceinline__ bool g_reg_epilogue_ok(const ConvK& a) { return a.res_mode == RES_NONE && !a.y_f32 && a.reg_epi; }
 
@@ -539,6 +664,40 @@ __device__ __forceinline__ void ws_copy_out_sp(const ConvK& a, const float* st, 
   }
 }
 
+// Epilogue of the pair tile kernels (BM x BN tile, after the K loop and a block barrier; smem becomes the staging tile).
+// `for_each_group(f)` calls f(cl, pl, acc) on an MFMA wave for each of its accumulator groups = 4 consecutive channels (cl..cl+3 inside
+// the tile) of one pixel (row pl of the tile).  F16X2 output without a residual: bias + activation + hi/lo split on the accumulators, the
+// tile's F16X2 rows through LDS, plain copy-out.  Otherwise fp32 staging, then ws_copy_out_sp (`yoff`: the split-K slice's offset).
+template <int BN, int BM, typename G>
+__device__ __forceinline__ void pair_epilogue(const ConvK& a, char* smem, bool loader, int tid, int m0, int n0, long long yoff, G&& for_each_group) {
+  constexpr int CH8 = BN / 8, RSTEP = 512 / CH8, CITERS = (BM + RSTEP - 1) / RSTEP;
+  constexpr int SLD = BN + 4, SLB = 2 * BN + 8;
+  if (a.y_split && a.res_mode == RES_NONE) {
+    sp16* sb = (sp16*)smem;
+    if (!loader) {
+      dispatch_act(a.act, [&](auto actc) {
+        constexpr int ACT = decltype(actc)::value;
+        for_each_group([&](int cl, int pl, const f32x4& v) {
+          const f32x4 bv = *(const f32x4*)(a.bias + n0 + cl);
+          sp16x4 oh, ol;
+#pragma unroll
+          for (int e = 0; e < 4; ++e) { sp16 hi, lo; split2(act_c<ACT>(v[e] + bv[e]), hi, lo); oh[e] = hi; ol[e] = lo; }
+          sp16* d = sb + pl * SLB + ((cl >> 5) << 6) + (cl & 31);
+          *(sp16x4*)d = oh;
+          *(sp16x4*)(d + SPLIT_GROUP) = ol;
+        });
+      });
+    }
+    __syncthreads();
+    ws_copy_out_split_rows<BN, BM>(a, sb, SLB, tid, m0, n0);
+    return;
+  }
+  float* st = (float*)smem;
+  if (!loader) for_each_group([&](int cl, int pl, const f32x4& v) { *(f32x4*)(&st[pl * SLD + cl]) = v; });
+  __syncthreads();
+  dispatch_act(a.act, [&](auto actc) { ws_copy_out_sp<CITERS, decltype(actc)::value, BN, BM>(a, st, SLD, tid, m0, n0, yoff); });
+}
+
 // ------------------------------------------------------------------------------------------------
 // Wave-specialised LDS-DMA kernel (bf16 / fp32 operands).  8 waves per block with fixed roles: waves 0-3 only read fragments and
 // issue MFMAs (one per SIMD, 64x64 outputs each), waves 4-7 only compute im2col offsets and issue the `buffer_load ... lds` DMA,
@@ -557,15 +716,12 @@ __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_ws_kern
   static_assert(BN == 128 || BN == 64, "tile widths");
   constexpr int TJ = BN == 128 ? 2 : 1;          // pixel tiles (32 rows) per MFMA wave; channel tiles per wave: always 2
   constexpr int NBI = BN / 32;                    // 32-row filter pieces per loader wave and K-step
-  constexpr int PPT = 4 + NBI;                    // LDS-DMA pieces per loader wave and K-step (counted waits)
   constexpr int CH8 = BN / 8, RSTEP = 512 / CH8, CITERS = BM / RSTEP;   // copy-out: 16-byte chunks per row, rows per pass, passes
   constexpr int ES = (int)sizeof(T);
   constexpr int BK = 128 / ES;
   constexpr int STAGE = (BM + BN) * 128;
   constexpr int SLD = BN + 4;
   constexpr int SMEM = (STAGES * STAGE > BM * SLD * 4) ? STAGES * STAGE : BM * SLD * 4;
-  constexpr int AHEAD = STAGES - 1;
-  static_assert(STAGES >= 2 && STAGES <= 4, "counted waits below assume 1..3 tiles ahead");
   typedef typename Mma<T>::Frag Frag;
   __shared__ __attribute__((aligned(16))) char smem[SMEM + 256];   // + the prefetch dummy
 
@@ -575,21 +731,10 @@ __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_ws_kern
   const bool loader = wv >= 4;
   const int w4 = wv & 3;
   const int wm = BN == 128 ? (w4 & 1) : w4, wn = BN == 128 ? (w4 >> 1) : 0;
-  int wg;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int wg = xcd_tile_order();
   const int nt = wg % a.ntn, mt = wg / a.ntn;
   const int m0 = mt * BM, n0 = nt * BN;
   const int nk = a.Kpad / BK;
-
-  // diagnostic (glds_drop bit 5): block-level stamps [block][0..7] (shader clocks from kernel entry; [6],[7] = 100 MHz wall clock
-  // at entry / exit): first tile landed, K loop done, staged, stores issued, stores complete
-  long long* stamps = ((g.probe & 32) && g.slab && blockIdx.x < 4096 && lane == 0) ? (long long*)g.slab + (size_t)blockIdx.x * 8 : nullptr;
-  const long long t_base = stamps ? (long long)__builtin_amdgcn_s_memtime() : 0;
-  if (stamps && wv == 0) stamps[6] = (long long)__builtin_amdgcn_s_memrealtime();
 
   f32x16 acc[2][TJ];
 #pragma unroll
@@ -620,84 +765,7 @@ __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_ws_kern
   if (!loader) prefetch_share(a, blockIdx.x, gridDim.x, tid, 256, smem + SMEM);   // next layer's filter; the MFMA waves idle until tile 0 lands
 
   if (loader) {
-    // ---- loader role -------------------------------------------------------------------------------
-    const int lrow = w4 * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((w4 * 4 + (lane >> 4)) & 7);
-    int a_off[4], a_iy0[4], a_ix0[4], b_off[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = m0 + i * 32 + lrow;
-      if (m < a.M) {
-        const int b = m / a.OHW;
-        const int r = m - b * a.OHW;
-        const int oy = r / a.OW;
-        const int ox = r - oy * a.OW;
-        a_iy0[i] = oy * a.stride - a.pad;
-        a_ix0[i] = ox * a.stride - a.pad;
-        a_off[i] = (int)(((long long)b * a.x_bstride + ((long long)a_iy0[i] * a.W + a_ix0[i]) * a.ldx) * ES) + chunk * 16;
-        if (a.x_up2)   // 1x1 over a nearest-upsampled x: the source pixel of (oy, ox) is (oy / 2, ox / 2) of the half-size tensor
-          a_off[i] = (int)(((long long)b * a.x_bstride + ((long long)(oy >> 1) * (a.W >> 1) + (ox >> 1)) * a.ldx) * ES) + chunk * 16;
-      } else {
-        a_iy0[i] = -(1 << 28);
-        a_ix0[i] = -(1 << 28);
-        a_off[i] = 0;
-      }
-      b_off[i] = (n0 + i * 32 + lrow) * a.Kpad * ES + chunk * 16;
-    }
-    // dual input: K elements from k2_start on are channels of x2 at the OUTPUT pixel (a 1x1 tap of another tensor)
-    int a2_off[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = m0 + i * 32 + lrow;
-      a2_off[i] = (int)0x80000000;
-      if (a.x2 && m < a.M) {
-        const int b = m / a.OHW;
-        const int r = m - b * a.OHW;
-        a2_off[i] = (int)(((long long)b * a.x2_bstride + (long long)r * a.ldx2) * ES) + chunk * 16;
-      }
-    }
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, g.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx2 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x2 ? a.x2 : a.x), 0, a.x2 ? g.x2_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, g.w_bytes, 0x00020000);
-    int k0 = 0, kh = 0, kw = 0, c0 = 0;
-    auto issue = [&](int buf) {
-      if (g.probe & 4) return;
-      char* sa = smem + buf * STAGE + w4 * 1024;
-      if (a.x2 && k0 >= a.k2_start) {
-        const int d2 = (k0 - a.k2_start) * ES;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)                                 // rows past M keep the out-of-range bit: zeros
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx2, (lds_ptr_t)(sa + i * 4096), 16, (unsigned)a2_off[i] + (a2_off[i] < 0 ? 0u : (unsigned)d2), 0, 0, 0);
-      } else {
-        const int delta = ((kh * a.W + kw) * (int)a.ldx + c0) * ES;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int iy = a_iy0[i] + kh, ix = a_ix0[i] + kw;
-          const bool ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-          const unsigned vo = ok ? (unsigned)(a_off[i] + delta) : 0x80000000u;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(sa + i * 4096), 16, vo, 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < NBI; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(sa + BM * 128 + i * 4096), 16, (unsigned)(b_off[i] + k0 * ES), 0, 0, 0);
-      k0 += BK;
-      c0 += BK;
-      if (c0 >= a.Cin) {
-        c0 = 0;
-        if (++kw == a.KW) { kw = 0; ++kh; }
-      }
-    };
-    for (int t = 0; t < AHEAD && t < nk; ++t) issue(t);
-    for (int ks = 0; ks < nk; ++ks) {
-      const int younger = nk - 1 - ks;
-      if (STAGES == 4 && younger >= 2) wait_vmcnt<2 * PPT>();
-      else if (STAGES >= 3 && younger >= 1) wait_vmcnt<PPT>();
-      else wait_vmcnt<0>();
-      if (stamps && wv == 4 && ks == 0) stamps[0] = (long long)__builtin_amdgcn_s_memtime() - t_base;
-      __builtin_amdgcn_s_barrier();
-      if (ks + AHEAD < nk) issue((ks + AHEAD) % STAGES);
-    }
+    tile_loader<ES, STAGES, BM, NBI, false>(g, smem, w4, lane, m0, n0, nk, 0);
   } else {
     // ---- MFMA role ---------------------------------------------------------------------------------
     int foff[4];
@@ -727,7 +795,6 @@ __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_ws_kern
       }
     }
   }
-  if (stamps && wv == 0) stamps[1] = (long long)__builtin_amdgcn_s_memtime() - t_base;
   __syncthreads();                                 // every MFMA operand read is done: smem becomes the fp32 staging tile
 
   if (g_reg_epilogue_ok(a)) {
@@ -775,24 +842,17 @@ __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_ws_kern
     }
   }
   __syncthreads();
-  if (stamps && wv == 0) stamps[2] = (long long)__builtin_amdgcn_s_memtime() - t_base;
   dispatch_act(a.act, [&](auto actc) { ws_copy_out<CITERS, decltype(actc)::value, BN>(a, st, SLD, tid, m0, n0, rpre); });
-  if (stamps && wv == 0) {
-    stamps[3] = (long long)__builtin_amdgcn_s_memtime() - t_base;
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    stamps[4] = (long long)__builtin_amdgcn_s_memtime() - t_base;
-    stamps[7] = (long long)__builtin_amdgcn_s_memrealtime();
-  }
 }
 
 
 // ------------------------------------------------------------------------------------------------
 // The wave-specialised kernel for PAIR operands (F16X2 tensors: the f16x3 engine's convolution).  The loader role, the LDS image
-// (128-byte rows = one [32 hi | 32 lo] channel group, source-side XOR swizzle) and the barrier protocol are conv_igemm_ws_kernel's: to
-// the loader a pair tensor is a 16-bit tensor of twice the channels.  The MFMA waves run hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16
+// (128-byte rows = one [32 hi | 32 lo] channel group, source-side XOR swizzle) and the barrier protocol are tile_loader's: to the loader
+// a pair tensor is a 16-bit tensor of twice the channels, walked channel groups outer.  The MFMA waves run hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16
 // (one 32-deep step per K-step: lane l reads row l & 15, 16-byte chunk l >> 4 of the hi half, chunk 4 + (l >> 4) of the lo half -
 // conflict-free under the same swizzle); the dropped lo*lo term is 2^-22 relative.  Microbenchmarks with the DMA switched off
-// (tools/conv_bench.py --opt glds_drop --vals 0,4) show the MFMA-wave side, not the data movement, bounds this kernel (3x3 256 -> 256 at
+// (EXPERIMENTS.md "Timing probes") show the MFMA-wave side, not the data movement, bounds this kernel (3x3 256 -> 256 at
 // 80^2: 133 us with, 113 us without any DMA), and on random data the chip's clock under MFMA load; the 16x16x32 shape holds a higher
 // clock than 32x32x16 for the same flops (measured +3.6 % end to end in round 2; MI355X_MICROARCH.md, DVFS give-back item 7).
 template <int STAGES, int BN>
@@ -801,15 +861,10 @@ __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_wsx_ker
   constexpr int BM = 128;
   static_assert(BN == 128 || BN == 64, "tile widths");
   constexpr int TJ = BN == 128 ? 2 : 1;          // 32-pixel tiles per MFMA wave; 64 channels per wave
-  constexpr int NBI = BN / 32;
-  constexpr int PPT = 4 + NBI;
-  constexpr int CH8 = BN / 8, RSTEP = 512 / CH8, CITERS = BM / RSTEP;
   constexpr int BK = 64;                          // sp16 elements per K-step = 32 channels x (hi, lo)
   constexpr int STAGE = (BM + BN) * 128;
   constexpr int SLD = BN + 4;
   constexpr int SMEM = (STAGES * STAGE > BM * SLD * 4) ? STAGES * STAGE : BM * SLD * 4;
-  constexpr int AHEAD = STAGES - 1;
-  static_assert(STAGES >= 2 && STAGES <= 4, "counted waits below assume 1..3 tiles ahead");
   __shared__ __attribute__((aligned(16))) char smem[SMEM + 256];
 
   const int tid = threadIdx.x;
@@ -818,16 +873,8 @@ __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_wsx_ker
   const bool loader = wv >= 4;
   const int w4 = wv & 3;
   const int wm = BN == 128 ? (w4 & 1) : w4, wn = BN == 128 ? (w4 >> 1) : 0;
-  int wg;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  // two-pass split-K (g.splitk = S > 1): the grid is S x tiles, slice-major; slice sl multiplies the channel groups [sl, sl + 1) Cin / S of every
-  // tap and writes bare partial sums to its slab slice (ConvK::raw, set up by the host); k_splitk_reduce finishes the layer
-  int sl = 0;
-  if (g.splitk > 1) { const int tiles = (int)gridDim.x / g.splitk; sl = wg / tiles; wg -= sl * tiles; }
+  int wg = xcd_tile_order();
+  const int sl = split_k_slice(g, wg);
   const long long yoff = (long long)sl * a.M * a.N;
   const int nt = wg % a.ntn, mt = wg / a.ntn;
   const int m0 = mt * BM, n0 = nt * BN;
@@ -842,81 +889,7 @@ __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_wsx_ker
   if (!loader) prefetch_share(a, blockIdx.x, gridDim.x, tid, 256, smem + SMEM);
 
   if (loader) {
-    // ---- loader role (conv_igemm_ws_kernel's) ---------------------------------------------------------
-    const int lrow = w4 * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((w4 * 4 + (lane >> 4)) & 7);
-    int a_off[4], a_iy0[4], a_ix0[4], b_off[4], a2_off[4];
-    PixWalk pw;
-    pix_init(a, m0 + lrow, pw);
-    const int dq32 = 32 / a.OW, dr32 = 32 - dq32 * a.OW;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-      const int m = m0 + i * 32 + lrow;
-      a2_off[i] = (int)0x80000000;
-      const int b = pw.b, oy = pw.oy, ox = pw.ox, r = oy * a.OW + ox;
-      pix_step32(a, dq32, dr32, pw);
-      if (m < a.M) {
-        a_iy0[i] = oy * a.stride - a.pad;
-        a_ix0[i] = ox * a.stride - a.pad;
-        a_off[i] = (int)(((long long)b * a.x_bstride + ((long long)a_iy0[i] * a.W + a_ix0[i]) * a.ldx) * 2) + chunk * 16;
-        if (a.x_up2) a_off[i] = (int)(((long long)b * a.x_bstride + ((long long)(oy >> 1) * (a.W >> 1) + (ox >> 1)) * a.ldx) * 2) + chunk * 16;
-        if (a.x2) a2_off[i] = (int)(((long long)b * a.x2_bstride + (long long)r * a.ldx2) * 2) + chunk * 16;
-      } else {
-        a_iy0[i] = -(1 << 28);
-        a_ix0[i] = -(1 << 28);
-        a_off[i] = 0;
-      }
-      b_off[i] = (n0 + i * 32 + lrow) * a.Kpad * 2 + chunk * 16;
-    }
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, g.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx2 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x2 ? a.x2 : a.x), 0, a.x2 ? g.x2_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, g.w_bytes, 0x00020000);
-    // K order: channel group outer, taps inner (the filter keeps its tap-major layout, only the walk changes).  With taps outer a pixel's 128-byte
-    // group slice is re-read by the nine taps eight K-steps apart - 8 MB of other slices per XCD in between, more than its L2 holds: the 3x3 layers
-    // at 80^2 fetched their input 4-6 times from beyond L2.  Every F16X2 tile kernel walks K the same way (one summation order per output).
-    // (one walk only: offered both at run time, hipcc merges the two mirror-image counters by selecting a POINTER to kh / kw / c0 and
-    // keeps them in scratch memory - the loaders then run a scratch round trip per K-step and every layer is 40-60 % slower)
-    const int nk_main = a.x2 ? a.k2_start / BK : nk;
-    int ksi = 0, kh = 0, kw = 0, c0 = sl * (a.Cin / g.splitk);
-    auto issue = [&](int buf) __attribute__((always_inline)) {      // (called twice: left to the inliner's budget, its captures live in scratch)
-      if (g.probe & 4) return;
-      char* sa = smem + buf * STAGE + w4 * 1024;
-      int kf;                                                   // filter column of this K-step (sp16 elements)
-      if (ksi >= nk_main) {
-        const int d2 = (ksi - nk_main) * BK * 2;
-        kf = a.k2_start + (ksi - nk_main) * BK;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx2, (lds_ptr_t)(sa + i * 4096), 16, (unsigned)a2_off[i] + (a2_off[i] < 0 ? 0u : (unsigned)d2), 0, 0, 0);
-      } else {
-        const int delta = ((kh * a.W + kw) * (int)a.ldx + c0) * 2;
-        kf = (kh * a.KW + kw) * a.Cin + c0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          const int iy = a_iy0[i] + kh, ix = a_ix0[i] + kw;
-          const bool ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-          const unsigned vo = ok ? (unsigned)(a_off[i] + delta) : 0x80000000u;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(sa + i * 4096), 16, vo, 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < NBI; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(sa + BM * 128 + i * 4096), 16, (unsigned)(b_off[i] + kf * 2), 0, 0, 0);
-      ++ksi;
-      if (++kw == a.KW) {
-        kw = 0;
-        if (++kh == a.KH) { kh = 0; c0 += BK; }
-      }
-    };
-    for (int t = 0; t < AHEAD && t < nk; ++t) issue(t);
-    for (int ks = 0; ks < nk; ++ks) {
-      const int younger = nk - 1 - ks;
-      if (STAGES == 4 && younger >= 2) wait_vmcnt<2 * PPT>();
-      else if (STAGES >= 3 && younger >= 1) wait_vmcnt<PPT>();
-      else wait_vmcnt<0>();
-      __builtin_amdgcn_s_barrier();
-      if (ks + AHEAD < nk) issue((ks + AHEAD) % STAGES);
-    }
+    tile_loader<2, STAGES, BM, BN / 32, true>(g, smem, w4, lane, m0, n0, nk, sl * (a.Cin / g.splitk));
   } else {
     // ---- MFMA role, 16x16x32: one 32-deep step per K-step.  The wave's 8 filter fragments stay live; pixel fragments come tile by tile ----
     const int r16 = lane & 15, c4 = lane >> 4;
@@ -942,41 +915,13 @@ __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_wsx_ker
     }
   }
   __syncthreads();                                 // every MFMA operand read is done: smem becomes the staging tile
-
-  // every accumulator group = 4 consecutive channels (cl..cl+3 inside the tile) of one pixel (row pl of the tile)
-  auto for_each_group = [&](auto&& f) {
+  pair_epilogue<BN, BM>(a, smem, loader, tid, m0, n0, yoff, [&](auto&& f) {
     const int r16 = lane & 15, c4 = lane >> 4;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
 #pragma unroll
       for (int j = 0; j < 2 * TJ; ++j) f(wn * 64 + 16 * i + 4 * c4, wm * (32 * TJ) + 16 * j + r16, acc16[i][j]);
-  };
-  if (a.y_split && a.res_mode == RES_NONE) {
-    // bias + activation + hi/lo split on the accumulators, the tile's F16X2 rows through LDS, plain copy-out
-    constexpr int SLB = 2 * BN + 8;
-    sp16* sb = (sp16*)smem;
-    if (!loader) {
-      dispatch_act(a.act, [&](auto actc) {
-        constexpr int ACT = decltype(actc)::value;
-        for_each_group([&](int cl, int pl, const f32x4& v) {
-          const f32x4 bv = *(const f32x4*)(a.bias + n0 + cl);
-          sp16x4 oh, ol;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { sp16 hi, lo; split2(act_c<ACT>(v[e] + bv[e]), hi, lo); oh[e] = hi; ol[e] = lo; }
-          sp16* d = sb + pl * SLB + ((cl >> 5) << 6) + (cl & 31);
-          *(sp16x4*)d = oh;
-          *(sp16x4*)(d + SPLIT_GROUP) = ol;
-        });
-      });
-    }
-    __syncthreads();
-    ws_copy_out_split_rows<BN>(a, sb, SLB, tid, m0, n0);
-    return;
-  }
-  float* st = (float*)smem;
-  if (!loader) for_each_group([&](int cl, int pl, const f32x4& v) { *(f32x4*)(&st[pl * SLD + cl]) = v; });
-  __syncthreads();
-  dispatch_act(a.act, [&](auto actc) { ws_copy_out_sp<CITERS, decltype(actc)::value, BN>(a, st, SLD, tid, m0, n0, yoff); });
+  });
 }
 
 
@@ -987,23 +932,19 @@ __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_wsx_ker
 // tile height so that the grid is close to a whole number of rounds of the chip (launch_conv_split), e.g. 208 x 128 for 80^2 x 256
 // channels: 494 blocks = 2 rounds of one block per CU, 96 % full.
 // Wave layout 1 x 4: every MFMA wave owns ALL MT pixel tiles and BN / 4 channels (any MT balances), v_mfma_f32_16x16x32_f16, its
-// 2 (BN = 128) or 1 (BN = 64) filter fragment pairs live for the K-step, pixel fragments tile by tile.  Loader role, LDS image, swizzle and
+// 2 (BN = 128) or 1 (BN = 64) filter fragment pairs live for the K-step, pixel fragments tile by tile.  Loader role (tile_loader), LDS image and
 // barrier protocol as conv_igemm_wsx_kernel; the A part of a stage holds AROWS = MT x 16 rounded up to 32 rows.
 template <int STAGES, int BN, int MT>
 __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_wsf_kernel(const ConvG g) {
   const ConvK& a = g.k;
   constexpr int BM = MT * 16;
   constexpr int AROWS = (BM + 31) / 32 * 32;
-  constexpr int NAI = AROWS / 32, NBI = BN / 32;
-  constexpr int PPT = NAI + NBI;
   constexpr int CT = BN / 64;                     // 16-channel tiles per MFMA wave
-  constexpr int CH8 = BN / 8, RSTEP = 512 / CH8, CITERS = (BM + RSTEP - 1) / RSTEP;
   constexpr int BK = 64;
   constexpr int STAGE = (AROWS + BN) * 128;
   constexpr int SLD = BN + 4, SLB = 2 * BN + 8;
   constexpr int EPI = (BM * SLD * 4 > BM * SLB * 2) ? BM * SLD * 4 : BM * SLB * 2;
   constexpr int SMEM = (STAGES * STAGE > EPI) ? STAGES * STAGE : EPI;
-  constexpr int AHEAD = STAGES - 1;
   static_assert(STAGES >= 2 && STAGES <= 4 && MT >= 1 && MT <= 14 && (BN == 64 || BN == 128), "tile shape");
   static_assert(SMEM + 256 <= 160 * 1024, "LDS");
   __shared__ __attribute__((aligned(16))) char smem[SMEM + 256];
@@ -1013,16 +954,8 @@ __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_wsf_ker
   const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
   const bool loader = wv >= 4;
   const int w4 = wv & 3;
-  int wg;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
-  // two-pass split-K (g.splitk = S > 1): the grid is S x tiles, slice-major; slice sl multiplies the channel groups [sl, sl + 1) Cin / S of every
-  // tap and writes bare partial sums to its slab slice (ConvK::raw, set up by the host); k_splitk_reduce finishes the layer
-  int sl = 0;
-  if (g.splitk > 1) { const int tiles = (int)gridDim.x / g.splitk; sl = wg / tiles; wg -= sl * tiles; }
+  int wg = xcd_tile_order();
+  const int sl = split_k_slice(g, wg);
   const long long yoff = (long long)sl * a.M * a.N;
   const int nt = wg % a.ntn, mt = wg / a.ntn;
   const int m0 = mt * BM, n0 = nt * BN;
@@ -1036,84 +969,7 @@ __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_wsf_ker
   if (!loader) prefetch_share(a, blockIdx.x, gridDim.x, tid, 256, smem + SMEM);
 
   if (loader) {
-    const int lrow = w4 * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((w4 * 4 + (lane >> 4)) & 7);
-    int a_off[NAI], a_iy0[NAI], a_ix0[NAI], b_off[NBI];
-    unsigned a2_off[8];   // fixed extent (NAI <= 7): with a dependent extent hipcc (ROCm 7.2) silently drops the HOST stub of every instantiation
-    static_assert(NAI <= 8, "a2_off");
-    PixWalk pw;
-    pix_init(a, m0 + lrow, pw);
-    const int dq32 = 32 / a.OW, dr32 = 32 - dq32 * a.OW;
-#pragma unroll
-    for (int i = 0; i < NAI; ++i) {
-      const int row = i * 32 + lrow;
-      const int m = m0 + row;
-      a2_off[i] = 0x80000000u;
-      const int b = pw.b, oy = pw.oy, ox = pw.ox, r = oy * a.OW + ox;
-      pix_step32(a, dq32, dr32, pw);
-      if (m < a.M && row < BM) {
-        a_iy0[i] = oy * a.stride - a.pad;
-        a_ix0[i] = ox * a.stride - a.pad;
-        a_off[i] = (int)(((long long)b * a.x_bstride + ((long long)a_iy0[i] * a.W + a_ix0[i]) * a.ldx) * 2) + chunk * 16;
-        if (a.x_up2) a_off[i] = (int)(((long long)b * a.x_bstride + ((long long)(oy >> 1) * (a.W >> 1) + (ox >> 1)) * a.ldx) * 2) + chunk * 16;
-        if (a.x2) a2_off[i] = (unsigned)(((long long)b * a.x2_bstride + (long long)r * a.ldx2) * 2) + chunk * 16;
-      } else {
-        a_iy0[i] = -(1 << 28);
-        a_ix0[i] = -(1 << 28);
-        a_off[i] = 0;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NBI; ++i) b_off[i] = (n0 + i * 32 + lrow) * a.Kpad * 2 + chunk * 16;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, g.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx2 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x2 ? a.x2 : a.x), 0, a.x2 ? g.x2_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, g.w_bytes, 0x00020000);
-    // K order: channel group outer, taps inner (the filter keeps its tap-major layout, only the walk changes).  With taps outer a pixel's 128-byte
-    // group slice is re-read by the nine taps eight K-steps apart - 8 MB of other slices per XCD in between, more than its L2 holds: the 3x3 layers
-    // at 80^2 fetched their input 4-6 times from beyond L2.  Every F16X2 tile kernel walks K the same way (one summation order per output).
-    // (one walk only: offered both at run time, hipcc merges the two mirror-image counters by selecting a POINTER to kh / kw / c0 and
-    // keeps them in scratch memory - the loaders then run a scratch round trip per K-step and every layer is 40-60 % slower)
-    const int nk_main = a.x2 ? a.k2_start / BK : nk;
-    int ksi = 0, kh = 0, kw = 0, c0 = sl * (a.Cin / g.splitk);
-    auto issue = [&](int buf) __attribute__((always_inline)) {      // (called twice: left to the inliner's budget, its captures live in scratch)
-      if (g.probe & 4) return;
-      char* sa = smem + buf * STAGE + w4 * 1024;
-      int kf;                                                   // filter column of this K-step (sp16 elements)
-      if (ksi >= nk_main) {
-        const int d2 = (ksi - nk_main) * BK * 2;
-        kf = a.k2_start + (ksi - nk_main) * BK;
-#pragma unroll
-        for (int i = 0; i < NAI; ++i)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx2, (lds_ptr_t)(sa + i * 4096), 16, a2_off[i] + ((a2_off[i] >> 31) ? 0u : (unsigned)d2), 0, 0, 0);
-      } else {
-        const int delta = ((kh * a.W + kw) * (int)a.ldx + c0) * 2;
-        kf = (kh * a.KW + kw) * a.Cin + c0;
-#pragma unroll
-        for (int i = 0; i < NAI; ++i) {
-          const int iy = a_iy0[i] + kh, ix = a_ix0[i] + kw;
-          const bool ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-          const unsigned vo = ok ? (unsigned)(a_off[i] + delta) : 0x80000000u;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(sa + i * 4096), 16, vo, 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < NBI; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(sa + AROWS * 128 + i * 4096), 16, (unsigned)(b_off[i] + kf * 2), 0, 0, 0);
-      ++ksi;
-      if (++kw == a.KW) {
-        kw = 0;
-        if (++kh == a.KH) { kh = 0; c0 += BK; }
-      }
-    };
-    for (int t = 0; t < AHEAD && t < nk; ++t) issue(t);
-    for (int ks = 0; ks < nk; ++ks) {
-      const int younger = nk - 1 - ks;
-      if (STAGES == 4 && younger >= 2) wait_vmcnt<2 * PPT>();
-      else if (STAGES >= 3 && younger >= 1) wait_vmcnt<PPT>();
-      else wait_vmcnt<0>();
-      __builtin_amdgcn_s_barrier();
-      if (ks + AHEAD < nk) issue((ks + AHEAD) % STAGES);
-    }
+    tile_loader<2, STAGES, BM, BN / 32, true>(g, smem, w4, lane, m0, n0, nk, sl * (a.Cin / g.splitk));
   } else {
     const int r16 = lane & 15, c4 = lane >> 4;
     const int sw = (r16 >> 1) & 7;
@@ -1203,38 +1059,13 @@ __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_wsf_ker
     }
   }
   __syncthreads();
-
-  auto for_each_group = [&](auto&& f) {
+  pair_epilogue<BN, BM>(a, smem, loader, tid, m0, n0, yoff, [&](auto&& f) {
     const int r16 = lane & 15, c4 = lane >> 4;
 #pragma unroll
     for (int i = 0; i < CT; ++i)
 #pragma unroll
       for (int j = 0; j < MT; ++j) f(w4 * (BN / 4) + 16 * i + 4 * c4, 16 * j + r16, acc[i][j]);
-  };
-  if (a.y_split && a.res_mode == RES_NONE) {
-    sp16* sb = (sp16*)smem;
-    if (!loader) {
-      dispatch_act(a.act, [&](auto actc) {
-        constexpr int ACT = decltype(actc)::value;
-        for_each_group([&](int cl, int pl, const f32x4& v) {
-          const f32x4 bv = *(const f32x4*)(a.bias + n0 + cl);
-          sp16x4 oh, ol;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { sp16 hi, lo; split2(act_c<ACT>(v[e] + bv[e]), hi, lo); oh[e] = hi; ol[e] = lo; }
-          sp16* d = sb + pl * SLB + ((cl >> 5) << 6) + (cl & 31);
-          *(sp16x4*)d = oh;
-          *(sp16x4*)(d + SPLIT_GROUP) = ol;
-        });
-      });
-    }
-    __syncthreads();
-    ws_copy_out_split_rows<BN, BM>(a, sb, SLB, tid, m0, n0);
-    return;
-  }
-  float* st = (float*)smem;
-  if (!loader) for_each_group([&](int cl, int pl, const f32x4& v) { *(f32x4*)(&st[pl * SLD + cl]) = v; });
-  __syncthreads();
-  dispatch_act(a.act, [&](auto actc) { ws_copy_out_sp<CITERS, decltype(actc)::value, BN, BM>(a, st, SLD, tid, m0, n0, yoff); });
+  });
 }
 
 
@@ -1246,25 +1077,21 @@ __global__ __launch_bounds__(512, (STAGES == 2 ? 4 : 2)) void conv_igemm_wsf_ker
 // fragment reads per 12 MT MFMAs (7 x 4: 22 reads per 84 MFMAs, 3.8 MFMAs per read instead of 3), one filter tile staged per 256 instead
 // of 128 pixels, 12 instead of 16 DMA instructions per loader wave and 1536 MFMA cycles, and the host picks MTA + MTB so that the grid is
 // close to whole rounds of 256 blocks (launch_conv_split: 224 x 128 for 80^2 x 8 x 256 channels = 458 blocks, 160 x 128 for 512 channels
-// = 1280 blocks = 5 rounds).  The pixel fragments of tile j + 1 are read under the MFMAs of tile j.  Loader role, LDS image, swizzle,
-// barrier protocol, K walk and the order of the three products are conv_igemm_wsx_kernel's: an output's arithmetic does not depend on which
+// = 1280 blocks = 5 rounds).  The pixel fragments of tile j + 1 are read under the MFMAs of tile j.  Loader role (tile_loader), LDS
+// image, barrier protocol, K walk and the order of the three products are conv_igemm_wsx_kernel's: an output's arithmetic does not depend on which
 // of the tile kernels ran it (bit-identical results, tested).
-template <int MTA, int MTB, bool STAMP = false>   // STAMP: the diagnostic build (tools/conv_bench.py with glds_drop = 32 and RTD_CONV_STAMPS=2), never dispatched by a plan
+template <int MTA, int MTB>
 __global__ __launch_bounds__(512, 2) void conv_igemm_wsq_kernel(const ConvG g) {
   const ConvK& a = g.k;
   constexpr int BN = 128, STAGES = 3;
   constexpr int BM = (MTA + MTB) * 16;
   constexpr int AROWS = (BM + 31) / 32 * 32;
-  constexpr int NAI = AROWS / 32, NBI = BN / 32;
-  constexpr int PPT = NAI + NBI;
   constexpr int MTX = MTA > MTB ? MTA : MTB;
-  constexpr int CH8 = BN / 8, RSTEP = 512 / CH8, CITERS = (BM + RSTEP - 1) / RSTEP;
   constexpr int BK = 64;
   constexpr int STAGE = (AROWS + BN) * 128;
   constexpr int SLD = BN + 4, SLB = 2 * BN + 8;
   constexpr int EPI = (BM * SLD * 4 > BM * SLB * 2) ? BM * SLD * 4 : BM * SLB * 2;
   constexpr int SMEM = (STAGES * STAGE > EPI) ? STAGES * STAGE : EPI;
-  constexpr int AHEAD = STAGES - 1;
   static_assert(MTA >= MTB && MTB >= 1 && MTA <= 8, "row split");
   static_assert(SMEM + 256 <= 160 * 1024, "LDS");
   __shared__ __attribute__((aligned(16))) char smem[SMEM + 256];
@@ -1275,18 +1102,10 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_wsq_kernel(const ConvG g) {
   const bool loader = wv >= 4;
   const int w4 = wv & 3;
   const int wm = w4 & 1, wn = w4 >> 1;
-  int wg;
-  {
-    const int nwg = gridDim.x, bid = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, xcd = bid & 7;
-    wg = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (bid >> 3);
-  }
+  const int wg = xcd_tile_order();
   const int nt = wg % a.ntn, mt = wg / a.ntn;
   const int m0 = mt * BM, n0 = nt * BN;
   const int nk = a.Kpad / BK;
-  long long* stamps = (STAMP && g.slab && blockIdx.x < 4096 && lane == 0) ? (long long*)g.slab + (size_t)blockIdx.x * 8 : nullptr;
-  const long long t_base = STAMP ? (long long)__builtin_amdgcn_s_memtime() : 0;
-  if (STAMP && stamps && wv == 0) stamps[6] = (long long)__builtin_amdgcn_s_memrealtime();
 
   f32x4 acc[4][MTX];
 #pragma unroll
@@ -1296,78 +1115,7 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_wsq_kernel(const ConvG g) {
   if (!loader) prefetch_share(a, blockIdx.x, gridDim.x, tid, 256, smem + SMEM);
 
   if (loader) {
-    const int lrow = w4 * 8 + (lane >> 3);
-    const int chunk = (lane & 7) ^ ((w4 * 4 + (lane >> 4)) & 7);
-    int a_off[NAI], a_iy0[NAI], a_ix0[NAI], b_off[NBI];
-    unsigned a2_off[8];   // fixed extent (see conv_igemm_wsf_kernel)
-    static_assert(NAI <= 8, "a2_off");
-    PixWalk pw;
-    pix_init(a, m0 + lrow, pw);
-    const int dq32 = 32 / a.OW, dr32 = 32 - dq32 * a.OW;
-#pragma unroll
-    for (int i = 0; i < NAI; ++i) {
-      const int row = i * 32 + lrow;
-      const int m = m0 + row;
-      a2_off[i] = 0x80000000u;
-      const int b = pw.b, oy = pw.oy, ox = pw.ox, r = oy * a.OW + ox;
-      pix_step32(a, dq32, dr32, pw);
-      if (m < a.M && row < BM) {
-        a_iy0[i] = oy * a.stride - a.pad;
-        a_ix0[i] = ox * a.stride - a.pad;
-        a_off[i] = (int)(((long long)b * a.x_bstride + ((long long)a_iy0[i] * a.W + a_ix0[i]) * a.ldx) * 2) + chunk * 16;
-        if (a.x_up2) a_off[i] = (int)(((long long)b * a.x_bstride + ((long long)(oy >> 1) * (a.W >> 1) + (ox >> 1)) * a.ldx) * 2) + chunk * 16;
-        if (a.x2) a2_off[i] = (unsigned)(((long long)b * a.x2_bstride + (long long)r * a.ldx2) * 2) + chunk * 16;
-      } else {
-        a_iy0[i] = -(1 << 28);
-        a_ix0[i] = -(1 << 28);
-        a_off[i] = 0;
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < NBI; ++i) b_off[i] = (n0 + i * 32 + lrow) * a.Kpad * 2 + chunk * 16;
-    const __amdgpu_buffer_rsrc_t rx = __builtin_amdgcn_make_buffer_rsrc((void*)a.x, 0, g.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rx2 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x2 ? a.x2 : a.x), 0, a.x2 ? g.x2_bytes : 0u, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rw = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, g.w_bytes, 0x00020000);
-    // K order: channel group outer, taps inner (conv_igemm_wsx_kernel)
-    const int nk_main = a.x2 ? a.k2_start / BK : nk;
-    int ksi = 0, kh = 0, kw = 0, c0 = 0;
-    auto issue = [&](int buf) __attribute__((always_inline)) {
-      if (g.probe & 4) return;
-      char* sa = smem + buf * STAGE + w4 * 1024;
-      int kf;
-      if (ksi >= nk_main) {
-        const int d2 = (ksi - nk_main) * BK * 2;
-        kf = a.k2_start + (ksi - nk_main) * BK;
-#pragma unroll
-        for (int i = 0; i < NAI; ++i)
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx2, (lds_ptr_t)(sa + i * 4096), 16, a2_off[i] + ((a2_off[i] >> 31) ? 0u : (unsigned)d2), 0, 0, 0);
-      } else {
-        const int delta = ((kh * a.W + kw) * (int)a.ldx + c0) * 2;
-        kf = (kh * a.KW + kw) * a.Cin + c0;
-#pragma unroll
-        for (int i = 0; i < NAI; ++i) {
-          const int iy = a_iy0[i] + kh, ix = a_ix0[i] + kw;
-          const bool ok = (unsigned)iy < (unsigned)a.H && (unsigned)ix < (unsigned)a.W;
-          const unsigned vo = ok ? (unsigned)(a_off[i] + delta) : 0x80000000u;
-          __builtin_amdgcn_raw_ptr_buffer_load_lds(rx, (lds_ptr_t)(sa + i * 4096), 16, vo, 0, 0, 0);
-        }
-      }
-#pragma unroll
-      for (int i = 0; i < NBI; ++i)
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rw, (lds_ptr_t)(sa + AROWS * 128 + i * 4096), 16, (unsigned)(b_off[i] + kf * 2), 0, 0, 0);
-      ++ksi;
-      if (++kw == a.KW) {
-        kw = 0;
-        if (++kh == a.KH) { kh = 0; c0 += BK; }
-      }
-    };
-    for (int t = 0; t < AHEAD && t < nk; ++t) issue(t);
-    for (int ks = 0; ks < nk; ++ks) {
-      if (nk - 1 - ks >= 1) wait_vmcnt<PPT>();
-      else wait_vmcnt<0>();
-      __builtin_amdgcn_s_barrier();
-      if (ks + AHEAD < nk) issue((ks + AHEAD) % STAGES);
-    }
+    tile_loader<2, STAGES, BM, BN / 32, true>(g, smem, w4, lane, m0, n0, nk, 0);
   } else {
     const int r16 = lane & 15, c4 = lane >> 4;
     const int sw = (r16 >> 1) & 7;
@@ -1391,7 +1139,6 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_wsq_kernel(const ConvG g) {
       auto step = [&](auto parc, const int ks) __attribute__((always_inline)) {
         constexpr int P = decltype(parc)::value, Q = P ^ 1;
         __builtin_amdgcn_s_barrier();
-        if (STAMP && stamps && wv == 0 && ks == 0) stamps[0] = (long long)__builtin_amdgcn_s_memtime() - t_base;
         const char* sa = smem + (ks % STAGES) * STAGE + rb * 128;
         const char* sb = smem + (ks % STAGES) * STAGE + (AROWS + wn * 64) * 128;
         wh[P][0] = *(const sp16x8*)(sb + foh); xh[0] = *(const sp16x8*)(sa + foh); RTD_SB();
@@ -1440,10 +1187,8 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_wsq_kernel(const ConvG g) {
     if (wm == 0) body(ActC<MTA>{}, 0);              // (ActC: a compile-time int)
     else body(ActC<MTB>{}, MTA * 16);
   }
-  if (STAMP && stamps && wv == 0) stamps[1] = (long long)__builtin_amdgcn_s_memtime() - t_base;
   __syncthreads();
-
-  auto for_each_group = [&](auto&& f) {
+  pair_epilogue<BN, BM>(a, smem, loader, tid, m0, n0, 0, [&](auto&& f) {
     const int r16 = lane & 15, c4 = lane >> 4;
     const int rb = wm ? MTA * 16 : 0, mtw = wm ? MTB : MTA;
 #pragma unroll
@@ -1451,40 +1196,8 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_wsq_kernel(const ConvG g) {
 #pragma unroll
       for (int j = 0; j < MTX; ++j)
         if (j < mtw) f(wn * 64 + 16 * i + 4 * c4, rb + 16 * j + r16, acc[i][j]);
-  };
-  if (a.y_split && a.res_mode == RES_NONE) {
-    sp16* sb = (sp16*)smem;
-    if (!loader) {
-      dispatch_act(a.act, [&](auto actc) {
-        constexpr int ACT = decltype(actc)::value;
-        for_each_group([&](int cl, int pl, const f32x4& v) {
-          const f32x4 bv = *(const f32x4*)(a.bias + n0 + cl);
-          sp16x4 oh, ol;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) { sp16 hi, lo; split2(act_c<ACT>(v[e] + bv[e]), hi, lo); oh[e] = hi; ol[e] = lo; }
-          sp16* d = sb + pl * SLB + ((cl >> 5) << 6) + (cl & 31);
-          *(sp16x4*)d = oh;
-          *(sp16x4*)(d + SPLIT_GROUP) = ol;
-        });
-      });
-    }
-    __syncthreads();
-    if (STAMP && stamps && wv == 0) stamps[2] = (long long)__builtin_amdgcn_s_memtime() - t_base;
-    ws_copy_out_split_rows<BN, BM>(a, sb, SLB, tid, m0, n0);
-    if (STAMP && stamps && wv == 0) {
-      stamps[3] = (long long)__builtin_amdgcn_s_memtime() - t_base;
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      stamps[4] = (long long)__builtin_amdgcn_s_memtime() - t_base;
-      stamps[7] = (long long)__builtin_amdgcn_s_memrealtime();
-    }
-    return;
-  }
-  float* st = (float*)smem;
-  if (!loader) for_each_group([&](int cl, int pl, const f32x4& v) { *(f32x4*)(&st[pl * SLD + cl]) = v; });
-  __syncthreads();
-  dispatch_act(a.act, [&](auto actc) { ws_copy_out_sp<CITERS, decltype(actc)::value, BN, BM>(a, st, SLD, tid, m0, n0, 0); });
+  });
 }
-
 
 
 int conv_kpad(int K) { return (K + 63) / 64 * 64; }
@@ -1499,7 +1212,7 @@ bool conv_set_option(const char* name, int value) {
       {"ws2_min_blocks", &o.ws2_min_blocks}, {"ws64_max_blocks", &o.ws64_max_blocks}, 
       {"reg_epilogue", &o.reg_epilogue}, {"conv_reg", &o.conv_reg}, 
       {"prefetch", &o.prefetch},
-      {"glds_drop", &o.glds_drop}, {"split_ws2_min_blocks", &o.split_ws2_min_blocks}, {"split_ws64_max_blocks", &o.split_ws64_max_blocks},
+      {"split_ws2_min_blocks", &o.split_ws2_min_blocks}, {"split_ws64_max_blocks", &o.split_ws64_max_blocks},
       {"split_flex", &o.split_flex}, {"split_flex_min_nk", &o.split_flex_min_nk}, {"split_flex_small_max", &o.split_flex_small_max},
       {"split_sx", &o.split_sx}, {"split_k2", &o.split_k2}, {"split_wsq", &o.split_wsq}, {"split_wsq_min_blocks", &o.split_wsq_min_blocks},
       {"split_wsq_min_nk", &o.split_wsq_min_nk},
@@ -1512,8 +1225,7 @@ static inline const ConvOpts& opts_of(const ConvArgs& a) { return a.opts ? *a.op
 
 // LDS-DMA tile kernels on bf16 / fp32 operands; returns true when the launch was taken
 template <typename T>
-static bool dispatch_glds(const ConvOpts& o, const ConvK& k, bool ok, bool prefer256, long long x_bytes, long long w_bytes, unsigned y_bytes, unsigned x2_bytes,
-                          const ConvWorkspace& ws, hipStream_t s) {
+static bool dispatch_glds(const ConvOpts& o, const ConvK& k, bool ok, bool prefer256, long long x_bytes, long long w_bytes, unsigned x2_bytes, hipStream_t s) {
   if (!ok || (o.conv_mode == 1 && !k.x2)) return false;
   static_assert(sizeof(T) == 2 || sizeof(T) == 4, "bf16 / fp32");
   const long long mt = (k.M + 127) / 128, ntn = (k.N + 127) / 128;
@@ -1523,11 +1235,8 @@ static bool dispatch_glds(const ConvOpts& o, const ConvK& k, bool ok, bool prefe
   ConvG g;
   g.k = k;
   g.k.ntn = (int)ntn;
-  g.probe = o.glds_drop;
-  g.splitk = 1; g.slab = (o.glds_drop & 32) ? ws.slab : nullptr; g.y_bytes = 0;
-  g.x_bytes = (o.glds_drop & 1) ? 0u : (unsigned)x_bytes;
-  g.w_bytes = (o.glds_drop & 2) ? 0u : (unsigned)w_bytes;
-  g.x2_bytes = x2_bytes;
+  g.splitk = 1;
+  g.x_bytes = (unsigned)x_bytes; g.w_bytes = (unsigned)w_bytes; g.x2_bytes = x2_bytes;
   // small grids: 128 x 64 tiles double the blocks (latency profile only: with other batches in flight the idle CUs are taken anyway and
   // the narrower tile stages 1.5x the bytes per MFMA - measured +1.4 % for one handle, -1 % for three); conv_mode 10 forces it for the tests
   if ((o.conv_mode == 0 && !prefer256 && mt * ntn < o.ws64_max_blocks && k.N > 64) || o.conv_mode == 10) {
@@ -2543,8 +2252,7 @@ static void launch_conv_split(const ConvArgs& a, hipStream_t s) {
   const long long x_bytes = ((long long)(x.n - 1) * x.bstride + ((long long)x.h * x.w - 1) * x.ld + x.c) * 4;
   const long long w_bytes = (long long)a.Npad * a.Kpad * 2;
   RTD_CHECK(x_bytes < (1ll << 31) && x2_bytes < (1ll << 31) && w_bytes < (1ll << 31), 1, "conv (f16x3): operand larger than a buffer descriptor (2 GiB)");
-  g.probe = o.glds_drop & ~32; g.splitk = 1; g.slab = nullptr; g.y_bytes = 0;      // timing-only probes (rtd_debug_option "glds_drop")
-  g.x_bytes = (o.glds_drop & 1) ? 0u : (unsigned)x_bytes; g.w_bytes = (o.glds_drop & 2) ? 0u : (unsigned)w_bytes; g.x2_bytes = (unsigned)x2_bytes;
+  g.splitk = 1; g.x_bytes = (unsigned)x_bytes; g.w_bytes = (unsigned)w_bytes; g.x2_bytes = (unsigned)x2_bytes;
   // thin 1x1 expand convs on wide grids (stage-0 / stage-1 c3): the streaming kernel, with the next block's reduce conv riding on it
   if (dispatch_sx(k, a, x_bytes, x2_bytes, s)) { HIP_CHECK(hipGetLastError()); return; }
   RTD_CHECK(a.next_y.p == nullptr, 1, "conv (f16x3): a fused following conv exists in the streaming kernel only");
@@ -2649,18 +2357,9 @@ static void launch_conv_split(const ConvArgs& a, hipStream_t s) {
       const double cost = (double)((blocks + 255) / 256) * ((double)nk * cand[c][0] * 192.0 + 1500.0 + 10.0 * bm);
       if (cost < best_cost) { best_cost = cost; best = c; }
     }
-    const bool stamped = (o.glds_drop & 32) && a.ws.slab && a.ws.slab_bytes >= (size_t)4096 * 64;
-    if (stamped && best != 6) best = 4;                        // the diagnostic build exists for 7 + 7 and 8 + 8 tiles only
     const int bm = 16 * (cand[best][0] + cand[best][1]);
     k.ntn = (int)ntn;
     const dim3 grid((unsigned)(((k.M + bm - 1) / bm) * ntn)), blk(512);
-    if (stamped) {     // diagnostic build: block stamps
-      g.slab = a.ws.slab;
-      if (best == 4) rtd_launch((conv_igemm_wsq_kernel<7, 7, true>), grid, blk, 0, s, g);
-      else rtd_launch((conv_igemm_wsq_kernel<8, 8, true>), grid, blk, 0, s, g);
-      finish();
-      return;
-    }
     switch (best) {
       case 0: rtd_launch((conv_igemm_wsq_kernel<5, 5>), grid, blk, 0, s, g); break;
       case 1: rtd_launch((conv_igemm_wsq_kernel<6, 5>), grid, blk, 0, s, g); break;
@@ -2804,12 +2503,8 @@ void launch_conv(const ConvArgs& a, hipStream_t s) {
     const long long x_bytes = ((long long)(x.n - 1) * x.bstride + ((long long)x.h * x.w - 1) * x.ld + x.c) * es;
     const long long w_bytes = (long long)a.Npad * a.Kpad * es;
     RTD_CHECK(!a.next_y.p, 1, "conv: a fused following conv exists on F16X2 operands only (see conv_next_supported)");
-    {
-      const long long yb = ((long long)(y.n - 1) * y.bstride + ((long long)y.h * y.w - 1) * y.ld + y.c) * (long long)dtype_size(y.dt);
-      const unsigned y_bytes = yb < (1ll << 31) ? (unsigned)yb : 0u;
-      if (x.dt == BF16) done = dispatch_glds<bf16>(o, k, tile_ok, a.prefer256 != 0, x_bytes, w_bytes, y_bytes, (unsigned)x2_bytes, a.ws, s);
-      else done = dispatch_glds<float>(o, k, tile_ok, a.prefer256 != 0, x_bytes, w_bytes, y_bytes, (unsigned)x2_bytes, a.ws, s);
-    }
+    if (x.dt == BF16) done = dispatch_glds<bf16>(o, k, tile_ok, a.prefer256 != 0, x_bytes, w_bytes, (unsigned)x2_bytes, s);
+    else done = dispatch_glds<float>(o, k, tile_ok, a.prefer256 != 0, x_bytes, w_bytes, (unsigned)x2_bytes, s);
   }
   RTD_CHECK(done || !dual, 1, "conv: no kernel took the dual-input launch");
   RTD_CHECK(done || !a.next_y.p, 1, "conv: no kernel took the launch with a fused following conv (see conv_next_supported)");

@@ -313,9 +313,11 @@ int rtd_bench_conv(int dtype, int B, int H, int W, int Cin, int Cout, int KH, in
     a.w = w; a.bias = bias; a.KH = KH; a.KW = KH; a.stride = stride; a.pad = pad; a.Kpad = Kpad; a.Npad = Npad;
     a.act = 1; a.res_mode = with_res ? RES_PRE : RES_NONE;
     if (with_res) a.res = mk(r, dtype, B, OH, OW, Cout);
-    a.ws.slab_bytes = std::max<size_t>((size_t)4096 * 8 * 8, conv_split_slab_bytes(a));   // block stamps (glds_drop 32) / two-pass split-K
-    HIP_CHECK(hipMalloc((void**)&a.ws.slab, a.ws.slab_bytes));
-    HIP_CHECK(hipMemset(a.ws.slab, 0, a.ws.slab_bytes));
+    a.ws.slab_bytes = conv_split_slab_bytes(a);                  // two-pass split-K
+    if (a.ws.slab_bytes) {
+      HIP_CHECK(hipMalloc((void**)&a.ws.slab, a.ws.slab_bytes));
+      HIP_CHECK(hipMemset(a.ws.slab, 0, a.ws.slab_bytes));
+    }
     hipEvent_t e0, e1;
     HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
     for (int i = 0; i < 3; ++i) launch_conv(a, nullptr);
@@ -352,54 +354,8 @@ int rtd_bench_conv(int dtype, int B, int H, int W, int Cin, int Cout, int KH, in
       us_out[1] = tot * 1e3f / reps;
     }
     HIP_CHECK(hipDeviceSynchronize());
-    if (getenv("RTD_CONV_STAMPS") && atoi(getenv("RTD_CONV_STAMPS")) == 3) {      // A-stationary kernel: per channel tile of blocks 0, 1, 40
-      std::vector<long long> st((size_t)64 * 16 * 4);
-      HIP_CHECK(hipMemcpy(st.data(), a.ws.slab, st.size() * 8, hipMemcpyDeviceToHost));
-      for (int blk : {0, 1, 40}) {
-        fprintf(stderr, "block %d: first tile landed %lld | per channel tile: K steps done, slab barrier passed, copy-out issued (shader clocks)\n", blk,
-                st[((size_t)blk * 16 + 15) * 4]);
-        for (int t = 0; t < 8; ++t) fprintf(stderr, "  tile %d: %7lld %7lld %7lld\n", t, st[((size_t)blk * 16 + t) * 4], st[((size_t)blk * 16 + t) * 4 + 1], st[((size_t)blk * 16 + t) * 4 + 2]);
-      }
-    } else if (getenv("RTD_CONV_STAMPS") && atoi(getenv("RTD_CONV_STAMPS")) == 2) {      // block-level stamps of the 128-pixel ws kernels
-      const int nb = 4096;
-      std::vector<long long> st((size_t)nb * 8);
-      HIP_CHECK(hipMemcpy(st.data(), a.ws.slab, st.size() * 8, hipMemcpyDeviceToHost));
-      long long t0 = -1;
-      for (int i = 0; i < nb; ++i) if (st[i * 8 + 6] && (t0 < 0 || st[i * 8 + 6] < t0)) t0 = st[i * 8 + 6];
-      double s_land = 0, s_k = 0, s_stage = 0, s_copy = 0, s_ack = 0; int cnt = 0; long long tend = 0;
-      for (int i = 0; i < nb; ++i) {
-        const long long* q = &st[(size_t)i * 8];
-        if (!q[6] || !q[7]) continue;
-        s_land += q[0]; s_k += q[1] - q[0]; s_stage += q[2] - q[1]; s_copy += q[3] - q[2]; s_ack += q[4] - q[3]; ++cnt;
-        if (q[7] > tend) tend = q[7];
-      }
-      fprintf(stderr, "ws blocks stamped %d: mean clocks: first tile landed %.0f | K loop %.0f | staging %.0f | copy-out %.0f | store ack %.0f ; kernel wall %.2f us\n",
-              cnt, s_land / cnt, s_k / cnt, s_stage / cnt, s_copy / cnt, s_ack / cnt, (tend - t0) * 0.01);
-      {   // the core clock the blocks ran at: shader clocks (s_memtime) per 100 MHz tick (s_memrealtime) over a block's life
-        double clk = 0; int c2 = 0;
-        for (int i = 0; i < nb; ++i) { const long long* q = &st[(size_t)i * 8]; if (q[6] && q[7] > q[6]) { clk += (double)q[4] / ((double)(q[7] - q[6]) * 10.0); ++c2; } }
-        if (c2) fprintf(stderr, "  in-kernel core clock %.3f GHz (mean over %d blocks)\n", clk / c2, c2);
-      }
-      for (int i : {0, 1, 600, 1500, 3000}) {
-        const long long* q = &st[(size_t)i * 8];
-        if (q[6]) fprintf(stderr, "  block %4d: start %+8.2f us  landed %6lld  kdone %6lld  staged %6lld  stored %6lld  acked %6lld  life %.2f us\n", i,
-                          (q[6] - t0) * 0.01, q[0], q[1], q[2], q[3], q[4], (q[7] - q[6]) * 0.01);
-      }
-    } else if (getenv("RTD_CONV_STAMPS")) {           // with rtd_debug_option("glds_drop", 32) + conv_mode 7: per-K-step stamps of blocks 0..63
-      std::vector<long long> st((size_t)64 * 48 * 8);
-      HIP_CHECK(hipMemcpy(st.data(), a.ws.slab, st.size() * 8, hipMemcpyDeviceToHost));
-      for (int blk : {0, 1, 17}) {
-        fprintf(stderr, "block %d: ks | landed  barrier issued | mfma: barrier done   (shader clocks from kernel start)\n", blk);
-        for (int ks = 0; ks < 20; ++ks) {
-          const long long* q = &st[((size_t)blk * 48 + ks) * 8];
-          fprintf(stderr, "  %2d | %7lld %7lld %7lld | %7lld %7lld\n", ks, q[0], q[1], q[2], q[3], q[4]);
-        }
-        const long long* z = &st[((size_t)blk * 48 + 47) * 8];
-        fprintf(stderr, "  K loop done %lld, staged %lld, stores issued %lld, stores complete %lld clocks; wall %lld x10ns\n", z[0], z[1], z[2], z[3], z[6] - z[5]);
-      }
-    }
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    (void)hipFree(a.ws.slab);
+    if (a.ws.slab) (void)hipFree(a.ws.slab);
     (void)hipFree(x); (void)hipFree(y); (void)hipFree(w); (void)hipFree(bias);
     if (r) (void)hipFree(r);
     if (flush) (void)hipFree(flush);

@@ -297,6 +297,13 @@ SPLIT_CONV_CASES = [
     (1, 20, 20, 512, 256, 3, 1, 1, "silu", 1, 1),       # 144 K-steps on 8 tiles per image: two-pass split-K in 4 slices, residual + fp32 rows in the reduce pass
     (2, 160, 160, 64, 64, 3, 1, 1, "relu", 0, 0),       # stage-0 c2: the direct 64-channel kernel (>= 128 8 x 16 tiles per image)
     (1, 130, 125, 64, 64, 3, 1, 1, "silu", 0, 0),       # ... ragged tiles both ways
+    # dual input (ConvArgs::x2: + C2 channels of a second tensor at the output pixel) and x_up2 (1x1 over a 2x nearest-upsampled x):
+    # ..., C2, x_up2 - the tile kernels' loader paths for both, on pairs
+    (2, 30, 26, 128, 256, 1, 1, 0, "relu", 0, 0, 256, 0),   # 1x1 main conv + 1x1 of x2 (bottleneck block 0), ragged last tile
+    (2, 24, 20, 64, 128, 3, 1, 1, "silu", 0, 0, 64, 0),     # 3x3 main conv + 1x1 shortcut (basic block)
+    (1, 20, 18, 128, 192, 3, 1, 1, "none", 0, 1, 64, 0),    # ... partial last channel tile, fp32 output
+    (2, 40, 36, 256, 256, 1, 1, 0, "silu", 0, 0, 256, 1),   # x_up2: FPN lateral upsampled + the skip input
+    (3, 22, 20, 128, 128, 1, 1, 0, "relu", 0, 1, 64, 1),    # ... ragged, fp32 output
 ]
 
 
@@ -306,36 +313,67 @@ def test_conv_split_f16x3(L, case):
     (inputs rounded to hi + lo).  Error budget: the dropped lo*lo term (2^-18 per product) + fp32 accumulation + one hi/lo rounding
     of the output (2^-18) -> 2e-5 relative, 250x tighter than the bf16 kernels' tolerance."""
     from telescope_cam_detection_amd import _capi
-    B, H, W, Cin, Cout, k, stride, pad, act, res_mode, out_f32 = case
+    B, H, W, Cin, Cout, k, stride, pad, act, res_mode, out_f32 = case[:11]
+    C2, up2 = case[11:] if len(case) > 11 else (0, 0)
     g = torch.Generator().manual_seed(4000 + SPLIT_CONV_CASES.index(case))
-    x = torch.randn(B, H, W, Cin, generator=g)
+    x = torch.randn(B, H // 2 if up2 else H, W // 2 if up2 else W, Cin, generator=g)
     w = torch.randn(Cout, Cin, k, k, generator=g) * (1.0 / (Cin * k * k)) ** 0.5
     b = torch.randn(Cout, generator=g) * 0.1
     OH, OW = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
     res = torch.randn(B, OH, OW, Cout, generator=g) if res_mode else None
+    x2 = torch.randn(B, OH, OW, C2, generator=g) if C2 else None
+    w2 = torch.randn(Cout, C2, generator=g) * (1.0 / C2) ** 0.5 if C2 else torch.zeros(Cout, 0)
+    wcat = torch.cat([w.permute(0, 2, 3, 1).reshape(Cout, -1), w2], dim=1).contiguous()     # [tap-major x | x2] filter columns
     xs = _capi.to_split(x.numpy())
     xq = torch.from_numpy(_capi.from_split(xs)).permute(0, 3, 1, 2)
-    wq = torch.from_numpy(_capi.from_split(_capi.to_split(w.permute(0, 2, 3, 1).reshape(Cout, -1).numpy()))).reshape(Cout, k, k, Cin).permute(0, 3, 1, 2)
+    wcq = torch.from_numpy(_capi.from_split(_capi.to_split(wcat.numpy())))
+    wq = wcq[:, :k * k * Cin].reshape(Cout, k, k, Cin).permute(0, 3, 1, 2)
     rs = _capi.to_split(res.numpy()) if res is not None else None
     rq = torch.from_numpy(_capi.from_split(rs)).permute(0, 3, 1, 2).double() if res is not None else None
-    y = F.conv2d(xq.double(), wq.double(), b.double(), stride=stride, padding=pad)
+    xin = F.interpolate(xq.double(), scale_factor=2.0, mode="nearest") if up2 else xq.double()
+    y = F.conv2d(xin, wq.double(), b.double(), stride=stride, padding=pad)
+    x2s = _capi.to_split(x2.numpy()) if C2 else None
+    if C2:
+        y = y + F.conv2d(torch.from_numpy(_capi.from_split(x2s)).permute(0, 3, 1, 2).double(), wcq[:, k * k * Cin:, None, None].double())
     if res_mode == 1:
         y = y + rq
     y = {"none": lambda t: t, "relu": F.relu, "silu": F.silu, "gelu": F.gelu}[act](y)
     if res_mode == 2:
         y = y + rq
     xd = torch.from_numpy(xs.view(np.int16)).cuda()
-    wd = w.permute(0, 2, 3, 1).contiguous().cuda()
+    x2d = torch.from_numpy(x2s.view(np.int16)).cuda() if C2 else None
+    wd = wcat.cuda()
     bd = b.cuda()
     rd = torch.from_numpy(rs.view(np.int16)).cuda() if rs is not None else None
     if out_f32:
         yd = torch.full((B, OH, OW, Cout), float("nan"), dtype=torch.float32, device="cuda")
     else:
         yd = torch.full((B, OH, OW, 2 * Cout), -1, dtype=torch.int16, device="cuda")
+    A = {"none": 0, "relu": 1, "silu": 2, "gelu": 3}
+
+    def run(label):
+        yd.fill_(float("nan") if out_f32 else -1)
+        if C2:
+            ck(L, L.rtd_op_conv_dual(_capi.DT_F16X2, xd.data_ptr(), x2d.data_ptr(), wd.data_ptr(), bd.data_ptr(), rd.data_ptr() if rd is not None else None,
+                                     yd.data_ptr(), B, H, W, Cin, C2, Cout, k, stride, pad, A[act], res_mode, out_f32, up2))
+        else:
+            ck(L, L.rtd_op_conv(_capi.DT_F16X2, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), rd.data_ptr() if rd is not None else None,
+                                yd.data_ptr(), B, H, W, Cin, Cout, k, k, stride, pad, A[act], res_mode, out_f32))
+        got = yd.cpu().numpy() if out_f32 else _capi.from_split(yd.cpu().numpy().view(np.uint16))
+        got = torch.from_numpy(got).permute(0, 3, 1, 2).double()
+        assert torch.isfinite(got).all()
+        err = (got - y).abs().max().item() / y.abs().max().item()
+        rel = (torch.linalg.norm(got - y) / torch.linalg.norm(y)).item()
+        print(f"split conv {case}: max err / max |y| {err:.2e}, rel l2 {rel:.2e}")
+        assert err < 2e-5 and rel < 1e-5, (case, label, err, rel)
+        return yd.cpu().numpy().view(np.uint32 if out_f32 else np.uint16).copy()
+
     # dispatch variants: "auto" = the default; "flex" = flexible-height tiles (conv_igemm_wsf_kernel) on every grid and K length;
     # "tiled" = only the fixed-tile kernel (no streaming / direct 3x3 / flexible kernels) with 2-stage 128-wide or 4-stage 64-wide tiles everywhere
-    # "quad" = the 160..256-pixel one-block-per-CU kernel (conv_igemm_wsq_kernel) wherever its shape rules allow (Cout > 64), else the tiled kernel
-    tiled_bits = None
+    # "quad" = the 160..256-pixel one-block-per-CU kernel (conv_igemm_wsq_kernel) wherever its shape rules allow (Cout > 64), else the tiled kernel.
+    # Every pass re-runs with split_k2 0 where the default may split K: the tile kernels walk K in one order and issue the three products in one
+    # order, so which of them ran a layer does not show in its bits
+    tile_bits = {}
     for ws2, ws64, kern in ((257, 160, "auto"), (257, 160, "flex"), (1, 0, "tiled"), (1 << 30, 1 << 30, "tiled"), (1, 0, "quad")):
         _capi.debug_option("reset", 0)
         _capi.debug_option("split_ws2_min_blocks", ws2)
@@ -353,25 +391,19 @@ def test_conv_split_f16x3(L, case):
         if kern == "flex":
             _capi.debug_option("split_flex_small_max", 1 << 30)
             _capi.debug_option("split_flex_min_nk", 1)
-        ck(L, L.rtd_op_conv(_capi.DT_F16X2, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), rd.data_ptr() if rd is not None else None,
-                            yd.data_ptr(), B, H, W, Cin, Cout, k, k, stride, pad, {"none": 0, "relu": 1, "silu": 2, "gelu": 3}[act],
-                            res_mode, out_f32))
-        got = yd.cpu().numpy() if out_f32 else _capi.from_split(yd.cpu().numpy().view(np.uint16))
-        got = torch.from_numpy(got).permute(0, 3, 1, 2).double()
-        assert torch.isfinite(got).all()
-        err = (got - y).abs().max().item() / y.abs().max().item()
-        rel = (torch.linalg.norm(got - y) / torch.linalg.norm(y)).item()
-        print(f"split conv {case}: max err / max |y| {err:.2e}, rel l2 {rel:.2e}")
-        assert err < 2e-5 and rel < 1e-5, (case, ws2, ws64, kern, err, rel)
-        # the tile kernels walk K in one order and issue the three products in one order: which of them ran a layer does not show in its bits
-        if kern == "tiled" and ws2 == 1:
+        bits = run(f"{kern} {ws2}")
+        if kern == "auto":
+            continue
+        if kern == "flex":                           # the flexible kernel alone: no streaming / direct 3x3 kernel takes the shape
+            _capi.debug_option("split_sx", 0)
+            _capi.debug_option("conv_reg", 0)
+        if kern != "quad":
             _capi.debug_option("split_k2", 0)
-            ck(L, L.rtd_op_conv(_capi.DT_F16X2, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), rd.data_ptr() if rd is not None else None,
-                                yd.data_ptr(), B, H, W, Cin, Cout, k, k, stride, pad, {"none": 0, "relu": 1, "silu": 2, "gelu": 3}[act],
-                                res_mode, out_f32))
-            tiled_bits = yd.cpu().numpy().copy()
-        if kern == "quad":
-            np.testing.assert_array_equal(yd.cpu().numpy().view(np.uint32 if out_f32 else np.uint16), tiled_bits.view(np.uint32 if out_f32 else np.uint16))
+            bits = run(f"{kern} {ws2} split_k2 0")
+        tile_bits[f"{kern} {ws2}"] = bits
+    first = next(iter(tile_bits))
+    for label, bits in tile_bits.items():
+        np.testing.assert_array_equal(bits, tile_bits[first], err_msg=f"{case}: {label} vs {first}")
     _capi.debug_option("reset", 0)
 
 
