@@ -54,8 +54,7 @@ int rtd_profile(rtd_handle h, int32_t n, int32_t reps, rtd_layer_time* out, int3
  *   dead_out [1] (f16x3): the stage-0 output is not written when its only readers are that launch's fused follower conv and fused average |
  *   aifi_pair [1] (f16x3): the un-fused AIFI's linears on the pair kernels | side_stream [7: bit 0 query
  *   selection on a second stream beside the value projection, bit 1 decoder input projections beside the PAN path, bit 2 encoder input
- *   projections beside stages 2 / 3 and AIFI] | dec_fused [1],
- *   dec_split [1: 0 fp32 MFMA, 2 hi-only filters], sel_fused [1] | dec_stamps [0]
+ *   projections beside stages 2 / 3 and AIFI] | dec_fused [1] | sel_fused [1]
  * Tools: profile_twice [0], bench_rewarm [0: bit 5 = rtd_bench_conv fills its operands with random fp16 values instead of zeros].
  * "reset" (any value): every template back to the values in brackets. */
 int rtd_debug_option(const char* name, int value);

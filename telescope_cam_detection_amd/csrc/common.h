@@ -287,7 +287,7 @@ struct DecArgs {
   int mode;                 // 0 = prologue (enc_bbox head + ref init + next projections), 1 = layer, 2 = last layer (+ class head),
                             // 3 = AIFI prologue (x + pos -> q, K/V fragments), 4 = AIFI encoder layer
   int attn_split;           // bf16 / f16x3 engines: self-attention on hi/lo fp16 MFMAs with K / V stored as split fragments (0: exact fp32 MFMAs, A/B + tests)
-  int split;                // 1: the linear layers run as 3 fp16 MFMAs on hi/lo splits of both operands (bf16 / f16x3 engines), 0: exact fp32 MFMA
+  int split;                // 1 (bf16 / f16x3 engines): the linear layers run as 3 fp16 MFMAs on hi/lo splits of both operands; 0 (fp32 engine): exact fp32 MFMAs
   int B, Q, D, heads, S, n_levels, n_points, ffn, C;
   float offset_scale;
   // per-row state (global, fp32)
@@ -313,9 +313,6 @@ struct DecArgs {
   float* vfrag_out;
   float* logits;            // mode 2: [B*Q, C]
   void* out_bf16;           // mode 4: write the output tokens as bf16 here instead of fp32 hs_out (nullptr = fp32)
-  float* stamps;            // diagnostic: [blocks][16] phase end times (10 ns units) or nullptr
-  int probe;                // diagnostic, timing only (results wrong), rtd_debug_option "dec_stamps" bits 1 / 2: the linear layers skip their MFMAs (filter
-                            // stream alone) / their filter loads (arithmetic alone): tools/dec_stamps.py RTD_DEC_PROBE
   // weights
   DecLin o, offaw, op, fc1, fc2, bb0, bb1, bb2, qp0, qp1, qk, v, cls;
   DecLN ln1, ln2, ln3;

@@ -28,8 +28,51 @@ __device__ __forceinline__ float dinv_sig(float x) {
   return __logf(fmaxf(x, 1e-5f) / fmaxf(1.f - x, 1e-5f));
 }
 
-// Ys[16][N] = act(Xs[16][K] @ W^T + b (+ Rs)).   Xs / Ys / Rs live in LDS; K % 64 == 0 (zero padded).
-// The 4 waves take the N/16 column tiles round-robin; a lane's A fragment is Xs[row = lane & 15][k0 + 4 (lane >> 4) .. +3],
+// A GEMM operand or result: 16 rows in LDS as fp32 (f, ld) and, for the split engines' GEMMs, optionally as fp16 hi / lo rows (h, l, ldb).
+// The split form reads and writes the hi/lo rows where there are some (ldb != 0: the wide FFN and qpos hidden layers), the fp32 rows
+// elsewhere.  (ldb, not h, tells them apart: hipcc cannot prove an LDS pointer non-null, and the test must fold at every call.)
+struct LdsRows {
+  float* f;
+  int ld;
+  sp16* h = nullptr;
+  sp16* l = nullptr;
+  int ldb = 0;
+};
+
+// The epilogue of both GEMM forms, one pass = column tiles n0 (acc0) and n1 (acc1, if has2): Y = act(acc + b (+ Y when res)).
+// The split form requests the pass's bias with its first filter fragments (bias0 / bias1), the fp32 form reads it here.
+template <int SPLIT, int ACT>
+__device__ __forceinline__ void gemm_epilogue(const f32x4_& acc0, const f32x4_& acc1, float bias0, float bias1, const DecLin& L, int n0, int n1,
+                                              bool has2, const LdsRows& Y, bool res, int lane) {
+  const int r16 = lane & 15, q = lane >> 4;
+  const bool pair = SPLIT && Y.ldb;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    if (h == 1 && !has2) break;
+    const int col = (h == 0 ? n0 : n1) + r16;
+    if (col < L.N) {
+      const float bv = SPLIT ? (h == 0 ? bias0 : bias1) : L.b[col];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int row = q * 4 + r;
+        float v = (h == 0 ? acc0[r] : acc1[r]) + bv;
+        if (res) v += Y.f[row * Y.ld + col];
+        if (ACT == ACT_RELU) v = fmaxf(v, 0.f);
+        if (ACT == ACT_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
+        if (pair) {
+          const sp16 hi = (sp16)v;
+          Y.h[row * Y.ldb + col] = hi;
+          Y.l[row * Y.ldb + col] = (sp16)(v - (float)hi);
+        } else {
+          Y.f[row * Y.ld + col] = v;
+        }
+      }
+    }
+  }
+}
+
+// Y[16][N] = act(X[16][K] @ W^T + b (+ Y)), exact fp32 MFMAs on the fp32 rows.  K % 64 == 0 (zero padded).
+// The waves take the N/16 column tiles round-robin; a lane's A fragment is X[row = lane & 15][k0 + 4 (lane >> 4) .. +3],
 // its B fragment W[n0 + (lane & 15)][same k] - each 16-byte load feeds 4 MFMAs (the k order inside a
 // step only has to agree between A and B).  The weights are stored FRAGMENT-MAJOR (engine.hip pack_fragments):
 // block (tile t, 16-wide k chunk c) is 64 lanes x 16 bytes in lane order, so one wave load is one contiguous
@@ -42,10 +85,10 @@ __device__ __forceinline__ float dinv_sig(float x) {
 // request the whole filter in their first round and later rounds hit in L2.  The fp32 summation order of a row depends only on
 // its tile index, not on the batch size (batch invariance holds bit for bit).
 template <int ACT>
-__device__ void row_gemm(const float* Xs, int ldx, const DecLin& L, float* Ys, int ldy, const float* Rs, int ldr, int wave, int lane, int rot) {
+__device__ void row_gemm(const LdsRows& X, const DecLin& L, const LdsRows& Y, bool res, int wave, int lane, int rot) {
   const int ntiles = (L.N + 15) >> 4;
   const int r16 = lane & 15, q = lane >> 4;
-  const float* xrow = Xs + r16 * ldx + 4 * q;
+  const float* xrow = X.f + r16 * X.ld + 4 * q;
   const int nsteps = L.K >> 6;
   const int npass = (ntiles - wave + 2 * NW - 1) / (2 * NW);   // passes of this wave (wave < ntiles for every layer here)
   // two column tiles (t, t+NW) per pass share the A fragment and give the MFMA pipe two independent accumulators
@@ -91,23 +134,7 @@ __device__ void row_gemm(const float* Xs, int ldx, const DecLin& L, float* Ys, i
 #pragma unroll
       for (int j = 0; j < 4; ++j) { c0[j] = p0[j]; c1[j] = p1[j]; }
     }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      if (h == 1 && !has2) break;
-      const int col = (h == 0 ? n0 : n1) + r16;
-      if (col < L.N) {
-        const float bv = L.b[col];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = q * 4 + r;
-          float v = (h == 0 ? acc0[r] : acc1[r]) + bv;
-          if (Rs) v += Rs[row * ldr + col];
-          if (ACT == ACT_RELU) v = fmaxf(v, 0.f);
-          if (ACT == ACT_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-          Ys[row * ldy + col] = v;
-        }
-      }
-    }
+    gemm_epilogue<0, ACT>(acc0, acc1, 0.f, 0.f, L, n0, n1, has2, Y, res, lane);
   }
 }
 
@@ -130,18 +157,19 @@ __device__ __forceinline__ void split_rows(const float* Xs, int ldx, int K, sp16
   }
 }
 
-// The split form of row_gemm: A = (Ah + Al) [16][K] bf16 in LDS, W = hi + lo bf16 fragments (DecLin, split layout), three
+// The split form of row_gemm: A = X's hi/lo rows [16][K] fp16, W = hi + lo fp16 fragments (DecLin, split layout), three
 // v_mfma_f32_16x16x32_f16 per 32-deep chunk (lo*hi, hi*lo, hi*hi; fp32 accumulate) instead of 8 v_mfma_f32_16x16x4_f32:
 // 5x less MFMA time for the same filter bytes, products exact to ~2^-17.  A lane's fragments: A[row = lane & 15][32c + 8 (lane >> 4) .. +7],
-// W[n0 + (lane & 15)][same k].  Output: fp32 Ys and / or a hi/lo split (Yh, Yl) for a following GEMM.
-template <int ACT, bool WLO = true>   // WLO = false: the filter's lo half is neither loaded nor multiplied (hi-only filter, split activations)
-__device__ void row_gemm_split(const sp16* Ah, const sp16* Al, int lda, const DecLin& L, float* Ys, int ldy, const float* Rs, int ldr,
-                               sp16* Yh, sp16* Yl, int ldyb, int wave, int lane, int rot, int probe = 0) {
-  constexpr int PF = 2;   // K steps of filter fragments in flight per wave (round 2: 3 changed nothing; round 4: 4 needs 128 VGPRs of fragments - 256 + 704 B of scratch, 140 us per layer)
+// W[n0 + (lane & 15)][same k].  Output: Y's hi/lo rows if it has some (for a following GEMM), else its fp32 rows.
+template <int ACT>
+__device__ void row_gemm_split(const LdsRows& X, const DecLin& L, const LdsRows& Y, bool res, int wave, int lane, int rot) {
+  // K steps of filter fragments in flight per wave.  Round 2: 3 changed nothing.  Round 4: 4 needs 128 VGPRs of fragments (140 us per layer);
+  // the "704 B of scratch" seen then was an inlining artefact, not spilling (EXPERIMENTS.md round 5).
+  constexpr int PF = 2;
   const int ntiles = (L.N + 15) >> 4;
   const int r16 = lane & 15, q = lane >> 4;
-  const sp16* ah = Ah + r16 * lda + 8 * q;
-  const sp16* al = Al + r16 * lda + 8 * q;
+  const sp16* ah = X.h + r16 * X.ldb + 8 * q;
+  const sp16* al = X.l + r16 * X.ldb + 8 * q;
   const int kc = L.K >> 5;                                     // 32-deep chunks per tile, 2 KiB each (hi 1 KiB | lo 1 KiB)
   const int nsteps = L.K >> 6;
   const int npass = (ntiles - wave + 2 * NW - 1) / (2 * NW);
@@ -165,9 +193,9 @@ __device__ void row_gemm_split(const sp16* Ah, const sp16* Al, int lda, const De
 #pragma unroll
       for (int j = 0; j < 2; ++j) {
         h0[j] = *(const sp16x8*)(w0 + (step << 1) * 2048 + 2048 * j);
-        if (WLO) l0[j] = *(const sp16x8*)(w0 + (step << 1) * 2048 + 2048 * j + 1024);
+        l0[j] = *(const sp16x8*)(w0 + (step << 1) * 2048 + 2048 * j + 1024);
         h1[j] = *(const sp16x8*)(w1 + (step << 1) * 2048 + 2048 * j);
-        if (WLO) l1[j] = *(const sp16x8*)(w1 + (step << 1) * 2048 + 2048 * j + 1024);
+        l1[j] = *(const sp16x8*)(w1 + (step << 1) * 2048 + 2048 * j + 1024);
       }
     };
     auto mma = [&](const sp16x8 (&h0)[2], const sp16x8 (&l0)[2], const sp16x8 (&h1)[2], const sp16x8 (&l1)[2], int step) {
@@ -177,10 +205,8 @@ __device__ void row_gemm_split(const sp16* Ah, const sp16* Al, int lda, const De
         const sp16x8 xh = *(const sp16x8*)(ah + k0 + 32 * j), xl = *(const sp16x8*)(al + k0 + 32 * j);
         acc0 = mfma_pair16(xl, h0[j], acc0);
         acc1 = mfma_pair16(xl, h1[j], acc1);
-        if (WLO) {
-          acc0 = mfma_pair16(xh, l0[j], acc0);
-          acc1 = mfma_pair16(xh, l1[j], acc1);
-        }
+        acc0 = mfma_pair16(xh, l0[j], acc0);
+        acc1 = mfma_pair16(xh, l1[j], acc1);
         acc0 = mfma_pair16(xh, h0[j], acc0);
         acc1 = mfma_pair16(xh, h1[j], acc1);
       }
@@ -195,42 +221,20 @@ __device__ void row_gemm_split(const sp16* Ah, const sp16* Al, int lda, const De
       for (int u = 0; u < PF; ++u) {
         if (it + u < nsteps) {
           __builtin_amdgcn_sched_barrier(0);
-          if (!(probe & 1)) mma(wh0[u], wl0[u], wh1[u], wl1[u], cur);
-          else { acc0[0] += (float)wh0[u][1][7] + (float)wl1[u][1][7]; acc1[0] += (float)wh1[u][1][7] + (float)wl0[u][1][7]; }   // probe: waits for the step's loads, no MFMA
+          mma(wh0[u], wl0[u], wh1[u], wl1[u], cur);
           cur = nxt(cur);
           __builtin_amdgcn_sched_barrier(0);
-          if (it + u + PF < nsteps && !(probe & 2)) { load(wh0[u], wl0[u], wh1[u], wl1[u], pf); pf = nxt(pf); }
+          if (it + u + PF < nsteps) { load(wh0[u], wl0[u], wh1[u], wl1[u], pf); pf = nxt(pf); }
         }
       }
     }
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      if (h == 1 && !has2) break;
-      const int col = (h == 0 ? n0 : n1) + r16;
-      if (col < L.N) {
-        const float bv = h == 0 ? bias0 : bias1;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int row = q * 4 + r;
-          float v = (h == 0 ? acc0[r] : acc1[r]) + bv;
-          if (Rs) v += Rs[row * ldr + col];
-          if (ACT == ACT_RELU) v = fmaxf(v, 0.f);
-          if (ACT == ACT_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-          if (Ys) Ys[row * ldy + col] = v;
-          if (Yh) {
-            const sp16 hi = (sp16)v;
-            Yh[row * ldyb + col] = hi;
-            Yl[row * ldyb + col] = (sp16)(v - (float)hi);
-          }
-        }
-      }
-    }
+    gemm_epilogue<1, ACT>(acc0, acc1, bias0, bias1, L, n0, n1, has2, Y, res, lane);
   }
 }
 
 // in-place LayerNorm of Xs[16][D] (D <= 256, D % 4 == 0); each wave owns DR / NW rows.  The affine parameters come in registers: the caller
 // requests them (ln_fetch) BEFORE the GEMM that produces the rows, so their L2 round trip (~1.5 us of this 2.5 us phase when it was issued
-// here, tools/dec_stamps.py) runs under that GEMM.  Same arithmetic, same order: bit-identical rows.
+// here, EXPERIMENTS.md "Decoder, round 4") runs under that GEMM.  Same arithmetic, same order: bit-identical rows.
 struct LNRegs { float g[4], b[4]; };
 __device__ __forceinline__ LNRegs ln_fetch(const DecLN& P, int D, int lane) {
   LNRegs R;
@@ -533,17 +537,11 @@ __device__ void self_attention_rows_split(const DecArgs& a, const float* sQ, int
   }
 }
 
-// diagnostic phase stamps (100 MHz wall clock), enabled only when a.stamps != nullptr (rtd_debug_option "dec_stamps")
-#define DEC_STAMP(i)                                                                         \
-  do {                                                                                       \
-    if (a.stamps && tid == 0) a.stamps[(size_t)blockIdx.x * 16 + (i)] = (float)(long long)(__builtin_amdgcn_s_memrealtime() - t_start); \
-  } while (0)
-
 typedef __attribute__((address_space(3))) void* dec_lds_ptr_t;
 // Ask L2 for a later GEMM's filter: one dword per 128-byte line, this block's 1/nparts share, LDS-DMA into a dummy (no VGPR,
 // nothing waits).  The blocks of an XCD together request the whole filter one phase before they stream it, so the stream
-// hits in L2 instead of every block waiting on the same misses (tools/dec_stamps.py: 137 -> 115 us per layer came from
-// de-synchronising the blocks; this removes the remaining first-touch misses).
+// hits in L2 instead of every block waiting on the same misses (137 -> 115 us per layer came from de-synchronising the blocks,
+// EXPERIMENTS.md "Decoder, round 4"; this removes the remaining first-touch misses).
 __device__ __forceinline__ void touch_weights(const DecLin& L, int part, int nparts, int tid, char* dummy) {
   if (!L.w) return;
   const unsigned bytes = (unsigned)((L.N + 15) >> 4) * (unsigned)L.K * 64u;
@@ -552,9 +550,10 @@ __device__ __forceinline__ void touch_weights(const DecLin& L, int part, int npa
   for (unsigned l = part + nparts * tid; l < lines; l += nparts * NT) __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (dec_lds_ptr_t)dummy, 4, l << 7, 0, 0, 0);
 }
 
-// SPLIT: the linear layers take hi/lo fp16 splits of their operands (row_gemm_split); every fp32 A operand of K <= 256 is split
-// into the sXh/sXl staging rows right before its GEMM, the two wide ones (FFN hidden 1024, qpos hidden 512) are written as
-// splits by the producing GEMM straight into the sF region (same bytes as the fp32 rows they replace).
+// SPLIT = 0: fp32 engines, exact fp32 MFMAs (row_gemm).  SPLIT = 1: bf16 / f16x3 engines, the linear layers take hi/lo fp16 splits of
+// their operands (row_gemm_split); every fp32 A operand of K <= 256 is split into the sXh/sXl staging rows right before its GEMM, the
+// two wide ones (FFN hidden 1024, qpos hidden 512) are written as splits by the producing GEMM straight into the sF region (same bytes
+// as the fp32 rows they replace).
 // (The phase functions above are plain __device__ functions that hipcc inlines here.  When the inliner's budget runs out - any experiment that
 // grows this kernel - it leaves one of them as a CALL, the by-reference DecArgs must then live in memory, and the whole 704-byte argument
 // struct is copied to scratch at kernel entry: round 4 read that as register spilling ("256 registers + 704 B of scratch"); it is an
@@ -580,27 +579,35 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
   __shared__ __attribute__((aligned(16))) float sO[DR * LDO];   // sampling offsets | attention logits
   __shared__ __attribute__((aligned(16))) float sR[DR * LDR];   // ref boxes (cols 0..3), zero padded to 64 (K of qpos.0)
 
+  const LdsRows ffn_hidden = {sF, LDF, sFh, sFl, LDFB}, qpos_hidden = {sT, LDQ, sQh, sQl, LDQB};
+
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  // Y[16][N] = act(X[16][K] W^T + b (+ R)); X fp32 rows in LDS.  SPLIT: X is first split into sXh/sXl (all waves must have
-  // left the previous GEMM: every call site below sits behind a __syncthreads()).
-#define DEC_TOUCH(LW) touch_weights(LW, rot, tiles, tid, sDummy)
-#define DEC_GEMM(ACT, X, LDXS, LW, Y, LDY, R, LDRS, NEXT)                                                   \
-  do {                                                                                                       \
-    if (SPLIT) {                                                                                             \
-      split_rows(X, LDXS, (LW).K, sXh, sXl, LDX, tid);                                                       \
-      __syncthreads();                                                                                       \
-      row_gemm_split<ACT, (SPLIT != 2) >(sXh, sXl, LDX, LW, Y, LDY, R, LDRS, nullptr, nullptr, 0, wave, lane, rot, a.probe);         \
-    } else {                                                                                                 \
-      row_gemm<ACT>(X, LDXS, LW, Y, LDY, R, LDRS, wave, lane, rot);                                          \
-    }                                                                                                        \
-    DEC_TOUCH(NEXT);                                                                                         \
-  } while (0)
-  const unsigned long long t_start = a.stamps ? __builtin_amdgcn_s_memrealtime() : 0ull;
   const int tiles = (a.Q + DR - 1) / DR;
   const int b = blockIdx.x / tiles;
   const int q0 = (blockIdx.x - b * tiles) * DR;
   const int rot = q0 / DR;                                       // GEMM pass / K-step rotation (row_gemm)
   const DecLin no_next = {nullptr, nullptr, 0, 0, 0};
+  auto touch = [&](const DecLin& L) { touch_weights(L, rot, tiles, tid, sDummy); };
+  // Every linear layer: Y = act(X W^T + b (+ Y when res)), then `next`, a later GEMM's filter, is requested (touch).  SPLIT: fp32 X
+  // rows are first split into sXh/sXl (all waves must have left the previous GEMM: every call below sits behind a __syncthreads()).
+  // `act` is a constant at every call but fc1's; the branches fold once this is inlined.
+  auto linear = [&](int act, LdsRows X, const DecLin& L, const LdsRows& Y, bool res, const DecLin& next) __attribute__((always_inline)) {
+    if (SPLIT && !X.ldb) {
+      split_rows(X.f, X.ld, L.K, sXh, sXl, LDX, tid);
+      __syncthreads();
+      X = {nullptr, 0, sXh, sXl, LDX};
+    }
+    if (SPLIT) {
+      if (act == ACT_GELU) row_gemm_split<ACT_GELU>(X, L, Y, res, wave, lane, rot);
+      else if (act == ACT_RELU) row_gemm_split<ACT_RELU>(X, L, Y, res, wave, lane, rot);
+      else row_gemm_split<ACT_NONE>(X, L, Y, res, wave, lane, rot);
+    } else {
+      if (act == ACT_GELU) row_gemm<ACT_GELU>(X, L, Y, res, wave, lane, rot);
+      else if (act == ACT_RELU) row_gemm<ACT_RELU>(X, L, Y, res, wave, lane, rot);
+      else row_gemm<ACT_NONE>(X, L, Y, res, wave, lane, rot);
+    }
+    touch(next);
+  };
   const int D = a.D;
   const long long row0 = (long long)b * a.Q + q0;
   const int nvalid = min(DR, a.Q - q0);
@@ -622,12 +629,12 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
       if (has_cross) vp[i] = *(const f32x4_*)(a.qpos_in + (row0 + rr) * D + c);
       if (a.mode == 3) vp[i] = *(const f32x4_*)(a.qpos_in + (long long)(q0 + rr) * D + c);   // AIFI: one sin-cos table for every image
     }
-    // first filters of this launch (the later ones are requested one GEMM ahead, DEC_GEMM)
-    if (has_attn) { DEC_TOUCH(a.o); DEC_TOUCH(a.fc1); }
-    if (has_cross) DEC_TOUCH(a.offaw);
-    if (a.mode == 4) DEC_TOUCH(a.fc2);
-    if (a.mode == 0) { DEC_TOUCH(a.bb0); DEC_TOUCH(a.bb1); }
-    if (a.mode == 3) { DEC_TOUCH(a.qk); DEC_TOUCH(a.v); }
+    // first filters of this launch (the later ones are requested one GEMM ahead, linear())
+    if (has_attn) { touch(a.o); touch(a.fc1); }
+    if (has_cross) touch(a.offaw);
+    if (a.mode == 4) touch(a.fc2);
+    if (a.mode == 0) { touch(a.bb0); touch(a.bb1); }
+    if (a.mode == 3) { touch(a.qk); touch(a.v); }
     const f32x4_ z4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < PER; ++i) {
@@ -643,7 +650,6 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
     sR[e] = (has_cross && r < nvalid && c < 4) ? a.ref8[(row0 + r) * 8 + c] : 0.f;
   }
   __syncthreads();
-  DEC_STAMP(0);   // rows loaded
 
   if (has_attn) {
     // ---- self-attention (q in sT, K/V fragments from the previous launch) -> sA ----------------------------
@@ -652,15 +658,12 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
       else self_attention_rows(a, sT, LDQ, sA, LDH, b, tiles, head, lane);
     }
     __syncthreads();
-    DEC_STAMP(12);  // self-attention
     // ---- self-attention output projection + residual + LN1 (HF:v2.py:395-405) ---------------------
     const LNRegs ln1 = ln_fetch(a.ln1, D, lane);
-    DEC_GEMM(ACT_NONE, sA, LDH, a.o, sH, LDH, sH, LDH, a.op);      // x = hs + att @ Wo   (in place: each element read then written by one lane)
+    linear(ACT_NONE, {sA, LDH}, a.o, {sH, LDH}, true, a.op);     // x = hs + att @ Wo   (in place: each element read then written by one lane)
     __syncthreads();
-    DEC_STAMP(1);   // o_proj
     row_ln(sH, LDH, D, ln1, wave, lane);
     __syncthreads();
-    DEC_STAMP(2);   // ln1
   }
   if (has_cross) {
     // ---- cross attention: (x + qpos) -> offsets | weights (HF:v2.py:170-186) -------------------------
@@ -669,44 +672,28 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
       sA[r * LDH + c] = sH[r * LDH + c] + sP[r * LDH + c];
     }
     __syncthreads();
-    DEC_GEMM(ACT_NONE, sA, LDH, a.offaw, sO, LDO, nullptr, 0, a.fc1);
+    linear(ACT_NONE, {sA, LDH}, a.offaw, {sO, LDO}, false, a.fc1);
     __syncthreads();
-    DEC_STAMP(3);   // add + offaw
     // ---- MS-deformable sampling (HF:v2.py:44-115,203-221): 32 lanes = one (row, head) ---------------
     if (a.value_f32) sample_rows<float>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
     else sample_rows<bf16>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
     __syncthreads();
-    DEC_STAMP(4);   // sampling
     // ---- output projection + residual + LN2 (HF:v2.py:221,418-421) ----------------------------------
     const LNRegs ln2 = ln_fetch(a.ln2, D, lane);
-    DEC_GEMM(ACT_NONE, sA, LDH, a.op, sH, LDH, sH, LDH, a.fc2);
+    linear(ACT_NONE, {sA, LDH}, a.op, {sH, LDH}, true, a.fc2);
     __syncthreads();
     row_ln(sH, LDH, D, ln2, wave, lane);
     __syncthreads();
-    DEC_STAMP(5);   // op + ln2
   }
   if (has_attn) {
     // ---- FFN + residual + LN3 (HF:v2.py:423-428; AIFI: GELU, :888-896) ---------------------------------
-    if (SPLIT) {
-      split_rows(sH, LDH, a.fc1.K, sXh, sXl, LDX, tid);
-      __syncthreads();
-      if (a.mode == 4) row_gemm_split<ACT_GELU, (SPLIT != 2) >(sXh, sXl, LDX, a.fc1, nullptr, 0, nullptr, 0, sFh, sFl, LDFB, wave, lane, rot, a.probe);
-      else row_gemm_split<ACT_RELU, (SPLIT != 2) >(sXh, sXl, LDX, a.fc1, nullptr, 0, nullptr, 0, sFh, sFl, LDFB, wave, lane, rot, a.probe);
-    } else {
-      if (a.mode == 4) row_gemm<ACT_GELU>(sH, LDH, a.fc1, sF, LDF, nullptr, 0, wave, lane, rot);
-      else row_gemm<ACT_RELU>(sH, LDH, a.fc1, sF, LDF, nullptr, 0, wave, lane, rot);
-    }
-    DEC_TOUCH(a.bb0);
+    linear(a.mode == 4 ? ACT_GELU : ACT_RELU, {sH, LDH}, a.fc1, ffn_hidden, false, a.bb0);
     __syncthreads();
-    DEC_STAMP(6);   // fc1
     const LNRegs ln3 = ln_fetch(a.ln3, D, lane);
-    if (SPLIT) row_gemm_split<ACT_NONE, (SPLIT != 2) >(sFh, sFl, LDFB, a.fc2, sH, LDH, sH, LDH, nullptr, nullptr, 0, wave, lane, rot, a.probe);
-    else row_gemm<ACT_NONE>(sF, LDF, a.fc2, sH, LDH, sH, LDH, wave, lane, rot);
-    DEC_TOUCH(a.bb1);
+    linear(ACT_NONE, ffn_hidden, a.fc2, {sH, LDH}, true, a.bb1);
     __syncthreads();
     row_ln(sH, LDH, D, ln3, wave, lane);
     __syncthreads();
-    DEC_STAMP(7);   // fc2 + ln3
   }
   if (a.mode == 4) {
     // AIFI output tokens in the trunk's storage type (they feed the CCFF convolutions)
@@ -722,13 +709,13 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
 
   if (a.mode != 3) {
   // ---- box head: mode 0 = enc_bbox_head(target) + anchors (HF:v2.py:1588-1599), else bbox_embed[i] + logit(ref) (:636-639)
-  DEC_GEMM(ACT_RELU, sH, LDH, a.bb0, sA, LDH, nullptr, 0, a.qp0);
-  DEC_TOUCH(a.bb2);
+  linear(ACT_RELU, {sH, LDH}, a.bb0, {sA, LDH}, false, a.qp0);
+  touch(a.bb2);
   __syncthreads();
-  DEC_GEMM(ACT_RELU, sA, LDH, a.bb1, sT, LDQ, nullptr, 0, a.qp1);
-  DEC_TOUCH(a.cls);
+  linear(ACT_RELU, {sA, LDH}, a.bb1, {sT, LDQ}, false, a.qp1);
+  touch(a.cls);
   __syncthreads();
-  DEC_GEMM(ACT_NONE, sT, LDQ, a.bb2, sO, LDO, nullptr, 0, a.qk);    // [16][4] deltas in sO cols 0..3
+  linear(ACT_NONE, {sT, LDQ}, a.bb2, {sO, LDO}, false, a.qk);      // [16][4] deltas in sO cols 0..3
   __syncthreads();
   if (tid < DR * 4) {
     const int r = tid >> 2, c = tid & 3;
@@ -749,7 +736,6 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
       a.ref8[(row0 + r) * 8 + 4 + c] = 0.f;
     }
   }
-  DEC_STAMP(8);   // bbox head + refine
   // hidden state of this layer
   if (a.mode != 0) {
     for (int e = tid; e < DR * D; e += NT) {
@@ -762,7 +748,7 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
 
   if (a.mode == 2) {
     // ---- class head of the last layer (HF:v2.py:644-646,1880) ----------------------------------------
-    DEC_GEMM(ACT_NONE, sH, LDH, a.cls, sT, LDQ, nullptr, 0, no_next);
+    linear(ACT_NONE, {sH, LDH}, a.cls, {sT, LDQ}, false, no_next);
     __syncthreads();
     for (int e = tid; e < DR * a.C; e += NT) {
       const int r = e / a.C, c = e - r * a.C;
@@ -773,33 +759,21 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
 
   // ---- projections for the NEXT layer: qpos = MLP(ref) (HF:v2.py:613), q|k = (hs+qpos) Wqk, v = hs Wv ----
   if (a.mode != 3) {
-    if (SPLIT) {
-      split_rows(sR, LDR, a.qp0.K, sXh, sXl, LDX, tid);
-      __syncthreads();
-      row_gemm_split<ACT_RELU, (SPLIT != 2) >(sXh, sXl, LDX, a.qp0, nullptr, 0, nullptr, 0, sQh, sQl, LDQB, wave, lane, rot, a.probe);
-      DEC_TOUCH(a.v);
-      __syncthreads();
-      row_gemm_split<ACT_NONE, (SPLIT != 2) >(sQh, sQl, LDQB, a.qp1, sP, LDH, nullptr, 0, nullptr, nullptr, 0, wave, lane, rot, a.probe);
-    } else {
-      row_gemm<ACT_RELU>(sR, LDR, a.qp0, sT, LDQ, nullptr, 0, wave, lane, rot);
-      DEC_TOUCH(a.v);
-      __syncthreads();
-      row_gemm<ACT_NONE>(sT, LDQ, a.qp1, sP, LDH, nullptr, 0, wave, lane, rot);
-    }
+    linear(ACT_RELU, {sR, LDR}, a.qp0, qpos_hidden, false, a.v);
+    __syncthreads();
+    linear(ACT_NONE, qpos_hidden, a.qp1, {sP, LDH}, false, no_next);
     __syncthreads();
   }
-  DEC_STAMP(9);   // hs store + qpos MLP
   for (int e = tid; e < DR * D; e += NT) {
     const int r = e / D, c = e - r * D;
     sA[r * LDH + c] = sH[r * LDH + c] + sP[r * LDH + c];
     if (a.mode != 3 && r < nvalid) a.qpos_out[(row0 + r) * D + c] = sP[r * LDH + c];
   }
   __syncthreads();
-  DEC_GEMM(ACT_NONE, sA, LDH, a.qk, sT, LDQ, nullptr, 0, no_next);
+  linear(ACT_NONE, {sA, LDH}, a.qk, {sT, LDQ}, false, no_next);
   if (SPLIT) __syncthreads();                                   // every wave is out of the q|k GEMM before its staging rows are re-split
-  DEC_GEMM(ACT_NONE, sH, LDH, a.v, sO, LDO, nullptr, 0, no_next);
+  linear(ACT_NONE, {sH, LDH}, a.v, {sO, LDO}, false, no_next);
   __syncthreads();
-  DEC_STAMP(10);  // qk + v
   // q rows, and K / V of these 16 rows (= key tile `tile`) in the fragment order self_attention_rows() reads
   for (int e = tid; e < DR * D; e += NT) {
     const int r = e / D, c = e - r * D;
@@ -848,7 +822,6 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
       a.vfrag_out[dst] = vr < nvalid ? sO[vr * LDO + h * 32 + 16 * c + (ln & 15)] : 0.f;
     }
   }
-  DEC_STAMP(11);  // stores
 }
 
 // ---- query selection scores: LayerNorm + enc_score_head + class max in one launch (exact fp32 MFMA) ----------------------------
@@ -980,8 +953,7 @@ void launch_dec_layer(const DecArgs& a, hipStream_t s) {
   RTD_CHECK(a.D == 256 && a.D / a.heads == 32 && a.ffn <= 1024 && a.C <= 512, 1, "fused decoder: d_model 256, head dim 32, ffn <= 1024");
   RTD_CHECK(a.n_levels == 3 && a.n_points == 4 && a.heads == NW, 1, "fused decoder: 3 levels x 4 points, one head per wave");
   const int tiles = (a.Q + DR - 1) / DR;
-  if (a.split == 2) rtd_launch(dec_layer_kernel<2>, dim3(a.B * tiles), dim3(NT), 0, s, a);
-  else if (a.split) rtd_launch(dec_layer_kernel<1>, dim3(a.B * tiles), dim3(NT), 0, s, a);
+  if (a.split) rtd_launch(dec_layer_kernel<1>, dim3(a.B * tiles), dim3(NT), 0, s, a);
   else rtd_launch(dec_layer_kernel<0>, dim3(a.B * tiles), dim3(NT), 0, s, a);
   HIP_CHECK(hipGetLastError());
 }

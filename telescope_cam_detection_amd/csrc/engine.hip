@@ -460,6 +460,20 @@ struct Builder {
     push(name, "convert", 0.0, tbytes(x) + tbytes(y), [x, y, rows](hipStream_t s) { launch_f32_to_split((const float*)x.p, x.ld, y.p, y.ld, rows, x.c, s); });
     return y;
   }
+  // a filter / LayerNorm of the fused row kernels (decoder.hip: fused AIFI and decoder).  bf16 and f16x3 engines get the hi/lo fragment
+  // layout of their pair MFMAs (DecArgs::split = 1), the fp32 engine fp32 fragments.  Kuse < K: zero-padded columns.
+  DecLin dec_lin(const std::string& name, int N, int K, int Kuse = 0) {
+    DecLin L{};
+    if (dry) return L;
+    const DevWeight w = get_weight_packed(e, name, N, K, Kuse ? Kuse : K, e->P != F32);
+    L.w = (const float*)w.w; L.b = w.bias; L.ldw = w.Kpad; L.N = N; L.K = w.K;
+    return L;
+  }
+  DecLN dec_ln(const std::string& name, int D) {
+    DecLN P{};
+    if (!dry) { P.g = get_vec(e, name + ".g", D); P.b = get_vec(e, name + ".b", D); }
+    return P;
+  }
   Tensor layernorm(const std::string& name, const Tensor& x, int odt, const std::string& tname = "") {
     if (odt == F16X2) return to_split(name + ".split", layernorm(name, x, F32), tname);
     Tensor y = act(odt, x.n, x.h, x.w, x.c, tname);
@@ -737,16 +751,8 @@ void build_graph(rtd_engine* e, Builder& B, int n) {
     const int tlp = (tl + 1) & ~1;                              // the kernels stride the fragment buffers by an even tile count
     float* kf = (float*)B.alloc((size_t)n * 8 * tlp * 512 * 4);
     float* vf = (float*)B.alloc((size_t)n * 8 * tlp * 512 * 4);
-    auto elin = [&](const std::string& name, int N, int K) {
-      DecLin Lw{};
-      if (!B.dry) {
-        DevWeight w = get_weight_packed(e, name, N, K, K, e->opts.dec_split && P != F32);
-        Lw.w = (const float*)w.w; Lw.b = w.bias; Lw.ldw = w.Kpad; Lw.N = N; Lw.K = w.K;
-      }
-      return Lw;
-    };
     DecArgs a0{};
-    a0.split = P != F32 ? e->opts.dec_split : 0;
+    a0.split = P != F32;
     a0.attn_split = e->opts.attn_split & 1;                          // bit 0: AIFI, bit 1: decoder
     a0.B = n; a0.Q = L; a0.D = d; a0.heads = 8; a0.S = 0; a0.n_levels = 3; a0.n_points = 4; a0.ffn = c.enc_ffn; a0.C = 4;
     a0.hs_in = (const float*)t0.p; a0.qpos_in = e->pos_dev;
@@ -754,15 +760,12 @@ void build_graph(rtd_engine* e, Builder& B, int n) {
     a0.kfrag_in = kf; a0.vfrag_in = vf; a0.kfrag_out = kf; a0.vfrag_out = vf;
     DecArgs a3 = a0;
     a3.mode = 3;
-    a3.qk = elin("enc.aifi.qk", 2 * d, d); a3.v = elin("enc.aifi.v", d, d);
+    a3.qk = B.dec_lin("enc.aifi.qk", 2 * d, d); a3.v = B.dec_lin("enc.aifi.v", d, d);
     B.push("enc.aifi.qkv", "dec_layer", 2.0 * n * L * 3.0 * d * d, (double)n * L * d * 4 * 5, [a3](hipStream_t s) { launch_dec_layer(a3, s); });
     DecArgs a4 = a0;
     a4.mode = 4;
-    a4.o = elin("enc.aifi.o", d, d); a4.fc1 = elin("enc.aifi.fc1", c.enc_ffn, d); a4.fc2 = elin("enc.aifi.fc2", d, c.enc_ffn);
-    if (!B.dry) {
-      a4.ln1.g = get_vec(e, "enc.aifi.ln1.g", d); a4.ln1.b = get_vec(e, "enc.aifi.ln1.b", d);
-      a4.ln3.g = get_vec(e, "enc.aifi.ln2.g", d); a4.ln3.b = get_vec(e, "enc.aifi.ln2.b", d);
-    }
+    a4.o = B.dec_lin("enc.aifi.o", d, d); a4.fc1 = B.dec_lin("enc.aifi.fc1", c.enc_ffn, d); a4.fc2 = B.dec_lin("enc.aifi.fc2", d, c.enc_ffn);
+    a4.ln1 = B.dec_ln("enc.aifi.ln1", d); a4.ln3 = B.dec_ln("enc.aifi.ln2", d);
     Tensor t2f;
     if (SP) { t2f = B.act(F32, n, L, 1, d); a4.hs_out = (float*)t2f.p; }
     else if (P == BF16) a4.out_bf16 = t2.p;
@@ -961,21 +964,8 @@ void build_graph(rtd_engine* e, Builder& B, int n) {
       vfrag[i] = (float*)B.alloc((size_t)n * c.dec_heads * ((dtiles + 1) & ~1) * 512 * 4);
     }
     logits = B.act(F32, n, Q, 1, C, "logits");
-    auto lin = [&](const std::string& name, int N, int K, int Kuse = 0) {
-      DecLin L{};
-      if (!B.dry) {
-        DevWeight w = get_weight_packed(e, name, N, K, Kuse ? Kuse : K, e->opts.dec_split && P != F32);
-        L.w = (const float*)w.w; L.b = w.bias; L.ldw = w.Kpad; L.N = N; L.K = w.K;
-      }
-      return L;
-    };
-    auto lnp = [&](const std::string& name) {
-      DecLN P{};
-      if (!B.dry) { P.g = get_vec(e, name + ".g", dm); P.b = get_vec(e, name + ".b", dm); }
-      return P;
-    };
     DecArgs base{};
-    base.split = P != F32 ? e->opts.dec_split : 0;
+    base.split = P != F32;
     base.attn_split = (e->opts.attn_split >> 1) & 1;
     base.B = n; base.Q = Q; base.D = dm; base.heads = c.dec_heads; base.S = S; base.n_levels = c.n_levels;
     base.n_points = c.n_points; base.ffn = c.dec_ffn; base.C = C; base.offset_scale = c.offset_scale;
@@ -984,15 +974,15 @@ void build_graph(rtd_engine* e, Builder& B, int n) {
     base.qpos_in = (const float*)qpos.p; base.qpos_out = (float*)qpos.p;
     base.q_in = (const float*)qrows.p; base.q_out = (float*)qrows.p;
     base.logits = (float*)logits.p;
-    base.qp0 = lin("dec.qpos.0", 2 * dm, 8, 64);   // K padded to one 64-wide step (zero weights / zero LDS columns)
-    base.qp1 = lin("dec.qpos.1", dm, 2 * dm);
+    base.qp0 = B.dec_lin("dec.qpos.0", 2 * dm, 8, 64);   // K padded to one 64-wide step (zero weights / zero LDS columns)
+    base.qp1 = B.dec_lin("dec.qpos.1", dm, 2 * dm);
     const double row_flops_next = 2.0 * n * Q * ((double)8 * 2 * dm + 2.0 * dm * dm + 2.0 * dm * dm + (double)dm * dm);
     {
       DecArgs a = base;
       a.mode = 0;
       a.hs_in = (const float*)target.p; a.hs_out = nullptr;
-      a.bb0 = lin("dec.enc_bbox.0", dm, dm); a.bb1 = lin("dec.enc_bbox.1", dm, dm); a.bb2 = lin("dec.enc_bbox.2", 4, dm);
-      a.qk = lin("dec.l0.sa.qk", 2 * dm, dm); a.v = lin("dec.l0.sa.v", dm, dm);
+      a.bb0 = B.dec_lin("dec.enc_bbox.0", dm, dm); a.bb1 = B.dec_lin("dec.enc_bbox.1", dm, dm); a.bb2 = B.dec_lin("dec.enc_bbox.2", 4, dm);
+      a.qk = B.dec_lin("dec.l0.sa.qk", 2 * dm, dm); a.v = B.dec_lin("dec.l0.sa.v", dm, dm);
       a.kfrag_out = kfrag[0]; a.vfrag_out = vfrag[0];
       if (!side_joined) B.lane = 1;
       B.push("dec.prologue", "dec_layer", 2.0 * n * Q * (2.0 * dm * dm + 4.0 * dm) + row_flops_next, (double)n * Q * dm * 4 * 6,
@@ -1010,18 +1000,12 @@ void build_graph(rtd_engine* e, Builder& B, int n) {
       a.value_coff = i * dm;
       a.kfrag_in = kfrag[i & 1]; a.vfrag_in = vfrag[i & 1];
       a.kfrag_out = kfrag[(i + 1) & 1]; a.vfrag_out = vfrag[(i + 1) & 1];
-      a.o = lin(p + ".sa.o", dm, dm); a.ln1 = lnp(p + ".ln1");
-      a.offaw = lin(p + ".ca.offaw", 3 * npts, dm); a.op = lin(p + ".ca.op", dm, dm); a.ln2 = lnp(p + ".ln2");
-      a.fc1 = lin(p + ".fc1", c.dec_ffn, dm); a.fc2 = lin(p + ".fc2", dm, c.dec_ffn); a.ln3 = lnp(p + ".ln3");
-      a.bb0 = lin(nm("dec.bbox.%d.0", i), dm, dm); a.bb1 = lin(nm("dec.bbox.%d.1", i), dm, dm); a.bb2 = lin(nm("dec.bbox.%d.2", i), 4, dm);
-      if (last) a.cls = lin("dec.cls", C, dm);
-      else { a.qk = lin(nm("dec.l%d.sa.qk", i + 1), 2 * dm, dm); a.v = lin(nm("dec.l%d.sa.v", i + 1), dm, dm); }
-      a.probe = e->opts.dec_stamps >> 1;                           // diagnostic (timing only): bits 1 / 2 of "dec_stamps"
-      if ((e->opts.dec_stamps & 1) && i == std::min(2, NL - 1)) {
-        const int blocks = n * ((Q + 15) / 16);
-        Tensor st = B.act(F32, 1, blocks, 1, 16, "dec_stamps");
-        a.stamps = (float*)st.p;
-      }
+      a.o = B.dec_lin(p + ".sa.o", dm, dm); a.ln1 = B.dec_ln(p + ".ln1", dm);
+      a.offaw = B.dec_lin(p + ".ca.offaw", 3 * npts, dm); a.op = B.dec_lin(p + ".ca.op", dm, dm); a.ln2 = B.dec_ln(p + ".ln2", dm);
+      a.fc1 = B.dec_lin(p + ".fc1", c.dec_ffn, dm); a.fc2 = B.dec_lin(p + ".fc2", dm, c.dec_ffn); a.ln3 = B.dec_ln(p + ".ln3", dm);
+      a.bb0 = B.dec_lin(nm("dec.bbox.%d.0", i), dm, dm); a.bb1 = B.dec_lin(nm("dec.bbox.%d.1", i), dm, dm); a.bb2 = B.dec_lin(nm("dec.bbox.%d.2", i), 4, dm);
+      if (last) a.cls = B.dec_lin("dec.cls", C, dm);
+      else { a.qk = B.dec_lin(nm("dec.l%d.sa.qk", i + 1), 2 * dm, dm); a.v = B.dec_lin(nm("dec.l%d.sa.v", i + 1), dm, dm); }
       const double fl = 4.0 * n * (double)Q * Q * dm + 2.0 * n * Q * ((double)dm * dm * 2 + 3.0 * npts * dm + 2.0 * dm * c.dec_ffn + 2.0 * dm * dm + 4.0 * dm) +
                         2.0 * n * Q * dm * c.n_levels * c.n_points * 4 + (last ? 2.0 * n * Q * dm * C : row_flops_next);
       B.push(p + ".fused", "dec_layer", fl, (double)n * Q * dm * 4 * 8, [a](hipStream_t s) { launch_dec_layer(a, s); });

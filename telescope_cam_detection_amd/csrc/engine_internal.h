@@ -23,8 +23,6 @@ using namespace rtd;
 // plans of a handle (one per batch size, built lazily) agree with each other and a later rtd_debug_option call - e.g. by another
 // test - cannot change a live handle.
 struct PlanOpts {
-  int dec_stamps = 0;   // record per-phase stamps of decoder layer 2 into debug tensor "dec_stamps"
-  int dec_split = 1;    // bf16 / f16x3 engines run the fused decoder / AIFI linears as bf16 hi/lo splits (0: fp32 MFMA, 2: bf16 filters)
   int sc_fold = 1;      // fold a block's projection shortcut into its last conv (ConvArgs::x2)
   int c1_fuse = 1;      // bf16 plans run a stage-0 block's reduce conv inside the previous block's last conv
   // self-attention on hi/lo fp16 MFMAs - bit 0 the fused AIFI layer, bit 1 decoder.  Both since round 5: with round 2's bf16 pairs AIFI's
