@@ -197,6 +197,27 @@ int64_t rtd_arena_bytes(rtd_handle h);
 int rtd_crop_resize_batch(int32_t n, const uint8_t* const* frames_dev, const int32_t* frame_hw, const int32_t* rects,
                           int32_t out_size, const float* mean3, const float* std3, float* out_dev, void* stream);
 
+/* ---- Empty-frame filter: a motion gate ahead of detection (the reference's src/empty_frame_filter.py, config key
+ * performance.empty_frame_filter) --------------------------------------------------------------------------------------------------
+ * Per frame, exactly as EmptyFrameFilter.has_motion computes it with OpenCV on 8-bit frames (restated in tests/motion_ref.py):
+ * BGR2GRAY, GaussianBlur(k x k, sigma 0) on OpenCV's bit-exact fixed-point path with BORDER_REFLECT_101,
+ * area = #{ |blurred - stored| > threshold }, and the blurred frame replaces the camera's stored one.  One fused launch covers a whole
+ * batch of frames from different cameras (csrc/motion.hip).  Independent of a detection engine: it has its own handle, which owns a
+ * non-blocking stream, a pinned staging buffer for host frames (grown on demand, one upload per call) and one state buffer per slot
+ * (allocated on the slot's first frame, reallocated on a size change; nothing is allocated on the steady path). */
+typedef struct rtd_motion* rtd_motion_handle;
+int rtd_motion_create(int32_t device, int32_t blur_size /* odd, 1..63 */, rtd_motion_handle* out);
+/* n frames (HWC uint8, C = 1 or 3, host or device pointers), slots[i] = the camera's state slot (>= 0);
+ * area[i] receives the count above, or -1 for a first frame (new slot, reset, size change).  threshold is the integer one (the caller
+ * floors a fractional threshold; < 0 counts every pixel, >= 255 none).
+ * Synchronous: returns when area[] is on the host.  Two frames with the same slot in one call are applied in order. */
+int rtd_motion_check(rtd_motion_handle m, int32_t n, const uint8_t* const* frames, const int32_t* hwc /* [n][3] */,
+                     int32_t frames_on_device, const int32_t* slots, int32_t threshold, int64_t* area);
+int rtd_motion_reset(rtd_motion_handle m, int32_t slot /* -1 = all */);   /* the slot's next frame is a first frame */
+int rtd_motion_wait_stream(rtd_motion_handle m, void* producer_stream);   /* as rtd_wait_stream */
+const char* rtd_motion_last_error(rtd_motion_handle m);                  /* m may be NULL: last error of a failed rtd_motion_create */
+void rtd_motion_destroy(rtd_motion_handle m);
+
 #ifdef __cplusplus
 }
 #endif

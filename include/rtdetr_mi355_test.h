@@ -98,6 +98,10 @@ int rtd_bench_conv(int dtype, int B, int H, int W, int Cin, int Cout, int KH, in
  * (s_memtime per s_memrealtime), out[2] = kernel milliseconds.  ~`ms_target` milliseconds of work per timed launch (3 launches). */
 int rtd_bench_mfma_rate(int random_operands, int ms_target, float* out);
 
+/* the blurred frame a motion slot holds (rows x cols uint8), copied to the host: what the bit-exactness tests compare with
+ * tests/motion_ref.py.  RTD_E_STATE when the slot holds none (reset); implemented in csrc/motion.hip. */
+int rtd_debug_motion_state(rtd_motion_handle m, int32_t slot, uint8_t* out, size_t nbytes);
+
 #ifdef __cplusplus
 }
 #endif

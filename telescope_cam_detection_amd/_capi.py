@@ -105,12 +105,13 @@ EXPORTS = [
     "rtd_version", "rtd_create", "rtd_load_weights", "rtd_infer", "rtd_infer_raw", "rtd_infer_async", "rtd_collect", "rtd_prepare",
     "rtd_result_block", "rtd_sync", "rtd_stream", "rtd_wait_stream", "rtd_signal_stream", "rtd_get_stats", "rtd_arena_bytes", "rtd_destroy",
     "rtd_last_error", "rtd_crop_resize_batch", "rtd_self_check", "rtd_preprocess",
+    "rtd_motion_create", "rtd_motion_check", "rtd_motion_reset", "rtd_motion_wait_stream", "rtd_motion_last_error", "rtd_motion_destroy",
 ]
 # every symbol include/rtdetr_mi355_test.h declares: kernel-level test / bench / debug entry points (csrc/testapi.hip)
 TEST_EXPORTS = [
     "rtd_debug_tensor", "rtd_debug_force_topk", "rtd_profile", "rtd_debug_option", "rtd_op_conv", "rtd_op_conv_dual", "rtd_op_conv_next",
     "rtd_op_layernorm", "rtd_op_attention", "rtd_op_msdeform", "rtd_op_topk", "rtd_op_resize", "rtd_bench_conv", "rtd_bench_conv_pair",
-    "rtd_bench_mfma_rate",
+    "rtd_bench_mfma_rate", "rtd_debug_motion_state",
 ]
 
 
@@ -183,6 +184,16 @@ def lib() -> C.CDLL:
     if hasattr(L, "rtd_bench_mfma_rate"):      # (absent from older builds loaded through RTD_LIB_PATH)
         L.rtd_bench_mfma_rate.argtypes = [i32, i32, C.POINTER(f32)]
     L.rtd_crop_resize_batch.argtypes = [i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(f32), C.POINTER(f32), vp, vp]
+    if hasattr(L, "rtd_motion_create"):        # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_motion_create.argtypes = [i32, i32, C.POINTER(vp)]
+        L.rtd_motion_check.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), i32, C.POINTER(i32), i32, C.POINTER(i64)]
+        L.rtd_motion_reset.argtypes = [vp, i32]
+        L.rtd_motion_wait_stream.argtypes = [vp, vp]
+        L.rtd_motion_last_error.argtypes = [vp]
+        L.rtd_motion_last_error.restype = C.c_char_p
+        L.rtd_motion_destroy.argtypes = [vp]
+        L.rtd_motion_destroy.restype = None
+        L.rtd_debug_motion_state.argtypes = [vp, i32, vp, C.c_size_t]
     _lib = L
     return L
 

@@ -182,8 +182,12 @@ class BatchCoordinator:
     coordinator stopped before it ran."""
 
     def __init__(self, detector: Any, max_batch_size: int = 4, max_batch_wait_ms: float = 10.0,
-                 enable_metrics: bool = True, max_queue_depth: int = 60, extra_detectors: Optional[List[Any]] = None):
+                 enable_metrics: bool = True, max_queue_depth: int = 60, extra_detectors: Optional[List[Any]] = None,
+                 empty_frame_filter: Any = None):
         self.detector = detector
+        # motion gate (motion.EmptyFrameFilter or anything with has_motion_batch / get_stats): each batch is checked once, by camera_id,
+        # right after it is cut; only its moving frames reach a detector, the static ones are answered [] in submission order
+        self.empty_frame_filter = empty_frame_filter
         self.detectors: List[Any] = [detector] + list(extra_detectors or [])
         self.max_batch_size = int(max_batch_size)
         self.max_batch_wait_ms = max_batch_wait_ms / 1000.0          # seconds (the reference keeps the converted value under this name)
@@ -193,7 +197,7 @@ class BatchCoordinator:
         self.dropped_frames = 0
         self._inbox = _Inbox(self.max_queue_depth)
         self._lanes = [_Lane(d) for d in self.detectors]
-        self._flying: deque = deque()                                # (lane, asks, t_begin) in submission order
+        self._flying: deque = deque()                                # (lane or None, asks, t_begin, moving mask) in submission order
         self._flying_cv = threading.Condition()
         self._threads: List[threading.Thread] = []
         # failures: counted, and the FIRST one kept verbatim (the reference answers [] and logs; a silent "no detections" must be visible)
@@ -270,23 +274,46 @@ class BatchCoordinator:
             if not asks:
                 lane.idle.release()
                 continue
-            turn = (turn + 1) % len(self._lanes)
             t_begin = time.monotonic()
+            mask = self._gate(asks)
+            moving = [a for a, m in zip(asks, mask) if m]
+            if not moving:
+                # nothing moved: the lane goes back at once, and the batch still queues behind the ones in flight, so that its []
+                # answers cannot overtake an earlier batch of the same camera
+                lane.idle.release()
+                with self._flying_cv:
+                    self._flying.append((None, asks, t_begin, mask))
+                    self._flying_cv.notify()
+                continue
+            turn = (turn + 1) % len(self._lanes)
             if self.enable_metrics:
-                self.wait_times_ms.extend((t_begin - a.t_in) * 1000.0 for a in asks)
+                self.wait_times_ms.extend((t_begin - a.t_in) * 1000.0 for a in moving)
             try:
-                lane.begin([a.frame for a in asks])
+                lane.begin([a.frame for a in moving])
             except Exception as e:
-                self._note_failure("begin", e, len(asks))
+                self._note_failure("begin", e, len(moving))
                 lane.failed(e)
                 lane.idle.release()
-                logger.error(f"batch coordinator: could not start a batch of {len(asks)}: {e}", exc_info=True)
+                logger.error(f"batch coordinator: could not start a batch of {len(moving)}: {e}", exc_info=True)
                 for a in asks:
                     a.reply([])
                 continue
             with self._flying_cv:
-                self._flying.append((lane, asks, t_begin))
+                self._flying.append((lane, asks, t_begin, mask))
                 self._flying_cv.notify()
+
+    def _gate(self, asks: List[_Ask]) -> List[bool]:
+        """Which frames of the batch go to the detector: all of them without a filter, or when the filter fails (served unfiltered)."""
+        if self.empty_frame_filter is None:
+            return [True] * len(asks)
+        try:
+            mask = [bool(m) for m in self.empty_frame_filter.has_motion_batch([a.frame for a in asks], [a.camera_id for a in asks])]
+            if len(mask) == len(asks):
+                return mask
+            raise RuntimeError(f"the filter returned {len(mask)} decisions for {len(asks)} frames")
+        except Exception as e:
+            logger.error(f"batch coordinator: empty-frame filter failed, batch served unfiltered: {e}")
+            return [True] * len(asks)
 
     def _finish(self):
         while True:
@@ -298,32 +325,38 @@ class BatchCoordinator:
                         self._flying_cv.wait(0.02)
                         continue
                     return
-                lane, asks, t_begin = self._flying.popleft()
+                lane, asks, t_begin, mask = self._flying.popleft()
+            if lane is None:                                          # a batch the filter found static throughout
+                for a in asks:
+                    a.reply([])
+                continue
+            n_run = sum(mask)
             failed = False
             try:
                 results = list(lane.finish())
             except Exception as e:
-                self._note_failure("finish", e, len(asks))
+                self._note_failure("finish", e, n_run)
                 lane.failed(e)
-                logger.error(f"batch coordinator: batch of {len(asks)} failed: {e}", exc_info=True)
-                results = [[] for _ in asks]
+                logger.error(f"batch coordinator: batch of {n_run} failed: {e}", exc_info=True)
+                results = [[] for _ in range(n_run)]
                 failed = True
             else:
                 lane.succeeded()
-                if len(results) != len(asks):
+                if len(results) != n_run:
                     # the reference pairs requests and results with zip (src/shared_inference_coordinator.py:253): the leading
                     # requests get their lists; here the ones left over are answered too (with []), and the miscount is on record
-                    self._note_failure("finish", RuntimeError(f"detector returned {len(results)} results for {len(asks)} frames"), 0)
-                    logger.error(f"batch coordinator: detector returned {len(results)} results for {len(asks)} frames")
-                    results = results[:len(asks)] + [[] for _ in range(len(asks) - len(results))]
+                    self._note_failure("finish", RuntimeError(f"detector returned {len(results)} results for {n_run} frames"), 0)
+                    logger.error(f"batch coordinator: detector returned {len(results)} results for {n_run} frames")
+                    results = results[:n_run] + [[] for _ in range(n_run - len(results))]
             # every callback of the batch has fired before the lane is handed back: the next batch reaches the detector afterwards
-            for a, dets in zip(asks, results):
-                a.reply(dets)
+            it = iter(results)
+            for a, m in zip(asks, mask):
+                a.reply(next(it) if m else [])
             if self.enable_metrics and not failed:
                 self.total_batches += 1
-                self.total_frames += len(asks)
+                self.total_frames += n_run
                 self.total_batch_time_ms += (time.monotonic() - t_begin) * 1000.0
-                self.batch_sizes.append(len(asks))
+                self.batch_sizes.append(n_run)
             lane.idle.release()
 
     def _note_failure(self, where: str, e: BaseException, n_frames: int) -> None:
@@ -339,10 +372,13 @@ class BatchCoordinator:
                 "detector_rebuild_seconds": round(sum(l.rebuild_seconds for l in self._lanes), 3)}
 
     def get_stats(self) -> Dict[str, Any]:
+        # the filter's counts under the key the reference's engine reports them (src/inference_engine_yolox.py:782-783)
+        gate = {"empty_frame_filter": self.empty_frame_filter.get_stats()} if self.empty_frame_filter is not None else {}
         if not self.enable_metrics or self.total_batches == 0:
-            return {"enabled": False, "total_batches": 0, "total_frames": 0, **self.failure_stats()}
+            return {"enabled": False, "total_batches": 0, "total_frames": 0, **self.failure_stats(), **gate}
         busy_s = self.total_batch_time_ms / 1000.0
         return {
+            **gate,
             **self.failure_stats(),
             "enabled": True,
             "total_batches": self.total_batches,
@@ -407,8 +443,9 @@ def make_rtdetr_coordinator(config: Dict[str, Any], coordinator_cls=None, detect
         if not detector.load_model():
             logger.error("Failed to load RT-DETR detector for coordinator")
             return None
+        gate = _make_filter(config, detector)
+        extra = []
         if depth > 1:
-            extra = []
             for _ in range(depth - 1):
                 d2 = detector_cls(config_path=detector.config_path, model_path=detector.model_path, device=detector.device,
                                   conf_threshold=detector.conf_threshold, input_size=detector.input_size,
@@ -418,15 +455,32 @@ def make_rtdetr_coordinator(config: Dict[str, Any], coordinator_cls=None, detect
                     extra = []
                     break
                 extra.append(d2)
-            if extra:       # the pipeline is a feature of this build's coordinator, whatever class was asked for
-                return BatchCoordinator(detector=detector, max_batch_size=max_batch,
-                                        max_batch_wait_ms=batching.get("max_batch_wait_ms", 10.0),
-                                        enable_metrics=batching.get("enable_metrics", True), extra_detectors=extra)
+        if extra or gate is not None:   # the pipeline and the motion gate are features of this build's coordinator, whatever class was asked for
+            return BatchCoordinator(detector=detector, max_batch_size=max_batch,
+                                    max_batch_wait_ms=batching.get("max_batch_wait_ms", 10.0),
+                                    enable_metrics=batching.get("enable_metrics", True), extra_detectors=extra,
+                                    empty_frame_filter=gate)
         return coordinator_cls(detector=detector, max_batch_size=max_batch,
                                max_batch_wait_ms=batching.get("max_batch_wait_ms", 10.0),
                                enable_metrics=batching.get("enable_metrics", True))
     except Exception as e:
         logger.error(f"Failed to initialize shared coordinator: {e}")
+        return None
+
+
+def _make_filter(config: Dict[str, Any], detector):
+    """The reference's own key `performance.empty_frame_filter` (fields and defaults of src/inference_engine_yolox.py:148-153), which
+    its coordinator path ignores: here the filter gates every batch.  None when absent / disabled, or when it cannot be built (logged:
+    the coordinator then serves unfiltered)."""
+    cfg = (config.get("performance") or {}).get("empty_frame_filter") or {}
+    if not cfg.get("enabled", False):
+        return None
+    try:
+        from .motion import EmptyFrameFilter
+        return EmptyFrameFilter(min_motion_area=cfg.get("min_motion_area", 200), threshold=cfg.get("threshold", 25),
+                                blur_size=cfg.get("blur_size", 21), device=getattr(detector, "device", None))
+    except Exception as e:
+        logger.error(f"Failed to build the empty-frame filter, serving unfiltered: {e}")
         return None
 
 

@@ -1,0 +1,394 @@
+// motion.hip - the empty-frame filter (the reference's src/empty_frame_filter.py) as one fused launch per batch of camera frames.
+//
+// Per frame: BGR -> gray (OpenCV's 14-bit fixed point), k x k Gaussian blur on OpenCV's bit-exact 8-bit path (ufixedpoint16 taps, exact
+// integer row pass, column pass rounded once), |blur - stored| > threshold counted, the stored blurred frame replaced in place.  The
+// restatement the results must equal bit for bit is tests/motion_ref.py; it lists the arithmetic.
+//
+// Work split: a flattened list of 64 x 32 output tiles over all frames of the call (frames may differ in size).  A workgroup loads its
+// tile plus a halo of the kernel radius once (reflect-101 at the frame edges) and converts it to gray in LDS, runs the row pass into a
+// uint16 LDS tile and the column pass in registers, compares with and overwrites the camera's stored frame at its own output pixels
+// only (so the in-place update is race-free), and adds its count to the frame's counter with one global atomic.
+#include <algorithm>
+#include <cmath>
+#include <map>
+#include <mutex>
+#include <new>
+
+#include "../../include/rtdetr_mi355.h"
+#include "../../include/rtdetr_mi355_test.h"
+#include "common.h"
+
+namespace motion_gate {
+
+using rtd::Error;
+
+constexpr int TW = 64, TH = 32;            // output tile
+constexpr int MAX_R = 31;                  // k <= 63
+constexpr int THREADS = 256;
+constexpr int ROWS_PER_THREAD = TH / (THREADS / TW);   // column pass: 8 output rows per thread
+
+struct FrameDesc {
+  const uint8_t* src;     // HWC, C = 1 or 3
+  uint8_t* state;         // rows x cols stored blurred frame (read, then overwritten)
+  int rows, cols, ch;
+  int first;              // 1: no stored frame to compare with - blur and store only
+  int tiles_x;
+  int tile0;              // first tile of this frame in the flattened list
+};
+
+struct Taps {
+  int radius;
+  uint16_t c[2 * MAX_R + 1];
+};
+
+// borderInterpolate(p, n, BORDER_REFLECT_101), reflecting repeatedly (a frame shorter than the radius)
+__device__ __forceinline__ int reflect101(int p, int n) {
+  if (n == 1) return 0;
+  while ((unsigned)p >= (unsigned)n) p = p < 0 ? -p : 2 * (n - 1) - p;
+  return p;
+}
+
+// One instantiation per radius: the tap loops unroll, the taps stay in scalar registers and the LDS tiles are sized to the halo.
+template <int R>
+__global__ void __launch_bounds__(THREADS) motion_kernel(const FrameDesc* __restrict__ descs, int n_frames, Taps taps, int threshold,
+                                                          unsigned int* __restrict__ area) {
+  constexpr int k = 2 * R + 1, gw = TW + 2 * R, gh = TH + 2 * R;
+  __shared__ uint8_t gray[gh * gw];
+  __shared__ uint16_t rowp[gh * TW];
+  __shared__ unsigned int block_count;
+
+  // which frame: the last one whose first tile is <= this block (binary search over the descriptors)
+  const int tile = blockIdx.x;
+  int lo = 0, hi = n_frames - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (descs[mid].tile0 <= tile) lo = mid; else hi = mid - 1;
+  }
+  const FrameDesc d = descs[lo];
+  const int t = tile - d.tile0;
+  const int x0 = (t % d.tiles_x) * TW, y0 = (t / d.tiles_x) * TH;
+  const int tid = threadIdx.x;
+  uint32_t cs[k];
+#pragma unroll
+  for (int j = 0; j < k; ++j) cs[j] = taps.c[j];
+  if (tid == 0) block_count = 0;
+
+  // 1. tile + halo -> gray (LDS)
+  for (int i = tid; i < gh * gw; i += THREADS) {
+    const int gy = i / gw, gx = i - gy * gw;
+    const int sy = reflect101(y0 - R + gy, d.rows), sx = reflect101(x0 - R + gx, d.cols);
+    const uint8_t* p = d.src + ((size_t)sy * d.cols + sx) * d.ch;
+    uint32_t y;
+    if (d.ch == 3) y = (1868u * p[0] + 9617u * p[1] + 4899u * p[2] + 8192u) >> 14;
+    else y = p[0];
+    gray[gy * gw + gx] = (uint8_t)y;
+  }
+  __syncthreads();
+
+  // 2. row pass: R = sum_j c_j Y[x + j], exact (<= 255 * 256)
+  {
+    const int tx = tid % TW;
+    for (int gy = tid / TW; gy < gh; gy += THREADS / TW) {
+      const uint8_t* g = gray + gy * gw + tx;
+      uint32_t acc = 0;
+#pragma unroll
+      for (int j = 0; j < k; ++j) acc += cs[j] * g[j];
+      rowp[gy * TW + tx] = (uint16_t)acc;
+    }
+  }
+  __syncthreads();
+
+  // 3. column pass in registers, compare, store, count
+  const int tx = tid % TW, ty0 = (tid / TW) * ROWS_PER_THREAD;
+  const int x = x0 + tx;
+  unsigned int count = 0;
+#pragma unroll
+  for (int j = 0; j < ROWS_PER_THREAD; ++j) {
+    const int ty = ty0 + j, y = y0 + ty;
+    const uint16_t* rp = rowp + ty * TW + tx;
+    uint32_t acc = 0;
+#pragma unroll
+    for (int i = 0; i < k; ++i) acc += cs[i] * rp[i * TW];
+    const int v = (int)((acc + 32768u) >> 16);           // <= 255: the taps sum to 256, both passes together to 65536
+    bool moved = false;
+    if (x < d.cols && y < d.rows) {
+      uint8_t* s = d.state + (size_t)y * d.cols + x;
+      if (!d.first) moved = abs(v - (int)*s) > threshold;
+      *s = (uint8_t)v;
+    }
+    count += (unsigned int)__popcll(__ballot(moved));   // wave-uniform
+  }
+  if ((tid & 63) == 0 && count) atomicAdd(&block_count, count);
+  __syncthreads();
+  if (tid == 0 && block_count) atomicAdd(area + lo, block_count);
+}
+
+template <int R>
+static void launch_radius(int r, dim3 grid, hipStream_t s, const FrameDesc* descs, int n, const Taps& taps, int threshold, unsigned int* area) {
+  if (r == R) {
+    rtd::rtd_launch(motion_kernel<R>, grid, dim3(THREADS), 0, s, descs, n, taps, threshold, area);   // the library's one launch path
+    return;
+  }
+  if constexpr (R < MAX_R) launch_radius<R + 1>(r, grid, s, descs, n, taps, threshold, area);
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------------------
+struct Slot {
+  uint8_t* buf = nullptr;
+  int rows = 0, cols = 0;
+  bool valid = false;       // holds a blurred frame to compare with
+};
+
+static std::string g_motion_create_error;
+
+static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+
+}  // namespace motion_gate
+
+using namespace motion_gate;
+
+struct rtd_motion {
+  int device = 0;
+  Taps taps{};
+  hipStream_t stream = nullptr;
+  hipEvent_t ev_xs = nullptr;
+  std::mutex mu;
+  std::string err;
+  std::map<int, Slot> slots;
+  // one upload per launch: [descriptors | area counters | host frames]; pinned on the host, mirrored on the device, grown on demand
+  uint8_t* pin = nullptr;
+  uint8_t* dev = nullptr;
+  size_t cap = 0;
+};
+
+namespace motion_gate {
+
+// taps of GaussianBlur(k, sigma = 0) on 8-bit input (tests/motion_ref.py taps(): fixed tables up to k = 7, error-diffused rounding above)
+static void make_taps(int k, Taps& t) {
+  static const uint16_t fixed[4][7] = {{256}, {64, 128, 64}, {16, 64, 96, 64, 16}, {8, 28, 56, 72, 56, 28, 8}};
+  t.radius = k / 2;
+  if (k <= 7) {
+    for (int i = 0; i < k; ++i) t.c[i] = fixed[k / 2][i];
+    return;
+  }
+  const double sigma = 0.15 * k + 0.35;
+  std::vector<double> g(k);
+  double sum = 0;
+  for (int i = 0; i < k; ++i) {
+    const double xx = i - (k - 1) / 2.0;
+    g[i] = std::exp(-(xx * xx) / (2.0 * sigma * sigma));
+    sum += g[i];
+  }
+  double e = 0;
+  int off = 0;
+  for (int i = 0; i < k / 2; ++i) {
+    const double adj = 256.0 * (g[i] / sum) + e;
+    const int v = (int)std::nearbyint(adj);         // round half to even (the default rounding mode), like cvRound
+    e = adj - v;
+    t.c[i] = t.c[k - 1 - i] = (uint16_t)v;
+    off += v;
+  }
+  t.c[k / 2] = (uint16_t)(256 - 2 * off);
+}
+
+template <typename F>
+static int guarded(rtd_motion* m, F&& f) {
+  if (!m) return RTD_E_INVALID;
+  std::lock_guard<std::mutex> lk(m->mu);
+  try {
+    f();
+    return RTD_OK;
+  } catch (const Error& er) {
+    m->err = er.what();
+    return er.code;
+  } catch (const std::bad_alloc&) {
+    m->err = "host allocation failed";
+    return RTD_E_OOM;
+  } catch (const std::exception& ex) {
+    m->err = ex.what();
+    return RTD_E_HIP;
+  }
+}
+
+static void reserve(rtd_motion* m, size_t bytes) {
+  if (bytes <= m->cap) return;
+  const size_t cap = std::max(bytes, m->cap * 2);
+  if (m->pin) (void)hipHostFree(m->pin);
+  if (m->dev) (void)hipFree(m->dev);
+  m->pin = nullptr;
+  m->dev = nullptr;
+  m->cap = 0;
+  HIP_CHECK(hipHostMalloc((void**)&m->pin, cap, hipHostMallocDefault));
+  HIP_CHECK(hipMalloc((void**)&m->dev, cap));
+  m->cap = cap;
+}
+
+// one launch over frames [b, e) of the call, whose slots are all distinct
+static void launch(rtd_motion* m, int b, int e, const uint8_t* const* frames, const int32_t* hwc, int on_device, const int32_t* slots,
+                   int threshold, int64_t* area) {
+  const int n = e - b;
+  const size_t area_off = align_up(sizeof(FrameDesc) * n, 256);
+  const size_t frames_off = align_up(area_off + sizeof(unsigned int) * n, 256);
+  size_t total = frames_off;
+  std::vector<size_t> foff(n);
+  for (int i = 0; i < n; ++i) {
+    const int32_t* s = hwc + 3 * (b + i);
+    foff[i] = total;
+    if (!on_device) total = align_up(total + (size_t)s[0] * s[1] * s[2], 256);
+  }
+  reserve(m, total);
+  FrameDesc* descs = (FrameDesc*)m->pin;
+  int tiles = 0;
+  std::vector<char> first(n);
+  for (int i = 0; i < n; ++i) {
+    const int32_t* s = hwc + 3 * (b + i);
+    Slot& sl = m->slots[slots[b + i]];
+    const bool resized = sl.buf && (sl.rows != s[0] || sl.cols != s[1]);
+    first[i] = !sl.valid || resized;
+    if (resized) {                                       // a new size: a new state buffer (the old one is not read again)
+      HIP_CHECK(hipFree(sl.buf));
+      sl.buf = nullptr;
+      sl.valid = false;
+    }
+    if (!sl.buf) {
+      HIP_CHECK(hipMalloc((void**)&sl.buf, (size_t)s[0] * s[1]));
+      sl.rows = s[0];
+      sl.cols = s[1];
+    }
+    FrameDesc& d = descs[i];
+    d.src = on_device ? frames[b + i] : m->dev + foff[i];
+    d.state = sl.buf;
+    d.rows = s[0];
+    d.cols = s[1];
+    d.ch = s[2];
+    d.first = first[i] ? 1 : 0;
+    d.tiles_x = (s[1] + TW - 1) / TW;
+    d.tile0 = tiles;
+    tiles += d.tiles_x * ((s[0] + TH - 1) / TH);
+    if (!on_device) memcpy(m->pin + foff[i], frames[b + i], (size_t)s[0] * s[1] * s[2]);
+  }
+  memset(m->pin + area_off, 0, sizeof(unsigned int) * n);
+  HIP_CHECK(hipMemcpyAsync(m->dev, m->pin, total, hipMemcpyHostToDevice, m->stream));
+  launch_radius<0>(m->taps.radius, dim3(tiles), m->stream, (const FrameDesc*)m->dev, n, m->taps, threshold,
+                   (unsigned int*)(m->dev + area_off));
+  HIP_CHECK(hipGetLastError());
+  // the counters come back through the start of the pinned buffer (the descriptors there are no longer needed)
+  HIP_CHECK(hipMemcpyAsync(m->pin, m->dev + area_off, sizeof(unsigned int) * n, hipMemcpyDeviceToHost, m->stream));
+  HIP_CHECK(hipStreamSynchronize(m->stream));
+  const unsigned int* got = (const unsigned int*)m->pin;
+  for (int i = 0; i < n; ++i) {
+    area[b + i] = first[i] ? -1 : (int64_t)got[i];
+    m->slots[slots[b + i]].valid = true;
+  }
+}
+
+}  // namespace motion_gate
+
+extern "C" {
+
+int rtd_motion_create(int32_t device, int32_t blur_size, rtd_motion_handle* out) {
+  if (!out) return RTD_E_INVALID;
+  *out = nullptr;
+  if (blur_size < 1 || blur_size > 2 * MAX_R + 1 || blur_size % 2 == 0) {
+    g_motion_create_error = "blur_size must be odd and in 1..63, got " + std::to_string(blur_size);
+    return RTD_E_INVALID;
+  }
+  rtd_motion* m = new (std::nothrow) rtd_motion();
+  if (!m) return RTD_E_OOM;
+  try {
+    int count = 0;
+    HIP_CHECK(hipGetDeviceCount(&count));
+    RTD_CHECK(device >= 0 && device < count, RTD_E_INVALID, "no such device");
+    m->device = device;
+    make_taps(blur_size, m->taps);
+    HIP_CHECK(hipSetDevice(device));
+    HIP_CHECK(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
+    HIP_CHECK(hipEventCreateWithFlags(&m->ev_xs, hipEventDisableTiming));
+  } catch (const Error& er) {
+    g_motion_create_error = er.what();
+    rtd_motion_destroy(m);
+    return er.code;
+  }
+  *out = m;
+  return RTD_OK;
+}
+
+int rtd_motion_check(rtd_motion_handle m, int32_t n, const uint8_t* const* frames, const int32_t* hwc, int32_t frames_on_device,
+                     const int32_t* slots, int32_t threshold, int64_t* area) {
+  return guarded(m, [&] {
+    RTD_CHECK(n >= 0, RTD_E_INVALID, "n must be >= 0");
+    if (n == 0) return;
+    RTD_CHECK(frames && hwc && slots && area, RTD_E_INVALID, "null argument");
+    for (int i = 0; i < n; ++i) {
+      RTD_CHECK(frames[i], RTD_E_INVALID, "frame " + std::to_string(i) + " is null");
+      RTD_CHECK(hwc[3 * i] >= 1 && hwc[3 * i + 1] >= 1 && (int64_t)hwc[3 * i] * hwc[3 * i + 1] < (1ll << 31), RTD_E_INVALID,
+                "frame " + std::to_string(i) + " has a bad size");
+      RTD_CHECK(hwc[3 * i + 2] == 1 || hwc[3 * i + 2] == 3, RTD_E_INVALID, "frames must have 1 or 3 channels");
+      RTD_CHECK(slots[i] >= 0, RTD_E_INVALID, "slots must be >= 0");
+    }
+    HIP_CHECK(hipSetDevice(m->device));
+    // a slot seen twice in one call: the later frame goes into the next launch (launches run in order on the handle's stream)
+    int b = 0;
+    while (b < n) {
+      int e = b + 1;
+      for (; e < n; ++e) {
+        bool dup = false;
+        for (int j = b; j < e && !dup; ++j) dup = slots[j] == slots[e];
+        if (dup) break;
+      }
+      try {
+        launch(m, b, e, frames, hwc, frames_on_device, slots, threshold, area);
+      } catch (...) {
+        (void)hipStreamSynchronize(m->stream);           // nothing of a failed launch may still read the staging buffers
+        throw;
+      }
+      b = e;
+    }
+  });
+}
+
+int rtd_motion_reset(rtd_motion_handle m, int32_t slot) {
+  return guarded(m, [&] {
+    RTD_CHECK(slot >= -1, RTD_E_INVALID, "slot must be >= -1");
+    for (auto& kv : m->slots)
+      if (slot < 0 || kv.first == slot) kv.second.valid = false;
+  });
+}
+
+int rtd_motion_wait_stream(rtd_motion_handle m, void* producer_stream) {
+  return guarded(m, [&] {
+    HIP_CHECK(hipSetDevice(m->device));
+    HIP_CHECK(hipEventRecord(m->ev_xs, (hipStream_t)producer_stream));
+    HIP_CHECK(hipStreamWaitEvent(m->stream, m->ev_xs, 0));
+  });
+}
+
+const char* rtd_motion_last_error(rtd_motion_handle m) { return m ? m->err.c_str() : g_motion_create_error.c_str(); }
+
+void rtd_motion_destroy(rtd_motion_handle m) {
+  if (!m) return;
+  (void)hipSetDevice(m->device);
+  if (m->stream) (void)hipStreamSynchronize(m->stream);
+  for (auto& kv : m->slots)
+    if (kv.second.buf) (void)hipFree(kv.second.buf);
+  if (m->pin) (void)hipHostFree(m->pin);
+  if (m->dev) (void)hipFree(m->dev);
+  if (m->ev_xs) (void)hipEventDestroy(m->ev_xs);
+  if (m->stream) (void)hipStreamDestroy(m->stream);
+  delete m;
+}
+
+int rtd_debug_motion_state(rtd_motion_handle m, int32_t slot, uint8_t* out, size_t nbytes) {
+  return guarded(m, [&] {
+    auto it = m->slots.find(slot);
+    RTD_CHECK(it != m->slots.end(), RTD_E_INVALID, "unknown slot");
+    const Slot& s = it->second;
+    RTD_CHECK(s.valid, RTD_E_STATE, "the slot holds no frame (reset, or never checked)");
+    RTD_CHECK(out && nbytes >= (size_t)s.rows * s.cols, RTD_E_INVALID, "output buffer too small");
+    HIP_CHECK(hipSetDevice(m->device));
+    HIP_CHECK(hipMemcpyAsync(out, s.buf, (size_t)s.rows * s.cols, hipMemcpyDeviceToHost, m->stream));
+    HIP_CHECK(hipStreamSynchronize(m->stream));
+  });
+}
+
+}  // extern "C"
