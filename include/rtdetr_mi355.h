@@ -218,6 +218,29 @@ int rtd_motion_wait_stream(rtd_motion_handle m, void* producer_stream);   /* as 
 const char* rtd_motion_last_error(rtd_motion_handle m);                  /* m may be NULL: last error of a failed rtd_motion_create */
 void rtd_motion_destroy(rtd_motion_handle m);
 
+/* ---- Motion filter: MOG2 background model and per-box motion after detection (the reference's src/motion_filter.py MotionFilter,
+ * config key motion_filter) ------------------------------------------------------------------------------------------------------------
+ * cv2.createBackgroundSubtractorMOG2(history, var_threshold, detect_shadows) with OpenCV's defaults otherwise (5 modes, background ratio
+ * 0.9, generation threshold 9, variance 15 in [4, 75], complexity reduction 0.05, shadow tau 0.5), applied to 8-bit frames as OpenCV's
+ * CPU path computes it (restated in tests/mog2_ref.py).  Per update i of a call: the model is updated with the frame and its
+ * foreground mask (shadows dropped: mask == 255) is blurred with GaussianBlur(blur_size, sigma 0) on the bit-exact 8-bit path
+ * (BORDER_REFLECT_101 at the frame edges); counts[i] = #{ blurred > 25 } inside box i.  One fused launch per chunk of 32 updates and
+ * one launch for every box of the call (csrc/mog2.hip).  Own handle with a non-blocking stream and a pinned staging buffer for host
+ * frames; the model (25 floats + 1 byte per pixel for BGR) is allocated on the first frame and reallocated on a size or channel change,
+ * which re-initialises it as OpenCV does.  Nothing is allocated on the steady path. */
+typedef struct rtd_mog2* rtd_mog2_handle;
+int rtd_mog2_create(int32_t device, int32_t history /* >= 1 */, double var_threshold, int32_t detect_shadows, rtd_mog2_handle* out);
+/* = a new subtractor with these parameters: the model is forgotten (the next update initialises it) */
+int rtd_mog2_configure(rtd_mog2_handle g, int32_t history, double var_threshold, int32_t detect_shadows);
+/* n updates of the model with one frame (HWC uint8, C = 1 or 3, host or device pointer), in order; rects = [n][4] boxes x1, y1, x2, y2
+ * already clamped to the frame (an empty box is allowed: its update happens, its count is 0); blur_size odd, 1..63.
+ * counts[i] receives the count of update i.  Synchronous: returns when counts[] is on the host.  n = 0: nothing happens. */
+int rtd_mog2_apply(rtd_mog2_handle g, const uint8_t* frame, const int32_t* hwc /* [3] */, int32_t frame_on_device, int32_t n,
+                   const int32_t* rects, int32_t blur_size, int64_t* counts);
+int rtd_mog2_wait_stream(rtd_mog2_handle g, void* producer_stream);   /* as rtd_wait_stream */
+const char* rtd_mog2_last_error(rtd_mog2_handle g);                  /* g may be NULL: last error of a failed rtd_mog2_create */
+void rtd_mog2_destroy(rtd_mog2_handle g);
+
 #ifdef __cplusplus
 }
 #endif

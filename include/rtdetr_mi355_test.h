@@ -102,6 +102,14 @@ int rtd_bench_mfma_rate(int random_operands, int ms_target, float* out);
  * tests/motion_ref.py.  RTD_E_STATE when the slot holds none (reset); implemented in csrc/motion.hip. */
 int rtd_debug_motion_state(rtd_motion_handle m, int32_t slot, uint8_t* out, size_t nbytes);
 
+/* the MOG2 model of a motion filter in a canonical layout: weight / variance [npix][5], mean [npix][5][C], modes_used [npix], with
+ * hwc[3] and nframes (the updates since the model was initialised).  hwc and nframes are always written (zeros when the filter holds no
+ * model); with all four arrays NULL nothing else is.  RTD_E_STATE when arrays are given but there is no model.  And the foreground
+ * words of the last rtd_mog2_apply, [ceil(n / 32)][npix] (bit i of chunk c: update 32 c + i marked the pixel 255).  csrc/mog2.hip. */
+int rtd_debug_mog2_model(rtd_mog2_handle g, int32_t* hwc, int64_t* nframes, float* weight, float* variance, float* mean,
+                         uint8_t* modes_used, size_t npix);
+int rtd_debug_mog2_fg_bits(rtd_mog2_handle g, uint32_t* out, size_t nwords);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,13 +17,16 @@
 #include "../../include/rtdetr_mi355.h"
 #include "../../include/rtdetr_mi355_test.h"
 #include "common.h"
+#include "gauss8.h"
 
 namespace motion_gate {
 
 using rtd::Error;
+using gauss8::MAX_R;
+using gauss8::Taps;
+using gauss8::reflect101;
 
 constexpr int TW = 64, TH = 32;            // output tile
-constexpr int MAX_R = 31;                  // k <= 63
 constexpr int THREADS = 256;
 constexpr int ROWS_PER_THREAD = TH / (THREADS / TW);   // column pass: 8 output rows per thread
 
@@ -35,18 +38,6 @@ struct FrameDesc {
   int tiles_x;
   int tile0;              // first tile of this frame in the flattened list
 };
-
-struct Taps {
-  int radius;
-  uint16_t c[2 * MAX_R + 1];
-};
-
-// borderInterpolate(p, n, BORDER_REFLECT_101), reflecting repeatedly (a frame shorter than the radius)
-__device__ __forceinline__ int reflect101(int p, int n) {
-  if (n == 1) return 0;
-  while ((unsigned)p >= (unsigned)n) p = p < 0 ? -p : 2 * (n - 1) - p;
-  return p;
-}
 
 // One instantiation per radius: the tap loops unroll, the taps stay in scalar registers and the LDS tiles are sized to the halo.
 template <int R>
@@ -69,8 +60,7 @@ __global__ void __launch_bounds__(THREADS) motion_kernel(const FrameDesc* __rest
   const int x0 = (t % d.tiles_x) * TW, y0 = (t / d.tiles_x) * TH;
   const int tid = threadIdx.x;
   uint32_t cs[k];
-#pragma unroll
-  for (int j = 0; j < k; ++j) cs[j] = taps.c[j];
+  gauss8::load_taps<R>(taps, cs);
   if (tid == 0) block_count = 0;
 
   // 1. tile + halo -> gray (LDS)
@@ -86,16 +76,7 @@ __global__ void __launch_bounds__(THREADS) motion_kernel(const FrameDesc* __rest
   __syncthreads();
 
   // 2. row pass: R = sum_j c_j Y[x + j], exact (<= 255 * 256)
-  {
-    const int tx = tid % TW;
-    for (int gy = tid / TW; gy < gh; gy += THREADS / TW) {
-      const uint8_t* g = gray + gy * gw + tx;
-      uint32_t acc = 0;
-#pragma unroll
-      for (int j = 0; j < k; ++j) acc += cs[j] * g[j];
-      rowp[gy * TW + tx] = (uint16_t)acc;
-    }
-  }
+  gauss8::row_pass<R, TW, THREADS>(gray, gh, rowp, cs);
   __syncthreads();
 
   // 3. column pass in registers, compare, store, count
@@ -105,11 +86,7 @@ __global__ void __launch_bounds__(THREADS) motion_kernel(const FrameDesc* __rest
 #pragma unroll
   for (int j = 0; j < ROWS_PER_THREAD; ++j) {
     const int ty = ty0 + j, y = y0 + ty;
-    const uint16_t* rp = rowp + ty * TW + tx;
-    uint32_t acc = 0;
-#pragma unroll
-    for (int i = 0; i < k; ++i) acc += cs[i] * rp[i * TW];
-    const int v = (int)((acc + 32768u) >> 16);           // <= 255: the taps sum to 256, both passes together to 65536
+    const int v = gauss8::col_pass<R, TW>(rowp + ty * TW + tx, cs);
     bool moved = false;
     if (x < d.cols && y < d.rows) {
       uint8_t* s = d.state + (size_t)y * d.cols + x;
@@ -162,34 +139,6 @@ struct rtd_motion {
 };
 
 namespace motion_gate {
-
-// taps of GaussianBlur(k, sigma = 0) on 8-bit input (tests/motion_ref.py taps(): fixed tables up to k = 7, error-diffused rounding above)
-static void make_taps(int k, Taps& t) {
-  static const uint16_t fixed[4][7] = {{256}, {64, 128, 64}, {16, 64, 96, 64, 16}, {8, 28, 56, 72, 56, 28, 8}};
-  t.radius = k / 2;
-  if (k <= 7) {
-    for (int i = 0; i < k; ++i) t.c[i] = fixed[k / 2][i];
-    return;
-  }
-  const double sigma = 0.15 * k + 0.35;
-  std::vector<double> g(k);
-  double sum = 0;
-  for (int i = 0; i < k; ++i) {
-    const double xx = i - (k - 1) / 2.0;
-    g[i] = std::exp(-(xx * xx) / (2.0 * sigma * sigma));
-    sum += g[i];
-  }
-  double e = 0;
-  int off = 0;
-  for (int i = 0; i < k / 2; ++i) {
-    const double adj = 256.0 * (g[i] / sum) + e;
-    const int v = (int)std::nearbyint(adj);         // round half to even (the default rounding mode), like cvRound
-    e = adj - v;
-    t.c[i] = t.c[k - 1 - i] = (uint16_t)v;
-    off += v;
-  }
-  t.c[k / 2] = (uint16_t)(256 - 2 * off);
-}
 
 template <typename F>
 static int guarded(rtd_motion* m, F&& f) {
@@ -300,7 +249,7 @@ int rtd_motion_create(int32_t device, int32_t blur_size, rtd_motion_handle* out)
     HIP_CHECK(hipGetDeviceCount(&count));
     RTD_CHECK(device >= 0 && device < count, RTD_E_INVALID, "no such device");
     m->device = device;
-    make_taps(blur_size, m->taps);
+    gauss8::make_taps(blur_size, m->taps);
     HIP_CHECK(hipSetDevice(device));
     HIP_CHECK(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
     HIP_CHECK(hipEventCreateWithFlags(&m->ev_xs, hipEventDisableTiming));
