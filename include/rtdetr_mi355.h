@@ -241,6 +241,28 @@ int rtd_mog2_wait_stream(rtd_mog2_handle g, void* producer_stream);   /* as rtd_
 const char* rtd_mog2_last_error(rtd_mog2_handle g);                  /* g may be NULL: last error of a failed rtd_mog2_create */
 void rtd_mog2_destroy(rtd_mog2_handle g);
 
+/* ---- JPEG encoder for device-resident frames (the reference's cv2.imencode('.jpg', ...) in src/snapshot_saver.py add_frame_to_buffer
+ * and the MJPEG loop of src/web_server.py) -----------------------------------------------------------------------------------------------
+ * Baseline sequential JPEG (SOF0, one scan, 8-bit; BGR frames as YCbCr 4:2:0, one-channel frames as gray), standard Huffman tables,
+ * IJG quality scaling, JFIF APP0: byte for byte the file libjpeg writes at its defaults for a quality alone, which is what cv2.imencode
+ * with IMWRITE_JPEG_QUALITY and Pillow's save(..., "JPEG", quality=q) produce (restated in tests/jpeg_ref.py).  The transform, the
+ * Huffman coding and the byte stuffing run on the device (csrc/jpeg.hip); the host writes the markers.  Own handle with a non-blocking
+ * stream, a pinned staging buffer and device buffers grown on demand: no device or pinned allocation on the steady path (a call makes
+ * a few small host vectors; the marker block of a frame shape and quality is built once per handle).  Calls on one handle are
+ * serialised by the handle.  Frames are at most 65535 pixels per side and 16 Mpixel each. */
+typedef struct rtd_jpeg* rtd_jpeg_handle;
+int rtd_jpeg_create(int32_t device, rtd_jpeg_handle* out);
+/* n frames (HWC uint8, C = 1 or 3 = BGR; host or device pointers) -> n complete JPEG files, back to back in out (HOST memory,
+ * capacity out_cap bytes); offsets[n+1] receives where each file starts and the total.  RTD_E_INVALID with the needed size in
+ * offsets[n] when out_cap is too small (the call may be repeated; out may then be NULL).  The size is known only after the frames
+ * have been coded, so such a call costs a whole encode except the copy of the bytes: size out for the largest batch once (a 1080p
+ * frame at quality 90 takes about 0.5 MB) rather than asking every time.  quality 1..100.  Synchronous. */
+int rtd_jpeg_encode(rtd_jpeg_handle j, int32_t n, const uint8_t* const* frames, const int32_t* hwc /* [n][3] */,
+                    int32_t frames_on_device, int32_t quality, uint8_t* out, int64_t out_cap, int64_t* offsets);
+int rtd_jpeg_wait_stream(rtd_jpeg_handle j, void* producer_stream);   /* as rtd_wait_stream */
+const char* rtd_jpeg_last_error(rtd_jpeg_handle j);                  /* j may be NULL: last error of a failed rtd_jpeg_create */
+void rtd_jpeg_destroy(rtd_jpeg_handle j);
+
 #ifdef __cplusplus
 }
 #endif

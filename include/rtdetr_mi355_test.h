@@ -110,6 +110,11 @@ int rtd_debug_mog2_model(rtd_mog2_handle g, int32_t* hwc, int64_t* nframes, floa
                          uint8_t* modes_used, size_t npix);
 int rtd_debug_mog2_fg_bits(rtd_mog2_handle g, uint32_t* out, size_t nwords);
 
+/* the quantised coefficients of the last rtd_jpeg_encode: int16 [blocks][64] in zig-zag order, the blocks of all frames in scan order
+ * (gray: raster order; BGR: per MCU Y00 Y01 Y10 Y11 Cb Cr) - locates a byte mismatch before the entropy coder (tests/jpeg_ref.py
+ * coefficients).  *count receives the number of int16 values; out may be NULL to ask for it.  csrc/jpeg.hip. */
+int rtd_debug_jpeg_coefficients(rtd_jpeg_handle j, int16_t* out, int64_t capacity, int64_t* count);
+
 #ifdef __cplusplus
 }
 #endif
