@@ -91,6 +91,13 @@ const HostTensor& host_tensor(rtd_engine* e, const std::string& name) {
   return it->second;
 }
 
+// device copy of `bytes` host bytes, owned by the handle
+void* upload(rtd_engine* e, const void* host, size_t bytes) {
+  void* d = e->dmalloc(bytes);
+  if (bytes) HIP_CHECK(hipMemcpy(d, host, bytes, hipMemcpyHostToDevice));
+  return d;
+}
+
 // host [Npad][Kcols] fp32 (zero padded) -> device filter in dt: fp32 as is, bf16 rounded, F16X2 as [32 hi | 32 lo] groups along K
 // (Kcols % 32 == 0: a row has 2 * Kcols bf16 elements, the layout of an activation pixel with Kcols channels)
 static const char* dt_tag(int dt) { return dt == BF16 ? "#bf16" : (dt == F16X2 ? "#f16x2" : "#f32"); }
@@ -124,59 +131,53 @@ static void* upload_filter(rtd_engine* e, const std::vector<float>& pad, int Npa
   return out;
 }
 
-// filter [N][K] fp32 -> device [Npad][Kpad] in dt (zero padded), bias -> fp32 [Npad]
-DevWeight get_weight(rtd_engine* e, const std::string& name, int dt, int N, int K) {
-  const std::string key = name + dt_tag(dt);
-  auto it = e->wcache.find(key);
-  if (it != e->wcache.end()) return it->second;
+// one filter of a conv, or one of the two a conv reads side by side: blob tensors `name`.w [N][K] and `name`.b [N]
+struct FilterSeg { std::string name; int K; };
+
+static const float* host_filter(rtd_engine* e, const std::string& name, int N, int K) {
   const HostTensor& w = host_tensor(e, name + ".w");
-  const HostTensor& b = host_tensor(e, name + ".b");
   RTD_CHECK(!w.shape.empty() && w.shape[0] == N && w.numel() == (int64_t)N * K, RTD_E_WEIGHTS, "weight shape mismatch: " + name);
-  RTD_CHECK(b.numel() == N, RTD_E_WEIGHTS, "bias shape mismatch: " + name);
+  return w.data;
+}
+
+// tail of every filter upload: the segments' biases summed (one segment: its bias) -> fp32 [Npad] on the device, then the cache entry
+static DevWeight finish_weight(rtd_engine* e, const std::string& key, DevWeight d, const std::vector<FilterSeg>& segs) {
+  std::vector<float> bp(d.Npad, 0.f);
+  for (size_t i = 0; i < segs.size(); ++i) {
+    const HostTensor& b = host_tensor(e, segs[i].name + ".b");
+    RTD_CHECK(b.numel() == d.N, RTD_E_WEIGHTS, "bias shape mismatch: " + segs[i].name);
+    for (int r = 0; r < d.N; ++r) bp[r] = i ? bp[r] + b.data[r] : b.data[r];
+  }
+  d.bias = (float*)upload(e, bp.data(), bp.size() * 4);
+  e->wcache[key] = d;
+  return d;
+}
+
+// filter [N][K] fp32 -> device [Npad][Kpad] in dt (zero padded), bias -> fp32 [Npad].  Two segments: two filters over the same output
+// channels, concatenated along K: [N][K1 | K2], bias = b1 + b2 (a block's last conv with its projection shortcut folded in, ConvArgs::x2).
+// `extents_only` (the dry builder pass): the padded extents and nothing on the device.
+DevWeight get_weight(rtd_engine* e, const std::vector<FilterSeg>& segs, int dt, int N, bool extents_only = false) {
+  std::string key = segs[0].name;
+  int K = 0;
+  for (size_t i = 0; i < segs.size(); ++i) { if (i) key += "+" + segs[i].name; K += segs[i].K; }
+  key += dt_tag(dt);
   DevWeight d;
   d.N = N; d.K = K; d.Kpad = dt == F16X2 ? conv_kpad_split(K) : conv_kpad(K); d.Npad = conv_npad(N); d.dt = dt;
-  const int kcols = dt == F16X2 ? d.Kpad / 2 : d.Kpad;
-  std::vector<float> pad((size_t)d.Npad * kcols, 0.f);
-  for (int r = 0; r < N; ++r) memcpy(&pad[(size_t)r * kcols], w.data + (size_t)r * K, (size_t)K * 4);
-  d.w = upload_filter(e, pad, d.Npad, kcols, dt);
-  std::vector<float> bp(d.Npad, 0.f);
-  memcpy(bp.data(), b.data, (size_t)N * 4);
-  d.bias = (float*)e->dmalloc(bp.size() * 4);
-  HIP_CHECK(hipMemcpy(d.bias, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
-  e->wcache[key] = d;
-  return d;
-}
-
-// two filters over the same output channels, concatenated along K: [N][K1 | K2] -> device [Npad][Kpad], bias = b1 + b2
-// (a block's last conv with its projection shortcut folded in, ConvArgs::x2)
-DevWeight get_weight_cat(rtd_engine* e, const std::string& n1, const std::string& n2, int dt, int N, int K1, int K2) {
-  const std::string key = n1 + "+" + n2 + dt_tag(dt);
+  if (extents_only) return d;
   auto it = e->wcache.find(key);
   if (it != e->wcache.end()) return it->second;
-  const HostTensor& w1 = host_tensor(e, n1 + ".w");
-  const HostTensor& w2 = host_tensor(e, n2 + ".w");
-  const HostTensor& b1 = host_tensor(e, n1 + ".b");
-  const HostTensor& b2 = host_tensor(e, n2 + ".b");
-  RTD_CHECK(w1.numel() == (int64_t)N * K1 && w2.numel() == (int64_t)N * K2 && b1.numel() == N && b2.numel() == N, RTD_E_WEIGHTS,
-            "weight shape mismatch: " + n1 + " + " + n2);
-  DevWeight d;
-  d.N = N; d.K = K1 + K2; d.Kpad = dt == F16X2 ? conv_kpad_split(d.K) : conv_kpad(d.K); d.Npad = conv_npad(N); d.dt = dt;
   const int kcols = dt == F16X2 ? d.Kpad / 2 : d.Kpad;
   std::vector<float> pad((size_t)d.Npad * kcols, 0.f);
-  for (int r = 0; r < N; ++r) {
-    memcpy(&pad[(size_t)r * kcols], w1.data + (size_t)r * K1, (size_t)K1 * 4);
-    memcpy(&pad[(size_t)r * kcols + K1], w2.data + (size_t)r * K2, (size_t)K2 * 4);
+  int k0 = 0;
+  for (const FilterSeg& s : segs) {
+    const float* w = host_filter(e, s.name, N, s.K);
+    for (int r = 0; r < N; ++r) memcpy(&pad[(size_t)r * kcols + k0], w + (size_t)r * s.K, (size_t)s.K * 4);
+    k0 += s.K;
   }
   d.w = upload_filter(e, pad, d.Npad, kcols, dt);
-  std::vector<float> bp(d.Npad, 0.f);
-  for (int r = 0; r < N; ++r) bp[r] = b1.data[r] + b2.data[r];
-  d.bias = (float*)e->dmalloc(bp.size() * 4);
-  HIP_CHECK(hipMemcpy(d.bias, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
-  e->wcache[key] = d;
-  return d;
+  return finish_weight(e, key, d, segs);
 }
 
-// fp32 filter [N][K] -> fragment-major layout of decoder.hip's row_gemm (K padded to Kuse, N to 8 tiles)
 // host-side fp16 round-to-nearest-even (subnormals kept, saturating like common.h split2) through the compiler's _Float16
 static inline uint16_t f2h_rne(float f) {
   f = f > 65504.f ? 65504.f : (f < -65504.f ? -65504.f : f);
@@ -191,57 +192,53 @@ static inline float h2f(uint16_t u) {
   return (float)h;
 }
 
-DevWeight get_weight_packed(rtd_engine* e, const std::string& name, int N, int K, int Kuse, bool split = false) {
-  const std::string key = name + (split ? "#split" : "#packed");
-  auto it = e->wcache.find(key);
-  if (it != e->wcache.end()) return it->second;
-  const HostTensor& w = host_tensor(e, name + ".w");
-  const HostTensor& b = host_tensor(e, name + ".b");
-  RTD_CHECK(!w.shape.empty() && w.shape[0] == N && w.numel() == (int64_t)N * K, RTD_E_WEIGHTS, "weight shape mismatch: " + name);
-  RTD_CHECK(b.numel() == N && Kuse % 64 == 0 && Kuse >= K, RTD_E_WEIGHTS, "bias / K padding: " + name);
-  DevWeight d;
-  d.N = N; d.K = Kuse; d.Kpad = Kuse; d.dt = F32;
-  const int ntiles = ((N + 15) / 16 + 7) / 8 * 8, kc = Kuse / 16;
-  d.Npad = ntiles * 16;
-  std::vector<float> pk(split ? 0 : (size_t)ntiles * kc * 256, 0.f);
-  for (int t = 0; t < (split ? 0 : ntiles); ++t)
+// fp32 filter [N][K] -> fragment-major layout of decoder.hip's row_gemm (K padded to Kuse, N to `ntiles` 16-row tiles): fp32 fragments ...
+static void* pack_fragments_f32(rtd_engine* e, const float* w, int N, int K, int Kuse, int ntiles) {
+  const int kc = Kuse / 16;
+  std::vector<float> pk((size_t)ntiles * kc * 256, 0.f);
+  for (int t = 0; t < ntiles; ++t)
     for (int c = 0; c < kc; ++c)
       for (int lane = 0; lane < 64; ++lane)
         for (int j = 0; j < 4; ++j) {
           const int n = t * 16 + (lane & 15), k = c * 16 + 4 * (lane >> 4) + j;
-          if (n < N && k < K) pk[(((size_t)t * kc + c) * 64 + lane) * 4 + j] = w.data[(size_t)n * K + k];
+          if (n < N && k < K) pk[(((size_t)t * kc + c) * 64 + lane) * 4 + j] = w[(size_t)n * K + k];
         }
-  if (split) {
-    // W = hi + lo (two fp16, round-to-nearest-even each): decoder.hip row_gemm_split multiplies both against a hi/lo split of
-    // the activations with 3 fp16 MFMAs (hi*hi + hi*lo + lo*hi); the dropped lo*lo term is ~2^-22 relative
-    const int kc32 = Kuse / 32;
-    std::vector<uint16_t> ps((size_t)ntiles * kc32 * 2 * 512, 0);
-    for (int t = 0; t < ntiles; ++t)
-      for (int c = 0; c < kc32; ++c)
-        for (int lane = 0; lane < 64; ++lane)
-          for (int j = 0; j < 8; ++j) {
-            const int n = t * 16 + (lane & 15), k = c * 32 + 8 * (lane >> 4) + j;
-            if (n < N && k < K) {
-              const float v = w.data[(size_t)n * K + k];
-              const uint16_t hi = f2h_rne(v);
-              const uint16_t lo = f2h_rne(v - h2f(hi));
-              const size_t base = ((size_t)t * kc32 + c) * 1024;
-              ps[base + lane * 8 + j] = hi;
-              ps[base + 512 + lane * 8 + j] = lo;
-            }
+  return upload(e, pk.data(), pk.size() * 4);
+}
+// ... or W = hi + lo (two fp16, round-to-nearest-even each): decoder.hip row_gemm_split multiplies both against a hi/lo split of
+// the activations with 3 fp16 MFMAs (hi*hi + hi*lo + lo*hi); the dropped lo*lo term is ~2^-22 relative
+static void* pack_fragments_f16x2(rtd_engine* e, const float* w, int N, int K, int Kuse, int ntiles) {
+  const int kc32 = Kuse / 32;
+  std::vector<uint16_t> ps((size_t)ntiles * kc32 * 2 * 512, 0);
+  for (int t = 0; t < ntiles; ++t)
+    for (int c = 0; c < kc32; ++c)
+      for (int lane = 0; lane < 64; ++lane)
+        for (int j = 0; j < 8; ++j) {
+          const int n = t * 16 + (lane & 15), k = c * 32 + 8 * (lane >> 4) + j;
+          if (n < N && k < K) {
+            const float v = w[(size_t)n * K + k];
+            const uint16_t hi = f2h_rne(v);
+            const uint16_t lo = f2h_rne(v - h2f(hi));
+            const size_t base = ((size_t)t * kc32 + c) * 1024;
+            ps[base + lane * 8 + j] = hi;
+            ps[base + 512 + lane * 8 + j] = lo;
           }
-    d.w = e->dmalloc(ps.size() * 2);
-    HIP_CHECK(hipMemcpy(d.w, ps.data(), ps.size() * 2, hipMemcpyHostToDevice));
-  } else {
-  d.w = e->dmalloc(pk.size() * 4);
-  HIP_CHECK(hipMemcpy(d.w, pk.data(), pk.size() * 4, hipMemcpyHostToDevice));
-  }
-  std::vector<float> bp(d.Npad, 0.f);
-  memcpy(bp.data(), b.data, (size_t)N * 4);
-  d.bias = (float*)e->dmalloc(bp.size() * 4);
-  HIP_CHECK(hipMemcpy(d.bias, bp.data(), bp.size() * 4, hipMemcpyHostToDevice));
-  e->wcache[key] = d;
-  return d;
+        }
+  return upload(e, ps.data(), ps.size() * 2);
+}
+
+DevWeight get_weight_packed(rtd_engine* e, const std::string& name, int N, int K, int Kuse, bool split = false) {
+  const std::string key = name + (split ? "#split" : "#packed");
+  auto it = e->wcache.find(key);
+  if (it != e->wcache.end()) return it->second;
+  const float* w = host_filter(e, name, N, K);
+  RTD_CHECK(Kuse % 64 == 0 && Kuse >= K, RTD_E_WEIGHTS, "K padding: " + name);
+  DevWeight d;
+  d.N = N; d.K = Kuse; d.Kpad = Kuse; d.dt = F32;
+  const int ntiles = ((N + 15) / 16 + 7) / 8 * 8;
+  d.Npad = ntiles * 16;
+  d.w = split ? pack_fragments_f16x2(e, w, N, K, Kuse, ntiles) : pack_fragments_f32(e, w, N, K, Kuse, ntiles);
+  return finish_weight(e, key, d, {{name, K}});
 }
 
 float* get_vec(rtd_engine* e, const std::string& name, int n) {
@@ -249,8 +246,7 @@ float* get_vec(rtd_engine* e, const std::string& name, int n) {
   if (it != e->vcache.end()) return it->second;
   const HostTensor& t = host_tensor(e, name);
   RTD_CHECK(t.numel() == n, RTD_E_WEIGHTS, "vector shape mismatch: " + name);
-  float* d = (float*)e->dmalloc((size_t)n * 4);
-  HIP_CHECK(hipMemcpy(d, t.data, (size_t)n * 4, hipMemcpyHostToDevice));
+  float* d = (float*)upload(e, t.data, (size_t)n * 4);
   e->vcache[name] = d;
   return d;
 }
@@ -340,11 +336,7 @@ const ResizeCoef& resize_tables(rtd_engine* e, int sh, int sw) {
   pil_coeffs(sw, e->cfg.input_w, hb, hk, hks);
   pil_coeffs(sh, e->cfg.input_h, vb, vk, vks);
   ResizeTables t;
-  auto up = [&](const std::vector<int32_t>& v) {
-    void* d = e->dmalloc(v.size() * 4);
-    HIP_CHECK(hipMemcpy(d, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-    return (const int32_t*)d;
-  };
+  auto up = [&](const std::vector<int32_t>& v) { return (const int32_t*)upload(e, v.data(), v.size() * 4); };
   t.coef.hb = up(hb); t.coef.hk = up(hk); t.coef.vb = up(vb); t.coef.vk = up(vk);
   t.coef.hks = hks; t.coef.vks = vks;
   e->resize[key] = t;
@@ -352,11 +344,55 @@ const ResizeCoef& resize_tables(rtd_engine* e, int sh, int sw) {
 }
 
 // ------------------------------------------------------------------------------------------ plan builder
+// What a conv of the plan is besides its name, input and output (Builder::conv, Builder::probe).  Filled with designated initialisers.
+struct ConvSpec {
+  int k = 1, stride = 1, pad = 0, act = ACT_NONE;
+  const Tensor* res = nullptr;      // residual, added as res_mode says
+  int res_mode = RES_NONE;
+  int real_cin = 0;                 // input channels that carry data (flops figure only; 0 = all)
+  // `x2` + `name2`: a second input read as an extra 1x1 tap at output resolution, its filter `name2` concatenated along K
+  // (ConvArgs::x2: the projection shortcut folded into the block's last conv).  name2 empty: the conv's own filter is already the one
+  // over [x | x2] (a conv over a concatenation that is read from its two sources)
+  const Tensor* x2 = nullptr;
+  std::string name2;
+  int x_up2 = 0;                    // x is read through a 2x nearest upsampling (ConvArgs::x_up2)
+  const Tensor* next_y = nullptr;   // the following 1x1 conv `next_name` rides on this launch (ConvArgs::next_*)
+  std::string next_name;
+  int next_act = ACT_NONE;
+  Tensor avg_y;                     // .c != 0: the launch also writes the 2 x 2 average of its output (ConvArgs::avg_y)
+  bool y_dead = false;              // the output has no reader outside this launch (see ConvArgs::y_dead)
+};
+
+// stands for every device pointer of a shape probe: non-null and 16-byte aligned, never dereferenced
+static void* const SHAPE_ONLY = (void*)16;
+
+static std::string nm(const char* fmt, int a = 0, int b = 0) {
+  char buf[96];
+  snprintf(buf, sizeof buf, fmt, a, b);
+  return std::string(buf);
+}
+
+// state that build_graph's stages hand to each other
+struct Flow {
+  Tensor cur; int h = 0, w = 0;     // the trunk's newest map
+  Tensor feats[3];                  // outputs of stages 1..3: the encoder's inputs
+  Tensor cat0, cat1;                // the FPN's concat buffers [up(lat0) | proj1], [up(lat1) | proj0]
+  Tensor prepooled; bool have_prepooled = false;   // the 2 x 2 average of the stage input already exists (avg_fuse)
+  Tensor t1_next; bool c1_done = false;            // the next block's c1 already ran inside the previous block's last conv
+  bool side_open = false;           // the side stream holds work the main stream has not joined yet
+};
+struct Queries { Tensor target; int32_t* tk = nullptr; };     // query selection -> decoder
+struct Decoded { Tensor logits; float* ref8 = nullptr; };     // decoder -> post-processor
+
 struct Builder {
   rtd_engine* e;
   Plan* plan;
   bool dry;
+  const rtd_config& c;
+  const int n, P;
+  const bool SP;                    // rtd_config.precision = RTD_PREC_F16X3: the trunk carries hi/lo fp16 pairs
   size_t off = 0;
+  Builder(rtd_engine* e_, Plan* plan_, bool dry_) : e(e_), plan(plan_), dry(dry_), c(e_->cfg), n(plan_->n), P(e_->P), SP(e_->P == F16X2) {}
 
   void* alloc(size_t bytes) {
     off = (off + 255) / 256 * 256;
@@ -364,15 +400,16 @@ struct Builder {
     off += bytes;
     return p;
   }
+  Tensor named(const std::string& name, const Tensor& t) { if (!name.empty()) plan->named[name] = t; return t; }
   Tensor act(int dt, int n, int h, int w, int c, const std::string& name = "") {
-    Tensor t;
-    t.dt = dt; t.n = n; t.h = h; t.w = w; t.c = c; t.ld = c; t.bstride = (int64_t)h * w * c;
+    Tensor t = mk(nullptr, dt, n, h, w, c);
     const size_t nbytes = (size_t)n * h * w * c * dtype_size(dt);
     t.p = alloc(nbytes);
     if (!dry && dt == F16X2) plan->split_acts.emplace_back(t.p, nbytes);
-    if (!name.empty()) plan->named[name] = t;
-    return t;
+    return named(name, t);
   }
+  // a dense h x w x c tensor at the start of `buf` (the recycled buffers of a stage)
+  Tensor view(const Tensor& buf, int h, int w, int c, const std::string& name = "") { return named(name, mk(buf.p, buf.dt, buf.n, h, w, c)); }
   int lane = 0;              // lane of the ops being pushed
   void push(const std::string& name, const char* kernel, double flops, double bytes, std::function<void(hipStream_t)> f) {
     if (dry) return;
@@ -382,42 +419,57 @@ struct Builder {
     if (dry) return;
     plan->ops.push_back(Op{kind == 1 ? "fork" : "join", "sync", 0.0, 0.0, nullptr, false, 0, kind});
   }
+  // a closed excursion to the side stream: fork, `body` on lane 1, back to lane 0 (the join is the caller's: it sits where main needs the result)
+  template <typename F>
+  void on_side(F&& body) { marker(1); lane = 1; body(); lane = 0; }
   static double tbytes(const Tensor& t) { return (double)t.pixels() * t.c * dtype_size(t.dt); }
 
+  // What the conv_*_supported() predicates look at for conv(.., x, y, s): shapes, alignment and which operands exist - so a fusion can be
+  // asked about before its tensors are allocated.  ONE image unless `plan_batch`: every plan of an engine must use the same filters (the
+  // host copies are dropped after the first plan) and the same arithmetic (batch invariance), and a single image has the smallest grid.
+  static Tensor probe_shape(Tensor t, int n) { t.p = SHAPE_ONLY; t.n = n; return t; }
+  ConvArgs probe(const Tensor& x, const Tensor& y, const ConvSpec& s, bool plan_batch = false) const {
+    const int pn = plan_batch ? n : 1;
+    ConvArgs a;
+    a.opts = &e->conv_opts;
+    a.w = SHAPE_ONLY; a.bias = nullptr;
+    a.x = probe_shape(x, pn); a.y = probe_shape(y, pn);
+    if (s.x2) a.x2 = probe_shape(*s.x2, pn);
+    if (s.res) { a.res = probe_shape(*s.res, pn); a.res_mode = s.res_mode; }
+    if (s.next_y) a.next_y = probe_shape(*s.next_y, pn);
+    if (s.avg_y.c) a.avg_y = probe_shape(s.avg_y, pn);
+    a.x_up2 = s.x_up2;
+    a.KH = a.KW = s.k; a.stride = s.stride; a.pad = s.pad; a.act = s.act;
+    return a;
+  }
+
   // conv / linear.  `y` may be a channel-slice view of a wider buffer.
-  // `x2` + `name2`: a second input read as an extra 1x1 tap at output resolution, its filter `name2` concatenated along K
-  // (ConvArgs::x2: the projection shortcut folded into the block's last conv)
-  void conv(const std::string& name, const Tensor& x, const Tensor& y, int k, int stride, int pad, int act,
-            const Tensor* res = nullptr, int res_mode = RES_NONE, int real_cin = 0, const Tensor* x2 = nullptr,
-            const std::string& name2 = "", int x_up2 = 0, const Tensor* next_y = nullptr, const std::string& next_name = "", int next_act = ACT_NONE) {
-    const int K = k * k * x.c + (x2 ? x2->c : 0);
-    DevWeight w;
-    // name2 empty: `name` is already the filter over [x | x2] (a conv over a concatenation that is read from its two sources)
-    if (!dry) w = (x2 && !name2.empty()) ? get_weight_cat(e, name, name2, x.dt, y.c, k * k * x.c, x2->c) : get_weight(e, name, x.dt, y.c, K);
-    else { w.Kpad = x.dt == F16X2 ? conv_kpad_split(K) : conv_kpad(K); w.Npad = conv_npad(y.c); }
+  void conv(const std::string& name, const Tensor& x, const Tensor& y, const ConvSpec& s) {
+    const int k = s.k, K = k * k * x.c + (s.x2 ? s.x2->c : 0);
+    std::vector<FilterSeg> segs{{name, K}};
+    if (s.x2 && !s.name2.empty()) segs = {{name, k * k * x.c}, {s.name2, s.x2->c}};
+    const DevWeight w = get_weight(e, segs, x.dt, y.c, dry);
     ConvArgs a;
     a.x = x; a.y = y; a.w = w.w; a.bias = w.bias;
-    if (x2) a.x2 = *x2;
-    a.x_up2 = x_up2;
-    a.KH = k; a.KW = k; a.stride = stride; a.pad = pad; a.Kpad = w.Kpad; a.Npad = w.Npad;
-    a.act = act; a.res_mode = res ? res_mode : RES_NONE;
-    if (res) a.res = *res;
-    if (next_y) {                                              // the following 1x1 conv rides on this launch (ConvArgs::next_*)
-      DevWeight wn;
-      if (!dry) wn = get_weight(e, next_name, x.dt, next_y->c, y.c);
-      else { wn.Kpad = x.dt == F16X2 ? conv_kpad_split(y.c) : conv_kpad(y.c); wn.Npad = conv_npad(next_y->c); }
-      a.next_w = wn.w; a.next_bias = wn.bias; a.next_y = *next_y; a.next_kpad = wn.Kpad; a.next_act = next_act;
+    if (s.x2) a.x2 = *s.x2;
+    a.x_up2 = s.x_up2;
+    a.KH = k; a.KW = k; a.stride = s.stride; a.pad = s.pad; a.Kpad = w.Kpad; a.Npad = w.Npad;
+    a.act = s.act; a.res_mode = s.res ? s.res_mode : RES_NONE;
+    if (s.res) a.res = *s.res;
+    if (s.next_y) {
+      const DevWeight wn = get_weight(e, {{s.next_name, y.c}}, x.dt, s.next_y->c, dry);
+      a.next_w = wn.w; a.next_bias = wn.bias; a.next_y = *s.next_y; a.next_kpad = wn.Kpad; a.next_act = s.next_act;
     }
     a.opts = &e->conv_opts;
     a.prefer256 = e->cfg.profile == RTD_PROFILE_THROUGHPUT;
-    if (avg_pending) { a.avg_y = avg_pending_y; if (dry) a.avg_y.p = nullptr; avg_pending = false; }
-    if (y_dead_pending) { a.y_dead = (a.avg_y.c && next_y) ? 1 : 0; y_dead_pending = false; }
+    a.avg_y = s.avg_y;
+    a.y_dead = (s.y_dead && a.avg_y.c && s.next_y) ? 1 : 0;
     slab_need[lane] = std::max(slab_need[lane], conv_split_slab_bytes(a));
     const double M = (double)y.pixels();
-    const double kreal = (double)k * k * (real_cin ? real_cin : x.c) + (x2 ? x2->c : 0);
-    const double flops = 2.0 * M * y.c * kreal + (next_y ? 2.0 * M * y.c * next_y->c : 0.0);
+    const double kreal = (double)k * k * (s.real_cin ? s.real_cin : x.c) + (s.x2 ? s.x2->c : 0);
+    const double flops = 2.0 * M * y.c * kreal + (s.next_y ? 2.0 * M * y.c * s.next_y->c : 0.0);
     const double bytes = (double)x.pixels() * x.c * dtype_size(x.dt) + tbytes(y) + (double)y.c * K * dtype_size(x.dt) +
-                         (res ? tbytes(*res) : 0.0) + (x2 ? tbytes(*x2) : 0.0) + (next_y ? tbytes(*next_y) : 0.0) + (a.avg_y.c ? tbytes(a.avg_y) : 0.0) -
+                         (s.res ? tbytes(*s.res) : 0.0) + (s.x2 ? tbytes(*s.x2) : 0.0) + (s.next_y ? tbytes(*s.next_y) : 0.0) + (a.avg_y.c ? tbytes(a.avg_y) : 0.0) -
                          (a.y_dead ? tbytes(y) : 0.0);
     auto ap = std::make_shared<ConvArgs>(a);
     if (!dry) {
@@ -428,10 +480,6 @@ struct Builder {
     }
     push(name, "conv_igemm", flops, bytes, [ap](hipStream_t s) { launch_conv(*ap, s); });
   }
-  // set by the plan builder right before the conv that should also write the 2 x 2 average of its output (ConvArgs::avg_y); consumed by conv()
-  bool avg_pending = false;
-  Tensor avg_pending_y;
-  bool y_dead_pending = false;   // the next conv's output has no reader outside that launch (see ConvArgs::y_dead)
   std::shared_ptr<ConvArgs> last_conv;
   // two-pass split-K workspace of this plan: sized for the plan's own batch (the slice count depends on per-image extents only, so every
   // batch size up to max_batch runs the same arithmetic), allocated once every conv is known.  ONE SLAB PER LANE: launches of a lane are
@@ -450,22 +498,26 @@ struct Builder {
   Tensor linear(const std::string& name, const Tensor& x, int N, int odt, int act, const Tensor* res = nullptr,
                 const std::string& tname = "") {
     Tensor y = this->act(odt, x.n, x.h, x.w, N, tname);
-    conv(name, x, y, 1, 1, 0, act, res, RES_PRE);
+    conv(name, x, y, {.act = act, .res = res, .res_mode = RES_PRE});
     return y;
   }
-  // dense fp32 rows -> F16X2 rows (the split engine's trunk type) as its own launch
+  // dense fp32 rows -> F16X2 rows (the split engine's trunk type) as its own launch, into `y`
+  void split_into(const std::string& name, const Tensor& x, const Tensor& y, double bytes) {
+    const int64_t rows = x.pixels();
+    push(name, "convert", 0.0, bytes, [x, y, rows](hipStream_t s) { launch_f32_to_split((const float*)x.p, x.ld, y.p, y.ld, rows, x.c, s); });
+  }
   Tensor to_split(const std::string& name, const Tensor& x, const std::string& tname = "") {
     Tensor y = act(F16X2, x.n, x.h, x.w, x.c, tname);
-    const int64_t rows = x.pixels();
-    push(name, "convert", 0.0, tbytes(x) + tbytes(y), [x, y, rows](hipStream_t s) { launch_f32_to_split((const float*)x.p, x.ld, y.p, y.ld, rows, x.c, s); });
+    split_into(name, x, y, tbytes(x) + tbytes(y));
     return y;
   }
   // a filter / LayerNorm of the fused row kernels (decoder.hip: fused AIFI and decoder).  bf16 and f16x3 engines get the hi/lo fragment
   // layout of their pair MFMAs (DecArgs::split = 1), the fp32 engine fp32 fragments.  Kuse < K: zero-padded columns.
-  DecLin dec_lin(const std::string& name, int N, int K, int Kuse = 0) {
+  DecLin dec_lin(const std::string& name, int N, int K, int Kuse = 0) { return dec_lin(name, N, K, Kuse, e->P != F32); }
+  DecLin dec_lin(const std::string& name, int N, int K, int Kuse, bool split) {
     DecLin L{};
     if (dry) return L;
-    const DevWeight w = get_weight_packed(e, name, N, K, Kuse ? Kuse : K, e->P != F32);
+    const DevWeight w = get_weight_packed(e, name, N, K, Kuse ? Kuse : K, split);
     L.w = (const float*)w.w; L.b = w.bias; L.ldw = w.Kpad; L.N = N; L.K = w.K;
     return L;
   }
@@ -484,607 +536,582 @@ struct Builder {
          [x, y, g, b](hipStream_t s) { launch_layernorm(x, nullptr, g, b, y, 1e-5f, s); });
     return y;
   }
+
+  // ---- the stages of build_graph, in the order they run
+  struct StageBufs { Tensor pp[2], tb1, tb2; };   // the recycled buffers of a stage (arena_reuse)
+  struct Block {                                  // one residual block: what its shortcut part hands to its body
+    std::string pfx, oname;
+    int si, bi, stride, oh, ow, cin, cout;
+    bool last, fold_sc;
+    Tensor res, sc_in, out;
+  };
+  void stem(Flow& F);
+  void backbone_stage(Flow& F, int si, int cin);
+  void shortcut(Flow& F, Block& b);
+  void bottleneck_body(Flow& F, const StageBufs& sb, const Block& b);
+  void basic_body(Flow& F, const StageBufs& sb, const Block& b);
+  Tensor aifi_fused(const Tensor& t0), aifi_by_op(const Tensor& t0);
+  Tensor csp(const std::string& pfx, const Tensor& cat, const std::string& oname, const Tensor* up_src = nullptr);
+  Tensor encoder(Flow& F);
+  bool dec_fused() const { return e->opts.dec_fused && c.d_model == 256 && c.dec_heads == 8 && c.dec_ffn <= 1024 && c.num_classes <= 512 && c.n_levels == 3 && c.n_points == 4; }
+  Queries select_queries(Flow& F, const Tensor& mem);
+  Decoded decoder(Flow& F, const Tensor& mem, const Queries& q);
+  Tensor decoder_fused(Flow& F, const Queries& q, const Tensor& vall, float* ref8, float* ref_unact8);
+  Tensor decoder_by_op(const Queries& q, const Tensor& vall, const Tensor& ref8t, float* ref_unact8);
+  void post_process(const Decoded& d);
 };
 
-void build_graph(rtd_engine* e, Builder& B, int n) {
-  const rtd_config& c = e->cfg;
-  const int P = e->P;
-  const bool SP = P == F16X2;            // rtd_config.precision = RTD_PREC_F16X3: the trunk carries hi/lo fp16 pairs
+// ---- input + stem (HF:rt_detr_resnet.py:71-114) ----------------------------------------------
+void Builder::stem(Flow& F) {
   const int H = c.input_h, W = c.input_w;
-  Plan* plan = B.plan;
-  auto nm = [](const char* fmt, int a = 0, int b = 0) {
-    char buf[96];
-    snprintf(buf, sizeof buf, fmt, a, b);
-    return std::string(buf);
-  };
-
-  // ---- input + stem (HF:rt_detr_resnet.py:71-114) ----------------------------------------------
-  Tensor x = B.act(SP ? F32 : P, n, H, W, 8, "input");   // split engine: fp32 pixels, stem.0 runs on fp32 MFMAs (K = 27) and writes F16X2
+  Tensor x = act(SP ? F32 : P, n, H, W, 8, "input");   // split engine: fp32 pixels, stem.0 runs on fp32 MFMAs (K = 27) and writes F16X2
   plan->input = x;
   const int eh = c.embedding_size / 2;
-  int h = down2(H), w = down2(W);
-  Tensor s0 = B.act(P, n, h, w, eh);
+  const int h = down2(H), w = down2(W);
+  Tensor s0 = act(P, n, h, w, eh);
   // f16x3: on by default - the generic form there is a 105 MB fp32 NHWC-8 image + an fp32-MFMA stem conv (30 + 180 us at R50 bs 8)
   plan->stem_fused = SP && e->opts.stem_fused_split && eh == 32;
   if (plan->stem_fused) {
     // straight from the uint8 frames (ops.hip stem0_u8_kernel); `x` is only materialised on demand for rtd_debug_tensor("input")
-    const uint8_t** table = (const uint8_t**)B.alloc((size_t)c.max_batch * sizeof(void*));
+    const uint8_t** table = (const uint8_t**)alloc((size_t)c.max_batch * sizeof(void*));
     plan->frame_table = table;
-    if (!B.dry) {
-      DevWeight w0 = get_weight(e, "backbone.stem.0", P, eh, 9 * 8);
-      const void* wp = w0.w; const float* bp = w0.bias; const int kp = w0.Kpad;
-      B.push("backbone.stem.0", "conv_igemm", 2.0 * n * h * w * eh * 27.0, (double)n * H * W * 3 + Builder::tbytes(s0),
-             [table, n, H, W, wp, kp, bp, s0](hipStream_t st) { launch_stem0_u8(table, n, H, W, wp, kp, bp, s0, ACT_RELU, st); });
+    if (!dry) {
+      DevWeight w0 = get_weight(e, {{"backbone.stem.0", 9 * 8}}, P, eh);
+      const void* wp = w0.w; const float* bp = w0.bias; const int kp = w0.Kpad; const int n = this->n;
+      push("backbone.stem.0", "conv_igemm", 2.0 * n * h * w * eh * 27.0, (double)n * H * W * 3 + tbytes(s0),
+           [table, n, H, W, wp, kp, bp, s0](hipStream_t st) { launch_stem0_u8(table, n, H, W, wp, kp, bp, s0, ACT_RELU, st); });
     }
   } else {
-    B.conv("backbone.stem.0", x, s0, 3, 2, 1, ACT_RELU, nullptr, RES_NONE, 3);
+    conv("backbone.stem.0", x, s0, {.k = 3, .stride = 2, .pad = 1, .act = ACT_RELU, .real_cin = 3});
   }
-  Tensor s1 = B.act(P, n, h, w, eh);
-  B.conv("backbone.stem.1", s0, s1, 3, 1, 1, ACT_RELU);
-  Tensor cur;
-  {
-    // stem.2 + max-pool (HF:rt_detr_resnet.py:100-113).  f16x3: one pass when the direct kernel takes the conv (stem_pool_fuse) - the
-    // 320^2 x 64-channel conv output (210 MB at R50 bs 8) is neither written nor read back
-    Tensor s2v;                                    // stem.2's output as a shape (allocated only when the pool runs on its own)
-    s2v.dt = P; s2v.n = n; s2v.h = h; s2v.w = w; s2v.c = c.embedding_size; s2v.ld = c.embedding_size; s2v.bstride = (int64_t)h * w * c.embedding_size;
-    const int ph = down2(h), pw = down2(w);
-    Tensor pv = s2v; pv.h = ph; pv.w = pw; pv.bstride = (int64_t)ph * pw * pv.ld;
-    ConvArgs probe;
-    probe.opts = &e->conv_opts;
-    probe.x = s1; probe.x.p = (void*)16; probe.y = s2v; probe.y.p = (void*)16;
-    probe.KH = probe.KW = 3; probe.stride = 1; probe.pad = 1; probe.act = ACT_RELU; probe.w = (const void*)16;
-    Tensor pvp = pv; pvp.p = (void*)16;
-    Tensor probe1 = probe.x; probe1.n = 1;          // asked for ONE image: every plan of a handle makes the same choice
-    ConvArgs probe_one = probe; probe_one.x = probe1; probe_one.y.n = 1;
-    Tensor pv1 = pvp; pv1.n = 1;
-    // (conv -> pool and the fused pass agree bit for bit, so the side buffers' 2 GiB descriptor limit may decide per batch size)
-    const long long pool_tiles = (long long)n * ((w + 31) / 32) * ((h + 7) / 8);
-    const bool fuse = SP && e->opts.stem_pool_fuse && conv_pool_supported(probe_one, pv1) && pool_tiles * 8192 < (1ll << 31);
-    if (fuse) {
-      h = ph; w = pw;
-      cur = B.act(P, n, h, w, c.embedding_size, "stem");
-      ConvArgs a;
-      a.x = s1; a.y = s2v; a.y.p = nullptr;
-      a.KH = a.KW = 3; a.stride = 1; a.pad = 1; a.act = ACT_RELU; a.opts = &e->conv_opts;
-      DevWeight w2;
-      if (!B.dry) w2 = get_weight(e, "backbone.stem.2", P, c.embedding_size, 9 * s1.c);
-      else { w2.Kpad = conv_kpad_split(9 * s1.c); w2.Npad = conv_npad(c.embedding_size); }
-      a.w = w2.w; a.bias = w2.bias; a.Kpad = w2.Kpad; a.Npad = w2.Npad;
-      void* side = B.alloc(conv_pool_side_bytes(a));
-      const Tensor curv = cur;
-      B.push("backbone.stem.2+pool", "conv_igemm", 2.0 * s2v.pixels() * s2v.c * 9.0 * s1.c, Builder::tbytes(s1) + Builder::tbytes(cur),
-             [a, curv, side](hipStream_t st) { launch_conv_pool(a, curv, side, st); });
+  Tensor s1 = act(P, n, h, w, eh);
+  conv("backbone.stem.1", s0, s1, {.k = 3, .pad = 1, .act = ACT_RELU});
+  // stem.2 + max-pool (HF:rt_detr_resnet.py:100-113).  f16x3: one pass when the direct kernel takes the conv (stem_pool_fuse) - the
+  // 320^2 x 64-channel conv output (210 MB at R50 bs 8) is neither written nor read back
+  const Tensor s2v = mk(nullptr, P, n, h, w, c.embedding_size);   // stem.2's output as a shape (allocated only when the pool runs on its own)
+  const int ph = down2(h), pw = down2(w);
+  const ConvSpec stem2{.k = 3, .pad = 1, .act = ACT_RELU};
+  // asked for ONE image: every plan of a handle makes the same choice
+  // (conv -> pool and the fused pass agree bit for bit, so the side buffers' 2 GiB descriptor limit may decide per batch size)
+  const long long pool_tiles = (long long)n * ((w + 31) / 32) * ((h + 7) / 8);
+  const bool fuse = SP && e->opts.stem_pool_fuse && conv_pool_supported(probe(s1, s2v, stem2), probe_shape(mk(nullptr, P, n, ph, pw, c.embedding_size), 1)) &&
+                    pool_tiles * 8192 < (1ll << 31);
+  F.h = ph; F.w = pw;
+  if (fuse) {
+    F.cur = act(P, n, ph, pw, c.embedding_size, "stem");
+    ConvArgs a;
+    a.x = s1; a.y = s2v;
+    a.KH = a.KW = 3; a.stride = 1; a.pad = 1; a.act = ACT_RELU; a.opts = &e->conv_opts;
+    const DevWeight w2 = get_weight(e, {{"backbone.stem.2", 9 * s1.c}}, P, c.embedding_size, dry);
+    a.w = w2.w; a.bias = w2.bias; a.Kpad = w2.Kpad; a.Npad = w2.Npad;
+    void* side = alloc(conv_pool_side_bytes(a));
+    const Tensor curv = F.cur;
+    push("backbone.stem.2+pool", "conv_igemm", 2.0 * s2v.pixels() * s2v.c * 9.0 * s1.c, tbytes(s1) + tbytes(curv),
+         [a, curv, side](hipStream_t st) { launch_conv_pool(a, curv, side, st); });
+  } else {
+    Tensor s2 = act(P, n, h, w, c.embedding_size);
+    conv("backbone.stem.2", s1, s2, stem2);
+    F.cur = act(P, n, ph, pw, c.embedding_size, "stem");
+    const Tensor curv = F.cur;
+    push("backbone.pool", "maxpool", 9.0 * curv.pixels() * curv.c, tbytes(s2) + tbytes(curv),
+         [s2, curv](hipStream_t s) { launch_maxpool3x3s2(s2, curv, s); });
+  }
+}
+
+// ---- residual stages (HF:rt_detr_resnet.py:135-310) ------------------------------------------
+void Builder::backbone_stage(Flow& F, int si, int cin) {
+  const int cout = c.hidden_sizes[si];
+  const bool bottleneck = c.layer_type == RTD_LAYER_BOTTLENECK;
+  // Buffers are recycled inside a stage (rtd_debug_option "arena_reuse"): the blocks' outputs ping-pong between two buffers
+  // (a block's input is dead once its last conv has read it as the residual) and the c1 / c2 temporaries of every block
+  // share one buffer each.  Fewer distinct lines means more of a stage lives in L2 + the 256 MB Infinity Cache, and dead
+  // activations are overwritten in cache instead of being written back to HBM.
+  StageBufs sb;
+  if (e->opts.arena_reuse) {
+    const int s0 = (si > 0) ? 2 : 1;
+    const int oh0 = s0 == 2 ? down2(F.h) : F.h, ow0 = s0 == 2 ? down2(F.w) : F.w;
+    sb.pp[0] = act(P, n, oh0, ow0, cout);
+    if (c.depths[si] > 1) sb.pp[1] = act(P, n, oh0, ow0, cout);
+    const int mid0 = bottleneck ? cout / 4 : cout;
+    sb.tb1 = act(P, n, bottleneck ? F.h : oh0, bottleneck ? F.w : ow0, mid0);   // block 0's c1 runs before the stride
+    sb.tb2 = act(P, n, oh0, ow0, mid0);
+  }
+  for (int bi = 0; bi < c.depths[si]; ++bi) {
+    Block b;
+    b.si = si; b.bi = bi; b.cin = cin; b.cout = cout;
+    b.stride = (si > 0 && bi == 0) ? 2 : 1;
+    b.pfx = nm("backbone.s%d.b%d", si, bi);
+    b.oh = b.stride == 2 ? down2(F.h) : F.h; b.ow = b.stride == 2 ? down2(F.w) : F.w;
+    b.last = bi == c.depths[si] - 1;
+    b.oname = (b.last && si >= 1) ? nm("backbone%d", si - 1) : std::string();
+    shortcut(F, b);
+    b.out = e->opts.arena_reuse ? view(sb.pp[bi & 1], b.oh, b.ow, cout, b.oname) : act(P, n, b.oh, b.ow, cout, b.oname);
+    if (bottleneck) bottleneck_body(F, sb, b);
+    else basic_body(F, sb, b);
+    F.cur = b.out; F.h = b.oh; F.w = b.ow; cin = cout;
+  }
+  if (si >= 1) F.feats[si - 1] = F.cur;
+  if ((e->opts.side_stream & 4) && (si == 1 || si == 2)) {
+    // HF:v2.py:1348-1360 encoder input projection of this level, beside the next stage (side stream)
+    on_side([&] { conv(si == 1 ? "enc.proj.0" : "enc.proj.1", F.cur, (si == 1 ? F.cat1 : F.cat0).slice_c(c.enc_dim, c.enc_dim), {}); });
+    F.side_open = true;
+  }
+}
+
+// The residual operand of block `b`: the block input, or its projection shortcut - as a tensor (b.res) or folded into the block's last conv
+// (b.fold_sc, b.sc_in = what the shortcut's 1x1 reads)
+void Builder::shortcut(Flow& F, Block& b) {
+  const bool bottleneck = c.layer_type == RTD_LAYER_BOTTLENECK;
+  const Tensor cur = F.cur;
+  b.res = cur;
+  b.sc_in = cur;
+  b.fold_sc = false;
+  const bool has_sc = bottleneck ? (b.cin != b.cout || b.stride != 1) : (b.bi == 0);
+  if (!has_sc) return;
+  // stride 2: AvgPool2d(2,2,ceil) then 1x1 (HF:rt_detr_resnet.py:199-213); extents are even here
+  if (b.stride == 2) {
+    if (F.have_prepooled) {
+      b.sc_in = F.prepooled;                               // written by the previous stage's last conv (ConvArgs::avg_y)
+      F.have_prepooled = false;
     } else {
-      Tensor s2 = B.act(P, n, h, w, c.embedding_size);
-      B.conv("backbone.stem.2", s1, s2, 3, 1, 1, ACT_RELU);
-      h = ph; w = pw;
-      cur = B.act(P, n, h, w, c.embedding_size, "stem");
-      const Tensor curv = cur;
-      B.push("backbone.pool", "maxpool", 9.0 * cur.pixels() * cur.c, Builder::tbytes(s2) + Builder::tbytes(cur),
-             [s2, curv](hipStream_t s) { launch_maxpool3x3s2(s2, curv, s); });
+      Tensor pooled = act(P, n, b.oh, b.ow, b.cin);
+      push(b.pfx + ".avgpool", "avgpool", 4.0 * pooled.pixels() * b.cin, tbytes(cur) + tbytes(pooled),
+           [cur, pooled](hipStream_t s) { launch_avgpool2(cur, pooled, s); });
+      b.sc_in = pooled;
     }
   }
+  // The projection shortcut is a 1x1 conv over the block input whose only use is the pre-activation add of the block's last
+  // conv: y = relu(W_last * t + b_last + (W_sc * x_in + b_sc)).  In bf16 plans it is folded into that conv as extra K
+  // (ConvArgs::x2): the [B,OH,OW,cout] shortcut tensor is neither written nor read back (R50 bs 8 stage 0: 2 x 105 MB), one
+  // launch less, and the sum is rounded once instead of twice.  fp32 plans keep the reference's op sequence.
+  if ((P == BF16 || SP) && e->opts.sc_fold) {
+    // shapes only (ONE image): would the kernels take the folded launch?
+    const int k = bottleneck ? 1 : 3;
+    b.fold_sc = conv_dual_supported(probe(mk(nullptr, P, n, b.oh, b.ow, bottleneck ? b.cout / 4 : b.cout), mk(nullptr, P, n, b.oh, b.ow, b.cout),
+                                          {.k = k, .pad = k / 2, .x2 = &b.sc_in}));
+  }
+  if (!b.fold_sc) {
+    b.res = act(P, n, b.oh, b.ow, b.cout);
+    conv(b.pfx + ".sc", b.sc_in, b.res, {});
+  }
+}
 
-  // the FPN's concat buffers exist before the backbone runs: their projection halves are filled as soon as a stage's map is complete
-  const int d = c.enc_dim, hh = c.csp_hidden;
-  const int* lh = e->lvl_h; const int* lw = e->lvl_w;
-  Tensor cat1 = B.act(P, n, lh[0], lw[0], 2 * d);   // [up(lat1) | proj0]
-  Tensor cat0 = B.act(P, n, lh[1], lw[1], 2 * d);   // [up(lat0) | proj1]
-  const bool early_enc_proj = (e->opts.side_stream & 4) != 0;
-  bool enc_proj_forked = false;
+void Builder::bottleneck_body(Flow& F, const StageBufs& sb, const Block& b) {
+  const int si = b.si, oh = b.oh, ow = b.ow, cout = b.cout, mid = cout / 4;
+  const bool reuse = e->opts.arena_reuse;
+  // the c1 output of this block: with recycled buffers it is the stage's shared temporary, which the PREVIOUS block's last conv
+  // may already have filled (ConvArgs::next_*: the reduce conv fused into the expand conv that produced its input)
+  Tensor t1 = F.c1_done ? F.t1_next : (reuse ? view(sb.tb1, F.h, F.w, mid) : act(P, n, F.h, F.w, mid));
+  if (!F.c1_done) conv(b.pfx + ".c1", F.cur, t1, {.act = ACT_RELU});
+  F.c1_done = false;
+  Tensor t2 = reuse ? view(sb.tb2, oh, ow, mid) : act(P, n, oh, ow, mid);
+  conv(b.pfx + ".c2", t1, t2, {.k = 3, .stride = b.stride, .pad = 1, .act = ACT_RELU});
+  ConvSpec c3{.act = ACT_RELU};
+  if (b.fold_sc) { c3.x2 = &b.sc_in; c3.name2 = b.pfx + ".sc"; }
+  else { c3.res = &b.res; c3.res_mode = RES_PRE; }
+  // fuse the NEXT block's c1 (1x1, stride 1, reads `out` at these extents) when the streaming kernel takes this conv: the next block of
+  // this stage, or (f16x3 plans) block 0 of the next stage, whose c1 runs before that block's stride
+  const bool same_stage = b.bi + 1 < c.depths[si];
+  const bool cross_stage = !same_stage && SP && si + 1 < 4;
+  if ((P == BF16 || SP) && e->opts.c1_fuse && (same_stage || cross_stage)) {
+    const int mid_n = same_stage ? mid : c.hidden_sizes[si + 1] / 4;
+    const Tensor t1_shape = mk(nullptr, P, n, oh, ow, mid_n);
+    ConvSpec with_next = c3;
+    with_next.next_y = &t1_shape;
+    if (conv_next_supported(probe(t2, b.out, with_next, /*plan_batch=*/true))) {   // this plan's shapes (fused and separate launches are bit-identical)
+      F.t1_next = (same_stage && reuse) ? view(sb.tb1, oh, ow, mid_n) : act(P, n, oh, ow, mid_n);
+      F.c1_done = true;
+      c3.next_y = &F.t1_next; c3.next_act = ACT_RELU;
+      c3.next_name = (same_stage ? nm("backbone.s%d.b%d", si, b.bi + 1) : nm("backbone.s%d.b0", si + 1)) + ".c1";
+    }
+  }
+  if (SP && e->opts.avg_fuse && b.last && si + 1 < 4 && !b.fold_sc && (oh & 1) == 0 && (ow & 1) == 0) {
+    // the next stage's vd shortcut reads AvgPool2d(2, 2) of `out`: let this launch write it (shapes for ONE image decide, like every fusion)
+    // ... except the 2 GiB descriptor limits, which depend on the batch: beyond them (R50 / R101 at 1280 px from batch 41 on) this
+    // plan keeps the separate avg-pool launch - bit-identical results (test_f16x3_fused_vd_shortcut_average_equals_the_avgpool_launch)
+    ConvSpec with_avg = c3;
+    with_avg.avg_y = mk(nullptr, P, n, oh / 2, ow / 2, cout);
+    if (conv_avg_supported(probe(t2, b.out, c3)) && conv_sx_batch_fits(probe(t2, b.out, with_avg, /*plan_batch=*/true))) {
+      F.prepooled = act(P, n, oh / 2, ow / 2, cout);
+      F.have_prepooled = true;
+      c3.avg_y = F.prepooled;
+      // `out` is then read by nobody but this launch's own fused consumers when (a) the next stage's first reduce conv rides on it
+      // (next_y: stage 1's block 0 reads its c1 input from the tile) and (b) the stage output is not an encoder feature (stage 0):
+      // block 0 of the next stage takes its residual from the shortcut conv over the fused average, never from `out`
+      c3.y_dead = e->opts.dead_out && c3.next_y && si == 0 && b.oname.empty();
+    }
+  }
+  conv(b.pfx + ".c3", t2, b.out, c3);
+}
 
-  // ---- residual stages (HF:rt_detr_resnet.py:135-310) ------------------------------------------
-  Tensor feats[3];
-  int cin = c.embedding_size;
-  bool c1_done = false;                                         // this block's c1 already ran inside the previous block's last conv
-  Tensor t1_next;
-  bool have_prepooled = false;                                  // the 2 x 2 average of the stage input already exists (avg_fuse)
-  Tensor prepooled;
-  for (int si = 0; si < 4; ++si) {
-    const int cout = c.hidden_sizes[si];
-    // Buffers are recycled inside a stage (rtd_debug_option "arena_reuse"): the blocks' outputs ping-pong between two buffers
-    // (a block's input is dead once its last conv has read it as the residual) and the c1 / c2 temporaries of every block
-    // share one buffer each.  Fewer distinct lines means more of a stage lives in L2 + the 256 MB Infinity Cache, and dead
-    // activations are overwritten in cache instead of being written back to HBM.
-    Tensor pp[2], tb1, tb2;
-    if (e->opts.arena_reuse) {
-      const int s0 = (si > 0) ? 2 : 1;
-      const int oh0 = s0 == 2 ? down2(h) : h, ow0 = s0 == 2 ? down2(w) : w;
-      pp[0] = B.act(P, n, oh0, ow0, cout);
-      if (c.depths[si] > 1) pp[1] = B.act(P, n, oh0, ow0, cout);
-      const int mid0 = c.layer_type == RTD_LAYER_BOTTLENECK ? cout / 4 : cout;
-      tb1 = B.act(P, n, c.layer_type == RTD_LAYER_BOTTLENECK ? h : oh0, c.layer_type == RTD_LAYER_BOTTLENECK ? w : ow0, mid0);   // block 0's c1 runs before the stride
-      tb2 = B.act(P, n, oh0, ow0, mid0);
-    }
-    auto view = [&](const Tensor& buf, int hh_, int ww_, int cc_, const std::string& name) {
-      Tensor t = buf;
-      t.h = hh_; t.w = ww_; t.c = cc_; t.ld = cc_; t.bstride = (int64_t)hh_ * ww_ * cc_;
-      if (!name.empty()) B.plan->named[name] = t;
-      return t;
-    };
-    for (int bi = 0; bi < c.depths[si]; ++bi) {
-      const int stride = (si > 0 && bi == 0) ? 2 : 1;
-      const std::string pfx = nm("backbone.s%d.b%d", si, bi);
-      const int oh = stride == 2 ? down2(h) : h, ow = stride == 2 ? down2(w) : w;
-      const bool last = bi == c.depths[si] - 1;
-      const std::string oname = (last && si >= 1) ? nm("backbone%d", si - 1) : std::string();
-      Tensor res = cur;
-      bool has_sc;
-      if (c.layer_type == RTD_LAYER_BOTTLENECK) has_sc = (cin != cout) || stride != 1;
-      else has_sc = (bi == 0);
-      // The projection shortcut is a 1x1 conv over the block input whose only use is the pre-activation add of the block's last
-      // conv: y = relu(W_last * t + b_last + (W_sc * x_in + b_sc)).  In bf16 plans it is folded into that conv as extra K
-      // (ConvArgs::x2): the [B,OH,OW,cout] shortcut tensor is neither written nor read back (R50 bs 8 stage 0: 2 x 105 MB), one
-      // launch less, and the sum is rounded once instead of twice.  fp32 plans keep the reference's op sequence.
-      const int mid = cout / 4;
-      Tensor sc_in = cur;                                    // what the shortcut's 1x1 reads
-      bool fold_sc = false;
-      if (has_sc) {
-        // stride 2: AvgPool2d(2,2,ceil) then 1x1 (HF:rt_detr_resnet.py:199-213); extents are even here
-        if (stride == 2) {
-          if (have_prepooled) {
-            sc_in = prepooled;                                 // written by the previous stage's last conv (ConvArgs::avg_y)
-            have_prepooled = false;
-          } else {
-            Tensor pooled = B.act(P, n, oh, ow, cin);
-            B.push(pfx + ".avgpool", "avgpool", 4.0 * pooled.pixels() * cin, Builder::tbytes(cur) + Builder::tbytes(pooled),
-                   [cur, pooled](hipStream_t s) { launch_avgpool2(cur, pooled, s); });
-            sc_in = pooled;
-          }
-        }
-        if ((P == BF16 || SP) && e->opts.sc_fold) {
-          // shapes only: would the kernels take the folded launch?  Asked for ONE image whatever this plan's batch: every plan
-          // of an engine must use the same filters (the host copies are dropped after the first plan) and the same arithmetic
-          // (batch invariance), and a single image has the smallest grid
-          ConvArgs probe;
-          probe.opts = &e->conv_opts;
-          Tensor yv; yv.dt = P; yv.n = 1; yv.h = oh; yv.w = ow; yv.c = cout; yv.ld = cout; yv.bstride = (int64_t)oh * ow * cout; yv.p = (void*)16;
-          Tensor xv = yv; xv.c = xv.ld = (c.layer_type == RTD_LAYER_BOTTLENECK ? mid : cout); xv.bstride = (int64_t)oh * ow * xv.c;
-          Tensor x2v = sc_in; x2v.p = (void*)16; x2v.n = 1;
-          probe.x = xv; probe.x2 = x2v; probe.y = yv;
-          probe.KH = probe.KW = (c.layer_type == RTD_LAYER_BOTTLENECK ? 1 : 3); probe.stride = 1; probe.pad = probe.KH / 2;
-          fold_sc = conv_dual_supported(probe);
-        }
-        if (!fold_sc) {
-          res = B.act(P, n, oh, ow, cout);
-          B.conv(pfx + ".sc", sc_in, res, 1, 1, 0, ACT_NONE);
-        }
-      }
-      Tensor out = e->opts.arena_reuse ? view(pp[bi & 1], oh, ow, cout, oname) : B.act(P, n, oh, ow, cout, oname);
-      if (c.layer_type == RTD_LAYER_BOTTLENECK) {
-        // the c1 output of this block: with recycled buffers it is the stage's shared temporary, which the PREVIOUS block's last conv
-        // may already have filled (ConvArgs::next_*: the reduce conv fused into the expand conv that produced its input)
-        Tensor t1 = c1_done ? t1_next : (e->opts.arena_reuse ? view(tb1, h, w, mid, "") : B.act(P, n, h, w, mid));
-        if (!c1_done) B.conv(pfx + ".c1", cur, t1, 1, 1, 0, ACT_RELU);
-        c1_done = false;
-        Tensor t2 = e->opts.arena_reuse ? view(tb2, oh, ow, mid, "") : B.act(P, n, oh, ow, mid);
-        B.conv(pfx + ".c2", t1, t2, 3, stride, 1, ACT_RELU);
-        // fuse the NEXT block's c1 (1x1, stride 1, reads `out` at these extents) when the streaming kernel takes this conv: the next block of
-        // this stage, or (f16x3 plans) block 0 of the next stage, whose c1 runs before that block's stride
-        const Tensor* nx = nullptr;
-        std::string nx_name;
-        const bool same_stage = bi + 1 < c.depths[si];
-        const bool cross_stage = !same_stage && SP && si + 1 < 4;
-        if ((P == BF16 || SP) && e->opts.c1_fuse && (same_stage || cross_stage)) {
-          const int mid_n = same_stage ? mid : c.hidden_sizes[si + 1] / 4;
-          Tensor t1_shape = out; t1_shape.c = t1_shape.ld = mid_n; t1_shape.bstride = (int64_t)oh * ow * mid_n;
-          ConvArgs probe;                                        // this plan's shapes (fused and separate launches are bit-identical)
-          probe.opts = &e->conv_opts;
-          probe.x = t2; probe.x.p = (void*)16;
-          probe.y = out; probe.y.p = (void*)16;
-          if (fold_sc) { probe.x2 = sc_in; probe.x2.p = (void*)16; }
-          else { probe.res = res; probe.res.p = (void*)16; probe.res_mode = RES_PRE; }
-          probe.next_y = t1_shape; probe.next_y.p = (void*)16;
-          if (conv_next_supported(probe)) {
-            t1_next = (same_stage && e->opts.arena_reuse) ? view(tb1, oh, ow, mid_n, "") : B.act(P, n, oh, ow, mid_n);
-            nx = &t1_next; nx_name = (same_stage ? nm("backbone.s%d.b%d", si, bi + 1) : nm("backbone.s%d.b0", si + 1)) + ".c1"; c1_done = true;
-          }
-        }
-        if (SP && e->opts.avg_fuse && last && si + 1 < 4 && !fold_sc && (oh & 1) == 0 && (ow & 1) == 0) {
-          // the next stage's vd shortcut reads AvgPool2d(2, 2) of `out`: let this launch write it (shapes for ONE image decide, like every fusion)
-          ConvArgs probe;
-          probe.opts = &e->conv_opts;
-          probe.x = t2; probe.x.p = (void*)16; probe.x.n = 1;
-          probe.y = out; probe.y.p = (void*)16; probe.y.n = 1;
-          probe.res = res; probe.res.p = (void*)16; probe.res.n = 1; probe.res_mode = RES_PRE;
-          if (nx) { probe.next_y = *nx; probe.next_y.p = (void*)16; probe.next_y.n = 1; }
-          // ... except the 2 GiB descriptor limits, which depend on the batch: beyond them (R50 / R101 at 1280 px from batch 41 on) this
-          // plan keeps the separate avg-pool launch - bit-identical results (test_f16x3_fused_vd_shortcut_average_equals_the_avgpool_launch)
-          ConvArgs whole = probe;
-          whole.x.n = whole.y.n = whole.res.n = n;
-          if (nx) whole.next_y.n = n;
-          whole.avg_y = out; whole.avg_y.p = (void*)16; whole.avg_y.n = n; whole.avg_y.h = oh / 2; whole.avg_y.w = ow / 2;
-          whole.avg_y.ld = cout; whole.avg_y.bstride = (int64_t)(oh / 2) * (ow / 2) * cout;
-          if (conv_avg_supported(probe) && conv_sx_batch_fits(whole)) {
-            prepooled = B.act(P, n, oh / 2, ow / 2, cout);
-            have_prepooled = true;
-            B.avg_pending = true; B.avg_pending_y = prepooled;
-            // `out` is then read by nobody but this launch's own fused consumers when (a) the next stage's first reduce conv rides on it
-            // (nx: stage 1's block 0 reads its c1 input from the tile) and (b) the stage output is not an encoder feature (stage 0):
-            // block 0 of the next stage takes its residual from the shortcut conv over the fused average, never from `out`
-            if (e->opts.dead_out && nx && si == 0 && oname.empty()) B.y_dead_pending = true;
-          }
-        }
-        if (fold_sc) B.conv(pfx + ".c3", t2, out, 1, 1, 0, ACT_RELU, nullptr, RES_NONE, 0, &sc_in, pfx + ".sc", 0, nx, nx_name, ACT_RELU);
-        else B.conv(pfx + ".c3", t2, out, 1, 1, 0, ACT_RELU, &res, RES_PRE, 0, nullptr, "", 0, nx, nx_name, ACT_RELU);
-      } else {
-        Tensor t1 = e->opts.arena_reuse ? view(tb1, oh, ow, cout, "") : B.act(P, n, oh, ow, cout);
-        B.conv(pfx + ".c1", cur, t1, 3, stride, 1, ACT_RELU);
-        if (fold_sc) B.conv(pfx + ".c2", t1, out, 3, 1, 1, ACT_RELU, nullptr, RES_NONE, 0, &sc_in, pfx + ".sc");
-        else B.conv(pfx + ".c2", t1, out, 3, 1, 1, ACT_RELU, &res, RES_PRE);
-      }
-      cur = out; h = oh; w = ow; cin = cout;
-    }
-    if (si >= 1) feats[si - 1] = cur;
-    if (early_enc_proj && (si == 1 || si == 2)) {
-      // HF:v2.py:1348-1360 encoder input projection of this level, beside the next stage (side stream)
-      B.marker(1); B.lane = 1;
-      B.conv(si == 1 ? "enc.proj.0" : "enc.proj.1", cur, (si == 1 ? cat1 : cat0).slice_c(d, d), 1, 1, 0, ACT_NONE);
-      B.lane = 0;
-      enc_proj_forked = true;
-    }
-  }
+void Builder::basic_body(Flow& F, const StageBufs& sb, const Block& b) {
+  Tensor t1 = e->opts.arena_reuse ? view(sb.tb1, b.oh, b.ow, b.cout) : act(P, n, b.oh, b.ow, b.cout);
+  conv(b.pfx + ".c1", F.cur, t1, {.k = 3, .stride = b.stride, .pad = 1, .act = ACT_RELU});
+  if (b.fold_sc) conv(b.pfx + ".c2", t1, b.out, {.k = 3, .pad = 1, .act = ACT_RELU, .x2 = &b.sc_in, .name2 = b.pfx + ".sc"});
+  else conv(b.pfx + ".c2", t1, b.out, {.k = 3, .pad = 1, .act = ACT_RELU, .res = &b.res, .res_mode = RES_PRE});
+}
 
-  // ---- hybrid encoder (HF:v2.py:1348-1360 input proj, :1041-1095 AIFI, :1183-1209 FPN/PAN) ------
-  Tensor pcat0 = B.act(P, n, lh[1], lw[1], 2 * d);  // [down0 | lat1]
-  Tensor pcat1 = B.act(P, n, lh[2], lw[2], 2 * d);  // [down1 | lat0]
-  if (!early_enc_proj) {
-    B.conv("enc.proj.0", feats[0], cat1.slice_c(d, d), 1, 1, 0, ACT_NONE);
-    B.conv("enc.proj.1", feats[1], cat0.slice_c(d, d), 1, 1, 0, ACT_NONE);
-  }
-  const int L = lh[2] * lw[2];
-  Tensor t0 = B.act(F32, n, L, 1, d, "aifi_in");
-  {
-    Tensor t0v = t0; t0v.h = lh[2]; t0v.w = lw[2];
-    B.conv("enc.proj.2", feats[2], t0v, 1, 1, 0, ACT_NONE);
-  }
-  // AIFI in fp32 (0.5 % of the FLOPs; keeps the only global-mixing layer of the encoder exact)
-  Tensor pos;
-  pos.p = e->pos_dev; pos.dt = F32; pos.n = 1; pos.h = L; pos.w = 1; pos.c = d; pos.ld = d; pos.bstride = (int64_t)L * d;
-  Tensor t2;
-  const bool aifi_fused = e->opts.dec_fused && d == 256 && c.enc_heads == 8 && c.enc_ffn <= 1024;
-  if (aifi_fused) {
-    // ---- fused AIFI: 2 launches of decoder.hip's row kernel (modes 3, 4) instead of 9 ----------------------------
-    t2 = B.act(P, n, L, 1, d, "aifi_out");
-    Tensor qrows = B.act(F32, n, L, 1, d);
-    const int tl = (L + 15) / 16;
-    const int tlp = (tl + 1) & ~1;                              // the kernels stride the fragment buffers by an even tile count
-    float* kf = (float*)B.alloc((size_t)n * 8 * tlp * 512 * 4);
-    float* vf = (float*)B.alloc((size_t)n * 8 * tlp * 512 * 4);
-    DecArgs a0{};
-    a0.split = P != F32;
-    a0.attn_split = e->opts.attn_split & 1;                          // bit 0: AIFI, bit 1: decoder
-    a0.B = n; a0.Q = L; a0.D = d; a0.heads = 8; a0.S = 0; a0.n_levels = 3; a0.n_points = 4; a0.ffn = c.enc_ffn; a0.C = 4;
-    a0.hs_in = (const float*)t0.p; a0.qpos_in = e->pos_dev;
-    a0.q_in = (const float*)qrows.p; a0.q_out = (float*)qrows.p;
-    a0.kfrag_in = kf; a0.vfrag_in = vf; a0.kfrag_out = kf; a0.vfrag_out = vf;
-    DecArgs a3 = a0;
-    a3.mode = 3;
-    a3.qk = B.dec_lin("enc.aifi.qk", 2 * d, d); a3.v = B.dec_lin("enc.aifi.v", d, d);
-    B.push("enc.aifi.qkv", "dec_layer", 2.0 * n * L * 3.0 * d * d, (double)n * L * d * 4 * 5, [a3](hipStream_t s) { launch_dec_layer(a3, s); });
-    DecArgs a4 = a0;
-    a4.mode = 4;
-    a4.o = B.dec_lin("enc.aifi.o", d, d); a4.fc1 = B.dec_lin("enc.aifi.fc1", c.enc_ffn, d); a4.fc2 = B.dec_lin("enc.aifi.fc2", d, c.enc_ffn);
-    a4.ln1 = B.dec_ln("enc.aifi.ln1", d); a4.ln3 = B.dec_ln("enc.aifi.ln2", d);
-    Tensor t2f;
-    if (SP) { t2f = B.act(F32, n, L, 1, d); a4.hs_out = (float*)t2f.p; }
-    else if (P == BF16) a4.out_bf16 = t2.p;
-    else a4.hs_out = (float*)t2.p;
-    B.push("enc.aifi.layer", "dec_layer", 4.0 * n * (double)L * L * d + 2.0 * n * L * ((double)d * d + 2.0 * d * c.enc_ffn),
-           (double)n * L * d * 4 * 4, [a4](hipStream_t s) { launch_dec_layer(a4, s); });
-    if (SP) {
-      const Tensor src = t2f, dst = t2;
-      const int64_t rows = src.pixels();
-      B.push("enc.aifi.out_split", "convert", 0.0, 2 * Builder::tbytes(src), [src, dst, rows](hipStream_t s) {
-        launch_f32_to_split((const float*)src.p, src.ld, dst.p, dst.ld, rows, src.c, s);
-      });
-    }
-  } else {
-  Tensor xp = B.act(F32, n, L, 1, d);
-  B.push("enc.aifi.addpos", "add", (double)xp.pixels() * d, 3 * Builder::tbytes(xp), [t0, pos, xp](hipStream_t s) { launch_add(t0, pos, xp, s); });
+// ---- fused AIFI: 2 launches of decoder.hip's row kernel (modes 3, 4) instead of 9 ----------------------------
+Tensor Builder::aifi_fused(const Tensor& t0) {
+  const int d = c.enc_dim, L = t0.h;
+  Tensor t2 = act(P, n, L, 1, d, "aifi_out");
+  Tensor qrows = act(F32, n, L, 1, d);
+  const int tl = (L + 15) / 16;
+  const int tlp = (tl + 1) & ~1;                              // the kernels stride the fragment buffers by an even tile count
+  float* kf = (float*)alloc((size_t)n * 8 * tlp * 512 * 4);
+  float* vf = (float*)alloc((size_t)n * 8 * tlp * 512 * 4);
+  DecArgs a0{};
+  a0.split = P != F32;
+  a0.attn_split = e->opts.attn_split & 1;                          // bit 0: AIFI, bit 1: decoder
+  a0.B = n; a0.Q = L; a0.D = d; a0.heads = 8; a0.S = 0; a0.n_levels = 3; a0.n_points = 4; a0.ffn = c.enc_ffn; a0.C = 4;
+  a0.hs_in = (const float*)t0.p; a0.qpos_in = e->pos_dev;
+  a0.q_in = (const float*)qrows.p; a0.q_out = (float*)qrows.p;
+  a0.kfrag_in = kf; a0.vfrag_in = vf; a0.kfrag_out = kf; a0.vfrag_out = vf;
+  DecArgs a3 = a0;
+  a3.mode = 3;
+  a3.qk = dec_lin("enc.aifi.qk", 2 * d, d); a3.v = dec_lin("enc.aifi.v", d, d);
+  push("enc.aifi.qkv", "dec_layer", 2.0 * n * L * 3.0 * d * d, (double)n * L * d * 4 * 5, [a3](hipStream_t s) { launch_dec_layer(a3, s); });
+  DecArgs a4 = a0;
+  a4.mode = 4;
+  a4.o = dec_lin("enc.aifi.o", d, d); a4.fc1 = dec_lin("enc.aifi.fc1", c.enc_ffn, d); a4.fc2 = dec_lin("enc.aifi.fc2", d, c.enc_ffn);
+  a4.ln1 = dec_ln("enc.aifi.ln1", d); a4.ln3 = dec_ln("enc.aifi.ln2", d);
+  Tensor t2f;
+  if (SP) { t2f = act(F32, n, L, 1, d); a4.hs_out = (float*)t2f.p; }
+  else if (P == BF16) a4.out_bf16 = t2.p;
+  else a4.hs_out = (float*)t2.p;
+  push("enc.aifi.layer", "dec_layer", 4.0 * n * (double)L * L * d + 2.0 * n * L * ((double)d * d + 2.0 * d * c.enc_ffn),
+       (double)n * L * d * 4 * 4, [a4](hipStream_t s) { launch_dec_layer(a4, s); });
+  if (SP) split_into("enc.aifi.out_split", t2f, t2, 2 * tbytes(t2f));
+  return t2;
+}
+
+// ---- AIFI op by op (encoders the row kernel does not take, rtd_debug_option dec_fused = 0) ----------------------------
+Tensor Builder::aifi_by_op(const Tensor& t0) {
+  const int d = c.enc_dim, L = t0.h;
+  const Tensor pos = mk(e->pos_dev, F32, 1, L, 1, d);
+  Tensor xp = act(F32, n, L, 1, d);
+  push("enc.aifi.addpos", "add", (double)xp.pixels() * d, 3 * tbytes(xp), [t0, pos, xp](hipStream_t s) { launch_add(t0, pos, xp, s); });
   // f16x3 plans run the five linears on the pair kernels (inputs converted to hi / lo rows, fp32 rows out; fc1 hands fc2 a pair tensor):
   // on fp32 MFMAs they were 0.33 ms of R101 1280's step.  The attention itself stays exact fp32.
   const bool aifi_pair = SP && e->opts.aifi_pair && d % SPLIT_GROUP == 0 && c.enc_ffn % SPLIT_GROUP == 0;
-  auto pin = [&](const char* nm_, const Tensor& x) { return aifi_pair ? B.to_split(std::string(nm_) + ".in_split", x) : x; };
-  Tensor qk = B.linear("enc.aifi.qk", pin("enc.aifi.qk", xp), 2 * d, F32, ACT_NONE);
-  Tensor vv = B.linear("enc.aifi.v", pin("enc.aifi.v", t0), d, F32, ACT_NONE);
-  Tensor att = B.act(F32, n, L, 1, d);
-  {
-    const int heads = c.enc_heads;
-    B.push("enc.aifi.attn", "attention", 4.0 * n * (double)L * L * d, Builder::tbytes(qk) + 2 * Builder::tbytes(vv),
-           [qk, vv, att, heads](hipStream_t s) { launch_attention(qk, vv, att, heads, s); });
+  auto pin = [&](const char* nm_, const Tensor& x) { return aifi_pair ? to_split(std::string(nm_) + ".in_split", x) : x; };
+  Tensor qk = linear("enc.aifi.qk", pin("enc.aifi.qk", xp), 2 * d, F32, ACT_NONE);
+  Tensor vv = linear("enc.aifi.v", pin("enc.aifi.v", t0), d, F32, ACT_NONE);
+  Tensor att = act(F32, n, L, 1, d);
+  const int heads = c.enc_heads;
+  push("enc.aifi.attn", "attention", 4.0 * n * (double)L * L * d, tbytes(qk) + 2 * tbytes(vv),
+       [qk, vv, att, heads](hipStream_t s) { launch_attention(qk, vv, att, heads, s); });
+  Tensor ao = linear("enc.aifi.o", pin("enc.aifi.o", att), d, F32, ACT_NONE, &t0);
+  Tensor t1 = layernorm("enc.aifi.ln1", ao, F32);
+  Tensor f1 = linear("enc.aifi.fc1", pin("enc.aifi.fc1", t1), c.enc_ffn, aifi_pair ? F16X2 : F32, ACT_GELU);
+  Tensor f2 = linear("enc.aifi.fc2", f1, d, F32, ACT_NONE, &t1);
+  return layernorm("enc.aifi.ln2", f2, P, "aifi_out");
+}
+
+// One CSPRep layer of the FPN / PAN over `cat`.  `up_src`: the half-resolution tensor whose 2x nearest upsampling is the first half of
+// `cat`.  In bf16 plans the CSP's first 1x1 conv reads it directly (ConvArgs::x_up2 + x2 = the second half of cat): no upsample launch,
+// no upsampled tensor.
+Tensor Builder::csp(const std::string& pfx, const Tensor& cat, const std::string& oname, const Tensor* up_src) {
+  const int d = c.enc_dim, hh = c.csp_hidden;
+  Tensor h12 = act(P, cat.n, cat.h, cat.w, 2 * hh);
+  const Tensor second = cat.slice_c(d, d);
+  const ConvSpec folded{.act = ACT_SILU, .x2 = &second, .x_up2 = 1};
+  if (up_src && (P == BF16 || SP) && e->opts.up_fold && conv_dual_supported(probe(*up_src, h12, folded))) {   // shapes for ONE image, like the shortcut fold
+    conv(pfx + ".c12", *up_src, h12, folded);
+  } else {
+    if (up_src) {
+      const Tensor src = *up_src, dst = cat.slice_c(0, d);
+      push(pfx + ".up", "upsample2x", 0.0, tbytes(src) + 4 * tbytes(src), [src, dst](hipStream_t s) { launch_upsample2x(src, dst, s); });
+    }
+    conv(pfx + ".c12", cat, h12, {.act = ACT_SILU});
   }
-  Tensor ao = B.linear("enc.aifi.o", pin("enc.aifi.o", att), d, F32, ACT_NONE, &t0);
-  Tensor t1 = B.layernorm("enc.aifi.ln1", ao, F32);
-  Tensor f1 = B.linear("enc.aifi.fc1", pin("enc.aifi.fc1", t1), c.enc_ffn, aifi_pair ? F16X2 : F32, ACT_GELU);
-  Tensor f2 = B.linear("enc.aifi.fc2", f1, d, F32, ACT_NONE, &t1);
-  t2 = B.layernorm("enc.aifi.ln2", f2, P, "aifi_out");
+  Tensor r0 = act(P, cat.n, cat.h, cat.w, hh);
+  conv(pfx + ".rep0", h12.slice_c(0, hh), r0, {.k = 3, .pad = 1, .act = ACT_SILU});
+  Tensor r1 = act(P, cat.n, cat.h, cat.w, hh);
+  conv(pfx + ".rep1", r0, r1, {.k = 3, .pad = 1, .act = ACT_SILU});
+  Tensor h2 = h12.slice_c(hh, hh);
+  Tensor r2 = act(P, cat.n, cat.h, cat.w, hh, hh == d ? oname : std::string());
+  conv(pfx + ".rep2", r1, r2, {.k = 3, .pad = 1, .act = ACT_SILU, .res = &h2, .res_mode = RES_POST});
+  if (hh == d) return r2;
+  Tensor o = act(P, cat.n, cat.h, cat.w, d, oname);
+  conv(pfx + ".c3", r2, o, {.act = ACT_SILU});
+  return o;
+}
+
+// ---- hybrid encoder (HF:v2.py:1348-1360 input proj, :1041-1095 AIFI, :1183-1209 FPN/PAN) and the decoder's input projections
+// (HF:v2.py:1533-1623); returns the decoder's memory
+Tensor Builder::encoder(Flow& F) {
+  const int d = c.enc_dim, dm = c.d_model;
+  const int* lh = e->lvl_h; const int* lw = e->lvl_w;
+  Tensor pcat0 = act(P, n, lh[1], lw[1], 2 * d);  // [down0 | lat1]
+  Tensor pcat1 = act(P, n, lh[2], lw[2], 2 * d);  // [down1 | lat0]
+  if (!(e->opts.side_stream & 4)) {
+    conv("enc.proj.0", F.feats[0], F.cat1.slice_c(d, d), {});
+    conv("enc.proj.1", F.feats[1], F.cat0.slice_c(d, d), {});
   }
+  const int L = lh[2] * lw[2];
+  Tensor t0 = act(F32, n, L, 1, d, "aifi_in");
+  conv("enc.proj.2", F.feats[2], mk(t0.p, F32, n, lh[2], lw[2], d), {});
+  // AIFI in fp32 (0.5 % of the FLOPs; keeps the only global-mixing layer of the encoder exact)
+  const bool fused = e->opts.dec_fused && d == 256 && c.enc_heads == 8 && c.enc_ffn <= 1024;
+  Tensor t2 = fused ? aifi_fused(t0) : aifi_by_op(t0);
   t2.h = lh[2]; t2.w = lw[2];
 
-  // `up_src`: the half-resolution tensor whose 2x nearest upsampling is the first half of `cat`.  In bf16 plans the CSP's first
-  // 1x1 conv reads it directly (ConvArgs::x_up2 + x2 = the second half of cat): no upsample launch, no upsampled tensor.
-  auto csp = [&](const std::string& pfx, const Tensor& cat, const std::string& oname, const Tensor* up_src = nullptr) {
-    Tensor h12 = B.act(P, cat.n, cat.h, cat.w, 2 * hh);
-    bool up_fold = false;
-    if (up_src && (P == BF16 || SP) && e->opts.up_fold) {
-      ConvArgs probe;                                          // shapes for ONE image, like the shortcut fold
-      probe.opts = &e->conv_opts;
-      probe.x = *up_src; probe.x.p = (void*)16; probe.x.n = 1;
-      probe.x2 = cat.slice_c(d, d); probe.x2.p = (void*)16; probe.x2.n = 1;
-      probe.y = h12; probe.y.p = (void*)16; probe.y.n = 1;
-      probe.x_up2 = 1;
-      up_fold = conv_dual_supported(probe);
-    }
-    if (up_fold) {
-      Tensor second = cat.slice_c(d, d);
-      B.conv(pfx + ".c12", *up_src, h12, 1, 1, 0, ACT_SILU, nullptr, RES_NONE, 0, &second, "", 1);
-    } else {
-      if (up_src) {
-        const Tensor src = *up_src, dst = cat.slice_c(0, d);
-        B.push(pfx + ".up", "upsample2x", 0.0, Builder::tbytes(src) + 4 * Builder::tbytes(src), [src, dst](hipStream_t s) { launch_upsample2x(src, dst, s); });
-      }
-      B.conv(pfx + ".c12", cat, h12, 1, 1, 0, ACT_SILU);
-    }
-    Tensor r0 = B.act(P, cat.n, cat.h, cat.w, hh);
-    B.conv(pfx + ".rep0", h12.slice_c(0, hh), r0, 3, 1, 1, ACT_SILU);
-    Tensor r1 = B.act(P, cat.n, cat.h, cat.w, hh);
-    B.conv(pfx + ".rep1", r0, r1, 3, 1, 1, ACT_SILU);
-    Tensor h2 = h12.slice_c(hh, hh);
-    if (hh == d) {
-      Tensor r2 = B.act(P, cat.n, cat.h, cat.w, hh, oname);
-      B.conv(pfx + ".rep2", r1, r2, 3, 1, 1, ACT_SILU, &h2, RES_POST);
-      return r2;
-    }
-    Tensor r2 = B.act(P, cat.n, cat.h, cat.w, hh);
-    B.conv(pfx + ".rep2", r1, r2, 3, 1, 1, ACT_SILU, &h2, RES_POST);
-    Tensor o = B.act(P, cat.n, cat.h, cat.w, d, oname);
-    B.conv(pfx + ".c3", r2, o, 1, 1, 0, ACT_SILU);
-    return o;
-  };
   // FPN top-down
   Tensor lat0 = pcat1.slice_c(d, d);
-  B.conv("enc.lat.0", t2, lat0, 1, 1, 0, ACT_SILU);
-  if (enc_proj_forked) B.marker(2);                  // the projection halves of cat0 / cat1 are complete
-  Tensor F0 = csp("enc.fpn.0", cat0, "", &lat0);
+  conv("enc.lat.0", t2, lat0, {.act = ACT_SILU});
+  if (F.side_open) { marker(2); F.side_open = false; }   // the projection halves of cat0 / cat1 are complete
+  Tensor F0 = csp("enc.fpn.0", F.cat0, "", &lat0);
   Tensor lat1 = pcat0.slice_c(d, d);
-  B.conv("enc.lat.1", F0, lat1, 1, 1, 0, ACT_SILU);
-  Tensor F1 = csp("enc.fpn.1", cat1, "enc0", &lat1);
-  // ---- decoder input (HF:v2.py:1533-1623): the projections of the two larger levels only need F1 / P1, so (side_stream bit 1) they run on the
+  conv("enc.lat.1", F0, lat1, {.act = ACT_SILU});
+  Tensor F1 = csp("enc.fpn.1", F.cat1, "enc0", &lat1);
+  // decoder input: the projections of the two larger levels only need F1 / P1, so (side_stream bit 1) they run on the
   // side stream beside the PAN path, whose 40^2 and 20^2 grids leave a quarter to two thirds of the CUs idle
-  const int dm = c.d_model, S = e->S, Q = c.num_queries, C = c.num_classes, NL = c.dec_layers;
-  Tensor mem = B.act(P, n, S, 1, dm, "memory");
+  Tensor mem = act(P, n, e->S, 1, dm, "memory");
   const bool early_proj = (e->opts.side_stream & 2) != 0;
   auto dec_proj = [&](int l, const Tensor& src) {
     Tensor v = mem;
-    v.p = B.dry ? nullptr : (char*)mem.p + (size_t)e->lvl_start[l] * dm * dtype_size(P);
+    v.p = dry ? nullptr : (char*)mem.p + (size_t)e->lvl_start[l] * dm * dtype_size(P);
     v.h = lh[l]; v.w = lw[l];
-    B.conv(nm("dec.proj.%d", l), src, v, 1, 1, 0, ACT_NONE);
+    conv(nm("dec.proj.%d", l), src, v, {});
   };
   // PAN bottom-up
-  if (early_proj) { B.marker(1); B.lane = 1; dec_proj(0, F1); B.lane = 0; }
-  B.conv("enc.down.0", F1, pcat0.slice_c(0, d), 3, 2, 1, ACT_SILU);
+  if (early_proj) on_side([&] { dec_proj(0, F1); });
+  conv("enc.down.0", F1, pcat0.slice_c(0, d), {.k = 3, .stride = 2, .pad = 1, .act = ACT_SILU});
   Tensor P1 = csp("enc.pan.0", pcat0, "enc1");
-  if (early_proj) { B.marker(1); B.lane = 1; dec_proj(1, P1); B.lane = 0; }
-  B.conv("enc.down.1", P1, pcat1.slice_c(0, d), 3, 2, 1, ACT_SILU);
+  if (early_proj) on_side([&] { dec_proj(1, P1); });
+  conv("enc.down.1", P1, pcat1.slice_c(0, d), {.k = 3, .stride = 2, .pad = 1, .act = ACT_SILU});
   Tensor P2 = csp("enc.pan.1", pcat1, "enc2");
   if (!early_proj) { dec_proj(0, F1); dec_proj(1, P1); }
   dec_proj(2, P2);
-  if (early_proj) B.marker(2);
-  // The query-selection chain (enc_output -> scores -> top-k -> gather: narrow grids, latency-bound) and the value projection both start
-  // from `mem` and meet again in the decoder prologue: the chain runs on the side stream beside the projection (e->opts.side_stream).
-  const bool side = (e->opts.side_stream & 1) != 0;
-  if (side) { B.marker(1); B.lane = 1; }
+  if (early_proj) marker(2);
+  return mem;
+}
+
+// The query-selection chain (enc_output -> scores -> top-k -> gather: narrow grids, latency-bound) and the value projection both start
+// from `mem` and meet again in the decoder prologue: the chain runs on the side stream beside the projection (e->opts.side_stream).
+Queries Builder::select_queries(Flow& F, const Tensor& mem) {
+  const int dm = c.d_model, S = e->S, Q = c.num_queries, C = c.num_classes;
+  const int n = this->n;
+  // not on_side(): the join sits after the decoder prologue (decoder_fused), not at the end of this chain
+  if (e->opts.side_stream & 1) { marker(1); lane = 1; F.side_open = true; }
   // enc_output on masked memory, fp32 from here on (selection + decoder are exact fp32)
-  Tensor eo = B.linear("dec.enc_out.fc", mem, dm, F32, ACT_NONE);
-  if (!B.dry && e->n_invalid > 0) {
-    const float* bias = get_weight(e, "dec.enc_out.fc", P, dm, dm).bias;
+  Tensor eo = linear("dec.enc_out.fc", mem, dm, F32, ACT_NONE);
+  if (!dry && e->n_invalid > 0) {
+    const float* bias = get_weight(e, {{"dec.enc_out.fc", dm}}, P, dm).bias;
     const int32_t* rows = e->invalid_rows_dev;
     const int nr = e->n_invalid;
-    B.push("dec.mask_rows", "set_rows", 0.0, (double)n * nr * dm * 4, [eo, rows, nr, S, bias](hipStream_t s) { launch_set_rows(eo, rows, nr, S, bias, s); });
+    push("dec.mask_rows", "set_rows", 0.0, (double)n * nr * dm * 4, [eo, rows, nr, S, bias](hipStream_t s) { launch_set_rows(eo, rows, nr, S, bias, s); });
   }
-  const bool fused = e->opts.dec_fused && dm == 256 && c.dec_heads == 8 && c.dec_ffn <= 1024 && C <= 512 && c.n_levels == 3 && c.n_points == 4;
-  const bool sel_fused = fused && e->opts.sel_fused && eo.ld == dm;
-  float* mx = (float*)B.alloc((size_t)n * S * 4);
-  {
-    Tensor t; t.p = mx; t.dt = F32; t.n = n; t.h = S; t.w = 1; t.c = 1; t.ld = 1; t.bstride = S;
-    plan->named["enc_cls_max"] = t;
-  }
+  const bool sel_fused = dec_fused() && e->opts.sel_fused && eo.ld == dm;
+  float* mx = (float*)alloc((size_t)n * S * 4);
+  named("enc_cls_max", mk(mx, F32, n, S, 1, 1));
   Tensor om;
   DecLN sel_ln{};
   if (sel_fused) {
     // LayerNorm + enc_score_head + class max in one launch: the normalised memory (69 MB fp32 at R50 bs 8) and the logits are
     // never written; the selected rows are normalised again in the gather
     SelArgs sa{};
-    if (!B.dry) {
-      DevWeight w = get_weight_packed(e, "dec.enc_score", C, dm, dm, false);
-      sa.score.w = (const float*)w.w; sa.score.b = w.bias; sa.score.ldw = w.Kpad; sa.score.N = C; sa.score.K = w.K;
-      sel_ln.g = get_vec(e, "dec.enc_out.ln.g", dm); sel_ln.b = get_vec(e, "dec.enc_out.ln.b", dm);
-      sa.ln = sel_ln;
-    }
+    sa.score = dec_lin("dec.enc_score", C, dm, dm, /*split=*/false);
+    sa.ln = sel_ln = dec_ln("dec.enc_out.ln", dm);
     sa.x = (const float*)eo.p; sa.ldx = eo.ld; sa.rows = n * S; sa.C = C; sa.rows_per_image = S; sa.mx = mx;
-    B.push("dec.select_score", "select_score", (double)n * S * (2.0 * C * dm + 8.0 * dm), (double)n * S * dm * 4 + (double)n * S * 4,
-           [sa](hipStream_t s) { launch_select_score(sa, s); });
+    push("dec.select_score", "select_score", (double)n * S * (2.0 * C * dm + 8.0 * dm), (double)n * S * dm * 4 + (double)n * S * 4,
+         [sa](hipStream_t s) { launch_select_score(sa, s); });
   } else {
-    om = B.layernorm("dec.enc_out.ln", eo, F32, "output_memory");
-    Tensor cls = B.linear("dec.enc_score", om, C, F32, ACT_NONE);
-    B.push("dec.enc_rowmax", "rowmax", (double)n * S * C, (double)n * S * C * 4, [cls, mx](hipStream_t s) { launch_rowmax(cls, mx, s); });
+    om = layernorm("dec.enc_out.ln", eo, F32, "output_memory");
+    Tensor cls = linear("dec.enc_score", om, C, F32, ACT_NONE);
+    push("dec.enc_rowmax", "rowmax", (double)n * S * C, (double)n * S * C * 4, [cls, mx](hipStream_t s) { launch_rowmax(cls, mx, s); });
   }
-  int32_t* tk = (int32_t*)B.alloc((size_t)n * Q * 4);
+  Queries q;
+  int32_t* tk = q.tk = (int32_t*)alloc((size_t)n * Q * 4);
   plan->tk_idx = tk;
-  {
-    Tensor t; t.p = tk; t.dt = I32; t.n = n; t.h = Q; t.w = 1; t.c = 1; t.ld = 1; t.bstride = Q;
-    plan->named["topk"] = t;          // the memory-token ids the decoder ran on (after rtd_debug_force_topk, the forced ones)
-  }
-  {
-    const int32_t* forced = e->forced_idx; const int32_t* flag = e->force_flag;
-    B.push("dec.enc_topk", "topk", 0.0, (double)n * S * 4 * 6, [mx, n, S, Q, tk](hipStream_t s) { launch_topk(mx, n, S, Q, tk, nullptr, s); });
-    // test hook (rtd_debug_force_topk): overrides the selection with the caller's indices.  Not part of the product graph: the op is
-    // skipped - and absent from the built hipGraph - until the hook is used on this handle
-    B.push("dec.force_topk", "select", 0.0, 0.0, [tk, forced, flag, n, Q](hipStream_t s) {
-      launch_force_idx(tk, forced, flag, n * Q, s);
-    });
-    if (!B.dry) plan->ops.back().debug_only = true;
-  }
-  Tensor target = B.act(F32, n, Q, 1, dm, "target");
+  named("topk", mk(tk, I32, n, Q, 1, 1));          // the memory-token ids the decoder ran on (after rtd_debug_force_topk, the forced ones)
+  const int32_t* forced = e->forced_idx; const int32_t* flag = e->force_flag;
+  push("dec.enc_topk", "topk", 0.0, (double)n * S * 4 * 6, [mx, n, S, Q, tk](hipStream_t s) { launch_topk(mx, n, S, Q, tk, nullptr, s); });
+  // test hook (rtd_debug_force_topk): overrides the selection with the caller's indices.  Not part of the product graph: the op is
+  // skipped - and absent from the built hipGraph - until the hook is used on this handle
+  push("dec.force_topk", "select", 0.0, 0.0, [tk, forced, flag, n, Q](hipStream_t s) { launch_force_idx(tk, forced, flag, n * Q, s); });
+  if (!dry) plan->ops.back().debug_only = true;
+  Tensor target = q.target = act(F32, n, Q, 1, dm, "target");
   if (sel_fused) {
     const float* xp = (const float*)eo.p; const int64_t ldx = eo.ld; float* tp = (float*)target.p; const int64_t ldt = target.ld;
-    B.push("dec.gather_target", "gather", 8.0 * n * Q * dm, 2.0 * n * Q * dm * 4, [xp, ldx, S, tk, n, Q, sel_ln, tp, ldt](hipStream_t s) {
+    push("dec.gather_target", "gather", 8.0 * n * Q * dm, 2.0 * n * Q * dm * 4, [xp, ldx, S, tk, n, Q, sel_ln, tp, ldt](hipStream_t s) {
       launch_gather_ln(xp, ldx, S, tk, n, Q, sel_ln, tp, ldt, s);
     });
   } else {
-    B.push("dec.gather_target", "gather", 0.0, 2.0 * n * Q * dm * 4, [om, tk, S, target](hipStream_t s) { launch_gather_rows(om, tk, S, target, s); });
+    push("dec.gather_target", "gather", 0.0, 2.0 * n * Q * dm * 4, [om, tk, S, target](hipStream_t s) { launch_gather_rows(om, tk, S, target, s); });
   }
-  B.lane = 0;
-  // value_proj of every decoder layer in ONE GEMM (they all read `mem`, HF:v2.py:177)
-  Tensor vall = B.linear("dec.vp_all", mem, NL * dm, SP ? F32 : P, ACT_NONE, nullptr, "value_all");   // the samplers read bf16 or fp32 values
-  // the join sits after the decoder prologue in the fused plan (the prologue needs the selected rows, not the value maps: it stays on the
-  // side stream and the chain's 150 + 45 us run beside the projection's 175 instead of 45 after it)
-  bool side_joined = !side;
-  const int npts = c.dec_heads * c.n_levels * c.n_points;
-  float* ref_unact8 = (float*)B.alloc((size_t)n * Q * 8 * 4);
-  float* ref8 = (float*)B.alloc((size_t)n * Q * 8 * 4);
-  Tensor ref8t; ref8t.p = ref8; ref8t.dt = F32; ref8t.n = n; ref8t.h = Q; ref8t.w = 1; ref8t.c = 8; ref8t.ld = 8; ref8t.bstride = (int64_t)Q * 8;
-  plan->named["ref"] = ref8t;
-  {
-    Tensor ru = ref8t; ru.p = ref_unact8;
-    plan->named["ref_unact"] = ru;
-  }
-  Tensor hs = target;
-  Tensor logits;
-  if (!fused && !side_joined) { B.marker(2); side_joined = true; }
-  if (fused) {
-    // ---- fused decoder: 1 prologue + per layer (self-attention kernel + one fused kernel), decoder.hip -----
-    Tensor qpos = B.act(F32, n, Q, 1, dm);
-    Tensor qrows = B.act(F32, n, Q, 1, dm);
-    const int dtiles = (Q + 15) / 16;
-    float* kfrag[2]; float* vfrag[2];
-    for (int i = 0; i < 2; ++i) {
-      kfrag[i] = (float*)B.alloc((size_t)n * c.dec_heads * ((dtiles + 1) & ~1) * 512 * 4);
-      vfrag[i] = (float*)B.alloc((size_t)n * c.dec_heads * ((dtiles + 1) & ~1) * 512 * 4);
-    }
-    logits = B.act(F32, n, Q, 1, C, "logits");
-    DecArgs base{};
-    base.split = P != F32;
-    base.attn_split = (e->opts.attn_split >> 1) & 1;
-    base.B = n; base.Q = Q; base.D = dm; base.heads = c.dec_heads; base.S = S; base.n_levels = c.n_levels;
-    base.n_points = c.n_points; base.ffn = c.dec_ffn; base.C = C; base.offset_scale = c.offset_scale;
-    base.ref8 = ref8; base.ref_unact8 = ref_unact8; base.anchors = e->anchors_dev; base.tk_idx = tk;
-    base.value = vall.p; base.value_ld = (int)vall.ld; base.value_f32 = vall.dt == F32; base.lvl = e->lvl_dev;
-    base.qpos_in = (const float*)qpos.p; base.qpos_out = (float*)qpos.p;
-    base.q_in = (const float*)qrows.p; base.q_out = (float*)qrows.p;
-    base.logits = (float*)logits.p;
-    base.qp0 = B.dec_lin("dec.qpos.0", 2 * dm, 8, 64);   // K padded to one 64-wide step (zero weights / zero LDS columns)
-    base.qp1 = B.dec_lin("dec.qpos.1", dm, 2 * dm);
-    const double row_flops_next = 2.0 * n * Q * ((double)8 * 2 * dm + 2.0 * dm * dm + 2.0 * dm * dm + (double)dm * dm);
-    {
-      DecArgs a = base;
-      a.mode = 0;
-      a.hs_in = (const float*)target.p; a.hs_out = nullptr;
-      a.bb0 = B.dec_lin("dec.enc_bbox.0", dm, dm); a.bb1 = B.dec_lin("dec.enc_bbox.1", dm, dm); a.bb2 = B.dec_lin("dec.enc_bbox.2", 4, dm);
-      a.qk = B.dec_lin("dec.l0.sa.qk", 2 * dm, dm); a.v = B.dec_lin("dec.l0.sa.v", dm, dm);
-      a.kfrag_out = kfrag[0]; a.vfrag_out = vfrag[0];
-      if (!side_joined) B.lane = 1;
-      B.push("dec.prologue", "dec_layer", 2.0 * n * Q * (2.0 * dm * dm + 4.0 * dm) + row_flops_next, (double)n * Q * dm * 4 * 6,
-             [a](hipStream_t s) { launch_dec_layer(a, s); });
-      B.lane = 0;
-      if (!side_joined) { B.marker(2); side_joined = true; }
-    }
-    for (int i = 0; i < NL; ++i) {
-      const std::string p = nm("dec.l%d", i);
-      Tensor hs_out = B.act(F32, n, Q, 1, dm, nm("dec%d.hs", i));
-      DecArgs a = base;
-      const bool last = i == NL - 1;
-      a.mode = last ? 2 : 1;
-      a.hs_in = (const float*)hs.p; a.hs_out = (float*)hs_out.p;
-      a.value_coff = i * dm;
-      a.kfrag_in = kfrag[i & 1]; a.vfrag_in = vfrag[i & 1];
-      a.kfrag_out = kfrag[(i + 1) & 1]; a.vfrag_out = vfrag[(i + 1) & 1];
-      a.o = B.dec_lin(p + ".sa.o", dm, dm); a.ln1 = B.dec_ln(p + ".ln1", dm);
-      a.offaw = B.dec_lin(p + ".ca.offaw", 3 * npts, dm); a.op = B.dec_lin(p + ".ca.op", dm, dm); a.ln2 = B.dec_ln(p + ".ln2", dm);
-      a.fc1 = B.dec_lin(p + ".fc1", c.dec_ffn, dm); a.fc2 = B.dec_lin(p + ".fc2", dm, c.dec_ffn); a.ln3 = B.dec_ln(p + ".ln3", dm);
-      a.bb0 = B.dec_lin(nm("dec.bbox.%d.0", i), dm, dm); a.bb1 = B.dec_lin(nm("dec.bbox.%d.1", i), dm, dm); a.bb2 = B.dec_lin(nm("dec.bbox.%d.2", i), 4, dm);
-      if (last) a.cls = B.dec_lin("dec.cls", C, dm);
-      else { a.qk = B.dec_lin(nm("dec.l%d.sa.qk", i + 1), 2 * dm, dm); a.v = B.dec_lin(nm("dec.l%d.sa.v", i + 1), dm, dm); }
-      const double fl = 4.0 * n * (double)Q * Q * dm + 2.0 * n * Q * ((double)dm * dm * 2 + 3.0 * npts * dm + 2.0 * dm * c.dec_ffn + 2.0 * dm * dm + 4.0 * dm) +
-                        2.0 * n * Q * dm * c.n_levels * c.n_points * 4 + (last ? 2.0 * n * Q * dm * C : row_flops_next);
-      B.push(p + ".fused", "dec_layer", fl, (double)n * Q * dm * 4 * 8, [a](hipStream_t s) { launch_dec_layer(a, s); });
-      hs = hs_out;
-    }
-  } else {
-  Tensor b0 = B.linear("dec.enc_bbox.0", target, dm, F32, ACT_RELU);
-  Tensor b1 = B.linear("dec.enc_bbox.1", b0, dm, F32, ACT_RELU);
-  Tensor b2 = B.linear("dec.enc_bbox.2", b1, 4, F32, ACT_NONE);
-  {
-    const float* anchors = e->anchors_dev;
-    B.push("dec.ref_init", "ref_init", 0.0, (double)n * Q * 64, [b2, anchors, tk, S, ref_unact8, ref8](hipStream_t s) { launch_ref_init(b2, anchors, tk, S, ref_unact8, ref8, s); });
-  }
+  lane = 0;
+  return q;
+}
 
-  // ---- decoder layers (HF:v2.py:603-661, layer :339-431) ---------------------------------------
+Decoded Builder::decoder(Flow& F, const Tensor& mem, const Queries& q) {
+  const int dm = c.d_model, Q = c.num_queries;
+  // value_proj of every decoder layer in ONE GEMM (they all read `mem`, HF:v2.py:177)
+  Tensor vall = linear("dec.vp_all", mem, c.dec_layers * dm, SP ? F32 : P, ACT_NONE, nullptr, "value_all");   // the samplers read bf16 or fp32 values
+  float* ref_unact8 = (float*)alloc((size_t)n * Q * 8 * 4);
+  Decoded out;
+  out.ref8 = (float*)alloc((size_t)n * Q * 8 * 4);
+  const Tensor ref8t = named("ref", mk(out.ref8, F32, n, Q, 1, 8));
+  named("ref_unact", mk(ref_unact8, F32, n, Q, 1, 8));
+  if (dec_fused()) {
+    out.logits = decoder_fused(F, q, vall, out.ref8, ref_unact8);
+  } else {
+    if (F.side_open) { marker(2); F.side_open = false; }
+    out.logits = decoder_by_op(q, vall, ref8t, ref_unact8);
+  }
+  return out;
+}
+
+// ---- fused decoder: 1 prologue + per layer (self-attention kernel + one fused kernel), decoder.hip -----
+Tensor Builder::decoder_fused(Flow& F, const Queries& q, const Tensor& vall, float* ref8, float* ref_unact8) {
+  const int dm = c.d_model, S = e->S, Q = c.num_queries, C = c.num_classes, NL = c.dec_layers;
+  const int npts = c.dec_heads * c.n_levels * c.n_points;
+  Tensor qpos = act(F32, n, Q, 1, dm);
+  Tensor qrows = act(F32, n, Q, 1, dm);
+  const int dtiles = (Q + 15) / 16;
+  float* kfrag[2]; float* vfrag[2];
+  for (int i = 0; i < 2; ++i) {
+    kfrag[i] = (float*)alloc((size_t)n * c.dec_heads * ((dtiles + 1) & ~1) * 512 * 4);
+    vfrag[i] = (float*)alloc((size_t)n * c.dec_heads * ((dtiles + 1) & ~1) * 512 * 4);
+  }
+  Tensor logits = act(F32, n, Q, 1, C, "logits");
+  DecArgs base{};
+  base.split = P != F32;
+  base.attn_split = (e->opts.attn_split >> 1) & 1;
+  base.B = n; base.Q = Q; base.D = dm; base.heads = c.dec_heads; base.S = S; base.n_levels = c.n_levels;
+  base.n_points = c.n_points; base.ffn = c.dec_ffn; base.C = C; base.offset_scale = c.offset_scale;
+  base.ref8 = ref8; base.ref_unact8 = ref_unact8; base.anchors = e->anchors_dev; base.tk_idx = q.tk;
+  base.value = vall.p; base.value_ld = (int)vall.ld; base.value_f32 = vall.dt == F32; base.lvl = e->lvl_dev;
+  base.qpos_in = (const float*)qpos.p; base.qpos_out = (float*)qpos.p;
+  base.q_in = (const float*)qrows.p; base.q_out = (float*)qrows.p;
+  base.logits = (float*)logits.p;
+  base.qp0 = dec_lin("dec.qpos.0", 2 * dm, 8, 64);   // K padded to one 64-wide step (zero weights / zero LDS columns)
+  base.qp1 = dec_lin("dec.qpos.1", dm, 2 * dm);
+  const double row_flops_next = 2.0 * n * Q * ((double)8 * 2 * dm + 2.0 * dm * dm + 2.0 * dm * dm + (double)dm * dm);
+  {
+    DecArgs a = base;
+    a.mode = 0;
+    a.hs_in = (const float*)q.target.p; a.hs_out = nullptr;
+    a.bb0 = dec_lin("dec.enc_bbox.0", dm, dm); a.bb1 = dec_lin("dec.enc_bbox.1", dm, dm); a.bb2 = dec_lin("dec.enc_bbox.2", 4, dm);
+    a.qk = dec_lin("dec.l0.sa.qk", 2 * dm, dm); a.v = dec_lin("dec.l0.sa.v", dm, dm);
+    a.kfrag_out = kfrag[0]; a.vfrag_out = vfrag[0];
+    // the prologue needs the selected rows, not the value maps: it stays on the side stream with the selection chain, and the join sits
+    // after it (the chain's 150 + 45 us run beside the projection's 175 instead of 45 after it)
+    if (F.side_open) lane = 1;
+    push("dec.prologue", "dec_layer", 2.0 * n * Q * (2.0 * dm * dm + 4.0 * dm) + row_flops_next, (double)n * Q * dm * 4 * 6,
+         [a](hipStream_t s) { launch_dec_layer(a, s); });
+    lane = 0;
+    if (F.side_open) { marker(2); F.side_open = false; }
+  }
+  Tensor hs = q.target;
   for (int i = 0; i < NL; ++i) {
     const std::string p = nm("dec.l%d", i);
-    Tensor qp0 = B.linear("dec.qpos.0", ref8t, 2 * dm, F32, ACT_RELU);
-    Tensor qpos = B.linear("dec.qpos.1", qp0, dm, F32, ACT_NONE);
-    Tensor hp = B.act(F32, n, Q, 1, dm);
-    B.push(p + ".addpos1", "add", (double)n * Q * dm, 3.0 * n * Q * dm * 4, [hs, qpos, hp](hipStream_t s) { launch_add(hs, qpos, hp, s); });
-    Tensor sqk = B.linear(p + ".sa.qk", hp, 2 * dm, F32, ACT_NONE);
-    Tensor sv = B.linear(p + ".sa.v", hs, dm, F32, ACT_NONE);
-    Tensor sa = B.act(F32, n, Q, 1, dm);
-    {
-      const int heads = c.dec_heads;
-      B.push(p + ".sa.attn", "attention", 4.0 * n * (double)Q * Q * dm, Builder::tbytes(sqk) + 2 * Builder::tbytes(sv),
-             [sqk, sv, sa, heads](hipStream_t s) { launch_attention(sqk, sv, sa, heads, s); });
-    }
-    Tensor so = B.linear(p + ".sa.o", sa, dm, F32, ACT_NONE, &hs);
-    Tensor hs1 = B.layernorm(p + ".ln1", so, F32);
-    Tensor hp2 = B.act(F32, n, Q, 1, dm);
-    B.push(p + ".addpos2", "add", (double)n * Q * dm, 3.0 * n * Q * dm * 4, [hs1, qpos, hp2](hipStream_t s) { launch_add(hs1, qpos, hp2, s); });
-    Tensor offaw = B.linear(p + ".ca.offaw", hp2, 3 * npts, F32, ACT_NONE);
-    Tensor samp = B.act(F32, n, Q, 1, dm);
-    {
-      const int heads = c.dec_heads, hd = dm / c.dec_heads, nl = c.n_levels, np = c.n_points, coff = i * dm;
-      const int32_t* lvl = e->lvl_dev;
-      const float osc = c.offset_scale;
-      B.push(p + ".ca.sample", "msdeform", 2.0 * n * Q * dm * nl * np * 4, (double)n * Q * heads * nl * np * 4 * hd * dtype_size(P),
-             [vall, coff, offaw, ref8, samp, heads, hd, nl, np, lvl, osc](hipStream_t s) {
-               launch_msdeform(vall, coff, offaw, ref8, samp, heads, hd, nl, np, lvl, osc, s);
-             });
-    }
-    Tensor co = B.linear(p + ".ca.op", samp, dm, F32, ACT_NONE, &hs1);
-    Tensor hs2 = B.layernorm(p + ".ln2", co, F32);
-    Tensor g1 = B.linear(p + ".fc1", hs2, c.dec_ffn, F32, ACT_RELU);
-    Tensor g2 = B.linear(p + ".fc2", g1, dm, F32, ACT_NONE, &hs2);
-    Tensor hs3 = B.layernorm(p + ".ln3", g2, F32, nm("dec%d.hs", i));
-    Tensor d0 = B.linear(nm("dec.bbox.%d.0", i), hs3, dm, F32, ACT_RELU);
-    Tensor d1 = B.linear(nm("dec.bbox.%d.1", i), d0, dm, F32, ACT_RELU);
-    Tensor d2 = B.linear(nm("dec.bbox.%d.2", i), d1, 4, F32, ACT_NONE);
-    B.push(p + ".refine", "box_refine", 0.0, (double)n * Q * 48, [d2, ref8](hipStream_t s) { launch_box_refine(d2, ref8, s); });
+    Tensor hs_out = act(F32, n, Q, 1, dm, nm("dec%d.hs", i));
+    DecArgs a = base;
+    const bool last = i == NL - 1;
+    a.mode = last ? 2 : 1;
+    a.hs_in = (const float*)hs.p; a.hs_out = (float*)hs_out.p;
+    a.value_coff = i * dm;
+    a.kfrag_in = kfrag[i & 1]; a.vfrag_in = vfrag[i & 1];
+    a.kfrag_out = kfrag[(i + 1) & 1]; a.vfrag_out = vfrag[(i + 1) & 1];
+    a.o = dec_lin(p + ".sa.o", dm, dm); a.ln1 = dec_ln(p + ".ln1", dm);
+    a.offaw = dec_lin(p + ".ca.offaw", 3 * npts, dm); a.op = dec_lin(p + ".ca.op", dm, dm); a.ln2 = dec_ln(p + ".ln2", dm);
+    a.fc1 = dec_lin(p + ".fc1", c.dec_ffn, dm); a.fc2 = dec_lin(p + ".fc2", dm, c.dec_ffn); a.ln3 = dec_ln(p + ".ln3", dm);
+    a.bb0 = dec_lin(nm("dec.bbox.%d.0", i), dm, dm); a.bb1 = dec_lin(nm("dec.bbox.%d.1", i), dm, dm); a.bb2 = dec_lin(nm("dec.bbox.%d.2", i), 4, dm);
+    if (last) a.cls = dec_lin("dec.cls", C, dm);
+    else { a.qk = dec_lin(nm("dec.l%d.sa.qk", i + 1), 2 * dm, dm); a.v = dec_lin(nm("dec.l%d.sa.v", i + 1), dm, dm); }
+    const double fl = 4.0 * n * (double)Q * Q * dm + 2.0 * n * Q * ((double)dm * dm * 2 + 3.0 * npts * dm + 2.0 * dm * c.dec_ffn + 2.0 * dm * dm + 4.0 * dm) +
+                      2.0 * n * Q * dm * c.n_levels * c.n_points * 4 + (last ? 2.0 * n * Q * dm * C : row_flops_next);
+    push(p + ".fused", "dec_layer", fl, (double)n * Q * dm * 4 * 8, [a](hipStream_t s) { launch_dec_layer(a, s); });
+    hs = hs_out;
+  }
+  return logits;
+}
+
+// ---- decoder op by op (HF:v2.py:603-661, layer :339-431): shapes the row kernel does not take, rtd_debug_option dec_fused = 0 -----
+Tensor Builder::decoder_by_op(const Queries& q, const Tensor& vall, const Tensor& ref8t, float* ref_unact8) {
+  const int dm = c.d_model, S = e->S, Q = c.num_queries, C = c.num_classes, NL = c.dec_layers;
+  const int npts = c.dec_heads * c.n_levels * c.n_points, n = this->n;
+  float* ref8 = (float*)ref8t.p; const int32_t* tk = q.tk;
+  Tensor b0 = linear("dec.enc_bbox.0", q.target, dm, F32, ACT_RELU);
+  Tensor b1 = linear("dec.enc_bbox.1", b0, dm, F32, ACT_RELU);
+  Tensor b2 = linear("dec.enc_bbox.2", b1, 4, F32, ACT_NONE);
+  const float* anchors = e->anchors_dev; const int32_t* lvl = e->lvl_dev; const float osc = c.offset_scale;
+  const int heads = c.dec_heads, hd = dm / c.dec_heads, nl = c.n_levels, np = c.n_points;
+  push("dec.ref_init", "ref_init", 0.0, (double)n * Q * 64, [b2, anchors, tk, S, ref_unact8, ref8](hipStream_t s) { launch_ref_init(b2, anchors, tk, S, ref_unact8, ref8, s); });
+  Tensor hs = q.target;
+  for (int i = 0; i < NL; ++i) {
+    const std::string p = nm("dec.l%d", i);
+    Tensor qp0 = linear("dec.qpos.0", ref8t, 2 * dm, F32, ACT_RELU);
+    Tensor qpos = linear("dec.qpos.1", qp0, dm, F32, ACT_NONE);
+    Tensor hp = act(F32, n, Q, 1, dm);
+    push(p + ".addpos1", "add", (double)n * Q * dm, 3.0 * n * Q * dm * 4, [hs, qpos, hp](hipStream_t s) { launch_add(hs, qpos, hp, s); });
+    Tensor sqk = linear(p + ".sa.qk", hp, 2 * dm, F32, ACT_NONE);
+    Tensor sv = linear(p + ".sa.v", hs, dm, F32, ACT_NONE);
+    Tensor sa = act(F32, n, Q, 1, dm);
+    push(p + ".sa.attn", "attention", 4.0 * n * (double)Q * Q * dm, tbytes(sqk) + 2 * tbytes(sv),
+         [sqk, sv, sa, heads](hipStream_t s) { launch_attention(sqk, sv, sa, heads, s); });
+    Tensor so = linear(p + ".sa.o", sa, dm, F32, ACT_NONE, &hs);
+    Tensor hs1 = layernorm(p + ".ln1", so, F32);
+    Tensor hp2 = act(F32, n, Q, 1, dm);
+    push(p + ".addpos2", "add", (double)n * Q * dm, 3.0 * n * Q * dm * 4, [hs1, qpos, hp2](hipStream_t s) { launch_add(hs1, qpos, hp2, s); });
+    Tensor offaw = linear(p + ".ca.offaw", hp2, 3 * npts, F32, ACT_NONE);
+    Tensor samp = act(F32, n, Q, 1, dm);
+    const int coff = i * dm;
+    push(p + ".ca.sample", "msdeform", 2.0 * n * Q * dm * nl * np * 4, (double)n * Q * heads * nl * np * 4 * hd * dtype_size(P),
+         [vall, coff, offaw, ref8, samp, heads, hd, nl, np, lvl, osc](hipStream_t s) { launch_msdeform(vall, coff, offaw, ref8, samp, heads, hd, nl, np, lvl, osc, s); });
+    Tensor co = linear(p + ".ca.op", samp, dm, F32, ACT_NONE, &hs1);
+    Tensor hs2 = layernorm(p + ".ln2", co, F32);
+    Tensor g1 = linear(p + ".fc1", hs2, c.dec_ffn, F32, ACT_RELU);
+    Tensor g2 = linear(p + ".fc2", g1, dm, F32, ACT_NONE, &hs2);
+    Tensor hs3 = layernorm(p + ".ln3", g2, F32, nm("dec%d.hs", i));
+    Tensor d0 = linear(nm("dec.bbox.%d.0", i), hs3, dm, F32, ACT_RELU);
+    Tensor d1 = linear(nm("dec.bbox.%d.1", i), d0, dm, F32, ACT_RELU);
+    Tensor d2 = linear(nm("dec.bbox.%d.2", i), d1, 4, F32, ACT_NONE);
+    push(p + ".refine", "box_refine", 0.0, (double)n * Q * 48, [d2, ref8](hipStream_t s) { launch_box_refine(d2, ref8, s); });
     hs = hs3;
   }
-    logits = B.linear("dec.cls", hs, C, F32, ACT_NONE, nullptr, "logits");
-  }
-  // ---- heads + post-processor (HF:v2.py:1880-1881; image_processing_rt_detr.py:510-533) ---------
-  float* scores = (float*)B.alloc((size_t)n * Q * C * 4);
-  float* topv = (float*)B.alloc((size_t)n * Q * 4);
-  int32_t* topi = (int32_t*)B.alloc((size_t)n * Q * 4);
-  plan->block6 = (float*)B.alloc((size_t)n * Q * 6 * 4);
-  plan->scale_wh = (float*)B.alloc((size_t)n * 2 * 4);
-  {
-    float* block6 = plan->block6; float* scale = plan->scale_wh;
-    // one launch when the shape allows (every decoder here: dense [n * Q, C] fp32 logits, Q * C <= 32768), else sigmoid -> top-k -> gather
-    const bool fused_ok = e->opts.post_fused && logits.dt == F32 && logits.ld == C && (int64_t)Q * C <= 32768 && Q <= 1024 && logits.pixels() == (int64_t)n * Q;
-    if (fused_ok) {
-      B.push("post.fused", "topk", (double)n * Q * C, (double)n * Q * C * 4 + (double)n * Q * 64, [logits, ref8, scale, n, Q, block6](hipStream_t s) {
-        RTD_CHECK(launch_postprocess_fused(logits, ref8, scale, n, Q, block6, s), 1, "post-processor: fused launch refused a shape the plan accepted");
-      });
-    } else {
-    B.push("post.sigmoid", "postprocess", (double)n * Q * C, 2.0 * n * Q * C * 4, [logits, scores](hipStream_t s) { launch_postprocess_scores(logits, scores, s); });
-    B.push("post.topk", "topk", 0.0, (double)n * Q * C * 4 * 6, [scores, n, Q, C, topi, topv](hipStream_t s) { launch_topk(scores, n, Q * C, Q, topi, topv, s); });
-    B.push("post.gather", "postprocess", 0.0, (double)n * Q * 64, [topv, topi, ref8, scale, n, Q, C, block6](hipStream_t s) {
-      launch_postprocess_gather(topv, topi, ref8, scale, n, Q, C, block6, s);
+  return linear("dec.cls", hs, C, F32, ACT_NONE, nullptr, "logits");
+}
+
+// ---- heads + post-processor (HF:v2.py:1880-1881; image_processing_rt_detr.py:510-533) ---------
+void Builder::post_process(const Decoded& d) {
+  const int Q = c.num_queries, C = c.num_classes;
+  const int n = this->n;
+  const Tensor logits = d.logits;
+  float* ref8 = d.ref8;
+  float* scores = (float*)alloc((size_t)n * Q * C * 4);
+  float* topv = (float*)alloc((size_t)n * Q * 4);
+  int32_t* topi = (int32_t*)alloc((size_t)n * Q * 4);
+  float* block6 = plan->block6 = (float*)alloc((size_t)n * Q * 6 * 4);
+  float* scale = plan->scale_wh = (float*)alloc((size_t)n * 2 * 4);
+  // one launch when the shape allows (every decoder here: dense [n * Q, C] fp32 logits, Q * C <= 32768), else sigmoid -> top-k -> gather
+  const bool fused_ok = e->opts.post_fused && logits.dt == F32 && logits.ld == C && (int64_t)Q * C <= 32768 && Q <= 1024 && logits.pixels() == (int64_t)n * Q;
+  if (fused_ok) {
+    push("post.fused", "topk", (double)n * Q * C, (double)n * Q * C * 4 + (double)n * Q * 64, [logits, ref8, scale, n, Q, block6](hipStream_t s) {
+      RTD_CHECK(launch_postprocess_fused(logits, ref8, scale, n, Q, block6, s), 1, "post-processor: fused launch refused a shape the plan accepted");
     });
-    }
+    return;
   }
+  push("post.sigmoid", "postprocess", (double)n * Q * C, 2.0 * n * Q * C * 4, [logits, scores](hipStream_t s) { launch_postprocess_scores(logits, scores, s); });
+  push("post.topk", "topk", 0.0, (double)n * Q * C * 4 * 6, [scores, n, Q, C, topi, topv](hipStream_t s) { launch_topk(scores, n, Q * C, Q, topi, topv, s); });
+  push("post.gather", "postprocess", 0.0, (double)n * Q * 64, [topv, topi, ref8, scale, n, Q, C, block6](hipStream_t s) {
+    launch_postprocess_gather(topv, topi, ref8, scale, n, Q, C, block6, s);
+  });
+}
+
+void build_graph(Builder& B) {
+  const rtd_config& c = B.c;
+  Flow F;
+  B.stem(F);
+  // the FPN's concat buffers exist before the backbone runs: their projection halves are filled as soon as a stage's map is complete
+  F.cat1 = B.act(B.P, B.n, B.e->lvl_h[0], B.e->lvl_w[0], 2 * c.enc_dim);   // [up(lat1) | proj0]
+  F.cat0 = B.act(B.P, B.n, B.e->lvl_h[1], B.e->lvl_w[1], 2 * c.enc_dim);   // [up(lat0) | proj1]
+  for (int si = 0; si < 4; ++si) B.backbone_stage(F, si, si ? c.hidden_sizes[si - 1] : c.embedding_size);
+  const Tensor mem = B.encoder(F);
+  const Queries q = B.select_queries(F, mem);
+  B.post_process(B.decoder(F, mem, q));
   B.finish_workspace();
 }
 
@@ -1094,14 +1121,14 @@ Plan* get_plan(rtd_engine* e, int n) {
   std::unique_ptr<Plan> plan(new Plan());
   plan->n = n;
   Builder dry{e, plan.get(), true};
-  build_graph(e, dry, n);
+  build_graph(dry);
   plan->arena_bytes = dry.off + 4096;
   HIP_CHECK(hipMalloc(&plan->arena, plan->arena_bytes));
   e->allocs.push_back(plan->arena);
   HIP_CHECK(hipMemsetAsync(plan->arena, 0, plan->arena_bytes, e->stream));
   plan->named.clear();
   Builder real{e, plan.get(), false};
-  build_graph(e, real, n);
+  build_graph(real);
   HIP_CHECK(hipStreamSynchronize(e->stream));
   Plan* p = plan.get();
   e->plans[n] = std::move(plan);
@@ -1188,6 +1215,16 @@ void run_plan(rtd_engine* e, Plan* p) {
   }
 }
 
+// A per-call staging buffer that only grows.  Work enqueued earlier may still read the old one: the stream drains before it is freed.
+static void grow(rtd_engine* e, uint8_t*& ptr, size_t& have, size_t need, bool pinned = false) {
+  if (need <= have) return;
+  HIP_CHECK(hipStreamSynchronize(e->stream));
+  if (ptr) (void)(pinned ? hipHostFree(ptr) : hipFree(ptr));
+  ptr = nullptr; have = 0;
+  HIP_CHECK(pinned ? hipHostMalloc((void**)&ptr, need, hipHostMallocDefault) : hipMalloc((void**)&ptr, need));
+  have = need;
+}
+
 // preprocess n frames into plan->input and set the post-processor's (w,h) scale
 void enqueue_frames(rtd_engine* e, Plan* p, int n, const uint8_t* const* frames, const int32_t* hw, bool on_device, bool via_pinned = false) {
   const int H = e->cfg.input_h, W = e->cfg.input_w;
@@ -1203,27 +1240,9 @@ void enqueue_frames(rtd_engine* e, Plan* p, int n, const uint8_t* const* frames,
   // coefficients): the horizontal pass' intermediate [src_h][W][3] must fit the largest of them, not only the resized ones
   if (any_resize)
     for (int i = 0; i < n; ++i) max_tmp = std::max(max_tmp, (size_t)hw[2 * i] * W * 3);   // (the fused uint8 stem resamples only the odd-sized ones)
-  if (!on_device && total > e->frame_stage_bytes) {
-    HIP_CHECK(hipStreamSynchronize(e->stream));
-    if (e->frame_stage) (void)hipFree(e->frame_stage);
-    e->frame_stage = nullptr; e->frame_stage_bytes = 0;
-    HIP_CHECK(hipMalloc((void**)&e->frame_stage, total));
-    e->frame_stage_bytes = total;
-  }
-  if (!on_device && via_pinned && total > e->pin_stage_bytes) {
-    HIP_CHECK(hipStreamSynchronize(e->stream));
-    if (e->pin_stage) (void)hipHostFree(e->pin_stage);
-    e->pin_stage = nullptr; e->pin_stage_bytes = 0;
-    HIP_CHECK(hipHostMalloc((void**)&e->pin_stage, total, hipHostMallocDefault));
-    e->pin_stage_bytes = total;
-  }
-  if (max_tmp > e->resize_tmp_bytes) {
-    HIP_CHECK(hipStreamSynchronize(e->stream));
-    if (e->resize_tmp) (void)hipFree(e->resize_tmp);
-    e->resize_tmp = nullptr; e->resize_tmp_bytes = 0;
-    HIP_CHECK(hipMalloc((void**)&e->resize_tmp, max_tmp));
-    e->resize_tmp_bytes = max_tmp;
-  }
+  if (!on_device) grow(e, e->frame_stage, e->frame_stage_bytes, total);
+  if (!on_device && via_pinned) grow(e, e->pin_stage, e->pin_stage_bytes, total, /*pinned=*/true);
+  grow(e, e->resize_tmp, e->resize_tmp_bytes, max_tmp);
   size_t off = 0;
   bool all_identity = true;
   FrameArgs fa;
@@ -1314,7 +1333,6 @@ void point_at_blank_frames(rtd_engine* h, Plan* p, int n) {
   h->last_fa = fa;
 }
 
-
 }  // namespace rtd_eng
 
 namespace rtd {
@@ -1326,8 +1344,6 @@ __global__ void k_force_idx(int32_t* dst, const int32_t* src, const int32_t* fla
 void launch_force_idx(int32_t* dst, const int32_t* src, const int32_t* flag, int n, hipStream_t s) {
   rtd_launch(rtd::k_force_idx, dim3((n + 255) / 256), dim3(256), 0, s, dst, src, flag, n);
 }
-
-
 
 // =========================================================================================== C ABI
 extern "C" {
@@ -1406,18 +1422,14 @@ int rtd_load_weights(rtd_handle h, const void* blob, size_t nbytes) {
     RTD_CHECK(c.num_queries <= e->S, RTD_E_INVALID, "num_queries exceeds the number of memory tokens");
     std::vector<float> anchors; std::vector<int32_t> invalid;
     make_anchors(e, anchors, invalid);
-    e->anchors_dev = (float*)e->dmalloc(anchors.size() * 4);
-    HIP_CHECK(hipMemcpy(e->anchors_dev, anchors.data(), anchors.size() * 4, hipMemcpyHostToDevice));
+    e->anchors_dev = (float*)upload(e, anchors.data(), anchors.size() * 4);
     e->n_invalid = (int)invalid.size();
-    e->invalid_rows_dev = (int32_t*)e->dmalloc(invalid.size() * 4 + 16);
-    if (!invalid.empty()) HIP_CHECK(hipMemcpy(e->invalid_rows_dev, invalid.data(), invalid.size() * 4, hipMemcpyHostToDevice));
+    e->invalid_rows_dev = (int32_t*)upload(e, invalid.data(), invalid.size() * 4);
     int32_t lv[9];
     for (int l = 0; l < 3; ++l) { lv[l * 3] = e->lvl_h[l]; lv[l * 3 + 1] = e->lvl_w[l]; lv[l * 3 + 2] = e->lvl_start[l]; }
-    e->lvl_dev = (int32_t*)e->dmalloc(sizeof lv);
-    HIP_CHECK(hipMemcpy(e->lvl_dev, lv, sizeof lv, hipMemcpyHostToDevice));
+    e->lvl_dev = (int32_t*)upload(e, lv, sizeof lv);
     std::vector<float> pos = sincos_pos(e->lvl_h[2], e->lvl_w[2], c.enc_dim);
-    e->pos_dev = (float*)e->dmalloc(pos.size() * 4);
-    HIP_CHECK(hipMemcpy(e->pos_dev, pos.data(), pos.size() * 4, hipMemcpyHostToDevice));
+    e->pos_dev = (float*)upload(e, pos.data(), pos.size() * 4);
     e->forced_idx = (int32_t*)e->dmalloc((size_t)c.max_batch * c.num_queries * 4);
     e->force_flag = (int32_t*)e->dmalloc(16);
     HIP_CHECK(hipMemset(e->force_flag, 0, 16));
@@ -1524,25 +1536,12 @@ int rtd_preprocess(rtd_handle h, const uint8_t* frame, int32_t fh, int32_t fw, i
     const size_t bytes = (size_t)fh * fw * 3;
     const uint8_t* src = frame;
     if (!frame_on_device) {
-      if (bytes > e->frame_stage_bytes) {
-        HIP_CHECK(hipStreamSynchronize(e->stream));
-        if (e->frame_stage) (void)hipFree(e->frame_stage);
-        e->frame_stage = nullptr; e->frame_stage_bytes = 0;
-        HIP_CHECK(hipMalloc((void**)&e->frame_stage, bytes));
-        e->frame_stage_bytes = bytes;
-      }
+      grow(e, e->frame_stage, e->frame_stage_bytes, bytes);
       HIP_CHECK(hipMemcpyAsync(e->frame_stage, frame, bytes, hipMemcpyHostToDevice, e->stream));
       src = e->frame_stage;
     }
     if (fh != H || fw != W) {                                                    // PIL-exact antialiased stretch, uint8 in and out (T.Resize on the PIL image)
-      const size_t tmp = (size_t)fh * W * 3;
-      if (tmp > e->resize_tmp_bytes) {
-        HIP_CHECK(hipStreamSynchronize(e->stream));
-        if (e->resize_tmp) (void)hipFree(e->resize_tmp);
-        e->resize_tmp = nullptr; e->resize_tmp_bytes = 0;
-        HIP_CHECK(hipMalloc((void**)&e->resize_tmp, tmp));
-        e->resize_tmp_bytes = tmp;
-      }
+      grow(e, e->resize_tmp, e->resize_tmp_bytes, (size_t)fh * W * 3);
       if (!e->u8_stage) HIP_CHECK(hipMalloc((void**)&e->u8_stage, (size_t)e->cfg.max_batch * H * W * 3));
       const ResizeCoef& rc = resize_tables(e, fh, fw);
       launch_resize_pil_u8(src, fh, fw, e->resize_tmp, e->u8_stage, H, W, rc, e->stream);
@@ -1562,10 +1561,7 @@ int rtd_prepare(rtd_handle h, int32_t n) {
     h->in_flight = false;
     Plan* p = get_plan(h, n);
     if (!h->cfg.use_graph || p->exec) return;
-    point_at_blank_frames(h, p, n);
-    if (!p->stem_fused) {
-      // the stand-alone preprocess writes plan->input per call; the arena is zero-filled, which is a valid (black) input
-    }
+    point_at_blank_frames(h, p, n);   // (without the fused stem the preprocess writes plan->input per call; the zero-filled arena is a valid, black, input)
     warm_and_build(h, p);
     HIP_CHECK(hipStreamSynchronize(h->stream));
   });

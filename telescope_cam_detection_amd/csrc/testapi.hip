@@ -211,51 +211,49 @@ int rtd_debug_option(const char* name, int value) {
   return RTD_E_INVALID;
 }
 
+// a caller's filter [N][K] fp32 + bias [N] (device) as launch_conv wants them: [Npad][Kpad] in `dtype`, zero padded, and fp32 [Npad]
+struct DevFilter {
+  float* wpad = nullptr; void* w = nullptr; float* bias = nullptr;
+  int Kpad = 0, Npad = 0;
+  void release() { if (w != wpad) (void)hipFree(w); (void)hipFree(wpad); (void)hipFree(bias); }
+};
+static DevFilter dev_filter(int dtype, const void* w_f32, const float* bias, int N, int K) {
+  DevFilter f;
+  f.Npad = conv_npad(N);
+  f.Kpad = dtype == F16X2 ? conv_kpad_split(K) : conv_kpad(K);
+  const int kcols = dtype == F16X2 ? f.Kpad / 2 : f.Kpad;        // fp32 staging row (F16X2: 2 bf16 per column)
+  HIP_CHECK(hipMalloc((void**)&f.wpad, (size_t)f.Npad * kcols * 4));
+  HIP_CHECK(hipMemset(f.wpad, 0, (size_t)f.Npad * kcols * 4));
+  HIP_CHECK(hipMemcpy2D(f.wpad, (size_t)kcols * 4, w_f32, (size_t)K * 4, (size_t)K * 4, N, hipMemcpyDeviceToDevice));
+  HIP_CHECK(hipMalloc((void**)&f.bias, (size_t)f.Npad * 4));
+  HIP_CHECK(hipMemset(f.bias, 0, (size_t)f.Npad * 4));
+  HIP_CHECK(hipMemcpy(f.bias, bias, (size_t)N * 4, hipMemcpyDeviceToDevice));
+  f.w = f.wpad;
+  if (dtype == BF16 || dtype == F16X2) HIP_CHECK(hipMalloc(&f.w, (size_t)f.Npad * f.Kpad * 2));
+  if (dtype == BF16) launch_f32_to(f.wpad, f.w, BF16, (int64_t)f.Npad * f.Kpad, nullptr);
+  else if (dtype == F16X2) launch_f32_to_split(f.wpad, kcols, f.w, kcols, f.Npad, kcols, nullptr);
+  return f;
+}
+
 static int op_conv_impl(int dtype, const void* x, const void* x2, int C2, const void* w_ohwi_f32, const float* bias, const void* res, void* y,
                         int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, int act, int res_mode, int out_f32, int x_up2 = 0,
                         const void* w1_f32 = nullptr, const float* bias1 = nullptr, void* y1 = nullptr, int Cnext = 0, int next_act = 0) {
   return op_guard([&] {
     RTD_CHECK(KH == KW, RTD_E_INVALID, "square filters only");
-    const int K = KH * KW * Cin + (x2 ? C2 : 0), Npad = conv_npad(Cout);
-    const int Kpad = dtype == F16X2 ? conv_kpad_split(K) : conv_kpad(K);
-    const int kcols = dtype == F16X2 ? Kpad / 2 : Kpad;          // fp32 staging row (F16X2: 2 bf16 per column)
     const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-    float* wpad = nullptr; void* wdev = nullptr; float* bpad = nullptr;
-    HIP_CHECK(hipMalloc((void**)&wpad, (size_t)Npad * kcols * 4));
-    HIP_CHECK(hipMemset(wpad, 0, (size_t)Npad * kcols * 4));
-    HIP_CHECK(hipMemcpy2D(wpad, (size_t)kcols * 4, w_ohwi_f32, (size_t)K * 4, (size_t)K * 4, Cout, hipMemcpyDeviceToDevice));
-    HIP_CHECK(hipMalloc((void**)&bpad, (size_t)Npad * 4));
-    HIP_CHECK(hipMemset(bpad, 0, (size_t)Npad * 4));
-    HIP_CHECK(hipMemcpy(bpad, bias, (size_t)Cout * 4, hipMemcpyDeviceToDevice));
-    if (dtype == BF16) {
-      HIP_CHECK(hipMalloc(&wdev, (size_t)Npad * Kpad * 2));
-      launch_f32_to(wpad, wdev, BF16, (int64_t)Npad * Kpad, nullptr);
-    } else if (dtype == F16X2) {
-      HIP_CHECK(hipMalloc(&wdev, (size_t)Npad * Kpad * 2));
-      launch_f32_to_split(wpad, kcols, wdev, kcols, Npad, kcols, nullptr);
-    } else wdev = wpad;
+    DevFilter f = dev_filter(dtype, w_ohwi_f32, bias, Cout, KH * KW * Cin + (x2 ? C2 : 0)), f1;
     ConvArgs a;
     a.x = x_up2 ? mk(x, dtype, B, H / 2, W / 2, Cin) : mk(x, dtype, B, H, W, Cin);      // x_up2: H, W are the OUTPUT extents
     a.x_up2 = x_up2;
     a.y = mk(y, out_f32 ? F32 : dtype, B, OH, OW, Cout);
-    a.w = wdev; a.bias = bpad; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.Kpad = Kpad; a.Npad = Npad;
+    a.w = f.w; a.bias = f.bias; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.Kpad = f.Kpad; a.Npad = f.Npad;
     a.act = act; a.res_mode = res ? res_mode : RES_NONE;
     if (res) a.res = mk(res, dtype, B, OH, OW, Cout);
     if (x2) a.x2 = mk(x2, dtype, B, OH, OW, C2);
-    float* w1pad = nullptr; void* w1dev = nullptr; float* b1pad = nullptr;
     if (y1) {                                                    // a following 1x1 conv Cout -> Cnext fused into this launch (ConvArgs::next_*)
       RTD_CHECK(dtype == BF16 || dtype == F16X2, RTD_E_INVALID, "fused following conv: bf16 / f16x2 only");
-      const int N1 = conv_npad(Cnext), K1 = dtype == F16X2 ? conv_kpad_split(Cout) : conv_kpad(Cout), k1cols = dtype == F16X2 ? K1 / 2 : K1;
-      HIP_CHECK(hipMalloc((void**)&w1pad, (size_t)N1 * k1cols * 4));
-      HIP_CHECK(hipMemset(w1pad, 0, (size_t)N1 * k1cols * 4));
-      HIP_CHECK(hipMemcpy2D(w1pad, (size_t)k1cols * 4, w1_f32, (size_t)Cout * 4, (size_t)Cout * 4, Cnext, hipMemcpyDeviceToDevice));
-      HIP_CHECK(hipMalloc((void**)&b1pad, (size_t)N1 * 4));
-      HIP_CHECK(hipMemset(b1pad, 0, (size_t)N1 * 4));
-      HIP_CHECK(hipMemcpy(b1pad, bias1, (size_t)Cnext * 4, hipMemcpyDeviceToDevice));
-      HIP_CHECK(hipMalloc(&w1dev, (size_t)N1 * K1 * 2));
-      if (dtype == BF16) launch_f32_to(w1pad, w1dev, BF16, (int64_t)N1 * K1, nullptr);
-      else launch_f32_to_split(w1pad, k1cols, w1dev, k1cols, N1, k1cols, nullptr);
-      a.next_w = w1dev; a.next_bias = b1pad; a.next_y = mk(y1, dtype, B, OH, OW, Cnext); a.next_kpad = K1; a.next_act = next_act;
+      f1 = dev_filter(dtype, w1_f32, bias1, Cnext, Cout);
+      a.next_w = f1.w; a.next_bias = f1.bias; a.next_y = mk(y1, dtype, B, OH, OW, Cnext); a.next_kpad = f1.Kpad; a.next_act = next_act;
       RTD_CHECK(conv_next_supported(a), RTD_E_INVALID, "fused following conv: shape not taken by the streaming kernels");
     }
     ConvWorkspace ws;
@@ -266,9 +264,8 @@ static int op_conv_impl(int dtype, const void* x, const void* x2, int C2, const 
     HIP_CHECK(hipDeviceSynchronize());
     if (ws.slab) (void)hipFree(ws.slab);
     HIP_CHECK(hipDeviceSynchronize());
-    if (wdev != wpad) (void)hipFree(wdev);
-    (void)hipFree(wpad); (void)hipFree(bpad);
-    if (w1pad) { (void)hipFree(w1pad); (void)hipFree(w1dev); (void)hipFree(b1pad); }
+    f.release();
+    if (f1.wpad) f1.release();
   });
 }
 
@@ -495,7 +492,6 @@ int rtd_op_msdeform(int dtype, const void* value, const float* offaw, const floa
     (void)hipFree(lvd); (void)hipFree(ref8);
   });
 }
-
 
 int rtd_op_topk(const float* keys, int B, int N, int K, int32_t* idx_out, float* val_out) {
   return op_guard([&] { launch_topk(keys, B, N, K, idx_out, val_out, nullptr); });
