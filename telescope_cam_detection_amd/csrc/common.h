@@ -141,15 +141,15 @@ struct ConvOpts {
   int split_ws2_min_blocks = 257;
   int split_ws64_max_blocks = 160;
   int split_flex = 1;             // flexible tile heights (conv_igemm_wsf_kernel) on grids of <= split_flex_small_max 128 x 128 tiles
-  int split_flex_min_nk = 4;      // ... from this many K-steps on (same-box sweep, R50 bs 8: 16 / 8 / 4 / 2 -> 4.884 / 4.878 / 4.854 / 4.866 ms)
-  int split_flex_small_max = 200; // (sweep 128 / 200 / 256 / 400 -> 4.816 / 4.776 / 4.779 / 4.777 ms per step)
+  int split_flex_min_nk = 4;      // ... from this many K-steps on (the sweeps behind both numbers: choose_pair(), conv_igemm.hip)
+  int split_flex_small_max = 200;
   int split_sx = 3;               // streaming pair kernel: 0 off, 1 = K = 64 (+ 64) -> 256 (stage 0), 2 = also K = 128 (stage 1), 3 = also K = 256 -> N >= 1024
                                   // without a residual (value projection), 4 = also with a residual from 40^2 maps on (51.5 vs 39.5 us on the tiled kernel: off)
   int split_k2 = 1;               // two-pass split-K on long-K layers with few tiles per image
   int split_wsq = 1;              // 160..256-pixel tiles at one block per CU (conv_igemm_wsq_kernel) on grids of >= split_wsq_min_blocks 128 x 128 tiles
                                   // with >= split_wsq_min_nk K-steps (2 = on every grid: tests)
   int split_wsq_min_blocks = 257;
-  int split_wsq_min_nk = 24;         // same-box A/B (tools/profile_layers.py --ab split_wsq): 3x3 layers 1.05-1.18x, 1x1 layers of 8-16 K-steps 0.80-0.96x
+  int split_wsq_min_nk = 24;      // (the A/B behind it: choose_pair(), conv_igemm.hip)
 };
 ConvOpts& conv_opts_template();
 bool conv_set_option(const char* name, int value);   // edits the template; false = not a conv option
@@ -201,15 +201,16 @@ struct ConvArgs {
   size_t pf_bytes = 0;
 };
 void launch_conv(const ConvArgs& a, hipStream_t s);
-bool conv_dual_supported(const ConvArgs& a);
-bool conv_next_supported(const ConvArgs& a);   // can `a` (shapes for ONE image) carry a fused following 1x1 conv (ConvArgs::next_*)?   // can this build's kernels run `a` with its second input? (the plan builder asks before fusing)
 int conv_kpad(int K);                 // padded filter row length the kernels expect
 int conv_kpad_split(int K);           // F16X2 filter row length in bf16 elements (K real taps x channels)
-bool conv_split_supported(const ConvArgs& a);   // F16X2 input: does the split kernel take this launch?
 int conv_npad(int N);
+// What the plan builder asks before it relies on a fusion (shape-only probes: the answers read extents, dtypes, alignment and the options)
+bool conv_dual_supported(const ConvArgs& a);    // can this build's kernels run `a` with its second input (ConvArgs::x2)?
+bool conv_next_supported(const ConvArgs& a);    // can `a` (shapes for ONE image) carry a fused following 1x1 conv (ConvArgs::next_*)?
+bool conv_split_supported(const ConvArgs& a);   // F16X2 input: does the split kernel take this launch?
+bool conv_avg_supported(const ConvArgs& a);     // can this launch (shapes for ONE image) carry ConvArgs::avg_y?
+bool conv_sx_batch_fits(const ConvArgs& a);     // ... and do the tensors of THIS plan's batch fit the streaming kernel's 2 GiB descriptors?
 // stem.2 + the 3x3 / stride-2 max-pool in one pass (f16x3 engine): `a` = the conv whose output would be pooled into `pooled`
-bool conv_avg_supported(const ConvArgs& a);      // can this launch (shapes for ONE image) carry ConvArgs::avg_y?
-bool conv_sx_batch_fits(const ConvArgs& a);      // ... and do the tensors of THIS plan's batch fit the streaming kernel's 2 GiB descriptors?
 bool conv_pool_supported(const ConvArgs& a, const Tensor& pooled);
 size_t conv_pool_side_bytes(const ConvArgs& a);
 void launch_conv_pool(const ConvArgs& a, const Tensor& pooled, void* side, hipStream_t s);

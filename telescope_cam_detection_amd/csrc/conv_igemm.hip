@@ -21,38 +21,39 @@
 #include <string.h>
 
 #include <algorithm>
+#include <type_traits>
 
 #include "common.h"
 
 namespace rtd {
 
 struct ConvK {
-  const void* x;
-  const void* w;
-  const float* bias;
-  const void* res;
-  void* y;
-  int M, H, W, Cin;
-  long long ldx, x_bstride;
-  int OH, OW, OHW;
-  int N, Kreal, Kpad;
-  int KH, KW, stride, pad;
-  long long ldy, y_bstride, ldr, r_bstride;
-  int act, res_mode, y_f32, res_f32;
-  int ntn;
-  const void* pf;        // prefetch target (next layer's filter) or nullptr
-  unsigned pf_bytes;
-  int reg_epi;           // 1: the ws kernels may finish residual-free bf16 tiles in registers (A/B: rtd_debug_option "reg_epilogue")
-  const void* x2;        // second input (ConvArgs::x2) or nullptr; K elements k2_start.. come from it
-  long long ldx2, x2_bstride;
-  int k2_start;
-  int prefer256;         // ConvArgs::prefer256
-  int x_up2;             // ConvArgs::x_up2 (ws kernel loader only)
-  const void* next_w;    // ConvArgs::next_* (streaming kernel only)
-  const float* next_bias;
-  void* next_y;
-  long long next_ldy, next_y_bstride;
-  int next_kpad, next_act;
+  const void* x = nullptr;
+  const void* w = nullptr;
+  const float* bias = nullptr;
+  const void* res = nullptr;
+  void* y = nullptr;
+  int M = 0, H = 0, W = 0, Cin = 0;
+  long long ldx = 0, x_bstride = 0;
+  int OH = 0, OW = 0, OHW = 0;
+  int N = 0, Kreal = 0, Kpad = 0;
+  int KH = 1, KW = 1, stride = 1, pad = 0;
+  long long ldy = 0, y_bstride = 0, ldr = 0, r_bstride = 0;
+  int act = ACT_NONE, res_mode = RES_NONE, y_f32 = 0, res_f32 = 0;
+  int ntn = 1;
+  const void* pf = nullptr;   // prefetch target (next layer's filter) or nullptr
+  unsigned pf_bytes = 0;
+  int reg_epi = 0;       // 1: the ws kernels may finish residual-free bf16 tiles in registers (A/B: rtd_debug_option "reg_epilogue")
+  const void* x2 = nullptr;   // second input (ConvArgs::x2) or nullptr; K elements k2_start.. come from it
+  long long ldx2 = 0, x2_bstride = 0;
+  int k2_start = 0;
+  int prefer256 = 0;     // ConvArgs::prefer256
+  int x_up2 = 0;         // ConvArgs::x_up2 (ws kernel loader only)
+  const void* next_w = nullptr;    // ConvArgs::next_* (streaming kernel only)
+  const float* next_bias = nullptr;
+  void* next_y = nullptr;
+  long long next_ldy = 0, next_y_bstride = 0;
+  int next_kpad = 0, next_act = 0;
   // F16X2 operands (common.h): `split` = x / x2 / w are [32 hi | 32 lo] grouped bf16 and Cin, ldx, x_bstride, Kreal, Kpad, k2_start,
   // ldx2, x2_bstride count bf16 ELEMENTS (twice the channels); y_split / res_split = the output / residual is a F16X2 tensor, its
   // ldy / y_bstride (ldr / r_bstride) count channels as for fp32 and addresses go through split_off()
@@ -1199,67 +1200,6 @@ __global__ __launch_bounds__(512, 2) void conv_igemm_wsq_kernel(const ConvG g) {
   });
 }
 
-
-int conv_kpad(int K) { return (K + 63) / 64 * 64; }
-int conv_npad(int N) { return (N + 127) / 128 * 128; }
-
-static ConvOpts g_conv_opts;
-ConvOpts& conv_opts_template() { return g_conv_opts; }
-bool conv_set_option(const char* name, int value) {
-  ConvOpts& o = g_conv_opts;
-  const struct { const char* n; int* p; } table[] = {
-      {"conv_mode", &o.conv_mode}, {"glds_min_blocks", &o.glds_min_blocks}, {"glds_min_n", &o.glds_min_n}, 
-      {"ws2_min_blocks", &o.ws2_min_blocks}, {"ws64_max_blocks", &o.ws64_max_blocks}, 
-      {"reg_epilogue", &o.reg_epilogue}, {"conv_reg", &o.conv_reg}, 
-      {"prefetch", &o.prefetch},
-      {"split_ws2_min_blocks", &o.split_ws2_min_blocks}, {"split_ws64_max_blocks", &o.split_ws64_max_blocks},
-      {"split_flex", &o.split_flex}, {"split_flex_min_nk", &o.split_flex_min_nk}, {"split_flex_small_max", &o.split_flex_small_max},
-      {"split_sx", &o.split_sx}, {"split_k2", &o.split_k2}, {"split_wsq", &o.split_wsq}, {"split_wsq_min_blocks", &o.split_wsq_min_blocks},
-      {"split_wsq_min_nk", &o.split_wsq_min_nk},
-  };
-  for (const auto& t : table)
-    if (strcmp(name, t.n) == 0) { *t.p = value; return true; }
-  return false;
-}
-static inline const ConvOpts& opts_of(const ConvArgs& a) { return a.opts ? *a.opts : g_conv_opts; }
-
-// LDS-DMA tile kernels on bf16 / fp32 operands; returns true when the launch was taken
-template <typename T>
-static bool dispatch_glds(const ConvOpts& o, const ConvK& k, bool ok, bool prefer256, long long x_bytes, long long w_bytes, unsigned x2_bytes, hipStream_t s) {
-  if (!ok || (o.conv_mode == 1 && !k.x2)) return false;
-  static_assert(sizeof(T) == 2 || sizeof(T) == 4, "bf16 / fp32");
-  const long long mt = (k.M + 127) / 128, ntn = (k.N + 127) / 128;
-  // N >= 64 may use a partly empty N tile (the filter is padded to 128 rows): the N = 64 reduce convs of stage 0 are HBM-bound,
-  // and the LDS-DMA pipeline (2 blocks per CU) streams their input faster than the register-staged kernel
-  if (k.N < (sizeof(T) == 2 ? o.glds_min_n : 64) || mt * ntn < (sizeof(T) == 2 ? o.glds_min_blocks : 512) || x_bytes >= (1ll << 31) || w_bytes >= (1ll << 31)) return false;
-  ConvG g;
-  g.k = k;
-  g.k.ntn = (int)ntn;
-  g.splitk = 1;
-  g.x_bytes = (unsigned)x_bytes; g.w_bytes = (unsigned)w_bytes; g.x2_bytes = x2_bytes;
-  // small grids: 128 x 64 tiles double the blocks (latency profile only: with other batches in flight the idle CUs are taken anyway and
-  // the narrower tile stages 1.5x the bytes per MFMA - measured +1.4 % for one handle, -1 % for three); conv_mode 10 forces it for the tests
-  if ((o.conv_mode == 0 && !prefer256 && mt * ntn < o.ws64_max_blocks && k.N > 64) || o.conv_mode == 10) {
-    const long long ntn64 = (k.N + 63) / 64;
-    g.k.ntn = (int)ntn64;
-    rtd_launch((conv_igemm_ws_kernel<T, 4, 64>), dim3((unsigned)(mt * ntn64)), dim3(512), 0, s, g);
-    return true;
-  }
-  if (k.x2) {
-    // dual-input launches exist in the wave-specialised kernel only (every conv_mode): 4 stages on small grids, 2 above
-    if (mt * ntn < o.ws2_min_blocks) rtd_launch((conv_igemm_ws_kernel<T, 4>), dim3((unsigned)(mt * ntn)), dim3(512), 0, s, g);
-    else rtd_launch((conv_igemm_ws_kernel<T, 2>), dim3((unsigned)(mt * ntn)), dim3(512), 0, s, g);
-    return true;
-  }
-  // loader / MFMA wave roles win at every grid size (tools/profile_layers.py): grids beyond one block per CU run 2 blocks per CU with
-  // 2 stages, smaller grids 1 block per CU with 4 stages (3 tiles of DMA in flight); conv_mode 3 / 4 force either
-  const bool four = o.conv_mode == 3 || (o.conv_mode != 4 && mt * ntn < o.ws2_min_blocks);
-  if (four) rtd_launch((conv_igemm_ws_kernel<T, 4>), dim3((unsigned)(mt * ntn)), dim3(512), 0, s, g);
-  else rtd_launch((conv_igemm_ws_kernel<T, 2>), dim3((unsigned)(mt * ntn)), dim3(512), 0, s, g);
-  return true;
-}
-
-
 // F16X2 form of the direct 3x3 kernel for 32 input channels (stem.1 32 -> 32, stem.2 32 -> 64 at 320^2): a pixel's 128 bytes are
 // [32 hi | 32 lo], so the patch, its LDS-DMA and its swizzle are the sp16 kernel's CIN = 64 case; each wave keeps the hi AND the lo filter
 // of its 32 output channels in registers (36 fragments = 144 VGPRs) and runs hi*hi + hi*lo + lo*hi per tap (6 MFMAs per tap and row).
@@ -1673,103 +1613,6 @@ __global__ __launch_bounds__(512, 1) void conv3x3_reg_split64_kernel(const ConvK
   }
 }
 
-
-
-// register-staged fallback: every shape (small channel counts, grids below the LDS-DMA kernels' thresholds)
-template <typename T>
-static void dispatch(const ConvK& k, bool smallc, hipStream_t s) {
-  const long long b128 = (long long)((k.M + 127) / 128);
-  const int n128 = (k.N + 127) / 128, n64 = (k.N + 63) / 64;
-  int cfg;  // 0: 128x128, 1: 128x64, 2: 64x64
-  if (b128 * n128 >= 512 && k.N > 64) cfg = 0;
-  else if (b128 * n64 >= 384) cfg = 1;
-  else cfg = 2;
-  ConvK kk = k;
-#define RTD_LAUNCH(BM, BN)                                                                        \
-  do {                                                                                            \
-    kk.ntn = (k.N + BN - 1) / BN;                                                                 \
-    const long long blocks = (long long)((k.M + BM - 1) / BM) * kk.ntn;                           \
-    if (smallc) rtd_launch((conv_igemm_kernel<T, BM, BN, true>), dim3((unsigned)blocks), dim3(256), 0, s, kk); \
-    else rtd_launch((conv_igemm_kernel<T, BM, BN, false>), dim3((unsigned)blocks), dim3(256), 0, s, kk);       \
-  } while (0)
-  if (cfg == 0) RTD_LAUNCH(128, 128);
-  else if (cfg == 1) RTD_LAUNCH(128, 64);
-  else RTD_LAUNCH(64, 64);
-#undef RTD_LAUNCH
-}
-
-// The second input exists in the wave-specialised LDS-DMA kernel (and, for 64 + 64 channels, the streaming kernel): the shapes
-// dispatch_glds accepts, a K-step-aligned split point and whole K-steps of x2.
-bool conv_dual_supported(const ConvArgs& a) {
-  const ConvOpts& o = opts_of(a);
-  const Tensor& x = a.x;
-  const Tensor& y = a.y;
-  const Tensor& x2 = a.x2;
-  if (!x2.p || x2.dt != x.dt) return false;
-  const int up = a.x_up2 ? 2 : 1;
-  if (a.x_up2 && !(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0)) return false;
-  const int OH = (x.h * up + 2 * a.pad - a.KH) / a.stride + 1, OW = (x.w * up + 2 * a.pad - a.KW) / a.stride + 1;
-  if (x2.n != x.n || x2.h != OH || x2.w != OW) return false;
-  if (x.dt == F16X2) {                                           // the split kernel takes every grid size
-    const long long xb = ((long long)(x.n - 1) * x.bstride + ((long long)x.h * x.w - 1) * x.ld + x.c) * 4;
-    const long long x2b = ((long long)(x2.n - 1) * x2.bstride + ((long long)x2.h * x2.w - 1) * x2.ld + x2.c) * 4;
-    return conv_split_supported(a) && xb < (1ll << 31) && x2b < (1ll << 31);
-  }
-  const int es = (int)dtype_size(x.dt), bk = 128 / es, epc = 16 / es;
-  if ((a.KH * a.KW * x.c) % bk || x2.c % bk || x.c % bk || x2.ld % epc || ((uintptr_t)x2.p & 15)) return false;
-  if (!(y.c % 8 == 0 && y.ld % 8 == 0 && ((uintptr_t)y.p & 15) == 0)) return false;                       // tile_ok
-  if (a.res_mode != RES_NONE && !(a.res.ld % 8 == 0 && ((uintptr_t)a.res.p & 15) == 0)) return false;
-  const long long M = (long long)x.n * OH * OW;
-  const long long mt = (M + 127) / 128, ntn = (y.c + 127) / 128;
-  if (y.c < (es == 2 ? o.glds_min_n : 64) || mt * ntn < (es == 2 ? o.glds_min_blocks : 512)) return false;
-  const long long x_bytes = ((long long)(x.n - 1) * x.bstride + ((long long)x.h * x.w - 1) * x.ld + x.c) * es;
-  const long long x2_bytes = ((long long)(x2.n - 1) * x2.bstride + ((long long)x2.h * x2.w - 1) * x2.ld + x2.c) * es;
-  const long long w_bytes = (long long)conv_npad(y.c) * conv_kpad(a.KH * a.KW * x.c + x2.c) * es;
-  return x_bytes < (1ll << 31) && x2_bytes < (1ll << 31) && w_bytes < (1ll << 31);
-}
-
-// The fused following conv exists in the streaming kernel for N = 256 (K = 64, or 64 + 64 with a second input) -> 64 channels and
-// N = 512 (K = 128) -> 128 channels.  Asked per plan (batch size): the fused and the separate form use the same filter tensors and
-// give bit-identical outputs, so plans of different batch sizes may differ.
-static bool sx_shape_ok(const ConvArgs& a);
-// The streaming kernel addresses every tensor through a 2 GiB buffer descriptor and counts tiles in 30 bits: limits that depend on the
-// BATCH, unlike every shape test (which looks at one image).  The plan builder asks this with the plan's real batch before it relies on a
-// fusion that only the streaming kernel implements (ConvArgs::avg_y); dispatch_sx applies the same limits.
-bool conv_sx_batch_fits(const ConvArgs& a) {
-  auto span = [](const Tensor& t) { return ((long long)(t.n - 1) * t.bstride + ((long long)t.h * t.w - 1) * t.ld + t.c) * 4; };
-  const Tensor& y = a.y;
-  if (span(y) >= (1ll << 31)) return false;
-  if (a.res_mode != RES_NONE && span(a.res) >= (1ll << 31)) return false;
-  if (a.next_y.p && span(a.next_y) >= (1ll << 31)) return false;
-  if (a.avg_y.p && span(a.avg_y) >= (1ll << 31)) return false;
-  const long long ntiles = a.avg_y.p ? (long long)y.n * (y.h / 2) * (y.w / 16) : ((long long)y.n * y.h * y.w + 31) / 32;
-  return ntiles < (1ll << 30);
-}
-bool conv_avg_supported(const ConvArgs& a) {
-  const Tensor& x = a.x;
-  const Tensor& y = a.y;
-  if (x.dt != F16X2 || y.dt != F16X2 || !sx_shape_ok(a)) return false;
-  if (a.x2.p || a.res_mode == RES_NONE || (y.h & 1) || (y.w & 15) || y.ld % SPLIT_GROUP) return false;
-  if (x.c == 64) return y.c == 256 && a.next_y.p && a.next_y.c == 128 && conv_next_supported(a);
-  return x.c == 128 && !a.next_y.p;
-}
-bool conv_next_supported(const ConvArgs& a) {
-  const Tensor& x = a.x;
-  const Tensor& y = a.y;
-  if (x.dt == F16X2)
-    return sx_shape_ok(a) && y.c == 256 && (a.next_y.c == 64 || a.next_y.c == 128) && a.next_y.dt == F16X2 && a.next_y.ld % SPLIT_GROUP == 0 && y.ld % SPLIT_GROUP == 0;
-  return false;                                                 // bf16 / fp32 operands: no kernel with a fused following conv (round 5: the bf16 streaming kernels were removed)
-}
-
-// ------------------------------------------------------------------------------------------------
-// Pair operands (F16X2 tensors, common.h).  Shapes: Cin (and C2) multiples of 32 - one channel group per K-step; output F16X2 (N % 32 == 0)
-// or fp32; residual F16X2 or fp32.  Measured inside the network (R50 bs 8, random frames, same box): flexible tile heights on EVERY grid lose to
-// fixed 128 x 128 / 128 x 64 tiles (5578 vs 5529 us of kernels per step; on zero-filled microbenchmarks they win 10-15 % on the 80^2 maps -
-// at the clocks random data allows and with cold operands they do not), a persistent three-role kernel lost more (5740 us: its store waves
-// compete with the MFMA waves for the SIMDs' issue slots) - both were removed in round 3; flexible heights stay on the small grids where
-// they fill idle CUs (ConvOpts::split_flex).
-int conv_kpad_split(int K) { return 2 * ((K + SPLIT_GROUP - 1) / SPLIT_GROUP * SPLIT_GROUP); }   // 16-bit elements of a filter row
-
 // ------------------------------------------------------------------------------------------------
 // Streaming 1x1 convolution on F16X2 operands for the thin, very wide-grid expand convs of the first backbone stages
 // (stage-0 c3: 64 [+ 64 shortcut] -> 256 channels at 160^2, stage-1 c3: 128 -> 512 at 80^2): 0.3-0.5 GB per launch and 7-13 GFLOP, i.e.
@@ -2053,78 +1896,6 @@ __global__ __launch_bounds__(512, 2) void conv1x1_sx_kernel(const ConvK a, unsig
   });
 }
 
-// shapes the streaming pair kernel takes (ConvOpts::split_sx); per-IMAGE extents only (see the kernel comment)
-static bool sx_shape_ok(const ConvArgs& a) {
-  const int g_split_sx = opts_of(a).split_sx;
-  const Tensor& x = a.x;
-  const Tensor& y = a.y;
-  const bool dual = a.x2.p != nullptr;
-  if (!g_split_sx || x.dt != F16X2 || !(y.dt == F16X2 || y.dt == F32) || a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0 || a.x_up2) return false;
-  if (a.res_mode != RES_NONE && (a.res.dt != F16X2 || dual)) return false;
-  if (y.c % 256) return false;
-  // K = 256 (value projection 256 -> 1536 fp32; split_sx 4: stage-2 expand convs 256 -> 1024 + residual at 40^2): either output type
-  // (N >= 1024 only: with one or two channel blocks per pixel tile the tiled kernel is faster - decoder input projection 36 vs 46 us)
-  if (x.c == 256) return g_split_sx >= 3 && y.c >= 1024 && !dual && a.next_y.p == nullptr && (a.res_mode == RES_NONE || (g_split_sx >= 4 && y.dt == F16X2)) &&
-                         (long long)y.h * y.w >= (g_split_sx >= 4 ? 1600 : 6400);
-  if ((long long)y.h * y.w < 6400) return false;
-  if (y.dt != F16X2) return false;
-  if (dual) return x.c == 64 && a.x2.c == 64 && y.c == 256;
-  if (x.c == 64) return true;
-  return x.c == 128 && g_split_sx >= 2 && a.next_y.p == nullptr;
-}
-static bool dispatch_sx(const ConvK& k, const ConvArgs& a, long long x_bytes, long long x2_bytes, hipStream_t s) {
-  if (!sx_shape_ok(a)) return false;
-  const Tensor& y = a.y;
-  const bool dual = a.x2.p != nullptr, res = a.res_mode != RES_NONE, next = a.next_y.p != nullptr;
-  const long long y_bytes = ((long long)(y.n - 1) * y.bstride + ((long long)y.h * y.w - 1) * y.ld + y.c) * 4;
-  long long r_bytes = 0, yn_bytes = 0;
-  if (res) r_bytes = ((long long)(a.res.n - 1) * a.res.bstride + ((long long)a.res.h * a.res.w - 1) * a.res.ld + a.res.c) * 4;
-  if (next) {
-    if (!(y.c == 256 && (a.next_y.c == 64 || a.next_y.c == 128) && a.next_y.dt == F16X2 && a.next_y.ld % SPLIT_GROUP == 0 && ((uintptr_t)a.next_y.p & 15) == 0 &&
-          a.next_kpad == conv_kpad_split(256) && a.next_w && a.next_bias && (a.next_act == ACT_RELU || a.next_act == ACT_NONE))) return false;
-    yn_bytes = ((long long)(a.next_y.n - 1) * a.next_y.bstride + ((long long)a.next_y.h * a.next_y.w - 1) * a.next_y.ld + a.next_y.c) * 4;
-  }
-  if (y_bytes >= (1ll << 31) || r_bytes >= (1ll << 31) || yn_bytes >= (1ll << 31)) return false;
-  // the averaged copy for the next stage's vd shortcut (ConvArgs::avg_y): 2 x 16 patch tiles, the two variants a stage ends with
-  const bool avg = a.avg_y.p != nullptr;
-  AvgOut ao{};
-  if (avg) {
-    const Tensor& v = a.avg_y;
-    if (!(v.dt == F16X2 && y.dt == F16X2 && res && !dual && (y.h & 1) == 0 && (y.w & 15) == 0 && v.h == y.h / 2 && v.w == y.w / 2 && v.c == y.c && v.n == y.n &&
-          v.ld % SPLIT_GROUP == 0 && ((uintptr_t)v.p & 15) == 0 && ((a.x.c == 64 && next && a.next_y.c == 128) || (a.x.c == 128 && !next)))) return false;
-    const long long vb = ((long long)(v.n - 1) * v.bstride + ((long long)v.h * v.w - 1) * v.ld + v.c) * 4;
-    if (vb >= (1ll << 31)) return false;
-    ao.y = (sp16*)v.p; ao.ldy = v.ld; ao.bstride = v.bstride; ao.y_bytes = (unsigned)vb;
-  }
-  const long long ntiles = avg ? (long long)y.n * (y.h / 2) * (y.w / 16) : ((long long)k.M + 31) / 32;
-  if (ntiles >= (1ll << 30)) return false;
-  const int ny = y.c / 256;
-  // persistent, two 8-wave blocks per CU: 8 XCDs x nts tile streams x ny channel blocks
-  const int nts = (int)std::max<long long>(1, std::min<long long>(64 / ny, (ntiles + 7) / 8));
-  const dim3 grid((unsigned)(8 * nts * ny)), blk(512);
-#define RTD_SX(NGX, NG2, RES_, NX) rtd_launch((conv1x1_sx_kernel<NGX, NG2, RES_, NX>), grid, blk, 0, s, k, (unsigned)x_bytes, (unsigned)r_bytes, \
-                                                     (unsigned)y_bytes, (unsigned)x2_bytes, (int)ntiles, (unsigned)yn_bytes, ny, ao)
-  const int nx = next ? a.next_y.c : 0;
-  if (avg) {
-    // ConvArgs::y_dead: y's only readers are the two fused consumers of this very launch - a zero-byte descriptor drops its stores
-    const unsigned yb = (a.y_dead && next) ? 0u : (unsigned)y_bytes;
-    if (a.x.c == 64) rtd_launch((conv1x1_sx_kernel<2, 0, true, 128, false, true>), grid, blk, 0, s, k, (unsigned)x_bytes, (unsigned)r_bytes, yb,
-                                        (unsigned)x2_bytes, (int)ntiles, (unsigned)yn_bytes, ny, ao);
-    else rtd_launch((conv1x1_sx_kernel<4, 0, true, 0, false, true>), grid, blk, 0, s, k, (unsigned)x_bytes, (unsigned)r_bytes, (unsigned)y_bytes,
-                            (unsigned)x2_bytes, (int)ntiles, (unsigned)yn_bytes, ny, ao);
-  } else if (dual) { if (nx == 64) RTD_SX(2, 2, false, 64); else if (nx == 128) RTD_SX(2, 2, false, 128); else RTD_SX(2, 2, false, 0); }
-  else if (a.x.c == 64 && res) { if (nx == 64) RTD_SX(2, 0, true, 64); else if (nx == 128) RTD_SX(2, 0, true, 128); else RTD_SX(2, 0, true, 0); }
-  else if (a.x.c == 64) { if (nx == 64) RTD_SX(2, 0, false, 64); else if (nx == 128) RTD_SX(2, 0, false, 128); else RTD_SX(2, 0, false, 0); }
-  else if (a.x.c == 256 && y.dt == F32) rtd_launch((conv1x1_sx_kernel<8, 0, false, 0, true>), grid, blk, 0, s, k, (unsigned)x_bytes, 0u, (unsigned)y_bytes, 0u, (int)ntiles, 0u, ny, ao);
-  else if (a.x.c == 256 && res) RTD_SX(8, 0, true, 0);
-  else if (a.x.c == 256) RTD_SX(8, 0, false, 0);
-  else if (res) RTD_SX(4, 0, true, 0);
-  else RTD_SX(4, 0, false, 0);
-#undef RTD_SX
-  return true;
-}
-
-
 // Second pass of the two-pass split-K: y = act(sum_s slab[s] + bias (+ res)), slices in fixed order (one summation order per output whatever the
 // batch size), written in the layer's own output format.  One thread = 8 channels of a pixel.
 __global__ __launch_bounds__(256) void k_splitk_reduce(const ConvK a, const float* __restrict__ slab, int S) {
@@ -2166,6 +1937,475 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const ConvK a, const floa
     *(f32x4*)((float*)a.y + ypix + c + 4) = f32x4{v[4], v[5], v[6], v[7]};
   }
 }
+
+// ================================================================================================
+// Host side ("Conv dispatch"): geometry -> checks -> ConvK -> a pure choice of the kernel -> its launch.
+// ================================================================================================
+int conv_kpad(int K) { return (K + 63) / 64 * 64; }
+int conv_npad(int N) { return (N + 127) / 128 * 128; }
+int conv_kpad_split(int K) { return 2 * ((K + SPLIT_GROUP - 1) / SPLIT_GROUP * SPLIT_GROUP); }   // 16-bit elements of a filter row
+
+static ConvOpts g_conv_opts;
+ConvOpts& conv_opts_template() { return g_conv_opts; }
+bool conv_set_option(const char* name, int value) {
+  ConvOpts& o = g_conv_opts;
+  const struct { const char* n; int* p; } table[] = {
+      {"conv_mode", &o.conv_mode}, {"glds_min_blocks", &o.glds_min_blocks}, {"glds_min_n", &o.glds_min_n},
+      {"ws2_min_blocks", &o.ws2_min_blocks}, {"ws64_max_blocks", &o.ws64_max_blocks},
+      {"reg_epilogue", &o.reg_epilogue}, {"conv_reg", &o.conv_reg},
+      {"prefetch", &o.prefetch},
+      {"split_ws2_min_blocks", &o.split_ws2_min_blocks}, {"split_ws64_max_blocks", &o.split_ws64_max_blocks},
+      {"split_flex", &o.split_flex}, {"split_flex_min_nk", &o.split_flex_min_nk}, {"split_flex_small_max", &o.split_flex_small_max},
+      {"split_sx", &o.split_sx}, {"split_k2", &o.split_k2}, {"split_wsq", &o.split_wsq}, {"split_wsq_min_blocks", &o.split_wsq_min_blocks},
+      {"split_wsq_min_nk", &o.split_wsq_min_nk},
+  };
+  for (const auto& t : table)
+    if (strcmp(name, t.n) == 0) { *t.p = value; return true; }
+  return false;
+}
+static inline const ConvOpts& opts_of(const ConvArgs& a) { return a.opts ? *a.opts : g_conv_opts; }
+
+// ---- geometry and extents -----------------------------------------------------------------------------------------------------------
+static constexpr long long DESC_LIMIT = 1ll << 31;   // a buffer descriptor (and the tile kernels' 32-bit offsets) addresses less than 2 GiB
+static constexpr long long TILE_LIMIT = 1ll << 30;   // the persistent kernels count tiles in 30 bits
+
+// bytes from a view's first element to the end of its last pixel; F16X2 views: elem_bytes = 4 per channel
+static long long span_bytes(const Tensor& t, long long elem_bytes) {
+  return ((long long)(t.n - 1) * t.bstride + ((long long)t.h * t.w - 1) * t.ld + t.c) * elem_bytes;
+}
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+struct ConvGeom {
+  int up;        // 2: x is read through a nearest 2x upsampling (ConvArgs::x_up2)
+  int OH, OW;    // output map
+  long long M;   // output pixels of the whole batch
+  bool dual;     // a second input (ConvArgs::x2) follows the taps of x
+  int K;         // filter row: KH * KW * Cin (+ C2), in channels
+  explicit ConvGeom(const ConvArgs& a)
+      : up(a.x_up2 ? 2 : 1), OH((a.x.h * up + 2 * a.pad - a.KH) / a.stride + 1), OW((a.x.w * up + 2 * a.pad - a.KW) / a.stride + 1),
+        M((long long)a.x.n * OH * OW), dual(a.x2.p != nullptr), K(a.KH * a.KW * a.x.c + (dual ? a.x2.c : 0)) {}
+};
+
+// tiles of the direct 3x3 kernels: 8 rows x `tw` columns of the (same-size) map
+struct RegTiles {
+  int tx, ty;
+  long long n;   // over the batch
+  RegTiles(const Tensor& x, int tw) : tx((x.w + tw - 1) / tw), ty((x.h + 7) / 8), n((long long)x.n * tx * ty) {}
+};
+
+// ---- the kernels' argument block ----------------------------------------------------------------------------------------------------
+// Pair operands (x.dt == F16X2): every count along K or along a pixel of x / x2 is in 16-bit elements, two per channel (ConvK::split).
+// ntn stays 1 here: launch_choice() sets it from the choice.
+static ConvK make_convk(const ConvArgs& a, const ConvGeom& g, const ConvOpts& o) {
+  const Tensor& x = a.x;
+  const Tensor& y = a.y;
+  const bool pair = x.dt == F16X2, res = a.res_mode != RES_NONE;
+  const int e = pair ? 2 : 1;
+  ConvK k;
+  k.x = x.p; k.w = a.w; k.bias = a.bias; k.y = y.p;
+  k.M = (int)g.M; k.H = x.h * g.up; k.W = x.w * g.up; k.x_up2 = a.x_up2;
+  k.Cin = e * x.c; k.ldx = e * x.ld; k.x_bstride = e * x.bstride;
+  k.OH = g.OH; k.OW = g.OW; k.OHW = g.OH * g.OW;
+  k.N = y.c; k.Kreal = e * g.K; k.Kpad = a.Kpad;
+  k.KH = a.KH; k.KW = a.KW; k.stride = a.stride; k.pad = a.pad;
+  k.ldy = y.ld; k.y_bstride = y.bstride;                                             // channels (bf16, fp32 or F16X2 alike)
+  k.act = a.act; k.res_mode = a.res_mode; k.y_f32 = y.dt == F32;
+  k.split = pair; k.y_split = y.dt == F16X2;
+  if (res) { k.res = a.res.p; k.ldr = a.res.ld; k.r_bstride = a.res.bstride; k.res_f32 = a.res.dt == F32; k.res_split = pair && a.res.dt == F16X2; }
+  if (g.dual) { k.x2 = a.x2.p; k.ldx2 = e * a.x2.ld; k.x2_bstride = e * a.x2.bstride; k.k2_start = e * a.KH * a.KW * x.c; }
+  k.next_w = a.next_w; k.next_bias = a.next_bias; k.next_y = a.next_y.p; k.next_ldy = a.next_y.ld; k.next_y_bstride = a.next_y.bstride;   // channels
+  k.next_kpad = a.next_kpad; k.next_act = a.next_act;
+  k.reg_epi = pair ? 1 : o.reg_epilogue;
+  k.prefer256 = pair ? 0 : a.prefer256;
+  k.pf = o.prefetch ? a.pf : nullptr;
+  k.pf_bytes = (o.prefetch && a.pf && a.pf_bytes < (1ull << 31)) ? (unsigned)a.pf_bytes : 0u;
+  return k;
+}
+
+// Two-pass split-K, first pass: the tile kernels write bare fp32 partial sums (no bias, residual or activation) to their slice of the
+// slab; k_splitk_reduce finishes the layer from the unmodified ConvK.
+static ConvK splitk_partial(ConvK k, float* slab) {
+  k.raw = 1; k.act = ACT_NONE; k.res_mode = RES_NONE; k.res = nullptr; k.res_split = 0;
+  k.y = slab; k.y_f32 = 1; k.y_split = 0; k.ldy = k.N; k.y_bstride = (long long)k.OHW * k.N;
+  return k;
+}
+
+// the LDS-DMA tile kernels' argument block: ConvK + the operands' descriptor extents (pair filters: 2 bytes per 16-bit element)
+static ConvG make_convg(const ConvK& k, const ConvArgs& a, int S) {
+  const bool pair = a.x.dt == F16X2;
+  const long long xe = pair ? 4 : (long long)dtype_size(a.x.dt), we = pair ? 2 : xe;
+  ConvG g;
+  g.k = k; g.splitk = S;
+  g.x_bytes = (unsigned)span_bytes(a.x, xe); g.w_bytes = (unsigned)((long long)a.Npad * a.Kpad * we); g.x2_bytes = a.x2.p ? (unsigned)span_bytes(a.x2, xe) : 0u;
+  return g;
+}
+
+// ---- the choice ---------------------------------------------------------------------------------------------------------------------
+enum class ConvFamily {
+  Tile,       // conv_igemm_kernel<T, bm, bn, smallc>: register-staged, every shape
+  Ws,         // conv_igemm_ws_kernel<T, stages, bn>: LDS-DMA tiles on bf16 / fp32 operands
+  Sx,         // conv1x1_sx_kernel<SX_VARIANTS[sx]>: streaming 1x1 on pair operands
+  Reg3x3,     // conv3x3_reg_split_kernel<cog>: direct 3x3, 32 input channels
+  Reg3x3_64,  // conv3x3_reg_split64_kernel: direct 3x3, 64 -> 64 channels
+  Wsf,        // conv_igemm_wsf_kernel<stages, bn, mt>: pair tiles of 16 mt pixels
+  Wsq,        // conv_igemm_wsq_kernel<WSQ_TILES[wsq]>: pair tiles of 16 (MTA + MTB) pixels
+  Wsx,        // conv_igemm_wsx_kernel<stages, bn>: pair tiles of 128 pixels
+};
+struct ConvChoice {
+  ConvFamily family = ConvFamily::Tile;
+  int stages = 0, bn = 0;    // Ws, Wsf, Wsx; Tile: bn
+  int mt = 0;                // Wsf
+  int bm = 0;                // Tile
+  bool smallc = false;       // Tile
+  int wsq = -1;              // Wsq: index into WSQ_TILES
+  int sx = -1;               // Sx: index into SX_VARIANTS
+  int cog = 0;               // Reg3x3: output channel groups of 32
+  unsigned grid = 0;         // blocks
+  int ntn = 1;               // ConvK::ntn: tiles along the output channels (tile families)
+  int S = 1;                 // pair operands: slices of the two-pass split-K (1 = one pass); what conv_split_slab_bytes() sizes the slab for
+};
+
+// f(std::integral_constant<int, I>{}) for the runtime i in [LO, HI]; false (and no call) outside.  Every I of the range is instantiated.
+template <int LO, int HI, typename F>
+static bool with_int(int i, F&& f) {
+  if constexpr (LO > HI) {
+    return false;
+  } else {
+    if (i == LO) { f(std::integral_constant<int, LO>{}); return true; }
+    return with_int<LO + 1, HI>(i, f);
+  }
+}
+
+// "The LDS-DMA kernels take this" on bf16 / fp32 operands: whole K-steps of input channels, 16-byte output (and residual) rows, a grid and
+// a channel count worth the tile, operands inside a buffer descriptor.  choose_plain() and conv_dual_supported() both ask it.
+// N >= 64 may use a partly empty N tile (the filter is padded to 128 rows): the N = 64 reduce convs of stage 0 are HBM-bound, and the
+// LDS-DMA pipeline (2 blocks per CU) streams their input faster than the register-staged kernel
+static bool glds_takes(const ConvOpts& o, const ConvArgs& a, const ConvGeom& g, long long w_bytes) {
+  const Tensor& x = a.x;
+  const Tensor& y = a.y;
+  const int es = (int)dtype_size(x.dt);
+  if (x.c % (128 / es) || y.c % 8 || y.ld % 8 || !aligned16(y.p)) return false;
+  if (a.res_mode != RES_NONE && (a.res.ld % 8 || !aligned16(a.res.p))) return false;
+  const long long mt = (g.M + 127) / 128, ntn = (y.c + 127) / 128;
+  if (y.c < (es == 2 ? o.glds_min_n : 64) || mt * ntn < (es == 2 ? o.glds_min_blocks : 512)) return false;
+  return span_bytes(x, es) < DESC_LIMIT && w_bytes < DESC_LIMIT;
+}
+
+// bf16 / fp32 operands: the LDS-DMA tile where it is taken (the only family with a second input), else the register-staged kernel.
+// fp32 -> F16X2 (the split engine's stem.0) exists in the register-staged kernel's epilogue only.
+static ConvChoice choose_plain(const ConvArgs& a, const ConvGeom& g, const ConvOpts& o, long long w_bytes) {
+  const int N = a.y.c;
+  ConvChoice c;
+  if (a.y.dt != F16X2 && !(o.conv_mode == 1 && !g.dual) && glds_takes(o, a, g, w_bytes)) {
+    const long long mt = (g.M + 127) / 128, ntn = (N + 127) / 128;
+    c.family = ConvFamily::Ws;
+    // small grids: 128 x 64 tiles double the blocks (latency profile only: with other batches in flight the idle CUs are taken anyway and
+    // the narrower tile stages 1.5x the bytes per MFMA - measured +1.4 % for one handle, -1 % for three); conv_mode 10 forces it for the tests
+    if ((o.conv_mode == 0 && !a.prefer256 && mt * ntn < o.ws64_max_blocks && N > 64) || o.conv_mode == 10) {
+      c.stages = 4; c.bn = 64; c.ntn = (N + 63) / 64;
+    } else {
+      // loader / MFMA wave roles win at every grid size (tools/profile_layers.py): grids beyond one block per CU run 2 blocks per CU with
+      // 2 stages, smaller grids 1 block per CU with 4 stages (3 tiles of DMA in flight); conv_mode 3 / 4 force either, except on
+      // dual-input launches, which exist in this kernel only and follow the grid in every conv_mode
+      const bool four = g.dual ? mt * ntn < o.ws2_min_blocks : (o.conv_mode == 3 || (o.conv_mode != 4 && mt * ntn < o.ws2_min_blocks));
+      c.stages = four ? 4 : 2; c.bn = 128; c.ntn = (int)ntn;
+    }
+    c.grid = (unsigned)(mt * c.ntn);
+    return c;
+  }
+  // register-staged fallback: every shape (small channel counts, grids below the LDS-DMA kernels' thresholds)
+  const long long b128 = (g.M + 127) / 128;
+  const int n128 = (N + 127) / 128, n64 = (N + 63) / 64;
+  if (b128 * n128 >= 512 && N > 64) { c.bm = 128; c.bn = 128; }
+  else if (b128 * n64 >= 384) { c.bm = 128; c.bn = 64; }
+  else { c.bm = 64; c.bn = 64; }
+  c.smallc = (a.x.c % 32) != 0;
+  c.ntn = (N + c.bn - 1) / c.bn;
+  c.grid = (unsigned)(((g.M + c.bm - 1) / c.bm) * c.ntn);
+  return c;
+}
+
+// ---- the streaming pair kernel's rules (conv1x1_sx_kernel), stated once: conv_next_supported(), conv_avg_supported(),
+// conv_sx_batch_fits() and the choice are built from these ----
+// shapes it takes (ConvOpts::split_sx); per-IMAGE extents only (see the kernel comment)
+static bool sx_shape_ok(const ConvArgs& a) {
+  const int g_split_sx = opts_of(a).split_sx;
+  const Tensor& x = a.x;
+  const Tensor& y = a.y;
+  const bool dual = a.x2.p != nullptr;
+  if (!g_split_sx || x.dt != F16X2 || !(y.dt == F16X2 || y.dt == F32) || a.KH != 1 || a.KW != 1 || a.stride != 1 || a.pad != 0 || a.x_up2) return false;
+  if (a.res_mode != RES_NONE && (a.res.dt != F16X2 || dual)) return false;
+  if (y.c % 256) return false;
+  // K = 256 (value projection 256 -> 1536 fp32; split_sx 4: stage-2 expand convs 256 -> 1024 + residual at 40^2): either output type
+  // (N >= 1024 only: with one or two channel blocks per pixel tile the tiled kernel is faster - decoder input projection 36 vs 46 us)
+  if (x.c == 256) return g_split_sx >= 3 && y.c >= 1024 && !dual && a.next_y.p == nullptr && (a.res_mode == RES_NONE || (g_split_sx >= 4 && y.dt == F16X2)) &&
+                         (long long)y.h * y.w >= (g_split_sx >= 4 ? 1600 : 6400);
+  if ((long long)y.h * y.w < 6400) return false;
+  if (y.dt != F16X2) return false;
+  if (dual) return x.c == 64 && a.x2.c == 64 && y.c == 256;
+  if (x.c == 64) return true;
+  return x.c == 128 && g_split_sx >= 2 && a.next_y.p == nullptr;
+}
+// the fused following conv (ConvArgs::next_*): 256 -> 64 or 128 channels on the tile the eight slabs hold, F16X2 in whole groups
+static bool sx_next_shape_ok(const ConvArgs& a) {
+  return a.y.c == 256 && (a.next_y.c == 64 || a.next_y.c == 128) && a.next_y.dt == F16X2 && a.next_y.ld % SPLIT_GROUP == 0 && a.y.ld % SPLIT_GROUP == 0;
+}
+// the fused 2 x 2 average (ConvArgs::avg_y): 2-row x 16-column patch tiles, in the two variants a stage ends with (64 -> 256 with the
+// next stage's 256 -> 128 reduce conv riding on it, or 128 -> N alone), both with a residual
+static bool sx_avg_shape_ok(const ConvArgs& a) {
+  const bool next = a.next_y.p != nullptr;
+  return a.y.dt == F16X2 && !a.x2.p && a.res_mode != RES_NONE && (a.y.h & 1) == 0 && (a.y.w & 15) == 0 &&
+         ((a.x.c == 64 && next && a.next_y.c == 128) || (a.x.c == 128 && !next));
+}
+static long long sx_ntiles(const ConvArgs& a) {
+  const Tensor& y = a.y;
+  return a.avg_y.p ? (long long)y.n * (y.h / 2) * (y.w / 16) : ((long long)y.n * y.h * y.w + 31) / 32;
+}
+// The streaming kernel addresses every tensor through a 2 GiB buffer descriptor and counts tiles in 30 bits: limits that depend on the
+// BATCH, unlike every shape test (which looks at one image).  The plan builder asks this with the plan's real batch before it relies on a
+// fusion that only the streaming kernel implements (ConvArgs::avg_y); the choice applies the same limits.
+bool conv_sx_batch_fits(const ConvArgs& a) {
+  auto fits = [](bool used, const Tensor& t) { return !used || span_bytes(t, 4) < DESC_LIMIT; };
+  return fits(true, a.y) && fits(a.res_mode != RES_NONE, a.res) && fits(a.next_y.p, a.next_y) && fits(a.avg_y.p, a.avg_y) && sx_ntiles(a) < TILE_LIMIT;
+}
+// The fused following conv exists in the streaming kernel for N = 256 (K = 64, or 64 + 64 with a second input) -> 64 channels and
+// N = 512 (K = 128) -> 128 channels.  Asked per plan (batch size): the fused and the separate form use the same filter tensors and
+// give bit-identical outputs, so plans of different batch sizes may differ.  bf16 / fp32 operands: no kernel with a fused following
+// conv (round 5: the bf16 streaming kernels were removed)
+bool conv_next_supported(const ConvArgs& a) { return a.x.dt == F16X2 && sx_shape_ok(a) && sx_next_shape_ok(a); }
+bool conv_avg_supported(const ConvArgs& a) {
+  if (a.x.dt != F16X2 || a.y.dt != F16X2 || !sx_shape_ok(a) || a.y.ld % SPLIT_GROUP) return false;
+  return sx_avg_shape_ok(a) && (a.x.c != 64 || (a.y.c == 256 && conv_next_supported(a)));
+}
+
+// the instantiated conv1x1_sx_kernel<NGX, NG2, RES, NEXTN, F32OUT, AVG>: 32-channel K groups from x / x2, residual, fused next conv's
+// channels (0 = none), fp32 rows out, fused average
+struct SxVariant { int ngx, ng2; bool res; int nextn; bool f32out, avg; };
+static constexpr SxVariant SX_VARIANTS[16] = {
+    {2, 0, false, 0, false, false}, {2, 0, false, 64, false, false}, {2, 0, false, 128, false, false},   // stage-0 c3: 64 -> 256
+    {2, 0, true, 0, false, false},  {2, 0, true, 64, false, false},  {2, 0, true, 128, false, false},
+    {2, 2, false, 0, false, false}, {2, 2, false, 64, false, false}, {2, 2, false, 128, false, false},   // ... with the projection shortcut as x2
+    {4, 0, false, 0, false, false}, {4, 0, true, 0, false, false},                                       // stage-1 c3: 128 -> 512
+    {8, 0, false, 0, false, false}, {8, 0, true, 0, false, false},  {8, 0, false, 0, true, false},       // K = 256
+    {2, 0, true, 128, false, true}, {4, 0, true, 0, false, true},                                        // a stage's last conv: + average
+};
+
+// Takes the launch when the shape rules hold, the fused consumers' tensors are what the kernel expects (launch-side conditions the
+// shape predicates leave out: pointers present and 16-byte aligned, the next filter's padding and activation, the averaged tensor's
+// extents) and the batch fits.  A launch it declines goes on to the tile kernels; launch_conv_split() rejects one that needed a fusion.
+static bool choose_sx(const ConvArgs& a, ConvChoice& c) {
+  const Tensor& y = a.y;
+  if (!sx_shape_ok(a) || y.c < 256) return false;
+  const bool dual = a.x2.p != nullptr, res = a.res_mode != RES_NONE, next = a.next_y.p != nullptr, avg = a.avg_y.p != nullptr;
+  if (next && !(sx_next_shape_ok(a) && aligned16(a.next_y.p) && a.next_kpad == conv_kpad_split(256) && a.next_w && a.next_bias &&
+                (a.next_act == ACT_RELU || a.next_act == ACT_NONE))) return false;
+  if (avg) {
+    const Tensor& v = a.avg_y;
+    if (!(sx_avg_shape_ok(a) && v.dt == F16X2 && v.h == y.h / 2 && v.w == y.w / 2 && v.c == y.c && v.n == y.n && v.ld % SPLIT_GROUP == 0 && aligned16(v.p))) return false;
+  }
+  if (!conv_sx_batch_fits(a)) return false;
+  const SxVariant want{a.x.c / SPLIT_GROUP, dual ? 2 : 0, res, next ? a.next_y.c : 0, y.dt == F32, avg};
+  for (int i = 0; i < 16 && c.sx < 0; ++i) {
+    const SxVariant& v = SX_VARIANTS[i];
+    if (v.ngx == want.ngx && v.ng2 == want.ng2 && v.res == want.res && v.nextn == want.nextn && v.f32out == want.f32out && v.avg == want.avg) c.sx = i;
+  }
+  if (c.sx < 0) return false;   // (the shape rules admit instantiated variants only)
+  // persistent, two 8-wave blocks per CU: 8 XCDs x nts tile streams x ny channel blocks
+  const int ny = y.c / 256;
+  const int nts = (int)std::max<long long>(1, std::min<long long>(64 / ny, (sx_ntiles(a) + 7) / 8));
+  c.family = ConvFamily::Sx;
+  c.grid = (unsigned)(8 * nts * ny);
+  return true;
+}
+
+// Two-pass split-K (ConvOpts::split_k2) on long-K layers whose per-IMAGE tile count is small (stage 3, the 20^2 PAN level, enc.proj.2 at
+// 640 px; most layers at smaller inputs).  The slice count depends on per-image extents and K only: every batch size runs the same
+// arithmetic (the plan builder sizes the workspace from conv_split_slab_bytes() for its own batch).  Measured on R50 640^2 (stage-3 3x3,
+// K = 4608: 144 K-steps): batch 1 54 -> 35 us per layer (16 blocks -> 32), batch 8 57 -> 62 us; shorter K loops (stage-3 1x1, the 20^2 PAN
+// level) lose at batch 8 and gain nothing at batch 1, hence the 128-step floor.
+static int split_k2_slices(const ConvOpts& o, const ConvArgs& a, const ConvGeom& g) {
+  if (!o.split_k2 || g.dual || a.x_up2 || a.y.c % 8 || a.next_y.p) return 1;
+  if (sx_shape_ok(a)) return 1;
+  const long long tiles_img = (((long long)g.OH * g.OW + 127) / 128) * ((a.y.c + 127) / 128);
+  const int groups = a.x.c / SPLIT_GROUP, nk_total = a.KH * a.KW * groups;
+  if (nk_total >= 128 && tiles_img <= 8 && groups % 4 == 0) return 4;
+  if (nk_total >= 128 && tiles_img <= 16 && groups % 2 == 0) return 2;
+  return 1;
+}
+
+// the instantiated conv_igemm_wsf_kernel<ST, BN, MT>: MT = 4 .. wsf_max_mt(ST, BN) (0: none)
+static constexpr int wsf_max_mt(int st, int bn) { return st == 2 ? (bn == 128 ? 8 : 0) : (bn == 64 ? 8 : 13); }
+// the instantiated conv_igemm_wsq_kernel<MTA, MTB>
+static constexpr int WSQ_TILES[7][2] = {{5, 5}, {6, 5}, {6, 6}, {7, 6}, {7, 7}, {8, 7}, {8, 8}};
+
+// Pair operands (F16X2 tensors, common.h), in this order: streaming 1x1 -> direct 3x3 (32 input channels) -> direct 3x3 (64 -> 64) ->
+// [two-pass split-K slices] flexible tile height -> (MTA + MTB) x 16 pixel tiles -> fixed 128-pixel tiles.
+// Measured inside the network (R50 bs 8, random frames, same box): flexible tile heights on EVERY grid lose to
+// fixed 128 x 128 / 128 x 64 tiles (5578 vs 5529 us of kernels per step; on zero-filled microbenchmarks they win 10-15 % on the 80^2 maps -
+// at the clocks random data allows and with cold operands they do not), a persistent three-role kernel lost more (5740 us: its store waves
+// compete with the MFMA waves for the SIMDs' issue slots) - both were removed in round 3; flexible heights stay on the small grids where
+// they fill idle CUs (ConvOpts::split_flex).
+static ConvChoice choose_pair(const ConvArgs& a, const ConvGeom& g, const ConvOpts& o) {
+  const Tensor& x = a.x;
+  const Tensor& y = a.y;
+  ConvChoice c;
+  const int S = c.S = split_k2_slices(o, a, g);
+  // thin 1x1 expand convs on wide grids (stage-0 / stage-1 c3): the streaming kernel, with the next block's reduce conv riding on it
+  if (choose_sx(a, c)) return c;
+  // Direct 3x3 kernels for the narrow layers on wide maps.  Chosen on the per-IMAGE tile count: every batch size runs the same arithmetic
+  // (batch invariance is bit-exact).  32 input channels (stem.1, stem.2): every input pixel is staged once instead of nine times
+  const bool narrow3x3 = a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && !g.dual && a.res_mode == RES_NONE && y.dt == F16X2;
+  if (o.conv_reg && narrow3x3 && x.c == 32 && (y.c == 32 || y.c == 64)) {
+    const RegTiles t(x, 32);
+    if (t.tx * t.ty >= 32 && t.n < TILE_LIMIT && span_bytes(y, 4) < DESC_LIMIT) {
+      c.family = ConvFamily::Reg3x3; c.cog = y.c / 32;
+      c.grid = (unsigned)std::min<long long>(t.n, 256);        // persistent, one block per CU
+      return c;
+    }
+  }
+  // 64 -> 64 channels (stage-0 c2): direct kernel on 8 x 16 tiles
+  if ((o.conv_reg & 2) && narrow3x3 && x.c == 64 && y.c == 64) {
+    const RegTiles t(x, 16);
+    if (t.tx * t.ty >= 128 && t.n < TILE_LIMIT && span_bytes(y, 4) < DESC_LIMIT) {
+      c.family = ConvFamily::Reg3x3_64;
+      c.grid = (unsigned)std::min<long long>(t.n, 256);        // persistent, one block per CU
+      return c;
+    }
+  }
+  // ---- the LDS-DMA tile kernels; with S > 1 the grid is S x tiles and every block walks 1 / S of the channel groups
+  const long long M = g.M;
+  const int N = y.c;
+  const long long mt = (M + 127) / 128, ntn = (N + 127) / 128, ntn64 = (N + 63) / 64;
+  // ---- flexible tile height (conv_igemm_wsf_kernel) on grids that leave CUs idle with 128-pixel tiles (20^2 maps at batch 8, most layers at
+  // batch 1: R50 bs-1 latency 2.49 -> 2.36 ms): the tile whose grid fills whole rounds of the chip.
+  // split_flex_min_nk, same-box sweep, R50 bs 8: 16 / 8 / 4 / 2 -> 4.884 / 4.878 / 4.854 / 4.866 ms per step;
+  // split_flex_small_max, sweep 128 / 200 / 256 / 400 -> 4.816 / 4.776 / 4.779 / 4.777 ms per step
+  if (o.split_flex && a.Kpad / 64 / S >= o.split_flex_min_nk && N >= 64 && mt * ntn * S <= o.split_flex_small_max) {
+    int best_mt = 0, best_bn = 0, best_st = 0;
+    double best = 1e30;
+    for (int bn = (N > 64 ? 128 : 64); bn >= 64; bn -= 64) {
+      const long long ntb = (N + bn - 1) / bn;
+      for (int mtc = 4; mtc <= 13; ++mtc) {
+        const long long blocks = ((M + 16 * mtc - 1) / (16 * mtc)) * ntb * S;
+        const long long rounds = (blocks + 255) / 256;
+        const bool two = blocks > 256 && mtc <= 8;                 // 2 stages, two blocks per CU share the MFMA pipes; else 3 stages, one block per CU
+        double eff = (bn == 128 ? 1.0 : 0.78) * (1.0 - 0.6 / mtc);  // small tiles: more LDS reads and barriers per MFMA
+        if (!two && blocks > 256) eff *= 0.93;                     // nothing hides a lone block's barrier bubbles
+        const double cost = (double)rounds * mtc * bn / eff;
+        if (cost < best) { best = cost; best_mt = mtc; best_bn = bn; best_st = two ? 2 : 3; }
+      }
+    }
+    if (best_mt <= wsf_max_mt(best_st, best_bn)) {   // else: no such instantiation, the later families take the launch
+      c.family = ConvFamily::Wsf; c.stages = best_st; c.bn = best_bn; c.mt = best_mt;
+      c.ntn = (N + best_bn - 1) / best_bn;
+      c.grid = (unsigned)(((M + 16 * best_mt - 1) / (16 * best_mt)) * c.ntn * S);
+      return c;
+    }
+  }
+  // ---- grids of more than one round: (MTA + MTB) x 16 pixel tiles, one block per CU (conv_igemm_wsq_kernel).  The tile height minimises
+  // rounds x (K loop of the taller wave half + epilogue), in MFMA-pipe cycles.  split_wsq_min_nk, same-box A/B
+  // (tools/profile_layers.py --ab split_wsq): 3x3 layers 1.05-1.18x, 1x1 layers of 8-16 K-steps 0.80-0.96x
+  if (o.split_wsq && S == 1 && N > 64 && a.Kpad / 64 >= o.split_wsq_min_nk && (o.split_wsq == 2 || mt * ntn >= o.split_wsq_min_blocks)) {
+    const long long nk = a.Kpad / 64;
+    int best = -1;
+    double best_cost = 1e30;
+    for (int i = 0; i < 7; ++i) {
+      const int bm = 16 * (WSQ_TILES[i][0] + WSQ_TILES[i][1]);
+      const long long blocks = ((M + bm - 1) / bm) * ntn;
+      const double cost = (double)((blocks + 255) / 256) * ((double)nk * WSQ_TILES[i][0] * 192.0 + 1500.0 + 10.0 * bm);
+      if (cost < best_cost) { best_cost = cost; best = i; }
+    }
+    const int bm = 16 * (WSQ_TILES[best][0] + WSQ_TILES[best][1]);
+    c.family = ConvFamily::Wsq; c.wsq = best;
+    c.ntn = (int)ntn;
+    c.grid = (unsigned)(((M + bm - 1) / bm) * ntn);
+    return c;
+  }
+  // ---- fixed 128 x 128 / 128 x 64 tiles (conv_igemm_wsx_kernel): 4 stages at one block per CU below split_ws2_min_blocks blocks, 2 stages from there
+  const bool n64 = N <= 64 || (mt * ntn < o.split_ws64_max_blocks && ntn64 > ntn);
+  c.family = ConvFamily::Wsx; c.bn = n64 ? 64 : 128;
+  c.ntn = (int)(n64 ? ntn64 : ntn);
+  const long long blocks = mt * c.ntn * S;
+  c.stages = blocks < o.split_ws2_min_blocks ? 4 : 2;
+  c.grid = (unsigned)blocks;
+  return c;
+}
+
+// ---- the launch: instantiates what the choice names ---------------------------------------------------------------------------------
+static constexpr int TILE_BMN[3][2] = {{128, 128}, {128, 64}, {64, 64}};   // the instantiated conv_igemm_kernel<T, BM, BN, smallc>
+template <typename T>   // bf16 / fp32 operands: the register-staged kernel or the LDS-DMA tile
+static void launch_plain(const ConvChoice& c, const ConvK& k, const ConvArgs& a, hipStream_t s) {
+  if (c.family == ConvFamily::Tile) {
+    with_int<0, 2>(c.bm == 64 ? 2 : (c.bn == 64 ? 1 : 0), [&](auto I) {
+      with_int<0, 1>(c.smallc, [&](auto SC) { rtd_launch((conv_igemm_kernel<T, TILE_BMN[I()][0], TILE_BMN[I()][1], SC() != 0>), dim3(c.grid), dim3(256), 0, s, k); });
+    });
+    return;
+  }
+  const ConvG g = make_convg(k, a, 1);
+  auto go = [&](auto* kernel) { rtd_launch(kernel, dim3(c.grid), dim3(512), 0, s, g); };
+  if (c.bn == 64) go(conv_igemm_ws_kernel<T, 4, 64>);
+  else if (c.stages == 4) go(conv_igemm_ws_kernel<T, 4>);
+  else go(conv_igemm_ws_kernel<T, 2>);
+}
+static void launch_pair_tile(const ConvChoice& c, const ConvG& g, hipStream_t s) {
+  auto go = [&](auto* kernel) { rtd_launch(kernel, dim3(c.grid), dim3(512), 0, s, g); };
+  if (c.family == ConvFamily::Wsf) {
+    if (c.stages == 2) with_int<4, wsf_max_mt(2, 128)>(c.mt, [&](auto MT) { go(conv_igemm_wsf_kernel<2, 128, MT()>); });
+    else if (c.bn == 64) with_int<4, wsf_max_mt(3, 64)>(c.mt, [&](auto MT) { go(conv_igemm_wsf_kernel<3, 64, MT()>); });
+    else with_int<4, wsf_max_mt(3, 128)>(c.mt, [&](auto MT) { go(conv_igemm_wsf_kernel<3, 128, MT()>); });
+  } else if (c.family == ConvFamily::Wsq) {
+    with_int<0, 6>(c.wsq, [&](auto I) { go(conv_igemm_wsq_kernel<WSQ_TILES[I()][0], WSQ_TILES[I()][1]>); });
+  } else {
+    with_int<0, 1>(c.stages == 4, [&](auto FOUR) {
+      with_int<0, 1>(c.bn == 128, [&](auto WIDE) { go(conv_igemm_wsx_kernel<(FOUR() ? 4 : 2), (WIDE() ? 128 : 64)>); });
+    });
+  }
+}
+static void launch_sx(const ConvChoice& c, const ConvK& k, const ConvArgs& a, hipStream_t s) {
+  const bool next = a.next_y.p != nullptr;
+  const unsigned x_bytes = (unsigned)span_bytes(a.x, 4), x2_bytes = a.x2.p ? (unsigned)span_bytes(a.x2, 4) : 0u;
+  const unsigned r_bytes = a.res_mode != RES_NONE ? (unsigned)span_bytes(a.res, 4) : 0u, yn_bytes = next ? (unsigned)span_bytes(a.next_y, 4) : 0u;
+  // ConvArgs::y_dead: y's only readers are the two fused consumers of this very launch - a zero-byte descriptor drops its stores
+  const unsigned y_bytes = (a.avg_y.p && a.y_dead && next) ? 0u : (unsigned)span_bytes(a.y, 4);
+  AvgOut ao{};
+  if (a.avg_y.p) { ao.y = (sp16*)a.avg_y.p; ao.ldy = a.avg_y.ld; ao.bstride = a.avg_y.bstride; ao.y_bytes = (unsigned)span_bytes(a.avg_y, 4); }
+  with_int<0, 15>(c.sx, [&](auto I) {
+    constexpr SxVariant v = SX_VARIANTS[I()];
+    rtd_launch((conv1x1_sx_kernel<v.ngx, v.ng2, v.res, v.nextn, v.f32out, v.avg>), dim3(c.grid), dim3(512), 0, s, k, x_bytes, r_bytes, y_bytes, x2_bytes,
+               (int)sx_ntiles(a), yn_bytes, a.y.c / 256, ao);
+  });
+}
+static void launch_reg3x3(const ConvChoice& c, const ConvK& k, const ConvArgs& a, hipStream_t s) {
+  const unsigned x_bytes = (unsigned)span_bytes(a.x, 4), y_bytes = (unsigned)span_bytes(a.y, 4);
+  const RegTiles t(a.x, c.family == ConvFamily::Reg3x3_64 ? 16 : 32);
+  const dim3 grid(c.grid), blk(512);
+  if (c.family == ConvFamily::Reg3x3_64) rtd_launch(conv3x3_reg_split64_kernel, grid, blk, 0, s, k, x_bytes, y_bytes, t.tx, t.ty, (int)t.n);
+  else if (c.cog == 1) rtd_launch((conv3x3_reg_split_kernel<1>), grid, blk, 0, s, k, x_bytes, y_bytes, t.tx, t.ty, (int)t.n, PoolOut{});
+  else rtd_launch((conv3x3_reg_split_kernel<2>), grid, blk, 0, s, k, x_bytes, y_bytes, t.tx, t.ty, (int)t.n, PoolOut{});
+}
+
+// the chosen kernel and, behind a split-K first pass, the reduction that finishes the layer
+static void launch_choice(const ConvChoice& c, ConvK k, const ConvArgs& a, hipStream_t s) {
+  k.ntn = c.ntn;
+  const ConvK whole = k;
+  if (c.S > 1) k = splitk_partial(k, a.ws.slab);
+  switch (c.family) {
+    case ConvFamily::Tile:
+    case ConvFamily::Ws: if (a.x.dt == BF16) launch_plain<bf16>(c, k, a, s); else launch_plain<float>(c, k, a, s); break;
+    case ConvFamily::Sx: launch_sx(c, k, a, s); break;
+    case ConvFamily::Reg3x3:
+    case ConvFamily::Reg3x3_64: launch_reg3x3(c, k, a, s); break;
+    default: launch_pair_tile(c, make_convg(k, a, c.S), s); break;
+  }
+  HIP_CHECK(hipGetLastError());
+  if (c.S > 1) {
+    const long long items = (long long)whole.M * (whole.N >> 3);
+    rtd_launch(k_splitk_reduce, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, whole, (const float*)a.ws.slab, c.S);
+    HIP_CHECK(hipGetLastError());
+  }
+}
+
+// ---- predicates the plan builder asks before it relies on a fusion -------------------------------------------------------------------
 bool conv_split_supported(const ConvArgs& a) {
   const Tensor& x = a.x;
   const Tensor& y = a.y;
@@ -2182,205 +2422,49 @@ bool conv_split_supported(const ConvArgs& a) {
   }
   return a.next_y.p == nullptr || sx_shape_ok(a);
 }
-// Two-pass split-K (ConvOpts::split_k2) on long-K layers whose per-IMAGE tile count is small (stage 3, the 20^2 PAN level, enc.proj.2 at
-// 640 px; most layers at smaller inputs).  The slice count depends on per-image extents and K only: every batch size runs the same
-// arithmetic (the plan builder sizes the workspace from conv_split_slab_bytes() for its own batch).  Measured on R50 640^2 (stage-3 3x3,
-// K = 4608: 144 K-steps): batch 1 54 -> 35 us per layer (16 blocks -> 32), batch 8 57 -> 62 us; shorter K loops (stage-3 1x1, the 20^2 PAN
-// level) lose at batch 8 and gain nothing at batch 1, hence the 128-step floor.
-static int split_k2_slices(const ConvOpts& o, const ConvArgs& a, int OH, int OW) {
-  const bool dual = a.x2.p != nullptr;
-  if (!o.split_k2 || dual || a.x_up2 || a.y.c % 8 || a.next_y.p) return 1;
-  if (sx_shape_ok(a)) return 1;
-  const long long tiles_img = (((long long)OH * OW + 127) / 128) * ((a.y.c + 127) / 128);
-  const int groups = a.x.c / SPLIT_GROUP, nk_total = a.KH * a.KW * groups;
-  if (nk_total >= 128 && tiles_img <= 8 && groups % 4 == 0) return 4;
-  if (nk_total >= 128 && tiles_img <= 16 && groups % 2 == 0) return 2;
-  return 1;
+// The second input exists in the wave-specialised LDS-DMA kernel (glds_takes(), plus a K-step-aligned split point and whole K-steps of
+// x2) and in every pair kernel (for 64 + 64 channels also the streaming kernel): the split kernels take every grid size.
+bool conv_dual_supported(const ConvArgs& a) {
+  const Tensor& x = a.x;
+  const Tensor& x2 = a.x2;
+  if (!x2.p || x2.dt != x.dt) return false;
+  if (a.x_up2 && !(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0)) return false;
+  const ConvGeom g(a);
+  if (x2.n != x.n || x2.h != g.OH || x2.w != g.OW) return false;
+  if (x.dt == F16X2) return conv_split_supported(a) && span_bytes(x, 4) < DESC_LIMIT && span_bytes(x2, 4) < DESC_LIMIT;
+  const int es = (int)dtype_size(x.dt), bk = 128 / es, epc = 16 / es;
+  if ((a.KH * a.KW * x.c) % bk || x2.c % bk || x2.ld % epc || !aligned16(x2.p)) return false;
+  return glds_takes(opts_of(a), a, g, (long long)conv_npad(a.y.c) * conv_kpad(g.K) * es) && span_bytes(x2, es) < DESC_LIMIT;
 }
 size_t conv_split_slab_bytes(const ConvArgs& a) {
   if (a.x.dt != F16X2) return 0;
-  const int up = a.x_up2 ? 2 : 1;
-  const int OH = (a.x.h * up + 2 * a.pad - a.KH) / a.stride + 1, OW = (a.x.w * up + 2 * a.pad - a.KW) / a.stride + 1;
-  const int S = split_k2_slices(opts_of(a), a, OH, OW);
-  return S > 1 ? (size_t)S * (size_t)a.x.n * OH * OW * a.y.c * 4 : 0;
+  const ConvGeom g(a);
+  const int S = choose_pair(a, g, opts_of(a)).S;
+  return S > 1 ? (size_t)S * (size_t)g.M * a.y.c * 4 : 0;
 }
 
+// ---- launchers ------------------------------------------------------------------------------------------------------------------------
 static void launch_conv_split(const ConvArgs& a, hipStream_t s) {
   const ConvOpts& o = opts_of(a);
   const Tensor& x = a.x;
   const Tensor& y = a.y;
   RTD_CHECK(conv_split_supported(a), 1, "conv (f16x3): shape / layout not supported by the pair kernels (channels % 32, 16-byte alignment)");
-  const int up = a.x_up2 ? 2 : 1;
-  const int OH = (x.h * up + 2 * a.pad - a.KH) / a.stride + 1;
-  const int OW = (x.w * up + 2 * a.pad - a.KW) / a.stride + 1;
-  RTD_CHECK(OH == y.h && OW == y.w && x.n == y.n, 1, "conv: output shape mismatch");
-  const bool dual = a.x2.p != nullptr;
-  if (dual) RTD_CHECK(a.x2.n == x.n && a.x2.h == OH && a.x2.w == OW, 1, "conv: second input shape");
-  const int K = a.KH * a.KW * x.c + (dual ? a.x2.c : 0);
-  RTD_CHECK(a.Kpad == conv_kpad_split(K) && a.Npad >= y.c && a.Npad % 128 == 0, 1, "conv: pair filter padding");
-  RTD_CHECK((long long)x.n * OH * OW < (1ll << 31), 1, "conv: M overflow");
-  ConvG g;
-  ConvK& k = g.k;
-  k.x = x.p; k.w = a.w; k.bias = a.bias; k.y = y.p;
-  k.res = a.res_mode != RES_NONE ? a.res.p : nullptr;
-  k.M = x.n * OH * OW; k.H = x.h * up; k.W = x.w * up;
-  k.Cin = 2 * x.c; k.ldx = 2 * x.ld; k.x_bstride = 2 * x.bstride;                    // 16-bit elements
-  k.x_up2 = a.x_up2;
-  k.next_w = a.next_w; k.next_bias = a.next_bias; k.next_y = a.next_y.p; k.next_ldy = a.next_y.ld; k.next_y_bstride = a.next_y.bstride;   // channels
-  k.next_kpad = a.next_kpad; k.next_act = a.next_act;
-  k.OH = OH; k.OW = OW; k.OHW = OH * OW;
-  k.N = y.c; k.Kreal = 2 * K; k.Kpad = a.Kpad;
-  k.KH = a.KH; k.KW = a.KW; k.stride = a.stride; k.pad = a.pad;
-  k.ldy = y.ld; k.y_bstride = y.bstride;                                            // channels (fp32 or F16X2 alike)
-  k.ldr = 0; k.r_bstride = 0; k.res_f32 = 0;
-  if (a.res_mode != RES_NONE) {
-    RTD_CHECK(a.res.n == y.n && a.res.h == y.h && a.res.w == y.w && a.res.c == y.c, 1, "conv: residual shape");
-    k.ldr = a.res.ld; k.r_bstride = a.res.bstride; k.res_f32 = a.res.dt == F32;
-  }
-  k.act = a.act; k.res_mode = a.res_mode; k.y_f32 = y.dt == F32;
-  k.split = 1; k.y_split = y.dt == F16X2; k.res_split = a.res_mode != RES_NONE && a.res.dt == F16X2;
-  k.x2 = nullptr; k.ldx2 = 0; k.x2_bstride = 0; k.k2_start = 0;
-  long long x2_bytes = 0;
-  if (dual) {
-    k.x2 = a.x2.p; k.ldx2 = 2 * a.x2.ld; k.x2_bstride = 2 * a.x2.bstride; k.k2_start = 2 * a.KH * a.KW * x.c;
-    x2_bytes = ((long long)(a.x2.n - 1) * a.x2.bstride + ((long long)a.x2.h * a.x2.w - 1) * a.x2.ld + a.x2.c) * 4;
-  }
-  k.reg_epi = 1;
-  k.prefer256 = 0;
-  k.pf = o.prefetch ? a.pf : nullptr;
-  k.pf_bytes = (o.prefetch && a.pf && a.pf_bytes < (1ull << 31)) ? (unsigned)a.pf_bytes : 0u;
-  const long long x_bytes = ((long long)(x.n - 1) * x.bstride + ((long long)x.h * x.w - 1) * x.ld + x.c) * 4;
-  const long long w_bytes = (long long)a.Npad * a.Kpad * 2;
+  const ConvGeom g(a);
+  RTD_CHECK(g.OH == y.h && g.OW == y.w && x.n == y.n, 1, "conv: output shape mismatch");
+  if (g.dual) RTD_CHECK(a.x2.n == x.n && a.x2.h == g.OH && a.x2.w == g.OW, 1, "conv: second input shape");
+  RTD_CHECK(a.Kpad == conv_kpad_split(g.K) && a.Npad >= y.c && a.Npad % 128 == 0, 1, "conv: pair filter padding");
+  RTD_CHECK(g.M < (1ll << 31), 1, "conv: M overflow");
+  if (a.res_mode != RES_NONE) RTD_CHECK(a.res.n == y.n && a.res.h == y.h && a.res.w == y.w && a.res.c == y.c, 1, "conv: residual shape");
+  const long long x_bytes = span_bytes(x, 4), x2_bytes = g.dual ? span_bytes(a.x2, 4) : 0, w_bytes = (long long)a.Npad * a.Kpad * 2;
   RTD_CHECK(x_bytes < (1ll << 31) && x2_bytes < (1ll << 31) && w_bytes < (1ll << 31), 1, "conv (f16x3): operand larger than a buffer descriptor (2 GiB)");
-  g.splitk = 1; g.x_bytes = (unsigned)x_bytes; g.w_bytes = (unsigned)w_bytes; g.x2_bytes = (unsigned)x2_bytes;
-  // thin 1x1 expand convs on wide grids (stage-0 / stage-1 c3): the streaming kernel, with the next block's reduce conv riding on it
-  if (dispatch_sx(k, a, x_bytes, x2_bytes, s)) { HIP_CHECK(hipGetLastError()); return; }
-  RTD_CHECK(a.next_y.p == nullptr, 1, "conv (f16x3): a fused following conv exists in the streaming kernel only");
-  RTD_CHECK(a.avg_y.p == nullptr, 1, "conv (f16x3): the fused vd-shortcut average exists in the streaming kernel only (the plan must fall back to the avg-pool launch)");
-  // Direct 3x3 kernels for the narrow layers on wide maps.  Chosen on the per-IMAGE tile count: every batch size runs the same arithmetic
-  // (batch invariance is bit-exact).  32 input channels (stem.1, stem.2): every input pixel is staged once instead of nine times
-  if (o.conv_reg && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && !dual && a.res_mode == RES_NONE && x.c == 32 && (y.c == 32 || y.c == 64) &&
-      y.dt == F16X2) {
-    const long long y_bytes = ((long long)(y.n - 1) * y.bstride + ((long long)y.h * y.w - 1) * y.ld + y.c) * 4;
-    const int tiles_x = (x.w + 31) / 32, tiles_y = (x.h + 7) / 8;
-    const long long ntiles = (long long)x.n * tiles_x * tiles_y;
-    if (tiles_x * tiles_y >= 32 && ntiles < (1ll << 30) && y_bytes < (1ll << 31)) {
-      const unsigned gx = (unsigned)std::min<long long>(ntiles, 256);        // persistent, one block per CU
-      if (y.c == 32) rtd_launch((conv3x3_reg_split_kernel<1>), dim3(gx), dim3(512), 0, s, k, (unsigned)x_bytes, (unsigned)y_bytes, tiles_x, tiles_y, (int)ntiles, PoolOut{});
-      else rtd_launch((conv3x3_reg_split_kernel<2>), dim3(gx), dim3(512), 0, s, k, (unsigned)x_bytes, (unsigned)y_bytes, tiles_x, tiles_y, (int)ntiles, PoolOut{});
-      HIP_CHECK(hipGetLastError());
-      return;
-    }
+  const ConvChoice c = choose_pair(a, g, o);
+  if (c.family != ConvFamily::Sx) {
+    RTD_CHECK(a.next_y.p == nullptr, 1, "conv (f16x3): a fused following conv exists in the streaming kernel only");
+    RTD_CHECK(a.avg_y.p == nullptr, 1, "conv (f16x3): the fused vd-shortcut average exists in the streaming kernel only (the plan must fall back to the avg-pool launch)");
   }
-  // 64 -> 64 channels (stage-0 c2): direct kernel on 8 x 16 tiles
-  if ((o.conv_reg & 2) && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && !dual && a.res_mode == RES_NONE && x.c == 64 && y.c == 64 && y.dt == F16X2) {
-    const long long y_bytes = ((long long)(y.n - 1) * y.bstride + ((long long)y.h * y.w - 1) * y.ld + y.c) * 4;
-    const int tiles_x = (x.w + 15) / 16, tiles_y = (x.h + 7) / 8;
-    const long long ntiles = (long long)x.n * tiles_x * tiles_y;
-    if (tiles_x * tiles_y >= 128 && ntiles < (1ll << 30) && y_bytes < (1ll << 31)) {
-      const unsigned gx = (unsigned)std::min<long long>(ntiles, 256);        // persistent, one block per CU
-      rtd_launch(conv3x3_reg_split64_kernel, dim3(gx), dim3(512), 0, s, k, (unsigned)x_bytes, (unsigned)y_bytes, tiles_x, tiles_y, (int)ntiles);
-      HIP_CHECK(hipGetLastError());
-      return;
-    }
-  }
-  // ---- two-pass split-K: S slices of the channel groups, bare fp32 partial sums into the workspace slab, k_splitk_reduce finishes
-  const int S = split_k2_slices(o, a, OH, OW);
-  if (S > 1) RTD_CHECK(a.ws.slab && (size_t)S * (size_t)k.M * (size_t)k.N * 4 <= a.ws.slab_bytes, 1,
-                       "conv (f16x3): the launch needs a split-K workspace of conv_split_slab_bytes() bytes (ConvArgs::ws)");
-  const ConvK korig = k;
-  if (S > 1) {
-    k.raw = 1; k.act = ACT_NONE; k.res_mode = RES_NONE; k.res = nullptr; k.y = a.ws.slab; k.y_f32 = 1; k.y_split = 0; k.res_split = 0;
-    k.ldy = k.N; k.y_bstride = (long long)k.OHW * k.N; g.splitk = S;
-  }
-  auto finish = [&]() {
-    HIP_CHECK(hipGetLastError());
-    if (S > 1) {
-      const long long items = (long long)korig.M * (korig.N >> 3);
-      rtd_launch(k_splitk_reduce, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, korig, (const float*)a.ws.slab, S);
-      HIP_CHECK(hipGetLastError());
-    }
-  };
-  const long long mt = (k.M + 127) / 128, ntn = (k.N + 127) / 128, ntn64 = (k.N + 63) / 64;
-  // ---- flexible tile height (conv_igemm_wsf_kernel) on grids that leave CUs idle with 128-pixel tiles (20^2 maps at batch 8, most layers at
-  // batch 1: R50 bs-1 latency 2.49 -> 2.36 ms): the tile whose grid fills whole rounds of the chip
-  if (o.split_flex && k.Kpad / 64 / S >= o.split_flex_min_nk && k.N >= 64 && mt * ntn * S <= o.split_flex_small_max) {
-    int best_mt = 0, best_bn = 0, best_st = 0;
-    double best = 1e30;
-    for (int bn = (k.N > 64 ? 128 : 64); bn >= 64; bn -= 64) {
-      const long long ntb = (k.N + bn - 1) / bn;
-      for (int mtc = 4; mtc <= 13; ++mtc) {
-        const long long blocks = ((k.M + 16 * mtc - 1) / (16 * mtc)) * ntb * S;
-        const long long rounds = (blocks + 255) / 256;
-        const bool two = blocks > 256 && mtc <= 8;                 // 2 stages, two blocks per CU share the MFMA pipes; else 3 stages, one block per CU
-        double eff = (bn == 128 ? 1.0 : 0.78) * (1.0 - 0.6 / mtc);  // small tiles: more LDS reads and barriers per MFMA
-        if (!two && blocks > 256) eff *= 0.93;                     // nothing hides a lone block's barrier bubbles
-        const double cost = (double)rounds * mtc * bn / eff;
-        if (cost < best) { best = cost; best_mt = mtc; best_bn = bn; best_st = two ? 2 : 3; }
-      }
-    }
-    k.ntn = (int)((k.N + best_bn - 1) / best_bn);
-    const long long blocks = ((k.M + 16 * best_mt - 1) / (16 * best_mt)) * k.ntn * S;
-    const dim3 grid((unsigned)blocks), blk(512);
-    bool launched = true;
-#define RTD_WSF(ST, BNN, MTT) rtd_launch((conv_igemm_wsf_kernel<ST, BNN, MTT>), grid, blk, 0, s, g)
-#define RTD_WSF_MT(ST, BNN)                                                                                     \
-    switch (best_mt) {                                                                                         \
-      case 4: RTD_WSF(ST, BNN, 4); break; case 5: RTD_WSF(ST, BNN, 5); break; case 6: RTD_WSF(ST, BNN, 6); break;   \
-      case 7: RTD_WSF(ST, BNN, 7); break; case 8: RTD_WSF(ST, BNN, 8); break; default: launched = false; break; }
-    if (best_st == 2) {
-      if (best_bn == 128) { RTD_WSF_MT(2, 128) } else launched = false;
-    } else if (best_bn == 64) {
-      RTD_WSF_MT(3, 64)
-    } else {
-      switch (best_mt) {
-        case 4: RTD_WSF(3, 128, 4); break; case 5: RTD_WSF(3, 128, 5); break; case 6: RTD_WSF(3, 128, 6); break; case 7: RTD_WSF(3, 128, 7); break;
-        case 8: RTD_WSF(3, 128, 8); break; case 9: RTD_WSF(3, 128, 9); break; case 10: RTD_WSF(3, 128, 10); break; case 11: RTD_WSF(3, 128, 11); break;
-        case 12: RTD_WSF(3, 128, 12); break; case 13: RTD_WSF(3, 128, 13); break; default: launched = false; break;
-      }
-    }
-#undef RTD_WSF_MT
-#undef RTD_WSF
-    if (launched) { finish(); return; }
-    k.ntn = 1;
-  }
-  // ---- grids of more than one round: (MTA + MTB) x 16 pixel tiles, one block per CU (conv_igemm_wsq_kernel).  The tile height minimises
-  // rounds x (K loop of the taller wave half + epilogue), in MFMA-pipe cycles
-  if (o.split_wsq && S == 1 && k.N > 64 && k.Kpad / 64 >= o.split_wsq_min_nk && (o.split_wsq == 2 || mt * ntn >= o.split_wsq_min_blocks)) {
-    static const int cand[7][2] = {{5, 5}, {6, 5}, {6, 6}, {7, 6}, {7, 7}, {8, 7}, {8, 8}};
-    const long long nk = k.Kpad / 64;
-    int best = -1;
-    double best_cost = 1e30;
-    for (int c = 0; c < 7; ++c) {
-      const int bm = 16 * (cand[c][0] + cand[c][1]);
-      const long long blocks = ((k.M + bm - 1) / bm) * ntn;
-      const double cost = (double)((blocks + 255) / 256) * ((double)nk * cand[c][0] * 192.0 + 1500.0 + 10.0 * bm);
-      if (cost < best_cost) { best_cost = cost; best = c; }
-    }
-    const int bm = 16 * (cand[best][0] + cand[best][1]);
-    k.ntn = (int)ntn;
-    const dim3 grid((unsigned)(((k.M + bm - 1) / bm) * ntn)), blk(512);
-    switch (best) {
-      case 0: rtd_launch((conv_igemm_wsq_kernel<5, 5>), grid, blk, 0, s, g); break;
-      case 1: rtd_launch((conv_igemm_wsq_kernel<6, 5>), grid, blk, 0, s, g); break;
-      case 2: rtd_launch((conv_igemm_wsq_kernel<6, 6>), grid, blk, 0, s, g); break;
-      case 3: rtd_launch((conv_igemm_wsq_kernel<7, 6>), grid, blk, 0, s, g); break;
-      case 4: rtd_launch((conv_igemm_wsq_kernel<7, 7>), grid, blk, 0, s, g); break;
-      case 5: rtd_launch((conv_igemm_wsq_kernel<8, 7>), grid, blk, 0, s, g); break;
-      default: rtd_launch((conv_igemm_wsq_kernel<8, 8>), grid, blk, 0, s, g); break;
-    }
-    finish();
-    return;
-  }
-  // ---- fixed 128 x 128 / 128 x 64 tiles (conv_igemm_wsx_kernel): 4 stages at one block per CU below split_ws2_min_blocks blocks, 2 stages from there
-  const bool n64 = k.N <= 64 || (mt * ntn < o.split_ws64_max_blocks && ntn64 > ntn);
-  k.ntn = (int)(n64 ? ntn64 : ntn);
-  const long long blocks = mt * k.ntn * S;
-  const bool four = blocks < o.split_ws2_min_blocks;
-  const dim3 grid((unsigned)blocks), blk(512);
-  if (n64) { if (four) rtd_launch((conv_igemm_wsx_kernel<4, 64>), grid, blk, 0, s, g); else rtd_launch((conv_igemm_wsx_kernel<2, 64>), grid, blk, 0, s, g); }
-  else { if (four) rtd_launch((conv_igemm_wsx_kernel<4, 128>), grid, blk, 0, s, g); else rtd_launch((conv_igemm_wsx_kernel<2, 128>), grid, blk, 0, s, g); }
-  finish();
+  if (c.S > 1) RTD_CHECK(a.ws.slab && (size_t)c.S * (size_t)g.M * (size_t)y.c * 4 <= a.ws.slab_bytes, 1,
+                         "conv (f16x3): the launch needs a split-K workspace of conv_split_slab_bytes() bytes (ConvArgs::ws)");
+  launch_choice(c, make_convk(a, g, o), a, s);
 }
 
 // ---- stem.2 -> max-pool in one pass (conv3x3_reg_split_kernel<2, true> + k_pool_fixup) ----------------------------------------------
@@ -2394,41 +2478,27 @@ bool conv_pool_supported(const ConvArgs& a, const Tensor& pooled) {
   if (x.c != 32 || y.c != 64 || pooled.c != 64 || x.ld % SPLIT_GROUP || pooled.ld % SPLIT_GROUP) return false;
   if (y.h != x.h || y.w != x.w || (y.h & 1) || (y.w & 1) || pooled.h != y.h / 2 || pooled.w != y.w / 2 || pooled.n != x.n) return false;
   if (((uintptr_t)x.p & 15) || ((uintptr_t)pooled.p & 15) || ((uintptr_t)a.w & 15)) return false;
-  const int tiles_x = (x.w + 31) / 32, tiles_y = (x.h + 7) / 8;
-  return tiles_x * tiles_y >= 32 && opts_of(a).conv_reg != 0;
+  const RegTiles t(x, 32);
+  return t.tx * t.ty >= 32 && opts_of(a).conv_reg != 0;
 }
-size_t conv_pool_side_bytes(const ConvArgs& a) {
-  const long long ntiles = (long long)a.x.n * ((a.x.w + 31) / 32) * ((a.x.h + 7) / 8);
-  return (size_t)ntiles * (8192 + 1024) + 256;
-}
+size_t conv_pool_side_bytes(const ConvArgs& a) { return (size_t)RegTiles(a.x, 32).n * (8192 + 1024) + 256; }
 void launch_conv_pool(const ConvArgs& a, const Tensor& pooled, void* side, hipStream_t s) {
   RTD_CHECK(conv_pool_supported(a, pooled) && side, 1, "conv + max-pool: shape not supported");
-  const Tensor& x = a.x;
-  ConvK k;
-  k.x = x.p; k.w = a.w; k.bias = a.bias; k.y = nullptr; k.res = nullptr;
-  k.H = x.h; k.W = x.w; k.M = x.n * x.h * x.w;
-  k.Cin = 2 * x.c; k.ldx = 2 * x.ld; k.x_bstride = 2 * x.bstride;
-  k.OH = x.h; k.OW = x.w; k.OHW = x.h * x.w;
-  k.N = 64; k.Kreal = 2 * 9 * x.c; k.Kpad = a.Kpad;
-  k.KH = 3; k.KW = 3; k.stride = 1; k.pad = 1;
-  k.ldy = 0; k.y_bstride = 0; k.ldr = 0; k.r_bstride = 0; k.res_f32 = 0;
-  k.act = a.act; k.res_mode = RES_NONE; k.y_f32 = 0; k.split = 1; k.y_split = 1; k.res_split = 0;
-  k.x2 = nullptr; k.ldx2 = 0; k.x2_bstride = 0; k.k2_start = 0; k.ntn = 1; k.reg_epi = 1; k.prefer256 = 0; k.pf = nullptr; k.pf_bytes = 0; k.x_up2 = 0;
-  k.next_w = nullptr; k.next_bias = nullptr; k.next_y = nullptr; k.next_ldy = 0; k.next_y_bstride = 0; k.next_kpad = 0; k.next_act = 0;
-  const long long x_bytes = ((long long)(x.n - 1) * x.bstride + ((long long)x.h * x.w - 1) * x.ld + x.c) * 4;
-  const long long p_bytes = ((long long)(pooled.n - 1) * pooled.bstride + ((long long)pooled.h * pooled.w - 1) * pooled.ld + pooled.c) * 4;
-  const int tiles_x = (x.w + 31) / 32, tiles_y = (x.h + 7) / 8;
-  const long long ntiles = (long long)x.n * tiles_x * tiles_y;
+  ConvK k = make_convk(a, ConvGeom(a), opts_of(a));
+  k.y = nullptr; k.N = 64; k.pf = nullptr; k.pf_bytes = 0;       // the conv rows are never written; the launch carries no prefetch
+  const long long x_bytes = span_bytes(a.x, 4), p_bytes = span_bytes(pooled, 4);
+  const RegTiles t(a.x, 32);
+  const long long ntiles = t.n;   // over the batch
   RTD_CHECK(x_bytes < (1ll << 31) && p_bytes < (1ll << 31) && ntiles * 8192 < (1ll << 31), 1, "conv + max-pool: operand larger than a buffer descriptor");
   PoolOut po;
   po.y = (sp16*)pooled.p; po.ldy = pooled.ld; po.bstride = pooled.bstride; po.OH = pooled.h; po.OW = pooled.w; po.y_bytes = (unsigned)p_bytes;
   po.side_row = (sp16*)side; po.row_bytes = (unsigned)(ntiles * 8192);
   po.side_col = (sp16*)((char*)side + ntiles * 8192); po.col_bytes = (unsigned)(ntiles * 1024);
   const unsigned gx = (unsigned)std::min<long long>(ntiles, 256);
-  rtd_launch((conv3x3_reg_split_kernel<2, true>), dim3(gx), dim3(512), 0, s, k, (unsigned)x_bytes, 0u, tiles_x, tiles_y, (int)ntiles, po);
+  rtd_launch((conv3x3_reg_split_kernel<2, true>), dim3(gx), dim3(512), 0, s, k, (unsigned)x_bytes, 0u, t.tx, t.ty, (int)ntiles, po);
   HIP_CHECK(hipGetLastError());
   const long long items = ntiles * 19 * (64 / 8);
-  rtd_launch(k_pool_fixup, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, po, tiles_x, tiles_y, (int)ntiles, 64);
+  rtd_launch(k_pool_fixup, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, po, t.tx, t.ty, (int)ntiles, 64);
   HIP_CHECK(hipGetLastError());
 }
 
@@ -2442,77 +2512,25 @@ void launch_conv(const ConvArgs& a, hipStream_t s) {
   if (y.dt == F16X2) RTD_CHECK(y.c % SPLIT_GROUP == 0 && y.ld % SPLIT_GROUP == 0 && a.res_mode == RES_NONE && !a.x2.p && !a.next_y.p && ((uintptr_t)y.p & 15) == 0, 1,
                                 "conv: fp32 -> F16X2 output needs 32-channel groups and no residual / second input");
   const int epc = x.dt == BF16 ? 8 : 4;
-  const int up = a.x_up2 ? 2 : 1;
   if (a.x_up2) RTD_CHECK(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.pad == 0 && a.x2.p, 1, "conv: x_up2 needs a 1x1 conv with a second input");
-  const int OH = (x.h * up + 2 * a.pad - a.KH) / a.stride + 1;
-  const int OW = (x.w * up + 2 * a.pad - a.KW) / a.stride + 1;
-  RTD_CHECK(OH == y.h && OW == y.w && x.n == y.n, 1, "conv: output shape mismatch");
+  const ConvGeom g(a);
+  RTD_CHECK(g.OH == y.h && g.OW == y.w && x.n == y.n, 1, "conv: output shape mismatch");
   RTD_CHECK(x.c % epc == 0 && x.ld % epc == 0, 1, "conv: Cin / pixel stride must be a multiple of one 16-byte chunk");
   RTD_CHECK(((uintptr_t)x.p & 15) == 0 && ((uintptr_t)a.w & 15) == 0, 1, "conv: 16-byte alignment");
   RTD_CHECK(y.c % 4 == 0 && y.ld % 4 == 0, 1, "conv: Cout / output stride must be multiples of 4");
   RTD_CHECK(((uintptr_t)y.p & (y.dt == BF16 ? 7 : 15)) == 0, 1, "conv: output alignment");
-  const bool dual = a.x2.p != nullptr;
-  const int K = a.KH * a.KW * x.c + (dual ? a.x2.c : 0);
-  if (dual) RTD_CHECK(conv_dual_supported(a), 1, "conv: second input not supported for this shape (see conv_dual_supported)");
-  RTD_CHECK(a.Kpad == conv_kpad(K) && a.Npad >= y.c && a.Npad % 128 == 0, 1, "conv: filter padding");
-  RTD_CHECK((long long)x.n * OH * OW < (1ll << 31), 1, "conv: M overflow");
-  ConvK k;
-  k.x = x.p; k.w = a.w; k.bias = a.bias; k.y = y.p;
-  k.res = a.res_mode != RES_NONE ? a.res.p : nullptr;
-  k.M = x.n * OH * OW; k.H = x.h * up; k.W = x.w * up; k.Cin = x.c;
-  k.x_up2 = a.x_up2;
-  k.next_w = a.next_w; k.next_bias = a.next_bias; k.next_y = a.next_y.p; k.next_ldy = a.next_y.ld; k.next_y_bstride = a.next_y.bstride;
-  k.next_kpad = a.next_kpad; k.next_act = a.next_act;
+  if (g.dual) RTD_CHECK(conv_dual_supported(a), 1, "conv: second input not supported for this shape (see conv_dual_supported)");
+  RTD_CHECK(a.Kpad == conv_kpad(g.K) && a.Npad >= y.c && a.Npad % 128 == 0, 1, "conv: filter padding");
+  RTD_CHECK(g.M < (1ll << 31), 1, "conv: M overflow");
   if (a.next_y.p) RTD_CHECK(a.next_y.n == y.n && a.next_y.h == y.h && a.next_y.w == y.w, 1, "conv: fused next conv output shape");
-  k.ldx = x.ld; k.x_bstride = x.bstride;
-  k.OH = OH; k.OW = OW; k.OHW = OH * OW;
-  k.N = y.c; k.Kreal = K; k.Kpad = a.Kpad;
-  k.KH = a.KH; k.KW = a.KW; k.stride = a.stride; k.pad = a.pad;
-  k.ldy = y.ld; k.y_bstride = y.bstride;
-  k.ldr = 0; k.r_bstride = 0; k.res_f32 = 0;
   if (a.res_mode != RES_NONE) {
     RTD_CHECK(a.res.p && a.res.n == y.n && a.res.h == y.h && a.res.w == y.w && a.res.c == y.c, 1, "conv: residual shape");
     RTD_CHECK(a.res.ld % 4 == 0 && ((uintptr_t)a.res.p & (a.res.dt == BF16 ? 7 : 15)) == 0, 1, "conv: residual alignment");
-    k.ldr = a.res.ld; k.r_bstride = a.res.bstride; k.res_f32 = a.res.dt == F32;
   }
-  k.act = a.act; k.res_mode = a.res_mode; k.y_f32 = y.dt == F32;
-  k.y_split = y.dt == F16X2;
-  k.x2 = nullptr; k.ldx2 = 0; k.x2_bstride = 0; k.k2_start = 0;
-  long long x2_bytes = 0;
-  if (dual) {
-    k.x2 = a.x2.p; k.ldx2 = a.x2.ld; k.x2_bstride = a.x2.bstride; k.k2_start = a.KH * a.KW * x.c;
-    x2_bytes = ((long long)(a.x2.n - 1) * a.x2.bstride + ((long long)a.x2.h * a.x2.w - 1) * a.x2.ld + a.x2.c) * (long long)dtype_size(x.dt);
-  }
-  k.ntn = 1;
-  k.reg_epi = o.reg_epilogue;
-  k.prefer256 = a.prefer256;
-  k.pf = o.prefetch ? a.pf : nullptr;
-  k.pf_bytes = (o.prefetch && a.pf && a.pf_bytes < (1ull << 31)) ? (unsigned)a.pf_bytes : 0u;
-  const bool smallc = (x.c % 32) != 0;
-  const int bk2 = x.dt == BF16 ? 64 : 32;
-  bool tile_ok = (x.c % bk2 == 0) && (y.c % 8 == 0) && (y.ld % 8 == 0) && (((uintptr_t)y.p & 15) == 0);
-  if (a.res_mode != RES_NONE) tile_ok = tile_ok && (a.res.ld % 8 == 0) && (((uintptr_t)a.res.p & 15) == 0);
-  bool done = false;
-  if (k.y_split) {                        // fp32 input, F16X2 output (the split engine's stem.0): the register-staged kernel's epilogue writes it
-    dispatch<float>(k, smallc, s);
-    HIP_CHECK(hipGetLastError());
-    return;
-  }
-  {
-    const long long es = (long long)dtype_size(x.dt);
-    const long long x_bytes = ((long long)(x.n - 1) * x.bstride + ((long long)x.h * x.w - 1) * x.ld + x.c) * es;
-    const long long w_bytes = (long long)a.Npad * a.Kpad * es;
-    RTD_CHECK(!a.next_y.p, 1, "conv: a fused following conv exists on F16X2 operands only (see conv_next_supported)");
-    if (x.dt == BF16) done = dispatch_glds<bf16>(o, k, tile_ok, a.prefer256 != 0, x_bytes, w_bytes, (unsigned)x2_bytes, s);
-    else done = dispatch_glds<float>(o, k, tile_ok, a.prefer256 != 0, x_bytes, w_bytes, (unsigned)x2_bytes, s);
-  }
-  RTD_CHECK(done || !dual, 1, "conv: no kernel took the dual-input launch");
-  RTD_CHECK(done || !a.next_y.p, 1, "conv: no kernel took the launch with a fused following conv (see conv_next_supported)");
-  if (!done) {
-    if (x.dt == BF16) dispatch<bf16>(k, smallc, s);
-    else dispatch<float>(k, smallc, s);
-  }
-  HIP_CHECK(hipGetLastError());
+  RTD_CHECK(!a.next_y.p, 1, "conv: a fused following conv exists on F16X2 operands only (see conv_next_supported)");
+  const ConvChoice c = choose_plain(a, g, o, (long long)a.Npad * a.Kpad * (long long)dtype_size(x.dt));
+  RTD_CHECK(c.family == ConvFamily::Ws || !g.dual, 1, "conv: no kernel took the dual-input launch");
+  launch_choice(c, make_convk(a, g, o), a, s);
 }
 
 }  // namespace rtd
