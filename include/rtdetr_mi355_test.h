@@ -82,6 +82,9 @@ int rtd_op_attention(int dtype, const void* qk, const void* v, void* o, int B, i
 int rtd_op_msdeform(int dtype, const void* value, const float* offaw, const float* ref, float* out,
                     int B, int Q, int heads, int hd, int n_levels, int n_points, const int32_t* level_hw,
                     int value_ld, float offset_scale);
+/* the glue ops on an NHWC view x = [B, H, W, C] with pixel stride ldx (>= C: a channel slice), images dense: kind 0 = max-pool 3x3 / stride 2 /
+ * pad 1, 1 = 2x2 average (even H, W), 2 = nearest 2x upsample; dtype 0 bf16, 1 fp32, 4 F16X2; y = [B, OH, OW, C] with pixel stride ldy */
+int rtd_op_pool(int kind, int dtype, const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy);
 int rtd_op_topk(const float* keys, int B, int N, int K, int32_t* idx_out, float* val_out);
 int rtd_op_resize(const uint8_t* src, int sh, int sw, void* dst, int dh, int dw, int dtype);
 /* kernel micro-benchmark (tools/conv_bench.py): one conv layer on zero-filled buffers, timed with HIP events.

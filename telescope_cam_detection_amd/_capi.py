@@ -112,7 +112,7 @@ EXPORTS = [
 # every symbol include/rtdetr_mi355_test.h declares: kernel-level test / bench / debug entry points (csrc/testapi.hip)
 TEST_EXPORTS = [
     "rtd_debug_tensor", "rtd_debug_force_topk", "rtd_profile", "rtd_debug_option", "rtd_op_conv", "rtd_op_conv_dual", "rtd_op_conv_next",
-    "rtd_op_layernorm", "rtd_op_attention", "rtd_op_msdeform", "rtd_op_topk", "rtd_op_resize", "rtd_bench_conv", "rtd_bench_conv_pair",
+    "rtd_op_layernorm", "rtd_op_attention", "rtd_op_msdeform", "rtd_op_topk", "rtd_op_resize", "rtd_op_pool", "rtd_bench_conv", "rtd_bench_conv_pair",
     "rtd_bench_mfma_rate", "rtd_debug_motion_state", "rtd_debug_mog2_model", "rtd_debug_mog2_fg_bits",
     "rtd_debug_jpeg_coefficients",
 ]
@@ -182,6 +182,8 @@ def lib() -> C.CDLL:
     L.rtd_op_msdeform.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, i32, C.POINTER(i32), i32, f32]
     L.rtd_op_topk.argtypes = [vp, i32, i32, i32, vp, vp]
     L.rtd_op_resize.argtypes = [vp, i32, i32, vp, i32, i32, i32]
+    if hasattr(L, "rtd_op_pool"):              # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_op_pool.argtypes = [i32, i32, vp, vp] + [i32] * 6
     L.rtd_bench_conv.argtypes = [i32] * 12 + [C.POINTER(f32)]
     L.rtd_bench_conv_pair.argtypes = [C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(f32)]
     if hasattr(L, "rtd_bench_mfma_rate"):      # (absent from older builds loaded through RTD_LIB_PATH)

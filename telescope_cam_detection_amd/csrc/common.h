@@ -55,6 +55,10 @@ struct Tensor {
   }
 };
 
+// every pointer on a 16-byte boundary (what the kernels' 16-byte vector accesses and buffer loads need of a tensor's base)
+template <typename... P>
+inline bool aligned16(const P*... p) { return ((... | (uintptr_t)p) & 15) == 0; }
+
 struct Error : std::runtime_error {
   int code;
   Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}

@@ -1973,7 +1973,6 @@ static constexpr long long TILE_LIMIT = 1ll << 30;   // the persistent kernels c
 static long long span_bytes(const Tensor& t, long long elem_bytes) {
   return ((long long)(t.n - 1) * t.bstride + ((long long)t.h * t.w - 1) * t.ld + t.c) * elem_bytes;
 }
-static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 struct ConvGeom {
   int up;        // 2: x is read through a nearest 2x upsampling (ConvArgs::x_up2)

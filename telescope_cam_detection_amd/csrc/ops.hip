@@ -18,11 +18,73 @@ __device__ __forceinline__ float wave_sum(float v) { return wave_sum64(v); }
 
 static inline unsigned blocks_for(int64_t n, int per_block) { return (unsigned)((n + per_block - 1) / per_block); }
 
-#define DISPATCH_T(dt, ...)                     \
-  do {                                          \
-    if ((dt) == BF16) { typedef bf16 T; __VA_ARGS__; } \
-    else { typedef float T; __VA_ARGS__; }      \
-  } while (0)
+// the usual launch shape: one thread per item, 256-thread blocks, no LDS; the launch is checked here
+template <typename... KArgs, typename... Args>
+static void launch_1d(void (*kernel)(KArgs...), int64_t total, hipStream_t s, Args&&... args) {
+  rtd_launch(kernel, dim3(blocks_for(total, 256)), dim3(256), 0, s, std::forward<Args>(args)...);
+  HIP_CHECK(hipGetLastError());
+}
+
+// Dtype dispatch: with_dtype(dt, f) calls the generic lambda `f` with a tag of the element type, bf16 or float, and refuses every other
+// dtype (a U8, I32 or F16X2 tensor never runs as fp32 by accident).  Kernels over two or three tensor types nest it.
+template <typename T> struct TypeTag { typedef T type; };
+template <typename Tag> using type_of = typename Tag::type;
+template <typename F>
+static void with_dtype(int dt, F&& f) {
+  if (dt == BF16) f(TypeTag<bf16>{});
+  else if (dt == F32) f(TypeTag<float>{});
+  else RTD_CHECK(false, 1, "this op takes bf16 or fp32 tensors (dtype " + std::to_string(dt) + ")");
+}
+// ... for the ops that also take the trunk's pair tensors (the pools): element type sp16
+template <typename F>
+static void with_act_dtype(int dt, F&& f) {
+  if (dt == F16X2) f(TypeTag<sp16>{});
+  else with_dtype(dt, f);
+}
+
+static bool dense(const Tensor& t) { return t.bstride == (int64_t)t.h * t.w * t.ld; }   // images follow each other without a gap
+
+// One 16-byte chunk of a pixel's channels as fp32 and back: N channels per thread (bf16 8, fp32 4; a pair tensor's 8 channels are a
+// 16-byte hi chunk and a 16-byte lo chunk, common.h split_load8 / split_store8).  `pix_off` = pixel index * ld, `c` % N == 0.
+template <typename T>
+struct Chunk {
+  static constexpr int N = 16 / (int)sizeof(T);
+  typedef T V __attribute__((ext_vector_type(N)));
+  static __device__ __forceinline__ void load(const T* base, int64_t pix_off, int c, float (&v)[N]) {
+    const V t = *(const V*)(base + pix_off + c);
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = (float)t[k];
+  }
+  static __device__ __forceinline__ void store(T* base, int64_t pix_off, int c, const float (&v)[N]) {
+    V t;
+#pragma unroll
+    for (int k = 0; k < N; ++k) t[k] = (T)v[k];
+    *(V*)(base + pix_off + c) = t;
+  }
+};
+template <>
+struct Chunk<sp16> {
+  static constexpr int N = 8;
+  static __device__ __forceinline__ void load(const sp16* base, int64_t pix_off, int c, float (&v)[N]) { split_load8(base, pix_off, c, v); }
+  static __device__ __forceinline__ void store(sp16* base, int64_t pix_off, int c, const float (&v)[N]) { split_store8(base, pix_off, c, v); }
+};
+// what Chunk<T> needs of a view: whole chunks (pair tensors: whole 32-channel groups) per pixel, in 16-byte aligned rows
+static bool chunk_rows(const Tensor& t) {
+  const int g = t.dt == F16X2 ? SPLIT_GROUP : (t.dt == BF16 ? 8 : 4);
+  return t.c % g == 0 && t.ld % g == 0 && aligned16(t.p);
+}
+
+// flat thread index -> (image, row, column, first channel) of an NHWC extent [.][H][W][chunks * per_chunk]
+struct Nhwc { int b, y, x, c; };
+__device__ __forceinline__ Nhwc nhwc_of(int64_t i, int H, int W, int chunks, int per_chunk) {
+  Nhwc r;
+  r.c = (int)(i % chunks) * per_chunk;
+  int64_t p = i / chunks;
+  r.x = (int)(p % W); p /= W;
+  r.y = (int)(p % H);
+  r.b = (int)(p / H);
+  return r;
+}
 
 // ------------------------------------------------------------------------------------------ dtype conversion
 template <typename T>
@@ -37,13 +99,11 @@ __global__ void k_to_f32(const T* __restrict__ src, float* __restrict__ dst, int
 }
 void launch_f32_to(const float* src, void* dst, int dt, int64_t n, hipStream_t s) {
   if (n == 0) return;
-  DISPATCH_T(dt, rtd_launch(k_f32_to<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, src, (T*)dst, n));
-  HIP_CHECK(hipGetLastError());
+  with_dtype(dt, [&](auto t) { typedef type_of<decltype(t)> T; launch_1d(k_f32_to<T>, n, s, src, (T*)dst, n); });
 }
 void launch_to_f32(const void* src, int dt, float* dst, int64_t n, hipStream_t s) {
   if (n == 0) return;
-  DISPATCH_T(dt, rtd_launch(k_to_f32<T>, dim3(blocks_for(n, 256)), dim3(256), 0, s, (const T*)src, dst, n));
-  HIP_CHECK(hipGetLastError());
+  with_dtype(dt, [&](auto t) { typedef type_of<decltype(t)> T; launch_1d(k_to_f32<T>, n, s, (const T*)src, dst, n); });
 }
 
 // fp32 rows <-> F16X2 rows (common.h: groups of 32 channels, [32 hi | 32 lo]); a thread moves 8 channels
@@ -70,15 +130,13 @@ __global__ void k_split_to_f32(const sp16* __restrict__ src, int64_t lds_, float
 }
 void launch_f32_to_split(const float* src, int64_t lds_, void* dst, int64_t ldd, int64_t rows, int C, hipStream_t s) {
   if (rows == 0) return;
-  RTD_CHECK(C % SPLIT_GROUP == 0 && lds_ % 4 == 0 && ldd % SPLIT_GROUP == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0, 1, "f32 -> split: 32-channel groups, 16-byte rows");
-  rtd_launch(k_f32_to_split, dim3(blocks_for(rows * (C / 8), 256)), dim3(256), 0, s, src, lds_, (sp16*)dst, ldd, rows, C);
-  HIP_CHECK(hipGetLastError());
+  RTD_CHECK(C % SPLIT_GROUP == 0 && lds_ % 4 == 0 && ldd % SPLIT_GROUP == 0 && aligned16(src, dst), 1, "f32 -> split: 32-channel groups, 16-byte rows");
+  launch_1d(k_f32_to_split, rows * (C / 8), s, src, lds_, (sp16*)dst, ldd, rows, C);
 }
 void launch_split_to_f32(const void* src, int64_t lds_, float* dst, int64_t ldd, int64_t rows, int C, hipStream_t s) {
   if (rows == 0) return;
-  RTD_CHECK(C % SPLIT_GROUP == 0 && lds_ % SPLIT_GROUP == 0 && ldd % 4 == 0 && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0, 1, "split -> f32: 32-channel groups, 16-byte rows");
-  rtd_launch(k_split_to_f32, dim3(blocks_for(rows * (C / 8), 256)), dim3(256), 0, s, (const sp16*)src, lds_, dst, ldd, rows, C);
-  HIP_CHECK(hipGetLastError());
+  RTD_CHECK(C % SPLIT_GROUP == 0 && lds_ % SPLIT_GROUP == 0 && ldd % 4 == 0 && aligned16(src, dst), 1, "split -> f32: 32-channel groups, 16-byte rows");
+  launch_1d(k_split_to_f32, rows * (C / 8), s, (const sp16*)src, lds_, dst, ldd, rows, C);
 }
 
 // Real-weights guard (rtd_self_check): how many hi halves of an F16X2 buffer sit at the format's saturation value +-65504 (0x7BFF: split2
@@ -143,25 +201,14 @@ void launch_layernorm(const Tensor& x, const Tensor* res, const float* g, const 
                       hipStream_t s) {
   const int rows = (int)x.pixels(), dim = x.c;
   RTD_CHECK(dim <= 1024 && y.c == dim && y.pixels() == rows, 1, "layernorm: shape");
-  RTD_CHECK(x.bstride == (int64_t)x.h * x.w * x.ld && y.bstride == (int64_t)y.h * y.w * y.ld, 1, "layernorm: dense rows");
-  if (res) RTD_CHECK(res->c == dim && res->pixels() == rows && res->bstride == (int64_t)res->h * res->w * res->ld, 1, "layernorm: residual");
+  RTD_CHECK(dense(x) && dense(y), 1, "layernorm: dense rows");
+  if (res) RTD_CHECK(res->c == dim && res->pixels() == rows && dense(*res), 1, "layernorm: residual");
   const dim3 grid((rows + 3) / 4), blk(256);
-#define LN_GO(TX, TR, TY)                                                                                   \
-  rtd_launch((k_layernorm<TX, TR, TY>), grid, blk, 0, s, (const TX*)x.p, x.ld,                       \
-                     (const TR*)(res ? res->p : nullptr), res ? res->ld : 0, g, b, (TY*)y.p, y.ld, rows, dim, eps)
-  const int rdt = res ? res->dt : x.dt;
-  const int key = (x.dt == F32) * 4 + (rdt == F32) * 2 + (y.dt == F32);
-  switch (key) {
-    case 0: LN_GO(bf16, bf16, bf16); break;
-    case 1: LN_GO(bf16, bf16, float); break;
-    case 2: LN_GO(bf16, float, bf16); break;
-    case 3: LN_GO(bf16, float, float); break;
-    case 4: LN_GO(float, bf16, bf16); break;
-    case 5: LN_GO(float, bf16, float); break;
-    case 6: LN_GO(float, float, bf16); break;
-    default: LN_GO(float, float, float); break;
-  }
-#undef LN_GO
+  with_dtype(x.dt, [&](auto tx) { with_dtype(res ? res->dt : x.dt, [&](auto tr) { with_dtype(y.dt, [&](auto ty) {
+    typedef type_of<decltype(tx)> TX; typedef type_of<decltype(tr)> TR; typedef type_of<decltype(ty)> TY;
+    rtd_launch((k_layernorm<TX, TR, TY>), grid, blk, 0, s, (const TX*)x.p, x.ld, (const TR*)(res ? res->p : nullptr), res ? res->ld : 0, g, b,
+               (TY*)y.p, y.ld, rows, dim, eps);
+  }); }); });
   HIP_CHECK(hipGetLastError());
 }
 
@@ -179,305 +226,137 @@ void launch_add(const Tensor& a, const Tensor& b, const Tensor& y, hipStream_t s
   RTD_CHECK(a.ld == a.c && b.ld == b.c && y.ld == y.c && a.c == b.c && a.c == y.c, 1, "add: dense tensors");
   const int64_t per = (int64_t)a.h * a.w * a.c, total = per * a.n;
   RTD_CHECK((b.n == 1 || b.n == a.n) && (int64_t)b.h * b.w * b.c == per && y.pixels() == a.pixels(), 1, "add: shape");
-  const dim3 grid(blocks_for(total, 256)), blk(256);
   const int bb = (b.n == 1 && a.n != 1);
-#define ADD_GO(TA, TB, TY) rtd_launch((k_add<TA, TB, TY>), grid, blk, 0, s, (const TA*)a.p, (const TB*)b.p, (TY*)y.p, per, total, bb)
-  const int key = (a.dt == F32) * 4 + (b.dt == F32) * 2 + (y.dt == F32);
-  switch (key) {
-    case 0: ADD_GO(bf16, bf16, bf16); break;
-    case 1: ADD_GO(bf16, bf16, float); break;
-    case 2: ADD_GO(bf16, float, bf16); break;
-    case 3: ADD_GO(bf16, float, float); break;
-    case 4: ADD_GO(float, bf16, bf16); break;
-    case 5: ADD_GO(float, bf16, float); break;
-    case 6: ADD_GO(float, float, bf16); break;
-    default: ADD_GO(float, float, float); break;
-  }
-#undef ADD_GO
-  HIP_CHECK(hipGetLastError());
+  with_dtype(a.dt, [&](auto ta) { with_dtype(b.dt, [&](auto tb) { with_dtype(y.dt, [&](auto ty) {
+    typedef type_of<decltype(ta)> TA; typedef type_of<decltype(tb)> TB; typedef type_of<decltype(ty)> TY;
+    launch_1d(k_add<TA, TB, TY>, total, s, (const TA*)a.p, (const TB*)b.p, (TY*)y.p, per, total, bb);
+  }); }); });
 }
 
 // ------------------------------------------------------------------------------------------ max-pool 3x3 s2 p1
-// HF:rt_detr_resnet.py:103 nn.MaxPool2d(3, 2, 1); padding counts as -inf.  4 channels per thread.
-template <typename T>
-__global__ void k_maxpool(const T* __restrict__ x, T* __restrict__ y, int B, int H, int W, int C, int64_t ldx, int OH,
-                          int OW, int64_t ldy) {
+// HF:rt_detr_resnet.py:103 nn.MaxPool2d(3, 2, 1); padding counts as -inf.  A thread owns one Chunk<T> of channels of a PATCH x PATCH
+// output patch and reads the patch's (2 PATCH + 1)^2 input window once.
+// PATCH = 2 (bf16 and pair tensors, even output extents): 25 chunk loads for 4 outputs instead of 36; the taps a patch shares between
+// its outputs never leave registers, and the lanes of 8 consecutive threads cover one bf16 pixel's 128-byte line.
+// PATCH = 1 (fp32): one output per thread.
+// Pair tensors: hi + lo is exact in fp32, so the max is the max of the represented values and re-splitting it reproduces the winning
+// tap's (hi, lo) pair bit for bit.
+template <typename T, int PATCH>
+__global__ __launch_bounds__(256) void k_maxpool(const T* __restrict__ x, T* __restrict__ y, int B, int H, int W, int C, int64_t ldx, int OH, int OW,
+                                                 int64_t ldy) {
+  constexpr int N = Chunk<T>::N, WIN = 2 * PATCH + 1;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int c4 = C / 4;
-  const int64_t total = (int64_t)B * OH * OW * c4;
-  if (i >= total) return;
-  const int cc = (int)(i % c4) * 4;
-  int64_t p = i / c4;
-  const int ox = (int)(p % OW); p /= OW;
-  const int oy = (int)(p % OH);
-  const int b = (int)(p / OH);
-  float m[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-  for (int dy = 0; dy < 3; ++dy) {
-    const int iy = oy * 2 - 1 + dy;
-    if ((unsigned)iy >= (unsigned)H) continue;
-    for (int dx = 0; dx < 3; ++dx) {
-      const int ix = ox * 2 - 1 + dx;
-      if ((unsigned)ix >= (unsigned)W) continue;
-      const T* q = x + (((int64_t)b * H + iy) * W + ix) * ldx + cc;
+  const int cn = C / N, PW = OW / PATCH, PH = OH / PATCH;
+  if (i >= (int64_t)B * PH * PW * cn) return;
+  const Nhwc p = nhwc_of(i, PH, PW, cn, N);                       // (p.y, p.x): the patch
+  const int iy0 = 2 * PATCH * p.y - 1, ix0 = 2 * PATCH * p.x - 1;   // window rows iy0 .. iy0 + 2 PATCH, cols ix0 .. ix0 + 2 PATCH
+  float m[PATCH * PATCH][N];
 #pragma unroll
-      for (int k = 0; k < 4; ++k) m[k] = fmaxf(m[k], (float)q[k]);
-    }
-  }
-  T* o = y + (((int64_t)b * OH + oy) * OW + ox) * ldy + cc;
+  for (int o = 0; o < PATCH * PATCH; ++o)
 #pragma unroll
-  for (int k = 0; k < 4; ++k) o[k] = (T)m[k];
-}
-// bf16, C % 8 == 0, even output extents: a thread owns 8 channels of a 2 x 2 output patch and reads its 5 x 5 input window
-// once (25 x 16 bytes for 4 outputs instead of 36 x 8; the taps a patch shares between its outputs never leave registers,
-// and the lanes of 8 consecutive threads cover one pixel's 128-byte line)
-__global__ __launch_bounds__(256) void k_maxpool_bf16_2x2(const bf16* __restrict__ x, bf16* __restrict__ y, int B, int H, int W, int C, int64_t ldx,
-                                                          int OH, int OW, int64_t ldy) {
-  typedef __bf16 v8 __attribute__((ext_vector_type(8)));
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int c8 = C / 8, PW = OW / 2, PH = OH / 2;
-  const int64_t total = (int64_t)B * PH * PW * c8;
-  if (i >= total) return;
-  const int cc = (int)(i % c8) * 8;
-  int64_t p = i / c8;
-  const int px = (int)(p % PW); p /= PW;
-  const int py = (int)(p % PH);
-  const int b = (int)(p / PH);
-  const int iy0 = 4 * py - 1, ix0 = 4 * px - 1;                  // window rows iy0 .. iy0+4, cols ix0 .. ix0+4
-  float m[4][8];
+    for (int k = 0; k < N; ++k) m[o][k] = -INFINITY;
 #pragma unroll
-  for (int o = 0; o < 4; ++o)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) m[o][k] = -INFINITY;
-#pragma unroll
-  for (int dy = 0; dy < 5; ++dy) {
+  for (int dy = 0; dy < WIN; ++dy) {
     const int iy = iy0 + dy;
     if ((unsigned)iy >= (unsigned)H) continue;
 #pragma unroll
-    for (int dx = 0; dx < 5; ++dx) {
+    for (int dx = 0; dx < WIN; ++dx) {
       const int ix = ix0 + dx;
       if ((unsigned)ix >= (unsigned)W) continue;
-      const v8 v = *(const v8*)(x + (((int64_t)b * H + iy) * W + ix) * ldx + cc);
+      float v[N];
+      Chunk<T>::load(x, (((int64_t)p.b * H + iy) * W + ix) * ldx, p.c, v);
 #pragma unroll
-      for (int oy = 0; oy < 2; ++oy)
+      for (int oy = 0; oy < PATCH; ++oy)
 #pragma unroll
-        for (int ox = 0; ox < 2; ++ox)
+        for (int ox = 0; ox < PATCH; ++ox)
           if (dy >= 2 * oy && dy <= 2 * oy + 2 && dx >= 2 * ox && dx <= 2 * ox + 2) {     // compile-time after unrolling
 #pragma unroll
-            for (int k = 0; k < 8; ++k) m[oy * 2 + ox][k] = fmaxf(m[oy * 2 + ox][k], (float)v[k]);
+            for (int k = 0; k < N; ++k) m[oy * PATCH + ox][k] = fmaxf(m[oy * PATCH + ox][k], v[k]);
           }
     }
   }
 #pragma unroll
-  for (int oy = 0; oy < 2; ++oy)
+  for (int oy = 0; oy < PATCH; ++oy)
 #pragma unroll
-    for (int ox = 0; ox < 2; ++ox) {
-      v8 o;
-#pragma unroll
-      for (int k = 0; k < 8; ++k) o[k] = (bf16)m[oy * 2 + ox][k];
-      *(v8*)(y + (((int64_t)b * OH + 2 * py + oy) * OW + 2 * px + ox) * ldy + cc) = o;
-    }
+    for (int ox = 0; ox < PATCH; ++ox)
+      Chunk<T>::store(y, (((int64_t)p.b * OH + PATCH * p.y + oy) * OW + PATCH * p.x + ox) * ldy, p.c, m[oy * PATCH + ox]);
 }
 
-// F16X2: 8 channels (one 16-byte hi chunk + one 16-byte lo chunk) of one output per thread; hi + lo is exact in fp32, so the max
-// is the max of the represented values and re-splitting it reproduces the winning tap's (hi, lo) pair bit for bit
-__global__ __launch_bounds__(256) void k_maxpool_split(const sp16* __restrict__ x, sp16* __restrict__ y, int B, int H, int W, int C, int64_t ldx,
-                                                       int OH, int OW, int64_t ldy) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int c8 = C / 8;
-  const int64_t total = (int64_t)B * OH * OW * c8;
-  if (i >= total) return;
-  const int cc = (int)(i % c8) * 8;
-  int64_t p = i / c8;
-  const int ox = (int)(p % OW); p /= OW;
-  const int oy = (int)(p % OH);
-  const int b = (int)(p / OH);
-  float m[8];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) m[k] = -INFINITY;
-#pragma unroll
-  for (int dy = 0; dy < 3; ++dy) {
-    const int iy = oy * 2 - 1 + dy;
-    if ((unsigned)iy >= (unsigned)H) continue;
-#pragma unroll
-    for (int dx = 0; dx < 3; ++dx) {
-      const int ix = ox * 2 - 1 + dx;
-      if ((unsigned)ix >= (unsigned)W) continue;
-      float v[8];
-      split_load8(x, (((int64_t)b * H + iy) * W + ix) * ldx, cc, v);
-#pragma unroll
-      for (int k = 0; k < 8; ++k) m[k] = fmaxf(m[k], v[k]);
-    }
-  }
-  split_store8(y, (((int64_t)b * OH + oy) * OW + ox) * ldy, cc, m);
-}
-
-// ... on a 2 x 2 output patch per thread (even output extents): the 5 x 5 input window is read once - 25 x 32 bytes for 4 outputs instead
-// of 36 x 32 - and the taps the patch's outputs share stay in registers (k_maxpool_bf16_2x2's scheme)
-__global__ __launch_bounds__(256) void k_maxpool_split_2x2(const sp16* __restrict__ x, sp16* __restrict__ y, int B, int H, int W, int C, int64_t ldx,
-                                                           int OH, int OW, int64_t ldy) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int c8 = C / 8, PW = OW / 2, PH = OH / 2;
-  const int64_t total = (int64_t)B * PH * PW * c8;
-  if (i >= total) return;
-  const int cc = (int)(i % c8) * 8;
-  int64_t p = i / c8;
-  const int px = (int)(p % PW); p /= PW;
-  const int py = (int)(p % PH);
-  const int b = (int)(p / PH);
-  const int iy0 = 4 * py - 1, ix0 = 4 * px - 1;
-  float m[4][8];
-#pragma unroll
-  for (int o = 0; o < 4; ++o)
-#pragma unroll
-    for (int k = 0; k < 8; ++k) m[o][k] = -INFINITY;
-#pragma unroll
-  for (int dy = 0; dy < 5; ++dy) {
-    const int iy = iy0 + dy;
-    if ((unsigned)iy >= (unsigned)H) continue;
-#pragma unroll
-    for (int dx = 0; dx < 5; ++dx) {
-      const int ix = ix0 + dx;
-      if ((unsigned)ix >= (unsigned)W) continue;
-      float v[8];
-      split_load8(x, (((int64_t)b * H + iy) * W + ix) * ldx, cc, v);
-#pragma unroll
-      for (int oy = 0; oy < 2; ++oy)
-#pragma unroll
-        for (int ox = 0; ox < 2; ++ox)
-          if (dy >= 2 * oy && dy <= 2 * oy + 2 && dx >= 2 * ox && dx <= 2 * ox + 2) {     // compile-time after unrolling
-#pragma unroll
-            for (int k = 0; k < 8; ++k) m[oy * 2 + ox][k] = fmaxf(m[oy * 2 + ox][k], v[k]);
-          }
-    }
-  }
-#pragma unroll
-  for (int oy = 0; oy < 2; ++oy)
-#pragma unroll
-    for (int ox = 0; ox < 2; ++ox) split_store8(y, (((int64_t)b * OH + 2 * py + oy) * OW + 2 * px + ox) * ldy, cc, m[oy * 2 + ox]);
-}
-
+// Only what a plan can reach is instantiated: rtd_create admits inputs that are multiples of 32 and an embedding_size that is a multiple
+// of 16, so the pooled map has even extents and whole chunks, and the arena hands out 256-byte aligned dense tensors.  bf16 and pair
+// tensors take the 2 x 2 form and nothing else; fp32 (the exact engine, off the fast path) the one-output form.
 void launch_maxpool3x3s2(const Tensor& x, const Tensor& y, hipStream_t s) {
-  RTD_CHECK(x.dt == y.dt && x.c == y.c && x.c % 4 == 0 && x.n == y.n, 1, "maxpool: dtype/channels");
+  RTD_CHECK(x.dt == y.dt && x.c == y.c && x.n == y.n, 1, "maxpool: dtype/channels");
   RTD_CHECK(y.h == (x.h + 2 - 3) / 2 + 1 && y.w == (x.w + 2 - 3) / 2 + 1, 1, "maxpool: shape");
-  RTD_CHECK(x.bstride == (int64_t)x.h * x.w * x.ld && y.bstride == (int64_t)y.h * y.w * y.ld, 1, "maxpool: dense images");
-  if (x.dt == F16X2) {
-    RTD_CHECK(x.c % SPLIT_GROUP == 0 && x.ld % SPLIT_GROUP == 0 && y.ld % SPLIT_GROUP == 0 && (((uintptr_t)x.p | (uintptr_t)y.p) & 15) == 0, 1, "maxpool: split layout");
-    if (y.h % 2 == 0 && y.w % 2 == 0) {
-      const int64_t total2 = (int64_t)y.n * (y.h / 2) * (y.w / 2) * (y.c / 8);
-      rtd_launch(k_maxpool_split_2x2, dim3(blocks_for(total2, 256)), dim3(256), 0, s, (const sp16*)x.p, (sp16*)y.p, x.n, x.h, x.w, x.c, x.ld, y.h, y.w, y.ld);
-      HIP_CHECK(hipGetLastError());
-      return;
-    }
-    const int64_t total = (int64_t)y.n * y.h * y.w * (y.c / 8);
-    rtd_launch(k_maxpool_split, dim3(blocks_for(total, 256)), dim3(256), 0, s, (const sp16*)x.p, (sp16*)y.p, x.n, x.h, x.w, x.c, x.ld, y.h, y.w, y.ld);
-    HIP_CHECK(hipGetLastError());
-    return;
-  }
-  if (x.dt == BF16 && x.c % 8 == 0 && x.ld % 8 == 0 && y.ld % 8 == 0 && y.h % 2 == 0 && y.w % 2 == 0 && (((uintptr_t)x.p | (uintptr_t)y.p) & 15) == 0) {
-    const int64_t total2 = (int64_t)y.n * (y.h / 2) * (y.w / 2) * (y.c / 8);
-    rtd_launch(k_maxpool_bf16_2x2, dim3(blocks_for(total2, 256)), dim3(256), 0, s, (const bf16*)x.p, (bf16*)y.p, x.n, x.h, x.w, x.c,
-                       x.ld, y.h, y.w, y.ld);
-    HIP_CHECK(hipGetLastError());
-    return;
-  }
-  const int64_t total = (int64_t)y.n * y.h * y.w * (y.c / 4);
-  DISPATCH_T(x.dt, rtd_launch(k_maxpool<T>, dim3(blocks_for(total, 256)), dim3(256), 0, s, (const T*)x.p, (T*)y.p,
-                                      x.n, x.h, x.w, x.c, x.ld, y.h, y.w, y.ld));
-  HIP_CHECK(hipGetLastError());
+  RTD_CHECK(dense(x) && dense(y), 1, "maxpool: dense images");
+  RTD_CHECK(chunk_rows(x) && chunk_rows(y), 1, "maxpool: whole 16-byte channel chunks (bf16: C % 8, fp32: C % 4, pair tensors: C % 32) in 16-byte aligned rows");
+  RTD_CHECK(x.dt == F32 || (y.h % 2 == 0 && y.w % 2 == 0), 1, "maxpool: bf16 and pair tensors are pooled in 2 x 2 output patches: even pooled extents only");
+  with_act_dtype(x.dt, [&](auto t) {
+    typedef type_of<decltype(t)> T;
+    constexpr int PATCH = std::is_same<T, float>::value ? 1 : 2;
+    const int64_t total = (int64_t)y.n * (y.h / PATCH) * (y.w / PATCH) * (y.c / Chunk<T>::N);
+    launch_1d(k_maxpool<T, PATCH>, total, s, (const T*)x.p, (T*)y.p, x.n, x.h, x.w, x.c, x.ld, y.h, y.w, y.ld);
+  });
 }
-
 
 // ------------------------------------------------------------------------------------------ avg-pool 2x2 s2
 // nn.AvgPool2d(2, 2, 0, ceil_mode=True) of the ResNet-vd shortcut (HF:rt_detr_resnet.py:199-205); extents are
-// even here (input sizes are multiples of 32), so every window is a full 2x2.  8 channels per thread.
+// even here (input sizes are multiples of 32), so every window is a full 2x2.  One Chunk<T> per thread.  The summation order is part of
+// the contract: the fused average of the streaming conv kernel (conv_igemm.hip, ConvArgs::avg_y) reproduces the pair instantiation bit for bit.
 template <typename T>
 __global__ void k_avgpool2(const T* __restrict__ x, T* __restrict__ y, int B, int H, int W, int C, int64_t ldx, int64_t ldy) {
+  constexpr int N = Chunk<T>::N;
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  constexpr int V = 16 / (int)sizeof(T);
-  const int cv = C / V;
+  const int cn = C / N;
   const int OH = H / 2, OW = W / 2;
-  const int64_t total = (int64_t)B * OH * OW * cv;
-  if (i >= total) return;
-  const int cc = (int)(i % cv) * V;
-  int64_t p = i / cv;
-  const int ox = (int)(p % OW); p /= OW;
-  const int oy = (int)(p % OH);
-  const int b = (int)(p / OH);
-  const T* q = x + (((int64_t)b * H + 2 * oy) * W + 2 * ox) * ldx + cc;
-  typedef T VT __attribute__((ext_vector_type(V)));
-  const VT a0 = *(const VT*)q, a1 = *(const VT*)(q + ldx), a2 = *(const VT*)(q + (int64_t)W * ldx), a3 = *(const VT*)(q + (int64_t)(W + 1) * ldx);
-  VT o;
+  if (i >= (int64_t)B * OH * OW * cn) return;
+  const Nhwc o = nhwc_of(i, OH, OW, cn, N);
+  const int64_t q = (((int64_t)o.b * H + 2 * o.y) * W + 2 * o.x) * ldx;
+  float a0[N], a1[N], a2[N], a3[N], r[N];
+  Chunk<T>::load(x, q, o.c, a0); Chunk<T>::load(x, q + ldx, o.c, a1); Chunk<T>::load(x, q + (int64_t)W * ldx, o.c, a2); Chunk<T>::load(x, q + (int64_t)(W + 1) * ldx, o.c, a3);
 #pragma unroll
-  for (int k = 0; k < V; ++k) o[k] = (T)((((float)a0[k] + (float)a1[k]) + ((float)a2[k] + (float)a3[k])) * 0.25f);
-  *(VT*)(y + (((int64_t)b * OH + oy) * OW + ox) * ldy + cc) = o;
-}
-__global__ void k_avgpool2_split(const sp16* __restrict__ x, sp16* __restrict__ y, int B, int H, int W, int C, int64_t ldx, int64_t ldy) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int cv = C / 8;
-  const int OH = H / 2, OW = W / 2;
-  const int64_t total = (int64_t)B * OH * OW * cv;
-  if (i >= total) return;
-  const int cc = (int)(i % cv) * 8;
-  int64_t p = i / cv;
-  const int ox = (int)(p % OW); p /= OW;
-  const int oy = (int)(p % OH);
-  const int b = (int)(p / OH);
-  const int64_t q = (((int64_t)b * H + 2 * oy) * W + 2 * ox) * ldx;
-  float a0[8], a1[8], a2[8], a3[8], o[8];
-  split_load8(x, q, cc, a0); split_load8(x, q + ldx, cc, a1); split_load8(x, q + (int64_t)W * ldx, cc, a2); split_load8(x, q + (int64_t)(W + 1) * ldx, cc, a3);
-#pragma unroll
-  for (int k = 0; k < 8; ++k) o[k] = ((a0[k] + a1[k]) + (a2[k] + a3[k])) * 0.25f;
-  split_store8(y, (((int64_t)b * OH + oy) * OW + ox) * ldy, cc, o);
+  for (int k = 0; k < N; ++k) r[k] = ((a0[k] + a1[k]) + (a2[k] + a3[k])) * 0.25f;
+  Chunk<T>::store(y, (((int64_t)o.b * OH + o.y) * OW + o.x) * ldy, o.c, r);
 }
 void launch_avgpool2(const Tensor& x, const Tensor& y, hipStream_t s) {
-  if (x.dt == F16X2) {
-    RTD_CHECK(y.dt == F16X2 && x.c == y.c && x.c % SPLIT_GROUP == 0 && x.ld % SPLIT_GROUP == 0 && y.ld % SPLIT_GROUP == 0 && x.n == y.n, 1, "avgpool: split layout");
-    RTD_CHECK(x.h % 2 == 0 && x.w % 2 == 0 && y.h == x.h / 2 && y.w == x.w / 2, 1, "avgpool: even extents only");
-    RTD_CHECK(x.bstride == (int64_t)x.h * x.w * x.ld && y.bstride == (int64_t)y.h * y.w * y.ld && (((uintptr_t)x.p | (uintptr_t)y.p) & 15) == 0, 1, "avgpool: dense images");
-    const int64_t total = (int64_t)y.n * y.h * y.w * (y.c / 8);
-    rtd_launch(k_avgpool2_split, dim3(blocks_for(total, 256)), dim3(256), 0, s, (const sp16*)x.p, (sp16*)y.p, x.n, x.h, x.w, x.c, x.ld, y.ld);
-    HIP_CHECK(hipGetLastError());
-    return;
-  }
-  const int V = x.dt == BF16 ? 8 : 4;
-  RTD_CHECK(x.dt == y.dt && x.c == y.c && x.c % V == 0 && x.ld % V == 0 && y.ld % V == 0 && x.n == y.n, 1, "avgpool: dtype/channels");
+  RTD_CHECK(x.dt == y.dt && x.c == y.c && x.n == y.n, 1, "avgpool: dtype/channels");
   RTD_CHECK(x.h % 2 == 0 && x.w % 2 == 0 && y.h == x.h / 2 && y.w == x.w / 2, 1, "avgpool: even extents only");
-  RTD_CHECK(x.bstride == (int64_t)x.h * x.w * x.ld && y.bstride == (int64_t)y.h * y.w * y.ld, 1, "avgpool: dense images");
-  RTD_CHECK((((uintptr_t)x.p | (uintptr_t)y.p) & 15) == 0, 1, "avgpool: alignment");
-  const int64_t total = (int64_t)y.n * y.h * y.w * (y.c / V);
-  DISPATCH_T(x.dt, rtd_launch(k_avgpool2<T>, dim3(blocks_for(total, 256)), dim3(256), 0, s, (const T*)x.p, (T*)y.p, x.n,
-                                      x.h, x.w, x.c, x.ld, y.ld));
-  HIP_CHECK(hipGetLastError());
+  RTD_CHECK(dense(x) && dense(y), 1, "avgpool: dense images");
+  RTD_CHECK(chunk_rows(x) && chunk_rows(y), 1, "avgpool: whole 16-byte channel chunks (bf16: C % 8, fp32: C % 4, pair tensors: C % 32) in 16-byte aligned rows");
+  with_act_dtype(x.dt, [&](auto t) {
+    typedef type_of<decltype(t)> T;
+    launch_1d(k_avgpool2<T>, (int64_t)y.n * y.h * y.w * (y.c / Chunk<T>::N), s, (const T*)x.p, (T*)y.p, x.n, x.h, x.w, x.c, x.ld, y.ld);
+  });
 }
 
 // ------------------------------------------------------------------------------------------ nearest 2x upsample
 // F.interpolate(scale_factor=2, mode="nearest") (HF:v2.py:1191), written straight into the first
-// channel half of the FPN concat buffer (y is a channel-slice view).
+// channel half of the FPN concat buffer (y is a channel-slice view).  A pure copy of 4 elements per thread: no Chunk (a pair
+// would be summed and split again for nothing).
 template <typename T>
 __global__ void k_upsample2x(const T* __restrict__ x, T* __restrict__ y, int B, int H, int W, int C, int64_t ldx,
                              int64_t ldy) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int c4 = C / 4;
   const int OH = 2 * H, OW = 2 * W;
-  const int64_t total = (int64_t)B * OH * OW * c4;
-  if (i >= total) return;
-  const int cc = (int)(i % c4) * 4;
-  int64_t p = i / c4;
-  const int ox = (int)(p % OW); p /= OW;
-  const int oy = (int)(p % OH);
-  const int b = (int)(p / OH);
-  const T* q = x + (((int64_t)b * H + (oy >> 1)) * W + (ox >> 1)) * ldx + cc;
-  T* o = y + (((int64_t)b * OH + oy) * OW + ox) * ldy + cc;
+  if (i >= (int64_t)B * OH * OW * c4) return;
+  const Nhwc o = nhwc_of(i, OH, OW, c4, 4);
+  const T* q = x + (((int64_t)o.b * H + (o.y >> 1)) * W + (o.x >> 1)) * ldx + o.c;
+  T* d = y + (((int64_t)o.b * OH + o.y) * OW + o.x) * ldy + o.c;
 #pragma unroll
-  for (int k = 0; k < 4; ++k) o[k] = q[k];
+  for (int k = 0; k < 4; ++k) d[k] = q[k];
 }
 void launch_upsample2x(const Tensor& x, const Tensor& y, hipStream_t s) {
   RTD_CHECK(x.dt == y.dt && x.c == y.c && x.c % 4 == 0 && y.h == 2 * x.h && y.w == 2 * x.w && x.n == y.n, 1, "upsample: shape");
-  RTD_CHECK(x.bstride == (int64_t)x.h * x.w * x.ld && y.bstride == (int64_t)y.h * y.w * y.ld, 1, "upsample: dense images");
-  const int64_t total = (int64_t)y.n * y.h * y.w * (y.c / 4);
-  DISPATCH_T(x.dt, rtd_launch(k_upsample2x<T>, dim3(blocks_for(total, 256)), dim3(256), 0, s, (const T*)x.p,
-                                      (T*)y.p, x.n, x.h, x.w, x.c, x.ld, y.ld));
-  HIP_CHECK(hipGetLastError());
+  RTD_CHECK(dense(x) && dense(y), 1, "upsample: dense images");
+  // A pair tensor (the f16x3 plans, when the upsample fold declines) is copied by the fp32 instantiation as 4-byte units: `c`, `ld` and
+  // slice offsets of a F16X2 view count 4 bytes per channel (common.h), and a view of whole 32-channel groups [32 hi | 32 lo] is `c`
+  // consecutive units per pixel.  Nothing is computed, so the units' meaning does not matter.
+  RTD_CHECK(x.dt != F16X2 || (x.c % SPLIT_GROUP == 0 && x.ld % SPLIT_GROUP == 0 && y.ld % SPLIT_GROUP == 0), 1, "upsample: pair tensors in whole channel groups");
+  with_dtype(x.dt == F16X2 ? (int)F32 : x.dt, [&](auto t) {
+    typedef type_of<decltype(t)> T;
+    launch_1d(k_upsample2x<T>, (int64_t)y.n * y.h * y.w * (y.c / 4), s, (const T*)x.p, (T*)y.p, x.n, x.h, x.w, x.c, x.ld, y.ld);
+  });
 }
 
 // ------------------------------------------------------------------------------------------ multi-head attention
@@ -660,20 +539,20 @@ void launch_attention(const Tensor& qk, const Tensor& v, const Tensor& o, int he
   RTD_CHECK(D % heads == 0, 1, "attention: heads");
   const int hd = D / heads;
   const dim3 grid((L + 63) / 64, heads, B), blk(256);
-  if (qk.dt == F32 && L >= 64 && (hd == 32 || hd == 48 || hd == 64) && qk.ld % 4 == 0 && v.ld % 4 == 0 && o.ld % 4 == 0 &&
-      (((uintptr_t)qk.p | (uintptr_t)v.p | (uintptr_t)o.p) & 15) == 0) {
-    if (hd == 32) rtd_launch(k_attention_mfma_f32<32>, grid, blk, 0, s, (const float*)qk.p, qk.ld, (const float*)v.p, v.ld, (float*)o.p, o.ld, L, D);
-    else if (hd == 48) rtd_launch(k_attention_mfma_f32<48>, grid, blk, 0, s, (const float*)qk.p, qk.ld, (const float*)v.p, v.ld, (float*)o.p, o.ld, L, D);
-    else rtd_launch(k_attention_mfma_f32<64>, grid, blk, 0, s, (const float*)qk.p, qk.ld, (const float*)v.p, v.ld, (float*)o.p, o.ld, L, D);
-    HIP_CHECK(hipGetLastError());
-    return;
+  RTD_CHECK(hd == 32 || hd == 48 || hd == 64, 1, "attention: head dim must be 32, 48 or 64");
+  auto with_hd = [&](auto&& f) {
+    if (hd == 32) f(std::integral_constant<int, 32>{});
+    else if (hd == 48) f(std::integral_constant<int, 48>{});
+    else f(std::integral_constant<int, 64>{});
+  };
+  if (qk.dt == F32 && L >= 64 && qk.ld % 4 == 0 && v.ld % 4 == 0 && o.ld % 4 == 0 && aligned16(qk.p, v.p, o.p)) {
+    with_hd([&](auto HD) { rtd_launch(k_attention_mfma_f32<HD()>, grid, blk, 0, s, (const float*)qk.p, qk.ld, (const float*)v.p, v.ld, (float*)o.p, o.ld, L, D); });
+  } else {
+    with_dtype(qk.dt, [&](auto t) {
+      typedef type_of<decltype(t)> T;
+      with_hd([&](auto HD) { rtd_launch((k_attention<T, HD()>), grid, blk, 0, s, (const T*)qk.p, qk.ld, (const T*)v.p, v.ld, (T*)o.p, o.ld, L, D); });
+    });
   }
-#define ATT_GO(HD) DISPATCH_T(qk.dt, rtd_launch((k_attention<T, HD>), grid, blk, 0, s, (const T*)qk.p, qk.ld, (const T*)v.p, v.ld, (T*)o.p, o.ld, L, D))
-  if (hd == 32) ATT_GO(32);
-  else if (hd == 48) ATT_GO(48);
-  else if (hd == 64) ATT_GO(64);
-  else RTD_CHECK(false, 1, "attention: head dim must be 32, 48 or 64");
-#undef ATT_GO
   HIP_CHECK(hipGetLastError());
 }
 
@@ -694,9 +573,7 @@ __global__ void k_set_rows(T* __restrict__ y, int64_t ld, int C, const int32_t* 
 void launch_set_rows(const Tensor& y, const int32_t* rows, int nrows, int rows_per_image, const float* vec, hipStream_t s) {
   if (nrows == 0) return;
   const int64_t total = (int64_t)y.n * nrows * y.c;
-  DISPATCH_T(y.dt, rtd_launch(k_set_rows<T>, dim3(blocks_for(total, 256)), dim3(256), 0, s, (T*)y.p, y.ld, y.c, rows,
-                                      nrows, rows_per_image, vec, y.n));
-  HIP_CHECK(hipGetLastError());
+  with_dtype(y.dt, [&](auto t) { typedef type_of<decltype(t)> T; launch_1d(k_set_rows<T>, total, s, (T*)y.p, y.ld, y.c, rows, nrows, rows_per_image, vec, y.n); });
 }
 
 // ------------------------------------------------------------------------------------------ row max
@@ -715,8 +592,7 @@ __global__ void k_rowmax(const float* __restrict__ x, int64_t ld, int C, int64_t
 void launch_rowmax(const Tensor& x, float* out, hipStream_t s) {
   RTD_CHECK(x.dt == F32, 1, "rowmax: fp32 logits expected");
   const int64_t rows = x.pixels();
-  rtd_launch(k_rowmax, dim3(blocks_for(rows * 16, 256)), dim3(256), 0, s, (const float*)x.p, x.ld, x.c, rows, out);
-  HIP_CHECK(hipGetLastError());
+  launch_1d(k_rowmax, rows * 16, s, (const float*)x.p, x.ld, x.c, rows, out);
 }
 
 // ------------------------------------------------------------------------------------------ exact top-k
@@ -744,7 +620,7 @@ struct TopkPost {
   float* block6;           // [B][K][6]
   int C, Q;
 };
-__device__ __forceinline__ float topk_sigmoid(float x) { return 1.f / (1.f + __expf(-x)); }   // == sigmoidf_ below (k_pp_scores)
+__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 template <bool REG, bool POST = false>
 __global__ __launch_bounds__(1024) void k_topk(const float* __restrict__ keys, int N, int K, int32_t* __restrict__ idx_out,
                                                 float* __restrict__ val_out, const TopkPost pa) {
@@ -788,7 +664,7 @@ __global__ __launch_bounds__(1024) void k_topk(const float* __restrict__ keys, i
 #pragma unroll
     for (int j = 0; j < MAXPT; ++j) {
       const int i = tid + j * 1024;
-      kreg[j] = (j < npt && i < N) ? f2key(POST ? topk_sigmoid(kb[i]) : kb[i]) : 0u;         // slots beyond N are never counted (guarded by i < N)
+      kreg[j] = (j < npt && i < N) ? f2key(POST ? sigmoidf_(kb[i]) : kb[i]) : 0u;         // slots beyond N are never counted (guarded by i < N)
     }
   }
   // ---- fast path (round 5): bound the candidates before any pass over all the keys ----------------------------------------------
@@ -1088,18 +964,13 @@ void launch_gather_rows(const Tensor& src, const int32_t* idx, int rows_per_imag
   const int B = dst.n, Q = dst.h * dst.w, C = dst.c;
   RTD_CHECK(src.c == C && src.n == B && src.h * src.w == rows_per_image, 1, "gather: shape");
   const int64_t total = (int64_t)B * Q * C;
-  const dim3 grid(blocks_for(total, 256)), blk(256);
-#define G_GO(TS, TD) rtd_launch((k_gather_rows<TS, TD>), grid, blk, 0, s, (const TS*)src.p, src.ld, rows_per_image, idx, Q, C, (TD*)dst.p, dst.ld, B)
-  if (src.dt == BF16 && dst.dt == BF16) G_GO(bf16, bf16);
-  else if (src.dt == BF16) G_GO(bf16, float);
-  else if (dst.dt == BF16) G_GO(float, bf16);
-  else G_GO(float, float);
-#undef G_GO
-  HIP_CHECK(hipGetLastError());
+  with_dtype(src.dt, [&](auto ts) { with_dtype(dst.dt, [&](auto td) {
+    typedef type_of<decltype(ts)> TS; typedef type_of<decltype(td)> TD;
+    launch_1d(k_gather_rows<TS, TD>, total, s, (const TS*)src.p, src.ld, rows_per_image, idx, Q, C, (TD*)dst.p, dst.ld, B);
+  }); });
 }
 
 // ------------------------------------------------------------------------------------------ reference boxes
-__device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
 __device__ __forceinline__ float inv_sigmoid(float x) {   // HF:v2.py:548-552, eps 1e-5
   x = fminf(fmaxf(x, 0.f), 1.f);
   const float x1 = fmaxf(x, 1e-5f), x2 = fmaxf(1.f - x, 1e-5f);
@@ -1126,9 +997,7 @@ void launch_ref_init(const Tensor& boxdelta, const float* anchors, const int32_t
                      hipStream_t s) {
   RTD_CHECK(boxdelta.dt == F32 && boxdelta.c == 4, 1, "ref_init: fp32 [.,4] deltas expected");
   const int64_t total = boxdelta.pixels();
-  rtd_launch(k_ref_init, dim3(blocks_for(total, 256)), dim3(256), 0, s, (const float*)boxdelta.p, boxdelta.ld, anchors,
-                     idx, S, ref_unact8, ref8, total);
-  HIP_CHECK(hipGetLastError());
+  launch_1d(k_ref_init, total, s, (const float*)boxdelta.p, boxdelta.ld, anchors, idx, S, ref_unact8, ref8, total);
 }
 // new_reference = sigmoid(bbox_embed(hs) + inverse_sigmoid(reference))   (HF:v2.py:636-639)
 __global__ void k_box_refine(const float* __restrict__ delta, int64_t ldd, float* __restrict__ ref8, int64_t total) {
@@ -1140,8 +1009,7 @@ __global__ void k_box_refine(const float* __restrict__ delta, int64_t ldd, float
 void launch_box_refine(const Tensor& delta, float* ref8, hipStream_t s) {
   RTD_CHECK(delta.dt == F32 && delta.c == 4, 1, "box_refine: fp32 [.,4] deltas expected");
   const int64_t total = delta.pixels();
-  rtd_launch(k_box_refine, dim3(blocks_for(total, 256)), dim3(256), 0, s, (const float*)delta.p, delta.ld, ref8, total);
-  HIP_CHECK(hipGetLastError());
+  launch_1d(k_box_refine, total, s, (const float*)delta.p, delta.ld, ref8, total);
 }
 
 // ------------------------------------------------------------------------------------------ MS-deformable sampling
@@ -1208,12 +1076,11 @@ void launch_msdeform(const Tensor& value, int value_coff, const Tensor& offaw, c
   const int64_t items = (int64_t)B * Q * heads;
   const dim3 grid(blocks_for(items, 8)), blk(256);
   const char* vp = (const char*)value.p + (size_t)value_coff * dtype_size(value.dt);
-#define MS_GO(TV, TO) rtd_launch((k_msdeform<TV, TO>), grid, blk, 0, s, (const TV*)vp, value.ld, value.bstride, (const float*)offaw.p, offaw.ld, ref8, (TO*)out.p, out.ld, Q, heads, n_levels, n_points, level_hw_start, offset_scale, items)
-  if (value.dt == BF16 && out.dt == BF16) MS_GO(bf16, bf16);
-  else if (value.dt == BF16) MS_GO(bf16, float);
-  else if (out.dt == BF16) MS_GO(float, bf16);
-  else MS_GO(float, float);
-#undef MS_GO
+  with_dtype(value.dt, [&](auto tv) { with_dtype(out.dt, [&](auto to) {
+    typedef type_of<decltype(tv)> TV; typedef type_of<decltype(to)> TO;
+    rtd_launch((k_msdeform<TV, TO>), grid, blk, 0, s, (const TV*)vp, value.ld, value.bstride, (const float*)offaw.p, offaw.ld, ref8, (TO*)out.p, out.ld, Q,
+               heads, n_levels, n_points, level_hw_start, offset_scale, items);
+  }); });
   HIP_CHECK(hipGetLastError());
 }
 
@@ -1229,9 +1096,7 @@ __global__ void k_pp_scores(const float* __restrict__ logits, int64_t ld, int C,
 void launch_postprocess_scores(const Tensor& logits, float* scores, hipStream_t s) {
   RTD_CHECK(logits.dt == F32, 1, "postprocess: fp32 logits expected");
   const int64_t rows = logits.pixels();
-  rtd_launch(k_pp_scores, dim3(blocks_for(rows * logits.c, 256)), dim3(256), 0, s, (const float*)logits.p, logits.ld,
-                     logits.c, rows, scores);
-  HIP_CHECK(hipGetLastError());
+  launch_1d(k_pp_scores, rows * logits.c, s, (const float*)logits.p, logits.ld, logits.c, rows, scores);
 }
 // labels = index % C ; query = index // C ; boxes = cxcywh->xyxy * (w,h,w,h) of the ORIGINAL frame
 __global__ void k_pp_gather(const float* __restrict__ topv, const int32_t* __restrict__ topi, const float* __restrict__ ref8,
@@ -1257,8 +1122,7 @@ __global__ void k_pp_gather(const float* __restrict__ topv, const int32_t* __res
 void launch_postprocess_gather(const float* topv, const int32_t* topi, const float* ref8, const float* scale_wh, int B, int Q,
                                int C, float* block6, hipStream_t s) {
   const int64_t total = (int64_t)B * Q;
-  rtd_launch(k_pp_gather, dim3(blocks_for(total, 256)), dim3(256), 0, s, topv, topi, ref8, scale_wh, Q, C, block6, total);
-  HIP_CHECK(hipGetLastError());
+  launch_1d(k_pp_gather, total, s, topv, topi, ref8, scale_wh, Q, C, block6, total);
 }
 
 // ------------------------------------------------------------------------------------------ pre-process
@@ -1284,17 +1148,20 @@ __global__ void k_preprocess_identity(const FrameArgs fa, int H, int W, T* __res
 void launch_preprocess_identity(const FrameArgs& fa, int H, int W, const Tensor& y, float* scale_wh_dev, hipStream_t s) {
   RTD_CHECK(y.c == 8 && y.ld == 8 && y.h == H && y.w == W && y.n >= fa.n, 1, "preprocess: output must be [n,H,W,8]");
   const int64_t total = (int64_t)fa.n * H * W;
-  DISPATCH_T(y.dt, rtd_launch(k_preprocess_identity<T>, dim3(blocks_for(total, 256)), dim3(256), 0, s, fa, H, W, (T*)y.p, scale_wh_dev, total));
-  HIP_CHECK(hipGetLastError());
+  with_dtype(y.dt, [&](auto t) { typedef type_of<decltype(t)> T; launch_1d(k_preprocess_identity<T>, total, s, fa, H, W, (T*)y.p, scale_wh_dev, total); });
 }
-__global__ void k_set_scale(const FrameArgs fa, float* __restrict__ scale_wh) {
+// the per-call frame arguments on the device: the post-processor's orig_target_sizes and, for the fused uint8 stem, the frame pointers
+// (`table` may be null: the plans that read their frames through launch_resize_pil / launch_preprocess_identity only need the sizes)
+__global__ void k_set_frame_table(const FrameArgs fa, const uint8_t** __restrict__ table, float* __restrict__ scale_wh) {
   const int i = threadIdx.x;
   if (i < 2 * fa.n) scale_wh[i] = fa.scale_wh[i];
+  if (table && i < fa.n) table[i] = fa.ptr[i];
 }
-void launch_set_scale(const FrameArgs& fa, float* scale_wh_dev, hipStream_t s) {
-  rtd_launch(k_set_scale, dim3(1), dim3(2 * RTD_MAX_BATCH), 0, s, fa, scale_wh_dev);
+void launch_set_frame_table(const FrameArgs& fa, const uint8_t** table_dev, float* scale_wh_dev, hipStream_t s) {
+  rtd_launch(k_set_frame_table, dim3(1), dim3(2 * RTD_MAX_BATCH), 0, s, fa, table_dev, scale_wh_dev);
   HIP_CHECK(hipGetLastError());
 }
+void launch_set_scale(const FrameArgs& fa, float* scale_wh_dev, hipStream_t s) { launch_set_frame_table(fa, nullptr, scale_wh_dev, s); }
 
 // PIL's antialiased bilinear stretch-resize (ImagingResample, 8 bits per channel): two separable
 // passes with fixed-point coefficients (22 fractional bits) and a uint8 intermediate - the exact
@@ -1304,85 +1171,61 @@ __device__ __forceinline__ int clip8(int v) {
   v >>= 22;
   return v < 0 ? 0 : (v > 255 ? 255 : v);
 }
+// one output pixel of either pass: the three channels of `cnt` source pixels, `stride` bytes apart from `px` on, weighted by k[0 .. cnt),
+// rounded (+ 2^21) and clipped to uint8
+__device__ __forceinline__ void resample3(const uint8_t* __restrict__ px, int64_t stride, const int32_t* __restrict__ k, int cnt, int (&o)[3]) {
+  int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
+  for (int j = 0; j < cnt; ++j) {
+    const uint8_t* p = px + j * stride;
+    s0 += (int)p[0] * k[j];
+    s1 += (int)p[1] * k[j];
+    s2 += (int)p[2] * k[j];
+  }
+  o[0] = clip8(s0); o[1] = clip8(s1); o[2] = clip8(s2);
+}
 __global__ void k_resize_h(const uint8_t* __restrict__ src, int sh, int sw, uint8_t* __restrict__ tmp, int dw, ResizeCoef c) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)sh * dw) return;
   const int y = (int)(i / dw), x = (int)(i - (int64_t)y * dw);
   const int xmin = c.hb[x * 2], cnt = c.hb[x * 2 + 1];
-  const int32_t* k = c.hk + (int64_t)x * c.hks;
-  int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
-  const uint8_t* row = src + ((int64_t)y * sw + xmin) * 3;
-  for (int j = 0; j < cnt; ++j) {
-    s0 += (int)row[j * 3 + 0] * k[j];
-    s1 += (int)row[j * 3 + 1] * k[j];
-    s2 += (int)row[j * 3 + 2] * k[j];
-  }
+  int v[3];
+  resample3(src + ((int64_t)y * sw + xmin) * 3, 3, c.hk + (int64_t)x * c.hks, cnt, v);
   uint8_t* o = tmp + i * 3;
-  o[0] = (uint8_t)clip8(s0); o[1] = (uint8_t)clip8(s1); o[2] = (uint8_t)clip8(s2);
+  o[0] = (uint8_t)v[0]; o[1] = (uint8_t)v[1]; o[2] = (uint8_t)v[2];
 }
+// vertical pass; the result is either a padded NHWC-8 pixel of the network input (T = bf16 / float: BGR -> RGB, ToTensor's / 255) or
+// (T = uint8_t, the fused uint8 stem does BGR -> RGB itself) a uint8 HWC pixel in the SOURCE channel order
 template <typename T>
 __global__ void k_resize_v(const uint8_t* __restrict__ tmp, int sh, int dw, T* __restrict__ y, int dh, ResizeCoef c) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (int64_t)dh * dw) return;
   const int yy = (int)(i / dw), x = (int)(i - (int64_t)yy * dw);
   const int ymin = c.vb[yy * 2], cnt = c.vb[yy * 2 + 1];
-  const int32_t* k = c.vk + (int64_t)yy * c.vks;
-  int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
-  for (int j = 0; j < cnt; ++j) {
-    const uint8_t* p = tmp + ((int64_t)(ymin + j) * dw + x) * 3;
-    s0 += (int)p[0] * k[j];
-    s1 += (int)p[1] * k[j];
-    s2 += (int)p[2] * k[j];
-  }
-  T* o = y + i * 8;
-  o[0] = (T)((float)clip8(s2) / 255.0f);   // BGR -> RGB
-  o[1] = (T)((float)clip8(s1) / 255.0f);
-  o[2] = (T)((float)clip8(s0) / 255.0f);
+  int v[3];
+  resample3(tmp + ((int64_t)ymin * dw + x) * 3, (int64_t)dw * 3, c.vk + (int64_t)yy * c.vks, cnt, v);
+  if constexpr (std::is_same<T, uint8_t>::value) {
+    uint8_t* o = y + i * 3;
+    o[0] = (uint8_t)v[0]; o[1] = (uint8_t)v[1]; o[2] = (uint8_t)v[2];
+  } else {
+    T* o = y + i * 8;
+    o[0] = (T)((float)v[2] / 255.0f);   // BGR -> RGB
+    o[1] = (T)((float)v[1] / 255.0f);
+    o[2] = (T)((float)v[0] / 255.0f);
 #pragma unroll
-  for (int q = 3; q < 8; ++q) o[q] = (T)0.f;
+    for (int q = 3; q < 8; ++q) o[q] = (T)0.f;
+  }
 }
 void launch_resize_pil(const uint8_t* src, int sh, int sw, uint8_t* tmp, const Tensor& y, int image, const ResizeCoef& c,
                        hipStream_t s) {
   const int dh = y.h, dw = y.w;
   RTD_CHECK(y.c == 8 && y.ld == 8 && image < y.n, 1, "resize: output must be [n,H,W,8]");
-  rtd_launch(k_resize_h, dim3(blocks_for((int64_t)sh * dw, 256)), dim3(256), 0, s, src, sh, sw, tmp, dw, c);
+  launch_1d(k_resize_h, (int64_t)sh * dw, s, src, sh, sw, tmp, dw, c);
   char* yp = (char*)y.p + (size_t)image * y.bstride * dtype_size(y.dt);
-  DISPATCH_T(y.dt, rtd_launch(k_resize_v<T>, dim3(blocks_for((int64_t)dh * dw, 256)), dim3(256), 0, s, tmp, sh, dw, (T*)yp, dh, c));
-  HIP_CHECK(hipGetLastError());
-}
-
-
-__global__ void k_set_frame_table(const FrameArgs fa, const uint8_t** __restrict__ table, float* __restrict__ scale_wh) {
-  const int i = threadIdx.x;
-  if (i < 2 * fa.n) scale_wh[i] = fa.scale_wh[i];
-  if (i < fa.n) table[i] = fa.ptr[i];
-}
-void launch_set_frame_table(const FrameArgs& fa, const uint8_t** table_dev, float* scale_wh_dev, hipStream_t s) {
-  rtd_launch(k_set_frame_table, dim3(1), dim3(2 * RTD_MAX_BATCH), 0, s, fa, table_dev, scale_wh_dev);
-  HIP_CHECK(hipGetLastError());
-}
-
-// vertical pass of the PIL resampler with a uint8 HWC result in the SOURCE channel order (the fused stem does BGR->RGB itself)
-__global__ void k_resize_v_u8(const uint8_t* __restrict__ tmp, int sh, int dw, uint8_t* __restrict__ y, int dh, ResizeCoef c) {
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)dh * dw) return;
-  const int yy = (int)(i / dw), x = (int)(i - (int64_t)yy * dw);
-  const int ymin = c.vb[yy * 2], cnt = c.vb[yy * 2 + 1];
-  const int32_t* k = c.vk + (int64_t)yy * c.vks;
-  int s0 = 1 << 21, s1 = 1 << 21, s2 = 1 << 21;
-  for (int j = 0; j < cnt; ++j) {
-    const uint8_t* p = tmp + ((int64_t)(ymin + j) * dw + x) * 3;
-    s0 += (int)p[0] * k[j];
-    s1 += (int)p[1] * k[j];
-    s2 += (int)p[2] * k[j];
-  }
-  uint8_t* o = y + i * 3;
-  o[0] = (uint8_t)clip8(s0); o[1] = (uint8_t)clip8(s1); o[2] = (uint8_t)clip8(s2);
+  with_dtype(y.dt, [&](auto t) { typedef type_of<decltype(t)> T; launch_1d(k_resize_v<T>, (int64_t)dh * dw, s, tmp, sh, dw, (T*)yp, dh, c); });
 }
 void launch_resize_pil_u8(const uint8_t* src, int sh, int sw, uint8_t* tmp, uint8_t* dst, int dh, int dw, const ResizeCoef& c, hipStream_t s) {
-  rtd_launch(k_resize_h, dim3(blocks_for((int64_t)sh * dw, 256)), dim3(256), 0, s, src, sh, sw, tmp, dw, c);
-  rtd_launch(k_resize_v_u8, dim3(blocks_for((int64_t)dh * dw, 256)), dim3(256), 0, s, tmp, sh, dw, dst, dh, c);
-  HIP_CHECK(hipGetLastError());
+  launch_1d(k_resize_h, (int64_t)sh * dw, s, src, sh, sw, tmp, dw, c);
+  launch_1d(k_resize_v<uint8_t>, (int64_t)dh * dw, s, tmp, sh, dw, dst, dh, c);
 }
 
 // RTDETRDetector.preprocess (src/rtdetr_detector.py:206-236) as a value: uint8 HWC BGR at the network's size -> [3][H][W] fp32 RGB in [0, 1]
@@ -1397,8 +1240,7 @@ __global__ void k_u8_hwc_to_chw_f32(const uint8_t* __restrict__ src, int H, int 
   out[2 * hw + i] = (float)px[0] / 255.0f;
 }
 void launch_u8_hwc_to_chw_f32(const uint8_t* src, int H, int W, float* out, hipStream_t s) {
-  rtd_launch(k_u8_hwc_to_chw_f32, dim3(blocks_for((int64_t)H * W, 256)), dim3(256), 0, s, src, H, W, out);
-  HIP_CHECK(hipGetLastError());
+  launch_1d(k_u8_hwc_to_chw_f32, (int64_t)H * W, s, src, H, W, out);
 }
 
 // ---- backbone.stem.0 from uint8 frames -------------------------------------------------------------------------------------
@@ -1608,8 +1450,7 @@ void launch_crop_resize(const CropBatch& cb, int n, int out_size, const float me
   CropNorm nm;
   for (int k = 0; k < 3; ++k) { nm.mean[k] = mean[k]; nm.inv_std[k] = 1.0f / stdv[k]; }
   const int64_t total = (int64_t)n * out_size * out_size;
-  rtd_launch(k_crop_resize, dim3(blocks_for(total, 256)), dim3(256), 0, s, cb, n, out_size, nm, out);
-  HIP_CHECK(hipGetLastError());
+  launch_1d(k_crop_resize, total, s, cb, n, out_size, nm, out);
 }
 
 }  // namespace rtd

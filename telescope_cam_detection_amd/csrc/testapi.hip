@@ -493,6 +493,19 @@ int rtd_op_msdeform(int dtype, const void* value, const float* offaw, const floa
   });
 }
 
+int rtd_op_pool(int kind, int dtype, const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy) {
+  return op_guard([&] {
+    RTD_CHECK(kind >= 0 && kind <= 2 && ldx >= C && ldy >= C, RTD_E_INVALID, "op_pool: kind 0 max-pool, 1 avg-pool, 2 upsample; ld >= C");
+    const int OH = kind == 0 ? (H + 2 - 3) / 2 + 1 : (kind == 1 ? H / 2 : 2 * H), OW = kind == 0 ? (W + 2 - 3) / 2 + 1 : (kind == 1 ? W / 2 : 2 * W);
+    Tensor tx = mk(x, dtype, B, H, W, C), ty = mk(y, dtype, B, OH, OW, C);
+    tx.ld = ldx; tx.bstride = (int64_t)H * W * ldx;
+    ty.ld = ldy; ty.bstride = (int64_t)OH * OW * ldy;
+    if (kind == 0) launch_maxpool3x3s2(tx, ty, nullptr);
+    else if (kind == 1) launch_avgpool2(tx, ty, nullptr);
+    else launch_upsample2x(tx, ty, nullptr);
+  });
+}
+
 int rtd_op_topk(const float* keys, int B, int N, int K, int32_t* idx_out, float* val_out) {
   return op_guard([&] { launch_topk(keys, B, N, K, idx_out, val_out, nullptr); });
 }

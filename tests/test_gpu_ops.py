@@ -669,3 +669,57 @@ def test_resize_matches_pil_bit_exactly(L, size):
     got = out.cpu().numpy()
     assert (got[:, :, 3:] == 0).all()
     np.testing.assert_array_equal(got[:, :, :3], want.astype(np.float32) / np.float32(255.0))
+
+
+POOL_KIND = {"max": 0, "avg": 1, "up": 2}
+POOL_CASES = ([("max", dt, hw) for dt in ("bf16", "f16x2") for hw in ((8, 12), (7, 11))] + [("max", "f32", (6, 10))] +
+              [(kind, dt, (4, 6)) for kind in ("avg", "up") for dt in ("bf16", "f32", "f16x2")])
+
+
+@pytest.mark.parametrize("kind,dt,hw", POOL_CASES)
+def test_pools_and_upsample_exact(L, kind, dt, hw):
+    """launch_maxpool3x3s2 / launch_avgpool2 / launch_upsample2x through rtd_op_pool, bit for bit on the raw storage (uint16 for bf16 and
+    pair tensors) against torch / numpy on the CPU: max_pool2d(3, 2, 1) of the represented values (the max is one of its inputs, so
+    rounding it back reproduces that input's storage; pair tensors: one re-split), ((a0 + a1) + (a2 + a3)) * 0.25 in fp32 rounded once
+    to the storage type, and a pure copy for the upsample.  Shapes: (8, 12) -> whole 2 x 2 patches, (7, 11) -> the last patch's window
+    reaches the bottom / right padding, (6, 10) with C = 12 -> the fp32 one-output form with odd pooled extents and three chunks;
+    C = 64 = two pair groups = eight bf16 chunks; B = 2 and > 256 threads: more than one block.  Each view once dense and once as the
+    second channel half of a buffer twice as wide (ldx = ldy = 2C), whose first half must stay untouched."""
+    from telescope_cam_detection_amd import _capi
+    B, (H, W) = 2, hw
+    C_ = 12 if (kind, dt) == ("max", "f32") else 64
+    g = torch.Generator().manual_seed(7000 + POOL_CASES.index((kind, dt, hw)))
+    x = 4.0 * torch.randn(B, H, W, C_, generator=g)
+    if dt == "bf16":
+        raw = x.to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
+        val = torch.from_numpy(raw.view(np.int16)).view(torch.bfloat16).float()
+        store = lambda v: v.to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
+    elif dt == "f32":
+        raw, val = x.numpy(), x
+        store = lambda v: v.numpy()
+    else:
+        raw = _capi.to_split(x.numpy())
+        val = torch.from_numpy(_capi.from_split(raw))
+        store = lambda v: _capi.to_split(v.numpy())
+    if kind == "max":
+        want = store(F.max_pool2d(val.permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1).contiguous())
+    elif kind == "avg":
+        want = store((((val[:, 0::2, 0::2] + val[:, 0::2, 1::2]) + (val[:, 1::2, 0::2] + val[:, 1::2, 1::2])) * 0.25).contiguous())
+    else:
+        want = np.repeat(np.repeat(raw, 2, axis=1), 2, axis=2)
+    code = {"bf16": _capi.DT_BF16, "f32": _capi.DT_F32, "f16x2": _capi.DT_F16X2}[dt]
+    tdt = torch.float32 if dt == "f32" else torch.int16
+    per_c = raw.shape[-1] // C_                      # storage elements per channel (pair tensors: 2)
+    for view in ("dense", "slice"):
+        wide = 2 if view == "slice" else 1
+        xd = torch.zeros(B, H, W, wide * raw.shape[-1], dtype=tdt)
+        xd[..., (wide - 1) * raw.shape[-1]:] = torch.from_numpy(raw.view(np.int16) if dt != "f32" else raw)
+        xd = xd.cuda()
+        yd = torch.full((B,) + want.shape[1:3] + (wide * want.shape[-1],), 77, dtype=tdt, device="cuda")
+        off = (wide - 1) * C_ * per_c * xd.element_size()
+        ck(L, L.rtd_op_pool(POOL_KIND[kind], code, xd.data_ptr() + off, yd.data_ptr() + off, B, H, W, C_, wide * C_, wide * C_))
+        got = yd.cpu().numpy()
+        if dt != "f32":
+            got = got.view(np.uint16)
+        np.testing.assert_array_equal(got[..., (wide - 1) * want.shape[-1]:], want, err_msg=f"{kind} {dt} {hw} {view}")
+        assert (got[..., :(wide - 1) * want.shape[-1]] == 77).all(), "the other channel half of the output buffer was written"

@@ -95,6 +95,24 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert lib.rtd_debug_option(b"no_such_option", 1) == _capi.RTD_E_INVALID
 
 
+def test_maxpool_refuses_what_its_deleted_kernels_took():
+    """bf16 and pair tensors are pooled in 2 x 2 output patches of whole 16-byte chunks only (every plan rtd_create admits has even pooled
+    extents and C % 8 == 0): an odd pooled extent or a partial chunk is an RtdError from the launcher's checks, before any launch
+    (the placeholder pointers are never read)"""
+    from telescope_cam_detection_amd import _capi
+    lib = _capi.lib()
+    p = ctypes.c_void_p(4096)
+    for dt, C_ in ((_capi.DT_BF16, 64), (_capi.DT_F16X2, 64)):
+        rc = lib.rtd_op_pool(0, dt, p, p, 1, 6, 6, C_, C_, C_)                      # 6 x 6 -> 3 x 3
+        assert rc == _capi.RTD_E_INVALID
+        with pytest.raises(_capi.RtdError, match="even pooled extents"):
+            _capi._raise(rc, None)
+    rc = lib.rtd_op_pool(0, _capi.DT_BF16, p, p, 1, 8, 8, 12, 12, 12)                # C % 8 != 0
+    assert rc == _capi.RTD_E_INVALID
+    with pytest.raises(_capi.RtdError, match="16-byte channel chunks"):
+        _capi._raise(rc, None)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="CPU-only behaviour")
 def test_detector_fails_loudly_without_gpu():
     """the product path has no CPU fallback: load_model() -> False (never raises), detect() -> [] (reference :248-250)"""
