@@ -263,6 +263,45 @@ int rtd_jpeg_wait_stream(rtd_jpeg_handle j, void* producer_stream);   /* as rtd_
 const char* rtd_jpeg_last_error(rtd_jpeg_handle j);                  /* j may be NULL: last error of a failed rtd_jpeg_create */
 void rtd_jpeg_destroy(rtd_jpeg_handle j);
 
+/* ---- Detection overlays on device-resident frames (the reference's cv2.rectangle / cv2.putText in src/web_server.py _draw_detections
+ * and src/visualization_utils.py draw_detections) ------------------------------------------------------------------------------------------
+ * Filled rectangles, outlines and coverage masks (rasterised text) composited onto a batch of HWC uint8 frames in one launch
+ * (csrc/overlay.hip), all in integers (restated in tests/overlay_ref.py).  The primitives of a frame apply in list order, clipped to the
+ * frame:
+ *   FILL     every pixel of the inclusive rectangle (cv2.rectangle with thickness -1)
+ *   OUTLINE  with o = t / 2 and i = (t - 1) / 2: the pixels of [x1-o, x2+o] x [y1-o, y2+o] that are not strictly inside
+ *            (x1+i, x2-i) x (y1+i, y2-i): a strip exactly t pixels wide with square corners (t = 1 is cv2's outline; for t >= 2 cv2 rounds
+ *            the corners)
+ *   MASK     coverage a per pixel: out = (bg * (255 - a) + colour * a + 127) / 255 per channel, integer division
+ * One-channel frames take bgr[0].  Own handle with a non-blocking stream and a pinned staging buffer grown on demand: no device or pinned
+ * allocation on the steady path.  Calls on one handle are serialised by the handle.
+ * Limits: RTD_OVERLAY_MAX_FRAMES frames per call, RTD_OVERLAY_MAX_PRIMS primitives per frame, frames of 1..65535 pixels per side and
+ * less than 2 GiB, OUTLINE thickness 1..65535, masks of 0..65535 pixels per side.  Beyond a limit: RTD_E_INVALID, and nothing is copied
+ * or drawn. */
+enum { RTD_OVL_FILL = 0, RTD_OVL_OUTLINE = 1, RTD_OVL_MASK = 2 };
+enum { RTD_OVERLAY_MAX_FRAMES = 64, RTD_OVERLAY_MAX_PRIMS = 4096 };
+typedef struct rtd_overlay_prim { /* 40 bytes */
+  int32_t kind;
+  int32_t x1, y1, x2, y2; /* FILL / OUTLINE: opposite corners, both INCLUSIVE, in any order, may lie outside the frame.
+                             MASK: x1, y1 = where the mask's top-left pixel lands; x2, y2 = the mask's width and height */
+  int32_t thickness;      /* OUTLINE: >= 1 */
+  uint8_t bgr[3], reserved0;
+  int64_t mask_offset;    /* MASK: byte offset into `masks`; rows tightly packed */
+} rtd_overlay_prim;
+typedef struct rtd_overlay* rtd_overlay_handle;
+int rtd_overlay_create(int32_t device, rtd_overlay_handle* out);
+/* n frames (HWC uint8, C = 1 or 3 = BGR; host or device pointers), prim_counts[i] primitives for frame i, back to back in prims;
+ * masks = HOST memory of mask_bytes bytes (copied into the call).  out_dev[i] is device memory of the caller with room for the frame; it
+ * may equal frames[i] for a device frame (drawn in place); otherwise the frame is first copied there (one device-to-device copy, or one
+ * DMA from the staging buffer for a host frame).  Two frames of a call must not share out_dev memory.  Synchronous: returns when every
+ * out_dev[i] holds its annotated frame. */
+int rtd_overlay_draw(rtd_overlay_handle o, int32_t n, const uint8_t* const* frames, const int32_t* hwc /* [n][3] */,
+                     int32_t frames_on_device, const int32_t* prim_counts /* [n] */, const rtd_overlay_prim* prims,
+                     const uint8_t* masks, int64_t mask_bytes, uint8_t* const* out_dev /* [n] */);
+int rtd_overlay_wait_stream(rtd_overlay_handle o, void* producer_stream);   /* as rtd_wait_stream */
+const char* rtd_overlay_last_error(rtd_overlay_handle o);                  /* o may be NULL: last error of a failed rtd_overlay_create */
+void rtd_overlay_destroy(rtd_overlay_handle o);
+
 #ifdef __cplusplus
 }
 #endif

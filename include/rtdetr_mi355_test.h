@@ -118,6 +118,10 @@ int rtd_debug_mog2_fg_bits(rtd_mog2_handle g, uint32_t* out, size_t nwords);
  * coefficients).  *count receives the number of int16 values; out may be NULL to ask for it.  csrc/jpeg.hip. */
 int rtd_debug_jpeg_coefficients(rtd_jpeg_handle j, int16_t* out, int64_t capacity, int64_t* count);
 
+/* the tile of the overlay kernel (pixels) and the number of tiles the last rtd_overlay_draw launched (one workgroup each; 0 after a
+ * failed call): what tests/overlay_ref.py tiles_touched predicts.  Any pointer may be NULL.  csrc/overlay.hip. */
+int rtd_debug_overlay_tiles(rtd_overlay_handle o, int32_t* tile_h, int32_t* tile_w, int64_t* tiles);
+
 #ifdef __cplusplus
 }
 #endif

@@ -108,13 +108,14 @@ EXPORTS = [
     "rtd_motion_create", "rtd_motion_check", "rtd_motion_reset", "rtd_motion_wait_stream", "rtd_motion_last_error", "rtd_motion_destroy",
     "rtd_mog2_create", "rtd_mog2_configure", "rtd_mog2_apply", "rtd_mog2_wait_stream", "rtd_mog2_last_error", "rtd_mog2_destroy",
     "rtd_jpeg_create", "rtd_jpeg_encode", "rtd_jpeg_wait_stream", "rtd_jpeg_last_error", "rtd_jpeg_destroy",
+    "rtd_overlay_create", "rtd_overlay_draw", "rtd_overlay_wait_stream", "rtd_overlay_last_error", "rtd_overlay_destroy",
 ]
 # every symbol include/rtdetr_mi355_test.h declares: kernel-level test / bench / debug entry points (csrc/testapi.hip)
 TEST_EXPORTS = [
     "rtd_debug_tensor", "rtd_debug_force_topk", "rtd_profile", "rtd_debug_option", "rtd_op_conv", "rtd_op_conv_dual", "rtd_op_conv_next",
     "rtd_op_layernorm", "rtd_op_attention", "rtd_op_msdeform", "rtd_op_topk", "rtd_op_resize", "rtd_op_pool", "rtd_bench_conv", "rtd_bench_conv_pair",
     "rtd_bench_mfma_rate", "rtd_debug_motion_state", "rtd_debug_mog2_model", "rtd_debug_mog2_fg_bits",
-    "rtd_debug_jpeg_coefficients",
+    "rtd_debug_jpeg_coefficients", "rtd_debug_overlay_tiles",
 ]
 
 
@@ -219,6 +220,15 @@ def lib() -> C.CDLL:
         L.rtd_jpeg_destroy.argtypes = [vp]
         L.rtd_jpeg_destroy.restype = None
         L.rtd_debug_jpeg_coefficients.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    if hasattr(L, "rtd_overlay_create"):       # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_overlay_create.argtypes = [i32, C.POINTER(vp)]
+        L.rtd_overlay_draw.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), i32, C.POINTER(i32), vp, vp, i64, C.POINTER(vp)]
+        L.rtd_overlay_wait_stream.argtypes = [vp, vp]
+        L.rtd_overlay_last_error.argtypes = [vp]
+        L.rtd_overlay_last_error.restype = C.c_char_p
+        L.rtd_overlay_destroy.argtypes = [vp]
+        L.rtd_overlay_destroy.restype = None
+        L.rtd_debug_overlay_tiles.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
     _lib = L
     return L
 
