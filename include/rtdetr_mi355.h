@@ -302,6 +302,42 @@ int rtd_overlay_wait_stream(rtd_overlay_handle o, void* producer_stream);   /* a
 const char* rtd_overlay_last_error(rtd_overlay_handle o);                  /* o may be NULL: last error of a failed rtd_overlay_create */
 void rtd_overlay_destroy(rtd_overlay_handle o);
 
+/* ---- Stage-2 crop enhancement on device-resident frames (the reference's ImageEnhancer.enhance_clahe_bilateral in
+ * src/image_enhancement.py, enhancement method "clahe") -----------------------------------------------------------------------------------
+ * Per crop (3-channel BGR): cv2.cvtColor(BGR2LAB) on OpenCV's 8-bit integer path, CLAHE(clip_limit, tiles_x x tiles_y) on L,
+ * Lab -> BGR by this library's own integer tables, cv2.bilateralFilter(bilateral_d, sigma_color, sigma_space) with BORDER_REFLECT_101 of
+ * the CROP (not of the frame around it).  The arithmetic is restated in tests/enhance_ref.py and matched bit for bit: tables from double
+ * precision on the host, integers per pixel, fp32 in a fixed order for the CLAHE interpolation and the bilateral sums.  Three launches
+ * per call, each over all crops (csrc/enhance.hip).
+ * The handle owns the tables (built and uploaded at create) and the scratch (a Lab plane, the tile LUTs, a second BGR plane), which is
+ * grown on demand: nothing is allocated on the steady path.  It owns NO stream: rtd_enhance_crops is ASYNCHRONOUS on the caller's
+ * `stream`, exactly as rtd_crop_resize_batch, so a consumer on the same stream needs no synchronisation; frames and out_dev must stay
+ * alive until the stream has passed the call (the rectangles and sizes are copied into the launches before it returns).  The scratch
+ * belongs to the call in flight: calls on one handle must be enqueued on ONE stream, or be ordered by the caller.
+ * Limits: tiles 1..16 per axis, bilateral radius (d / 2; for d <= 0 rint(1.5 sigma_space)) 1..7, 1..64 crops per call, every crop at
+ * least 16 pixels per side and inside its frame.  Anything else: RTD_E_INVALID, nothing is launched and out_dev is left untouched.
+ * clip_limit <= 0 disables clipping; sigmas <= 0 become 1. */
+typedef struct rtd_enhance_params {
+  int32_t struct_size; /* = sizeof(rtd_enhance_params) */
+  float clip_limit;
+  int32_t tiles_x, tiles_y;
+  int32_t bilateral_d;
+  float sigma_color, sigma_space;
+} rtd_enhance_params;
+typedef struct rtd_enhance* rtd_enhance_handle;
+int rtd_enhance_create(int32_t device, const rtd_enhance_params* params, rtd_enhance_handle* out);
+/* Where the crops of a call lie in its output: THE packing rule, pure host arithmetic (no GPU, no handle).  rects = [n][4] x1, y1, x2, y2;
+ * offsets[n + 1]: crop i is h x w x 3 (HWC, rows tightly packed) at byte offsets[i], which is a multiple of 256; offsets[n] is the size
+ * the output needs.  n >= 0 (no upper limit here: offsets[k] of a long list is where a call on rects k.. of it writes, relative to
+ * offsets[k]).  RTD_E_INVALID for a rect with a negative corner or fewer than 16 pixels per side. */
+int rtd_enhance_layout(int32_t n, const int32_t* rects, int64_t* offsets /* [n + 1] */);
+/* crop i = frames_dev[i][y1:y2, x1:x2] of an HWC uint8 BGR frame of frame_hw[i] = (h, w); the enhanced crops go to out_dev (device
+ * memory of out_cap >= offsets[n] bytes) where rtd_enhance_layout says. */
+int rtd_enhance_crops(rtd_enhance_handle e, int32_t n, const uint8_t* const* frames_dev, const int32_t* frame_hw /* [n][2] */,
+                      const int32_t* rects /* [n][4] */, uint8_t* out_dev, int64_t out_cap, void* stream);
+const char* rtd_enhance_last_error(rtd_enhance_handle e);                  /* e may be NULL: last error of a failed create / layout */
+void rtd_enhance_destroy(rtd_enhance_handle e);
+
 #ifdef __cplusplus
 }
 #endif

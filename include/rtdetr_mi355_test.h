@@ -122,6 +122,11 @@ int rtd_debug_jpeg_coefficients(rtd_jpeg_handle j, int16_t* out, int64_t capacit
  * failed call): what tests/overlay_ref.py tiles_touched predicts.  Any pointer may be NULL.  csrc/overlay.hip. */
 int rtd_debug_overlay_tiles(rtd_overlay_handle o, int32_t* tile_h, int32_t* tile_w, int64_t* tiles);
 
+/* a piece of the scratch the last rtd_enhance_crops left behind, copied to the host after synchronising with that call's stream:
+ * stage 0 = the crop's Lab plane (h x w x 3), 1 = its tile LUTs (tiles_y x tiles_x x 256), 2 = its BGR plane before the bilateral
+ * filter (h x w x 3): what tests/enhance_ref.py stages() returns.  nbytes must be the piece's size.  csrc/enhance.hip. */
+int rtd_debug_enhance_stage(rtd_enhance_handle e, int32_t crop, int32_t stage, uint8_t* out, size_t nbytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -96,6 +96,11 @@ class RtdLayerTime(C.Structure):
                 ("bytes", C.c_double)]
 
 
+class RtdEnhanceParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("clip_limit", C.c_float), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32),
+                ("bilateral_d", C.c_int32), ("sigma_color", C.c_float), ("sigma_space", C.c_float)]
+
+
 DET_DTYPE = np.dtype([("class_id", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 
 _lib: Optional[C.CDLL] = None
@@ -109,13 +114,14 @@ EXPORTS = [
     "rtd_mog2_create", "rtd_mog2_configure", "rtd_mog2_apply", "rtd_mog2_wait_stream", "rtd_mog2_last_error", "rtd_mog2_destroy",
     "rtd_jpeg_create", "rtd_jpeg_encode", "rtd_jpeg_wait_stream", "rtd_jpeg_last_error", "rtd_jpeg_destroy",
     "rtd_overlay_create", "rtd_overlay_draw", "rtd_overlay_wait_stream", "rtd_overlay_last_error", "rtd_overlay_destroy",
+    "rtd_enhance_create", "rtd_enhance_layout", "rtd_enhance_crops", "rtd_enhance_last_error", "rtd_enhance_destroy",
 ]
 # every symbol include/rtdetr_mi355_test.h declares: kernel-level test / bench / debug entry points (csrc/testapi.hip)
 TEST_EXPORTS = [
     "rtd_debug_tensor", "rtd_debug_force_topk", "rtd_profile", "rtd_debug_option", "rtd_op_conv", "rtd_op_conv_dual", "rtd_op_conv_next",
     "rtd_op_layernorm", "rtd_op_attention", "rtd_op_msdeform", "rtd_op_topk", "rtd_op_resize", "rtd_op_pool", "rtd_bench_conv", "rtd_bench_conv_pair",
     "rtd_bench_mfma_rate", "rtd_debug_motion_state", "rtd_debug_mog2_model", "rtd_debug_mog2_fg_bits",
-    "rtd_debug_jpeg_coefficients", "rtd_debug_overlay_tiles",
+    "rtd_debug_jpeg_coefficients", "rtd_debug_overlay_tiles", "rtd_debug_enhance_stage",
 ]
 
 
@@ -229,6 +235,15 @@ def lib() -> C.CDLL:
         L.rtd_overlay_destroy.argtypes = [vp]
         L.rtd_overlay_destroy.restype = None
         L.rtd_debug_overlay_tiles.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
+    if hasattr(L, "rtd_enhance_create"):       # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_enhance_create.argtypes = [i32, C.POINTER(RtdEnhanceParams), C.POINTER(vp)]
+        L.rtd_enhance_layout.argtypes = [i32, C.POINTER(i32), C.POINTER(i64)]
+        L.rtd_enhance_crops.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), vp, i64, vp]
+        L.rtd_enhance_last_error.argtypes = [vp]
+        L.rtd_enhance_last_error.restype = C.c_char_p
+        L.rtd_enhance_destroy.argtypes = [vp]
+        L.rtd_enhance_destroy.restype = None
+        L.rtd_debug_enhance_stage.argtypes = [vp, i32, i32, vp, C.c_size_t]
     _lib = L
     return L
 

@@ -76,12 +76,17 @@ class CropBatcher:
 
     MAX_CROPS_PER_LAUNCH = 64        # rtd_crop_resize_batch's limit (include/rtdetr_mi355.h)
 
-    def preprocess_batch(self, frames, rects_per_frame):
+    def preprocess_batch(self, frames, rects_per_frame, enhancer=None):
         """frames: list of device uint8 HWC tensors; rects_per_frame: list (per frame) of (x1,y1,x2,y2) lists.
-        Returns a [N, 3, S, S] fp32 torch tensor on the frames' device (N = total number of crops)."""
+        Returns a [N, 3, S, S] fp32 torch tensor on the frames' device (N = total number of crops).
+        enhancer (enhance.CropEnhancer): every crop is enhanced first (CLAHE + bilateral, on the same stream) and the crop launch
+        reads the enhanced crops - each one a whole "frame" of its own size - instead of the frame slices."""
         import torch
 
         flat = [(f, r) for f, rects in zip(frames, rects_per_frame) for r in rects]
+        if enhancer is not None and flat:
+            buf, offsets, shapes = enhancer.enhance(frames, rects_per_frame)       # buf stays referenced by the views until the launches are enqueued
+            flat = [(buf[o:o + h * w * 3].view(h, w, 3), (0, 0, w, h)) for o, (h, w) in zip(offsets, shapes)]
         n = len(flat)
         dev = frames[0].device if frames else torch.device("cuda", 0)
         S = self.input_size
@@ -147,11 +152,20 @@ class BatchedStage2:
     """Batched stand-in for `TwoStageDetectionPipeline.process_detections`.  `pipeline` is the reference pipeline object (or
     anything with its attributes: enable_species_classification, class_id_to_category, species_classifiers, min_crop_size,
     crop_padding_percent, rejected_taxonomic_levels, time_of_day_top_k, time_of_day_penalty, enhancer); its classifiers need
-    `.model` (callable on a [N,3,S,S] batch) plus the attributes `format_predictions` reads.  Pipelines with an image enhancer
-    (Real-ESRGAN, ~1 s per crop) keep the reference's own per-detection path."""
+    `.model` (callable on a [N,3,S,S] batch) plus the attributes `format_predictions` reads.
+    enhancer: None (default) - pipelines with an image enhancer keep the reference's own per-detection path; "auto" - the pipeline's
+    `ImageEnhancer` is replaced by the device enhancer when `enhance.CropEnhancer.from_reference` can stand in for it (method "clahe"
+    within the library's limits; Real-ESRGAN, ~1 s per crop, keeps the per-detection path); a `CropEnhancer` - used as given.  On the
+    enhanced batched path the reference's LRU cache of enhanced crops and its hit counters are left alone."""
 
-    def __init__(self, pipeline, batcher: Optional[CropBatcher] = None, activity_fn=None):
+    def __init__(self, pipeline, batcher: Optional[CropBatcher] = None, activity_fn=None, enhancer=None):
         self.pipeline = pipeline
+        if isinstance(enhancer, str):
+            if enhancer != "auto":
+                raise ValueError(f"enhancer must be None, 'auto' or a CropEnhancer, not {enhancer!r}")
+            from .enhance import CropEnhancer
+            enhancer = CropEnhancer.from_reference(getattr(pipeline, "enhancer", None), pipeline.min_crop_size)
+        self.enhancer = enhancer
         self.batcher = batcher or CropBatcher(min_crop_size=pipeline.min_crop_size, crop_padding_percent=pipeline.crop_padding_percent)
         if activity_fn is None:
             try:
@@ -207,7 +221,7 @@ class BatchedStage2:
                     d["species"] = None
                     d["species_confidence"] = 0.0
             return detections_per_frame
-        if getattr(p, "enhancer", None) is not None:
+        if getattr(p, "enhancer", None) is not None and self.enhancer is None:
             return [p.process_detections(f, dets) for f, dets in zip(frames, detections_per_frame)]
         jobs = []                                                  # (frame index, detection, category, rect)
         for fi, (f, dets) in enumerate(zip(frames, detections_per_frame)):
@@ -232,7 +246,10 @@ class BatchedStage2:
         for j, (fi, _, _, rect) in enumerate(jobs):
             rects_per_frame[fi].append(rect)
             order[fi].append(j)
-        batch = self.batcher.preprocess_batch(frames, rects_per_frame)          # [N,3,S,S], crops in frame-major order
+        if self.enhancer is not None:
+            batch = self.batcher.preprocess_batch(frames, rects_per_frame, enhancer=self.enhancer)
+        else:
+            batch = self.batcher.preprocess_batch(frames, rects_per_frame)      # [N,3,S,S], crops in frame-major order
         row_of = {j: r for r, j in enumerate(j for per in order for j in per)}
         by_cat: Dict[str, List[int]] = {}
         for j, (_, _, category, _) in enumerate(jobs):
@@ -260,6 +277,15 @@ class BatchedStage2:
                 share = (time.perf_counter() - t_fwd) * 1000.0 / len(js)
                 for _ in js:
                     times.append(share)
+        # `enhancement_times` (milliseconds per enhanced crop in the reference, src/two_stage_pipeline_yolox.py:318-321): every crop
+        # books its share of the enhancement launches' device time (read after the forwards, so the wait is over already)
+        etimes = getattr(p, "enhancement_times", None)
+        last_ms = getattr(self.enhancer, "last_call_ms", None)
+        if etimes is not None and last_ms is not None:
+            ms = last_ms()
+            if ms is not None:
+                for _ in jobs:
+                    etimes.append(ms / len(jobs))
         return detections_per_frame
 
     def process_detections(self, frame, detections):
