@@ -338,6 +338,42 @@ int rtd_enhance_crops(rtd_enhance_handle e, int32_t n, const uint8_t* const* fra
 const char* rtd_enhance_last_error(rtd_enhance_handle e);                  /* e may be NULL: last error of a failed create / layout */
 void rtd_enhance_destroy(rtd_enhance_handle e);
 
+/* ---- Real-ESRGAN x4 upscaling of Stage-2 crops on device-resident frames (the reference's ImageEnhancer method "realesrgan",
+ * src/image_enhancement.py: RealESRGANer.enhance(outscale 4) around RRDBNet(3, 3, 64, num_block, 32, scale 4)) -------------------------
+ * Per crop (3-channel BGR): float32(v) / 255, BGR -> RGB, the network on the whole crop (tile = 0) or tile by tile (the core of a tile
+ * extended by tile_pad and clamped to the crop goes through the network, the core's x4 image is cut out), clamp(0, 1), RGB -> BGR,
+ * round half to even of x * 255.  The arithmetic is restated in tests/esrgan_ref.py; the network's 15 num_block + 6 convolutions run on
+ * the library's conv kernels in the handle's precision: RTD_PREC_F16X3 (fp16 hi + lo pairs) or RTD_PREC_FP32.  RTD_PREC_BF16 is refused
+ * (it changes a third of the output bytes).  csrc/esrgan.hip.
+ * blob = the container rtd_load_weights reads, holding the state dict's tensors under their own names (`conv_first.weight` [64][3][3][3],
+ * `body.<i>.rdb<j>.conv<k>.weight`, ... `.bias`; OIHW fp32).  A missing or mis-shaped tensor, a NaN / Inf and - pair engine - a value
+ * beyond 65504 return RTD_E_WEIGHTS with the tensor's name.
+ * The handle owns the filters and one arena (the activations of the largest tile shape seen, and the conv kernels' split-K workspace);
+ * a repeated shape allocates nothing.  It owns NO stream: rtd_esrgan_upscale is ASYNCHRONOUS on the caller's `stream`, exactly as
+ * rtd_enhance_crops; crops are processed one after another, tile by tile; calls on one handle go on ONE stream.
+ * Limits: 1..64 crops per call, every crop 8..4096 pixels per side and inside its frame; with tile = 0 a crop side is at most 576.
+ * Anything else: RTD_E_INVALID before anything is launched, out_dev untouched.  Arena exhaustion: RTD_E_OOM. */
+typedef struct rtd_esrgan_config {
+  int32_t struct_size; /* = sizeof(rtd_esrgan_config) */
+  int32_t device;
+  int32_t precision;   /* RTD_PREC_F16X3 | RTD_PREC_FP32 */
+  int32_t num_feat;    /* 64 */
+  int32_t num_grow_ch; /* 32 */
+  int32_t num_block;   /* 1..32 */
+  int32_t tile;        /* 0 (one pass) or 16..512 */
+  int32_t tile_pad;    /* 0..32 */
+} rtd_esrgan_config;
+typedef struct rtd_esrgan* rtd_esrgan_handle;
+int rtd_esrgan_create(const rtd_esrgan_config* cfg, const void* blob, size_t nbytes, rtd_esrgan_handle* out);
+/* pure host arithmetic: rects = [n][4] x1, y1, x2, y2; crop i is 4h x 4w x 3 (HWC, rows tightly packed) at byte offsets[i], a multiple
+ * of 256; offsets[n] is the size the output needs.  RTD_E_INVALID for a negative corner or a side outside 8..4096. */
+int rtd_esrgan_layout(int32_t n, const int32_t* rects, int64_t* offsets /* [n + 1] */);
+int rtd_esrgan_upscale(rtd_esrgan_handle e, int32_t n, const uint8_t* const* frames_dev, const int32_t* frame_hw /* [n][2] */,
+                       const int32_t* rects /* [n][4] */, uint8_t* out_dev, int64_t out_cap, void* stream);
+int64_t rtd_esrgan_arena_bytes(rtd_esrgan_handle e);
+const char* rtd_esrgan_last_error(rtd_esrgan_handle e);                    /* e may be NULL: last error of a failed create / layout */
+void rtd_esrgan_destroy(rtd_esrgan_handle e);
+
 #ifdef __cplusplus
 }
 #endif

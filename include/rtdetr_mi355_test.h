@@ -64,6 +64,11 @@ int rtd_debug_option(const char* name, int value);
 int rtd_op_conv(int dtype, const void* x, const void* w_ohwi_f32, const float* bias, const void* res,
                 void* y, int B, int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad,
                 int act, int res_mode, int out_f32);
+/* ... on channel-slice views: x, y and res are [B, H, W, .] with pixel strides ldx >= Cin, ldy >= Cout, ldres >= Cout (in channels),
+ * images dense - how a dense block reads the prefix of a wider buffer and writes its channels behind it.  act: 0 none, 1 ReLU, 2 SiLU,
+ * 3 GELU, 4 LeakyReLU(0.2) (rtd_op_conv too). */
+int rtd_op_conv_view(int dtype, const void* x, int ldx, const void* w_ohwi_f32, const float* bias, const void* res, int ldres,
+                     void* y, int ldy, int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad, int act, int res_mode);
 /* conv with a second input x2 [B,OH,OW,C2] read as an extra 1x1 tap at output resolution; w_f32 = [Cout][KH*KH*Cin + C2]
  * (how the plan folds a bottleneck's projection shortcut into its last conv).  x_up2 = 1 (1x1 only): x is [B,H/2,W/2,Cin] and is
  * read through a nearest 2x upsampling, H and W being the output extents (the FPN's conv over cat([upsample(lat), proj])). */
@@ -94,6 +99,9 @@ int rtd_op_resize(const uint8_t* src, int sh, int sw, void* dst, int dh, int dw,
 int rtd_bench_conv_pair(const int* shape_a, const int* shape_b, int reps, float* us_out);
 int rtd_bench_conv(int dtype, int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad, int with_res,
                    int reps, int flush_mb, float* us_out);
+/* ... with the epilogue's activation as an argument (rtd_bench_conv runs ReLU) */
+int rtd_bench_conv_act(int dtype, int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad, int with_res, int act,
+                       int reps, int flush_mb, float* us_out);
 
 /* What the matrix pipes of THIS device sustain (tools/mfma_rate_probe.hip inside the library; bench.py reports it beside `roofline`):
  * v_mfma_f32_16x16x32_f16 back to back on every CU, operands in registers, `random_operands` 0 = all-zero bits / 1 = random finite fp16
@@ -126,6 +134,12 @@ int rtd_debug_overlay_tiles(rtd_overlay_handle o, int32_t* tile_h, int32_t* tile
  * stage 0 = the crop's Lab plane (h x w x 3), 1 = its tile LUTs (tiles_y x tiles_x x 256), 2 = its BGR plane before the bilateral
  * filter (h x w x 3): what tests/enhance_ref.py stages() returns.  nbytes must be the piece's size.  csrc/enhance.hip. */
 int rtd_debug_enhance_stage(rtd_enhance_handle e, int32_t crop, int32_t stage, uint8_t* out, size_t nbytes);
+
+/* a float stage output of the LAST TILE of the last rtd_esrgan_upscale, [1, h, w, c] fp32: `ingest` and `last` (32 channels: RGB in
+ * 0..2, the padding above), `first`, `body.<i>.rdb<j>` (the 64-channel block output), `body.<i>`, `trunk`, `up1`, `up2`, `hr` (after
+ * its LeakyReLU).  The plan reuses its buffers, so the tile is run again up to that stage on the call's stream (the frame must still
+ * be alive).  out may be NULL to ask for the shape.  csrc/esrgan.hip. */
+int rtd_debug_esrgan_tensor(rtd_esrgan_handle e, const char* name, float* out, int64_t capacity, int64_t shape[4]);
 
 #ifdef __cplusplus
 }

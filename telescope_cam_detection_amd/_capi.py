@@ -57,7 +57,7 @@ def from_split(s: np.ndarray) -> np.ndarray:
     return np.ascontiguousarray((f[..., 0, :] + f[..., 1, :]).reshape(s.shape[:-1] + (C_,)))
 
 
-ACT = {"none": 0, "relu": 1, "silu": 2, "gelu": 3}
+ACT = {"none": 0, "relu": 1, "silu": 2, "gelu": 3, "lrelu": 4}
 
 
 class RtdConfig(C.Structure):
@@ -101,6 +101,11 @@ class RtdEnhanceParams(C.Structure):
                 ("bilateral_d", C.c_int32), ("sigma_color", C.c_float), ("sigma_space", C.c_float)]
 
 
+class RtdEsrganConfig(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("device", C.c_int32), ("precision", C.c_int32), ("num_feat", C.c_int32),
+                ("num_grow_ch", C.c_int32), ("num_block", C.c_int32), ("tile", C.c_int32), ("tile_pad", C.c_int32)]
+
+
 DET_DTYPE = np.dtype([("class_id", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 
 _lib: Optional[C.CDLL] = None
@@ -115,6 +120,7 @@ EXPORTS = [
     "rtd_jpeg_create", "rtd_jpeg_encode", "rtd_jpeg_wait_stream", "rtd_jpeg_last_error", "rtd_jpeg_destroy",
     "rtd_overlay_create", "rtd_overlay_draw", "rtd_overlay_wait_stream", "rtd_overlay_last_error", "rtd_overlay_destroy",
     "rtd_enhance_create", "rtd_enhance_layout", "rtd_enhance_crops", "rtd_enhance_last_error", "rtd_enhance_destroy",
+    "rtd_esrgan_create", "rtd_esrgan_layout", "rtd_esrgan_upscale", "rtd_esrgan_arena_bytes", "rtd_esrgan_last_error", "rtd_esrgan_destroy",
 ]
 # every symbol include/rtdetr_mi355_test.h declares: kernel-level test / bench / debug entry points (csrc/testapi.hip)
 TEST_EXPORTS = [
@@ -122,6 +128,7 @@ TEST_EXPORTS = [
     "rtd_op_layernorm", "rtd_op_attention", "rtd_op_msdeform", "rtd_op_topk", "rtd_op_resize", "rtd_op_pool", "rtd_bench_conv", "rtd_bench_conv_pair",
     "rtd_bench_mfma_rate", "rtd_debug_motion_state", "rtd_debug_mog2_model", "rtd_debug_mog2_fg_bits",
     "rtd_debug_jpeg_coefficients", "rtd_debug_overlay_tiles", "rtd_debug_enhance_stage",
+    "rtd_op_conv_view", "rtd_bench_conv_act", "rtd_debug_esrgan_tensor",
 ]
 
 
@@ -244,6 +251,19 @@ def lib() -> C.CDLL:
         L.rtd_enhance_destroy.argtypes = [vp]
         L.rtd_enhance_destroy.restype = None
         L.rtd_debug_enhance_stage.argtypes = [vp, i32, i32, vp, C.c_size_t]
+    if hasattr(L, "rtd_esrgan_create"):        # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_esrgan_create.argtypes = [C.POINTER(RtdEsrganConfig), vp, C.c_size_t, C.POINTER(vp)]
+        L.rtd_esrgan_layout.argtypes = [i32, C.POINTER(i32), C.POINTER(i64)]
+        L.rtd_esrgan_upscale.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), C.POINTER(i32), vp, i64, vp]
+        L.rtd_esrgan_arena_bytes.argtypes = [vp]
+        L.rtd_esrgan_arena_bytes.restype = i64
+        L.rtd_esrgan_last_error.argtypes = [vp]
+        L.rtd_esrgan_last_error.restype = C.c_char_p
+        L.rtd_esrgan_destroy.argtypes = [vp]
+        L.rtd_esrgan_destroy.restype = None
+        L.rtd_debug_esrgan_tensor.argtypes = [vp, C.c_char_p, vp, i64, C.POINTER(i64)]
+        L.rtd_op_conv_view.argtypes = [i32, vp, i32, vp, vp, vp, i32, vp, i32] + [i32] * 10
+        L.rtd_bench_conv_act.argtypes = [i32] * 13 + [C.POINTER(f32)]
     _lib = L
     return L
 

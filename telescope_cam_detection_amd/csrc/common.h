@@ -20,7 +20,7 @@ namespace rtd {
 // (rtd_config.precision = RTD_PREC_F16X3: fp32-grade products at 3/16 of the fp32 MFMA cost).
 enum DType : int { BF16 = 0, F32 = 1, U8 = 2, I32 = 3, F16X2 = 4 };
 constexpr int SPLIT_GROUP = 32;   // channels per [hi | lo] group of a F16X2 tensor
-enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_GELU = 3 };
+enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_GELU = 3, ACT_LRELU = 4 /* v >= 0 ? v : 0.2 v (RRDBNet) */ };
 enum ResMode : int { RES_NONE = 0, RES_PRE = 1, RES_POST = 2 };
 
 inline size_t dtype_size(int dt) { return dt == BF16 ? 2 : (dt == U8 ? 1 : 4); }
@@ -224,6 +224,8 @@ void launch_layernorm(const Tensor& x, const Tensor* res, const float* g, const 
                       float eps, hipStream_t s);
 // y = a + b (b broadcast over batch when b.n == 1)
 void launch_add(const Tensor& a, const Tensor& b, const Tensor& y, hipStream_t s);
+// y = alpha * a + b on channel-slice views (fp32 or pair tensors; y may alias a or b)
+void launch_axpby(float alpha, const Tensor& a, const Tensor& b, const Tensor& y, hipStream_t s);
 void launch_maxpool3x3s2(const Tensor& x, const Tensor& y, hipStream_t s);
 void launch_upsample2x(const Tensor& x, const Tensor& y, hipStream_t s);
 void launch_avgpool2(const Tensor& x, const Tensor& y, hipStream_t s);

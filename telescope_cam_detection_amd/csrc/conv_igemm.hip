@@ -85,6 +85,7 @@ template <int ACT> __device__ __forceinline__ float act_c(float v) {
   if (ACT == ACT_RELU) return fmaxf(v, 0.f);
   if (ACT == ACT_SILU) return v / (1.f + __expf(-v));
   if (ACT == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
+  if (ACT == ACT_LRELU) return v >= 0.f ? v : v * 0.2f;
   return v;
 }
 template <typename F> __device__ __forceinline__ void dispatch_act(int act, F&& f) {
@@ -92,6 +93,7 @@ template <typename F> __device__ __forceinline__ void dispatch_act(int act, F&& 
     case ACT_RELU: f(ActC<ACT_RELU>{}); break;
     case ACT_SILU: f(ActC<ACT_SILU>{}); break;
     case ACT_GELU: f(ActC<ACT_GELU>{}); break;
+    case ACT_LRELU: f(ActC<ACT_LRELU>{}); break;
     default: f(ActC<ACT_NONE>{}); break;
   }
 }
@@ -99,6 +101,7 @@ __device__ __forceinline__ float act_fn(float v, int act) {
   if (act == ACT_RELU) return fmaxf(v, 0.f);
   if (act == ACT_SILU) return v / (1.f + __expf(-v));
   if (act == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
+  if (act == ACT_LRELU) return v >= 0.f ? v : v * 0.2f;
   return v;
 }
 

@@ -233,6 +233,35 @@ void launch_add(const Tensor& a, const Tensor& b, const Tensor& y, hipStream_t s
   }); }); });
 }
 
+// ------------------------------------------------------------------------------------------ y = alpha * a + b
+// The tail of an RRDB (RRDBNet: `rdb3(rdb2(rdb1(x))) * 0.2 + x`) on channel-slice views of fp32 or pair tensors; one Chunk<T> per
+// thread, y may be a or b (every thread reads its own chunk before it writes it).
+template <typename T>
+__global__ void k_axpby(float alpha, const T* __restrict__ a, int64_t lda, const T* b, int64_t ldb, T* y, int64_t ldy, int64_t pixels, int C) {
+  constexpr int N = Chunk<T>::N;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int cn = C / N;
+  if (i >= pixels * cn) return;
+  const int64_t p = i / cn;
+  const int c = (int)(i - p * cn) * N;
+  float va[N], vb[N];
+  Chunk<T>::load(a, p * lda, c, va);
+  Chunk<T>::load(b, p * ldb, c, vb);
+#pragma unroll
+  for (int k = 0; k < N; ++k) vb[k] = alpha * va[k] + vb[k];
+  Chunk<T>::store(y, p * ldy, c, vb);
+}
+void launch_axpby(float alpha, const Tensor& a, const Tensor& b, const Tensor& y, hipStream_t s) {
+  RTD_CHECK((a.dt == F32 || a.dt == F16X2) && b.dt == a.dt && y.dt == a.dt, 1, "axpby: fp32 or pair tensors of one type");
+  RTD_CHECK(a.c == b.c && a.c == y.c && a.pixels() == b.pixels() && a.pixels() == y.pixels(), 1, "axpby: shape");
+  RTD_CHECK(dense(a) && dense(b) && dense(y), 1, "axpby: dense images");
+  RTD_CHECK(chunk_rows(a) && chunk_rows(b) && chunk_rows(y), 1, "axpby: whole 16-byte channel chunks (fp32: C % 4, pair tensors: C % 32) in 16-byte aligned rows");
+  with_act_dtype(a.dt, [&](auto t) {
+    typedef type_of<decltype(t)> T;
+    launch_1d(k_axpby<T>, a.pixels() * (a.c / Chunk<T>::N), s, alpha, (const T*)a.p, a.ld, (const T*)b.p, b.ld, (T*)y.p, y.ld, a.pixels(), a.c);
+  });
+}
+
 // ------------------------------------------------------------------------------------------ max-pool 3x3 s2 p1
 // HF:rt_detr_resnet.py:103 nn.MaxPool2d(3, 2, 1); padding counts as -inf.  A thread owns one Chunk<T> of channels of a PATCH x PATCH
 // output patch and reads the patch's (2 PATCH + 1)^2 input window once.

@@ -274,6 +274,30 @@ int rtd_op_conv(int dtype, const void* x, const void* w_ohwi_f32, const float* b
   return op_conv_impl(dtype, x, nullptr, 0, w_ohwi_f32, bias, res, y, B, H, W, Cin, Cout, KH, KW, stride, pad, act, res_mode, out_f32);
 }
 
+int rtd_op_conv_view(int dtype, const void* x, int ldx, const void* w_ohwi_f32, const float* bias, const void* res, int ldres, void* y, int ldy,
+                     int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad, int act, int res_mode) {
+  return op_guard([&] {
+    RTD_CHECK(x && y && w_ohwi_f32 && bias && ldx >= Cin && ldy >= Cout && (!res || ldres >= Cout), RTD_E_INVALID, "conv view: arguments");
+    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KH) / stride + 1;
+    DevFilter f = dev_filter(dtype, w_ohwi_f32, bias, Cout, KH * KH * Cin);
+    auto view = [&](const void* p, int h, int w, int c, int ld) { Tensor t = mk(p, dtype, B, h, w, c); t.ld = ld; t.bstride = (int64_t)h * w * ld; return t; };
+    ConvArgs a;
+    a.x = view(x, H, W, Cin, ldx);
+    a.y = view(y, OH, OW, Cout, ldy);
+    a.w = f.w; a.bias = f.bias; a.KH = a.KW = KH; a.stride = stride; a.pad = pad; a.Kpad = f.Kpad; a.Npad = f.Npad;
+    a.act = act; a.res_mode = res ? res_mode : RES_NONE;
+    if (res) a.res = view(res, OH, OW, Cout, ldres);
+    ConvWorkspace ws;
+    ws.slab_bytes = conv_split_slab_bytes(a);
+    if (ws.slab_bytes) HIP_CHECK(hipMalloc((void**)&ws.slab, ws.slab_bytes));
+    a.ws = ws;
+    launch_conv(a, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+    if (ws.slab) (void)hipFree(ws.slab);
+    f.release();
+  });
+}
+
 int rtd_op_conv_dual(int dtype, const void* x, const void* x2, const void* w_f32, const float* bias, const void* res, void* y, int B,
                      int H, int W, int Cin, int C2, int Cout, int KH, int stride, int pad, int act, int res_mode, int out_f32, int x_up2) {
   if (!x2 || (x_up2 && ((H | W) & 1))) return RTD_E_INVALID;
@@ -286,8 +310,8 @@ int rtd_op_conv_next(int dtype, const void* x, const void* x2, const void* w_f32
   return op_conv_impl(dtype, x, x2, x2 ? C2 : 0, w_f32, bias, res, y, B, H, W, Cin, Cout, 1, 1, 1, 0, act, res_mode, 0, 0, w1_f32, bias1, y1, Cnext, next_act);
 }
 
-int rtd_bench_conv(int dtype, int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad, int with_res, int reps,
-                   int flush_mb, float* us_out) {
+static int bench_conv_impl(int dtype, int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad, int with_res, int act, int reps,
+                           int flush_mb, float* us_out) {
   return op_guard([&] {
     const int K = KH * KH * Cin, Kpad = dtype == F16X2 ? conv_kpad_split(K) : conv_kpad(K), Npad = conv_npad(Cout);
     const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KH) / stride + 1;
@@ -308,7 +332,7 @@ int rtd_bench_conv(int dtype, int B, int H, int W, int Cin, int Cout, int KH, in
     a.x = mk(x, dtype, B, H, W, Cin);
     a.y = mk(y, dtype, B, OH, OW, Cout);
     a.w = w; a.bias = bias; a.KH = KH; a.KW = KH; a.stride = stride; a.pad = pad; a.Kpad = Kpad; a.Npad = Npad;
-    a.act = 1; a.res_mode = with_res ? RES_PRE : RES_NONE;
+    a.act = act; a.res_mode = with_res ? RES_PRE : RES_NONE;
     if (with_res) a.res = mk(r, dtype, B, OH, OW, Cout);
     a.ws.slab_bytes = conv_split_slab_bytes(a);                  // two-pass split-K
     if (a.ws.slab_bytes) {
@@ -357,6 +381,15 @@ int rtd_bench_conv(int dtype, int B, int H, int W, int Cin, int Cout, int KH, in
     if (r) (void)hipFree(r);
     if (flush) (void)hipFree(flush);
   });
+}
+int rtd_bench_conv(int dtype, int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad, int with_res, int reps,
+                   int flush_mb, float* us_out) {
+  return bench_conv_impl(dtype, B, H, W, Cin, Cout, KH, stride, pad, with_res, ACT_RELU, reps, flush_mb, us_out);
+}
+int rtd_bench_conv_act(int dtype, int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad, int with_res, int act, int reps,
+                       int flush_mb, float* us_out) {
+  if (act < ACT_NONE || act > ACT_LRELU) return RTD_E_INVALID;
+  return bench_conv_impl(dtype, B, H, W, Cin, Cout, KH, stride, pad, with_res, act, reps, flush_mb, us_out);
 }
 
 // Concurrency micro-benchmark (tools/pair_bench.py): conv A on one stream, conv B on another; us_out = {A alone, B alone,

@@ -5,8 +5,9 @@ BGR -> Lab, CLAHE on L, Lab -> BGR and the bilateral filter run on device-reside
 (`rtd_enhance_crops`, csrc/enhance.hip), asynchronously on torch's current stream; the arithmetic is restated in
 tests/enhance_ref.py and matched bit for bit.  `CropBatcher.preprocess_batch(..., enhancer=e)` feeds the enhanced crops straight to
 the unchanged crop-resize launch, `BatchedStage2(pipeline, enhancer="auto")` builds the enhancer from the pipeline's own
-`ImageEnhancer` object.  Out of scope: one-channel crops, Real-ESRGAN (method "realesrgan" keeps the reference's per-detection
-path) and the reference's LRU cache of enhanced crops (it exists to avoid a 1 s network).
+`ImageEnhancer` object.  Method "realesrgan" is served by esrgan.py (`UpscalingEnhancer`, an opt-in that chains the x4 network with this
+enhancer): `from_reference` here and "auto" keep answering None for it.  Out of scope: one-channel crops and the
+reference's LRU cache of enhanced crops.
 """
 from __future__ import annotations
 
