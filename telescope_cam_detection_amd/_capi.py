@@ -299,6 +299,142 @@ def _raise(code: int, handle) -> None:
     raise RtdError(code, msg)
 
 
+# ---- the stand-alone back ends (motion, mog2, jpeg, overlay, enhance, esrgan) ---------------------------------------------------------
+def device_index(device) -> int:
+    """an int, None (torch's current device), a torch.device or a string like 'cuda:1' -> the device's index"""
+    if isinstance(device, int):
+        return device
+    if device is None:
+        import torch
+        return torch.cuda.current_device() if torch.cuda.is_available() else 0
+    if hasattr(device, "index"):                  # torch.device
+        return device.index or 0
+    s = str(device)
+    return int(s.split(":")[1]) if ":" in s else 0
+
+
+def frame_ptrs(frames, on_device: bool):
+    """HxWxC uint8 frames (C-contiguous numpy arrays, or contiguous device tensors when on_device) -> (addresses, shapes)"""
+    return ([f.data_ptr() if on_device else f.ctypes.data for f in frames],
+            [(int(f.shape[0]), int(f.shape[1]), int(f.shape[2])) for f in frames])
+
+
+def c_frames(ptrs, shapes):
+    """(addresses, shapes) -> (n, void* [n], int32 hwc [n][3]) as the rtd_* calls take them; never zero-length arrays"""
+    n = len(ptrs)
+    return n, (C.c_void_p * max(n, 1))(*ptrs), (C.c_int32 * max(3 * n, 1))(*[int(v) for s in shapes for v in s])
+
+
+class Handle:
+    """One handle of a stand-alone back end: rtd_<x>_create / _last_error / _destroy, and _wait_stream where the back end owns a
+    stream.  A subclass names its functions' prefix and what the out-of-memory message calls it."""
+    _prefix = ""          # "rtd_jpeg"
+    _what = ""            # "the JPEG encoder"
+
+    def _fn(self, name: str):
+        return getattr(self._L, f"{self._prefix}_{name}")
+
+    def _open(self, *args) -> None:
+        """rtd_<x>_create(*args, &handle)"""
+        self._L = lib()
+        self._h = C.c_void_p()
+        rc = self._fn("create")(*args, C.byref(self._h))
+        if rc != RTD_OK:
+            self._h = C.c_void_p()        # (the message of a refused create is the one rtd_<x>_last_error(NULL) reports)
+            self._raise(rc)
+
+    def _raise(self, rc: int):
+        msg = (self._fn("last_error")(self._h) or b"").decode(errors="replace")
+        if rc == RTD_E_OOM:
+            import torch
+            # the only exception the reference's degrade path reacts to (src/inference_engine_yolox.py:607)
+            raise torch.cuda.OutOfMemoryError(f"HIP out of memory in {self._what}: {msg}")
+        raise RtdError(rc, msg)
+
+    def _check(self, rc: int) -> None:
+        if rc != RTD_OK:
+            self._raise(rc)
+
+    def wait_stream(self, producer_stream: int) -> None:
+        """The handle's stream waits for everything enqueued so far on `producer_stream` (a raw hipStream_t value; 0 = the default
+        stream)."""
+        self._check(self._fn("wait_stream")(self._h, C.c_void_p(int(producer_stream) or None)))
+
+    def close(self) -> None:
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._fn("destroy")(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+MAX_CROPS_PER_CALL = 64       # rtd_enhance_crops, rtd_esrgan_upscale
+
+
+def crop_layout(prefix: str, rects) -> list:
+    """rtd_<x>_layout: byte offsets of the crops (x1, y1, x2, y2) in the output buffer, plus its size.  Host arithmetic only."""
+    n = len(rects)
+    rc = (C.c_int32 * max(4 * n, 1))(*[int(v) for r in rects for v in r])
+    offsets = (C.c_int64 * (n + 1))()
+    code = getattr(lib(), prefix + "_layout")(n, rc, offsets)
+    if code != RTD_OK:
+        raise RtdError(code, (getattr(lib(), prefix + "_last_error")(None) or b"").decode(errors="replace"))
+    return list(offsets)
+
+
+class CropHandle(Handle):
+    """A back end whose call takes crops of device-resident frames and writes them, packed by its layout, into one buffer on the
+    caller's stream (enhance, esrgan)."""
+    _timing = None
+
+    def _crop_call(self, call: str, scale: int, frames, rects_per_frame):
+        """frames: device uint8 HWC BGR tensors; rects_per_frame: per frame a list of (x1, y1, x2, y2).  Returns (buffer, offsets,
+        shapes): one uint8 device tensor holding every output crop (frame-major order), crop i being buffer[offsets[i]:][:h * w * 3]
+        viewed as (h, w, 3) with shapes[i] = (h, w), `scale` times the rectangle; offsets has one more entry, the buffer's size.
+        Enqueued on torch's current stream: the buffer is ready when that stream reaches it."""
+        import torch
+
+        flat = [(f, tuple(int(v) for v in r)) for f, rects in zip(frames, rects_per_frame) for r in rects]
+        dev = frames[0].device if len(frames) else torch.device("cuda", self.device)
+        offsets = crop_layout(self._prefix, [r for _, r in flat])
+        shapes = [(scale * (r[3] - r[1]), scale * (r[2] - r[0])) for _, r in flat]
+        buf = torch.empty((offsets[-1],), dtype=torch.uint8, device=dev)
+        if not flat:
+            return buf, offsets, shapes
+        stream = torch.cuda.current_stream(dev)
+        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        ev0.record(stream)
+        for i0 in range(0, len(flat), MAX_CROPS_PER_CALL):
+            part = flat[i0:i0 + MAX_CROPS_PER_CALL]
+            k = len(part)
+            ptrs = (C.c_void_p * k)()
+            hw = (C.c_int32 * (2 * k))()
+            rc = (C.c_int32 * (4 * k))()
+            for i, (f, r) in enumerate(part):
+                assert f.is_cuda and f.dtype == torch.uint8 and f.is_contiguous() and f.dim() == 3 and f.shape[2] == 3
+                ptrs[i] = f.data_ptr()
+                hw[2 * i], hw[2 * i + 1] = int(f.shape[0]), int(f.shape[1])
+                rc[4 * i:4 * i + 4] = r
+            # the offsets of a chunk are the layout's for the whole list, relative to the chunk's first crop
+            self._check(self._fn(call)(self._h, k, ptrs, hw, rc, C.c_void_p(buf.data_ptr() + offsets[i0]), offsets[-1] - offsets[i0],
+                                       C.c_void_p(stream.cuda_stream)))
+        ev1.record(stream)
+        self._timing = (ev0, ev1)
+        return buf, offsets, shapes
+
+    def last_call_ms(self) -> Optional[float]:
+        """device time of the last crop call in milliseconds (waits for it); None before the first call"""
+        if self._timing is None:
+            return None
+        ev0, ev1 = self._timing
+        ev1.synchronize()
+        return float(ev0.elapsed_time(ev1))
+
+
 PROFILE_LATENCY, PROFILE_THROUGHPUT = 0, 1
 
 

@@ -11,6 +11,8 @@
 #include <utility>
 #include <vector>
 
+#include "error.h"   // rtd::Error, RTD_CHECK
+
 namespace rtd {
 
 // F16X2 ("split"): every value is carried as two IEEE fp16, x = hi + lo with hi = fp16(x), lo = fp16(x - hi) (22 significant bits; see sp16 below).
@@ -58,16 +60,6 @@ struct Tensor {
 // every pointer on a 16-byte boundary (what the kernels' 16-byte vector accesses and buffer loads need of a tensor's base)
 template <typename... P>
 inline bool aligned16(const P*... p) { return ((... | (uintptr_t)p) & 15) == 0; }
-
-struct Error : std::runtime_error {
-  int code;
-  Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-#define RTD_CHECK(cond, code, msg)                                                     \
-  do {                                                                                 \
-    if (!(cond)) throw ::rtd::Error((code), std::string(msg) + " [" #cond "] at " __FILE__ ":" + std::to_string(__LINE__)); \
-  } while (0)
 
 #define HIP_CHECK(expr)                                                                \
   do {                                                                                 \

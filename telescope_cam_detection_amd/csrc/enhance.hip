@@ -17,7 +17,7 @@
 
 #include "../../include/rtdetr_mi355.h"
 #include "../../include/rtdetr_mi355_test.h"
-#include "common.h"
+#include "backend.h"
 #include "enhance_tables.h"
 
 #pragma clang fp contract(off)
@@ -25,9 +25,12 @@
 namespace enhance {
 
 using rtd::Error;
+namespace bk = rtd::backend;
+using bk::align_up;
+using bk::guarded;
 
 constexpr int THREADS = 256;
-constexpr int MAX_CROPS = 64, MAX_TILES = 16, MAX_RADIUS = 7, MIN_SIDE = 16;
+constexpr int MAX_CROPS = bk::MAX_CROPS, MAX_TILES = 16, MAX_RADIUS = 7, MIN_SIDE = 16;
 constexpr int BIL_W = 64, BIL_H = 16;                         // output tile of the bilateral kernel
 constexpr int BIL_ROWS = BIL_W * BIL_H / THREADS;             // 4: thread t owns column t % 64 of rows t / 64 + 4 k
 constexpr int BIL_STEP = THREADS / BIL_W;
@@ -230,10 +233,6 @@ __global__ void __launch_bounds__(THREADS) enhance_bilateral(EnhArgs a, const fl
   }
 }
 
-static std::string g_enhance_create_error;
-
-static int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
-
 // THE packing rule (rtd_enhance_layout): crop i is HWC with tightly packed rows and starts on a multiple of CROP_ALIGN bytes
 static void layout(int n, const int32_t* rects, int64_t* offsets) {
   RTD_CHECK(n >= 0 && (n == 0 || rects) && offsets, RTD_E_INVALID, "null argument");
@@ -244,7 +243,7 @@ static void layout(int n, const int32_t* rects, int64_t* offsets) {
     RTD_CHECK(x1 >= 0 && y1 >= 0 && x2 - x1 >= MIN_SIDE && y2 - y1 >= MIN_SIDE, RTD_E_INVALID, ci + " is smaller than 16 pixels per side or has a negative corner");
     RTD_CHECK((x2 - x1) * (y2 - y1) * 3 < (1ll << 31), RTD_E_INVALID, ci + " has 2 GiB or more");
     offsets[i] = at;
-    at += align_up((x2 - x1) * (y2 - y1) * 3, CROP_ALIGN);
+    at += (int64_t)align_up((size_t)((x2 - x1) * (y2 - y1) * 3), CROP_ALIGN);
   }
   offsets[n] = at;
 }
@@ -253,17 +252,13 @@ static void layout(int n, const int32_t* rects, int64_t* offsets) {
 
 using namespace enhance;
 
-struct rtd_enhance {
-  int device = 0;
-  std::mutex mu;
-  std::string err;
+struct rtd_enhance : bk::Base {
   double clip_limit = 0;
   int tiles_x = 0, tiles_y = 0, radius = 0;
   LabConsts consts;
   uint8_t* tables = nullptr;                 // one device allocation; the offsets below are into it
   size_t o_gtab = 0, o_ctab = 0, o_tl = 0, o_ta = 0, o_tb = 0, o_finv = 0, o_gi = 0, o_sw = 0, o_cw = 0;
-  uint8_t *lab = nullptr, *bgr = nullptr, *luts = nullptr;     // scratch, grown on demand
-  int64_t plane_cap = 0, lut_cap = 0;
+  bk::DevBuf lab, bgr, luts;                 // scratch, grown on demand
   // what the last call left in the scratch (rtd_debug_enhance_stage)
   int last_n = 0;
   hipStream_t last_stream = nullptr;
@@ -273,30 +268,11 @@ struct rtd_enhance {
 
 namespace enhance {
 
-template <typename F>
-static int guarded(rtd_enhance* e, F&& f) {
-  if (!e) return RTD_E_INVALID;
-  std::lock_guard<std::mutex> lk(e->mu);
-  try {
-    f();
-    return RTD_OK;
-  } catch (const Error& er) {
-    e->err = er.what();
-    return er.code;
-  } catch (const std::bad_alloc&) {
-    e->err = "host allocation failed";
-    return RTD_E_OOM;
-  } catch (const std::exception& ex) {
-    e->err = ex.what();
-    return RTD_E_HIP;
-  }
-}
-
 static void upload_tables(rtd_enhance* e, const Tables& t) {
   size_t at = 0;
   auto place = [&](size_t bytes) {
     const size_t o = at;
-    at = (size_t)align_up((int64_t)(at + bytes), 256);
+    at = align_up(at + bytes, 256);
     return o;
   };
   e->o_gtab = place(t.gtab.size() * 2), e->o_ctab = place(t.ctab.size() * 2);
@@ -317,29 +293,6 @@ static void upload_tables(rtd_enhance* e, const Tables& t) {
   HIP_CHECK(hipMemcpy(e->tables, host.data(), at, hipMemcpyHostToDevice));
 }
 
-// scratch for planes of `plane` bytes and `lut` bytes of LUTs.  hipFree waits for the device, so nothing enqueued earlier still reads
-// a buffer that is replaced here; in the steady state nothing is allocated.
-static void reserve(rtd_enhance* e, int64_t plane, int64_t lut) {
-  if (plane > e->plane_cap) {
-    const int64_t cap = std::max(plane, e->plane_cap * 2);
-    if (e->lab) (void)hipFree(e->lab);
-    if (e->bgr) (void)hipFree(e->bgr);
-    e->lab = e->bgr = nullptr;
-    e->plane_cap = 0;
-    HIP_CHECK(hipMalloc((void**)&e->lab, (size_t)cap));
-    HIP_CHECK(hipMalloc((void**)&e->bgr, (size_t)cap));
-    e->plane_cap = cap;
-  }
-  if (lut > e->lut_cap) {
-    const int64_t cap = std::max(lut, e->lut_cap * 2);
-    if (e->luts) (void)hipFree(e->luts);
-    e->luts = nullptr;
-    e->lut_cap = 0;
-    HIP_CHECK(hipMalloc((void**)&e->luts, (size_t)cap));
-    e->lut_cap = cap;
-  }
-}
-
 template <int R>
 static void launch_bilateral(const EnhArgs& a, int blocks, const float* sw, const float* cw, const uint8_t* bgr, uint8_t* out, hipStream_t s) {
   rtd::rtd_launch(enhance_bilateral<R>, dim3((unsigned)blocks), dim3(THREADS), 0, s, a, sw, cw, bgr, out);
@@ -348,17 +301,10 @@ static void launch_bilateral(const EnhArgs& a, int blocks, const float* sw, cons
 static void run(rtd_enhance* e, int n, const uint8_t* const* frames, const int32_t* frame_hw, const int32_t* rects, uint8_t* out, int64_t out_cap,
                 hipStream_t s) {
   // ---- every argument is checked before anything is allocated or launched
-  RTD_CHECK(n >= 1 && n <= MAX_CROPS, RTD_E_INVALID, "1..64 crops per call");
-  RTD_CHECK(frames && frame_hw && rects && out, RTD_E_INVALID, "null argument");
+  bk::check_crop_call(n, frames, frame_hw, rects, out);
   int64_t offsets[MAX_CROPS + 1];
   layout(n, rects, offsets);
-  for (int i = 0; i < n; ++i) {
-    const std::string ci = "crop " + std::to_string(i);
-    const int64_t fh = frame_hw[2 * i], fw = frame_hw[2 * i + 1];
-    RTD_CHECK(frames[i], RTD_E_INVALID, ci + " has a null frame");
-    RTD_CHECK(fh >= 1 && fw >= 1 && fh <= 65535 && fw <= 65535, RTD_E_INVALID, ci + ": bad frame size (1..65535 per side)");
-    RTD_CHECK(rects[4 * i + 2] <= fw && rects[4 * i + 3] <= fh, RTD_E_INVALID, ci + " leaves its frame");
-  }
+  for (int i = 0; i < n; ++i) bk::check_crop_frame(i, frames, frame_hw, rects);
   RTD_CHECK(out_cap >= offsets[n], RTD_E_INVALID, "out_cap is smaller than rtd_enhance_layout's total (" + std::to_string(offsets[n]) + " bytes)");
 
   const int tiles = e->tiles_x * e->tiles_y;
@@ -397,24 +343,27 @@ static void run(rtd_enhance* e, int n, const uint8_t* const* frames, const int32
 
   HIP_CHECK(hipSetDevice(e->device));
   e->last_n = 0;
-  reserve(e, offsets[n], (int64_t)n * tiles * 256);
+  e->lab.reserve((size_t)offsets[n]);          // (hipFree waits for the device, so nothing enqueued earlier still reads a replaced buffer)
+  e->bgr.reserve((size_t)offsets[n]);
+  e->luts.reserve((size_t)n * tiles * 256);
+  uint8_t *lab = e->lab.p, *bgr = e->bgr.p, *luts = e->luts.p;
   const uint8_t* T = e->tables;
   rtd::rtd_launch(enhance_lab_hist, dim3((unsigned)(n * tiles)), dim3(THREADS), 0, s, lab_args, e->consts, (const uint16_t*)(T + e->o_gtab),
-                  (const uint16_t*)(T + e->o_ctab), e->lab, e->luts, e->tiles_x, tiles);
+                  (const uint16_t*)(T + e->o_ctab), lab, luts, e->tiles_x, tiles);
   HIP_CHECK(hipGetLastError());
   rtd::rtd_launch(enhance_apply, dim3((unsigned)apply_blocks), dim3(THREADS), 0, s, apply_args, e->consts, (const int32_t*)(T + e->o_tl),
-                  (const int32_t*)(T + e->o_ta), (const int32_t*)(T + e->o_tb), (const int32_t*)(T + e->o_finv), T + e->o_gi, (const uint8_t*)e->lab,
-                  (const uint8_t*)e->luts, e->bgr, e->tiles_x, e->tiles_y);
+                  (const int32_t*)(T + e->o_ta), (const int32_t*)(T + e->o_tb), (const int32_t*)(T + e->o_finv), T + e->o_gi, (const uint8_t*)lab,
+                  (const uint8_t*)luts, bgr, e->tiles_x, e->tiles_y);
   HIP_CHECK(hipGetLastError());
   const float *sw = (const float*)(T + e->o_sw), *cw = (const float*)(T + e->o_cw);
   switch (e->radius) {
-    case 1: launch_bilateral<1>(bil_args, (int)bil_blocks, sw, cw, e->bgr, out, s); break;
-    case 2: launch_bilateral<2>(bil_args, (int)bil_blocks, sw, cw, e->bgr, out, s); break;
-    case 3: launch_bilateral<3>(bil_args, (int)bil_blocks, sw, cw, e->bgr, out, s); break;
-    case 4: launch_bilateral<4>(bil_args, (int)bil_blocks, sw, cw, e->bgr, out, s); break;
-    case 5: launch_bilateral<5>(bil_args, (int)bil_blocks, sw, cw, e->bgr, out, s); break;
-    case 6: launch_bilateral<6>(bil_args, (int)bil_blocks, sw, cw, e->bgr, out, s); break;
-    default: launch_bilateral<7>(bil_args, (int)bil_blocks, sw, cw, e->bgr, out, s); break;
+    case 1: launch_bilateral<1>(bil_args, (int)bil_blocks, sw, cw, bgr, out, s); break;
+    case 2: launch_bilateral<2>(bil_args, (int)bil_blocks, sw, cw, bgr, out, s); break;
+    case 3: launch_bilateral<3>(bil_args, (int)bil_blocks, sw, cw, bgr, out, s); break;
+    case 4: launch_bilateral<4>(bil_args, (int)bil_blocks, sw, cw, bgr, out, s); break;
+    case 5: launch_bilateral<5>(bil_args, (int)bil_blocks, sw, cw, bgr, out, s); break;
+    case 6: launch_bilateral<6>(bil_args, (int)bil_blocks, sw, cw, bgr, out, s); break;
+    default: launch_bilateral<7>(bil_args, (int)bil_blocks, sw, cw, bgr, out, s); break;
   }
   HIP_CHECK(hipGetLastError());
   e->last_n = n;
@@ -427,22 +376,15 @@ static void run(rtd_enhance* e, int n, const uint8_t* const* frames, const int32
 extern "C" {
 
 int rtd_enhance_create(int32_t device, const rtd_enhance_params* p, rtd_enhance_handle* out) {
-  if (!out) return RTD_E_INVALID;
-  *out = nullptr;
-  rtd_enhance* e = new (std::nothrow) rtd_enhance();
-  if (!e) return RTD_E_OOM;
-  try {
+  return bk::create(out, rtd_enhance_destroy, [&](rtd_enhance* e) {
     RTD_CHECK(p && p->struct_size == (int32_t)sizeof(rtd_enhance_params), RTD_E_INVALID, "rtd_enhance_params: bad struct_size");
     RTD_CHECK(p->clip_limit == p->clip_limit && p->clip_limit <= 1e6f, RTD_E_INVALID, "clip_limit must be a number <= 1e6 (<= 0: no clipping)");
     RTD_CHECK(p->tiles_x >= 1 && p->tiles_x <= MAX_TILES && p->tiles_y >= 1 && p->tiles_y <= MAX_TILES, RTD_E_INVALID, "tile grid must be 1..16 per axis");
     RTD_CHECK(p->sigma_color == p->sigma_color && p->sigma_space == p->sigma_space && p->sigma_space <= 1e6f, RTD_E_INVALID, "bad sigma");
     const int radius = bilateral_radius(p->bilateral_d, (double)p->sigma_space);
     RTD_CHECK(radius >= 1 && radius <= MAX_RADIUS, RTD_E_INVALID, "the bilateral radius (d / 2, or rint(1.5 sigma_space) for d <= 0) must be 1..7");
-    int count = 0;
-    HIP_CHECK(hipGetDeviceCount(&count));
-    RTD_CHECK(device >= 0 && device < count, RTD_E_INVALID, "no such device");
+    bk::use_device(device);
     e->device = device;
-    HIP_CHECK(hipSetDevice(device));
     e->clip_limit = (double)p->clip_limit;
     e->tiles_x = p->tiles_x, e->tiles_y = p->tiles_y, e->radius = radius;
     const Tables t = make_tables(p->bilateral_d, (double)p->sigma_color, (double)p->sigma_space);
@@ -450,27 +392,11 @@ int rtd_enhance_create(int32_t device, const rtd_enhance_params* p, rtd_enhance_
     memcpy(e->consts.Ci, t.Ci, sizeof t.Ci);
     e->consts.fmin = t.fmin;
     upload_tables(e, t);
-  } catch (const Error& er) {
-    g_enhance_create_error = er.what();
-    rtd_enhance_destroy(e);
-    return er.code;
-  } catch (const std::exception& ex) {
-    g_enhance_create_error = ex.what();
-    rtd_enhance_destroy(e);
-    return RTD_E_HIP;
-  }
-  *out = e;
-  return RTD_OK;
+  });
 }
 
 int rtd_enhance_layout(int32_t n, const int32_t* rects, int64_t* offsets) {
-  try {
-    layout(n, rects, offsets);
-    return RTD_OK;
-  } catch (const Error& er) {
-    g_enhance_create_error = er.what();
-    return er.code;
-  }
+  return bk::caught(bk::create_error<rtd_enhance>(), [&] { layout(n, rects, offsets); });
 }
 
 int rtd_enhance_crops(rtd_enhance_handle e, int32_t n, const uint8_t* const* frames_dev, const int32_t* frame_hw, const int32_t* rects,
@@ -478,14 +404,14 @@ int rtd_enhance_crops(rtd_enhance_handle e, int32_t n, const uint8_t* const* fra
   return guarded(e, [&] { run(e, n, frames_dev, frame_hw, rects, out_dev, out_cap, (hipStream_t)stream); });
 }
 
-const char* rtd_enhance_last_error(rtd_enhance_handle e) { return e ? e->err.c_str() : g_enhance_create_error.c_str(); }
+const char* rtd_enhance_last_error(rtd_enhance_handle e) { return bk::last_error(e); }
 
 void rtd_enhance_destroy(rtd_enhance_handle e) {
   if (!e) return;
   (void)hipSetDevice(e->device);
-  if (e->lab) (void)hipFree(e->lab);          // (hipFree waits for the device: nothing enqueued still uses the scratch)
-  if (e->bgr) (void)hipFree(e->bgr);
-  if (e->luts) (void)hipFree(e->luts);
+  e->lab.release();                           // (hipFree waits for the device: nothing enqueued still uses the scratch)
+  e->bgr.release();
+  e->luts.release();
   if (e->tables) (void)hipFree(e->tables);
   (void)hipGetLastError();
   delete e;
@@ -501,7 +427,7 @@ int rtd_debug_enhance_stage(rtd_enhance_handle e, int32_t crop, int32_t stage, u
     RTD_CHECK(nbytes == want, RTD_E_INVALID, "nbytes must be " + std::to_string(want));
     HIP_CHECK(hipSetDevice(e->device));
     HIP_CHECK(hipStreamSynchronize(e->last_stream));
-    const uint8_t* src = stage == 1 ? e->luts + (size_t)crop * tiles * 256 : (stage == 0 ? e->lab : e->bgr) + e->last_off[crop];
+    const uint8_t* src = stage == 1 ? e->luts.p + (size_t)crop * tiles * 256 : (stage == 0 ? e->lab.p : e->bgr.p) + e->last_off[crop];
     HIP_CHECK(hipMemcpy(out, src, want, hipMemcpyDeviceToHost));
   });
 }

@@ -27,15 +27,16 @@
 
 #include "../../include/rtdetr_mi355.h"
 #include "../../include/rtdetr_mi355_test.h"
-#include "common.h"
+#include "backend.h"
 #include "esrgan_host.h"
 
 namespace esrgan {
 
 using namespace rtd;
 namespace eh = esrgan_host;
+namespace bk = rtd::backend;
+using bk::guarded;
 
-static thread_local std::string g_create_error;
 constexpr int IN_C = 32, FEAT = 64, GROW = 32, DENSE_C = 192, LAST_C = 32;
 
 // ---------------------------------------------------------------------------------------------------------------- kernels
@@ -112,17 +113,14 @@ struct Plan {
 
 }  // namespace esrgan
 
-struct rtd_esrgan {
+struct rtd_esrgan : rtd::backend::Base {
   rtd_esrgan_config cfg;
   int P = rtd::F16X2;
-  std::mutex mu;
-  std::string err;
   std::vector<char> blob;
   std::map<std::string, esrgan::DevW> weights;
   std::vector<void*> allocs;
   std::map<std::pair<int, int>, std::unique_ptr<esrgan::Plan>> plans;
-  char* arena = nullptr;
-  size_t arena_bytes = 0;
+  rtd::backend::DevBuf arena;   // holds the largest plan seen (a repeated shape allocates nothing)
   rtd::ConvOpts conv_opts;
   // the last tile of the last call (rtd_debug_esrgan_tensor re-runs it up to the stage asked for)
   const uint8_t* last_src = nullptr;
@@ -214,18 +212,8 @@ static Plan* get_plan(rtd_esrgan* e, int h, int w) {
   return p;
 }
 
-// hipFree waits for the device, so nothing enqueued earlier still uses an arena that is replaced here; a repeated shape allocates nothing
-static void reserve(rtd_esrgan* e, size_t bytes) {
-  if (bytes <= e->arena_bytes) return;
-  if (e->arena) (void)hipFree(e->arena);
-  e->arena = nullptr;
-  e->arena_bytes = 0;
-  HIP_CHECK(hipMalloc((void**)&e->arena, bytes));
-  e->arena_bytes = bytes;
-}
-
 static void run_op(rtd_esrgan* e, const Plan* p, const Op& op, hipStream_t s) {
-  char* base = e->arena;
+  char* base = (char*)e->arena.p;
   switch (op.kind) {
     case OP_CONV: {
       ConvArgs a = op.conv;
@@ -246,7 +234,7 @@ static void run_op(rtd_esrgan* e, const Plan* p, const Op& op, hipStream_t s) {
 
 static void run_ingest(rtd_esrgan* e, const Plan* p, const uint8_t* src, int pitch, hipStream_t s) {
   const unsigned blocks = (unsigned)(((int64_t)p->h * p->w + 255) / 256);
-  void* dst = e->arena + (size_t)p->in.p;
+  void* dst = e->arena.p + (size_t)p->in.p;
   if (e->P == F16X2) rtd_launch(esrgan_ingest<true>, dim3(blocks), dim3(256), 0, s, src, pitch, p->h, p->w, dst);
   else rtd_launch(esrgan_ingest<false>, dim3(blocks), dim3(256), 0, s, src, pitch, p->h, p->w, dst);
   HIP_CHECK(hipGetLastError());
@@ -255,24 +243,20 @@ static void run_ingest(rtd_esrgan* e, const Plan* p, const uint8_t* src, int pit
 static void run(rtd_esrgan* e, int n, const uint8_t* const* frames, const int32_t* frame_hw, const int32_t* rects, uint8_t* out, int64_t out_cap,
                 hipStream_t s) {
   // ---- every argument is checked before anything is allocated or launched
-  RTD_CHECK(n >= 1 && n <= eh::MAX_CROPS, RTD_E_INVALID, "1..64 crops per call");
-  RTD_CHECK(frames && frame_hw && rects && out, RTD_E_INVALID, "null argument");
+  static_assert(eh::MAX_CROPS == bk::MAX_CROPS, "the shared argument check and the layout agree on the crops per call");
+  bk::check_crop_call(n, frames, frame_hw, rects, out);
   int64_t offsets[eh::MAX_CROPS + 1];
   eh::layout(n, rects, offsets);
   const int tile = e->cfg.tile, pad = e->cfg.tile_pad;
   for (int i = 0; i < n; ++i) {
-    const std::string ci = "crop " + std::to_string(i);
-    const int64_t fh = frame_hw[2 * i], fw = frame_hw[2 * i + 1];
-    RTD_CHECK(frames[i], RTD_E_INVALID, ci + " has a null frame");
-    RTD_CHECK(fh >= 1 && fw >= 1 && fh <= 65535 && fw <= 65535, RTD_E_INVALID, ci + ": bad frame size (1..65535 per side)");
-    RTD_CHECK(rects[4 * i + 2] <= fw && rects[4 * i + 3] <= fh, RTD_E_INVALID, ci + " leaves its frame");
+    bk::check_crop_frame(i, frames, frame_hw, rects);
     if (tile == 0)
       RTD_CHECK(rects[4 * i + 2] - rects[4 * i] <= eh::MAX_ONE_PASS_SIDE && rects[4 * i + 3] - rects[4 * i + 1] <= eh::MAX_ONE_PASS_SIDE, RTD_E_INVALID,
-                ci + ": without tiling (tile = 0) a crop side is at most 576 pixels");
+                "crop " + std::to_string(i) + ": without tiling (tile = 0) a crop side is at most 576 pixels");
   }
   RTD_CHECK(out_cap >= offsets[n], RTD_E_INVALID, "out_cap is smaller than rtd_esrgan_layout's total (" + std::to_string(offsets[n]) + " bytes)");
 
-  HIP_CHECK(hipSetDevice(e->cfg.device));
+  HIP_CHECK(hipSetDevice(e->device));
   // ---- the plans of every tile shape of the call, and one arena that holds the largest
   struct Job { Plan* plan; eh::TileRect t; int crop; };
   std::vector<Job> jobs;
@@ -287,7 +271,7 @@ static void run(rtd_esrgan* e, int n, const uint8_t* const* frames, const int32_
       jobs.push_back(Job{p, t, i});
     }
   }
-  reserve(e, need);
+  e->arena.reserve(need);
   for (const Job& j : jobs) {
     const int i = j.crop;
     const int x1 = rects[4 * i], y1 = rects[4 * i + 1], W = rects[4 * i + 2] - x1, fw = frame_hw[2 * i + 1];
@@ -297,7 +281,7 @@ static void run(rtd_esrgan* e, int n, const uint8_t* const* frames, const int32_
     run_ingest(e, j.plan, src, pitch, s);
     for (const Op& op : j.plan->ops) run_op(e, j.plan, op, s);
     EmitArgs a;
-    a.last = (const float*)(e->arena + (size_t)j.plan->last.p);
+    a.last = (const float*)(e->arena.p + (size_t)j.plan->last.p);
     a.tw4 = 4 * j.plan->w;
     a.ox = 4 * (t.cx0 - t.ix0), a.oy = 4 * (t.cy0 - t.iy0);
     a.cw4 = 4 * (t.cx1 - t.cx0), a.ch4 = 4 * (t.cy1 - t.cy0);
@@ -356,28 +340,6 @@ static void upload_weights(rtd_esrgan* e, const std::map<std::string, eh::HostTe
   }
 }
 
-template <typename F>
-static int guarded(rtd_esrgan* e, F&& f) {
-  if (!e) return RTD_E_INVALID;
-  std::lock_guard<std::mutex> lk(e->mu);
-  try {
-    f();
-    return RTD_OK;
-  } catch (const eh::Fail& er) {
-    e->err = er.msg;
-    return er.code;
-  } catch (const Error& er) {
-    e->err = er.what();
-    return er.code;
-  } catch (const std::bad_alloc&) {
-    e->err = "host allocation failed";
-    return RTD_E_OOM;
-  } catch (const std::exception& ex) {
-    e->err = ex.what();
-    return RTD_E_HIP;
-  }
-}
-
 }  // namespace esrgan
 
 using namespace esrgan;
@@ -385,12 +347,7 @@ using namespace esrgan;
 extern "C" {
 
 int rtd_esrgan_create(const rtd_esrgan_config* cfg, const void* blob, size_t nbytes, rtd_esrgan_handle* out) {
-  if (!out) return RTD_E_INVALID;
-  *out = nullptr;
-  rtd_esrgan* e = new (std::nothrow) rtd_esrgan();
-  if (!e) return RTD_E_OOM;
-  int code = RTD_OK;
-  try {
+  return bk::create(out, rtd_esrgan_destroy, [&](rtd_esrgan* e) {
     eh::check_config(cfg);
     e->cfg = *cfg;
     e->P = cfg->precision == RTD_PREC_FP32 ? F32 : F16X2;
@@ -400,39 +357,17 @@ int rtd_esrgan_create(const rtd_esrgan_config* cfg, const void* blob, size_t nby
     eh::parse_blob(e->blob.data(), e->blob.size(), host);
     const std::vector<eh::ConvDesc> table = eh::conv_table(cfg->num_block);
     for (const eh::ConvDesc& d : table) eh::check_conv_tensors(host, d, e->P == F16X2);   // the whole blob is checked before the device is touched
-    int count = 0;
-    HIP_CHECK(hipGetDeviceCount(&count));
-    RTD_CHECK(cfg->device < count, RTD_E_INVALID, "no such device");
-    HIP_CHECK(hipSetDevice(cfg->device));
+    bk::use_device(cfg->device);
+    e->device = cfg->device;
     e->conv_opts = conv_opts_template();
     upload_weights(e, host, table);
     e->blob.clear();
     e->blob.shrink_to_fit();
-  } catch (const eh::Fail& er) {
-    g_create_error = er.msg; code = er.code;
-  } catch (const Error& er) {
-    g_create_error = er.what(); code = er.code;
-  } catch (const std::bad_alloc&) {
-    g_create_error = "host allocation failed"; code = RTD_E_OOM;
-  } catch (const std::exception& ex) {
-    g_create_error = ex.what(); code = RTD_E_HIP;
-  }
-  if (code != RTD_OK) {
-    rtd_esrgan_destroy(e);
-    return code;
-  }
-  *out = e;
-  return RTD_OK;
+  });
 }
 
 int rtd_esrgan_layout(int32_t n, const int32_t* rects, int64_t* offsets) {
-  try {
-    eh::layout(n, rects, offsets);
-    return RTD_OK;
-  } catch (const eh::Fail& er) {
-    g_create_error = er.msg;
-    return er.code;
-  }
+  return bk::caught(bk::create_error<rtd_esrgan>(), [&] { eh::layout(n, rects, offsets); });
 }
 
 int rtd_esrgan_upscale(rtd_esrgan_handle e, int32_t n, const uint8_t* const* frames_dev, const int32_t* frame_hw, const int32_t* rects,
@@ -443,15 +378,15 @@ int rtd_esrgan_upscale(rtd_esrgan_handle e, int32_t n, const uint8_t* const* fra
 int64_t rtd_esrgan_arena_bytes(rtd_esrgan_handle e) {
   if (!e) return 0;
   std::lock_guard<std::mutex> lk(e->mu);
-  return (int64_t)e->arena_bytes;
+  return (int64_t)e->arena.cap;
 }
 
-const char* rtd_esrgan_last_error(rtd_esrgan_handle e) { return e ? e->err.c_str() : g_create_error.c_str(); }
+const char* rtd_esrgan_last_error(rtd_esrgan_handle e) { return bk::last_error(e); }
 
 void rtd_esrgan_destroy(rtd_esrgan_handle e) {
   if (!e) return;
-  (void)hipSetDevice(e->cfg.device);
-  if (e->arena) (void)hipFree(e->arena);        // (hipFree waits for the device: nothing enqueued still uses the arena or the filters)
+  (void)hipSetDevice(e->device);
+  e->arena.release();                           // (hipFree waits for the device: nothing enqueued still uses the arena or the filters)
   for (void* q : e->allocs) (void)hipFree(q);
   (void)hipGetLastError();
   delete e;
@@ -475,11 +410,11 @@ int rtd_debug_esrgan_tensor(rtd_esrgan_handle e, const char* name, float* out, i
     const int64_t numel = t.pixels() * t.c;
     if (!out) return;
     RTD_CHECK(capacity >= numel, RTD_E_INVALID, "debug tensor: output capacity too small");
-    HIP_CHECK(hipSetDevice(e->cfg.device));
+    HIP_CHECK(hipSetDevice(e->device));
     hipStream_t s = e->last_stream;
     run_ingest(e, p, e->last_src, e->last_pitch, s);
     for (size_t i = 0; i < upto; ++i) run_op(e, p, p->ops[i], s);
-    t = based(t, e->arena);
+    t = based(t, (char*)e->arena.p);
     float* f32 = nullptr;
     HIP_CHECK(hipMalloc((void**)&f32, (size_t)numel * 4));
     hipError_t er = hipSuccess;

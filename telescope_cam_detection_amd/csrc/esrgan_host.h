@@ -11,15 +11,12 @@
 #include <vector>
 
 #include "../../include/rtdetr_mi355.h"
+#include "error.h"
 
 namespace esrgan_host {
 
-struct Fail {
-  int code;
-  std::string msg;
-};
-inline void need(bool ok, int code, const std::string& msg) {
-  if (!ok) throw Fail{code, msg};
+inline void need(bool ok, int code, const std::string& msg) {   // (the plain message: callers match on it)
+  if (!ok) throw rtd::Error(code, msg);
 }
 
 constexpr int SCALE = 4;

@@ -21,11 +21,14 @@
 
 #include "../../include/rtdetr_mi355.h"
 #include "../../include/rtdetr_mi355_test.h"
-#include "common.h"
+#include "backend.h"
 
 namespace jpeg_enc {
 
 using rtd::Error;
+namespace bk = rtd::backend;
+using bk::align_up;
+using bk::guarded;
 
 constexpr int TILE_W = 128, TILE_H = 16;
 constexpr int T_THREADS = 384;               // 48 blocks x 8 threads
@@ -592,92 +595,31 @@ static std::vector<uint8_t> make_headers(int H, int W, int C, int quality) {
   return o;
 }
 
-static std::string g_jpeg_create_error;
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct Buf {                 // a device buffer grown on demand (contents are not kept)
-  uint8_t* p = nullptr;
-  size_t cap = 0;
-  void reserve(size_t bytes) {
-    if (bytes <= cap) return;
-    const size_t want = std::max(bytes, cap * 2);
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-    HIP_CHECK(hipMalloc((void**)&p, want));
-    cap = want;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
 }  // namespace jpeg_enc
 
 using namespace jpeg_enc;
 
-struct rtd_jpeg {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_xs = nullptr;
-  std::mutex mu;
-  std::string err;
-  uint8_t* pin = nullptr;    // pinned: [descriptors | tables | host frames] on the way in, the sizes and the stuffed scans on the way out
-  size_t pin_cap = 0;
-  Buf in, coef, side, blk_off, chunks, sizes, ustream, scnt, out;
+struct rtd_jpeg : bk::Base {
+  bk::OwnStream q;
+  bk::PinBuf pin;            // pinned: [descriptors | tables | host frames] on the way in, the sizes and the stuffed scans on the way out
+  bk::DevBuf in, coef, side, blk_off, chunks, sizes, ustream, scnt, out;
   std::map<std::tuple<int, int, int, int>, std::vector<uint8_t>> headers;   // the marker block per (H, W, C, quality), built once
   int64_t last_values = 0;   // int16 coefficients of the last call
 };
 
 namespace jpeg_enc {
 
-template <typename F>
-static int guarded(rtd_jpeg* j, F&& f) {
-  if (!j) return RTD_E_INVALID;
-  std::lock_guard<std::mutex> lk(j->mu);
-  try {
-    f();
-    return RTD_OK;
-  } catch (const Error& er) {
-    j->err = er.what();
-    return er.code;
-  } catch (const std::bad_alloc&) {
-    j->err = "host allocation failed";
-    return RTD_E_OOM;
-  } catch (const std::exception& ex) {
-    j->err = ex.what();
-    return RTD_E_HIP;
-  }
-}
-
-static void reserve_pinned(rtd_jpeg* j, size_t bytes) {
-  if (bytes <= j->pin_cap) return;
-  const size_t cap = std::max(bytes, j->pin_cap * 2);
-  if (j->pin) (void)hipHostFree(j->pin);
-  j->pin = nullptr;
-  j->pin_cap = 0;
-  HIP_CHECK(hipHostMalloc((void**)&j->pin, cap, hipHostMallocDefault));
-  j->pin_cap = cap;
-}
-
 static void encode(rtd_jpeg* j, int n, const uint8_t* const* frames, const int32_t* hwc, int on_device, int quality, uint8_t* out,
                    int64_t out_cap, int64_t* offsets) {
-  hipStream_t s = j->stream;
+  hipStream_t s = j->q.stream;
   // ---- layout of the upload: descriptors, tables, host frames
   const size_t tab_off = align_up(sizeof(FrameDesc) * n, 256);
   const size_t frames_off = align_up(tab_off + sizeof(Tables), 256);
-  size_t total = frames_off;
-  std::vector<size_t> foff(n);
-  for (int i = 0; i < n; ++i) {
-    foff[i] = total;
-    if (!on_device) total = align_up(total + (size_t)hwc[3 * i] * hwc[3 * i + 1] * hwc[3 * i + 2], 256);
-  }
-  reserve_pinned(j, std::max(total, frames_off + (size_t)(n + 1) * 4));      // (the sizes come back through the frames' staging area)
+  std::vector<size_t> foff;
+  const size_t total = bk::stage_offsets(n, hwc, on_device, frames_off, foff);
+  j->pin.reserve(std::max(total, frames_off + (size_t)(n + 1) * 4));      // (the sizes come back through the frames' staging area)
   j->in.reserve(total);
-  FrameDesc* descs = (FrameDesc*)j->pin;
+  FrameDesc* descs = (FrameDesc*)j->pin.p;
   int tiles = 0, blocks = 0, chunks = 0;
   for (int i = 0; i < n; ++i) {
     const int H = hwc[3 * i], W = hwc[3 * i + 1], C = hwc[3 * i + 2];
@@ -699,9 +641,9 @@ static void encode(rtd_jpeg* j, int n, const uint8_t* const* frames, const int32
     d.chunk0 = chunks;
     d.nchunks = (d.nblocks + CHUNK - 1) / CHUNK;
     chunks += d.nchunks;
-    if (!on_device) memcpy(j->pin + foff[i], frames[i], (size_t)H * W * C);
+    if (!on_device) memcpy(j->pin.p + foff[i], frames[i], (size_t)H * W * C);
   }
-  make_tables(quality, *(Tables*)(j->pin + tab_off));
+  make_tables(quality, *(Tables*)(j->pin.p + tab_off));
   j->coef.reserve((size_t)blocks * 128);
   j->side.reserve((size_t)blocks * 4);
   j->blk_off.reserve((size_t)blocks * 4);
@@ -717,12 +659,12 @@ static void encode(rtd_jpeg* j, int n, const uint8_t* const* frames, const int32
   j->last_values = 0;
 
   // ---- transform, size, scan: the bit count of every frame comes back
-  HIP_CHECK(hipMemcpyAsync(j->in.p, j->pin, total, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(j->in.p, j->pin.p, total, hipMemcpyHostToDevice, s));
   rtd::rtd_launch(transform_kernel, dim3(tiles), dim3(T_THREADS), 0, s, ddev, n, tdev, coef, side);
   rtd::rtd_launch(size_kernel, dim3(chunks), dim3(CHUNK), 0, s, ddev, n, tdev, (const uint32_t*)side, blk_off, chunk_bits);
   rtd::rtd_launch(chunk_scan_kernel, dim3(1), dim3(256), 0, s, ddev, n, chunk_bits, sizes);
   HIP_CHECK(hipGetLastError());
-  uint32_t* got = (uint32_t*)(j->pin + frames_off);            // (the staged frames are on the device by then: stream order)
+  uint32_t* got = (uint32_t*)(j->pin.p + frames_off);            // (the staged frames are on the device by then: stream order)
   HIP_CHECK(hipMemcpyAsync(got, sizes, (size_t)n * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
   j->last_values = (int64_t)blocks * 64;
@@ -744,7 +686,7 @@ static void encode(rtd_jpeg* j, int n, const uint8_t* const* frames, const int32
   j->out.reserve(2 * ubytes + 8);                              // every byte could be 0xFF
   j->scnt.reserve((size_t)(schunks + 1) * 4);
   uint32_t* scnt = (uint32_t*)j->scnt.p;
-  HIP_CHECK(hipMemcpyAsync(j->in.p, j->pin, sizeof(FrameDesc) * n, hipMemcpyHostToDevice, s));
+  HIP_CHECK(hipMemcpyAsync(j->in.p, j->pin.p, sizeof(FrameDesc) * n, hipMemcpyHostToDevice, s));
   HIP_CHECK(hipMemsetAsync(j->ustream.p, 0, ubytes + 8, s));
   rtd::rtd_launch(write_kernel, dim3(2 * chunks), dim3(W_BLOCKS), 0, s, ddev, n, tdev, (const uint4*)coef, (const uint32_t*)side,
                   (const uint32_t*)blk_off, (const uint32_t*)chunk_bits, (uint32_t*)j->ustream.p);
@@ -770,16 +712,16 @@ static void encode(rtd_jpeg* j, int n, const uint8_t* const* frames, const int32
   }
   offsets[n] = need;
   RTD_CHECK(out_cap >= need, RTD_E_INVALID, "out_cap is " + std::to_string(out_cap) + " bytes, " + std::to_string(need) + " are needed");
-  reserve_pinned(j, start[n]);
+  j->pin.reserve(start[n]);
   if (start[n]) {
-    HIP_CHECK(hipMemcpyAsync(j->pin, j->out.p, start[n], hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipMemcpyAsync(j->pin.p, j->out.p, start[n], hipMemcpyDeviceToHost, s));
     HIP_CHECK(hipStreamSynchronize(s));
   }
   for (int i = 0; i < n; ++i) {
     uint8_t* o = out + offsets[i];
     memcpy(o, hdr[i]->data(), hdr[i]->size());
     o += hdr[i]->size();
-    memcpy(o, j->pin + start[i], start[i + 1] - start[i]);
+    memcpy(o, j->pin.p + start[i], start[i + 1] - start[i]);
     o += start[i + 1] - start[i];
     o[0] = 0xFF;
     o[1] = 0xD9;
@@ -791,25 +733,11 @@ static void encode(rtd_jpeg* j, int n, const uint8_t* const* frames, const int32
 extern "C" {
 
 int rtd_jpeg_create(int32_t device, rtd_jpeg_handle* out) {
-  if (!out) return RTD_E_INVALID;
-  *out = nullptr;
-  rtd_jpeg* j = new (std::nothrow) rtd_jpeg();
-  if (!j) return RTD_E_OOM;
-  try {
-    int count = 0;
-    HIP_CHECK(hipGetDeviceCount(&count));
-    RTD_CHECK(device >= 0 && device < count, RTD_E_INVALID, "no such device");
+  return bk::create(out, rtd_jpeg_destroy, [&](rtd_jpeg* j) {
+    bk::use_device(device);
     j->device = device;
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreateWithFlags(&j->stream, hipStreamNonBlocking));
-    HIP_CHECK(hipEventCreateWithFlags(&j->ev_xs, hipEventDisableTiming));
-  } catch (const Error& er) {
-    g_jpeg_create_error = er.what();
-    rtd_jpeg_destroy(j);
-    return er.code;
-  }
-  *out = j;
-  return RTD_OK;
+    j->q.open();
+  });
 }
 
 int rtd_jpeg_encode(rtd_jpeg_handle j, int32_t n, const uint8_t* const* frames, const int32_t* hwc, int32_t frames_on_device, int32_t quality,
@@ -833,7 +761,7 @@ int rtd_jpeg_encode(rtd_jpeg_handle j, int32_t n, const uint8_t* const* frames, 
     try {
       encode(j, n, frames, hwc, frames_on_device, quality, out, out_cap, offsets);
     } catch (...) {
-      (void)hipStreamSynchronize(j->stream);               // nothing of a failed call may still read the staging buffers
+      j->q.drain();                                        // nothing of a failed call may still read the staging buffers
       throw;
     }
   });
@@ -842,21 +770,19 @@ int rtd_jpeg_encode(rtd_jpeg_handle j, int32_t n, const uint8_t* const* frames, 
 int rtd_jpeg_wait_stream(rtd_jpeg_handle j, void* producer_stream) {
   return guarded(j, [&] {
     HIP_CHECK(hipSetDevice(j->device));
-    HIP_CHECK(hipEventRecord(j->ev_xs, (hipStream_t)producer_stream));
-    HIP_CHECK(hipStreamWaitEvent(j->stream, j->ev_xs, 0));
+    j->q.wait_for(producer_stream);
   });
 }
 
-const char* rtd_jpeg_last_error(rtd_jpeg_handle j) { return j ? j->err.c_str() : g_jpeg_create_error.c_str(); }
+const char* rtd_jpeg_last_error(rtd_jpeg_handle j) { return bk::last_error(j); }
 
 void rtd_jpeg_destroy(rtd_jpeg_handle j) {
   if (!j) return;
   (void)hipSetDevice(j->device);
-  if (j->stream) (void)hipStreamSynchronize(j->stream);
-  for (Buf* b : {&j->in, &j->coef, &j->side, &j->blk_off, &j->chunks, &j->sizes, &j->ustream, &j->scnt, &j->out}) b->release();
-  if (j->pin) (void)hipHostFree(j->pin);
-  if (j->ev_xs) (void)hipEventDestroy(j->ev_xs);
-  if (j->stream) (void)hipStreamDestroy(j->stream);
+  j->q.drain();
+  for (bk::DevBuf* b : {&j->in, &j->coef, &j->side, &j->blk_off, &j->chunks, &j->sizes, &j->ustream, &j->scnt, &j->out}) b->release();
+  j->pin.release();
+  j->q.close();
   delete j;
 }
 
@@ -868,8 +794,8 @@ int rtd_debug_jpeg_coefficients(rtd_jpeg_handle j, int16_t* out, int64_t capacit
     RTD_CHECK(capacity >= j->last_values, RTD_E_INVALID, "output buffer too small");
     if (!j->last_values) return;
     HIP_CHECK(hipSetDevice(j->device));
-    HIP_CHECK(hipMemcpyAsync(out, j->coef.p, (size_t)j->last_values * 2, hipMemcpyDeviceToHost, j->stream));
-    HIP_CHECK(hipStreamSynchronize(j->stream));
+    HIP_CHECK(hipMemcpyAsync(out, j->coef.p, (size_t)j->last_values * 2, hipMemcpyDeviceToHost, j->q.stream));
+    HIP_CHECK(hipStreamSynchronize(j->q.stream));
   });
 }
 

@@ -21,7 +21,7 @@
 
 #include "../../include/rtdetr_mi355.h"
 #include "../../include/rtdetr_mi355_test.h"
-#include "common.h"
+#include "backend.h"
 #include "gauss8.h"
 
 #pragma clang fp contract(off)
@@ -29,6 +29,9 @@
 namespace mog2 {
 
 using rtd::Error;
+namespace bk = rtd::backend;
+using bk::align_up;
+using bk::guarded;
 using gauss8::MAX_R;
 using gauss8::Taps;
 using gauss8::reflect101;
@@ -274,23 +277,15 @@ static void launch_roi(int r, dim3 grid, hipStream_t s, const RoiDesc* descs, in
   if constexpr (R < MAX_R) launch_roi<R + 1>(r, grid, s, descs, n, bits, rows, cols, taps, counts);
 }
 
-static std::string g_mog2_create_error;
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 }  // namespace mog2
 
 using namespace mog2;
 
-struct rtd_mog2 {
-  int device = 0;
+struct rtd_mog2 : bk::Base {
   int history = 500;
   float tb = 16.f;
   int shadows = 1;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_xs = nullptr;
-  std::mutex mu;
-  std::string err;
+  bk::OwnStream q;
   // the model: [NM][2 + C][rows * cols] float planes, then rows * cols modes-used bytes (allocated on the first frame, reallocated on a
   // size or channel change)
   uint8_t* state = nullptr;
@@ -298,37 +293,16 @@ struct rtd_mog2 {
   bool fresh = true;                         // the next update initialises the model (a new subtractor, or a new frame geometry)
   int64_t nframes = 0;
   // foreground words of the last call, [chunks][rows * cols]; grown on demand
-  uint32_t* bits = nullptr;
-  size_t bits_cap = 0;                       // words
+  bk::DevBuf bits;
   int last_chunks = 0;
   // one upload per call: [box descriptors | counters | host frame]; pinned on the host, mirrored on the device, grown on demand
-  uint8_t* pin = nullptr;
-  uint8_t* dev = nullptr;
-  size_t cap = 0;
+  bk::PinBuf pin;
+  bk::DevBuf dev;
   int taps_k = 0;
   Taps taps{};
 };
 
 namespace mog2 {
-
-template <typename F>
-static int guarded(rtd_mog2* g, F&& f) {
-  if (!g) return RTD_E_INVALID;
-  std::lock_guard<std::mutex> lk(g->mu);
-  try {
-    f();
-    return RTD_OK;
-  } catch (const Error& er) {
-    g->err = er.what();
-    return er.code;
-  } catch (const std::bad_alloc&) {
-    g->err = "host allocation failed";
-    return RTD_E_OOM;
-  } catch (const std::exception& ex) {
-    g->err = ex.what();
-    return RTD_E_HIP;
-  }
-}
 
 static size_t npix(const rtd_mog2* g) { return (size_t)g->rows * g->cols; }
 static size_t plane_bytes(const rtd_mog2* g) { return (size_t)NM * (2 + g->ch) * npix(g) * sizeof(float); }
@@ -336,19 +310,6 @@ static size_t plane_bytes(const rtd_mog2* g) { return (size_t)NM * (2 + g->ch) *
 static void check_params(int32_t history, double var_threshold) {
   RTD_CHECK(history >= 1, RTD_E_INVALID, "history must be >= 1, got " + std::to_string(history));
   RTD_CHECK(std::isfinite(var_threshold), RTD_E_INVALID, "var_threshold must be finite");
-}
-
-static void reserve(rtd_mog2* g, size_t bytes) {
-  if (bytes <= g->cap) return;
-  const size_t cap = std::max(bytes, g->cap * 2);
-  if (g->pin) (void)hipHostFree(g->pin);
-  if (g->dev) (void)hipFree(g->dev);
-  g->pin = nullptr;
-  g->dev = nullptr;
-  g->cap = 0;
-  HIP_CHECK(hipHostMalloc((void**)&g->pin, cap, hipHostMallocDefault));
-  HIP_CHECK(hipMalloc((void**)&g->dev, cap));
-  g->cap = cap;
 }
 
 // the model for a rows x cols x ch frame: a new geometry frees the old buffer and allocates a new one (OpenCV re-initialises on it too)
@@ -368,13 +329,7 @@ static void ensure_model(rtd_mog2* g, int rows, int cols, int ch) {
 static void apply(rtd_mog2* g, const uint8_t* frame, int on_device, int n, const int32_t* rects, int blur_size, int64_t* counts) {
   const size_t P = npix(g);
   const int chunks = (n + CHUNK - 1) / CHUNK;
-  if ((size_t)chunks * P > g->bits_cap) {
-    if (g->bits) (void)hipFree(g->bits);
-    g->bits = nullptr;
-    g->bits_cap = 0;
-    HIP_CHECK(hipMalloc((void**)&g->bits, (size_t)chunks * P * sizeof(uint32_t)));
-    g->bits_cap = (size_t)chunks * P;
-  }
+  g->bits.reserve((size_t)chunks * P * sizeof(uint32_t));
   if (g->taps_k != blur_size) {
     gauss8::make_taps(blur_size, g->taps);
     g->taps_k = blur_size;
@@ -382,8 +337,12 @@ static void apply(rtd_mog2* g, const uint8_t* frame, int on_device, int n, const
   const size_t cnt_off = align_up(sizeof(RoiDesc) * n, 256);
   const size_t frame_off = align_up(cnt_off + sizeof(unsigned int) * n, 256);
   const size_t total = on_device ? frame_off : frame_off + P * g->ch;
-  reserve(g, total);
-  RoiDesc* descs = (RoiDesc*)g->pin;
+  g->pin.reserve(total);
+  g->dev.reserve(total);
+  hipStream_t st = g->q.stream;
+  uint8_t *pin = g->pin.p, *dev = g->dev.p;
+  uint32_t* bits = (uint32_t*)g->bits.p;
+  RoiDesc* descs = (RoiDesc*)pin;
   int nd = 0, tiles = 0;
   for (int i = 0; i < n; ++i) {
     const int32_t* r = rects + 4 * i;
@@ -397,18 +356,18 @@ static void apply(rtd_mog2* g, const uint8_t* frame, int on_device, int n, const
     d.out = i;
     tiles += d.tiles_x * ((r[3] - r[1] + TH - 1) / TH);
   }
-  memset(g->pin + cnt_off, 0, sizeof(unsigned int) * n);
-  if (!on_device) memcpy(g->pin + frame_off, frame, P * g->ch);
-  HIP_CHECK(hipMemcpyAsync(g->dev, g->pin, total, hipMemcpyHostToDevice, g->stream));
+  memset(pin + cnt_off, 0, sizeof(unsigned int) * n);
+  if (!on_device) memcpy(pin + frame_off, frame, P * g->ch);
+  HIP_CHECK(hipMemcpyAsync(dev, pin, total, hipMemcpyHostToDevice, st));
   if (g->fresh) {                                 // a new model: all zeros, nframes = 0
-    HIP_CHECK(hipMemsetAsync(g->state, 0, plane_bytes(g) + P, g->stream));
+    HIP_CHECK(hipMemsetAsync(g->state, 0, plane_bytes(g) + P, st));
     g->nframes = 0;
     g->fresh = false;
   }
   StateArgs a;
   a.planes = (float*)g->state;
   a.modes = g->state + plane_bytes(g);
-  a.frame = on_device ? frame : g->dev + frame_off;
+  a.frame = on_device ? frame : dev + frame_off;
   a.npix = (int)P;
   a.tb = g->tb;
   a.shadows = g->shadows;
@@ -422,21 +381,21 @@ static void apply(rtd_mog2* g, const uint8_t* frame, int on_device, int n, const
       chunk.alpha_t[j] = (float)lr;
       chunk.prune[j] = (float)(-lr * FCT);
     }
-    a.bits = g->bits + (size_t)c * P;
-    if (g->ch == 3) rtd::rtd_launch(mog2_state_kernel<3>, grid, dim3(STATE_THREADS), 0, g->stream, a, chunk);
-    else rtd::rtd_launch(mog2_state_kernel<1>, grid, dim3(STATE_THREADS), 0, g->stream, a, chunk);
+    a.bits = bits + (size_t)c * P;
+    if (g->ch == 3) rtd::rtd_launch(mog2_state_kernel<3>, grid, dim3(STATE_THREADS), 0, st, a, chunk);
+    else rtd::rtd_launch(mog2_state_kernel<1>, grid, dim3(STATE_THREADS), 0, st, a, chunk);
     HIP_CHECK(hipGetLastError());
   }
   g->last_chunks = chunks;
-  unsigned int* dcounts = (unsigned int*)(g->dev + cnt_off);
+  unsigned int* dcounts = (unsigned int*)(dev + cnt_off);
   if (tiles) {
-    launch_roi<0>(g->taps.radius, dim3(tiles), g->stream, (const RoiDesc*)g->dev, nd, g->bits, g->rows, g->cols, g->taps, dcounts);
+    launch_roi<0>(g->taps.radius, dim3(tiles), st, (const RoiDesc*)dev, nd, bits, g->rows, g->cols, g->taps, dcounts);
     HIP_CHECK(hipGetLastError());
   }
   // the counters come back through the start of the pinned buffer (the descriptors there are no longer needed)
-  HIP_CHECK(hipMemcpyAsync(g->pin, dcounts, sizeof(unsigned int) * n, hipMemcpyDeviceToHost, g->stream));
-  HIP_CHECK(hipStreamSynchronize(g->stream));
-  const unsigned int* got = (const unsigned int*)g->pin;
+  HIP_CHECK(hipMemcpyAsync(pin, dcounts, sizeof(unsigned int) * n, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  const unsigned int* got = (const unsigned int*)pin;
   for (int i = 0; i < n; ++i) counts[i] = (int64_t)got[i];
 }
 
@@ -445,29 +404,15 @@ static void apply(rtd_mog2* g, const uint8_t* frame, int on_device, int n, const
 extern "C" {
 
 int rtd_mog2_create(int32_t device, int32_t history, double var_threshold, int32_t detect_shadows, rtd_mog2_handle* out) {
-  if (!out) return RTD_E_INVALID;
-  *out = nullptr;
-  rtd_mog2* g = new (std::nothrow) rtd_mog2();
-  if (!g) return RTD_E_OOM;
-  try {
+  return bk::create(out, rtd_mog2_destroy, [&](rtd_mog2* g) {
     check_params(history, var_threshold);
-    int count = 0;
-    HIP_CHECK(hipGetDeviceCount(&count));
-    RTD_CHECK(device >= 0 && device < count, RTD_E_INVALID, "no such device");
+    bk::use_device(device);
     g->device = device;
     g->history = history;
     g->tb = (float)var_threshold;
     g->shadows = detect_shadows ? 1 : 0;
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreateWithFlags(&g->stream, hipStreamNonBlocking));
-    HIP_CHECK(hipEventCreateWithFlags(&g->ev_xs, hipEventDisableTiming));
-  } catch (const Error& er) {
-    g_mog2_create_error = er.what();
-    rtd_mog2_destroy(g);
-    return er.code;
-  }
-  *out = g;
-  return RTD_OK;
+    g->q.open();
+  });
 }
 
 int rtd_mog2_configure(rtd_mog2_handle g, int32_t history, double var_threshold, int32_t detect_shadows) {
@@ -502,7 +447,7 @@ int rtd_mog2_apply(rtd_mog2_handle g, const uint8_t* frame, const int32_t* hwc, 
     try {
       mog2::apply(g, frame, frame_on_device, n, rects, blur_size, counts);
     } catch (...) {
-      (void)hipStreamSynchronize(g->stream);   // nothing of a failed launch may still read the staging buffers
+      g->q.drain();                            // nothing of a failed launch may still read the staging buffers
       throw;
     }
   });
@@ -511,23 +456,21 @@ int rtd_mog2_apply(rtd_mog2_handle g, const uint8_t* frame, const int32_t* hwc, 
 int rtd_mog2_wait_stream(rtd_mog2_handle g, void* producer_stream) {
   return guarded(g, [&] {
     HIP_CHECK(hipSetDevice(g->device));
-    HIP_CHECK(hipEventRecord(g->ev_xs, (hipStream_t)producer_stream));
-    HIP_CHECK(hipStreamWaitEvent(g->stream, g->ev_xs, 0));
+    g->q.wait_for(producer_stream);
   });
 }
 
-const char* rtd_mog2_last_error(rtd_mog2_handle g) { return g ? g->err.c_str() : g_mog2_create_error.c_str(); }
+const char* rtd_mog2_last_error(rtd_mog2_handle g) { return bk::last_error(g); }
 
 void rtd_mog2_destroy(rtd_mog2_handle g) {
   if (!g) return;
   (void)hipSetDevice(g->device);
-  if (g->stream) (void)hipStreamSynchronize(g->stream);
+  g->q.drain();
   if (g->state) (void)hipFree(g->state);
-  if (g->bits) (void)hipFree(g->bits);
-  if (g->pin) (void)hipHostFree(g->pin);
-  if (g->dev) (void)hipFree(g->dev);
-  if (g->ev_xs) (void)hipEventDestroy(g->ev_xs);
-  if (g->stream) (void)hipStreamDestroy(g->stream);
+  g->bits.release();
+  g->dev.release();
+  g->pin.release();
+  g->q.close();
   delete g;
 }
 
@@ -547,9 +490,9 @@ int rtd_debug_mog2_model(rtd_mog2_handle g, int32_t* hwc, int64_t* nframes, floa
     const int C = g->ch, F = 2 + C;
     std::vector<float> planes(plane_bytes(g) / sizeof(float));
     HIP_CHECK(hipSetDevice(g->device));
-    HIP_CHECK(hipMemcpyAsync(planes.data(), g->state, plane_bytes(g), hipMemcpyDeviceToHost, g->stream));
-    HIP_CHECK(hipMemcpyAsync(modes_used, g->state + plane_bytes(g), P, hipMemcpyDeviceToHost, g->stream));
-    HIP_CHECK(hipStreamSynchronize(g->stream));
+    HIP_CHECK(hipMemcpyAsync(planes.data(), g->state, plane_bytes(g), hipMemcpyDeviceToHost, g->q.stream));
+    HIP_CHECK(hipMemcpyAsync(modes_used, g->state + plane_bytes(g), P, hipMemcpyDeviceToHost, g->q.stream));
+    HIP_CHECK(hipStreamSynchronize(g->q.stream));
     for (size_t p = 0; p < P; ++p)
       for (int m = 0; m < NM; ++m) {
         weight[p * NM + m] = planes[(m * F + 0) * P + p];
@@ -565,8 +508,8 @@ int rtd_debug_mog2_fg_bits(rtd_mog2_handle g, uint32_t* out, size_t nwords) {
     const size_t words = (size_t)g->last_chunks * npix(g);
     RTD_CHECK(out && nwords >= words, RTD_E_INVALID, "output buffer too small");
     HIP_CHECK(hipSetDevice(g->device));
-    HIP_CHECK(hipMemcpyAsync(out, g->bits, words * sizeof(uint32_t), hipMemcpyDeviceToHost, g->stream));
-    HIP_CHECK(hipStreamSynchronize(g->stream));
+    HIP_CHECK(hipMemcpyAsync(out, g->bits.p, words * sizeof(uint32_t), hipMemcpyDeviceToHost, g->q.stream));
+    HIP_CHECK(hipStreamSynchronize(g->q.stream));
   });
 }
 

@@ -16,12 +16,15 @@
 
 #include "../../include/rtdetr_mi355.h"
 #include "../../include/rtdetr_mi355_test.h"
-#include "common.h"
+#include "backend.h"
 #include "gauss8.h"
 
 namespace motion_gate {
 
 using rtd::Error;
+namespace bk = rtd::backend;
+using bk::align_up;
+using bk::guarded;
 using gauss8::MAX_R;
 using gauss8::Taps;
 using gauss8::reflect101;
@@ -116,61 +119,20 @@ struct Slot {
   bool valid = false;       // holds a blurred frame to compare with
 };
 
-static std::string g_motion_create_error;
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 }  // namespace motion_gate
 
 using namespace motion_gate;
 
-struct rtd_motion {
-  int device = 0;
+struct rtd_motion : bk::Base {
   Taps taps{};
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_xs = nullptr;
-  std::mutex mu;
-  std::string err;
+  bk::OwnStream q;
   std::map<int, Slot> slots;
   // one upload per launch: [descriptors | area counters | host frames]; pinned on the host, mirrored on the device, grown on demand
-  uint8_t* pin = nullptr;
-  uint8_t* dev = nullptr;
-  size_t cap = 0;
+  bk::PinBuf pin;
+  bk::DevBuf dev;
 };
 
 namespace motion_gate {
-
-template <typename F>
-static int guarded(rtd_motion* m, F&& f) {
-  if (!m) return RTD_E_INVALID;
-  std::lock_guard<std::mutex> lk(m->mu);
-  try {
-    f();
-    return RTD_OK;
-  } catch (const Error& er) {
-    m->err = er.what();
-    return er.code;
-  } catch (const std::bad_alloc&) {
-    m->err = "host allocation failed";
-    return RTD_E_OOM;
-  } catch (const std::exception& ex) {
-    m->err = ex.what();
-    return RTD_E_HIP;
-  }
-}
-
-static void reserve(rtd_motion* m, size_t bytes) {
-  if (bytes <= m->cap) return;
-  const size_t cap = std::max(bytes, m->cap * 2);
-  if (m->pin) (void)hipHostFree(m->pin);
-  if (m->dev) (void)hipFree(m->dev);
-  m->pin = nullptr;
-  m->dev = nullptr;
-  m->cap = 0;
-  HIP_CHECK(hipHostMalloc((void**)&m->pin, cap, hipHostMallocDefault));
-  HIP_CHECK(hipMalloc((void**)&m->dev, cap));
-  m->cap = cap;
-}
 
 // one launch over frames [b, e) of the call, whose slots are all distinct
 static void launch(rtd_motion* m, int b, int e, const uint8_t* const* frames, const int32_t* hwc, int on_device, const int32_t* slots,
@@ -178,15 +140,13 @@ static void launch(rtd_motion* m, int b, int e, const uint8_t* const* frames, co
   const int n = e - b;
   const size_t area_off = align_up(sizeof(FrameDesc) * n, 256);
   const size_t frames_off = align_up(area_off + sizeof(unsigned int) * n, 256);
-  size_t total = frames_off;
-  std::vector<size_t> foff(n);
-  for (int i = 0; i < n; ++i) {
-    const int32_t* s = hwc + 3 * (b + i);
-    foff[i] = total;
-    if (!on_device) total = align_up(total + (size_t)s[0] * s[1] * s[2], 256);
-  }
-  reserve(m, total);
-  FrameDesc* descs = (FrameDesc*)m->pin;
+  std::vector<size_t> foff;
+  const size_t total = bk::stage_offsets(n, hwc + 3 * b, on_device, frames_off, foff);
+  m->pin.reserve(total);
+  m->dev.reserve(total);
+  hipStream_t st = m->q.stream;
+  uint8_t *pin = m->pin.p, *dev = m->dev.p;
+  FrameDesc* descs = (FrameDesc*)pin;
   int tiles = 0;
   std::vector<char> first(n);
   for (int i = 0; i < n; ++i) {
@@ -205,7 +165,7 @@ static void launch(rtd_motion* m, int b, int e, const uint8_t* const* frames, co
       sl.cols = s[1];
     }
     FrameDesc& d = descs[i];
-    d.src = on_device ? frames[b + i] : m->dev + foff[i];
+    d.src = on_device ? frames[b + i] : dev + foff[i];
     d.state = sl.buf;
     d.rows = s[0];
     d.cols = s[1];
@@ -214,17 +174,16 @@ static void launch(rtd_motion* m, int b, int e, const uint8_t* const* frames, co
     d.tiles_x = (s[1] + TW - 1) / TW;
     d.tile0 = tiles;
     tiles += d.tiles_x * ((s[0] + TH - 1) / TH);
-    if (!on_device) memcpy(m->pin + foff[i], frames[b + i], (size_t)s[0] * s[1] * s[2]);
+    if (!on_device) memcpy(pin + foff[i], frames[b + i], (size_t)s[0] * s[1] * s[2]);
   }
-  memset(m->pin + area_off, 0, sizeof(unsigned int) * n);
-  HIP_CHECK(hipMemcpyAsync(m->dev, m->pin, total, hipMemcpyHostToDevice, m->stream));
-  launch_radius<0>(m->taps.radius, dim3(tiles), m->stream, (const FrameDesc*)m->dev, n, m->taps, threshold,
-                   (unsigned int*)(m->dev + area_off));
+  memset(pin + area_off, 0, sizeof(unsigned int) * n);
+  HIP_CHECK(hipMemcpyAsync(dev, pin, total, hipMemcpyHostToDevice, st));
+  launch_radius<0>(m->taps.radius, dim3(tiles), st, (const FrameDesc*)dev, n, m->taps, threshold, (unsigned int*)(dev + area_off));
   HIP_CHECK(hipGetLastError());
   // the counters come back through the start of the pinned buffer (the descriptors there are no longer needed)
-  HIP_CHECK(hipMemcpyAsync(m->pin, m->dev + area_off, sizeof(unsigned int) * n, hipMemcpyDeviceToHost, m->stream));
-  HIP_CHECK(hipStreamSynchronize(m->stream));
-  const unsigned int* got = (const unsigned int*)m->pin;
+  HIP_CHECK(hipMemcpyAsync(pin, dev + area_off, sizeof(unsigned int) * n, hipMemcpyDeviceToHost, st));
+  HIP_CHECK(hipStreamSynchronize(st));
+  const unsigned int* got = (const unsigned int*)pin;
   for (int i = 0; i < n; ++i) {
     area[b + i] = first[i] ? -1 : (int64_t)got[i];
     m->slots[slots[b + i]].valid = true;
@@ -236,30 +195,17 @@ static void launch(rtd_motion* m, int b, int e, const uint8_t* const* frames, co
 extern "C" {
 
 int rtd_motion_create(int32_t device, int32_t blur_size, rtd_motion_handle* out) {
-  if (!out) return RTD_E_INVALID;
-  *out = nullptr;
-  if (blur_size < 1 || blur_size > 2 * MAX_R + 1 || blur_size % 2 == 0) {
-    g_motion_create_error = "blur_size must be odd and in 1..63, got " + std::to_string(blur_size);
+  if (out && (blur_size < 1 || blur_size > 2 * MAX_R + 1 || blur_size % 2 == 0)) {   // refused before a handle exists: no HIP call is made
+    *out = nullptr;
+    bk::create_error<rtd_motion>() = "blur_size must be odd and in 1..63, got " + std::to_string(blur_size);
     return RTD_E_INVALID;
   }
-  rtd_motion* m = new (std::nothrow) rtd_motion();
-  if (!m) return RTD_E_OOM;
-  try {
-    int count = 0;
-    HIP_CHECK(hipGetDeviceCount(&count));
-    RTD_CHECK(device >= 0 && device < count, RTD_E_INVALID, "no such device");
+  return bk::create(out, rtd_motion_destroy, [&](rtd_motion* m) {
+    bk::use_device(device);
     m->device = device;
     gauss8::make_taps(blur_size, m->taps);
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
-    HIP_CHECK(hipEventCreateWithFlags(&m->ev_xs, hipEventDisableTiming));
-  } catch (const Error& er) {
-    g_motion_create_error = er.what();
-    rtd_motion_destroy(m);
-    return er.code;
-  }
-  *out = m;
-  return RTD_OK;
+    m->q.open();
+  });
 }
 
 int rtd_motion_check(rtd_motion_handle m, int32_t n, const uint8_t* const* frames, const int32_t* hwc, int32_t frames_on_device,
@@ -288,7 +234,7 @@ int rtd_motion_check(rtd_motion_handle m, int32_t n, const uint8_t* const* frame
       try {
         launch(m, b, e, frames, hwc, frames_on_device, slots, threshold, area);
       } catch (...) {
-        (void)hipStreamSynchronize(m->stream);           // nothing of a failed launch may still read the staging buffers
+        m->q.drain();                                    // nothing of a failed launch may still read the staging buffers
         throw;
       }
       b = e;
@@ -307,23 +253,21 @@ int rtd_motion_reset(rtd_motion_handle m, int32_t slot) {
 int rtd_motion_wait_stream(rtd_motion_handle m, void* producer_stream) {
   return guarded(m, [&] {
     HIP_CHECK(hipSetDevice(m->device));
-    HIP_CHECK(hipEventRecord(m->ev_xs, (hipStream_t)producer_stream));
-    HIP_CHECK(hipStreamWaitEvent(m->stream, m->ev_xs, 0));
+    m->q.wait_for(producer_stream);
   });
 }
 
-const char* rtd_motion_last_error(rtd_motion_handle m) { return m ? m->err.c_str() : g_motion_create_error.c_str(); }
+const char* rtd_motion_last_error(rtd_motion_handle m) { return bk::last_error(m); }
 
 void rtd_motion_destroy(rtd_motion_handle m) {
   if (!m) return;
   (void)hipSetDevice(m->device);
-  if (m->stream) (void)hipStreamSynchronize(m->stream);
+  m->q.drain();
   for (auto& kv : m->slots)
     if (kv.second.buf) (void)hipFree(kv.second.buf);
-  if (m->pin) (void)hipHostFree(m->pin);
-  if (m->dev) (void)hipFree(m->dev);
-  if (m->ev_xs) (void)hipEventDestroy(m->ev_xs);
-  if (m->stream) (void)hipStreamDestroy(m->stream);
+  m->dev.release();
+  m->pin.release();
+  m->q.close();
   delete m;
 }
 
@@ -335,8 +279,8 @@ int rtd_debug_motion_state(rtd_motion_handle m, int32_t slot, uint8_t* out, size
     RTD_CHECK(s.valid, RTD_E_STATE, "the slot holds no frame (reset, or never checked)");
     RTD_CHECK(out && nbytes >= (size_t)s.rows * s.cols, RTD_E_INVALID, "output buffer too small");
     HIP_CHECK(hipSetDevice(m->device));
-    HIP_CHECK(hipMemcpyAsync(out, s.buf, (size_t)s.rows * s.cols, hipMemcpyDeviceToHost, m->stream));
-    HIP_CHECK(hipStreamSynchronize(m->stream));
+    HIP_CHECK(hipMemcpyAsync(out, s.buf, (size_t)s.rows * s.cols, hipMemcpyDeviceToHost, m->q.stream));
+    HIP_CHECK(hipStreamSynchronize(m->q.stream));
   });
 }
 

@@ -13,11 +13,14 @@
 
 #include "../../include/rtdetr_mi355.h"
 #include "../../include/rtdetr_mi355_test.h"
-#include "common.h"
+#include "backend.h"
 
 namespace overlay {
 
 using rtd::Error;
+namespace bk = rtd::backend;
+using bk::align_up;
+using bk::guarded;
 
 constexpr int TILE_W = 64, TILE_H = 16;
 constexpr int THREADS = 256;
@@ -133,24 +136,14 @@ __global__ void __launch_bounds__(THREADS) overlay_kernel(const FrameDesc* __res
   else draw_tile<1>(d, prims, masks, t.tile, kept, wave_cnt);
 }
 
-static std::string g_overlay_create_error;
-
-static size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
 }  // namespace overlay
 
 using namespace overlay;
 
-struct rtd_overlay {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev_xs = nullptr;
-  std::mutex mu;
-  std::string err;
-  uint8_t* pin = nullptr;    // pinned: [descriptors | primitives | tiles | masks | host frames]
-  size_t pin_cap = 0;
-  uint8_t* dev = nullptr;    // the same tables on the device (not the frames: they go straight to out_dev)
-  size_t dev_cap = 0;
+struct rtd_overlay : bk::Base {
+  bk::OwnStream q;
+  bk::PinBuf pin;   // pinned: [descriptors | primitives | tiles | masks | host frames]
+  bk::DevBuf dev;   // the same tables on the device (not the frames: they go straight to out_dev)
   std::vector<DevPrim> prims;            // host scratch, capacity kept between calls
   std::vector<TileRef> tiles;
   std::vector<uint8_t> marks;
@@ -158,44 +151,6 @@ struct rtd_overlay {
 };
 
 namespace overlay {
-
-template <typename F>
-static int guarded(rtd_overlay* o, F&& f) {
-  if (!o) return RTD_E_INVALID;
-  std::lock_guard<std::mutex> lk(o->mu);
-  try {
-    f();
-    return RTD_OK;
-  } catch (const Error& er) {
-    o->err = er.what();
-    return er.code;
-  } catch (const std::bad_alloc&) {
-    o->err = "host allocation failed";
-    return RTD_E_OOM;
-  } catch (const std::exception& ex) {
-    o->err = ex.what();
-    return RTD_E_HIP;
-  }
-}
-
-static void reserve(rtd_overlay* o, size_t pin_bytes, size_t dev_bytes) {
-  if (pin_bytes > o->pin_cap) {
-    const size_t cap = std::max(pin_bytes, o->pin_cap * 2);
-    if (o->pin) (void)hipHostFree(o->pin);
-    o->pin = nullptr;
-    o->pin_cap = 0;
-    HIP_CHECK(hipHostMalloc((void**)&o->pin, cap, hipHostMallocDefault));
-    o->pin_cap = cap;
-  }
-  if (dev_bytes > o->dev_cap) {
-    const size_t cap = std::max(dev_bytes, o->dev_cap * 2);
-    if (o->dev) (void)hipFree(o->dev);
-    o->dev = nullptr;
-    o->dev_cap = 0;
-    HIP_CHECK(hipMalloc((void**)&o->dev, cap));
-    o->dev_cap = cap;
-  }
-}
 
 struct Box {                 // inclusive; empty when x0 > x1 or y0 > y1
   int64_t x0, y0, x1, y1;
@@ -243,7 +198,7 @@ static void validate(int n, const uint8_t* const* frames, const int32_t* hwc, co
 
 static void draw(rtd_overlay* o, int n, const uint8_t* const* frames, const int32_t* hwc, int on_device, const int32_t* prim_counts,
                  const rtd_overlay_prim* prims, const uint8_t* masks, int64_t mask_bytes, uint8_t* const* out_dev) {
-  hipStream_t s = o->stream;
+  hipStream_t s = o->q.stream;
   // ---- the primitives the kernel will read, and the tiles they paint
   o->prims.clear();
   o->tiles.clear();
@@ -306,32 +261,29 @@ static void draw(rtd_overlay* o, int n, const uint8_t* const* frames, const int3
   const size_t tile_off = align_up(prim_off + sizeof(DevPrim) * o->prims.size(), 256);
   const size_t mask_off = align_up(tile_off + sizeof(TileRef) * o->tiles.size(), 256);
   const size_t tables = align_up(mask_off + (size_t)mask_bytes, 256);
-  size_t total = tables;
-  std::vector<size_t> foff(n);
-  for (int i = 0; i < n; ++i) {
-    foff[i] = total;
-    if (!on_device) total = align_up(total + (size_t)hwc[3 * i] * hwc[3 * i + 1] * hwc[3 * i + 2], 256);
-  }
-  reserve(o, total, tables);
-  memcpy(o->pin, descs.data(), sizeof(FrameDesc) * n);
-  if (!o->prims.empty()) memcpy(o->pin + prim_off, o->prims.data(), sizeof(DevPrim) * o->prims.size());
-  if (!o->tiles.empty()) memcpy(o->pin + tile_off, o->tiles.data(), sizeof(TileRef) * o->tiles.size());
-  if (mask_bytes) memcpy(o->pin + mask_off, masks, (size_t)mask_bytes);
+  std::vector<size_t> foff;
+  const size_t total = bk::stage_offsets(n, hwc, on_device, tables, foff);
+  o->pin.reserve(total);
+  o->dev.reserve(tables);
+  memcpy(o->pin.p, descs.data(), sizeof(FrameDesc) * n);
+  if (!o->prims.empty()) memcpy(o->pin.p + prim_off, o->prims.data(), sizeof(DevPrim) * o->prims.size());
+  if (!o->tiles.empty()) memcpy(o->pin.p + tile_off, o->tiles.data(), sizeof(TileRef) * o->tiles.size());
+  if (mask_bytes) memcpy(o->pin.p + mask_off, masks, (size_t)mask_bytes);
 
   // ---- the frames arrive where they are drawn, then one launch
   for (int i = 0; i < n; ++i) {
     const size_t bytes = (size_t)hwc[3 * i] * hwc[3 * i + 1] * hwc[3 * i + 2];
     if (!on_device) {
-      memcpy(o->pin + foff[i], frames[i], bytes);
-      HIP_CHECK(hipMemcpyAsync(out_dev[i], o->pin + foff[i], bytes, hipMemcpyHostToDevice, s));
+      memcpy(o->pin.p + foff[i], frames[i], bytes);
+      HIP_CHECK(hipMemcpyAsync(out_dev[i], o->pin.p + foff[i], bytes, hipMemcpyHostToDevice, s));
     } else if (frames[i] != out_dev[i]) {
       HIP_CHECK(hipMemcpyAsync(out_dev[i], frames[i], bytes, hipMemcpyDeviceToDevice, s));
     }
   }
   if (!o->tiles.empty()) {
-    HIP_CHECK(hipMemcpyAsync(o->dev, o->pin, tables, hipMemcpyHostToDevice, s));
-    rtd::rtd_launch(overlay_kernel, dim3((unsigned)o->tiles.size()), dim3(THREADS), 0, s, (const FrameDesc*)o->dev,
-                    (const DevPrim*)(o->dev + prim_off), (const TileRef*)(o->dev + tile_off), (const uint8_t*)(o->dev + mask_off));
+    HIP_CHECK(hipMemcpyAsync(o->dev.p, o->pin.p, tables, hipMemcpyHostToDevice, s));
+    rtd::rtd_launch(overlay_kernel, dim3((unsigned)o->tiles.size()), dim3(THREADS), 0, s, (const FrameDesc*)o->dev.p,
+                    (const DevPrim*)(o->dev.p + prim_off), (const TileRef*)(o->dev.p + tile_off), (const uint8_t*)(o->dev.p + mask_off));
     HIP_CHECK(hipGetLastError());
   }
   HIP_CHECK(hipStreamSynchronize(s));
@@ -343,25 +295,11 @@ static void draw(rtd_overlay* o, int n, const uint8_t* const* frames, const int3
 extern "C" {
 
 int rtd_overlay_create(int32_t device, rtd_overlay_handle* out) {
-  if (!out) return RTD_E_INVALID;
-  *out = nullptr;
-  rtd_overlay* o = new (std::nothrow) rtd_overlay();
-  if (!o) return RTD_E_OOM;
-  try {
-    int count = 0;
-    HIP_CHECK(hipGetDeviceCount(&count));
-    RTD_CHECK(device >= 0 && device < count, RTD_E_INVALID, "no such device");
+  return bk::create(out, rtd_overlay_destroy, [&](rtd_overlay* o) {
+    bk::use_device(device);
     o->device = device;
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreateWithFlags(&o->stream, hipStreamNonBlocking));
-    HIP_CHECK(hipEventCreateWithFlags(&o->ev_xs, hipEventDisableTiming));
-  } catch (const Error& er) {
-    g_overlay_create_error = er.what();
-    rtd_overlay_destroy(o);
-    return er.code;
-  }
-  *out = o;
-  return RTD_OK;
+    o->q.open();
+  });
 }
 
 int rtd_overlay_draw(rtd_overlay_handle o, int32_t n, const uint8_t* const* frames, const int32_t* hwc, int32_t frames_on_device,
@@ -375,7 +313,7 @@ int rtd_overlay_draw(rtd_overlay_handle o, int32_t n, const uint8_t* const* fram
     try {
       draw(o, n, frames, hwc, frames_on_device, prim_counts, prims, masks, mask_bytes, out_dev);
     } catch (...) {
-      (void)hipStreamSynchronize(o->stream);               // nothing of a failed call may still read the staging buffers
+      o->q.drain();                                        // nothing of a failed call may still read the staging buffers
       throw;
     }
   });
@@ -384,21 +322,19 @@ int rtd_overlay_draw(rtd_overlay_handle o, int32_t n, const uint8_t* const* fram
 int rtd_overlay_wait_stream(rtd_overlay_handle o, void* producer_stream) {
   return guarded(o, [&] {
     HIP_CHECK(hipSetDevice(o->device));
-    HIP_CHECK(hipEventRecord(o->ev_xs, (hipStream_t)producer_stream));
-    HIP_CHECK(hipStreamWaitEvent(o->stream, o->ev_xs, 0));
+    o->q.wait_for(producer_stream);
   });
 }
 
-const char* rtd_overlay_last_error(rtd_overlay_handle o) { return o ? o->err.c_str() : g_overlay_create_error.c_str(); }
+const char* rtd_overlay_last_error(rtd_overlay_handle o) { return bk::last_error(o); }
 
 void rtd_overlay_destroy(rtd_overlay_handle o) {
   if (!o) return;
   (void)hipSetDevice(o->device);
-  if (o->stream) (void)hipStreamSynchronize(o->stream);
-  if (o->dev) (void)hipFree(o->dev);
-  if (o->pin) (void)hipHostFree(o->pin);
-  if (o->ev_xs) (void)hipEventDestroy(o->ev_xs);
-  if (o->stream) (void)hipStreamDestroy(o->stream);
+  o->q.drain();
+  o->dev.release();
+  o->pin.release();
+  o->q.close();
   delete o;
 }
 

@@ -19,7 +19,7 @@ import numpy as np
 from . import _capi
 
 # the limits of rtd_enhance_create / rtd_enhance_crops (include/rtdetr_mi355.h)
-MAX_CROPS_PER_CALL = 64
+MAX_CROPS_PER_CALL = _capi.MAX_CROPS_PER_CALL
 MAX_TILES = 16
 MAX_RADIUS = 7
 MIN_CROP_SIDE = 16
@@ -41,24 +41,19 @@ def within_limits(tile_grid_size, bilateral_d, sigma_space) -> bool:
 
 def layout(rects: Sequence[Sequence[int]]) -> List[int]:
     """rtd_enhance_layout: byte offsets of the crops (x1, y1, x2, y2) in the output buffer, plus its size.  Host arithmetic only."""
-    n = len(rects)
-    rc = (C.c_int32 * max(4 * n, 1))(*[int(v) for r in rects for v in r])
-    offsets = (C.c_int64 * (n + 1))()
-    code = _capi.lib().rtd_enhance_layout(n, rc, offsets)
-    if code != _capi.RTD_OK:
-        raise _capi.RtdError(code, (_capi.lib().rtd_enhance_last_error(None) or b"").decode(errors="replace"))
-    return list(offsets)
+    return _capi.crop_layout("rtd_enhance", rects)
 
 
-class CropEnhancer:
+class CropEnhancer(_capi.CropHandle):
     """One rtd_enhance handle.  The parameters are the reference's (`clahe_clip_limit`, `clahe_tile_grid_size` = (tilesX, tilesY),
     `bilateral_d`, `bilateral_sigma_color`, `bilateral_sigma_space`); the library takes the three real ones as float32, and `params`
     holds the values it actually uses.  Calls are asynchronous on torch's current stream; the handle's scratch belongs to the call in
     flight, so use one enhancer from one stream at a time."""
 
+    _prefix, _what = "rtd_enhance", "libmi355rtdetr"
+
     def __init__(self, clip_limit: float = 2.0, tile_grid_size=(8, 8), bilateral_d: int = 9, sigma_color: float = 75, sigma_space: float = 75,
                  device: int = 0):
-        self._h = C.c_void_p()
         p = _capi.RtdEnhanceParams()
         p.struct_size = C.sizeof(_capi.RtdEnhanceParams)
         p.clip_limit = float(clip_limit)
@@ -68,19 +63,7 @@ class CropEnhancer:
         self.params = {"clip_limit": float(p.clip_limit), "tile_grid_size": (p.tiles_x, p.tiles_y), "bilateral_d": p.bilateral_d,
                        "sigma_color": float(p.sigma_color), "sigma_space": float(p.sigma_space)}
         self.device = int(device)
-        self._timing = None
-        rc = _capi.lib().rtd_enhance_create(self.device, C.byref(p), C.byref(self._h))
-        if rc != _capi.RTD_OK:
-            self._h = C.c_void_p()
-            self._raise(rc, None)
-
-    @staticmethod
-    def _raise(code: int, handle) -> None:
-        msg = (_capi.lib().rtd_enhance_last_error(handle) or b"").decode(errors="replace")
-        if code == _capi.RTD_E_OOM:
-            import torch
-            raise torch.cuda.OutOfMemoryError(f"HIP out of memory in libmi355rtdetr: {msg}")
-        raise _capi.RtdError(code, msg)
+        self._open(self.device, C.byref(p))
 
     @classmethod
     def from_reference(cls, image_enhancer, min_crop_size: int, device: int = 0) -> Optional["CropEnhancer"]:
@@ -104,62 +87,11 @@ class CropEnhancer:
         shapes): one uint8 device tensor holding every enhanced crop (frame-major order), crop i being buffer[offsets[i]:][:h * w * 3]
         viewed as (h, w, 3) with shapes[i] = (h, w); offsets has one more entry, the buffer's size.  Enqueued on torch's current
         stream: the buffer is ready when that stream reaches it."""
-        import torch
-
-        flat = [(f, tuple(int(v) for v in r)) for f, rects in zip(frames, rects_per_frame) for r in rects]
-        dev = frames[0].device if len(frames) else torch.device("cuda", self.device)
-        offsets = layout([r for _, r in flat])
-        shapes = [(r[3] - r[1], r[2] - r[0]) for _, r in flat]
-        buf = torch.empty((offsets[-1],), dtype=torch.uint8, device=dev)
-        if not flat:
-            return buf, offsets, shapes
-        stream = torch.cuda.current_stream(dev)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record(stream)
-        for i0 in range(0, len(flat), MAX_CROPS_PER_CALL):
-            part = flat[i0:i0 + MAX_CROPS_PER_CALL]
-            k = len(part)
-            ptrs = (C.c_void_p * k)()
-            hw = (C.c_int32 * (2 * k))()
-            rc = (C.c_int32 * (4 * k))()
-            for i, (f, r) in enumerate(part):
-                assert f.is_cuda and f.dtype == torch.uint8 and f.is_contiguous() and f.dim() == 3 and f.shape[2] == 3
-                ptrs[i] = f.data_ptr()
-                hw[2 * i], hw[2 * i + 1] = int(f.shape[0]), int(f.shape[1])
-                rc[4 * i:4 * i + 4] = r
-            # the offsets of a chunk are rtd_enhance_layout's for the whole list, relative to the chunk's first crop (the header)
-            code = _capi.lib().rtd_enhance_crops(self._h, k, ptrs, hw, rc, C.c_void_p(buf.data_ptr() + offsets[i0]), offsets[-1] - offsets[i0],
-                                                 C.c_void_p(stream.cuda_stream))
-            if code != _capi.RTD_OK:
-                self._raise(code, self._h)
-        ev1.record(stream)
-        self._timing = (ev0, ev1)
-        return buf, offsets, shapes
-
-    def last_call_ms(self) -> Optional[float]:
-        """device time of the last enhance() in milliseconds (waits for it); None before the first call"""
-        if self._timing is None:
-            return None
-        ev0, ev1 = self._timing
-        ev1.synchronize()
-        return float(ev0.elapsed_time(ev1))
+        return self._crop_call("crops", 1, frames, rects_per_frame)
 
     def debug_stage(self, crop: int, stage: int, shape) -> np.ndarray:
         """rtd_debug_enhance_stage: 0 = Lab (h, w, 3), 1 = LUTs (tiles_y, tiles_x, 256), 2 = BGR before the bilateral filter; `crop`
         counts inside the LAST rtd_enhance_crops call (the last chunk of an enhance())."""
         out = np.zeros(shape, np.uint8)
-        rc = _capi.lib().rtd_debug_enhance_stage(self._h, int(crop), int(stage), out.ctypes.data, out.nbytes)
-        if rc != _capi.RTD_OK:
-            self._raise(rc, self._h)
+        self._check(self._L.rtd_debug_enhance_stage(self._h, int(crop), int(stage), out.ctypes.data, out.nbytes))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _capi.lib().rtd_enhance_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass

@@ -22,7 +22,7 @@ import numpy as np
 from . import _capi
 from .enhance import MIN_CROP_SIDE, CropEnhancer, within_limits
 
-MAX_CROPS_PER_CALL = 64
+MAX_CROPS_PER_CALL = _capi.MAX_CROPS_PER_CALL
 MIN_SIDE, MAX_SIDE, MAX_ONE_PASS_SIDE = 8, 4096, 576
 NUM_FEAT, NUM_GROW_CH = 64, 32
 
@@ -87,21 +87,16 @@ def load_state(path_or_dict, num_block: Optional[int] = None) -> bytes:
 
 def layout(rects: Sequence[Sequence[int]]) -> List[int]:
     """rtd_esrgan_layout: byte offsets of the 4x crops (x1, y1, x2, y2) in the output buffer, plus its size.  Host arithmetic only."""
-    n = len(rects)
-    rc = (C.c_int32 * max(4 * n, 1))(*[int(v) for r in rects for v in r])
-    offsets = (C.c_int64 * (n + 1))()
-    code = _capi.lib().rtd_esrgan_layout(n, rc, offsets)
-    if code != _capi.RTD_OK:
-        raise _capi.RtdError(code, (_capi.lib().rtd_esrgan_last_error(None) or b"").decode(errors="replace"))
-    return list(offsets)
+    return _capi.crop_layout("rtd_esrgan", rects)
 
 
-class CropUpscaler:
+class CropUpscaler(_capi.CropHandle):
     """One rtd_esrgan handle.  state: a checkpoint path, a state dict, or the blob `load_state` returned.  Calls are asynchronous on
     torch's current stream; the handle's arena belongs to the call in flight, so use one upscaler from one stream at a time."""
 
+    _prefix, _what = "rtd_esrgan", "libmi355rtdetr"
+
     def __init__(self, state, num_block: int = 23, precision="f16x3", tile: int = 512, tile_pad: int = 10, device: int = 0):
-        self._h = C.c_void_p()
         blob = state if isinstance(state, (bytes, bytearray)) else load_state(state, num_block)
         cfg = _capi.RtdEsrganConfig()
         cfg.struct_size = C.sizeof(_capi.RtdEsrganConfig)
@@ -110,89 +105,24 @@ class CropUpscaler:
         cfg.num_feat, cfg.num_grow_ch = NUM_FEAT, NUM_GROW_CH
         cfg.num_block, cfg.tile, cfg.tile_pad = int(num_block), int(tile), int(tile_pad)
         self.device, self.num_block, self.tile, self.tile_pad, self.precision = int(device), int(num_block), int(tile), int(tile_pad), cfg.precision
-        self._timing = None
-        buf = (C.c_char * len(blob)).from_buffer_copy(blob)
-        rc = _capi.lib().rtd_esrgan_create(C.byref(cfg), buf, len(blob), C.byref(self._h))
-        if rc != _capi.RTD_OK:
-            self._h = C.c_void_p()
-            self._raise(rc, None)
-
-    @staticmethod
-    def _raise(code: int, handle) -> None:
-        msg = (_capi.lib().rtd_esrgan_last_error(handle) or b"").decode(errors="replace")
-        if code == _capi.RTD_E_OOM:
-            import torch
-            raise torch.cuda.OutOfMemoryError(f"HIP out of memory in libmi355rtdetr: {msg}")
-        raise _capi.RtdError(code, msg)
+        self._open(C.byref(cfg), (C.c_char * len(blob)).from_buffer_copy(blob), len(blob))
 
     def upscale(self, frames, rects_per_frame) -> Tuple["object", List[int], List[Tuple[int, int]]]:
         """frames: device uint8 HWC BGR tensors; rects_per_frame: per frame a list of (x1, y1, x2, y2).  Returns (buffer, offsets,
         shapes): one uint8 device tensor holding every 4x crop (frame-major order), crop i being buffer[offsets[i]:][:H * W * 3] viewed
         as (H, W, 3) with shapes[i] = (H, W) = (4h, 4w).  Enqueued on torch's current stream."""
-        import torch
-
-        flat = [(f, tuple(int(v) for v in r)) for f, rects in zip(frames, rects_per_frame) for r in rects]
-        dev = frames[0].device if len(frames) else torch.device("cuda", self.device)
-        offsets = layout([r for _, r in flat])
-        shapes = [(4 * (r[3] - r[1]), 4 * (r[2] - r[0])) for _, r in flat]
-        buf = torch.empty((offsets[-1],), dtype=torch.uint8, device=dev)
-        if not flat:
-            return buf, offsets, shapes
-        stream = torch.cuda.current_stream(dev)
-        ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        ev0.record(stream)
-        for i0 in range(0, len(flat), MAX_CROPS_PER_CALL):
-            part = flat[i0:i0 + MAX_CROPS_PER_CALL]
-            k = len(part)
-            ptrs = (C.c_void_p * k)()
-            hw = (C.c_int32 * (2 * k))()
-            rc = (C.c_int32 * (4 * k))()
-            for i, (f, r) in enumerate(part):
-                assert f.is_cuda and f.dtype == torch.uint8 and f.is_contiguous() and f.dim() == 3 and f.shape[2] == 3
-                ptrs[i] = f.data_ptr()
-                hw[2 * i], hw[2 * i + 1] = int(f.shape[0]), int(f.shape[1])
-                rc[4 * i:4 * i + 4] = r
-            code = _capi.lib().rtd_esrgan_upscale(self._h, k, ptrs, hw, rc, C.c_void_p(buf.data_ptr() + offsets[i0]), offsets[-1] - offsets[i0],
-                                                  C.c_void_p(stream.cuda_stream))
-            if code != _capi.RTD_OK:
-                self._raise(code, self._h)
-        ev1.record(stream)
-        self._timing = (ev0, ev1)
-        return buf, offsets, shapes
-
-    def last_call_ms(self) -> Optional[float]:
-        """device time of the last upscale() in milliseconds (waits for it); None before the first call"""
-        if self._timing is None:
-            return None
-        ev0, ev1 = self._timing
-        ev1.synchronize()
-        return float(ev0.elapsed_time(ev1))
+        return self._crop_call("upscale", 4, frames, rects_per_frame)
 
     def arena_bytes(self) -> int:
-        return int(_capi.lib().rtd_esrgan_arena_bytes(self._h))
+        return int(self._L.rtd_esrgan_arena_bytes(self._h))
 
     def debug_tensor(self, name: str) -> np.ndarray:
         """rtd_debug_esrgan_tensor: a float stage output [h, w, c] of the last tile of the last call"""
         shape = (C.c_int64 * 4)()
-        rc = _capi.lib().rtd_debug_esrgan_tensor(self._h, name.encode(), None, 0, shape)
-        if rc != _capi.RTD_OK:
-            self._raise(rc, self._h)
+        self._check(self._L.rtd_debug_esrgan_tensor(self._h, name.encode(), None, 0, shape))
         out = np.zeros(tuple(shape)[1:], np.float32)
-        rc = _capi.lib().rtd_debug_esrgan_tensor(self._h, name.encode(), out.ctypes.data, out.size, shape)
-        if rc != _capi.RTD_OK:
-            self._raise(rc, self._h)
+        self._check(self._L.rtd_debug_esrgan_tensor(self._h, name.encode(), out.ctypes.data, out.size, shape))
         return out
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            _capi.lib().rtd_esrgan_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class UpscalingEnhancer:

@@ -20,6 +20,8 @@ from typing import Dict, List, Optional, Sequence
 
 import numpy as np
 
+from . import _capi
+from ._capi import device_index as _device_index   # (overlay.py imports it from here)
 from .motion import _as_hwc
 
 logger = logging.getLogger(__name__)
@@ -29,7 +31,7 @@ DEFAULT_QUALITY = 95         # OpenCV's default
 SNAPSHOT_BUFFER_QUALITY = 90   # src/snapshot_saver.py:160
 
 
-class DeviceBackend:
+class DeviceBackend(_capi.Handle):
     """One rtd_jpeg handle.  A test may hand JpegEncoder another object with encode / wait_stream / close (tests/jpeg_ref.py
     RefBackend).
 
@@ -37,30 +39,16 @@ class DeviceBackend:
     serialises the calls on a handle, and `_lock` keeps a call and the copy out of the shared output array together, so that no other
     thread's call can overwrite or replace the array in between."""
 
+    _prefix, _what = "rtd_jpeg", "the JPEG encoder"
+
     def __init__(self, device: int):
-        from . import _capi
-        self._capi = _capi
-        self._L = _capi.lib()
-        self._h = C.c_void_p()
         self._out = np.empty(1 << 20, np.uint8)
         self._lock = threading.Lock()
-        rc = self._L.rtd_jpeg_create(int(device), C.byref(self._h))
-        if rc != _capi.RTD_OK:
-            self._h = C.c_void_p()
-            self._raise(rc)
-
-    def _raise(self, rc: int):
-        msg = (self._L.rtd_jpeg_last_error(self._h) or b"").decode(errors="replace")
-        if rc == self._capi.RTD_E_OOM:
-            import torch
-            raise torch.cuda.OutOfMemoryError(f"HIP out of memory in the JPEG encoder: {msg}")
-        raise self._capi.RtdError(rc, msg)
+        self._open(int(device))
 
     def encode_raw(self, ptrs: Sequence[Optional[int]], shapes: Sequence[Sequence[int]], on_device: bool, quality: int, out: Optional[np.ndarray]):
         """rtd_jpeg_encode as it is: (return code, offsets[n + 1])"""
-        n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
-        hwc = (C.c_int32 * max(3 * n, 1))(*[int(v) for s in shapes for v in s])
+        n, p, hwc = _capi.c_frames(ptrs, shapes)
         offs = (C.c_int64 * (n + 1))()
         rc = self._L.rtd_jpeg_encode(self._h, n, p, hwc, int(bool(on_device)), int(quality), out.ctypes.data if out is not None else None,
                                      out.nbytes if out is not None else 0, offs)
@@ -68,14 +56,13 @@ class DeviceBackend:
 
     def encode(self, frames: Sequence, on_device: bool, quality: int) -> List[bytes]:
         """frames: HxWxC uint8 (C = 1 or 3) - C-contiguous numpy arrays, or contiguous device tensors when on_device."""
-        ptrs = [f.data_ptr() if on_device else f.ctypes.data for f in frames]
-        shapes = [tuple(f.shape) for f in frames]
+        ptrs, shapes = _capi.frame_ptrs(frames, on_device)
         with self._lock:                       # the call, a retry with a larger array and the copy out of it: one critical section
             rc, offs = self.encode_raw(ptrs, shapes, on_device, quality, self._out)
-            if rc == self._capi.RTD_E_INVALID and len(frames) and offs[-1] > self._out.nbytes:  # too small: the needed size came back
+            if rc == _capi.RTD_E_INVALID and len(frames) and offs[-1] > self._out.nbytes:  # too small: the needed size came back
                 self._out = np.empty(max(offs[-1], 2 * self._out.nbytes), np.uint8)
                 rc, offs = self.encode_raw(ptrs, shapes, on_device, quality, self._out)
-            if rc != self._capi.RTD_OK:
+            if rc != _capi.RTD_OK:
                 self._raise(rc)
             return [self._out[offs[i]:offs[i + 1]].tobytes() for i in range(len(frames))]
 
@@ -83,42 +70,10 @@ class DeviceBackend:
         """int16 [blocks][64] of the last call (rtd_debug_jpeg_coefficients; a test aid: "the last call" is the caller's own only
         while no other thread encodes)"""
         count = C.c_int64()
-        rc = self._L.rtd_debug_jpeg_coefficients(self._h, None, 0, C.byref(count))
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
+        self._check(self._L.rtd_debug_jpeg_coefficients(self._h, None, 0, C.byref(count)))
         out = np.zeros(count.value, np.int16)
-        rc = self._L.rtd_debug_jpeg_coefficients(self._h, out.ctypes.data, out.size, C.byref(count))
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
+        self._check(self._L.rtd_debug_jpeg_coefficients(self._h, out.ctypes.data, out.size, C.byref(count)))
         return out.reshape(-1, 64)
-
-    def wait_stream(self, producer_stream: int) -> None:
-        rc = self._L.rtd_jpeg_wait_stream(self._h, C.c_void_p(int(producer_stream) or None))
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.rtd_jpeg_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-def _device_index(device) -> int:
-    if isinstance(device, int):
-        return device
-    if device is None:
-        import torch
-        return torch.cuda.current_device() if torch.cuda.is_available() else 0
-    if hasattr(device, "index"):                  # torch.device
-        return device.index or 0
-    s = str(device)
-    return int(s.split(":")[1]) if ":" in s else 0
 
 
 class JpegEncoder:

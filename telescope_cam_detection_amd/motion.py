@@ -24,6 +24,8 @@ from typing import Any, Dict, List, Optional, Sequence
 
 import numpy as np
 
+from . import _capi
+
 logger = logging.getLogger(__name__)
 
 MAX_BLUR = 63
@@ -39,70 +41,31 @@ def odd_blur(blur_size: int) -> int:
     return k
 
 
-class DeviceBackend:
+class DeviceBackend(_capi.Handle):
     """One rtd_motion handle: the per-slot stored frames live on the device.  A test may hand EmptyFrameFilter another object with the
     same four methods (tests/motion_ref.py RefBackend)."""
 
-    def __init__(self, device: int, blur_size: int):
-        from . import _capi
-        self._capi = _capi
-        self._L = _capi.lib()
-        self._h = C.c_void_p()
-        rc = self._L.rtd_motion_create(int(device), int(blur_size), C.byref(self._h))
-        if rc != _capi.RTD_OK:
-            self._h = C.c_void_p()
-            self._raise(rc)
+    _prefix, _what = "rtd_motion", "the motion gate"
 
-    def _raise(self, rc: int):
-        msg = (self._L.rtd_motion_last_error(self._h) or b"").decode(errors="replace")
-        if rc == self._capi.RTD_E_OOM:
-            import torch
-            raise torch.cuda.OutOfMemoryError(f"HIP out of memory in the motion gate: {msg}")
-        raise self._capi.RtdError(rc, msg)
+    def __init__(self, device: int, blur_size: int):
+        self._open(int(device), int(blur_size))
 
     def check(self, frames: Sequence, on_device: bool, slots: Sequence[int], threshold: int) -> List[int]:
         """frames: HxWxC uint8 (C = 1 or 3) - C-contiguous numpy arrays, or contiguous device tensors when on_device."""
-        n = len(frames)
-        ptrs = (C.c_void_p * n)()
-        hwc = (C.c_int32 * (3 * n))()
-        for i, f in enumerate(frames):
-            ptrs[i] = f.data_ptr() if on_device else f.ctypes.data
-            hwc[3 * i], hwc[3 * i + 1], hwc[3 * i + 2] = int(f.shape[0]), int(f.shape[1]), int(f.shape[2])
-        sl = (C.c_int32 * n)(*[int(s) for s in slots])
-        area = (C.c_int64 * n)()
-        rc = self._L.rtd_motion_check(self._h, n, ptrs, hwc, int(bool(on_device)), sl, int(threshold), area)
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
-        return list(area)
+        n, ptrs, hwc = _capi.c_frames(*_capi.frame_ptrs(frames, on_device))
+        sl = (C.c_int32 * max(n, 1))(*[int(s) for s in slots])
+        area = (C.c_int64 * max(n, 1))()
+        self._check(self._L.rtd_motion_check(self._h, n, ptrs, hwc, int(bool(on_device)), sl, int(threshold), area))
+        return list(area)[:n]
 
     def reset(self, slot: int = -1) -> None:
-        rc = self._L.rtd_motion_reset(self._h, int(slot))
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
-
-    def wait_stream(self, producer_stream: int) -> None:
-        rc = self._L.rtd_motion_wait_stream(self._h, C.c_void_p(int(producer_stream) or None))
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
+        self._check(self._L.rtd_motion_reset(self._h, int(slot)))
 
     def state(self, slot: int, shape) -> np.ndarray:
         """the blurred frame the slot holds (rtd_debug_motion_state)"""
         out = np.zeros(tuple(shape), np.uint8)
-        rc = self._L.rtd_debug_motion_state(self._h, int(slot), out.ctypes.data, out.nbytes)
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
+        self._check(self._L.rtd_debug_motion_state(self._h, int(slot), out.ctypes.data, out.nbytes))
         return out
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.rtd_motion_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def _as_hwc(frame):
@@ -137,24 +100,12 @@ class EmptyFrameFilter:
         self.min_motion_area = min_motion_area
         self.threshold = threshold
         self.blur_size = odd_blur(blur_size)
-        if device is None or not isinstance(device, int):
-            device = self._device_index(device)
-        self.device = device
+        self.device = device = _capi.device_index(device)
         self._backend = backend if backend is not None else DeviceBackend(device, self.blur_size)
         self._slots: Dict[Any, int] = {}
         self._counts: Dict[Any, List[int]] = {}      # key -> [total, skipped, motion]
         logger.info(f"EmptyFrameFilter (GPU) initialized: min_motion_area={min_motion_area}px², threshold={threshold}, "
                     f"blur_size={self.blur_size}, device={device}")
-
-    @staticmethod
-    def _device_index(device) -> int:
-        if device is None:
-            import torch
-            return torch.cuda.current_device() if torch.cuda.is_available() else 0
-        if hasattr(device, "index"):                  # torch.device
-            return device.index or 0
-        s = str(device)
-        return int(s.split(":")[1]) if ":" in s else 0
 
     def _int_threshold(self) -> int:
         # cv2.threshold on 8-bit input compares with floor(threshold); anything < 0 counts every pixel, >= 255 none

@@ -27,6 +27,7 @@ from typing import Any, Dict, List, Sequence, Tuple
 
 import numpy as np
 
+from . import _capi
 from .motion import _as_hwc, odd_blur
 from .stage2 import normalised_bbox
 
@@ -48,32 +49,18 @@ def roi(bbox: Dict[str, float], h: int, w: int) -> Tuple[int, int, int, int]:
     return max(0, x1), max(0, y1), min(w, x2), min(h, y2)
 
 
-class DeviceBackend:
+class DeviceBackend(_capi.Handle):
     """One rtd_mog2 handle: the background model lives on the device.  A test may hand MotionFilter another object with the same
     methods (tests/mog2_ref.py RefBackend)."""
 
-    def __init__(self, device: int, history: int, var_threshold, detect_shadows: bool):
-        from . import _capi
-        self._capi = _capi
-        self._L = _capi.lib()
-        self._h = C.c_void_p()
-        rc = self._L.rtd_mog2_create(int(device), int(history), float(var_threshold), int(bool(detect_shadows)), C.byref(self._h))
-        if rc != _capi.RTD_OK:
-            self._h = C.c_void_p()
-            self._raise(rc)
+    _prefix, _what = "rtd_mog2", "the motion filter"
 
-    def _raise(self, rc: int):
-        msg = (self._L.rtd_mog2_last_error(self._h) or b"").decode(errors="replace")
-        if rc == self._capi.RTD_E_OOM:
-            import torch
-            raise torch.cuda.OutOfMemoryError(f"HIP out of memory in the motion filter: {msg}")
-        raise self._capi.RtdError(rc, msg)
+    def __init__(self, device: int, history: int, var_threshold, detect_shadows: bool):
+        self._open(int(device), int(history), float(var_threshold), int(bool(detect_shadows)))
 
     def configure(self, history: int, var_threshold, detect_shadows: bool) -> None:
         """a new subtractor: the model is forgotten"""
-        rc = self._L.rtd_mog2_configure(self._h, int(history), float(var_threshold), int(bool(detect_shadows)))
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
+        self._check(self._L.rtd_mog2_configure(self._h, int(history), float(var_threshold), int(bool(detect_shadows))))
 
     def apply(self, frame, on_device: bool, rects: Sequence[Tuple[int, int, int, int]], blur_size: int) -> List[int]:
         """len(rects) model updates with `frame` (HxWxC uint8: a C-contiguous numpy array, or a contiguous device tensor when on_device);
@@ -83,54 +70,30 @@ class DeviceBackend:
         r = (C.c_int32 * max(4 * n, 1))(*[int(v) for b in rects for v in b])
         counts = (C.c_int64 * max(n, 1))()
         ptr = frame.data_ptr() if on_device else frame.ctypes.data
-        rc = self._L.rtd_mog2_apply(self._h, C.c_void_p(ptr), hwc, int(bool(on_device)), n, r, int(blur_size), counts)
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
+        self._check(self._L.rtd_mog2_apply(self._h, C.c_void_p(ptr), hwc, int(bool(on_device)), n, r, int(blur_size), counts))
         return list(counts)[:n]
-
-    def wait_stream(self, producer_stream: int) -> None:
-        rc = self._L.rtd_mog2_wait_stream(self._h, C.c_void_p(int(producer_stream) or None))
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
 
     def model(self) -> Dict[str, Any]:
         """the model in a canonical layout (rtd_debug_mog2_model): weight / variance [H, W, 5], mean [H, W, 5, C], modes_used [H, W],
         nframes; None when the filter holds no model"""
         hwc = (C.c_int32 * 3)()
         nf = C.c_int64()
-        rc = self._L.rtd_debug_mog2_model(self._h, hwc, C.byref(nf), None, None, None, None, 0)
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
+        self._check(self._L.rtd_debug_mog2_model(self._h, hwc, C.byref(nf), None, None, None, None, 0))
         H, W, Ch = hwc
         if H == 0:
             return None
         out = {"weight": np.zeros((H, W, NMODES), np.float32), "variance": np.zeros((H, W, NMODES), np.float32),
                "mean": np.zeros((H, W, NMODES, Ch), np.float32), "modes_used": np.zeros((H, W), np.uint8)}
-        rc = self._L.rtd_debug_mog2_model(self._h, hwc, C.byref(nf), out["weight"].ctypes.data, out["variance"].ctypes.data,
-                                          out["mean"].ctypes.data, out["modes_used"].ctypes.data, H * W)
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
+        self._check(self._L.rtd_debug_mog2_model(self._h, hwc, C.byref(nf), out["weight"].ctypes.data, out["variance"].ctypes.data,
+                                                 out["mean"].ctypes.data, out["modes_used"].ctypes.data, H * W))
         out["nframes"] = int(nf.value)
         return out
 
     def fg_bits(self, n: int, shape) -> np.ndarray:
         """the foreground words of the last apply of n updates: [ceil(n / 32), H, W] uint32"""
         out = np.zeros(((n + 31) // 32,) + tuple(shape), np.uint32)
-        rc = self._L.rtd_debug_mog2_fg_bits(self._h, out.ctypes.data, out.size)
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
+        self._check(self._L.rtd_debug_mog2_fg_bits(self._h, out.ctypes.data, out.size))
         return out
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.rtd_mog2_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class MotionFilter:
@@ -148,10 +111,7 @@ class MotionFilter:
         self.motion_required = motion_required
         self.motion_blur_size = odd_blur(motion_blur_size)
         self.min_motion_ratio = min_motion_ratio
-        if device is None or not isinstance(device, int):
-            from .motion import EmptyFrameFilter
-            device = EmptyFrameFilter._device_index(device)
-        self.device = device
+        self.device = _capi.device_index(device)
         self._lock = threading.RLock()                  # hot reload calls update_params from another thread
         self._new_backend = (lambda: backend) if backend is not None else (
             lambda: DeviceBackend(self.device, self.history, self.var_threshold, self.detect_shadows))

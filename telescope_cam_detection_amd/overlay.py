@@ -31,6 +31,7 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
+from . import _capi
 from .jpeg import _device_index, _is_device_tensor
 from .motion import _as_hwc
 
@@ -244,35 +245,21 @@ def lower(plans: Sequence[Sequence[tuple]], cache: MaskCache):
 
 
 # ---- backends -------------------------------------------------------------------------------------------------------------------------
-class DeviceBackend:
+class DeviceBackend(_capi.Handle):
     """One rtd_overlay handle.  A test may hand OverlayRenderer another object with draw / wait_stream / close (tests/overlay_ref.py
     RefBackend).  Safe to share between threads: the library serialises the calls on a handle."""
 
-    def __init__(self, device: int):
-        from . import _capi
-        self._capi = _capi
-        self._L = _capi.lib()
-        self.device = int(device)
-        self._h = C.c_void_p()
-        rc = self._L.rtd_overlay_create(self.device, C.byref(self._h))
-        if rc != _capi.RTD_OK:
-            self._h = C.c_void_p()
-            self._raise(rc)
+    _prefix, _what = "rtd_overlay", "the overlay renderer"
 
-    def _raise(self, rc: int):
-        msg = (self._L.rtd_overlay_last_error(self._h) or b"").decode(errors="replace")
-        if rc == self._capi.RTD_E_OOM:
-            import torch
-            raise torch.cuda.OutOfMemoryError(f"HIP out of memory in the overlay renderer: {msg}")
-        raise self._capi.RtdError(rc, msg)
+    def __init__(self, device: int):
+        self.device = int(device)
+        self._open(self.device)
 
     def draw_raw(self, ptrs: Sequence[Optional[int]], shapes: Sequence[Sequence[int]], on_device: bool, prims: Sequence[np.ndarray],
                  masks: np.ndarray, out_ptrs: Sequence[Optional[int]]) -> int:
         """rtd_overlay_draw as it is: the return code"""
-        n = len(ptrs)
-        p = (C.c_void_p * max(n, 1))(*ptrs)
+        n, p, hwc = _capi.c_frames(ptrs, shapes)
         o = (C.c_void_p * max(n, 1))(*out_ptrs)
-        hwc = (C.c_int32 * max(3 * n, 1))(*[int(v) for s in shapes for v in s])
         counts = (C.c_int32 * max(n, 1))(*[len(a) for a in prims])
         flat = np.ascontiguousarray(np.concatenate(list(prims)) if len(prims) else np.zeros(0, PRIM_DTYPE), PRIM_DTYPE)
         masks = np.ascontiguousarray(masks, np.uint8)
@@ -289,35 +276,15 @@ class DeviceBackend:
         outs = list(frames) if inplace else [torch.empty(tuple(f.shape), dtype=torch.uint8, device=dev) for f in frames]
         # the frames were written, and the new tensors' memory was last used, on torch's current stream: the handle's stream waits for it
         self.wait_stream(torch.cuda.current_stream(dev).cuda_stream)
-        ptrs = [f.data_ptr() if on_device else f.ctypes.data for f in frames]
-        rc = self.draw_raw(ptrs, [tuple(f.shape) for f in frames], on_device, prims, masks, [o.data_ptr() for o in outs])
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
+        ptrs, shapes = _capi.frame_ptrs(frames, on_device)
+        self._check(self.draw_raw(ptrs, shapes, on_device, prims, masks, [o.data_ptr() for o in outs]))
         return outs
 
     def tiles(self) -> Tuple[int, int, int]:
         """(tile height, tile width, tiles the last draw launched): rtd_debug_overlay_tiles"""
         th, tw, n = C.c_int32(), C.c_int32(), C.c_int64()
-        rc = self._L.rtd_debug_overlay_tiles(self._h, C.byref(th), C.byref(tw), C.byref(n))
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
+        self._check(self._L.rtd_debug_overlay_tiles(self._h, C.byref(th), C.byref(tw), C.byref(n)))
         return th.value, tw.value, n.value
-
-    def wait_stream(self, producer_stream: int) -> None:
-        rc = self._L.rtd_overlay_wait_stream(self._h, C.c_void_p(int(producer_stream) or None))
-        if rc != self._capi.RTD_OK:
-            self._raise(rc)
-
-    def close(self) -> None:
-        if getattr(self, "_h", None) is not None and self._h.value:
-            self._L.rtd_overlay_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 # ---- the renderer ---------------------------------------------------------------------------------------------------------------------

@@ -12,7 +12,7 @@ namespace eh = esrgan_host;
 
 template <typename F>
 static int code_of(F&& f) {
-  try { f(); return RTD_OK; } catch (const eh::Fail& e) { return e.code; }
+  try { f(); return RTD_OK; } catch (const rtd::Error& e) { return e.code; }
 }
 
 // weights.pack_blob of {name: fp32 tensor}
