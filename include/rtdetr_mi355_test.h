@@ -87,6 +87,36 @@ int rtd_op_attention(int dtype, const void* qk, const void* v, void* o, int B, i
 int rtd_op_msdeform(int dtype, const void* value, const float* offaw, const float* ref, float* out,
                     int B, int Q, int heads, int hd, int n_levels, int n_points, const int32_t* level_hw,
                     int value_ld, float offset_scale);
+/* ... with the value rows as the engine holds them: [B, S, value_ld] with this layer's heads * hd channels at channel offset value_coff
+ * (the decoder samples a 256-channel slice of the dec_layers * 256 wide projection of all layers); RTD_E_INVALID before any device work
+ * when hd != 32 or the slice leaves the row */
+int rtd_op_msdeform_view(int dtype, const void* value, int value_ld, int value_coff, const float* offaw, const float* ref, float* out,
+                         int B, int Q, int heads, int hd, int n_levels, int n_points, const int32_t* level_hw, float offset_scale);
+/* ---- query selection (decoder.hip).  x = [B * S] fp32 rows of K = 256 channels with row stride ldx; w_f32 = [C][K] row-major and
+ * bias = [C] (device, fp32: packed here exactly as the engine packs dec.enc_score); g, b = the LayerNorm's [256].
+ * select_score: mx[B * S] = max over classes of (LayerNorm(x) W^T + bias).  gather_ln: dst[b][q][0:256] = LayerNorm(x[b][idx[b][q]]) with
+ * row stride ldd; an index outside [0, S) is clamped to the nearest valid row. */
+int rtd_op_select_score(const float* x, int ldx, const float* w_f32, const float* bias, const float* g, const float* b, float* mx,
+                        int B, int S, int C, int K);
+int rtd_op_gather_ln(const float* x, int ldx, int S, const int32_t* idx, int B, int Q, const float* g, const float* b, float* dst, int ldd);
+/* fp32 rows <-> pair (F16X2) rows, C % 32 == 0, lds / ldd = row strides in channels: direction 0 = fp32 -> pair, 1 = pair -> fp32,
+ * 2 = ADD the number of hi halves at +-65504 among the rows * lds * 2 16-bit words at src to the uint64 at dst (rtd_self_check's scan) */
+int rtd_op_split_convert(int direction, const void* src, void* dst, int64_t rows, int C, int64_t lds, int64_t ldd);
+/* the decoder's glue kernels (ops.hip), device pointers, strides in elements:
+ * set_rows: y[b][rows[i]][0:C] = vec for every image b and i < nrows (y = [B][rows_per_image] rows of stride ld; rows[] in range)
+ * rowmax: out[r] = max(x[r][0:C]), fp32
+ * gather_rows: dst[b][q][0:C] (fp32, stride ldd) = src[b][clamp(idx[b][q], 0, S - 1)][0:C] (src_dtype 0 bf16 / 1 fp32, stride lds)
+ * boxes: anchors != NULL: ref_unact8[t][0:4] = delta[t][0:4] + anchors[clamp(idx[t], 0, S - 1)], ref8 = sigmoid(.), lanes 4..7 of both zero;
+ *        anchors == NULL: ref8[t][0:4] = sigmoid(delta[t][0:4] + inverse_sigmoid(ref8[t][0:4])) in place (delta rows of stride ldd)
+ * add: y = a + b on [B][rows][C] dense tensors of the given dtypes; b_broadcast: b is [1][rows][C], read for every image */
+int rtd_op_set_rows(int dtype, void* y, int ld, int C, const int32_t* rows, int nrows, int rows_per_image, const float* vec, int B);
+int rtd_op_rowmax(const float* x, int ld, int C, int rows, float* out);
+int rtd_op_gather_rows(int src_dtype, const void* src, int lds, int S, const int32_t* idx, int B, int Q, int C, float* dst, int ldd);
+int rtd_op_boxes(const float* delta, int ldd, int rows, float* ref8, const float* anchors, const int32_t* idx, int S, float* ref_unact8);
+int rtd_op_add(int dt_a, int dt_b, int dt_y, const void* a, const void* b, void* y, int B, int rows, int C, int b_broadcast);
+/* the post-processor: logits [B * Q][C], ref8 [B * Q][8] cxcywh, scale_wh [B][2] -> block6 [B][K][6] = label, score, x1, y1, x2, y2 (K == Q).
+ * fused 1 = the one-launch form (RTD_E_INVALID when it does not take the shape: never a fall-back), 0 = sigmoid + top-k + gather */
+int rtd_op_postprocess(const float* logits, const float* ref8, const float* scale_wh, int B, int Q, int C, int K, int fused, float* block6);
 /* the glue ops on an NHWC view x = [B, H, W, C] with pixel stride ldx (>= C: a channel slice), images dense: kind 0 = max-pool 3x3 / stride 2 /
  * pad 1, 1 = 2x2 average (even H, W), 2 = nearest 2x upsample; dtype 0 bf16, 1 fp32, 4 F16X2; y = [B, OH, OW, C] with pixel stride ldy */
 int rtd_op_pool(int kind, int dtype, const void* x, void* y, int B, int H, int W, int C, int ldx, int ldy);

@@ -129,6 +129,8 @@ TEST_EXPORTS = [
     "rtd_bench_mfma_rate", "rtd_debug_motion_state", "rtd_debug_mog2_model", "rtd_debug_mog2_fg_bits",
     "rtd_debug_jpeg_coefficients", "rtd_debug_overlay_tiles", "rtd_debug_enhance_stage",
     "rtd_op_conv_view", "rtd_bench_conv_act", "rtd_debug_esrgan_tensor",
+    "rtd_op_msdeform_view", "rtd_op_select_score", "rtd_op_gather_ln", "rtd_op_split_convert", "rtd_op_set_rows", "rtd_op_rowmax",
+    "rtd_op_gather_rows", "rtd_op_boxes", "rtd_op_add", "rtd_op_postprocess",
 ]
 
 
@@ -264,6 +266,17 @@ def lib() -> C.CDLL:
         L.rtd_debug_esrgan_tensor.argtypes = [vp, C.c_char_p, vp, i64, C.POINTER(i64)]
         L.rtd_op_conv_view.argtypes = [i32, vp, i32, vp, vp, vp, i32, vp, i32] + [i32] * 10
         L.rtd_bench_conv_act.argtypes = [i32] * 13 + [C.POINTER(f32)]
+    if hasattr(L, "rtd_op_select_score"):      # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_op_msdeform_view.argtypes = [i32, vp, i32, i32, vp, vp, vp] + [i32] * 6 + [C.POINTER(i32), f32]
+        L.rtd_op_select_score.argtypes = [vp, i32, vp, vp, vp, vp, vp, i32, i32, i32, i32]
+        L.rtd_op_gather_ln.argtypes = [vp, i32, i32, vp, i32, i32, vp, vp, vp, i32]
+        L.rtd_op_split_convert.argtypes = [i32, vp, vp, i64, i32, i64, i64]
+        L.rtd_op_set_rows.argtypes = [i32, vp, i32, i32, vp, i32, i32, vp, i32]
+        L.rtd_op_rowmax.argtypes = [vp, i32, i32, i32, vp]
+        L.rtd_op_gather_rows.argtypes = [i32, vp, i32, i32, vp, i32, i32, i32, vp, i32]
+        L.rtd_op_boxes.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp]
+        L.rtd_op_add.argtypes = [i32, i32, i32, vp, vp, vp, i32, i32, i32, i32]
+        L.rtd_op_postprocess.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
     _lib = L
     return L
 

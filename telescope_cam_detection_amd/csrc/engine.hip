@@ -193,7 +193,7 @@ static inline float h2f(uint16_t u) {
 }
 
 // fp32 filter [N][K] -> fragment-major layout of decoder.hip's row_gemm (K padded to Kuse, N to `ntiles` 16-row tiles): fp32 fragments ...
-static void* pack_fragments_f32(rtd_engine* e, const float* w, int N, int K, int Kuse, int ntiles) {
+std::vector<float> pack_fragments_f32_host(const float* w, int N, int K, int Kuse, int ntiles) {
   const int kc = Kuse / 16;
   std::vector<float> pk((size_t)ntiles * kc * 256, 0.f);
   for (int t = 0; t < ntiles; ++t)
@@ -203,6 +203,10 @@ static void* pack_fragments_f32(rtd_engine* e, const float* w, int N, int K, int
           const int n = t * 16 + (lane & 15), k = c * 16 + 4 * (lane >> 4) + j;
           if (n < N && k < K) pk[(((size_t)t * kc + c) * 64 + lane) * 4 + j] = w[(size_t)n * K + k];
         }
+  return pk;
+}
+static void* pack_fragments_f32(rtd_engine* e, const float* w, int N, int K, int Kuse, int ntiles) {
+  const std::vector<float> pk = pack_fragments_f32_host(w, N, K, Kuse, ntiles);
   return upload(e, pk.data(), pk.size() * 4);
 }
 // ... or W = hi + lo (two fp16, round-to-nearest-even each): decoder.hip row_gemm_split multiplies both against a hi/lo split of
@@ -235,7 +239,7 @@ DevWeight get_weight_packed(rtd_engine* e, const std::string& name, int N, int K
   RTD_CHECK(Kuse % 64 == 0 && Kuse >= K, RTD_E_WEIGHTS, "K padding: " + name);
   DevWeight d;
   d.N = N; d.K = Kuse; d.Kpad = Kuse; d.dt = F32;
-  const int ntiles = ((N + 15) / 16 + 7) / 8 * 8;
+  const int ntiles = packed_ntiles(N);
   d.Npad = ntiles * 16;
   d.w = split ? pack_fragments_f16x2(e, w, N, K, Kuse, ntiles) : pack_fragments_f32(e, w, N, K, Kuse, ntiles);
   return finish_weight(e, key, d, {{name, K}});

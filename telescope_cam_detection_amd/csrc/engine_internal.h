@@ -162,6 +162,10 @@ void check_n(rtd_engine* e, int n);
 Plan* get_plan(rtd_engine* e, int n);
 void point_at_blank_frames(rtd_engine* h, Plan* p, int n);
 void pil_coeffs(int in_size, int out_size, std::vector<int32_t>& bounds, std::vector<int32_t>& kk, int& ksize);
+// a row-GEMM filter [N][K] fp32 in decoder.hip's fragment-major order (common.h DecLin, split == 0), K zero padded to Kuse and N to
+// `ntiles` 16-row tiles; packed_ntiles(N) is the tile count get_weight_packed pads to (the bias vector is Npad = 16 * ntiles long)
+std::vector<float> pack_fragments_f32_host(const float* w, int N, int K, int Kuse, int ntiles);
+inline int packed_ntiles(int N) { return ((N + 15) / 16 + 7) / 8 * 8; }
 
 template <typename F>
 int guarded(rtd_engine* e, F&& f) {

@@ -5,6 +5,29 @@
 using namespace rtd;
 using namespace rtd_eng;
 
+// device scratch of one rtd_op_* call: freed on every path (a throwing RTD_CHECK / HIP_CHECK included)
+struct OpScratch {
+  std::vector<void*> bufs;
+  template <typename T> T* get(size_t count) {
+    void* p = nullptr;
+    HIP_CHECK(hipMalloc(&p, count ? count * sizeof(T) : 16));
+    bufs.push_back(p);
+    return (T*)p;
+  }
+  template <typename T> T* upload(const T* host, size_t count) {
+    T* d = get<T>(count);
+    HIP_CHECK(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
+    return d;
+  }
+  ~OpScratch() { for (void* p : bufs) (void)hipFree(p); }
+};
+static bool rows_fit_int(int a, int b) { return a >= 1 && b >= 1 && (int64_t)a * b <= 0x7fffffff; }
+static Tensor rows_view(const void* p, int dt, int n, int rows, int c, int64_t ld) {
+  Tensor t = mk(p, dt, n, rows, 1, c);
+  t.ld = ld; t.bstride = (int64_t)rows * ld;
+  return t;
+}
+
 extern "C" {
 
 int rtd_debug_tensor(rtd_handle h, const char* name, float* out, int64_t capacity, int64_t shape[4]) {
@@ -523,6 +546,128 @@ int rtd_op_msdeform(int dtype, const void* value, const float* offaw, const floa
                     n_levels, n_points, lvd, offset_scale, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
     (void)hipFree(lvd); (void)hipFree(ref8);
+  });
+}
+
+int rtd_op_msdeform_view(int dtype, const void* value, int value_ld, int value_coff, const float* offaw, const float* ref, float* out, int B, int Q,
+                         int heads, int hd, int n_levels, int n_points, const int32_t* level_hw, float offset_scale) {
+  return op_guard([&] {
+    RTD_CHECK(value && offaw && ref && out && level_hw && rows_fit_int(B, Q), RTD_E_INVALID, "msdeform view: arguments");
+    RTD_CHECK(hd == 32 && heads >= 1, RTD_E_INVALID, "msdeform view: head dim must be 32");
+    RTD_CHECK(n_levels >= 1 && n_levels <= 8 && n_points >= 1, RTD_E_INVALID, "msdeform view: 1..8 levels");
+    RTD_CHECK(value_coff >= 0 && value_coff + heads * hd <= value_ld, RTD_E_INVALID, "msdeform view: the channel slice leaves the value row");
+    int32_t lv[24]; int S = 0;
+    for (int l = 0; l < n_levels; ++l) {
+      RTD_CHECK(level_hw[2 * l] >= 1 && level_hw[2 * l + 1] >= 1, RTD_E_INVALID, "msdeform view: level extents");
+      lv[l * 3] = level_hw[2 * l]; lv[l * 3 + 1] = level_hw[2 * l + 1]; lv[l * 3 + 2] = S; S += level_hw[2 * l] * level_hw[2 * l + 1];
+    }
+    OpScratch sc;
+    const int32_t* lvd = sc.upload(lv, (size_t)3 * n_levels);
+    float* ref8 = sc.get<float>((size_t)B * Q * 8);
+    HIP_CHECK(hipMemset(ref8, 0, (size_t)B * Q * 32));
+    HIP_CHECK(hipMemcpy2D(ref8, 32, ref, 16, 16, (size_t)B * Q, hipMemcpyDeviceToDevice));
+    launch_msdeform(rows_view(value, dtype, B, S, heads * hd, value_ld), value_coff, mk(offaw, F32, B, Q, 1, heads * n_levels * n_points * 3), ref8,
+                    mk(out, F32, B, Q, 1, heads * hd), heads, hd, n_levels, n_points, lvd, offset_scale, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+  });
+}
+
+int rtd_op_select_score(const float* x, int ldx, const float* w_f32, const float* bias, const float* g, const float* b, float* mx, int B, int S,
+                        int C, int K) {
+  return op_guard([&] {
+    RTD_CHECK(x && w_f32 && bias && g && b && mx && rows_fit_int(B, S) && C >= 1, RTD_E_INVALID, "select_score: arguments");
+    RTD_CHECK(K == 256 && ldx >= K && ldx % 4 == 0 && aligned16(x, g, b), RTD_E_INVALID, "select_score: 256-wide rows in 16-byte aligned storage");
+    const int ntiles = packed_ntiles(C);                         // the engine's own packing (get_weight_packed): bias zero padded to Npad
+    std::vector<float> hw((size_t)C * K), hb((size_t)ntiles * 16, 0.f);
+    HIP_CHECK(hipMemcpy(hw.data(), w_f32, hw.size() * 4, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(hb.data(), bias, (size_t)C * 4, hipMemcpyDeviceToHost));
+    const std::vector<float> pk = pack_fragments_f32_host(hw.data(), C, K, K, ntiles);
+    OpScratch sc;
+    SelArgs a{};
+    a.score.w = sc.upload(pk.data(), pk.size()); a.score.b = sc.upload(hb.data(), hb.size()); a.score.ldw = K; a.score.N = C; a.score.K = K;
+    a.ln.g = g; a.ln.b = b;
+    a.x = x; a.ldx = ldx; a.rows = B * S; a.C = C; a.rows_per_image = S; a.mx = mx;
+    launch_select_score(a, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+  });
+}
+
+int rtd_op_gather_ln(const float* x, int ldx, int S, const int32_t* idx, int B, int Q, const float* g, const float* b, float* dst, int ldd) {
+  return op_guard([&] {
+    RTD_CHECK(x && idx && g && b && dst && rows_fit_int(B, S) && rows_fit_int(B, Q), RTD_E_INVALID, "gather_ln: arguments");
+    RTD_CHECK(ldx >= 256 && ldd >= 256 && ldx % 4 == 0 && ldd % 4 == 0 && aligned16(x, dst), RTD_E_INVALID, "gather_ln: 256-wide rows in 16-byte aligned storage");
+    DecLN ln{g, b};
+    launch_gather_ln(x, ldx, S, idx, B, Q, ln, dst, ldd, nullptr);
+  });
+}
+
+int rtd_op_split_convert(int direction, const void* src, void* dst, int64_t rows, int C, int64_t lds, int64_t ldd) {
+  return op_guard([&] {
+    RTD_CHECK(src && dst && rows >= 1 && C >= 1 && lds >= C, RTD_E_INVALID, "split_convert: arguments");
+    RTD_CHECK(C % SPLIT_GROUP == 0, RTD_E_INVALID, "split_convert: whole 32-channel groups");
+    if (direction == 0) { RTD_CHECK(ldd >= C, RTD_E_INVALID, "split_convert: ldd"); launch_f32_to_split((const float*)src, lds, dst, ldd, rows, C, nullptr); }
+    else if (direction == 1) { RTD_CHECK(ldd >= C, RTD_E_INVALID, "split_convert: ldd"); launch_split_to_f32(src, lds, (float*)dst, ldd, rows, C, nullptr); }
+    else if (direction == 2) { RTD_CHECK(lds % SPLIT_GROUP == 0, RTD_E_INVALID, "split_convert: lds"); launch_count_saturated(src, rows * lds * 2, (unsigned long long*)dst, nullptr); }
+    else RTD_CHECK(false, RTD_E_INVALID, "split_convert: direction 0 fp32 -> pair, 1 pair -> fp32, 2 count saturated");
+  });
+}
+
+int rtd_op_set_rows(int dtype, void* y, int ld, int C, const int32_t* rows, int nrows, int rows_per_image, const float* vec, int B) {
+  return op_guard([&] {
+    RTD_CHECK(y && rows && vec && nrows >= 0 && nrows <= rows_per_image && C >= 1 && ld >= C && rows_fit_int(B, rows_per_image), RTD_E_INVALID, "set_rows: arguments");
+    launch_set_rows(rows_view(y, dtype, B, rows_per_image, C, ld), rows, nrows, rows_per_image, vec, nullptr);
+  });
+}
+
+int rtd_op_rowmax(const float* x, int ld, int C, int rows, float* out) {
+  return op_guard([&] {
+    RTD_CHECK(x && out && rows >= 1 && C >= 1 && ld >= C, RTD_E_INVALID, "rowmax: arguments");
+    launch_rowmax(rows_view(x, F32, 1, rows, C, ld), out, nullptr);
+  });
+}
+
+int rtd_op_gather_rows(int src_dtype, const void* src, int lds, int S, const int32_t* idx, int B, int Q, int C, float* dst, int ldd) {
+  return op_guard([&] {
+    RTD_CHECK(src && idx && dst && rows_fit_int(B, S) && rows_fit_int(B, Q) && C >= 1 && lds >= C && ldd >= C, RTD_E_INVALID, "gather_rows: arguments");
+    launch_gather_rows(rows_view(src, src_dtype, B, S, C, lds), idx, S, rows_view(dst, F32, B, Q, C, ldd), nullptr);
+  });
+}
+
+int rtd_op_boxes(const float* delta, int ldd, int rows, float* ref8, const float* anchors, const int32_t* idx, int S, float* ref_unact8) {
+  return op_guard([&] {
+    RTD_CHECK(delta && ref8 && rows >= 1 && ldd >= 4, RTD_E_INVALID, "boxes: arguments");
+    const Tensor d = rows_view(delta, F32, 1, rows, 4, ldd);
+    if (!anchors) { launch_box_refine(d, ref8, nullptr); return; }
+    RTD_CHECK(idx && ref_unact8 && S >= 1, RTD_E_INVALID, "boxes: ref_init needs the token indices, S and the raw-box output");
+    launch_ref_init(d, anchors, idx, S, ref_unact8, ref8, nullptr);
+  });
+}
+
+int rtd_op_add(int dt_a, int dt_b, int dt_y, const void* a, const void* b, void* y, int B, int rows, int C, int b_broadcast) {
+  return op_guard([&] {
+    RTD_CHECK(a && b && y && rows_fit_int(B, rows) && C >= 1, RTD_E_INVALID, "add: arguments");
+    launch_add(mk(a, dt_a, B, rows, 1, C), mk(b, dt_b, b_broadcast ? 1 : B, rows, 1, C), mk(y, dt_y, B, rows, 1, C), nullptr);
+  });
+}
+
+int rtd_op_postprocess(const float* logits, const float* ref8, const float* scale_wh, int B, int Q, int C, int K, int fused, float* block6) {
+  return op_guard([&] {
+    RTD_CHECK(logits && ref8 && scale_wh && block6 && rows_fit_int(B, Q) && C >= 1 && (int64_t)Q * C <= 0x7fffffff, RTD_E_INVALID, "postprocess: arguments");
+    RTD_CHECK(K == Q, RTD_E_INVALID, "postprocess: one output row per query (K == Q)");
+    const Tensor lg = mk(logits, F32, B, Q, 1, C);
+    if (fused) {
+      RTD_CHECK(launch_postprocess_fused(lg, ref8, scale_wh, B, Q, block6, nullptr), RTD_E_INVALID, "postprocess: the one-launch form does not take this shape");
+      return;
+    }
+    RTD_CHECK(K <= 1024, RTD_E_INVALID, "postprocess: K <= 1024");
+    OpScratch sc;
+    float* scores = sc.get<float>((size_t)B * Q * C);
+    float* topv = sc.get<float>((size_t)B * K);
+    int32_t* topi = sc.get<int32_t>((size_t)B * K);
+    launch_postprocess_scores(lg, scores, nullptr);
+    launch_topk(scores, B, Q * C, K, topi, topv, nullptr);
+    launch_postprocess_gather(topv, topi, ref8, scale_wh, B, Q, C, block6, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
   });
 }
 

@@ -7,6 +7,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from tests.util import FACTOR, ulp32, within
+
 pytestmark = pytest.mark.gpu
 
 DT = {"bf16": (0, torch.bfloat16), "f32": (1, torch.float32)}
@@ -529,6 +531,106 @@ def test_layernorm(L, dt, dim):
         ck(L, L.rtd_op_layernorm(code, xd.data_ptr(), rd.data_ptr() if use_res else None, gd.data_ptr(),
                                  bd.data_ptr(), yd.data_ptr(), rows, dim, 1))
         torch.testing.assert_close(yd.cpu(), ref, atol=2e-5, rtol=2e-5)
+
+
+# The row with mean 1000 and std 0.5 is held to its own factor, every other row to the common 4: its fp32 row sum is ~1e6 (ulp 0.0625), an
+# error of 0.1 there is 1e-4 in the mean, and (x - mean) / std * gamma carries that into the output 2 |gamma| fold - 1e-4 .. 6e-4
+# whatever the summation order.  torch's own error on these rows swings between 1.5e-5 (dim 1000) and 3.3e-4 (dim 1024) with the order
+# its vector lanes happen to add in, so e_ref is one draw of that spread and so is the kernel's error: measured worst ratio 23.49
+# (fp32, dim 1000: kernel 3.7e-4 against torch's luckiest 1.5e-5; at dim 1024 the kernel's 4.1e-5 is 8x BETTER than torch).  Factor =
+# 1.5 x that ratio (kernel-level error table).
+LN_OFFSET_ROW_FACTOR = 1.5 * 23.49
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("rows", [1, 5])
+@pytest.mark.parametrize("dim", [4, 100, 256, 1000, 1024])
+def test_layernorm_edges_against_fp64(L, dt, rows, dim):
+    """k_layernorm at dims that are no multiple of the wave (4, 100, 1000), the largest it takes (1024) and one or five rows (a partial
+    block), against fp64 on the values it reads, tests/util.py within() as the bound: row 0 is constant (x - mean is exactly zero when the
+    row sum is exact, as for 3.0, so the row gives beta bit for bit) and the last row has mean 1000 and std 0.5.  With a bf16
+    output (out_f32 = 0) the result is the fp32-out result rounded once to bf16, bit for bit."""
+    code, tdt = DT[dt]
+    g = torch.Generator().manual_seed(9000 + dim + rows)
+    x = torch.randn(rows, dim, generator=g) * 2 + 0.5
+    x[0] = 3.0
+    if rows > 1:
+        x[rows - 1] = 1000.0 + 0.5 * torch.randn(dim, generator=g)
+    gam, bet = torch.randn(dim, generator=g), torch.randn(dim, generator=g)
+    xq = x.to(tdt).float()
+    xd, gd, bd = x.to(tdt).cuda(), gam.cuda(), bet.cuda()
+    y32 = torch.full((rows, dim), float("nan"), device="cuda")
+    ck(L, L.rtd_op_layernorm(code, xd.data_ptr(), None, gd.data_ptr(), bd.data_ptr(), y32.data_ptr(), rows, dim, 1))
+    y32 = y32.cpu()
+    ref64, ref32 = F.layer_norm(xq.double(), (dim,), gam.double(), bet.double(), 1e-5), F.layer_norm(xq, (dim,), gam, bet, 1e-5)
+    plain = rows - 1 if rows > 1 else rows
+    within("layernorm", f"{dt} rows {rows} dim {dim}", y32[:plain], ref64[:plain], ref32[:plain])
+    if rows > 1:
+        within("layernorm, mean >> spread", f"{dt} dim {dim}", y32[plain:], ref64[plain:], ref32[plain:], factor=LN_OFFSET_ROW_FACTOR)
+    assert torch.equal(y32[0].view(torch.int32), bet.view(torch.int32)), "a constant row must give beta exactly"
+    if dt == "bf16":
+        y16 = torch.zeros(rows, dim, dtype=torch.bfloat16, device="cuda")
+        ck(L, L.rtd_op_layernorm(code, xd.data_ptr(), None, gd.data_ptr(), bd.data_ptr(), y16.data_ptr(), rows, dim, 0))
+        assert torch.equal(y16.cpu().view(torch.int16), y32.to(torch.bfloat16).view(torch.int16))
+
+
+def test_layernorm_refuses_more_than_1024_columns(L):
+    x = torch.zeros(2, 1025, device="cuda")
+    assert L.rtd_op_layernorm(1, x.data_ptr(), None, x.data_ptr(), x.data_ptr(), x.data_ptr(), 2, 1025, 1) != 0
+
+
+def _attention_ref(qk, v, heads, hd, dt):
+    B, Lq, D = v.shape
+    qk, v = qk.to(dt), v.to(dt)
+    q = qk[..., :D].view(B, Lq, heads, hd).transpose(1, 2)
+    k = qk[..., D:].view(B, Lq, heads, hd).transpose(1, 2)
+    a = torch.softmax(q @ k.transpose(2, 3) * hd ** -0.5, -1)
+    return (a @ v.view(B, Lq, heads, hd).transpose(1, 2)).transpose(1, 2).reshape(B, Lq, D)
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("big", [False, True])
+@pytest.mark.parametrize("Lq", [1, 15, 16, 17, 63, 64, 65])
+def test_attention_short_sequences_and_large_logits_against_fp64(L, dt, big, Lq):
+    """launch_attention around its tile sizes (16-key MFMA sub-tiles, 64-key staging tiles, one key) against fp64 on the values it reads,
+    tests/util.py within() as the bound (bf16 storage: the same bound, then one bf16 rounding); `big` scales q so that
+    |q k / sqrt(hd)| reaches 60 (the online softmax must not lose the small terms' scale).  fp32 from L = 64 on runs on the matrix cores;
+    with the three base pointers 4 bytes off a 16-byte boundary the launcher takes the VALU kernel instead, held to the same bound."""
+    code, tdt = DT[dt]
+    B, heads, hd = 2, 2, 32
+    D = heads * hd
+    g = torch.Generator().manual_seed(9100 + Lq + 1000 * big)
+    qk = torch.randn(B, Lq, 2 * D, generator=g)
+    v = torch.randn(B, Lq, D, generator=g)
+    if big:
+        s = (qk[..., :D].view(B, Lq, heads, hd).transpose(1, 2) @ qk[..., D:].view(B, Lq, heads, hd).transpose(1, 2).transpose(2, 3)) * hd ** -0.5
+        qk[..., :D] *= 60.0 / s.abs().max()
+    qkq, vq = qk.to(tdt).float(), v.to(tdt).float()
+    ref64, ref32 = _attention_ref(qkq, vq, heads, hd, torch.float64), _attention_ref(qkq, vq, heads, hd, torch.float32)
+    if big:
+        s = (qkq[..., :D].view(B, Lq, heads, hd).transpose(1, 2) @ qkq[..., D:].view(B, Lq, heads, hd).transpose(1, 2).transpose(2, 3)) * hd ** -0.5
+        assert 55.0 < s.abs().max() < 65.0
+    for off in ((0, 1) if dt == "f32" else (0,)):                 # elements past a 16-byte aligned base
+        qkd = torch.zeros(qk.numel() + 4, dtype=tdt, device="cuda")
+        vd = torch.zeros(v.numel() + 4, dtype=tdt, device="cuda")
+        od = torch.full((v.numel() + 4,), float("nan"), dtype=tdt, device="cuda")
+        assert qkd.data_ptr() % 16 == 0 and vd.data_ptr() % 16 == 0 and od.data_ptr() % 16 == 0
+        qkd[off:off + qk.numel()] = qk.to(tdt).reshape(-1).cuda()
+        vd[off:off + v.numel()] = v.to(tdt).reshape(-1).cuda()
+        es = qkd.element_size()
+        ck(L, L.rtd_op_attention(code, qkd.data_ptr() + off * es, vd.data_ptr() + off * es, od.data_ptr() + off * es, B, Lq, heads, hd))
+        got = od[off:off + v.numel()].float().cpu().view(B, Lq, D)
+        name = f"{dt} L {Lq} big {big} offset {off}"
+        if dt == "f32":
+            within("attention", name, got, ref64, ref32)
+        else:
+            # the fp32 bound b before one bf16 rounding: a value within b of the fp64 result r rounds to within b + one bf16 ulp of bf16(r)
+            b = FACTOR * ((ref32.double() - ref64).abs().max().item() + ulp32(ref64.abs().max().item()))
+            want = ref64.to(torch.bfloat16).double()
+            ulp16 = ((want.abs() + b).clamp(min=2.0 ** -126).log2().floor() - 7).exp2()      # bf16 spacing at each expected value
+            over = ((got.double() - want).abs() - b) / ulp16
+            print(f"[attention] {name}: worst distance from the bf16-rounded fp64 result beyond the fp32 bound {b:.2e}: {over.max().item():.2f} bf16 ulp")
+            assert torch.isfinite(got).all() and over.max().item() <= 1.0, name
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])

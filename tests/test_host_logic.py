@@ -113,6 +113,30 @@ def test_maxpool_refuses_what_its_deleted_kernels_took():
         _capi._raise(rc, None)
 
 
+def test_decoder_op_entry_points_refuse_bad_shapes_before_any_device_work():
+    """the kernel-level entry points of the selection / decoder glue validate their shapes first: RTD_E_INVALID with the reason, and the
+    placeholder pointers (aligned, never read) are not touched - no HIP call is made, so this holds without a GPU"""
+    from telescope_cam_detection_amd import _capi
+    lib = _capi.lib()
+    p = ctypes.c_void_p(4096)
+    lv = (ctypes.c_int32 * 6)(4, 4, 2, 2, 1, 1)
+
+    def refused(rc, why):
+        assert rc == _capi.RTD_E_INVALID
+        with pytest.raises(_capi.RtdError, match=why):
+            _capi._raise(rc, None)
+
+    for direction in (0, 1, 2):
+        refused(lib.rtd_op_split_convert(direction, p, p, 5, 48, 64, 64), "32-channel groups")      # C % 32 != 0
+    refused(lib.rtd_op_split_convert(3, p, p, 5, 32, 32, 32), "direction")
+    refused(lib.rtd_op_select_score(p, 320, p, p, p, p, p, 1, 16, 80, 320), "256-wide rows")       # a score width other than 256
+    refused(lib.rtd_op_select_score(p, 128, p, p, p, p, p, 1, 16, 80, 128), "256-wide rows")
+    refused(lib.rtd_op_msdeform_view(_capi.DT_F32, p, 768, 513, p, p, p, 1, 4, 8, 32, 3, 4, lv, 0.5), "leaves the value row")   # coff + 256 > ld
+    refused(lib.rtd_op_msdeform_view(_capi.DT_F32, p, 256, 256, p, p, p, 1, 4, 8, 32, 3, 4, lv, 0.5), "leaves the value row")
+    refused(lib.rtd_op_msdeform_view(_capi.DT_F32, p, 768, 0, p, p, p, 1, 4, 8, 16, 3, 4, lv, 0.5), "head dim must be 32")      # hd != 32
+    refused(lib.rtd_op_postprocess(p, p, p, 1, 300, 80, 100, 1, p), "K == Q")
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="CPU-only behaviour")
 def test_detector_fails_loudly_without_gpu():
     """the product path has no CPU fallback: load_model() -> False (never raises), detect() -> [] (reference :248-250)"""

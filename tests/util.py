@@ -74,3 +74,23 @@ def match_detections(ref_labels, ref_boxes, ref_scores, labels, boxes, scores, s
     if return_unmatched:
         return matched, len(ref_labels), ws, wb, unmatched
     return matched, len(ref_labels), ws, wb
+
+
+# ---- the tolerance rule of the kernel-level fp64 comparisons (tests/test_gpu_decoder_ops.py) ----
+FACTOR = 4.0
+
+
+def ulp32(v):
+    return float(np.spacing(np.float32(abs(float(v)))))
+
+
+def within(family, name, got, ref64, ref32, factor=FACTOR):
+    """|got - ref64| <= factor * (e_ref + ulp(max |ref64|)) with e_ref = max |ref32 - ref64|; prints the figures first"""
+    got, ref64, ref32 = (torch.as_tensor(t).double().reshape(-1) for t in (got, ref64, ref32))
+    assert torch.isfinite(ref64).all(), "the reference itself must be finite"
+    e_ref = (ref32 - ref64).abs().max().item()
+    ulp = ulp32(ref64.abs().max().item())
+    err = (got - ref64).abs().max().item()
+    print(f"[{family}] {name}: kernel err {err:.3e}, e_ref {e_ref:.3e}, ulp {ulp:.3e}, ratio {err / (e_ref + ulp):.2f} (allowed {factor})")
+    assert torch.isfinite(got).all(), (family, name)
+    assert err <= factor * (e_ref + ulp), (family, name, err, e_ref, ulp)
