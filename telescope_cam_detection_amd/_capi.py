@@ -300,19 +300,23 @@ def _stats_of(handle) -> dict:
     return {k: (float(getattr(st, k)) if k == "max_abs_filter" else int(getattr(st, k))) for k, _ in RtdStats._fields_ if k not in ("struct_size", "reserved")}
 
 
-def _raise(code: int, handle) -> None:
-    msg = (lib().rtd_last_error(handle) or b"").decode(errors="replace")
-    st = _stats_of(handle)
-    if st:          # a failure describes itself: what the handle had done when it happened, and whether its stream is in capture state
-        msg += " | handle: " + ", ".join(f"{k}={v}" for k, v in st.items())
+def _raise_msg(code: int, what: str, msg: bytes, suffix: str = ""):
+    msg = (msg or b"").decode(errors="replace") + suffix
     if code == RTD_E_OOM:
         import torch
         # the only exception the reference's degrade path reacts to (src/inference_engine_yolox.py:607)
-        raise torch.cuda.OutOfMemoryError(f"HIP out of memory in libmi355rtdetr: {msg}")
+        raise torch.cuda.OutOfMemoryError(f"HIP out of memory in {what}: {msg}")
     raise RtdError(code, msg)
 
 
-# ---- the stand-alone back ends (motion, mog2, jpeg, overlay, enhance, esrgan) ---------------------------------------------------------
+def _raise(code: int, handle=None) -> None:
+    """the handle-less form: the calling thread's last refused rtd_create / rtd_op_* / rtd_crop_resize_batch (a call on a handle
+    raises through Handle._raise)"""
+    assert handle is None
+    _raise_msg(code, Engine._what, lib().rtd_last_error(None))
+
+
+# ---- the seven handles (the engine; motion, mog2, jpeg, overlay, enhance, esrgan) ------------------------------------------------------
 def device_index(device) -> int:
     """an int, None (torch's current device), a torch.device or a string like 'cuda:1' -> the device's index"""
     if isinstance(device, int):
@@ -339,7 +343,7 @@ def c_frames(ptrs, shapes):
 
 
 class Handle:
-    """One handle of a stand-alone back end: rtd_<x>_create / _last_error / _destroy, and _wait_stream where the back end owns a
+    """One handle of the engine or of a stand-alone back end: rtd_<x>_create / _last_error / _destroy, and _wait_stream where the back end owns a
     stream.  A subclass names its functions' prefix and what the out-of-memory message calls it."""
     _prefix = ""          # "rtd_jpeg"
     _what = ""            # "the JPEG encoder"
@@ -357,12 +361,7 @@ class Handle:
             self._raise(rc)
 
     def _raise(self, rc: int):
-        msg = (self._fn("last_error")(self._h) or b"").decode(errors="replace")
-        if rc == RTD_E_OOM:
-            import torch
-            # the only exception the reference's degrade path reacts to (src/inference_engine_yolox.py:607)
-            raise torch.cuda.OutOfMemoryError(f"HIP out of memory in {self._what}: {msg}")
-        raise RtdError(rc, msg)
+        _raise_msg(rc, self._what, self._fn("last_error")(self._h))
 
     def _check(self, rc: int) -> None:
         if rc != RTD_OK:
@@ -470,49 +469,33 @@ def make_config(arch: Arch, device: int, precision: int, max_batch: int, input_s
     return c
 
 
-class Engine:
+class Engine(Handle):
     """Thin RAII wrapper of one rtd_handle."""
+    _prefix = "rtd"
+    _what = "libmi355rtdetr"
 
     def __init__(self, arch: Arch, blob: bytes, device: int = 0, precision: int = PREC_BF16, max_batch: int = 8,
                  input_size=(640, 640), use_graph: bool = True, profile: int = PROFILE_LATENCY, prepare=()):
         self.arch = arch
         self.num_queries = arch.num_queries
         self.max_batch = max_batch
-        self._h = C.c_void_p()
-        cfg = make_config(arch, device, precision, max_batch, input_size, use_graph, profile)
-        rc = lib().rtd_create(C.byref(cfg), C.byref(self._h))
-        if rc != RTD_OK:
-            self._h = C.c_void_p()
-            _raise(rc, None)
-        buf = (C.c_char * len(blob)).from_buffer_copy(blob)
-        rc = lib().rtd_load_weights(self._h, buf, len(blob))
-        if rc != RTD_OK:
-            try:
-                _raise(rc, self._h)
-            finally:
-                self.close()
-        for n in sorted({int(b) for b in prepare}):        # plan + arena + hipGraph of every declared batch size: the serving path only replays
-            try:
+        self._open(C.byref(make_config(arch, device, precision, max_batch, input_size, use_graph, profile)))
+        try:
+            self._check(self._fn("load_weights")(self._h, (C.c_char * len(blob)).from_buffer_copy(blob), len(blob)))
+            for n in sorted({int(b) for b in prepare}):    # plan + arena + hipGraph of every declared batch size: the serving path only replays
                 self.prepare(n)
-            except BaseException:
-                self.close()
-                raise
+        except BaseException:
+            self.close()
+            raise
+
+    def _raise(self, rc: int):
+        st = self.stats()
+        # a failure describes itself: what the handle had done when it happened, and whether its stream is in capture state
+        suffix = " | handle: " + ", ".join(f"{k}={v}" for k, v in st.items()) if st else ""
+        _raise_msg(rc, self._what, self._fn("last_error")(self._h), suffix)
 
     def prepare(self, n: int):
-        rc = lib().rtd_prepare(self._h, int(n))
-        if rc != RTD_OK:
-            _raise(rc, self._h)
-
-    def close(self):
-        if getattr(self, "_h", None) is not None and self._h.value:
-            lib().rtd_destroy(self._h)
-            self._h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+        self._check(self._fn("prepare")(self._h, int(n)))
 
     # ---- helpers
     @staticmethod
@@ -538,10 +521,7 @@ class Engine:
         n, ptrs, hw, keep = self._frame_args(frames, on_device)
         out = np.zeros((n, self.num_queries), dtype=DET_DTYPE)
         counts = (C.c_int32 * n)()
-        rc = lib().rtd_infer(self._h, n, ptrs, hw, int(on_device), float(conf), int(bool(wildlife_only)),
-                             out.ctypes.data, counts)
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("infer")(self._h, n, ptrs, hw, int(on_device), float(conf), int(bool(wildlife_only)), out.ctypes.data, counts))
         return [out[i, : counts[i]] for i in range(n)]
 
     def infer_raw(self, frames, on_device: bool = False):
@@ -550,27 +530,21 @@ class Engine:
         labels = np.zeros((n, Q), np.int32)
         boxes = np.zeros((n, Q, 4), np.float32)
         scores = np.zeros((n, Q), np.float32)
-        rc = lib().rtd_infer_raw(self._h, n, ptrs, hw, int(on_device), labels.ctypes.data, boxes.ctypes.data, scores.ctypes.data)
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("infer_raw")(self._h, n, ptrs, hw, int(on_device), labels.ctypes.data, boxes.ctypes.data, scores.ctypes.data))
         return labels, boxes, scores
 
     def infer_async(self, frames, on_device: bool = True):
         """Enqueue one batch and return.  Host frames are staged inside the library (pinned buffer + one DMA): the arrays may be
         released at once; device frames must stay alive until collect() / sync()."""
         n, ptrs, hw, keep = self._frame_args(frames, on_device)
-        rc = lib().rtd_infer_async(self._h, n, ptrs, hw, int(on_device))
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("infer_async")(self._h, n, ptrs, hw, int(on_device)))
         return n
 
     def collect(self, conf: float, wildlife_only: bool):
         """Wait for the batch of the last infer_async and return what infer() returns for it."""
         out = np.zeros((self.max_batch, self.num_queries), dtype=DET_DTYPE)
         counts = (C.c_int32 * self.max_batch)()
-        rc = lib().rtd_collect(self._h, float(conf), int(bool(wildlife_only)), out.ctypes.data, counts)
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("collect")(self._h, float(conf), int(bool(wildlife_only)), out.ctypes.data, counts))
         return out, counts
 
     def make_async_args(self, frames_dev):
@@ -578,22 +552,16 @@ class Engine:
         return self._frame_args(frames_dev, True)
 
     def infer_async_prepared(self, args):
-        rc = lib().rtd_infer_async(self._h, args[0], args[1], args[2], 1)
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("infer_async")(self._h, args[0], args[1], args[2], 1))
 
     def wait_stream(self, producer_stream: int):
         """The engine's stream waits for everything enqueued so far on `producer_stream` (a raw hipStream_t value, e.g.
         torch.cuda.current_stream().cuda_stream; 0 = the default stream)."""
-        rc = lib().rtd_wait_stream(self._h, C.c_void_p(int(producer_stream) or None))
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("wait_stream")(self._h, C.c_void_p(int(producer_stream) or None)))
 
     def signal_stream(self, consumer_stream: int):
         """`consumer_stream` waits for everything enqueued so far on the engine's stream."""
-        rc = lib().rtd_signal_stream(self._h, C.c_void_p(int(consumer_stream) or None))
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("signal_stream")(self._h, C.c_void_p(int(consumer_stream) or None)))
 
     def stats(self) -> dict:
         return _stats_of(self._h)
@@ -602,18 +570,14 @@ class Engine:
         """rtd_preprocess: one HWC uint8 BGR frame (numpy array, or a contiguous device tensor when on_device) -> [3, H, W] fp32 at out_ptr (device)."""
         h, w = int(frame.shape[0]), int(frame.shape[1])
         src = frame.data_ptr() if on_device else frame.ctypes.data
-        rc = lib().rtd_preprocess(self._h, C.c_void_p(src), h, w, int(on_device), C.c_void_p(out_ptr))
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("preprocess")(self._h, C.c_void_p(src), h, w, int(on_device), C.c_void_p(out_ptr)))
 
     def self_check(self, blob: bytes) -> dict:
         """rtd_self_check: this engine's arithmetic against the library's exact fp32 engine on one built-in frame, with the weights of
         `blob` (the container this engine was loaded from: the handle keeps no host copy)."""
         rep = RtdCheckReport()
         rep.struct_size = C.sizeof(RtdCheckReport)
-        rc = lib().rtd_self_check(self._h, blob, len(blob), C.byref(rep))
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("self_check")(self._h, blob, len(blob), C.byref(rep)))
         return {"rows": rep.rows, "rows_matched": rep.rows_matched, "worst_score_err": rep.worst_score_err, "worst_box_err_px": rep.worst_box_err_px,
                 "score_tol": rep.score_tol, "box_tol_px": rep.box_tol_px, "saturated_values": rep.saturated_values,
                 "max_abs_filter": rep.max_abs_filter, "max_abs_filter_name": rep.max_abs_filter_name.decode(errors="replace")}
@@ -621,48 +585,31 @@ class Engine:
     def result_block(self):
         p = C.c_void_p()
         n = C.c_int64()
-        rc = lib().rtd_result_block(self._h, C.byref(p), C.byref(n))
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("result_block")(self._h, C.byref(p), C.byref(n)))
         return p.value, n.value
 
     def sync(self):
-        rc = lib().rtd_sync(self._h)
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("sync")(self._h))
 
     def stream(self) -> int:
         return lib().rtd_stream(self._h) or 0
 
     def debug_tensor(self, name: str) -> np.ndarray:
         shape = (C.c_int64 * 4)()
-        rc = lib().rtd_debug_tensor(self._h, name.encode(), None, 0, shape)
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("debug_tensor")(self._h, name.encode(), None, 0, shape))
         out = np.zeros(tuple(shape), np.float32)
-        rc = lib().rtd_debug_tensor(self._h, name.encode(), out.ctypes.data, out.size, shape)
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("debug_tensor")(self._h, name.encode(), out.ctypes.data, out.size, shape))
         return out
 
     def force_topk(self, idx: Optional[np.ndarray]):
-        if idx is None:
-            rc = lib().rtd_debug_force_topk(self._h, None, 0)
-        else:
-            a = np.ascontiguousarray(idx, np.int32)
-            rc = lib().rtd_debug_force_topk(self._h, a.ctypes.data, a.shape[0])
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        a = None if idx is None else np.ascontiguousarray(idx, np.int32)
+        self._check(self._fn("debug_force_topk")(self._h, None if a is None else a.ctypes.data, 0 if a is None else a.shape[0]))
 
     def profile(self, n: int, reps: int = 5):
         cnt = C.c_int32()
-        rc = lib().rtd_profile(self._h, n, reps, None, 0, C.byref(cnt))
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("profile")(self._h, n, reps, None, 0, C.byref(cnt)))
         arr = (RtdLayerTime * cnt.value)()
-        rc = lib().rtd_profile(self._h, n, reps, arr, cnt.value, C.byref(cnt))
-        if rc != RTD_OK:
-            _raise(rc, self._h)
+        self._check(self._fn("profile")(self._h, n, reps, arr, cnt.value, C.byref(cnt)))
         return [dict(name=a.name.decode(), kernel=a.kernel.decode(), ms=a.ms, flops=a.flops, bytes=a.bytes) for a in arr]
 
     def arena_bytes(self) -> int:

@@ -1,5 +1,6 @@
-// backend.h - the host-side scaffold of the stand-alone back ends (motion, mog2, jpeg, overlay, enhance, esrgan): what a handle holds,
-// how a C entry point turns exceptions into a return code and a message, how a handle is created, and the buffers it grows on demand.
+// backend.h - the host-side scaffold of all seven handles (seven handles, one scaffold): the detector engine (engine_internal.h) and the
+// stand-alone back ends (motion, mog2, jpeg, overlay, enhance, esrgan).  What a handle holds, how a C entry point turns exceptions into a
+// return code and a message, how a handle is created, and the buffers it grows on demand.
 // A back end writes its kernels, its argument checks and its extern "C" functions; nothing here generates an entry point.  Host only.
 #pragma once
 #include <algorithm>
@@ -34,7 +35,7 @@ int caught(std::string& err, F&& f) {
   }
 }
 
-// every back end's handle derives from this
+// every handle derives from this
 struct Base {
   int device = 0;
   std::mutex mu;

@@ -18,7 +18,6 @@ __thread long long t_launches = 0;
 void launch_force_idx(int32_t* dst, const int32_t* src, const int32_t* flag, int n, hipStream_t s);
 
 namespace rtd_eng {
-thread_local std::string g_create_error;
 PlanOpts g_opts;
 }  // namespace rtd_eng
 
@@ -114,12 +113,12 @@ static void* upload_filter(rtd_engine* e, const std::vector<float>& pad, int Npa
         tmp = nullptr;
       } else if (dt == F16X2) {
         out = e->dmalloc(pad.size() * 4);
-        launch_f32_to_split(tmp, Kcols, out, Kcols, Npad, Kcols, e->stream);
-        er = hipStreamSynchronize(e->stream);
+        launch_f32_to_split(tmp, Kcols, out, Kcols, Npad, Kcols, e->q.stream);
+        er = hipStreamSynchronize(e->q.stream);
       } else {
         out = e->dmalloc(pad.size() * 2);
-        launch_f32_to(tmp, out, BF16, (int64_t)pad.size(), e->stream);
-        er = hipStreamSynchronize(e->stream);
+        launch_f32_to(tmp, out, BF16, (int64_t)pad.size(), e->q.stream);
+        er = hipStreamSynchronize(e->q.stream);
       }
     }
   } catch (...) {
@@ -1129,11 +1128,11 @@ Plan* get_plan(rtd_engine* e, int n) {
   plan->arena_bytes = dry.off + 4096;
   HIP_CHECK(hipMalloc(&plan->arena, plan->arena_bytes));
   e->allocs.push_back(plan->arena);
-  HIP_CHECK(hipMemsetAsync(plan->arena, 0, plan->arena_bytes, e->stream));
+  HIP_CHECK(hipMemsetAsync(plan->arena, 0, plan->arena_bytes, e->q.stream));
   plan->named.clear();
   Builder real{e, plan.get(), false};
   build_graph(real);
-  HIP_CHECK(hipStreamSynchronize(e->stream));
+  HIP_CHECK(hipStreamSynchronize(e->q.stream));
   Plan* p = plan.get();
   e->plans[n] = std::move(plan);
   e->st_plans++;
@@ -1145,11 +1144,11 @@ void run_op(rtd_engine* e, Op& op) {
   if (op.debug_only && !e->force_used) return;
   if (op.kind == 1 || op.kind == 2) {
     hipEvent_t ev = op.kind == 1 ? e->ev_fork : e->ev_join;
-    hipStream_t from = op.kind == 1 ? e->stream : e->side, to = op.kind == 1 ? e->side : e->stream;
+    hipStream_t from = op.kind == 1 ? e->q.stream : e->side, to = op.kind == 1 ? e->side : e->q.stream;
     HIP_CHECK(hipEventRecord(ev, from));
     HIP_CHECK(hipStreamWaitEvent(to, ev, 0));
   } else {
-    op.run(op.lane == 1 ? e->side : e->stream);
+    op.run(op.lane == 1 ? e->side : e->q.stream);
   }
 }
 
@@ -1161,7 +1160,7 @@ void run_op(rtd_engine* e, Op& op) {
 void build_exec(rtd_engine* e, Plan* p, long long eager_launches) {
   GraphBuild gb;
   HIP_CHECK(hipGraphCreate(&gb.graph, 0));
-  gb.lane_stream[0] = e->stream;
+  gb.lane_stream[0] = e->q.stream;
   gb.lane_stream[1] = e->side;
   t_graph_build = &gb;
   try {
@@ -1169,7 +1168,7 @@ void build_exec(rtd_engine* e, Plan* p, long long eager_launches) {
       if (op.debug_only && !e->force_used) continue;
       if (op.kind == 1) gb.fork();
       else if (op.kind == 2) gb.join();
-      else op.run(op.lane == 1 ? e->side : e->stream);
+      else op.run(op.lane == 1 ? e->side : e->q.stream);
     }
   } catch (...) {
     t_graph_build = nullptr;
@@ -1199,11 +1198,11 @@ void warm_and_build(rtd_engine* e, Plan* p) {
     if (op.debug_only && !e->force_used) continue;
     if (trace) { fprintf(stderr, "[rtd] %s (%s)\n", op.name.c_str(), op.kernel); fflush(stderr); }
     run_op(e, op);
-    if (trace) { HIP_CHECK(hipStreamSynchronize(e->side)); HIP_CHECK(hipStreamSynchronize(e->stream)); }
+    if (trace) { HIP_CHECK(hipStreamSynchronize(e->side)); HIP_CHECK(hipStreamSynchronize(e->q.stream)); }
   }
   const long long launches = t_launches - l0;
   HIP_CHECK(hipStreamSynchronize(e->side));
-  HIP_CHECK(hipStreamSynchronize(e->stream));
+  HIP_CHECK(hipStreamSynchronize(e->q.stream));
   e->st_eager++;
   build_exec(e, p, launches);
 }
@@ -1211,7 +1210,7 @@ void warm_and_build(rtd_engine* e, Plan* p) {
 void run_plan(rtd_engine* e, Plan* p) {
   if (e->cfg.use_graph) {
     if (!p->exec) warm_and_build(e, p);      // (the eager pass above already produced this call's results once; the replay repeats them)
-    HIP_CHECK(hipGraphLaunch(p->exec, e->stream));
+    HIP_CHECK(hipGraphLaunch(p->exec, e->q.stream));
     e->st_graph_launches++;
   } else {
     for (auto& op : p->ops) run_op(e, op);
@@ -1219,14 +1218,12 @@ void run_plan(rtd_engine* e, Plan* p) {
   }
 }
 
-// A per-call staging buffer that only grows.  Work enqueued earlier may still read the old one: the stream drains before it is freed.
-static void grow(rtd_engine* e, uint8_t*& ptr, size_t& have, size_t need, bool pinned = false) {
-  if (need <= have) return;
-  HIP_CHECK(hipStreamSynchronize(e->stream));
-  if (ptr) (void)(pinned ? hipHostFree(ptr) : hipFree(ptr));
-  ptr = nullptr; have = 0;
-  HIP_CHECK(pinned ? hipHostMalloc((void**)&ptr, need, hipHostMallocDefault) : hipMalloc((void**)&ptr, need));
-  have = need;
+// A per-call staging buffer.  Work enqueued earlier may still read the old one (a batch is in flight by design): the stream drains
+// before it is replaced.
+template <bool PINNED>
+static void reserve(rtd_engine* e, backend::GrowBuf<PINNED>& b, size_t need) {
+  if (need > b.cap) HIP_CHECK(hipStreamSynchronize(e->q.stream));
+  b.reserve(need);
 }
 
 // preprocess n frames into plan->input and set the post-processor's (w,h) scale
@@ -1244,9 +1241,9 @@ void enqueue_frames(rtd_engine* e, Plan* p, int n, const uint8_t* const* frames,
   // coefficients): the horizontal pass' intermediate [src_h][W][3] must fit the largest of them, not only the resized ones
   if (any_resize)
     for (int i = 0; i < n; ++i) max_tmp = std::max(max_tmp, (size_t)hw[2 * i] * W * 3);   // (the fused uint8 stem resamples only the odd-sized ones)
-  if (!on_device) grow(e, e->frame_stage, e->frame_stage_bytes, total);
-  if (!on_device && via_pinned) grow(e, e->pin_stage, e->pin_stage_bytes, total, /*pinned=*/true);
-  grow(e, e->resize_tmp, e->resize_tmp_bytes, max_tmp);
+  if (!on_device) reserve(e, e->frame_stage, total);
+  if (!on_device && via_pinned) reserve(e, e->pin_stage, total);
+  reserve(e, e->resize_tmp, max_tmp);
   size_t off = 0;
   bool all_identity = true;
   FrameArgs fa;
@@ -1256,9 +1253,9 @@ void enqueue_frames(rtd_engine* e, Plan* p, int n, const uint8_t* const* frames,
     const size_t bytes = (size_t)hw[2 * i] * hw[2 * i + 1] * 3;
     const uint8_t* dev = frames[i];
     if (!on_device) {
-      if (via_pinned) memcpy(e->pin_stage + off, frames[i], bytes);   // the caller's buffer is free again when the call returns; one DMA below
-      else HIP_CHECK(hipMemcpyAsync(e->frame_stage + off, frames[i], bytes, hipMemcpyHostToDevice, e->stream));
-      dev = e->frame_stage + off;
+      if (via_pinned) memcpy(e->pin_stage.p + off, frames[i], bytes);   // the caller's buffer is free again when the call returns; one DMA below
+      else HIP_CHECK(hipMemcpyAsync(e->frame_stage.p + off, frames[i], bytes, hipMemcpyHostToDevice, e->q.stream));
+      dev = e->frame_stage.p + off;
       off += (bytes + 255) / 256 * 256;
     }
     fa.ptr[i] = dev;
@@ -1266,7 +1263,7 @@ void enqueue_frames(rtd_engine* e, Plan* p, int n, const uint8_t* const* frames,
     fa.scale_wh[2 * i + 1] = (float)hw[2 * i];
     if (hw[2 * i] != H || hw[2 * i + 1] != W) all_identity = false;
   }
-  if (!on_device && via_pinned) HIP_CHECK(hipMemcpyAsync(e->frame_stage, e->pin_stage, off, hipMemcpyHostToDevice, e->stream));
+  if (!on_device && via_pinned) HIP_CHECK(hipMemcpyAsync(e->frame_stage.p, e->pin_stage.p, off, hipMemcpyHostToDevice, e->q.stream));
   if (p->stem_fused) {
     // frames of the network's size are read in place; the others are resampled (PIL-exact, uint8) into the staging slots
     if (!all_identity && !e->u8_stage) HIP_CHECK(hipMalloc((void**)&e->u8_stage, (size_t)e->cfg.max_batch * H * W * 3));
@@ -1274,21 +1271,21 @@ void enqueue_frames(rtd_engine* e, Plan* p, int n, const uint8_t* const* frames,
       if (hw[2 * i] == H && hw[2 * i + 1] == W) continue;
       const ResizeCoef& rc = resize_tables(e, hw[2 * i], hw[2 * i + 1]);
       uint8_t* dst = e->u8_stage + (size_t)i * H * W * 3;
-      launch_resize_pil_u8(fa.ptr[i], hw[2 * i], hw[2 * i + 1], e->resize_tmp, dst, H, W, rc, e->stream);
+      launch_resize_pil_u8(fa.ptr[i], hw[2 * i], hw[2 * i + 1], e->resize_tmp.p, dst, H, W, rc, e->q.stream);
       fa.ptr[i] = dst;
     }
-    launch_set_frame_table(fa, p->frame_table, p->scale_wh, e->stream);
+    launch_set_frame_table(fa, p->frame_table, p->scale_wh, e->q.stream);
     e->last_fa = fa;
     return;
   }
   if (all_identity) {
-    launch_preprocess_identity(fa, H, W, p->input, p->scale_wh, e->stream);
+    launch_preprocess_identity(fa, H, W, p->input, p->scale_wh, e->q.stream);
   } else {
-    launch_set_scale(fa, p->scale_wh, e->stream);
+    launch_set_scale(fa, p->scale_wh, e->q.stream);
     for (int i = 0; i < n; ++i) {
       // the same resampler handles an identity-sized frame exactly (1-tap coefficients of 1.0)
       const ResizeCoef& rc = resize_tables(e, hw[2 * i], hw[2 * i + 1]);
-      launch_resize_pil(fa.ptr[i], hw[2 * i], hw[2 * i + 1], e->resize_tmp, p->input, i, rc, e->stream);
+      launch_resize_pil(fa.ptr[i], hw[2 * i], hw[2 * i + 1], e->resize_tmp.p, p->input, i, rc, e->q.stream);
     }
   }
 }
@@ -1301,13 +1298,13 @@ void check_n(rtd_engine* e, int n) {
 // Nobody else may have left the handle's streams in capture mode (the library itself never captures): if some other component of the
 // process did, say so instead of failing somewhere inside with a bare HIP code.
 void check_streams_live(rtd_engine* e) {
-  for (hipStream_t st : {e->stream, e->side}) {
+  for (hipStream_t st : {e->q.stream, e->side}) {
     if (!st) continue;
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
     const hipError_t er = hipStreamIsCapturing(st, &cs);
     if (er != hipSuccess) (void)hipGetLastError();
     RTD_CHECK(er == hipSuccess && cs == hipStreamCaptureStatusNone, RTD_E_STATE,
-              std::string("the handle's ") + (st == e->stream ? "main" : "side") + " stream is in capture state " + std::to_string((int)cs) + " (hipStreamIsCapturing: " +
+              std::string("the handle's ") + (st == e->q.stream ? "main" : "side") + " stream is in capture state " + std::to_string((int)cs) + " (hipStreamIsCapturing: " +
                   hipGetErrorString(er) + "); this library never captures - another component of the process put it there");
   }
 }
@@ -1316,7 +1313,7 @@ void forward(rtd_engine* e, int n, const uint8_t* const* frames, const int32_t* 
   check_n(e, n);
   HIP_CHECK(hipSetDevice(e->cfg.device));
   check_streams_live(e);
-  if (via_pinned && e->in_flight) { HIP_CHECK(hipStreamSynchronize(e->stream)); e->in_flight = false; }   // the staging buffers hold one batch
+  if (via_pinned && e->in_flight) { HIP_CHECK(hipStreamSynchronize(e->q.stream)); e->in_flight = false; }   // the staging buffers hold one batch
   Plan* p = get_plan(e, n);
   enqueue_frames(e, p, n, frames, hw, on_device, via_pinned);
   run_plan(e, p);
@@ -1328,12 +1325,12 @@ void point_at_blank_frames(rtd_engine* h, Plan* p, int n) {
   if (!p->stem_fused) return;
   const size_t fb = (size_t)h->cfg.input_h * h->cfg.input_w * 3;
   if (!h->u8_stage) HIP_CHECK(hipMalloc((void**)&h->u8_stage, (size_t)h->cfg.max_batch * fb));
-  HIP_CHECK(hipMemsetAsync(h->u8_stage, 0, (size_t)h->cfg.max_batch * fb, h->stream));
+  HIP_CHECK(hipMemsetAsync(h->u8_stage, 0, (size_t)h->cfg.max_batch * fb, h->q.stream));
   FrameArgs fa;
   memset(&fa, 0, sizeof fa);
   fa.n = n;
   for (int i = 0; i < n; ++i) { fa.ptr[i] = h->u8_stage + (size_t)i * fb; fa.scale_wh[2 * i] = (float)h->cfg.input_w; fa.scale_wh[2 * i + 1] = (float)h->cfg.input_h; }
-  launch_set_frame_table(fa, p->frame_table, p->scale_wh, h->stream);
+  launch_set_frame_table(fa, p->frame_table, p->scale_wh, h->q.stream);
   h->last_fa = fa;
 }
 
@@ -1354,11 +1351,12 @@ extern "C" {
 
 const char* rtd_version(void) { return "mi355-rtdetr 0.1 (gfx950)"; }
 
-const char* rtd_last_error(rtd_handle h) { return h ? h->err.c_str() : g_create_error.c_str(); }
+const char* rtd_last_error(rtd_handle h) { return backend::last_error(h); }
 
+// no HIP call: the device is first touched by rtd_load_weights
 int rtd_create(const rtd_config* cfg, rtd_handle* out) {
-  if (!cfg || !out) { g_create_error = "null argument"; return RTD_E_INVALID; }
-  try {
+  return backend::create(out, rtd_destroy, [&](rtd_engine* e) {
+    RTD_CHECK(cfg, RTD_E_INVALID, "null argument");
     RTD_CHECK(cfg->struct_size == (int32_t)sizeof(rtd_config), RTD_E_INVALID, "rtd_config.struct_size mismatch");
     RTD_CHECK(cfg->precision == RTD_PREC_BF16 || cfg->precision == RTD_PREC_FP32 || cfg->precision == RTD_PREC_F16X3, RTD_E_INVALID, "precision");
     RTD_CHECK(cfg->max_batch >= 1 && cfg->max_batch <= 64, RTD_E_INVALID, "max_batch must be in [1,64]");
@@ -1373,8 +1371,8 @@ int rtd_create(const rtd_config* cfg, rtd_handle* out) {
     for (int i = 0; i < 4; ++i) RTD_CHECK(cfg->depths[i] >= 1 && cfg->hidden_sizes[i] % 32 == 0, RTD_E_INVALID, "stage config");
     RTD_CHECK(cfg->num_queries >= 1 && cfg->num_queries <= 1024 && cfg->num_classes % 4 == 0, RTD_E_INVALID, "num_queries <= 1024, num_classes % 4 == 0");
     RTD_CHECK((cfg->dec_heads * cfg->n_levels * cfg->n_points * 3) % 4 == 0, RTD_E_INVALID, "sampling head width");
-    rtd_engine* e = new rtd_engine();
     e->cfg = *cfg;
+    e->device = cfg->device;
     e->opts = g_opts;
     e->conv_opts = conv_opts_template();
     e->P = cfg->precision == RTD_PREC_BF16 ? BF16 : (cfg->precision == RTD_PREC_F16X3 ? F16X2 : F32);
@@ -1382,17 +1380,9 @@ int rtd_create(const rtd_config* cfg, rtd_handle* out) {
       // hi/lo pairs travel in 32-channel groups (common.h F16X2): every trunk width must be whole groups
       bool ok = (cfg->embedding_size / 2) % SPLIT_GROUP == 0 && cfg->enc_dim % SPLIT_GROUP == 0 && cfg->csp_hidden % SPLIT_GROUP == 0 && cfg->d_model % SPLIT_GROUP == 0;
       for (int i = 0; i < 4; ++i) ok = ok && cfg->hidden_sizes[i] % SPLIT_GROUP == 0 && (cfg->layer_type != RTD_LAYER_BOTTLENECK || (cfg->hidden_sizes[i] / 4) % SPLIT_GROUP == 0);
-      if (!ok) { delete e; RTD_CHECK(false, RTD_E_INVALID, "precision f16x3 needs every trunk channel count to be a multiple of 32 (embedding_size of 64)"); }
+      RTD_CHECK(ok, RTD_E_INVALID, "precision f16x3 needs every trunk channel count to be a multiple of 32 (embedding_size of 64)");
     }
-    *out = e;
-    return RTD_OK;
-  } catch (const Error& er) {
-    g_create_error = er.what();
-    return er.code;
-  } catch (const std::exception& ex) {
-    g_create_error = ex.what();
-    return RTD_E_INVALID;
-  }
+  });
 }
 
 int rtd_load_weights(rtd_handle h, const void* blob, size_t nbytes) {
@@ -1400,15 +1390,11 @@ int rtd_load_weights(rtd_handle h, const void* blob, size_t nbytes) {
     rtd_engine* e = h;
     RTD_CHECK(!e->loaded, RTD_E_STATE, "weights already loaded on this handle");
     RTD_CHECK(blob && nbytes >= 12, RTD_E_WEIGHTS, "empty weight blob");
-    int ndev = 0;
-    HIP_CHECK(hipGetDeviceCount(&ndev));
-    RTD_CHECK(e->cfg.device >= 0 && e->cfg.device < ndev, RTD_E_INVALID, "device ordinal out of range");
-    HIP_CHECK(hipSetDevice(e->cfg.device));
-    if (!e->stream) HIP_CHECK(hipStreamCreateWithFlags(&e->stream, hipStreamNonBlocking));
+    backend::use_device(e->device);
+    if (!e->q.ev_xs) { e->q.close(); e->q.open(); }   // (a load that failed earlier may have left it open, or half open)
     if (!e->side) HIP_CHECK(hipStreamCreateWithFlags(&e->side, hipStreamNonBlocking));
     if (!e->ev_fork) HIP_CHECK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
     if (!e->ev_join) HIP_CHECK(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
-    if (!e->ev_xs) HIP_CHECK(hipEventCreateWithFlags(&e->ev_xs, hipEventDisableTiming));
     e->blob.assign((const char*)blob, (const char*)blob + nbytes);
     parse_blob(e);
     check_weight_range(e);
@@ -1451,8 +1437,8 @@ int rtd_load_weights(rtd_handle h, const void* blob, size_t nbytes) {
 }
 
 static void copy_block(rtd_engine* e, Plan* p, int n) {
-  HIP_CHECK(hipMemcpyAsync(e->block_host, p->block6, (size_t)n * e->cfg.num_queries * 24, hipMemcpyDeviceToHost, e->stream));
-  HIP_CHECK(hipStreamSynchronize(e->stream));
+  HIP_CHECK(hipMemcpyAsync(e->block_host, p->block6, (size_t)n * e->cfg.num_queries * 24, hipMemcpyDeviceToHost, e->q.stream));
+  HIP_CHECK(hipStreamSynchronize(e->q.stream));
 }
 
 static void filter_rows(rtd_engine* h, int n, float conf, int32_t wildlife_only, rtd_det* out, int32_t* counts) {
@@ -1506,7 +1492,7 @@ int rtd_infer_async(rtd_handle h, int32_t n, const uint8_t* const* frames, const
       forward(h, n, frames, hw, frames_on_device != 0, /*via_pinned=*/frames_on_device == 0);
     } catch (...) {
       // whatever was enqueued before the failure (the pinned -> HBM DMA) must not outlive the call: the next submit writes the staging buffer
-      if (h->stream) (void)hipStreamSynchronize(h->stream);
+      h->q.drain();
       h->in_flight = false;
       throw;
     }
@@ -1536,23 +1522,23 @@ int rtd_preprocess(rtd_handle h, const uint8_t* frame, int32_t fh, int32_t fw, i
     HIP_CHECK(hipSetDevice(e->cfg.device));
     check_streams_live(e);
     const int H = e->cfg.input_h, W = e->cfg.input_w;
-    if (e->in_flight) { HIP_CHECK(hipStreamSynchronize(e->stream)); }           // a submitted batch may still read the staging buffers used below
+    if (e->in_flight) { HIP_CHECK(hipStreamSynchronize(e->q.stream)); }           // a submitted batch may still read the staging buffers used below
     const size_t bytes = (size_t)fh * fw * 3;
     const uint8_t* src = frame;
     if (!frame_on_device) {
-      grow(e, e->frame_stage, e->frame_stage_bytes, bytes);
-      HIP_CHECK(hipMemcpyAsync(e->frame_stage, frame, bytes, hipMemcpyHostToDevice, e->stream));
-      src = e->frame_stage;
+      reserve(e, e->frame_stage, bytes);
+      HIP_CHECK(hipMemcpyAsync(e->frame_stage.p, frame, bytes, hipMemcpyHostToDevice, e->q.stream));
+      src = e->frame_stage.p;
     }
     if (fh != H || fw != W) {                                                    // PIL-exact antialiased stretch, uint8 in and out (T.Resize on the PIL image)
-      grow(e, e->resize_tmp, e->resize_tmp_bytes, (size_t)fh * W * 3);
+      reserve(e, e->resize_tmp, (size_t)fh * W * 3);
       if (!e->u8_stage) HIP_CHECK(hipMalloc((void**)&e->u8_stage, (size_t)e->cfg.max_batch * H * W * 3));
       const ResizeCoef& rc = resize_tables(e, fh, fw);
-      launch_resize_pil_u8(src, fh, fw, e->resize_tmp, e->u8_stage, H, W, rc, e->stream);
+      launch_resize_pil_u8(src, fh, fw, e->resize_tmp.p, e->u8_stage, H, W, rc, e->q.stream);
       src = e->u8_stage;
     }
-    launch_u8_hwc_to_chw_f32(src, H, W, out_chw_dev, e->stream);
-    HIP_CHECK(hipStreamSynchronize(e->stream));
+    launch_u8_hwc_to_chw_f32(src, H, W, out_chw_dev, e->q.stream);
+    HIP_CHECK(hipStreamSynchronize(e->q.stream));
   });
 }
 
@@ -1561,13 +1547,13 @@ int rtd_prepare(rtd_handle h, int32_t n) {
     check_n(h, n);
     HIP_CHECK(hipSetDevice(h->cfg.device));
     check_streams_live(h);
-    HIP_CHECK(hipStreamSynchronize(h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->q.stream));
     h->in_flight = false;
     Plan* p = get_plan(h, n);
     if (!h->cfg.use_graph || p->exec) return;
     point_at_blank_frames(h, p, n);   // (without the fused stem the preprocess writes plan->input per call; the zero-filled arena is a valid, black, input)
     warm_and_build(h, p);
-    HIP_CHECK(hipStreamSynchronize(h->stream));
+    HIP_CHECK(hipStreamSynchronize(h->q.stream));
   });
 }
 
@@ -1581,7 +1567,7 @@ int rtd_result_block(rtd_handle h, float** dev_ptr, int64_t* n_floats) {
 
 int rtd_sync(rtd_handle h) {
   return guarded(h, [&] {
-    if (h->stream) { HIP_CHECK(hipSetDevice(h->cfg.device)); HIP_CHECK(hipStreamSynchronize(h->stream)); }
+    if (h->q.stream) { HIP_CHECK(hipSetDevice(h->cfg.device)); HIP_CHECK(hipStreamSynchronize(h->q.stream)); }
     h->in_flight = false;
   });
 }
@@ -1593,8 +1579,7 @@ int rtd_wait_stream(rtd_handle h, void* producer_stream) {
   return guarded(h, [&] {
     RTD_CHECK(h->loaded, RTD_E_STATE, "weights not loaded");
     HIP_CHECK(hipSetDevice(h->cfg.device));
-    HIP_CHECK(hipEventRecord(h->ev_xs, (hipStream_t)producer_stream));
-    HIP_CHECK(hipStreamWaitEvent(h->stream, h->ev_xs, 0));
+    h->q.wait_for(producer_stream);
   });
 }
 
@@ -1602,8 +1587,8 @@ int rtd_signal_stream(rtd_handle h, void* consumer_stream) {
   return guarded(h, [&] {
     RTD_CHECK(h->loaded, RTD_E_STATE, "weights not loaded");
     HIP_CHECK(hipSetDevice(h->cfg.device));
-    HIP_CHECK(hipEventRecord(h->ev_xs, h->stream));
-    HIP_CHECK(hipStreamWaitEvent((hipStream_t)consumer_stream, h->ev_xs, 0));
+    HIP_CHECK(hipEventRecord(h->q.ev_xs, h->q.stream));
+    HIP_CHECK(hipStreamWaitEvent((hipStream_t)consumer_stream, h->q.ev_xs, 0));
   });
 }
 
@@ -1664,12 +1649,12 @@ int rtd_self_check(rtd_handle h, const void* blob, size_t nbytes, rtd_check_repo
       if (rc == RTD_OK && scan) {
         unsigned long long* cnt = nullptr;
         hipError_t er = hipMalloc((void**)&cnt, 8);
-        if (er == hipSuccess) er = hipMemsetAsync(cnt, 0, 8, t->stream);
+        if (er == hipSuccess) er = hipMemsetAsync(cnt, 0, 8, t->q.stream);
         if (er == hipSuccess) {
-          for (const auto& a : t->plans[1]->split_acts) launch_count_saturated(a.first, (int64_t)(a.second / 2), cnt, t->stream);
+          for (const auto& a : t->plans[1]->split_acts) launch_count_saturated(a.first, (int64_t)(a.second / 2), cnt, t->q.stream);
           unsigned long long v = 0;
-          er = hipMemcpyAsync(&v, cnt, 8, hipMemcpyDeviceToHost, t->stream);
-          if (er == hipSuccess) er = hipStreamSynchronize(t->stream);
+          er = hipMemcpyAsync(&v, cnt, 8, hipMemcpyDeviceToHost, t->q.stream);
+          if (er == hipSuccess) er = hipStreamSynchronize(t->q.stream);
           saturated = (int64_t)v;
         }
         if (cnt) (void)hipFree(cnt);
@@ -1726,12 +1711,12 @@ int rtd_get_stats(rtd_handle h, rtd_stats* out) {
   out->saturated_values = h->st_saturated;
   out->max_abs_filter = h->max_abs_filter;
   hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (h->stream && hipStreamIsCapturing(h->stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusInvalidated; }
+  if (h->q.stream && hipStreamIsCapturing(h->q.stream, &cs) != hipSuccess) { (void)hipGetLastError(); cs = hipStreamCaptureStatusInvalidated; }
   out->stream_capture_status = (int32_t)cs;
   return RTD_OK;
 }
 
-void* rtd_stream(rtd_handle h) { return h ? (void*)h->stream : nullptr; }
+void* rtd_stream(rtd_handle h) { return h ? (void*)h->q.stream : nullptr; }
 
 int64_t rtd_arena_bytes(rtd_handle h) {
   if (!h) return 0;
@@ -1743,27 +1728,26 @@ int64_t rtd_arena_bytes(rtd_handle h) {
 
 void rtd_destroy(rtd_handle h) {
   if (!h) return;
-  {
+  if (h->q.stream) {   // everything below is made after rtd_load_weights opened the stream: a handle rtd_create refused makes no HIP call
     std::lock_guard<std::mutex> lk(h->mu);
-    (void)hipSetDevice(h->cfg.device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    (void)hipSetDevice(h->device);
+    h->q.drain();
     if (h->side) (void)hipStreamSynchronize(h->side);
     for (auto& kv : h->plans) {
       if (kv.second->exec) (void)hipGraphExecDestroy(kv.second->exec);
       if (kv.second->graph) (void)hipGraphDestroy(kv.second->graph);
     }
     for (void* p : h->allocs) (void)hipFree(p);
-    if (h->frame_stage) (void)hipFree(h->frame_stage);
-    if (h->resize_tmp) (void)hipFree(h->resize_tmp);
+    h->frame_stage.release();
+    h->resize_tmp.release();
+    h->pin_stage.release();
     if (h->u8_stage) (void)hipFree(h->u8_stage);
     if (h->block_host) (void)hipHostFree(h->block_host);
-    if (h->pin_stage) (void)hipHostFree(h->pin_stage);
     if (h->side) (void)hipStreamSynchronize(h->side);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);             // only ever recorded on live streams: nothing in this library captures
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
-    if (h->ev_xs) (void)hipEventDestroy(h->ev_xs);
     if (h->side) (void)hipStreamDestroy(h->side);
-    if (h->stream) (void)hipStreamDestroy(h->stream);
+    h->q.close();
     (void)hipGetLastError();                         // nothing a teardown call reported may stay behind as this thread's sticky error
   }
   delete h;
@@ -1772,8 +1756,7 @@ void rtd_destroy(rtd_handle h) {
 int rtd_crop_resize_batch(int32_t n, const uint8_t* const* frames_dev, const int32_t* frame_hw, const int32_t* rects, int32_t out_size,
                           const float* mean3, const float* std3, float* out_dev, void* stream) {
   // asynchronous: validated, copied into the launch and enqueued on the caller's stream - no device synchronisation (the header)
-  try {
-    [&] {
+  return backend::caught(create_error(), [&] {
     RTD_CHECK(n >= 0 && frames_dev && frame_hw && rects && mean3 && std3 && out_dev, RTD_E_INVALID, "null argument");
     for (int base = 0; base < n; base += 64) {
       const int m = std::min(64, n - base);
@@ -1787,15 +1770,7 @@ int rtd_crop_resize_batch(int32_t n, const uint8_t* const* frames_dev, const int
       }
       launch_crop_resize(cb, m, out_size, mean3, std3, out_dev + (size_t)base * 3 * out_size * out_size, (hipStream_t)stream);
     }
-    }();
-    return RTD_OK;
-  } catch (const Error& er) {
-    g_create_error = er.what();
-    return er.code;
-  } catch (const std::exception& ex) {
-    g_create_error = ex.what();
-    return RTD_E_HIP;
-  }
+  });
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
 // engine_internal.h - what engine.hip (the product C ABI) and testapi.hip (kernel-level test / bench / debug entry points) share:
 // the handle, its plans and the few host helpers both translation units call.  Not installed, not part of the ABI.
+// The handle is the seventh on the one scaffold of backend.h (seven handles, one scaffold): Base, caught, create, OwnStream, GrowBuf.
 #pragma once
 #include <math.h>
 #include <string.h>
@@ -12,9 +13,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/rtdetr_mi355.h"
 #include "../../include/rtdetr_mi355_test.h"
-#include "common.h"
+#include "backend.h"
 
 namespace rtd_eng {
 using namespace rtd;
@@ -98,11 +98,10 @@ struct ResizeTables {
 
 
 extern PlanOpts g_opts;
-extern thread_local std::string g_create_error;   // last error of a call that has no handle (rtd_create, rtd_op_*, rtd_bench_*)
 
 }  // namespace rtd_eng
 
-struct rtd_engine {
+struct rtd_engine : rtd::backend::Base {   // device = cfg.device
   typedef rtd::ConvOpts ConvOpts; typedef rtd::FrameArgs FrameArgs;
   static constexpr int BF16 = rtd::BF16;
   typedef rtd_eng::PlanOpts PlanOpts; typedef rtd_eng::HostTensor HostTensor; typedef rtd_eng::DevWeight DevWeight;
@@ -111,12 +110,9 @@ struct rtd_engine {
   PlanOpts opts;           // snapshot of g_opts at rtd_create
   ConvOpts conv_opts;      // snapshot of the conv dispatch switches at rtd_create (every launch of this handle's plans points here)
   bool force_used = false; // rtd_debug_force_topk was called on this handle: plans include the (debug-only) index override launch
-  std::mutex mu;
-  std::string err;
-  hipStream_t stream = nullptr;
+  rtd::backend::OwnStream q;                       // the main stream, and the event of rtd_wait_stream / rtd_signal_stream (never handed out)
   hipStream_t side = nullptr;                      // Op::lane 1
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;  // eager passes only (a graph holds these edges as node dependencies)
-  hipEvent_t ev_xs = nullptr;                      // rtd_wait_stream / rtd_signal_stream: this handle's own event, never handed out
   bool loaded = false;
   // counters (rtd_get_stats): what this handle did, so that a failure report describes itself
   int64_t st_plans = 0, st_graphs = 0, st_graph_nodes = 0, st_graph_launches = 0, st_eager = 0, st_submits = 0, st_collects = 0, st_failed = 0;
@@ -124,7 +120,7 @@ struct rtd_engine {
   // real-weights guard: the largest |folded filter value| of the blob (rtd_load_weights) and the saturated activations the last rtd_self_check saw
   float max_abs_filter = 0.f; std::string max_abs_filter_name; int64_t st_saturated = -1;
   bool in_flight = false;                          // rtd_infer_async enqueued a batch that rtd_collect / rtd_sync has not waited for yet
-  uint8_t* pin_stage = nullptr; size_t pin_stage_bytes = 0;    // rtd_infer_async on host frames: pinned staging (one batch in flight per handle)
+  rtd::backend::PinBuf pin_stage;                  // rtd_infer_async on host frames: pinned staging (one batch in flight per handle)
   int P = BF16;  // storage / MFMA type of the conv trunk
   std::vector<char> blob;
   std::map<std::string, HostTensor> host;
@@ -134,8 +130,7 @@ struct rtd_engine {
   std::map<int, std::unique_ptr<Plan>> plans;
   std::map<std::pair<int, int>, ResizeTables> resize;
   // per-call staging
-  uint8_t* frame_stage = nullptr; size_t frame_stage_bytes = 0;
-  uint8_t* resize_tmp = nullptr; size_t resize_tmp_bytes = 0;
+  rtd::backend::DevBuf frame_stage, resize_tmp;
   uint8_t* u8_stage = nullptr;             // fused uint8 stem: resized frames, max_batch x H x W x 3
   FrameArgs last_fa;                       // frame table of the last call (rtd_debug_tensor("input") re-runs the preprocess from it)
   float* block_host = nullptr;
@@ -167,41 +162,22 @@ void pil_coeffs(int in_size, int out_size, std::vector<int32_t>& bounds, std::ve
 std::vector<float> pack_fragments_f32_host(const float* w, int N, int K, int Kuse, int ntiles);
 inline int packed_ntiles(int N) { return ((N + 15) / 16 + 7) / 8 * 8; }
 
+// last error of a call that has no handle (rtd_create, rtd_op_*, rtd_bench_*, rtd_crop_resize_batch): what rtd_last_error(NULL) reports
+inline std::string& create_error() { return backend::create_error<rtd_engine>(); }
+
+// backend::guarded plus the two failure counters of rtd_get_stats
 template <typename F>
 int guarded(rtd_engine* e, F&& f) {
   if (!e) return RTD_E_INVALID;
   std::lock_guard<std::mutex> lk(e->mu);
-  try {
-    f();
-    return RTD_OK;
-  } catch (const Error& er) {
-    e->err = er.what();
-    e->st_failed++; e->st_last_code = er.code;
-    return er.code;
-  } catch (const std::bad_alloc&) {
-    e->err = "host allocation failed";
-    e->st_failed++; e->st_last_code = RTD_E_OOM;
-    return RTD_E_OOM;
-  } catch (const std::exception& ex) {
-    e->err = ex.what();
-    e->st_failed++; e->st_last_code = RTD_E_HIP;
-    return RTD_E_HIP;
-  }
+  const int rc = backend::caught(e->err, f);
+  if (rc != RTD_OK) { e->st_failed++; e->st_last_code = rc; }
+  return rc;
 }
 
 template <typename F>
 inline int op_guard(F&& f) {
-  try {
-    f();
-    HIP_CHECK(hipDeviceSynchronize());
-    return RTD_OK;
-  } catch (const Error& er) {
-    g_create_error = er.what();
-    return er.code;
-  } catch (const std::exception& ex) {
-    g_create_error = ex.what();
-    return RTD_E_HIP;
-  }
+  return backend::caught(create_error(), [&] { f(); HIP_CHECK(hipDeviceSynchronize()); });
 }
 inline Tensor mk(const void* p, int dt, int n, int h, int w, int c) {
   Tensor t;

@@ -39,7 +39,7 @@ int rtd_debug_tensor(rtd_handle h, const char* name, float* out, int64_t capacit
     const Tensor& t = it->second;
     if (p->stem_fused && strcmp(name, "input") == 0 && out) {      // the fused stem never wrote it: run the stand-alone preprocess now
       HIP_CHECK(hipSetDevice(h->cfg.device));
-      launch_preprocess_identity(h->last_fa, h->cfg.input_h, h->cfg.input_w, p->input, p->scale_wh, h->stream);
+      launch_preprocess_identity(h->last_fa, h->cfg.input_h, h->cfg.input_w, p->input, p->scale_wh, h->q.stream);
     }
     shape[0] = t.n; shape[1] = t.h; shape[2] = t.w; shape[3] = t.c;
     const int64_t numel = t.pixels() * t.c;
@@ -50,7 +50,7 @@ int rtd_debug_tensor(rtd_handle h, const char* name, float* out, int64_t capacit
     const size_t es = dtype_size(t.dt);
     if (t.dt == I32) {                                             // index tensors: exact as fp32 (token ids < 2^24)
       std::vector<int32_t> tmp((size_t)numel);
-      HIP_CHECK(hipStreamSynchronize(h->stream));
+      HIP_CHECK(hipStreamSynchronize(h->q.stream));
       HIP_CHECK(hipMemcpy(tmp.data(), t.p, (size_t)numel * 4, hipMemcpyDeviceToHost));
       for (int64_t i = 0; i < numel; ++i) out[i] = (float)tmp[(size_t)i];
       return;
@@ -60,13 +60,13 @@ int rtd_debug_tensor(rtd_handle h, const char* name, float* out, int64_t capacit
     float* f32 = nullptr;
     HIP_CHECK(hipMalloc(&dense, (size_t)numel * es));
     hipError_t er = hipMalloc((void**)&f32, (size_t)numel * 4);
-    if (er == hipSuccess) er = hipMemcpy2DAsync(dense, (size_t)t.c * es, t.p, (size_t)t.ld * es, (size_t)t.c * es, (size_t)t.pixels(), hipMemcpyDeviceToDevice, h->stream);
+    if (er == hipSuccess) er = hipMemcpy2DAsync(dense, (size_t)t.c * es, t.p, (size_t)t.ld * es, (size_t)t.c * es, (size_t)t.pixels(), hipMemcpyDeviceToDevice, h->q.stream);
     if (er == hipSuccess) {
-      if (t.dt == F16X2) launch_split_to_f32(dense, t.c, f32, t.c, t.pixels(), t.c, h->stream);
-      else launch_to_f32(dense, t.dt, f32, numel, h->stream);
-      er = hipMemcpyAsync(out, f32, (size_t)numel * 4, hipMemcpyDeviceToHost, h->stream);
+      if (t.dt == F16X2) launch_split_to_f32(dense, t.c, f32, t.c, t.pixels(), t.c, h->q.stream);
+      else launch_to_f32(dense, t.dt, f32, numel, h->q.stream);
+      er = hipMemcpyAsync(out, f32, (size_t)numel * 4, hipMemcpyDeviceToHost, h->q.stream);
     }
-    if (er == hipSuccess) er = hipStreamSynchronize(h->stream);
+    if (er == hipSuccess) er = hipStreamSynchronize(h->q.stream);
     (void)hipFree(dense);
     if (f32) (void)hipFree(f32);
     HIP_CHECK(er);
@@ -80,7 +80,7 @@ int rtd_debug_force_topk(rtd_handle h, const int32_t* idx, int32_t n) {
     if (idx && !h->force_used) {
       // first use on this handle: the override launch joins the plans; graphs built without it are rebuilt on their next run
       h->force_used = true;
-      HIP_CHECK(hipStreamSynchronize(h->stream));
+      HIP_CHECK(hipStreamSynchronize(h->q.stream));
       for (auto& kv : h->plans) {
         if (kv.second->exec) { (void)hipGraphExecDestroy(kv.second->exec); kv.second->exec = nullptr; }
         if (kv.second->graph) { (void)hipGraphDestroy(kv.second->graph); kv.second->graph = nullptr; }
@@ -91,11 +91,11 @@ int rtd_debug_force_topk(rtd_handle h, const int32_t* idx, int32_t n) {
       RTD_CHECK(n >= 1 && n <= h->cfg.max_batch, RTD_E_INVALID, "batch size");
       for (int64_t i = 0; i < (int64_t)n * h->cfg.num_queries; ++i)
         RTD_CHECK(idx[i] >= 0 && idx[i] < h->S, RTD_E_INVALID, "forced token index out of range");
-      HIP_CHECK(hipMemcpyAsync(h->forced_idx, idx, (size_t)n * h->cfg.num_queries * 4, hipMemcpyHostToDevice, h->stream));
+      HIP_CHECK(hipMemcpyAsync(h->forced_idx, idx, (size_t)n * h->cfg.num_queries * 4, hipMemcpyHostToDevice, h->q.stream));
       flag = 1;
     }
-    HIP_CHECK(hipMemcpyAsync(h->force_flag, &flag, 4, hipMemcpyHostToDevice, h->stream));
-    HIP_CHECK(hipStreamSynchronize(h->stream));
+    HIP_CHECK(hipMemcpyAsync(h->force_flag, &flag, 4, hipMemcpyHostToDevice, h->q.stream));
+    HIP_CHECK(hipStreamSynchronize(h->q.stream));
   });
 }
 
@@ -119,7 +119,7 @@ int rtd_profile(rtd_handle h, int32_t n, int32_t reps, rtd_layer_time* out, int3
     std::vector<hipEvent_t> ev((size_t)nops + 1);
     for (auto& x : ev) HIP_CHECK(hipEventCreate(&x));
     std::vector<double> acc(nops, 0.0);
-    for (Op* op : ops) op->run(h->stream);   // warm-up
+    for (Op* op : ops) op->run(h->q.stream);   // warm-up
     for (int r = 0; r < reps; ++r) {
       if (g_profile_twice) {
         // diagnostic: every op runs twice back to back and only the SECOND run is timed (operands, filter and TLB entries
@@ -127,12 +127,12 @@ int rtd_profile(rtd_handle h, int32_t n, int32_t reps, rtd_layer_time* out, int3
         std::vector<hipEvent_t> ev2((size_t)nops);
         for (auto& x : ev2) HIP_CHECK(hipEventCreate(&x));
         for (int i = 0; i < nops; ++i) {
-          ops[i]->run(h->stream);
-          HIP_CHECK(hipEventRecord(ev2[i], h->stream));
-          ops[i]->run(h->stream);
-          HIP_CHECK(hipEventRecord(ev[i + 1], h->stream));
+          ops[i]->run(h->q.stream);
+          HIP_CHECK(hipEventRecord(ev2[i], h->q.stream));
+          ops[i]->run(h->q.stream);
+          HIP_CHECK(hipEventRecord(ev[i + 1], h->q.stream));
         }
-        HIP_CHECK(hipStreamSynchronize(h->stream));
+        HIP_CHECK(hipStreamSynchronize(h->q.stream));
         for (int i = 0; i < nops; ++i) {
           float ms = 0.f;
           HIP_CHECK(hipEventElapsedTime(&ms, ev2[i], ev[i + 1]));
@@ -141,12 +141,12 @@ int rtd_profile(rtd_handle h, int32_t n, int32_t reps, rtd_layer_time* out, int3
         for (auto& x : ev2) (void)hipEventDestroy(x);
         continue;
       }
-      HIP_CHECK(hipEventRecord(ev[0], h->stream));
+      HIP_CHECK(hipEventRecord(ev[0], h->q.stream));
       for (int i = 0; i < nops; ++i) {
-        ops[i]->run(h->stream);
-        HIP_CHECK(hipEventRecord(ev[i + 1], h->stream));
+        ops[i]->run(h->q.stream);
+        HIP_CHECK(hipEventRecord(ev[i + 1], h->q.stream));
       }
-      HIP_CHECK(hipStreamSynchronize(h->stream));
+      HIP_CHECK(hipStreamSynchronize(h->q.stream));
       for (int i = 0; i < nops; ++i) {
         float ms = 0.f;
         HIP_CHECK(hipEventElapsedTime(&ms, ev[i], ev[i + 1]));

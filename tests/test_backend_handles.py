@@ -1,9 +1,10 @@
-"""The handle scaffold the six stand-alone back ends share (csrc/backend.h, _capi.Handle): what a refused create returns and leaves
-behind, where its message is kept (one string per back end and per thread), and - on the GPU - one create / call / refused call / call
-/ close round of every back end against the restatement its own GPU test uses.
+"""The handle scaffold the seven handles share - the detector engine and the six stand-alone back ends (csrc/backend.h, _capi.Handle):
+what a refused create returns and leaves behind, where its message is kept (one string per handle type and per thread), and - on the
+GPU - one create / call / refused call / call / close round of every handle against the restatement its own GPU test uses.
 
-The first four tests need no GPU: a bad parameter is refused before any HIP call, and a device that does not exist is refused with
-RTD_E_INVALID where a GPU is present and with RTD_E_HIP (no device at all) where none is."""
+The first five tests need no GPU: a bad parameter is refused before any HIP call, and a device that does not exist is refused with
+RTD_E_INVALID where a GPU is present and with RTD_E_HIP (no device at all) where none is.  (rtd_create itself never touches the device:
+the engine meets a missing one in rtd_load_weights, on the GPU below.)"""
 import ctypes as C
 import threading
 
@@ -13,6 +14,7 @@ import pytest
 from telescope_cam_detection_amd import _capi
 
 BACKENDS = ("motion", "mog2", "jpeg", "overlay", "enhance", "esrgan")
+HANDLES = BACKENDS + ("engine",)
 NO_DEVICE = 10 ** 6
 _BLOB = {}
 
@@ -40,8 +42,14 @@ def esrgan_config(device, num_block=1):
     return c
 
 
+def engine_config(device, bad=False):
+    from telescope_cam_detection_amd.arch import ARCHS
+    return _capi.make_config(ARCHS["tiny"], device, _capi.PREC_FP32, 1, (641 if bad else 160, 160), False)
+
+
 def raw_create(name, device, bad=False):
-    """rtd_<name>_create as it is, with valid parameters or with the back end's one bad parameter: (return code, handle value)"""
+    """rtd_<name>_create (the engine's: rtd_create) as it is, with valid parameters or with the handle's one bad parameter: (return
+    code, handle value)"""
     L = _capi.lib()
     h = C.c_void_p(0xDEAD)                                  # a refused create must overwrite this with NULL
     if name == "motion":
@@ -54,6 +62,8 @@ def raw_create(name, device, bad=False):
         rc = L.rtd_overlay_create(device, C.byref(h))
     elif name == "enhance":
         rc = L.rtd_enhance_create(device, C.byref(enhance_params(17 if bad else 8)), C.byref(h))
+    elif name == "engine":
+        rc = L.rtd_create(C.byref(engine_config(device, bad)), C.byref(h))
     else:
         if bad:
             rc = L.rtd_esrgan_create(C.byref(esrgan_config(device, 0)), None, 0, C.byref(h))
@@ -64,10 +74,11 @@ def raw_create(name, device, bad=False):
 
 
 def create_error(name) -> bytes:
-    return getattr(_capi.lib(), f"rtd_{name}_last_error")(None) or b""
+    return getattr(_capi.lib(), "rtd_last_error" if name == "engine" else f"rtd_{name}_last_error")(None) or b""
 
 
-BAD = {"motion": b"blur_size must be odd", "mog2": b"history must be >= 1", "enhance": b"tile grid must be 1..16", "esrgan": b"num_block must be 1..32"}
+BAD = {"motion": b"blur_size must be odd", "mog2": b"history must be >= 1", "enhance": b"tile grid must be 1..16", "esrgan": b"num_block must be 1..32",
+       "engine": b"multiple of 32"}
 
 
 @pytest.mark.parametrize("name", sorted(BAD))
@@ -111,7 +122,23 @@ def test_the_create_message_belongs_to_the_thread_that_failed():
     assert create_error("motion") == mine
 
 
-# ---- on the GPU: one round per back end ------------------------------------------------------------------------------------------
+def test_the_engines_create_message_is_its_own_and_its_threads():
+    rc, h = raw_create("engine", 0, bad=True)               # input size 641
+    assert rc == _capi.RTD_E_INVALID and h is None
+    mine = create_error("engine")
+    assert BAD["engine"] in mine
+
+    def body():                                             # a fresh thread: empty; and the jpeg back end's refusal goes to its own string
+        before = create_error("engine")
+        rc, h = raw_create("jpeg", NO_DEVICE)
+        return before, rc, create_error("jpeg"), create_error("engine")
+    before, rc, jpeg_msg, engine_msg = in_thread(body)
+    assert before == b"" and rc != _capi.RTD_OK and len(jpeg_msg) > 0 and engine_msg == b""
+    assert in_thread(lambda: (raw_create("engine", 0, bad=True), create_error("jpeg"))[1]) == b""
+    assert create_error("engine") == mine
+
+
+# ---- on the GPU: one round per handle ------------------------------------------------------------------------------------------
 def frames16(seed):
     rng = np.random.default_rng(seed)
     return [rng.integers(0, 256, (16, 16, 3), dtype=np.uint8) for _ in range(2)]
@@ -262,24 +289,63 @@ class EsrganRound(CropRound):
         return got.tobytes()
 
 
-ROUNDS = {"motion": MotionRound, "mog2": Mog2Round, "jpeg": JpegRound, "overlay": OverlayRound, "enhance": EnhanceRound, "esrgan": EsrganRound}
+class EngineRound:
+    """the fp32 engine on t_tiny_160 (the smallest case there is: its two 160 x 160 frames in one call, as the parity test runs it),
+    held to everything tests/test_gpu_parity.py::test_fp32_engine_matches_oracle_and_golden asks of that case"""
+
+    def __init__(self, device):
+        from tests import test_gpu_parity as parity
+        self.parity = parity
+        self.case = c = parity.fp32_case("t_tiny_160")
+        self.be = parity.make_engine(c["arch"], c["w"], c["frames"], c["input_size"], "fp32")
+
+    def valid(self):
+        return b"".join(a.tobytes() for a in self.parity.check_fp32_engine(self.be, self.case))
+
+    def refused(self):
+        """one frame more than max_batch; the refusal is counted on the handle"""
+        be = self.be
+        n, ptrs, hw, keep = be._frame_args((self.case["frames"] * 2)[:be.max_batch + 1], False)
+        assert n == be.max_batch + 1
+        out = np.zeros(n * be.num_queries * 4, np.float32)
+        rc = be._L.rtd_infer_raw(be._h, n, ptrs, hw, 0, out.ctypes.data, out.ctypes.data, out.ctypes.data)
+        st = be.stats()
+        assert st["failed_calls"] == 1 and st["last_error_code"] == _capi.RTD_E_INVALID, st
+        return rc
+
+    def missing_device(self, device):
+        """the engine meets its device in rtd_load_weights: the constructor raises and leaves no open handle"""
+        from telescope_cam_detection_amd.weights import fold_weights, pack_blob
+        c = self.case
+        eng = _capi.Engine.__new__(_capi.Engine)
+        with pytest.raises(_capi.RtdError, match="no such device") as ei:
+            eng.__init__(c["arch"], pack_blob(fold_weights(c["arch"], c["w"])), device=device, precision=_capi.PREC_FP32, max_batch=len(c["frames"]),
+                         input_size=c["input_size"], use_graph=False)
+        assert ei.value.code == _capi.RTD_E_INVALID and not eng._h.value
+
+
+ROUNDS = {"motion": MotionRound, "mog2": Mog2Round, "jpeg": JpegRound, "overlay": OverlayRound, "enhance": EnhanceRound, "esrgan": EsrganRound,
+          "engine": EngineRound}
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("name", BACKENDS)
+@pytest.mark.parametrize("name", HANDLES)
 def test_create_call_refused_call_call_close(name):
     import torch
-    rc, h = raw_create(name, torch.cuda.device_count())
-    assert rc == _capi.RTD_E_INVALID and h is None and b"no such device" in create_error(name)
+    if name != "engine":
+        rc, h = raw_create(name, torch.cuda.device_count())
+        assert rc == _capi.RTD_E_INVALID and h is None and b"no such device" in create_error(name)
     r = ROUNDS[name](0)
     try:
         be = r.be
         assert be._h.value
-        if name in ("motion", "mog2", "jpeg", "overlay"):
+        if name == "engine":
+            r.missing_device(torch.cuda.device_count())
+        if name in ("motion", "mog2", "jpeg", "overlay", "engine"):
             be.wait_stream(0)                               # (raises unless RTD_OK)
         first = r.valid()
         assert r.refused() == _capi.RTD_E_INVALID
-        assert len(getattr(be._L, f"rtd_{name}_last_error")(be._h) or b"") > 0
+        assert len(be._fn("last_error")(be._h) or b"") > 0
         assert r.valid() == first
     finally:
         r.be.close()

@@ -49,12 +49,18 @@ FP32_CASES = ["t_tiny_160", "t_tiny_160x224", "t_tinyb_192x128", "t_tinyc_160x22
               "c2_r50_640_scene_bs2"]
 
 
-@pytest.mark.parametrize("name", FP32_CASES)
-def test_fp32_engine_matches_oracle_and_golden(name):
+def fp32_case(name):
+    """a fixture's inputs, its golden outputs and the oracle's outputs for them (computed once per call: share the result)"""
     arch, wseed, input_size, frames, g = load_case(name)
     w = weights_for(arch, wseed)
-    (ol, ob, osc), col = oracle_run(arch, w, frames, input_size)
-    eng = make_engine(arch, w, frames, input_size, "fp32")
+    oracle, col = oracle_run(arch, w, frames, input_size)
+    return dict(name=name, arch=arch, w=w, input_size=input_size, frames=frames, g=g, oracle=oracle, col=col)
+
+
+def check_fp32_engine(eng, case):
+    """one infer_raw of an fp32 engine on the case's frames, held stage by stage and on the final rows to the oracle and the HF fixture;
+    returns (labels, boxes, scores)"""
+    name, frames, g, (ol, ob, osc), col = case["name"], case["frames"], case["g"], case["oracle"], case["col"]
     labels, boxes, scores = eng.infer_raw(frames)
     # stage 0: preprocess is integer/byte work -> bit-exact
     x = nchw(eng.debug_tensor("input"))[:, :3]
@@ -77,6 +83,14 @@ def test_fp32_engine_matches_oracle_and_golden(name):
             # measured: every row on every case; ONE row is the allowance for a near-tie at a top-k cut (gap ~1e-5, see make_golden output)
             assert m >= n - 1, (m, n, ws, wb)
         assert (np.diff(scores[b]) <= 0).all(), "scores must be descending"
+    return labels, boxes, scores
+
+
+@pytest.mark.parametrize("name", FP32_CASES)
+def test_fp32_engine_matches_oracle_and_golden(name):
+    case = fp32_case(name)
+    eng = make_engine(case["arch"], case["w"], case["frames"], case["input_size"], "fp32")
+    check_fp32_engine(eng, case)
     eng.close()
 
 
