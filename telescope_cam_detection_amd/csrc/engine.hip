@@ -1090,11 +1090,8 @@ void Builder::post_process(const Decoded& d) {
   float* block6 = plan->block6 = (float*)alloc((size_t)n * Q * 6 * 4);
   float* scale = plan->scale_wh = (float*)alloc((size_t)n * 2 * 4);
   // one launch when the shape allows (every decoder here: dense [n * Q, C] fp32 logits, Q * C <= 32768), else sigmoid -> top-k -> gather
-  const bool fused_ok = e->opts.post_fused && logits.dt == F32 && logits.ld == C && (int64_t)Q * C <= 32768 && Q <= 1024 && logits.pixels() == (int64_t)n * Q;
-  if (fused_ok) {
-    push("post.fused", "topk", (double)n * Q * C, (double)n * Q * C * 4 + (double)n * Q * 64, [logits, ref8, scale, n, Q, block6](hipStream_t s) {
-      RTD_CHECK(launch_postprocess_fused(logits, ref8, scale, n, Q, block6, s), 1, "post-processor: fused launch refused a shape the plan accepted");
-    });
+  if (e->opts.post_fused && postprocess_fused_supported(logits, n, Q)) {
+    push("post.fused", "topk", (double)n * Q * C, (double)n * Q * C * 4 + (double)n * Q * 64, [logits, ref8, scale, n, Q, block6](hipStream_t s) { launch_postprocess_fused(logits, ref8, scale, n, Q, block6, s); });
     return;
   }
   push("post.sigmoid", "postprocess", (double)n * Q * C, 2.0 * n * Q * C * 4, [logits, scores](hipStream_t s) { launch_postprocess_scores(logits, scores, s); });

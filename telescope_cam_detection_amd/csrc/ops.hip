@@ -650,28 +650,35 @@ struct TopkPost {
   int C, Q;
 };
 __device__ __forceinline__ float sigmoidf_(float x) { return 1.f / (1.f + __expf(-x)); }
+// one candidate as a 64-bit composite (key, ~index): distinct per element, and a larger composite comes first in (key desc, index asc)
+__device__ __forceinline__ unsigned long long topk_entry(unsigned key, int i) { return ((unsigned long long)key << 32) | (unsigned)(0xffffffffu - (unsigned)i); }
+__device__ __forceinline__ int topk_entry_index(unsigned long long e) { return (int)(0xffffffffu - (unsigned)(e & 0xffffffffu)); }
+// one finished detection [label, score, x1, y1, x2, y2] from a flat index into [Q][C]: label = index % C, query = index / C, the query's
+// cxcywh box as xyxy scaled to the original frame (k_topk<true, true> and k_pp_gather)
+__device__ __forceinline__ void write_detection_row(int idx, float score, int b, int C, int Q, const float* __restrict__ ref8,
+                                                    const float* __restrict__ scale_wh, float* __restrict__ o) {
+  const int label = idx % C;
+  int q = idx / C;
+  q = min(max(q, 0), Q - 1);
+  const float* r = ref8 + ((int64_t)b * Q + q) * 8;
+  const float cx = r[0], cy = r[1], w = r[2], h = r[3];
+  const float sw = scale_wh[b * 2 + 0], sh = scale_wh[b * 2 + 1];
+  o[0] = (float)label;
+  o[1] = score;
+  o[2] = (cx - 0.5f * w) * sw;
+  o[3] = (cy - 0.5f * h) * sh;
+  o[4] = (cx + 0.5f * w) * sw;
+  o[5] = (cy + 0.5f * h) * sh;
+}
 template <bool REG, bool POST = false>
 __global__ __launch_bounds__(1024) void k_topk(const float* __restrict__ keys, int N, int K, int32_t* __restrict__ idx_out,
                                                 float* __restrict__ val_out, const TopkPost pa) {
   static_assert(!POST || REG, "the fused post-processor keeps its keys in registers");
   auto emit = [&](unsigned r, unsigned long long e) {            // rank r of this image: composite (key << 32 | ~index)
-    const int idx = (int)(0xffffffffu - (unsigned)(e & 0xffffffffu));
+    const int idx = topk_entry_index(e);
     const float val = key2f((unsigned)(e >> 32));
     if (POST) {
-      const int bimg = blockIdx.x;
-      const int label = idx % pa.C;
-      int q = idx / pa.C;
-      q = min(max(q, 0), pa.Q - 1);
-      const float* rr = pa.ref8 + ((int64_t)bimg * pa.Q + q) * 8;
-      const float cx = rr[0], cy = rr[1], w = rr[2], h = rr[3];
-      const float sw = pa.scale_wh[bimg * 2 + 0], sh = pa.scale_wh[bimg * 2 + 1];
-      float* o = pa.block6 + ((int64_t)bimg * K + r) * 6;
-      o[0] = (float)label;
-      o[1] = val;
-      o[2] = (cx - 0.5f * w) * sw;
-      o[3] = (cy - 0.5f * h) * sh;
-      o[4] = (cx + 0.5f * w) * sw;
-      o[5] = (cy + 0.5f * h) * sh;
+      write_detection_row(idx, val, blockIdx.x, pa.C, pa.Q, pa.ref8, pa.scale_wh, pa.block6 + ((int64_t)blockIdx.x * K + r) * 6);
     } else {
       idx_out[(int64_t)blockIdx.x * K + r] = idx;
       if (val_out) val_out[(int64_t)blockIdx.x * K + r] = val;
@@ -777,7 +784,7 @@ __global__ __launch_bounds__(1024) void k_topk(const float* __restrict__ keys, i
         if (lane_ == (int)__builtin_ctzll(bal)) base = atomicAdd(&s_cnt_gt, (unsigned)__popcll(bal));
         base = __shfl(base, (int)__builtin_ctzll(bal), 64);
         const unsigned pos = base + (unsigned)__popcll(bal & ((1ull << lane_) - 1ull));
-        if (take && pos < 1024) sel[pos] = ((unsigned long long)k << 32) | (unsigned)(0xffffffffu - (unsigned)i);
+        if (take && pos < 1024) sel[pos] = topk_entry(k, i);
       }
     };
     if (REG) {
@@ -871,7 +878,7 @@ __global__ __launch_bounds__(1024) void k_topk(const float* __restrict__ keys, i
       const int i = tid + j * 1024;
       if (j < npt && i < N && kreg[j] > T) {
         const unsigned pos = atomicAdd(&s_cnt_gt, 1u);
-        if (pos < 1024) sel[pos] = ((unsigned long long)kreg[j] << 32) | (unsigned)(0xffffffffu - (unsigned)i);
+        if (pos < 1024) sel[pos] = topk_entry(kreg[j], i);
       }
     }
   } else {
@@ -879,7 +886,7 @@ __global__ __launch_bounds__(1024) void k_topk(const float* __restrict__ keys, i
       const unsigned k = f2key(kb[i]);
       if (k > T) {
         const unsigned pos = atomicAdd(&s_cnt_gt, 1u);
-        if (pos < 1024) sel[pos] = ((unsigned long long)k << 32) | (unsigned)(0xffffffffu - (unsigned)i);
+        if (pos < 1024) sel[pos] = topk_entry(k, i);
       }
     }
   }
@@ -894,14 +901,14 @@ __global__ __launch_bounds__(1024) void k_topk(const float* __restrict__ keys, i
         const int i = tid + j * 1024;
         if (j < npt && i < N && kreg[j] == T) {
           const unsigned pos = n_gt + atomicAdd(&s_cnt_eq, 1u);
-          if (pos < 1024) sel[pos] = ((unsigned long long)T << 32) | (unsigned)(0xffffffffu - (unsigned)i);
+          if (pos < 1024) sel[pos] = topk_entry(T, i);
         }
       }
     } else {
       for (int i = tid; i < N; i += 1024) {
         if (f2key(kb[i]) == T) {
           const unsigned pos = n_gt + atomicAdd(&s_cnt_eq, 1u);
-          if (pos < 1024) sel[pos] = ((unsigned long long)T << 32) | (unsigned)(0xffffffffu - (unsigned)i);
+          if (pos < 1024) sel[pos] = topk_entry(T, i);
         }
       }
     }
@@ -926,7 +933,7 @@ __global__ __launch_bounds__(1024) void k_topk(const float* __restrict__ keys, i
     for (int w = 0; w < wv; ++w) before += wave_cnt[w];
     const unsigned my = before + (unsigned)__popcll(bal & ((1ull << lane) - 1ull));
     if (eq && my < need_eq && n_gt + my < 1024)
-      sel[n_gt + my] = ((unsigned long long)T << 32) | (unsigned)(0xffffffffu - (unsigned)i);
+      sel[n_gt + my] = topk_entry(T, i);
     __syncthreads();
     if (tid == 0) {
       unsigned tot = 0;
@@ -964,14 +971,16 @@ void launch_topk(const float* keys, int B, int N, int K, int32_t* idx, float* va
   else rtd_launch((k_topk<false, false>), dim3(B), dim3(1024), 0, s, keys, N, K, idx, vals, none);
   HIP_CHECK(hipGetLastError());
 }
-// the post-processor in one launch (TopkPost); false when the shape needs the three-launch form (dense logits rows, Q * C keys in registers)
-bool launch_postprocess_fused(const Tensor& logits, const float* ref8, const float* scale_wh, int B, int Q, float* block6, hipStream_t s) {
+// the shapes the post-processor takes in one launch (TopkPost): dense fp32 logits rows, Q * C keys in registers, one block of 1024 per image
+bool postprocess_fused_supported(const Tensor& logits, int B, int Q) {
   const int C = logits.c;
-  if (logits.dt != F32 || logits.ld != C || (int64_t)Q * C > 32768 || Q > 1024 || logits.pixels() != (int64_t)B * Q) return false;
-  const TopkPost pa = {ref8, scale_wh, block6, C, Q};
-  rtd_launch((k_topk<true, true>), dim3(B), dim3(1024), 0, s, (const float*)logits.p, Q * C, Q, (int32_t*)nullptr, (float*)nullptr, pa);
+  return logits.dt == F32 && logits.ld == C && (int64_t)Q * C <= 32768 && Q <= 1024 && logits.pixels() == (int64_t)B * Q;
+}
+void launch_postprocess_fused(const Tensor& logits, const float* ref8, const float* scale_wh, int B, int Q, float* block6, hipStream_t s) {
+  RTD_CHECK(postprocess_fused_supported(logits, B, Q), 1, "postprocess: the one-launch form does not take this shape");
+  const TopkPost pa = {ref8, scale_wh, block6, logits.c, Q};
+  rtd_launch((k_topk<true, true>), dim3(B), dim3(1024), 0, s, (const float*)logits.p, Q * logits.c, Q, (int32_t*)nullptr, (float*)nullptr, pa);
   HIP_CHECK(hipGetLastError());
-  return true;
 }
 
 // ------------------------------------------------------------------------------------------ gather rows
@@ -1132,21 +1141,7 @@ __global__ void k_pp_gather(const float* __restrict__ topv, const int32_t* __res
                             const float* __restrict__ scale_wh, int Q, int C, float* __restrict__ block6, int64_t total) {
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= total) return;
-  const int b = (int)(t / Q);
-  const int idx = topi[t];
-  const int label = idx % C;
-  int q = idx / C;
-  q = min(max(q, 0), Q - 1);
-  const float* r = ref8 + ((int64_t)b * Q + q) * 8;
-  const float cx = r[0], cy = r[1], w = r[2], h = r[3];
-  const float sw = scale_wh[b * 2 + 0], sh = scale_wh[b * 2 + 1];
-  float* o = block6 + t * 6;
-  o[0] = (float)label;
-  o[1] = topv[t];
-  o[2] = (cx - 0.5f * w) * sw;
-  o[3] = (cy - 0.5f * h) * sh;
-  o[4] = (cx + 0.5f * w) * sw;
-  o[5] = (cy + 0.5f * h) * sh;
+  write_detection_row(topi[t], topv[t], (int)(t / Q), C, Q, ref8, scale_wh, block6 + t * 6);
 }
 void launch_postprocess_gather(const float* topv, const int32_t* topi, const float* ref8, const float* scale_wh, int B, int Q,
                                int C, float* block6, hipStream_t s) {

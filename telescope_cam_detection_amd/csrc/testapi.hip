@@ -656,7 +656,8 @@ int rtd_op_postprocess(const float* logits, const float* ref8, const float* scal
     RTD_CHECK(K == Q, RTD_E_INVALID, "postprocess: one output row per query (K == Q)");
     const Tensor lg = mk(logits, F32, B, Q, 1, C);
     if (fused) {
-      RTD_CHECK(launch_postprocess_fused(lg, ref8, scale_wh, B, Q, block6, nullptr), RTD_E_INVALID, "postprocess: the one-launch form does not take this shape");
+      RTD_CHECK(postprocess_fused_supported(lg, B, Q), RTD_E_INVALID, "postprocess: the one-launch form does not take this shape");
+      launch_postprocess_fused(lg, ref8, scale_wh, B, Q, block6, nullptr);
       return;
     }
     RTD_CHECK(K <= 1024, RTD_E_INVALID, "postprocess: K <= 1024");

@@ -14,7 +14,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.util import within
+from tests.util import plateau_keys, topk_path, within
 
 pytestmark = pytest.mark.gpu
 
@@ -366,7 +366,12 @@ def test_box_refine_six_layers_against_fp64(L):
 POST_CASES = [(2, 50, 80, 50, "spread"), (1, 300, 80, 300, "spread"), (2, 300, 91, 300, "spread"),
               (1, 300, 110, 300, "spread"),     # Q * C > 32768: the one-launch form must decline
               (1, 7, 3, 7, "spread"),
-              (2, 300, 80, 300, "eighths")]     # logits quantised to 1/8: many sigmoid ties, some across the cut
+              (2, 300, 80, 300, "eighths"),     # logits quantised to 1/8: many sigmoid ties, some across the cut
+              # the cases above stay on k_topk's fast path (at most 1024 candidates); these leave it in the one-launch form too:
+              (2, 300, 80, 300, "flat"),        # one score everywhere: 24 000 candidates, the tie group walked in index order
+              (2, 300, 80, 300, "plateau"),     # a tie group of 200 at the cut, wholly taken
+              (1, 16, 80, 16, "flat")]          # 1 280 candidates: the smallest shape that leaves the fast path
+POST_PATHS = {"flat": "general/in-order", "plateau": "general/all-ties"}          # tests.util.topk_path; every other kind: "fast"
 
 
 @pytest.mark.parametrize("case", POST_CASES)
@@ -375,10 +380,15 @@ def test_postprocess_fused_and_three_launch_forms(L, case):
     index % C, query = index // C, cxcywh -> xyxy * (w, h, w, h): the one-launch POST form of k_topk == k_pp_scores + k_topk + k_pp_gather
     bit for bit; labels and queries exact and scores / boxes to the tolerance rule against torch in fp64.  sigmoid is monotone, so the
     expected order is that of the logits themselves: "spread" logits are a shuffled even grid over [-9, 5] (neighbouring scores differ by
-    far more than an fp32 rounding, so the order does not depend on how a sigmoid rounds), "eighths" are random multiples of 1/8."""
+    far more than an fp32 rounding, so the order does not depend on how a sigmoid rounds), "eighths" are random multiples of 1/8, "flat" is
+    -1.25 everywhere and "plateau" is tests.util.plateau_keys - 3 (logits -2, with 100 at 0 and 200 at -1)."""
     B, Q, C_, K, kind = case
     g_ = torch.Generator().manual_seed(2100 + POST_CASES.index(case))
-    if kind == "eighths":
+    if kind == "flat":
+        logits = torch.full((B, Q, C_), -1.25)
+    elif kind == "plateau":
+        logits = (plateau_keys(B, Q * C_, K) - 3.0).view(B, Q, C_)
+    elif kind == "eighths":
         logits = torch.round((torch.randn(B, Q, C_, generator=g_) * 2.0 - 3.0) * 8) / 8
     else:
         logits = torch.stack([torch.linspace(-9.0, 5.0, Q * C_)[torch.randperm(Q * C_, generator=g_)] for _ in range(B)]).view(B, Q, C_)
@@ -402,6 +412,8 @@ def test_postprocess_fused_and_three_launch_forms(L, case):
     flat = logits.reshape(B, Q * C_)
     order = np.stack([np.lexsort((np.arange(Q * C_), -flat[b].double().numpy()))[:K] for b in range(B)])     # (logit desc, index asc)
     order = torch.from_numpy(order)
+    for b in range(B):      # sigmoid is strictly increasing over these logits: the kernel's keys order and tie as the logits do
+        assert topk_path(flat[b].numpy(), K) == POST_PATHS.get(kind, "fast"), ("test data: the path this case is here for", case, b)
     if kind == "eighths":
         kth = torch.gather(flat, 1, order[:, K - 1:K])
         assert ((flat == kth).sum(1) > 1).all(), "test data: a tie group at the cut"

@@ -7,7 +7,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.util import FACTOR, ulp32, within
+from tests.util import FACTOR, plateau_keys, topk_path, ulp32, within
 
 pytestmark = pytest.mark.gpu
 
@@ -723,15 +723,39 @@ def test_topk_exact(L, case):
         assert (idx[b][1:][same_val & (val[b][1:] != 0)] > idx[b][:-1][same_val & (val[b][1:] != 0)]).all(), "ties: lowest index first"
 
 
-@pytest.mark.parametrize("kind", ["distinct", "sigmoid", "all_equal", "two_values", "ties_at_cut", "short"])
-@pytest.mark.parametrize("N,K", [(8400, 300), (24000, 300), (33600, 300), (1500, 1024), (300, 300)])
+TOPK_KINDS = ["distinct", "sigmoid", "all_equal", "two_values", "ties_at_cut", "short"]
+TOPK_PATH_CASES = [(kind, N, K) for kind in TOPK_KINDS for N, K in [(8400, 300), (24000, 300), (33600, 300), (1500, 1024), (300, 300)]]
+# "plateau": the general path's "tie group wholly taken" branch with a group of 200 (683) keys - 1025: the second register slot holds one
+# key; 32768: all 32 slots full, the last size with the keys in registers; 32769: the first size that re-reads them; K = 1024 there: the
+# 1024-slot sort.  distinct / all_equal at both sizes: the same two branches with 6 000 - 8 000 candidates and with every key tied
+TOPK_PATH_CASES += [("plateau", N, K) for N, K in [(1025, 300), (4096, 300), (32768, 300), (32769, 300), (32769, 1024)]]
+TOPK_PATH_CASES += [(kind, N, 1024) for kind in ("distinct", "all_equal") for N in (32769, 32768)]
+
+
+def expected_topk_path(kind, N, K):
+    """the way k_topk goes (tests.util.topk_path) for every image of a case, computed on the CPU when the case was chosen"""
+    if kind == "plateau":
+        return "general/all-ties"
+    if (N, K) == (300, 300):
+        return "fast"                                                                  # 300 candidates
+    if kind in ("all_equal", "two_values"):
+        return "general/in-order"
+    if K == 1024:
+        return "general/all-ties" if kind in ("distinct", "sigmoid") else "general/in-order"
+    return "fast"
+
+
+@pytest.mark.parametrize("kind,N,K", [pytest.param(kind, N, K, id=f"{N}-{K}-{kind}") for kind, N, K in TOPK_PATH_CASES])
 def test_topk_fast_and_general_paths(L, kind, N, K):
     """k_topk (round 5) bounds the candidates by the K-th largest per-thread maximum and ranks them by counting; more than 1024 candidates
     (heavy ties) take the general radix path.  Both must return torch.topk's values with the documented tie rule (lowest index first):
-    distinct keys and score-like keys (fast path), one or two distinct values (general path), a tie group that straddles the cut."""
+    distinct keys and score-like keys (fast path), one or two distinct values (general path), a tie group that straddles the cut, a
+    tie group at the cut that is wholly taken.  Every case asserts the path it was chosen for."""
     B = 3
     g = torch.Generator().manual_seed(N * 7 + K + len(kind))
-    if kind == "distinct":
+    if kind == "plateau":
+        keys = plateau_keys(B, N, K)
+    elif kind == "distinct":
         keys = torch.randperm(B * N, generator=g).float().view(B, N) * 0.25 - 1000.0
     elif kind == "sigmoid":
         keys = torch.sigmoid(torch.randn(B, N, generator=g) * 2.0 - 3.0)
@@ -746,6 +770,8 @@ def test_topk_fast_and_general_paths(L, kind, N, K):
     else:
         keys = torch.randn(B, N, generator=g)
         keys[:, N // 2:] = -float("inf")                                              # most threads hold only -inf
+    for b in range(B):
+        assert topk_path(keys[b].numpy(), K) == expected_topk_path(kind, N, K), ("test data: the path this case is here for", kind, N, K, b)
     idx = torch.empty(B, K, dtype=torch.int32, device="cuda")
     val = torch.empty(B, K, dtype=torch.float32, device="cuda")
     kd = keys.cuda()

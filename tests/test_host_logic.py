@@ -135,6 +135,7 @@ def test_decoder_op_entry_points_refuse_bad_shapes_before_any_device_work():
     refused(lib.rtd_op_msdeform_view(_capi.DT_F32, p, 256, 256, p, p, p, 1, 4, 8, 32, 3, 4, lv, 0.5), "leaves the value row")
     refused(lib.rtd_op_msdeform_view(_capi.DT_F32, p, 768, 0, p, p, p, 1, 4, 8, 16, 3, 4, lv, 0.5), "head dim must be 32")      # hd != 32
     refused(lib.rtd_op_postprocess(p, p, p, 1, 300, 80, 100, 1, p), "K == Q")
+    refused(lib.rtd_op_postprocess(p, p, p, 1, 300, 110, 300, 1, p), "one-launch form does not take this shape")   # Q * C > 32768 keys
 
 
 @pytest.mark.skipif(torch.cuda.is_available(), reason="CPU-only behaviour")

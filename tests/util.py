@@ -76,6 +76,35 @@ def match_detections(ref_labels, ref_boxes, ref_scores, labels, boxes, scores, s
     return matched, len(ref_labels), ws, wb
 
 
+# ---- which way k_topk goes for one image (csrc/ops.hip), restated on the CPU ----
+def topk_path(keys_1d, K):
+    """"fast", "general/all-ties" or "general/in-order" for one image's fp32 keys: the kernel orders keys as sign-flipped uint32, throws
+    them into 1024 bags by a hash of their index, and takes the fast path when at most 1024 keys reach L, the K-th largest bag maximum
+    (empty bags count as 0).  Otherwise, with T the K-th largest key, the tie group at T is either wholly taken or walked in index order."""
+    u = np.ascontiguousarray(np.asarray(keys_1d, dtype=np.float32)).view(np.uint32)
+    key = np.where(u & np.uint32(0x80000000), ~u, u | np.uint32(0x80000000)).astype(np.uint32)
+    bag = ((np.arange(key.size, dtype=np.uint64) * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)) >> np.uint64(22)
+    maxima = np.zeros(1024, np.uint32)
+    np.maximum.at(maxima, bag.astype(np.int64), key)
+    L = np.sort(maxima)[::-1][K - 1]
+    if int((key >= L).sum()) <= 1024:
+        return "fast"
+    T = np.sort(key)[::-1][K - 1]
+    return "general/all-ties" if int((key == T).sum()) == K - int((key > T).sum()) else "general/in-order"
+
+
+def plateau_keys(B, N, K):
+    """[B, N] keys that are all 1.0 but for K // 3 at 3.0 and K - K // 3 at 2.0 in random places: the special keys collide in bags, so the
+    bag bound falls to 1.0 and every key is a candidate; the K-th largest is 2.0 and its whole tie group is taken ("general/all-ties")"""
+    g = torch.Generator().manual_seed(N * 7 + K)
+    keys = torch.ones(B, N)
+    for b in range(B):
+        perm = torch.randperm(N, generator=g)
+        keys[b, perm[:K // 3]] = 3.0
+        keys[b, perm[K // 3:K]] = 2.0
+    return keys
+
+
 # ---- the tolerance rule of the kernel-level fp64 comparisons (tests/test_gpu_decoder_ops.py) ----
 FACTOR = 4.0
 
