@@ -1,6 +1,6 @@
 // backend.h - the host-side scaffold of all seven handles (seven handles, one scaffold): the detector engine (engine_internal.h) and the
 // stand-alone back ends (motion, mog2, jpeg, overlay, enhance, esrgan).  What a handle holds, how a C entry point turns exceptions into a
-// return code and a message, how a handle is created, and the buffers it grows on demand.
+// return code and a message, how a handle is created, the buffers it grows on demand, and the scratch of one call (OpScratch).
 // A back end writes its kernels, its argument checks and its extern "C" functions; nothing here generates an entry point.  Host only.
 #pragma once
 #include <algorithm>
@@ -130,6 +130,53 @@ struct GrowBuf {
 };
 using DevBuf = GrowBuf<false>;
 using PinBuf = GrowBuf<true>;
+
+// device buffers, events and streams of ONE call (the kernel-level test / bench / debug entry points, the staging of a filter upload):
+// released when the call ends, on every path - a throwing RTD_CHECK / HIP_CHECK included.  The buffers go first: hipFree waits for the
+// device, so nothing enqueued still uses what is released.
+struct OpScratch {
+  std::vector<void*> bufs;
+  std::vector<hipEvent_t> events;
+  std::vector<hipStream_t> streams;
+  OpScratch() = default;
+  OpScratch(const OpScratch&) = delete;
+  OpScratch& operator=(const OpScratch&) = delete;
+  template <typename T> T* get(size_t count) {
+    void* p = nullptr;
+    HIP_CHECK(hipMalloc(&p, count ? count * sizeof(T) : 16));
+    bufs.push_back(p);
+    return (T*)p;
+  }
+  template <typename T> T* zeros(size_t count) {
+    T* d = get<T>(count);
+    HIP_CHECK(hipMemset(d, 0, count * sizeof(T)));
+    return d;
+  }
+  template <typename T> T* upload(const T* host, size_t count) {
+    T* d = get<T>(count);
+    HIP_CHECK(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
+    return d;
+  }
+  hipEvent_t event() {
+    hipEvent_t e = nullptr;
+    HIP_CHECK(hipEventCreate(&e));
+    events.push_back(e);
+    return e;
+  }
+  hipStream_t stream() {   // non-blocking
+    hipStream_t s = nullptr;
+    HIP_CHECK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+    streams.push_back(s);
+    return s;
+  }
+  void release() {
+    for (void* p : bufs) (void)hipFree(p);
+    for (hipEvent_t e : events) (void)hipEventDestroy(e);
+    for (hipStream_t s : streams) (void)hipStreamDestroy(s);
+    bufs.clear(); events.clear(); streams.clear();
+  }
+  ~OpScratch() { release(); }
+};
 
 // frames that arrive from the host are staged one after the other from `at`, each on a 256-byte boundary: foff[i] is frame i's offset,
 // the return value the end of the last one.  hwc = [n][3] rows, cols, channels.  Device-resident frames take no room.

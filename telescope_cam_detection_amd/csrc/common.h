@@ -197,9 +197,9 @@ struct ConvArgs {
   size_t pf_bytes = 0;
 };
 void launch_conv(const ConvArgs& a, hipStream_t s);
-int conv_kpad(int K);                 // padded filter row length the kernels expect
-int conv_kpad_split(int K);           // F16X2 filter row length in bf16 elements (K real taps x channels)
-int conv_npad(int N);
+inline int conv_kpad(int K) { return (K + 63) / 64 * 64; }        // padded filter row length the kernels expect
+inline int conv_kpad_split(int K) { return 2 * ((K + SPLIT_GROUP - 1) / SPLIT_GROUP * SPLIT_GROUP); }   // F16X2 filter row length in 16-bit elements
+inline int conv_npad(int N) { return (N + 127) / 128 * 128; }
 // What the plan builder asks before it relies on a fusion (shape-only probes: the answers read extents, dtypes, alignment and the options)
 bool conv_dual_supported(const ConvArgs& a);    // can this build's kernels run `a` with its second input (ConvArgs::x2)?
 bool conv_next_supported(const ConvArgs& a);    // can `a` (shapes for ONE image) carry a fused following 1x1 conv (ConvArgs::next_*)?
@@ -351,6 +351,52 @@ void launch_to_f32(const void* src, int dt, float* dst, int64_t n, hipStream_t s
 void launch_f32_to_split(const float* src, int64_t lds, void* dst, int64_t ldd, int64_t rows, int C, hipStream_t s);
 void launch_split_to_f32(const void* src, int64_t lds, float* dst, int64_t ldd, int64_t rows, int C, hipStream_t s);
 void launch_count_saturated(const void* split_buf, int64_t n16, unsigned long long* count_dev, hipStream_t s);
+
+// ---- a conv's filter as launch_conv wants it: fp32 filter rows [N][K] -> [Npad][Kpad] in dt on the device, zero padded, bias fp32 [Npad].
+// Every back end that feeds launch_conv (the detector engine, the ESRGAN upscaler, the kernel-level test API) pads, converts and fills
+// its ConvArgs through the four functions below; who owns the device memory and who waits for the conversion stays with the caller.
+struct ConvFilter {
+  void* w = nullptr;
+  float* bias = nullptr;
+  int N = 0, K = 0, Kpad = 0, Npad = 0, dt = F32;
+  bool converts() const { return dt == BF16 || dt == F16X2; }     // otherwise the fp32 rows are the filter
+  int kcols() const { return dt == F16X2 ? Kpad / 2 : Kpad; }     // columns of an fp32 row (F16X2: a column becomes a hi and a lo half)
+  size_t bytes() const { return (size_t)Npad * Kpad * (converts() ? 2 : 4); }
+};
+// the padded extents for (dt, N, K); nothing on the device (host only: no HIP call)
+inline ConvFilter conv_filter_extents(int dt, int N, int K) {
+  ConvFilter f;
+  f.N = N; f.K = K; f.dt = dt;
+  f.Kpad = dt == F16X2 ? conv_kpad_split(K) : conv_kpad(K);
+  f.Npad = conv_npad(N);
+  return f;
+}
+// host: filters over the same N output channels, segs = {[N][K_i] fp32, K_i}, side by side along K -> the zero-padded fp32 rows
+// [Npad][kcols] of f (K = the sum of K_i)
+inline std::vector<float> conv_filter_rows(const ConvFilter& f, const std::vector<std::pair<const float*, int>>& segs) {
+  const int kcols = f.kcols();
+  std::vector<float> rows((size_t)f.Npad * kcols, 0.f);
+  int k0 = 0;
+  for (const auto& s : segs) {
+    for (int r = 0; r < f.N; ++r) memcpy(&rows[(size_t)r * kcols + k0], s.first + (size_t)r * s.second, (size_t)s.second * 4);
+    k0 += s.second;
+  }
+  return rows;
+}
+// zero-padded fp32 rows [Npad][kcols] on the device -> f.w in f.dt: bf16 rounded, F16X2 as [32 hi | 32 lo] groups along K (the layout
+// of an activation pixel with kcols channels); an fp32 filter IS its rows (nothing to do).  Enqueues only: no allocation, no wait.
+inline void conv_filter_convert(const ConvFilter& f, const float* rows, hipStream_t s) {
+  if (f.dt == BF16) launch_f32_to(rows, f.w, BF16, (int64_t)f.Npad * f.Kpad, s);
+  else if (f.dt == F16X2) launch_f32_to_split(rows, f.kcols(), f.w, f.kcols(), f.Npad, f.kcols(), s);
+}
+// the launch of a k x k conv x -> y with filter f; the caller adds what is special to it (residual, x2, next_*, avg_y, opts, ws)
+inline ConvArgs conv_args(const Tensor& x, const Tensor& y, const ConvFilter& f, int k, int stride, int pad, int act) {
+  ConvArgs a;
+  a.x = x; a.y = y;
+  a.w = f.w; a.bias = f.bias; a.Kpad = f.Kpad; a.Npad = f.Npad;
+  a.KH = a.KW = k; a.stride = stride; a.pad = pad; a.act = act;
+  return a;
+}
 
 #if defined(__HIPCC__)
 // ---- F16X2 helpers: element offset (in bf16 units, from the tensor base) of the hi half of channel c of a pixel whose first

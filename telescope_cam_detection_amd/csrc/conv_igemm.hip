@@ -1944,10 +1944,6 @@ __global__ __launch_bounds__(256) void k_splitk_reduce(const ConvK a, const floa
 // ================================================================================================
 // Host side ("Conv dispatch"): geometry -> checks -> ConvK -> a pure choice of the kernel -> its launch.
 // ================================================================================================
-int conv_kpad(int K) { return (K + 63) / 64 * 64; }
-int conv_npad(int N) { return (N + 127) / 128 * 128; }
-int conv_kpad_split(int K) { return 2 * ((K + SPLIT_GROUP - 1) / SPLIT_GROUP * SPLIT_GROUP); }   // 16-bit elements of a filter row
-
 static ConvOpts g_conv_opts;
 ConvOpts& conv_opts_template() { return g_conv_opts; }
 bool conv_set_option(const char* name, int value) {

@@ -97,37 +97,15 @@ void* upload(rtd_engine* e, const void* host, size_t bytes) {
   return d;
 }
 
-// host [Npad][Kcols] fp32 (zero padded) -> device filter in dt: fp32 as is, bf16 rounded, F16X2 as [32 hi | 32 lo] groups along K
-// (Kcols % 32 == 0: a row has 2 * Kcols bf16 elements, the layout of an activation pixel with Kcols channels)
 static const char* dt_tag(int dt) { return dt == BF16 ? "#bf16" : (dt == F16X2 ? "#f16x2" : "#f32"); }
-static void* upload_filter(rtd_engine* e, const std::vector<float>& pad, int Npad, int Kcols, int dt) {
-  float* tmp = nullptr;
-  void* out = nullptr;
-  HIP_CHECK(hipMalloc((void**)&tmp, pad.size() * 4));
-  hipError_t er = hipMemcpy(tmp, pad.data(), pad.size() * 4, hipMemcpyHostToDevice);
-  try {
-    if (er == hipSuccess) {
-      if (dt == F32) {
-        out = tmp;
-        e->allocs.push_back(tmp);
-        tmp = nullptr;
-      } else if (dt == F16X2) {
-        out = e->dmalloc(pad.size() * 4);
-        launch_f32_to_split(tmp, Kcols, out, Kcols, Npad, Kcols, e->q.stream);
-        er = hipStreamSynchronize(e->q.stream);
-      } else {
-        out = e->dmalloc(pad.size() * 2);
-        launch_f32_to(tmp, out, BF16, (int64_t)pad.size(), e->q.stream);
-        er = hipStreamSynchronize(e->q.stream);
-      }
-    }
-  } catch (...) {
-    if (tmp) (void)hipFree(tmp);
-    throw;
-  }
-  if (tmp) (void)hipFree(tmp);
-  HIP_CHECK(er);
-  return out;
+// host rows [Npad][kcols] fp32 (zero padded) -> f.w, owned by the handle.  An fp32 filter keeps its rows; the staging of a converted one
+// goes when the conversion has run.
+static void upload_filter(rtd_engine* e, ConvFilter& f, const std::vector<float>& rows) {
+  backend::OpScratch staging;
+  float* dev = f.converts() ? staging.upload(rows.data(), rows.size()) : (float*)upload(e, rows.data(), rows.size() * 4);
+  f.w = f.converts() ? e->dmalloc(f.bytes()) : dev;
+  conv_filter_convert(f, dev, e->q.stream);
+  if (f.converts()) HIP_CHECK(hipStreamSynchronize(e->q.stream));
 }
 
 // one filter of a conv, or one of the two a conv reads side by side: blob tensors `name`.w [N][K] and `name`.b [N]
@@ -140,7 +118,7 @@ static const float* host_filter(rtd_engine* e, const std::string& name, int N, i
 }
 
 // tail of every filter upload: the segments' biases summed (one segment: its bias) -> fp32 [Npad] on the device, then the cache entry
-static DevWeight finish_weight(rtd_engine* e, const std::string& key, DevWeight d, const std::vector<FilterSeg>& segs) {
+static ConvFilter finish_weight(rtd_engine* e, const std::string& key, ConvFilter d, const std::vector<FilterSeg>& segs) {
   std::vector<float> bp(d.Npad, 0.f);
   for (size_t i = 0; i < segs.size(); ++i) {
     const HostTensor& b = host_tensor(e, segs[i].name + ".b");
@@ -155,25 +133,18 @@ static DevWeight finish_weight(rtd_engine* e, const std::string& key, DevWeight 
 // filter [N][K] fp32 -> device [Npad][Kpad] in dt (zero padded), bias -> fp32 [Npad].  Two segments: two filters over the same output
 // channels, concatenated along K: [N][K1 | K2], bias = b1 + b2 (a block's last conv with its projection shortcut folded in, ConvArgs::x2).
 // `extents_only` (the dry builder pass): the padded extents and nothing on the device.
-DevWeight get_weight(rtd_engine* e, const std::vector<FilterSeg>& segs, int dt, int N, bool extents_only = false) {
+ConvFilter get_weight(rtd_engine* e, const std::vector<FilterSeg>& segs, int dt, int N, bool extents_only = false) {
   std::string key = segs[0].name;
   int K = 0;
   for (size_t i = 0; i < segs.size(); ++i) { if (i) key += "+" + segs[i].name; K += segs[i].K; }
   key += dt_tag(dt);
-  DevWeight d;
-  d.N = N; d.K = K; d.Kpad = dt == F16X2 ? conv_kpad_split(K) : conv_kpad(K); d.Npad = conv_npad(N); d.dt = dt;
+  ConvFilter d = conv_filter_extents(dt, N, K);
   if (extents_only) return d;
   auto it = e->wcache.find(key);
   if (it != e->wcache.end()) return it->second;
-  const int kcols = dt == F16X2 ? d.Kpad / 2 : d.Kpad;
-  std::vector<float> pad((size_t)d.Npad * kcols, 0.f);
-  int k0 = 0;
-  for (const FilterSeg& s : segs) {
-    const float* w = host_filter(e, s.name, N, s.K);
-    for (int r = 0; r < N; ++r) memcpy(&pad[(size_t)r * kcols + k0], w + (size_t)r * s.K, (size_t)s.K * 4);
-    k0 += s.K;
-  }
-  d.w = upload_filter(e, pad, d.Npad, kcols, dt);
+  std::vector<std::pair<const float*, int>> rows;
+  for (const FilterSeg& s : segs) rows.push_back({host_filter(e, s.name, N, s.K), s.K});
+  upload_filter(e, d, conv_filter_rows(d, rows));
   return finish_weight(e, key, d, segs);
 }
 
@@ -230,13 +201,13 @@ static void* pack_fragments_f16x2(rtd_engine* e, const float* w, int N, int K, i
   return upload(e, ps.data(), ps.size() * 2);
 }
 
-DevWeight get_weight_packed(rtd_engine* e, const std::string& name, int N, int K, int Kuse, bool split = false) {
+ConvFilter get_weight_packed(rtd_engine* e, const std::string& name, int N, int K, int Kuse, bool split = false) {
   const std::string key = name + (split ? "#split" : "#packed");
   auto it = e->wcache.find(key);
   if (it != e->wcache.end()) return it->second;
   const float* w = host_filter(e, name, N, K);
   RTD_CHECK(Kuse % 64 == 0 && Kuse >= K, RTD_E_WEIGHTS, "K padding: " + name);
-  DevWeight d;
+  ConvFilter d;
   d.N = N; d.K = Kuse; d.Kpad = Kuse; d.dt = F32;
   const int ntiles = packed_ntiles(N);
   d.Npad = ntiles * 16;
@@ -427,22 +398,27 @@ struct Builder {
   void on_side(F&& body) { marker(1); lane = 1; body(); lane = 0; }
   static double tbytes(const Tensor& t) { return (double)t.pixels() * t.c * dtype_size(t.dt); }
 
+  // the launch of conv(.., x, y, s) with filter f, without a following conv's filter (conv() adds it)
+  ConvArgs args(const Tensor& x, const Tensor& y, const ConvSpec& s, const ConvFilter& f) const {
+    ConvArgs a = conv_args(x, y, f, s.k, s.stride, s.pad, s.act);
+    a.opts = &e->conv_opts;
+    if (s.x2) a.x2 = *s.x2;
+    a.x_up2 = s.x_up2;
+    if (s.res) { a.res = *s.res; a.res_mode = s.res_mode; }
+    if (s.next_y) a.next_y = *s.next_y;
+    a.avg_y = s.avg_y;
+    return a;
+  }
   // What the conv_*_supported() predicates look at for conv(.., x, y, s): shapes, alignment and which operands exist - so a fusion can be
   // asked about before its tensors are allocated.  ONE image unless `plan_batch`: every plan of an engine must use the same filters (the
   // host copies are dropped after the first plan) and the same arithmetic (batch invariance), and a single image has the smallest grid.
   static Tensor probe_shape(Tensor t, int n) { t.p = SHAPE_ONLY; t.n = n; return t; }
   ConvArgs probe(const Tensor& x, const Tensor& y, const ConvSpec& s, bool plan_batch = false) const {
-    const int pn = plan_batch ? n : 1;
-    ConvArgs a;
-    a.opts = &e->conv_opts;
-    a.w = SHAPE_ONLY; a.bias = nullptr;
-    a.x = probe_shape(x, pn); a.y = probe_shape(y, pn);
-    if (s.x2) a.x2 = probe_shape(*s.x2, pn);
-    if (s.res) { a.res = probe_shape(*s.res, pn); a.res_mode = s.res_mode; }
-    if (s.next_y) a.next_y = probe_shape(*s.next_y, pn);
-    if (s.avg_y.c) a.avg_y = probe_shape(s.avg_y, pn);
-    a.x_up2 = s.x_up2;
-    a.KH = a.KW = s.k; a.stride = s.stride; a.pad = s.pad; a.act = s.act;
+    ConvFilter shape_only;
+    shape_only.w = SHAPE_ONLY;
+    ConvArgs a = args(x, y, s, shape_only);
+    for (Tensor* t : {&a.x, &a.y, &a.x2, &a.res, &a.next_y, &a.avg_y})
+      if (t->c) *t = probe_shape(*t, plan_batch ? n : 1);
     return a;
   }
 
@@ -451,21 +427,13 @@ struct Builder {
     const int k = s.k, K = k * k * x.c + (s.x2 ? s.x2->c : 0);
     std::vector<FilterSeg> segs{{name, K}};
     if (s.x2 && !s.name2.empty()) segs = {{name, k * k * x.c}, {s.name2, s.x2->c}};
-    const DevWeight w = get_weight(e, segs, x.dt, y.c, dry);
-    ConvArgs a;
-    a.x = x; a.y = y; a.w = w.w; a.bias = w.bias;
-    if (s.x2) a.x2 = *s.x2;
-    a.x_up2 = s.x_up2;
-    a.KH = k; a.KW = k; a.stride = s.stride; a.pad = s.pad; a.Kpad = w.Kpad; a.Npad = w.Npad;
-    a.act = s.act; a.res_mode = s.res ? s.res_mode : RES_NONE;
-    if (s.res) a.res = *s.res;
+    const ConvFilter w = get_weight(e, segs, x.dt, y.c, dry);
+    ConvArgs a = args(x, y, s, w);
     if (s.next_y) {
-      const DevWeight wn = get_weight(e, {{s.next_name, y.c}}, x.dt, s.next_y->c, dry);
-      a.next_w = wn.w; a.next_bias = wn.bias; a.next_y = *s.next_y; a.next_kpad = wn.Kpad; a.next_act = s.next_act;
+      const ConvFilter wn = get_weight(e, {{s.next_name, y.c}}, x.dt, s.next_y->c, dry);
+      a.next_w = wn.w; a.next_bias = wn.bias; a.next_kpad = wn.Kpad; a.next_act = s.next_act;
     }
-    a.opts = &e->conv_opts;
     a.prefer256 = e->cfg.profile == RTD_PROFILE_THROUGHPUT;
-    a.avg_y = s.avg_y;
     a.y_dead = (s.y_dead && a.avg_y.c && s.next_y) ? 1 : 0;
     slab_need[lane] = std::max(slab_need[lane], conv_split_slab_bytes(a));
     const double M = (double)y.pixels();
@@ -477,7 +445,7 @@ struct Builder {
     auto ap = std::make_shared<ConvArgs>(a);
     if (!dry) {
       // chain: the previous conv launch of the plan prefetches THIS filter while it runs (ConvArgs::pf)
-      if (last_conv) { last_conv->pf = w.w; last_conv->pf_bytes = (size_t)w.Npad * w.Kpad * (x.dt == F32 ? 4 : 2); }
+      if (last_conv) { last_conv->pf = w.w; last_conv->pf_bytes = w.bytes(); }
       last_conv = ap;
       convs.push_back({ap, lane});
     }
@@ -520,7 +488,7 @@ struct Builder {
   DecLin dec_lin(const std::string& name, int N, int K, int Kuse, bool split) {
     DecLin L{};
     if (dry) return L;
-    const DevWeight w = get_weight_packed(e, name, N, K, Kuse ? Kuse : K, split);
+    const ConvFilter w = get_weight_packed(e, name, N, K, Kuse ? Kuse : K, split);
     L.w = (const float*)w.w; L.b = w.bias; L.ldw = w.Kpad; L.N = N; L.K = w.K;
     return L;
   }
@@ -579,7 +547,7 @@ void Builder::stem(Flow& F) {
     const uint8_t** table = (const uint8_t**)alloc((size_t)c.max_batch * sizeof(void*));
     plan->frame_table = table;
     if (!dry) {
-      DevWeight w0 = get_weight(e, {{"backbone.stem.0", 9 * 8}}, P, eh);
+      ConvFilter w0 = get_weight(e, {{"backbone.stem.0", 9 * 8}}, P, eh);
       const void* wp = w0.w; const float* bp = w0.bias; const int kp = w0.Kpad; const int n = this->n;
       push("backbone.stem.0", "conv_igemm", 2.0 * n * h * w * eh * 27.0, (double)n * H * W * 3 + tbytes(s0),
            [table, n, H, W, wp, kp, bp, s0](hipStream_t st) { launch_stem0_u8(table, n, H, W, wp, kp, bp, s0, ACT_RELU, st); });
@@ -602,11 +570,7 @@ void Builder::stem(Flow& F) {
   F.h = ph; F.w = pw;
   if (fuse) {
     F.cur = act(P, n, ph, pw, c.embedding_size, "stem");
-    ConvArgs a;
-    a.x = s1; a.y = s2v;
-    a.KH = a.KW = 3; a.stride = 1; a.pad = 1; a.act = ACT_RELU; a.opts = &e->conv_opts;
-    const DevWeight w2 = get_weight(e, {{"backbone.stem.2", 9 * s1.c}}, P, c.embedding_size, dry);
-    a.w = w2.w; a.bias = w2.bias; a.Kpad = w2.Kpad; a.Npad = w2.Npad;
+    const ConvArgs a = args(s1, s2v, stem2, get_weight(e, {{"backbone.stem.2", 9 * s1.c}}, P, c.embedding_size, dry));
     void* side = alloc(conv_pool_side_bytes(a));
     const Tensor curv = F.cur;
     push("backbone.stem.2+pool", "conv_igemm", 2.0 * s2v.pixels() * s2v.c * 9.0 * s1.c, tbytes(s1) + tbytes(curv),

@@ -56,12 +56,6 @@ struct HostTensor {
   }
 };
 
-struct DevWeight {
-  void* w = nullptr;
-  float* bias = nullptr;
-  int N = 0, K = 0, Kpad = 0, Npad = 0, dt = F32;
-};
-
 struct Op {
   std::string name;
   const char* kernel;
@@ -104,7 +98,7 @@ extern PlanOpts g_opts;
 struct rtd_engine : rtd::backend::Base {   // device = cfg.device
   typedef rtd::ConvOpts ConvOpts; typedef rtd::FrameArgs FrameArgs;
   static constexpr int BF16 = rtd::BF16;
-  typedef rtd_eng::PlanOpts PlanOpts; typedef rtd_eng::HostTensor HostTensor; typedef rtd_eng::DevWeight DevWeight;
+  typedef rtd_eng::PlanOpts PlanOpts; typedef rtd_eng::HostTensor HostTensor;
   typedef rtd_eng::Plan Plan; typedef rtd_eng::ResizeTables ResizeTables;
   rtd_config cfg;
   PlanOpts opts;           // snapshot of g_opts at rtd_create
@@ -124,7 +118,7 @@ struct rtd_engine : rtd::backend::Base {   // device = cfg.device
   int P = BF16;  // storage / MFMA type of the conv trunk
   std::vector<char> blob;
   std::map<std::string, HostTensor> host;
-  std::map<std::string, DevWeight> wcache;
+  std::map<std::string, rtd::ConvFilter> wcache;
   std::map<std::string, float*> vcache;
   std::vector<void*> allocs;
   std::map<int, std::unique_ptr<Plan>> plans;

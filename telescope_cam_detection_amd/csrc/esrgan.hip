@@ -87,12 +87,6 @@ __global__ void __launch_bounds__(256) esrgan_emit(EmitArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- plan
-struct DevW {
-  void* w = nullptr;
-  float* bias = nullptr;
-  int Kpad = 0, Npad = 0;
-};
-
 enum OpKind { OP_CONV, OP_UPSAMPLE, OP_AXPBY, OP_COPY };
 // tensors of an op hold their byte OFFSET inside the arena in `p`; run() adds the arena's base (the arena may be replaced by a larger one
 // between calls, the plans stay)
@@ -117,7 +111,7 @@ struct rtd_esrgan : rtd::backend::Base {
   rtd_esrgan_config cfg;
   int P = rtd::F16X2;
   std::vector<char> blob;
-  std::map<std::string, esrgan::DevW> weights;
+  std::map<std::string, rtd::ConvFilter> weights;
   std::vector<void*> allocs;
   std::map<std::pair<int, int>, std::unique_ptr<esrgan::Plan>> plans;
   rtd::backend::DevBuf arena;   // holds the largest plan seen (a repeated shape allocates nothing)
@@ -160,12 +154,11 @@ static std::unique_ptr<Plan> build_plan(rtd_esrgan* e, int h, int w) {
 
   size_t slab = 0;
   auto conv = [&](const std::string& name, const Tensor& x, const Tensor& y, int act, const Tensor* res, const std::string& stage) {
-    const DevW& dw = e->weights.at(name);
     Op op;
     op.kind = OP_CONV;
     ConvArgs& a = op.conv;
-    a.x = x; a.y = y; a.w = dw.w; a.bias = dw.bias; a.KH = a.KW = 3; a.stride = 1; a.pad = 1; a.Kpad = dw.Kpad; a.Npad = dw.Npad;
-    a.act = act; a.opts = &e->conv_opts;
+    a = conv_args(x, y, e->weights.at(name), 3, 1, 1, act);
+    a.opts = &e->conv_opts;
     if (res) { a.res = *res; a.res_mode = RES_PRE; }
     slab = std::max(slab, conv_split_slab_bytes(a));
     op.stage = stage; op.stage_t = y;
@@ -293,51 +286,46 @@ static void run(rtd_esrgan* e, int n, const uint8_t* const* frames, const int32_
   }
 }
 
-// Filters and biases through the upload path of the handle's precision: host fp32 rows [Npad][kcols] -> device, then fp32 as they are
-// or launch_f32_to_split (the conversion rtd_op_conv and the detection engine use).  Two pools (filters, biases) and, on the pair
-// engine, one staging pool that is freed when every conversion has run: three allocations and one wait for the whole network.
+// Filters and biases through the upload path of the handle's precision: host fp32 rows [Npad][kcols] -> device, then conv_filter_convert
+// (common.h: the conversion rtd_op_conv and the detection engine use).  Two pools (filters, biases) and, on the pair engine, one
+// staging pool that is freed when every conversion has run: three allocations and one wait for the whole network.
 static void upload_weights(rtd_esrgan* e, const std::map<std::string, eh::HostTensor>& host, const std::vector<eh::ConvDesc>& table) {
-  const bool pair = e->P == F16X2;
-  struct Item { DevW dw; int cin_pad, kcols; size_t w_off, b_off; float scale; };
+  struct Item { ConvFilter f; int cin_pad; size_t w_off, b_off; float scale; };
   std::vector<Item> items;
   size_t w_bytes = 0, b_bytes = 0;
   for (const eh::ConvDesc& d : table) {
     Item it;
     it.cin_pad = d.cin == 3 ? IN_C : d.cin;
-    const int n_out = d.cout == 3 ? LAST_C : d.cout, K = 9 * it.cin_pad;
-    it.dw.Kpad = pair ? conv_kpad_split(K) : conv_kpad(K);
-    it.dw.Npad = conv_npad(n_out);
-    it.kcols = pair ? it.dw.Kpad / 2 : it.dw.Kpad;
+    it.f = conv_filter_extents(e->P, d.cout == 3 ? LAST_C : d.cout, 9 * it.cin_pad);
     const bool conv5 = d.name.size() > 6 && d.name.compare(d.name.size() - 6, 6, ".conv5") == 0;
     it.scale = conv5 ? 0.2f : 1.f;                                // `x5 * 0.2 + x`: the 0.2 lives in conv5's filter and bias
     it.w_off = w_bytes, it.b_off = b_bytes;
-    w_bytes += (size_t)it.dw.Npad * it.kcols * 4;                 // (multiples of 512 bytes: every filter stays 256-byte aligned)
-    b_bytes += (size_t)it.dw.Npad * 4;
+    w_bytes += it.f.bytes();                                      // (= the bytes of its fp32 rows; multiples of 512: every filter stays 256-byte aligned)
+    b_bytes += (size_t)it.f.Npad * 4;
     items.push_back(it);
   }
   auto dmalloc = [&](size_t bytes) { void* q = nullptr; HIP_CHECK(hipMalloc(&q, bytes)); e->allocs.push_back(q); return (char*)q; };
   char* wpool = dmalloc(w_bytes);
   char* bpool = dmalloc(b_bytes);
-  char* stage = pair ? dmalloc(w_bytes) : wpool;
+  bk::OpScratch staging;
+  char* stage = e->P == F16X2 ? staging.get<char>(w_bytes) : wpool;
   for (size_t i = 0; i < table.size(); ++i) {
     const eh::ConvDesc& d = table[i];
-    Item& it = items[i];
-    const std::vector<float> rows = eh::filter_rows(host.at(d.name + ".weight"), d.cout, d.cin, it.cin_pad, it.dw.Npad, it.kcols, it.scale);
-    std::vector<float> bias(it.dw.Npad, 0.f);
+    ConvFilter& f = items[i].f;
+    const float scale = items[i].scale;
+    const std::vector<float> rows = eh::filter_rows(host.at(d.name + ".weight"), d.cout, d.cin, items[i].cin_pad, f.Npad, f.kcols(), scale);
+    std::vector<float> bias(f.Npad, 0.f);
     const eh::HostTensor& b = host.at(d.name + ".bias");
-    for (int o = 0; o < d.cout; ++o) bias[o] = b.data[o] * it.scale;
-    it.dw.bias = (float*)(bpool + it.b_off);
-    it.dw.w = wpool + it.w_off;
-    HIP_CHECK(hipMemcpy(it.dw.bias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(stage + it.w_off, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
-    if (pair) launch_f32_to_split((const float*)(stage + it.w_off), it.kcols, it.dw.w, it.kcols, it.dw.Npad, it.kcols, nullptr);
-    e->weights[d.name] = it.dw;
+    for (int o = 0; o < d.cout; ++o) bias[o] = b.data[o] * scale;
+    f.bias = (float*)(bpool + items[i].b_off);
+    f.w = wpool + items[i].w_off;
+    float* dev_rows = (float*)(stage + items[i].w_off);
+    HIP_CHECK(hipMemcpy(f.bias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(dev_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
+    conv_filter_convert(f, dev_rows, nullptr);
+    e->weights[d.name] = f;
   }
   HIP_CHECK(hipDeviceSynchronize());
-  if (pair) {
-    (void)hipFree(stage);
-    e->allocs.pop_back();
-  }
 }
 
 }  // namespace esrgan
@@ -415,20 +403,12 @@ int rtd_debug_esrgan_tensor(rtd_esrgan_handle e, const char* name, float* out, i
     run_ingest(e, p, e->last_src, e->last_pitch, s);
     for (size_t i = 0; i < upto; ++i) run_op(e, p, p->ops[i], s);
     t = based(t, (char*)e->arena.p);
-    float* f32 = nullptr;
-    HIP_CHECK(hipMalloc((void**)&f32, (size_t)numel * 4));
-    hipError_t er = hipSuccess;
-    try {
-      if (t.dt == F16X2) launch_split_to_f32(t.p, t.ld, f32, t.c, t.pixels(), t.c, s);
-      else er = hipMemcpy2DAsync(f32, (size_t)t.c * 4, t.p, (size_t)t.ld * 4, (size_t)t.c * 4, (size_t)t.pixels(), hipMemcpyDeviceToDevice, s);
-      if (er == hipSuccess) er = hipMemcpyAsync(out, f32, (size_t)numel * 4, hipMemcpyDeviceToHost, s);
-      if (er == hipSuccess) er = hipStreamSynchronize(s);
-    } catch (...) {
-      (void)hipFree(f32);
-      throw;
-    }
-    (void)hipFree(f32);
-    HIP_CHECK(er);
+    bk::OpScratch sc;
+    float* f32 = sc.get<float>((size_t)numel);
+    if (t.dt == F16X2) launch_split_to_f32(t.p, t.ld, f32, t.c, t.pixels(), t.c, s);
+    else HIP_CHECK(hipMemcpy2DAsync(f32, (size_t)t.c * 4, t.p, (size_t)t.ld * 4, (size_t)t.c * 4, (size_t)t.pixels(), hipMemcpyDeviceToDevice, s));
+    HIP_CHECK(hipMemcpyAsync(out, f32, (size_t)numel * 4, hipMemcpyDeviceToHost, s));
+    HIP_CHECK(hipStreamSynchronize(s));
   });
 }
 

@@ -5,22 +5,7 @@
 using namespace rtd;
 using namespace rtd_eng;
 
-// device scratch of one rtd_op_* call: freed on every path (a throwing RTD_CHECK / HIP_CHECK included)
-struct OpScratch {
-  std::vector<void*> bufs;
-  template <typename T> T* get(size_t count) {
-    void* p = nullptr;
-    HIP_CHECK(hipMalloc(&p, count ? count * sizeof(T) : 16));
-    bufs.push_back(p);
-    return (T*)p;
-  }
-  template <typename T> T* upload(const T* host, size_t count) {
-    T* d = get<T>(count);
-    HIP_CHECK(hipMemcpy(d, host, count * sizeof(T), hipMemcpyHostToDevice));
-    return d;
-  }
-  ~OpScratch() { for (void* p : bufs) (void)hipFree(p); }
-};
+using backend::OpScratch;   // device buffers, events and streams of one call here: released on every path, a throw included
 static bool rows_fit_int(int a, int b) { return a >= 1 && b >= 1 && (int64_t)a * b <= 0x7fffffff; }
 static Tensor rows_view(const void* p, int dt, int n, int rows, int c, int64_t ld) {
   Tensor t = mk(p, dt, n, rows, 1, c);
@@ -56,20 +41,14 @@ int rtd_debug_tensor(rtd_handle h, const char* name, float* out, int64_t capacit
       return;
     }
     if (t.dt == F16X2) RTD_CHECK(t.c % SPLIT_GROUP == 0, RTD_E_INVALID, "debug tensor: split tensor with a partial channel group");
-    void* dense = nullptr;
-    float* f32 = nullptr;
-    HIP_CHECK(hipMalloc(&dense, (size_t)numel * es));
-    hipError_t er = hipMalloc((void**)&f32, (size_t)numel * 4);
-    if (er == hipSuccess) er = hipMemcpy2DAsync(dense, (size_t)t.c * es, t.p, (size_t)t.ld * es, (size_t)t.c * es, (size_t)t.pixels(), hipMemcpyDeviceToDevice, h->q.stream);
-    if (er == hipSuccess) {
-      if (t.dt == F16X2) launch_split_to_f32(dense, t.c, f32, t.c, t.pixels(), t.c, h->q.stream);
-      else launch_to_f32(dense, t.dt, f32, numel, h->q.stream);
-      er = hipMemcpyAsync(out, f32, (size_t)numel * 4, hipMemcpyDeviceToHost, h->q.stream);
-    }
-    if (er == hipSuccess) er = hipStreamSynchronize(h->q.stream);
-    (void)hipFree(dense);
-    if (f32) (void)hipFree(f32);
-    HIP_CHECK(er);
+    OpScratch sc;
+    void* dense = sc.get<char>((size_t)numel * es);
+    float* f32 = sc.get<float>((size_t)numel);
+    HIP_CHECK(hipMemcpy2DAsync(dense, (size_t)t.c * es, t.p, (size_t)t.ld * es, (size_t)t.c * es, (size_t)t.pixels(), hipMemcpyDeviceToDevice, h->q.stream));
+    if (t.dt == F16X2) launch_split_to_f32(dense, t.c, f32, t.c, t.pixels(), t.c, h->q.stream);
+    else launch_to_f32(dense, t.dt, f32, numel, h->q.stream);
+    HIP_CHECK(hipMemcpyAsync(out, f32, (size_t)numel * 4, hipMemcpyDeviceToHost, h->q.stream));
+    HIP_CHECK(hipStreamSynchronize(h->q.stream));
   });
 }
 
@@ -116,16 +95,18 @@ int rtd_profile(rtd_handle h, int32_t n, int32_t reps, rtd_layer_time* out, int3
     // zero-filled staging frames (timings do not depend on pixel values)
     if (p->stem_fused && (h->last_n != n || h->last_fa.n != n)) point_at_blank_frames(h, p, n);
     RTD_CHECK(capacity >= nops, RTD_E_INVALID, "profile: capacity too small");
+    OpScratch sc;
     std::vector<hipEvent_t> ev((size_t)nops + 1);
-    for (auto& x : ev) HIP_CHECK(hipEventCreate(&x));
+    for (auto& x : ev) x = sc.event();
     std::vector<double> acc(nops, 0.0);
     for (Op* op : ops) op->run(h->q.stream);   // warm-up
     for (int r = 0; r < reps; ++r) {
       if (g_profile_twice) {
         // diagnostic: every op runs twice back to back and only the SECOND run is timed (operands, filter and TLB entries
         // warm from the first) - the gap to the normal profile is what the op pays for cold operands inside the network
+        OpScratch sc2;
         std::vector<hipEvent_t> ev2((size_t)nops);
-        for (auto& x : ev2) HIP_CHECK(hipEventCreate(&x));
+        for (auto& x : ev2) x = sc2.event();
         for (int i = 0; i < nops; ++i) {
           ops[i]->run(h->q.stream);
           HIP_CHECK(hipEventRecord(ev2[i], h->q.stream));
@@ -138,7 +119,6 @@ int rtd_profile(rtd_handle h, int32_t n, int32_t reps, rtd_layer_time* out, int3
           HIP_CHECK(hipEventElapsedTime(&ms, ev2[i], ev[i + 1]));
           acc[i] += ms;
         }
-        for (auto& x : ev2) (void)hipEventDestroy(x);
         continue;
       }
       HIP_CHECK(hipEventRecord(ev[0], h->q.stream));
@@ -153,7 +133,6 @@ int rtd_profile(rtd_handle h, int32_t n, int32_t reps, rtd_layer_time* out, int3
         acc[i] += ms;
       }
     }
-    for (auto& x : ev) (void)hipEventDestroy(x);
     for (int i = 0; i < nops; ++i) {
       rtd_layer_time& t = out[i];
       memset(&t, 0, sizeof t);
@@ -234,28 +213,21 @@ int rtd_debug_option(const char* name, int value) {
   return RTD_E_INVALID;
 }
 
-// a caller's filter [N][K] fp32 + bias [N] (device) as launch_conv wants them: [Npad][Kpad] in `dtype`, zero padded, and fp32 [Npad]
-struct DevFilter {
-  float* wpad = nullptr; void* w = nullptr; float* bias = nullptr;
-  int Kpad = 0, Npad = 0;
-  void release() { if (w != wpad) (void)hipFree(w); (void)hipFree(wpad); (void)hipFree(bias); }
-};
-static DevFilter dev_filter(int dtype, const void* w_f32, const float* bias, int N, int K) {
-  DevFilter f;
-  f.Npad = conv_npad(N);
-  f.Kpad = dtype == F16X2 ? conv_kpad_split(K) : conv_kpad(K);
-  const int kcols = dtype == F16X2 ? f.Kpad / 2 : f.Kpad;        // fp32 staging row (F16X2: 2 bf16 per column)
-  HIP_CHECK(hipMalloc((void**)&f.wpad, (size_t)f.Npad * kcols * 4));
-  HIP_CHECK(hipMemset(f.wpad, 0, (size_t)f.Npad * kcols * 4));
-  HIP_CHECK(hipMemcpy2D(f.wpad, (size_t)kcols * 4, w_f32, (size_t)K * 4, (size_t)K * 4, N, hipMemcpyDeviceToDevice));
-  HIP_CHECK(hipMalloc((void**)&f.bias, (size_t)f.Npad * 4));
-  HIP_CHECK(hipMemset(f.bias, 0, (size_t)f.Npad * 4));
+// a caller's filter [N][K] fp32 + bias [N] (device) as launch_conv wants them, staged in the call's scratch
+static ConvFilter dev_filter(OpScratch& sc, int dtype, const void* w_f32, const float* bias, int N, int K) {
+  ConvFilter f = conv_filter_extents(dtype, N, K);
+  float* rows = sc.zeros<float>((size_t)f.Npad * f.kcols());
+  HIP_CHECK(hipMemcpy2D(rows, (size_t)f.kcols() * 4, w_f32, (size_t)K * 4, (size_t)K * 4, N, hipMemcpyDeviceToDevice));
+  f.bias = sc.zeros<float>(f.Npad);
   HIP_CHECK(hipMemcpy(f.bias, bias, (size_t)N * 4, hipMemcpyDeviceToDevice));
-  f.w = f.wpad;
-  if (dtype == BF16 || dtype == F16X2) HIP_CHECK(hipMalloc(&f.w, (size_t)f.Npad * f.Kpad * 2));
-  if (dtype == BF16) launch_f32_to(f.wpad, f.w, BF16, (int64_t)f.Npad * f.Kpad, nullptr);
-  else if (dtype == F16X2) launch_f32_to_split(f.wpad, kcols, f.w, kcols, f.Npad, kcols, nullptr);
+  f.w = f.converts() ? sc.get<char>(f.bytes()) : (void*)rows;
+  conv_filter_convert(f, rows, nullptr);
   return f;
+}
+// the two-pass split-K workspace of a launch that owns none, from the call's scratch
+static void give_slab(OpScratch& sc, ConvArgs& a) {
+  a.ws.slab_bytes = conv_split_slab_bytes(a);
+  if (a.ws.slab_bytes) a.ws.slab = sc.get<float>(a.ws.slab_bytes / 4);
 }
 
 static int op_conv_impl(int dtype, const void* x, const void* x2, int C2, const void* w_ohwi_f32, const float* bias, const void* res, void* y,
@@ -264,31 +236,23 @@ static int op_conv_impl(int dtype, const void* x, const void* x2, int C2, const 
   return op_guard([&] {
     RTD_CHECK(KH == KW, RTD_E_INVALID, "square filters only");
     const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-    DevFilter f = dev_filter(dtype, w_ohwi_f32, bias, Cout, KH * KW * Cin + (x2 ? C2 : 0)), f1;
-    ConvArgs a;
-    a.x = x_up2 ? mk(x, dtype, B, H / 2, W / 2, Cin) : mk(x, dtype, B, H, W, Cin);      // x_up2: H, W are the OUTPUT extents
+    OpScratch sc;
+    const ConvFilter f = dev_filter(sc, dtype, w_ohwi_f32, bias, Cout, KH * KW * Cin + (x2 ? C2 : 0));
+    // x_up2: H, W are the OUTPUT extents
+    ConvArgs a = conv_args(x_up2 ? mk(x, dtype, B, H / 2, W / 2, Cin) : mk(x, dtype, B, H, W, Cin), mk(y, out_f32 ? F32 : dtype, B, OH, OW, Cout), f, KH, stride, pad, act);
     a.x_up2 = x_up2;
-    a.y = mk(y, out_f32 ? F32 : dtype, B, OH, OW, Cout);
-    a.w = f.w; a.bias = f.bias; a.KH = KH; a.KW = KW; a.stride = stride; a.pad = pad; a.Kpad = f.Kpad; a.Npad = f.Npad;
-    a.act = act; a.res_mode = res ? res_mode : RES_NONE;
+    a.res_mode = res ? res_mode : RES_NONE;
     if (res) a.res = mk(res, dtype, B, OH, OW, Cout);
     if (x2) a.x2 = mk(x2, dtype, B, OH, OW, C2);
     if (y1) {                                                    // a following 1x1 conv Cout -> Cnext fused into this launch (ConvArgs::next_*)
       RTD_CHECK(dtype == BF16 || dtype == F16X2, RTD_E_INVALID, "fused following conv: bf16 / f16x2 only");
-      f1 = dev_filter(dtype, w1_f32, bias1, Cnext, Cout);
+      const ConvFilter f1 = dev_filter(sc, dtype, w1_f32, bias1, Cnext, Cout);
       a.next_w = f1.w; a.next_bias = f1.bias; a.next_y = mk(y1, dtype, B, OH, OW, Cnext); a.next_kpad = f1.Kpad; a.next_act = next_act;
       RTD_CHECK(conv_next_supported(a), RTD_E_INVALID, "fused following conv: shape not taken by the streaming kernels");
     }
-    ConvWorkspace ws;
-    ws.slab_bytes = conv_split_slab_bytes(a);
-    if (ws.slab_bytes) HIP_CHECK(hipMalloc((void**)&ws.slab, ws.slab_bytes));
-    a.ws = ws;
+    give_slab(sc, a);
     launch_conv(a, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
-    if (ws.slab) (void)hipFree(ws.slab);
-    HIP_CHECK(hipDeviceSynchronize());
-    f.release();
-    if (f1.wpad) f1.release();
   });
 }
 
@@ -302,22 +266,15 @@ int rtd_op_conv_view(int dtype, const void* x, int ldx, const void* w_ohwi_f32, 
   return op_guard([&] {
     RTD_CHECK(x && y && w_ohwi_f32 && bias && ldx >= Cin && ldy >= Cout && (!res || ldres >= Cout), RTD_E_INVALID, "conv view: arguments");
     const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KH) / stride + 1;
-    DevFilter f = dev_filter(dtype, w_ohwi_f32, bias, Cout, KH * KH * Cin);
+    OpScratch sc;
+    const ConvFilter f = dev_filter(sc, dtype, w_ohwi_f32, bias, Cout, KH * KH * Cin);
     auto view = [&](const void* p, int h, int w, int c, int ld) { Tensor t = mk(p, dtype, B, h, w, c); t.ld = ld; t.bstride = (int64_t)h * w * ld; return t; };
-    ConvArgs a;
-    a.x = view(x, H, W, Cin, ldx);
-    a.y = view(y, OH, OW, Cout, ldy);
-    a.w = f.w; a.bias = f.bias; a.KH = a.KW = KH; a.stride = stride; a.pad = pad; a.Kpad = f.Kpad; a.Npad = f.Npad;
-    a.act = act; a.res_mode = res ? res_mode : RES_NONE;
+    ConvArgs a = conv_args(view(x, H, W, Cin, ldx), view(y, OH, OW, Cout, ldy), f, KH, stride, pad, act);
+    a.res_mode = res ? res_mode : RES_NONE;
     if (res) a.res = view(res, OH, OW, Cout, ldres);
-    ConvWorkspace ws;
-    ws.slab_bytes = conv_split_slab_bytes(a);
-    if (ws.slab_bytes) HIP_CHECK(hipMalloc((void**)&ws.slab, ws.slab_bytes));
-    a.ws = ws;
+    give_slab(sc, a);
     launch_conv(a, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
-    if (ws.slab) (void)hipFree(ws.slab);
-    f.release();
   });
 }
 
@@ -333,37 +290,51 @@ int rtd_op_conv_next(int dtype, const void* x, const void* x2, const void* w_f32
   return op_conv_impl(dtype, x, x2, x2 ? C2 : 0, w_f32, bias, res, y, B, H, W, Cin, Cout, 1, 1, 1, 0, act, res_mode, 0, 0, w1_f32, bias1, y1, Cnext, next_act);
 }
 
+// operands of one benchmarked conv in the call's scratch: zero-filled input, filter, bias and residual, the output, the split-K workspace
+struct BenchConv {
+  ConvArgs a;
+  ConvFilter f;
+  void *x = nullptr, *r = nullptr;
+  size_t xb = 0, yb = 0;
+};
+static BenchConv bench_conv_make(OpScratch& sc, int dtype, int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad, int with_res, int act) {
+  BenchConv c;
+  c.f = conv_filter_extents(dtype, Cout, KH * KH * Cin);
+  const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KH) / stride + 1;
+  const size_t es = dtype == BF16 ? 2 : 4;
+  c.xb = (size_t)B * H * W * Cin * es; c.yb = (size_t)B * OH * OW * Cout * es;
+  c.x = sc.zeros<char>(c.xb);
+  void* y = sc.get<char>(c.yb);
+  c.f.w = sc.zeros<char>(c.f.bytes());
+  c.f.bias = sc.zeros<float>(c.f.Npad);
+  c.a = conv_args(mk(c.x, dtype, B, H, W, Cin), mk(y, dtype, B, OH, OW, Cout), c.f, KH, stride, pad, act);
+  if (with_res) {
+    c.r = sc.zeros<char>(c.yb);
+    c.a.res = mk(c.r, dtype, B, OH, OW, Cout);
+    c.a.res_mode = RES_PRE;
+  }
+  give_slab(sc, c.a);                                            // two-pass split-K
+  if (c.a.ws.slab) HIP_CHECK(hipMemset(c.a.ws.slab, 0, c.a.ws.slab_bytes));
+  return c;
+}
+
 static int bench_conv_impl(int dtype, int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad, int with_res, int act, int reps,
                            int flush_mb, float* us_out) {
   return op_guard([&] {
-    const int K = KH * KH * Cin, Kpad = dtype == F16X2 ? conv_kpad_split(K) : conv_kpad(K), Npad = conv_npad(Cout);
-    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KH) / stride + 1;
-    const size_t es = dtype == BF16 ? 2 : 4;
-    const size_t xb = (size_t)B * H * W * Cin * es, yb = (size_t)B * OH * OW * Cout * es, wb = (size_t)Npad * Kpad * (dtype == F32 ? 4 : 2);
-    void *x = nullptr, *y = nullptr, *r = nullptr, *w = nullptr, *flush = nullptr; float* bias = nullptr;
-    HIP_CHECK(hipMalloc(&x, xb)); HIP_CHECK(hipMalloc(&y, yb)); HIP_CHECK(hipMalloc(&w, wb)); HIP_CHECK(hipMalloc((void**)&bias, Npad * 4));
-    HIP_CHECK(hipMemset(x, 0, xb)); HIP_CHECK(hipMemset(w, 0, wb)); HIP_CHECK(hipMemset(bias, 0, Npad * 4));
-    if (with_res) { HIP_CHECK(hipMalloc(&r, yb)); HIP_CHECK(hipMemset(r, 0, yb)); }
+    OpScratch sc;
+    const BenchConv c = bench_conv_make(sc, dtype, B, H, W, Cin, Cout, KH, stride, pad, with_res, act);
+    const ConvArgs& a = c.a;
+    void *x = c.x, *r = c.r, *w = c.f.w, *y = a.y.p; float* bias = c.f.bias;
+    const size_t xb = c.xb, yb = c.yb, wb = c.f.bytes();
+    const int OH = a.y.h, OW = a.y.w;
     if ((g_bench_rewarm & 32) && dtype != F32) {                 // "bench_rewarm" bit 5: random 16-bit operands instead of zeros
       rtd_launch(k_fill_rand16, dim3(1024), dim3(256), 0, nullptr, (uint16_t*)x, xb / 2, 1u);
       rtd_launch(k_fill_rand16, dim3(1024), dim3(256), 0, nullptr, (uint16_t*)w, wb / 2, 2u);
       if (r) rtd_launch(k_fill_rand16, dim3(1024), dim3(256), 0, nullptr, (uint16_t*)r, yb / 2, 3u);
       HIP_CHECK(hipDeviceSynchronize());
     }
-    if (flush_mb > 0) HIP_CHECK(hipMalloc(&flush, (size_t)flush_mb << 20));
-    ConvArgs a;
-    a.x = mk(x, dtype, B, H, W, Cin);
-    a.y = mk(y, dtype, B, OH, OW, Cout);
-    a.w = w; a.bias = bias; a.KH = KH; a.KW = KH; a.stride = stride; a.pad = pad; a.Kpad = Kpad; a.Npad = Npad;
-    a.act = act; a.res_mode = with_res ? RES_PRE : RES_NONE;
-    if (with_res) a.res = mk(r, dtype, B, OH, OW, Cout);
-    a.ws.slab_bytes = conv_split_slab_bytes(a);                  // two-pass split-K
-    if (a.ws.slab_bytes) {
-      HIP_CHECK(hipMalloc((void**)&a.ws.slab, a.ws.slab_bytes));
-      HIP_CHECK(hipMemset(a.ws.slab, 0, a.ws.slab_bytes));
-    }
-    hipEvent_t e0, e1;
-    HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1));
+    void* flush = flush_mb > 0 ? sc.get<char>((size_t)flush_mb << 20) : nullptr;
+    const hipEvent_t e0 = sc.event(), e1 = sc.event();
     for (int i = 0; i < 3; ++i) launch_conv(a, nullptr);
     HIP_CHECK(hipEventRecord(e0, nullptr));
     for (int i = 0; i < reps; ++i) launch_conv(a, nullptr);
@@ -398,11 +369,6 @@ static int bench_conv_impl(int dtype, int B, int H, int W, int Cin, int Cout, in
       us_out[1] = tot * 1e3f / reps;
     }
     HIP_CHECK(hipDeviceSynchronize());
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
-    if (a.ws.slab) (void)hipFree(a.ws.slab);
-    (void)hipFree(x); (void)hipFree(y); (void)hipFree(w); (void)hipFree(bias);
-    if (r) (void)hipFree(r);
-    if (flush) (void)hipFree(flush);
   });
 }
 int rtd_bench_conv(int dtype, int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad, int with_res, int reps,
@@ -416,38 +382,18 @@ int rtd_bench_conv_act(int dtype, int B, int H, int W, int Cin, int Cout, int KH
 }
 
 // Concurrency micro-benchmark (tools/pair_bench.py): conv A on one stream, conv B on another; us_out = {A alone, B alone,
-// A and B issued together} per repetition (`reps` launches of each, events on both streams).
-struct BenchConv {
-  ConvArgs a;
-  void *x = nullptr, *y = nullptr, *w = nullptr; float* bias = nullptr;
-};
-static void bench_conv_make(BenchConv& c, const int* sh) {   // sh: B, HW, Cin, Cout, K, stride, pad
-  const int B = sh[0], H = sh[1], W = sh[1], Cin = sh[2], Cout = sh[3], KH = sh[4], stride = sh[5], pad = sh[6];
-  const int K = KH * KH * Cin, Kpad = conv_kpad(K), Npad = conv_npad(Cout);
-  const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KH) / stride + 1;
-  const size_t xb = (size_t)B * H * W * Cin * 2, yb = (size_t)B * OH * OW * Cout * 2, wb = (size_t)Npad * Kpad * 2;
-  HIP_CHECK(hipMalloc(&c.x, xb)); HIP_CHECK(hipMalloc(&c.y, yb)); HIP_CHECK(hipMalloc(&c.w, wb)); HIP_CHECK(hipMalloc((void**)&c.bias, Npad * 4));
-  HIP_CHECK(hipMemset(c.x, 0, xb)); HIP_CHECK(hipMemset(c.w, 0, wb)); HIP_CHECK(hipMemset(c.bias, 0, Npad * 4));
-  c.a.x = mk(c.x, BF16, B, H, W, Cin);
-  c.a.y = mk(c.y, BF16, B, OH, OW, Cout);
-  c.a.w = c.w; c.a.bias = c.bias; c.a.KH = KH; c.a.KW = KH; c.a.stride = stride; c.a.pad = pad; c.a.Kpad = Kpad; c.a.Npad = Npad;
-  c.a.act = 1; c.a.res_mode = RES_NONE;
-}
+// A and B issued together} per repetition (`reps` launches of each).  sh: B, HW, Cin, Cout, K, stride, pad
 int rtd_bench_conv_pair(const int* shape_a, const int* shape_b, int reps, float* us_out) {
   return op_guard([&] {
-    BenchConv A, B;
-    bench_conv_make(A, shape_a);
-    bench_conv_make(B, shape_b);
-    hipStream_t s1, s2;
-    HIP_CHECK(hipStreamCreateWithFlags(&s1, hipStreamNonBlocking));
-    HIP_CHECK(hipStreamCreateWithFlags(&s2, hipStreamNonBlocking));
-    hipEvent_t e0, e1, f0, f1;
-    HIP_CHECK(hipEventCreate(&e0)); HIP_CHECK(hipEventCreate(&e1)); HIP_CHECK(hipEventCreate(&f0)); HIP_CHECK(hipEventCreate(&f1));
+    OpScratch sc;
+    auto make = [&](const int* sh) { return bench_conv_make(sc, BF16, sh[0], sh[1], sh[1], sh[2], sh[3], sh[4], sh[5], sh[6], 0, ACT_RELU).a; };
+    const ConvArgs A = make(shape_a), B = make(shape_b);
+    const hipStream_t s1 = sc.stream(), s2 = sc.stream();
     auto run = [&](bool ra, bool rb) {
-      for (int i = 0; i < 3; ++i) { if (ra) launch_conv(A.a, s1); if (rb) launch_conv(B.a, s2); }
+      for (int i = 0; i < 3; ++i) { if (ra) launch_conv(A, s1); if (rb) launch_conv(B, s2); }
       HIP_CHECK(hipDeviceSynchronize());
       const auto t0 = std::chrono::steady_clock::now();
-      for (int i = 0; i < reps; ++i) { if (ra) launch_conv(A.a, s1); if (rb) launch_conv(B.a, s2); }
+      for (int i = 0; i < reps; ++i) { if (ra) launch_conv(A, s1); if (rb) launch_conv(B, s2); }
       HIP_CHECK(hipStreamSynchronize(s1));
       HIP_CHECK(hipStreamSynchronize(s2));
       return (float)(std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() / reps);
@@ -455,25 +401,10 @@ int rtd_bench_conv_pair(const int* shape_a, const int* shape_b, int reps, float*
     us_out[0] = run(true, false);
     us_out[1] = run(false, true);
     us_out[2] = run(true, true);
-    (void)hipEventDestroy(e0); (void)hipEventDestroy(e1); (void)hipEventDestroy(f0); (void)hipEventDestroy(f1);
-    (void)hipStreamDestroy(s1); (void)hipStreamDestroy(s2);
-    for (BenchConv* c : {&A, &B}) { (void)hipFree(c->x); (void)hipFree(c->y); (void)hipFree(c->w); (void)hipFree(c->bias); }
   });
 }
 
 int rtd_bench_mfma_rate(int random_operands, int ms_target, float* out) {
-  // device buffers and events are released on every path (a throwing HIP_CHECK included)
-  struct Scratch {
-    unsigned* seed = nullptr; long long* stamps = nullptr; float* sink = nullptr;
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    ~Scratch() {
-      if (e0) (void)hipEventDestroy(e0);
-      if (e1) (void)hipEventDestroy(e1);
-      if (seed) (void)hipFree(seed);
-      if (stamps) (void)hipFree(stamps);
-      if (sink) (void)hipFree(sink);
-    }
-  };
   return op_guard([&] {
     RTD_CHECK(out && ms_target >= 1 && ms_target <= 2000, RTD_E_INVALID, "arguments");
     int dev = 0;
@@ -490,22 +421,23 @@ int rtd_bench_mfma_rate(int random_operands, int ms_target, float* out) {
         const unsigned hi = (h2 & 0x8000u) | ((10u + ((h2 >> 20) & 7u)) << 10) | (h2 & 0x3ffu);
         hs[i] = lo | (hi << 16);
       }
-    Scratch sc;
-    HIP_CHECK(hipMalloc((void**)&sc.seed, 4096 * 4)); HIP_CHECK(hipMalloc((void**)&sc.stamps, (size_t)cus * 4 * 2 * 8)); HIP_CHECK(hipMalloc((void**)&sc.sink, 16));
-    HIP_CHECK(hipMemcpy(sc.seed, hs.data(), 4096 * 4, hipMemcpyHostToDevice));
+    OpScratch sc;
+    const unsigned* seed = sc.upload(hs.data(), hs.size());
+    long long* stamps = sc.get<long long>((size_t)cus * 4 * 2);
+    float* sink = sc.get<float>(4);
     // 16 MFMAs of 16 cycles per iteration at <= 2.4 GHz: 9400 iterations per millisecond
     const int iters = ms_target * 9400;
-    HIP_CHECK(hipEventCreate(&sc.e0)); HIP_CHECK(hipEventCreate(&sc.e1));
+    const hipEvent_t e0 = sc.event(), e1 = sc.event();
     float ms = 0.f;
     for (int rep = 0; rep < 3; ++rep) {
-      HIP_CHECK(hipEventRecord(sc.e0, nullptr));
-      rtd_launch(k_mfma_rate, dim3(cus), dim3(256), 0, nullptr, sc.seed, iters, sc.stamps, sc.sink);
-      HIP_CHECK(hipEventRecord(sc.e1, nullptr));
-      HIP_CHECK(hipEventSynchronize(sc.e1));
-      HIP_CHECK(hipEventElapsedTime(&ms, sc.e0, sc.e1));
+      HIP_CHECK(hipEventRecord(e0, nullptr));
+      rtd_launch(k_mfma_rate, dim3(cus), dim3(256), 0, nullptr, seed, iters, stamps, sink);
+      HIP_CHECK(hipEventRecord(e1, nullptr));
+      HIP_CHECK(hipEventSynchronize(e1));
+      HIP_CHECK(hipEventElapsedTime(&ms, e0, e1));
     }
     std::vector<long long> h((size_t)cus * 4 * 2);
-    HIP_CHECK(hipMemcpy(h.data(), sc.stamps, h.size() * 8, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(h.data(), stamps, h.size() * 8, hipMemcpyDeviceToHost));
     double cyc = 0, rt = 0;
     for (int w = 0; w < cus * 4; ++w) { cyc += (double)h[2 * w]; rt += (double)h[2 * w + 1]; }
     out[0] = (float)((double)iters * 16.0 * cus * 4.0 * 16384.0 / (ms * 1e-3) / 1e12);
@@ -528,24 +460,26 @@ int rtd_op_attention(int dtype, const void* qk, const void* v, void* o, int B, i
   });
 }
 
+// the body both msdeform entry points share (each keeps its own argument checks): the level table [n_levels][3] h, w, start on the
+// device, the reference boxes widened to 8-float rows, the launch
+static void op_msdeform_body(int dtype, const void* value, int value_ld, int value_coff, const float* offaw, const float* ref, float* out, int B, int Q,
+                             int heads, int hd, int n_levels, int n_points, const int32_t* level_hw, float offset_scale) {
+  int32_t lv[24]; int S = 0;
+  for (int l = 0; l < n_levels; ++l) { lv[l * 3] = level_hw[2 * l]; lv[l * 3 + 1] = level_hw[2 * l + 1]; lv[l * 3 + 2] = S; S += level_hw[2 * l] * level_hw[2 * l + 1]; }
+  OpScratch sc;
+  const int32_t* lvd = sc.upload(lv, (size_t)3 * n_levels);
+  float* ref8 = sc.zeros<float>((size_t)B * Q * 8);
+  HIP_CHECK(hipMemcpy2D(ref8, 32, ref, 16, 16, (size_t)B * Q, hipMemcpyDeviceToDevice));
+  launch_msdeform(rows_view(value, dtype, B, S, heads * hd, value_ld), value_coff, mk(offaw, F32, B, Q, 1, heads * n_levels * n_points * 3), ref8,
+                  mk(out, F32, B, Q, 1, heads * hd), heads, hd, n_levels, n_points, lvd, offset_scale, nullptr);
+  HIP_CHECK(hipDeviceSynchronize());
+}
+
 int rtd_op_msdeform(int dtype, const void* value, const float* offaw, const float* ref, float* out, int B, int Q, int heads, int hd,
                     int n_levels, int n_points, const int32_t* level_hw, int value_ld, float offset_scale) {
   return op_guard([&] {
     RTD_CHECK(n_levels >= 1 && n_levels <= 8, RTD_E_INVALID, "n_levels");
-    int32_t lv[24]; int S = 0;
-    for (int l = 0; l < n_levels; ++l) { lv[l * 3] = level_hw[2 * l]; lv[l * 3 + 1] = level_hw[2 * l + 1]; lv[l * 3 + 2] = S; S += level_hw[2 * l] * level_hw[2 * l + 1]; }
-    int32_t* lvd = nullptr; float* ref8 = nullptr;
-    HIP_CHECK(hipMalloc((void**)&lvd, sizeof lv));
-    HIP_CHECK(hipMemcpy(lvd, lv, sizeof lv, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMalloc((void**)&ref8, (size_t)B * Q * 32));
-    HIP_CHECK(hipMemset(ref8, 0, (size_t)B * Q * 32));
-    HIP_CHECK(hipMemcpy2D(ref8, 32, ref, 16, 16, (size_t)B * Q, hipMemcpyDeviceToDevice));
-    Tensor tv = mk(value, dtype, B, S, 1, heads * hd);
-    tv.ld = value_ld; tv.bstride = (int64_t)S * value_ld;
-    launch_msdeform(tv, 0, mk(offaw, F32, B, Q, 1, heads * n_levels * n_points * 3), ref8, mk(out, F32, B, Q, 1, heads * hd), heads, hd,
-                    n_levels, n_points, lvd, offset_scale, nullptr);
-    HIP_CHECK(hipDeviceSynchronize());
-    (void)hipFree(lvd); (void)hipFree(ref8);
+    op_msdeform_body(dtype, value, value_ld, 0, offaw, ref, out, B, Q, heads, hd, n_levels, n_points, level_hw, offset_scale);
   });
 }
 
@@ -556,19 +490,8 @@ int rtd_op_msdeform_view(int dtype, const void* value, int value_ld, int value_c
     RTD_CHECK(hd == 32 && heads >= 1, RTD_E_INVALID, "msdeform view: head dim must be 32");
     RTD_CHECK(n_levels >= 1 && n_levels <= 8 && n_points >= 1, RTD_E_INVALID, "msdeform view: 1..8 levels");
     RTD_CHECK(value_coff >= 0 && value_coff + heads * hd <= value_ld, RTD_E_INVALID, "msdeform view: the channel slice leaves the value row");
-    int32_t lv[24]; int S = 0;
-    for (int l = 0; l < n_levels; ++l) {
-      RTD_CHECK(level_hw[2 * l] >= 1 && level_hw[2 * l + 1] >= 1, RTD_E_INVALID, "msdeform view: level extents");
-      lv[l * 3] = level_hw[2 * l]; lv[l * 3 + 1] = level_hw[2 * l + 1]; lv[l * 3 + 2] = S; S += level_hw[2 * l] * level_hw[2 * l + 1];
-    }
-    OpScratch sc;
-    const int32_t* lvd = sc.upload(lv, (size_t)3 * n_levels);
-    float* ref8 = sc.get<float>((size_t)B * Q * 8);
-    HIP_CHECK(hipMemset(ref8, 0, (size_t)B * Q * 32));
-    HIP_CHECK(hipMemcpy2D(ref8, 32, ref, 16, 16, (size_t)B * Q, hipMemcpyDeviceToDevice));
-    launch_msdeform(rows_view(value, dtype, B, S, heads * hd, value_ld), value_coff, mk(offaw, F32, B, Q, 1, heads * n_levels * n_points * 3), ref8,
-                    mk(out, F32, B, Q, 1, heads * hd), heads, hd, n_levels, n_points, lvd, offset_scale, nullptr);
-    HIP_CHECK(hipDeviceSynchronize());
+    for (int l = 0; l < n_levels; ++l) RTD_CHECK(level_hw[2 * l] >= 1 && level_hw[2 * l + 1] >= 1, RTD_E_INVALID, "msdeform view: level extents");
+    op_msdeform_body(dtype, value, value_ld, value_coff, offaw, ref, out, B, Q, heads, hd, n_levels, n_points, level_hw, offset_scale);
   });
 }
 
@@ -695,22 +618,12 @@ int rtd_op_resize(const uint8_t* src, int sh, int sw, void* dst, int dh, int dw,
     int hks, vks;
     pil_coeffs(sw, dw, hb, hk, hks);
     pil_coeffs(sh, dh, vb, vk, vks);
-    std::vector<void*> tmp;
-    auto up = [&](const std::vector<int32_t>& v) {
-      void* d = nullptr;
-      HIP_CHECK(hipMalloc(&d, v.size() * 4));
-      tmp.push_back(d);
-      HIP_CHECK(hipMemcpy(d, v.data(), v.size() * 4, hipMemcpyHostToDevice));
-      return (const int32_t*)d;
-    };
+    OpScratch sc;
+    auto up = [&](const std::vector<int32_t>& v) { return (const int32_t*)sc.upload(v.data(), v.size()); };
     ResizeCoef c;
     c.hb = up(hb); c.hk = up(hk); c.vb = up(vb); c.vk = up(vk); c.hks = hks; c.vks = vks;
-    uint8_t* t = nullptr;
-    HIP_CHECK(hipMalloc((void**)&t, (size_t)sh * dw * 3));
-    tmp.push_back(t);
-    launch_resize_pil(src, sh, sw, t, mk(dst, dtype, 1, dh, dw, 8), 0, c, nullptr);
+    launch_resize_pil(src, sh, sw, sc.get<uint8_t>((size_t)sh * dw * 3), mk(dst, dtype, 1, dh, dw, 8), 0, c, nullptr);
     HIP_CHECK(hipDeviceSynchronize());
-    for (void* p : tmp) (void)hipFree(p);
   });
 }
 

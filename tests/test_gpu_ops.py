@@ -513,6 +513,44 @@ def test_conv_split_streaming_with_fused_next(L, case):
         _capi.debug_option("reset", 0)
 
 
+def test_refused_conv_calls_free_their_scratch_between_live_calls(L):
+    """rtd_op_conv_next with split_sx 0 is refused AFTER both of its filters are staged on the device (conv_next_supported says no).
+    The refusal is RTD_E_INVALID, and between three of them rtd_op_conv on one small layer (1 x 8 x 8, 64 -> 64, 3x3) answers bit for
+    bit what it answered the first time, in bf16, fp32 and F16X2: the refused call's scratch is released, nothing of a live call is."""
+    from telescope_cam_detection_amd import _capi
+    B, H, W, Cin, C2, Cnext, act, res_mode, next_act = SX_NEXT_CASES[2]
+    assert C2 == 0 and res_mode == 1
+    g = torch.Generator().manual_seed(5300)
+    dev = lambda t: torch.from_numpy(_capi.to_split(t.numpy()).view(np.int16)).cuda()
+    xd, rd = dev(torch.randn(B, H, W, Cin, generator=g)), dev(torch.randn(B, H, W, 256, generator=g))
+    wd, bd = (torch.randn(256, Cin, generator=g) / 8).cuda(), torch.randn(256, generator=g).cuda()
+    w1d, b1d = (torch.randn(Cnext, 256, generator=g) / 16).cuda(), torch.randn(Cnext, generator=g).cuda()
+    yd = torch.zeros(B, H, W, 2 * 256, dtype=torch.int16, device="cuda")
+    y1d = torch.zeros(B, H, W, 2 * Cnext, dtype=torch.int16, device="cuda")
+    x8 = torch.randn(1, 8, 8, 64, generator=g)
+    w8 = (torch.randn(64, 3, 3, 64, generator=g) / 24).contiguous().cuda()          # OHWI fp32
+    b8 = torch.randn(64, generator=g).cuda()
+    small = {_capi.DT_BF16: x8.to(torch.bfloat16).cuda(), _capi.DT_F32: x8.cuda(), _capi.DT_F16X2: dev(x8)}
+    first = {}
+    for rnd in range(3):
+        _capi.debug_option("split_sx", 0)
+        try:
+            rc = L.rtd_op_conv_next(_capi.DT_F16X2, xd.data_ptr(), None, wd.data_ptr(), bd.data_ptr(), rd.data_ptr(), yd.data_ptr(), w1d.data_ptr(),
+                                    b1d.data_ptr(), y1d.data_ptr(), B, H, W, Cin, C2, 256, Cnext, 1, res_mode, 1)
+        finally:
+            _capi.debug_option("reset", 0)
+        assert rc == _capi.RTD_E_INVALID, (rnd, rc, L.rtd_last_error(None))
+        for code, x in small.items():
+            y = torch.full_like(x, -1)
+            ck(L, L.rtd_op_conv(code, x.data_ptr(), w8.data_ptr(), b8.data_ptr(), None, y.data_ptr(), 1, 8, 8, 64, 64, 3, 3, 1, 1, 1, 0, 0))
+            if rnd == 0:
+                first[code] = y
+                vals = torch.from_numpy(_capi.from_split(y.cpu().numpy().view(np.uint16))) if code == _capi.DT_F16X2 else y.float().cpu()
+                assert torch.isfinite(vals).all() and (vals >= 0).all() and vals.max() > 0      # ReLU output, written everywhere
+            else:
+                assert torch.equal(y, first[code]), (rnd, code)
+
+
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 @pytest.mark.parametrize("dim", [64, 256, 384])
 def test_layernorm(L, dt, dim):

@@ -99,6 +99,65 @@ int main() {
   h->q.drain();
   h->q.close();
 
+  // ---- the scratch of one call: a failed get / event / stream throws and leaves nothing held; what is held goes exactly once (release
+  // empties the lists, so the destructor after it - and a second release - frees nothing; there is no copy that could free it again)
+  static_assert(!std::is_copy_constructible<bk::OpScratch>::value && !std::is_copy_assignable<bk::OpScratch>::value, "one owner");
+  {
+    bk::OpScratch sc;
+    std::string err;
+    CHECK(bk::caught(err, [&] { sc.get<float>(64); }) != RTD_OK && err.find("hipMalloc") != std::string::npos);
+    CHECK(bk::caught(err, [&] { sc.zeros<float>(64); }) != RTD_OK);
+    const float one = 1.f;
+    CHECK(bk::caught(err, [&] { sc.upload(&one, 1); }) != RTD_OK);
+    CHECK(bk::caught(err, [&] { sc.event(); }) != RTD_OK && err.find("hipEventCreate") != std::string::npos);
+    CHECK(bk::caught(err, [&] { sc.stream(); }) != RTD_OK);
+    CHECK(sc.bufs.empty() && sc.events.empty() && sc.streams.empty());
+    sc.release();                                                       // empty: frees nothing
+    CHECK(sc.bufs.empty() && sc.events.empty() && sc.streams.empty());
+    // (no device: hipFree refuses the address without touching it)
+    sc.bufs.push_back((void*)0x1000);
+    sc.release();
+    CHECK(sc.bufs.empty());
+    sc.release();
+  }
+  rc = bk::guarded(h, [&] {                                             // a throw past a scratch that holds something unwinds through its destructor
+    bk::OpScratch sc;
+    sc.bufs.push_back((void*)0x1000);
+    RTD_CHECK(false, RTD_E_INVALID, "refused after staging");
+  });
+  CHECK(rc == RTD_E_INVALID && strncmp(bk::last_error(h), "refused after staging", 21) == 0);
+
+  // ---- the padded extents of a conv filter against the kernels' three padding formulas, and the host-side row padding
+  for (int K : {27, 64, 576, 2304 + 256})
+    for (int N : {3, 32, 80, 256, 300}) {
+      const int kpad = (K + 63) / 64 * 64, npad = (N + 127) / 128 * 128, kpad_split = 2 * ((K + 31) / 32 * 32);
+      for (int dt : {(int)rtd::BF16, (int)rtd::F32, (int)rtd::F16X2}) {
+        const rtd::ConvFilter f = rtd::conv_filter_extents(dt, N, K);
+        CHECK(f.N == N && f.K == K && f.dt == dt && f.w == nullptr && f.bias == nullptr);
+        CHECK(f.Npad == npad && f.Kpad == (dt == rtd::F16X2 ? kpad_split : kpad));
+        CHECK(f.kcols() == (dt == rtd::F16X2 ? kpad_split / 2 : kpad));
+        CHECK(f.bytes() == (size_t)npad * f.Kpad * (dt == rtd::F32 ? 4 : 2));
+        CHECK(f.kcols() >= K && f.kcols() % 32 == 0 && f.bytes() % 512 == 0);
+      }
+    }
+  {
+    // two segments side by side along K (a block's last conv with its projection shortcut): [N][K1 | K2], zero padded to [Npad][kcols]
+    const int N = 3, K1 = 5, K2 = 27;
+    std::vector<float> w1((size_t)N * K1), w2((size_t)N * K2);
+    for (size_t i = 0; i < w1.size(); ++i) w1[i] = 1.f + (float)i;
+    for (size_t i = 0; i < w2.size(); ++i) w2[i] = -1.f - (float)i;
+    for (int dt : {(int)rtd::BF16, (int)rtd::F16X2}) {
+      const rtd::ConvFilter f = rtd::conv_filter_extents(dt, N, K1 + K2);
+      const std::vector<float> rows = rtd::conv_filter_rows(f, {{w1.data(), K1}, {w2.data(), K2}});
+      CHECK(rows.size() == (size_t)f.Npad * f.kcols());
+      for (int r = 0; r < f.Npad; ++r)
+        for (int k = 0; k < f.kcols(); ++k) {
+          const float want = r >= N || k >= K1 + K2 ? 0.f : (k < K1 ? w1[(size_t)r * K1 + k] : w2[(size_t)r * K2 + k - K1]);
+          CHECK(rows[(size_t)r * f.kcols() + k] == want);
+        }
+    }
+  }
+
   // ---- the staged-frame offsets and the shared crop checks
   {
     const int32_t hwc[6] = {2, 3, 3, 1, 1, 1};
