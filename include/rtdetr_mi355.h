@@ -44,6 +44,12 @@ enum {
  * arithmetic on fp32 MFMAs. */
 enum { RTD_PREC_BF16 = 0, RTD_PREC_FP32 = 1, RTD_PREC_F16X3 = 2 };
 enum { RTD_LAYER_BASIC = 0, RTD_LAYER_BOTTLENECK = 1 };
+/* The decoder's cross-attention sampler (upstream's `cross_attn_method`, HF's `decoder_method`).  RTD_DEC_DEFAULT: zero-padded bilinear
+ * grid_sample.  RTD_DEC_DISCRETE (upstream's "dsp" checkpoints, e.g. rtdetrv2_r18vd_dsp_3x_coco.yml): per sampling point ONE tap at
+ * int(loc * extent + 0.5), truncated toward zero and clamped into the map.  Same weight shapes; a checkpoint served with the other
+ * sampler computes other logits (0.65 on the small test model) and no check can see it, so the configuration must say which.
+ * RTD_PREC_BF16 is refused with RTD_DEC_DISCRETE: a bf16 offset carries 2^-9 relative, which moves the tap of a large share of points. */
+enum { RTD_DEC_DEFAULT = 0, RTD_DEC_DISCRETE = 1 };
 
 /* Constructor arguments of RTDETRDetector (src/rtdetr_detector.py:29-58) that matter to the device
  * side, plus the network description the reference obtains from upstream's YAML config
@@ -71,6 +77,7 @@ typedef struct rtd_config {
    * GPU (batching pipeline_depth > 1, bench.py --streams > 1) - other launches fill idle CUs anyway, so the convs take the
    * 256-pixel tile with the least LDS traffic per MFMA (+2.6 % frames/s with 3 handles, -6 % for a lone handle). */
   int32_t profile;
+  int32_t dec_method;       /* RTD_DEC_* */
 } rtd_config;
 
 /* One detection row: what the per-row loop of src/rtdetr_detector.py:267-303 emits before it

@@ -17,6 +17,7 @@ from .arch import Arch
 RTD_OK, RTD_E_INVALID, RTD_E_OOM, RTD_E_HIP, RTD_E_WEIGHTS, RTD_E_STATE = range(6)
 PREC_BF16, PREC_FP32, PREC_F16X3 = 0, 1, 2
 DT_BF16, DT_F32, DT_F16X2 = 0, 1, 4
+DEC_METHODS = {"default": 0, "discrete": 1}      # Arch.dec_method -> RTD_DEC_*
 SPLIT_GROUP = 32      # channels per [hi | lo] group of a F16X2 tensor (csrc/common.h)
 
 
@@ -69,7 +70,7 @@ class RtdConfig(C.Structure):
         ("enc_dim", C.c_int32), ("enc_ffn", C.c_int32), ("enc_heads", C.c_int32), ("csp_hidden", C.c_int32),
         ("d_model", C.c_int32), ("dec_ffn", C.c_int32), ("dec_heads", C.c_int32), ("dec_layers", C.c_int32),
         ("num_queries", C.c_int32), ("num_classes", C.c_int32), ("n_levels", C.c_int32), ("n_points", C.c_int32),
-        ("offset_scale", C.c_float), ("profile", C.c_int32),
+        ("offset_scale", C.c_float), ("profile", C.c_int32), ("dec_method", C.c_int32),
     ]
 
 
@@ -130,7 +131,7 @@ TEST_EXPORTS = [
     "rtd_debug_jpeg_coefficients", "rtd_debug_overlay_tiles", "rtd_debug_enhance_stage",
     "rtd_op_conv_view", "rtd_bench_conv_act", "rtd_debug_esrgan_tensor",
     "rtd_op_msdeform_view", "rtd_op_select_score", "rtd_op_gather_ln", "rtd_op_split_convert", "rtd_op_set_rows", "rtd_op_rowmax",
-    "rtd_op_gather_rows", "rtd_op_boxes", "rtd_op_add", "rtd_op_postprocess",
+    "rtd_op_gather_rows", "rtd_op_boxes", "rtd_op_add", "rtd_op_postprocess", "rtd_op_msdeform_discrete_view",
 ]
 
 
@@ -277,6 +278,8 @@ def lib() -> C.CDLL:
         L.rtd_op_boxes.argtypes = [vp, i32, i32, vp, vp, vp, i32, vp]
         L.rtd_op_add.argtypes = [i32, i32, i32, vp, vp, vp, i32, i32, i32, i32]
         L.rtd_op_postprocess.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
+    if hasattr(L, "rtd_op_msdeform_discrete_view"):      # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_op_msdeform_discrete_view.argtypes = L.rtd_op_msdeform_view.argtypes
     _lib = L
     return L
 
@@ -466,7 +469,14 @@ def make_config(arch: Arch, device: int, precision: int, max_batch: int, input_s
     c.num_queries, c.num_classes, c.n_levels, c.n_points = arch.num_queries, arch.num_classes, arch.n_levels, arch.n_points
     c.offset_scale = arch.offset_scale
     c.profile = profile
+    c.dec_method = DEC_METHODS[arch.dec_method]
     return c
+
+
+def cfg_for(arch: Arch, device: int = 0, precision: int = PREC_F16X3, max_batch: int = 1, input_size=(640, 640), use_graph: bool = False,
+            profile: int = PROFILE_LATENCY) -> RtdConfig:
+    """the rtd_config of `arch` with plain defaults for everything else (tests, tools)"""
+    return make_config(arch, device, precision, max_batch, input_size, use_graph, profile)
 
 
 class Engine(Handle):

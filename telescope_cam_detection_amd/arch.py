@@ -11,7 +11,9 @@ the HIP engine and drives the weight recipe / packer (weights.py) and the CPU or
 """
 from __future__ import annotations
 
-from dataclasses import dataclass, field
+import os
+import re
+from dataclasses import dataclass, field, replace
 from typing import List, Tuple
 
 
@@ -39,6 +41,9 @@ class Arch:
     n_points: int = 4
     offset_scale: float = 0.5
     feat_strides: Tuple[int, int, int] = (8, 16, 32)
+    # cross-attention sampler (upstream `cross_attn_method`, HF `decoder_method`, :44-115): "default" = zero-padded bilinear grid_sample,
+    # "discrete" = one clamped nearest tap per point (the "dsp" checkpoints).  Same weight shapes either way.
+    dec_method: str = "default"
 
     @property
     def backbone_out_channels(self) -> Tuple[int, int, int]:
@@ -82,16 +87,45 @@ ARCHS = {
                   enc_dim=64, enc_ffn=128, enc_heads=2, d_model=64, dec_ffn=128, dec_heads=2,
                   dec_layers=2, num_queries=50, expansion=0.5),
 }
+# the discrete-sampling ("dsp") twins, e.g. upstream's rtdetrv2_r18vd_dsp_3x_coco.yml: the same graph and weight shapes, another sampler.
+# They come AFTER the plain entries: a checkpoint's shapes cannot tell the two apart and checkpoint.guess_arch takes the first fit.
+DSP_SUFFIX = "_dsp"
+ARCHS.update({n + DSP_SUFFIX: replace(ARCHS[n], name=n + DSP_SUFFIX, dec_method="discrete") for n in ("r18", "r34", "r50", "r101", "tinyc")})
+
+
+def same_weights(a: Arch, b: Arch) -> bool:
+    """the two variants read the same checkpoint: they differ in nothing but the name and the sampler"""
+    return replace(a, name="", dec_method="default") == replace(b, name="", dec_method="default")
+
+
+_DISCRETE_LINE = re.compile(r"^\s*cross_attn_method\s*:\s*[\"']?discrete[\"']?\s*(#.*)?$", re.MULTILINE)
+
+
+def _config_is_discrete(config_path: str) -> bool:
+    """upstream's dsp configs set `cross_attn_method: discrete` on the decoder and carry the tag `dsp` in their file name.  The YAML
+    decides when it can be read (a plain text scan: no include is followed); otherwise the name does, `dsp` being one of its
+    `_`-delimited tokens (rtdetrv2_r18vd_dsp_3x_coco.yml) - never a part of another word."""
+    try:
+        if os.path.isfile(config_path):
+            with open(config_path, "r", errors="replace") as fh:
+                if _DISCRETE_LINE.search(fh.read()):
+                    return True
+    except OSError:
+        pass
+    stem = os.path.basename(str(config_path)).lower().split(".")[0]
+    return "dsp" in stem.split("_")
 
 
 def arch_from_config_path(config_path: str) -> Arch:
     """Map the reference's `config_path` argument (src/rtdetr_detector.py:31) to a variant.
 
     The reference passes e.g. "RT-DETR/rtdetrv2_pytorch/configs/rtdetrv2/rtdetrv2_r18vd_120e_coco.yml";
-    upstream's file names carry the backbone tag, which is all this build needs from the YAML.
+    upstream's file names carry the backbone tag; beside it this build needs the decoder's sampler (`_config_is_discrete`).
     """
     s = str(config_path).lower()
     for tag in ("r101", "r50", "r34", "r18", "tinyc", "tinyb", "tiny"):
         if tag in s:
+            if tag + DSP_SUFFIX in ARCHS and _config_is_discrete(str(config_path)):
+                return ARCHS[tag + DSP_SUFFIX]
             return ARCHS[tag]
     raise ValueError(f"cannot infer RT-DETR variant from config_path={config_path!r}")

@@ -24,6 +24,7 @@ enum DType : int { BF16 = 0, F32 = 1, U8 = 2, I32 = 3, F16X2 = 4 };
 constexpr int SPLIT_GROUP = 32;   // channels per [hi | lo] group of a F16X2 tensor
 enum Act : int { ACT_NONE = 0, ACT_RELU = 1, ACT_SILU = 2, ACT_GELU = 3, ACT_LRELU = 4 /* v >= 0 ? v : 0.2 v (RRDBNet) */ };
 enum ResMode : int { RES_NONE = 0, RES_PRE = 1, RES_POST = 2 };
+enum DecMethod : int { DEC_DEFAULT = 0, DEC_DISCRETE = 1 };   // rtd_config.dec_method (RTD_DEC_*): the cross-attention sampler
 
 inline size_t dtype_size(int dt) { return dt == BF16 ? 2 : (dt == U8 ? 1 : 4); }
 
@@ -56,6 +57,28 @@ struct Tensor {
     return t;
   }
 };
+
+// The tap of RT-DETRv2's discrete cross attention (cross_attn_method: discrete; HF:v2.py multi_scale_deformable_attention_v2, method ==
+// "discrete", and the module above it) along one axis, in the order and rounding torch applies op by op in fp32:
+//   off = ((offset * (1 / n_points)) * ref_wh) * offset_scale;  loc = ref + off;  c = int(loc * extent + 0.5) clamped to [0, extent - 1].
+// Every product and sum must be rounded on its own: a fused loc * extent + 0.5 picks another tap at a rounding boundary (c an integer
+// op by op, just below it fused).  hipcc's default -ffp-contract=fast-honor-pragmas fuses a * b + c into v_fma_f32 across statements,
+// and __fmul_rn / __fadd_rn do not prevent it: in this toolchain they are inline header functions that return x * y and x + y
+// (unless OCML_BASIC_ROUNDED_OPERATIONS is defined), whose operations keep the contract flag wherever they are inlined - a pragma here
+// does not reach into them.  So the arithmetic is written with plain operators INSIDE this function under `fp contract(off)`, which
+// clears the flag of exactly these operations and survives inlining into the kernels.  Checked in the ISA of dec_layer_kernel<., 1>
+// and k_msdeform_discrete: three v_mul_f32, v_add_f32, v_mul_f32, v_add_f32, v_max, v_min feed every v_cvt_i32_f32; no v_fma / v_fmac.
+// The clamp runs in float BEFORE the conversion - masked-anchor boxes (ref = 1) with large offsets lie far outside and a NaN becomes
+// tap 0; for an integer bound, min(trunc(c), extent - 1) == trunc(min(c, extent - 1)) and truncation toward zero sends every c in
+// (-1, 0) to 0, which the lower clamp does too.  The fused decoder kernel and k_msdeform_discrete both call this, so the same inputs
+// give the same taps on both decoder paths.
+__device__ __forceinline__ int discrete_tap(float ref, float offset, float pscale, float wh, float offset_scale, int extent) {
+#pragma clang fp contract(off)
+  const float off = ((offset * pscale) * wh) * offset_scale;
+  const float loc = ref + off;
+  const float c = loc * (float)extent + 0.5f;
+  return (int)fminf(fmaxf(c, 0.f), (float)(extent - 1));
+}
 
 // every pointer on a 16-byte boundary (what the kernels' 16-byte vector accesses and buffer loads need of a tensor's base)
 template <typename... P>
@@ -231,9 +254,10 @@ void launch_gather_rows(const Tensor& src, const int32_t* idx, int rows_per_imag
 // dst[b,q,0:4] = src[b, idx[b,q], 0:4] + anchors[idx[b,q]] ; dst rows are 8 floats (4..7 = 0)
 void launch_ref_init(const Tensor& boxdelta, const float* anchors, const int32_t* idx, int S, float* ref_unact8,
                      float* ref8, hipStream_t s);
+// method: DEC_DEFAULT = zero-padded bilinear grid_sample, DEC_DISCRETE = one clamped nearest tap per point (discrete_tap below)
 void launch_msdeform(const Tensor& value, int value_coff, const Tensor& offaw, const float* ref8, const Tensor& out,
                      int heads, int hd, int n_levels, int n_points, const int32_t* level_hw_start, float offset_scale,
-                     hipStream_t s);
+                     int method, hipStream_t s);
 void launch_box_refine(const Tensor& delta, float* ref8, hipStream_t s);
 void launch_postprocess_scores(const Tensor& logits, float* scores, hipStream_t s);
 // the post-processor in one launch, for the shapes postprocess_fused_supported accepts (anything else throws)
@@ -291,6 +315,7 @@ struct DecArgs {
   int split;                // 1 (bf16 / f16x3 engines): the linear layers run as 3 fp16 MFMAs on hi/lo splits of both operands; 0 (fp32 engine): exact fp32 MFMAs
   int B, Q, D, heads, S, n_levels, n_points, ffn, C;
   float offset_scale;
+  int method;               // DEC_DEFAULT | DEC_DISCRETE: the cross-attention sampler (modes 1 and 2)
   // per-row state (global, fp32)
   // self-attention inputs of this layer (written by the previous launch): q rows + K / V in MFMA-fragment order
   const float* q_in;        // [B*Q, D]

@@ -367,6 +367,67 @@ __device__ void sample_rows(const DecArgs& a, const float* sO, int LDO, const fl
 }
 
 
+// The discrete sampler (cross_attn_method: discrete, HF:v2.py method "discrete"): one clamped nearest tap per sampling point instead
+// of four zero-padded bilinear ones.  Same item-to-lane mapping as sample_rows (4 lanes per (row, head) item, 8 channels each).  The
+// 12 row offsets of an item are computed first (discrete_tap, the helper k_msdeform_discrete calls too), then all 12 taps' 16-byte
+// loads are issued before the first FMA: 12 (bf16) / 24 (fp32) loads in flight per lane where the bilinear sampler has 16 / 32 per
+// level and three dependent rounds of them.
+template <typename TV>
+__device__ void sample_rows_discrete(const DecArgs& a, const float* sO, int LDO, const float* sR, int LDR, float* sA, int LDH, int b,
+                                     int nvalid, int tid) {
+  constexpr int NL = 3, NP = 4, LP = NL * NP;
+  constexpr int V = 16 / (int)sizeof(TV);                      // channels per 16-byte load: 8 (bf16) / 4 (fp32)
+  typedef TV VT __attribute__((ext_vector_type(V)));
+  const int c8 = tid & 3;
+  const float pscale = 1.f / (float)NP;
+  for (int item = tid >> 2; item < DR * a.heads; item += NT / 4) {
+    const int r = item / a.heads, head = item - r * a.heads;
+    float acc[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) acc[k] = 0.f;
+    if (r < nvalid) {
+      const float* offs = sO + r * LDO + head * LP * 2;
+      const float* awl = sO + r * LDO + a.heads * LP * 2 + head * LP;
+      float lg[LP];
+      float mx = -INFINITY;
+#pragma unroll
+      for (int i = 0; i < LP; ++i) { lg[i] = awl[i]; mx = fmaxf(mx, lg[i]); }
+      float den = 0.f;
+#pragma unroll
+      for (int i = 0; i < LP; ++i) { lg[i] = __expf(lg[i] - mx); den += lg[i]; }
+      const float inv_den = 1.f / den;
+      const float rx = sR[r * LDR + 0], ry = sR[r * LDR + 1], rw = sR[r * LDR + 2], rh = sR[r * LDR + 3];
+      const TV* vb = (const TV*)a.value + (long long)b * a.S * a.value_ld + a.value_coff + head * 32 + c8 * 8;
+      int of[LP];
+#pragma unroll
+      for (int l = 0; l < NL; ++l) {
+        const int H = a.lvl[l * 3 + 0], W = a.lvl[l * 3 + 1], start = a.lvl[l * 3 + 2];
+#pragma unroll
+        for (int p = 0; p < NP; ++p) {
+          const int i = l * NP + p;
+          const int cx = discrete_tap(rx, offs[i * 2 + 0], pscale, rw, a.offset_scale, W);     // in [0, W - 1]
+          const int cy = discrete_tap(ry, offs[i * 2 + 1], pscale, rh, a.offset_scale, H);     // in [0, H - 1]
+          of[i] = (start + cy * W + cx) * a.value_ld;
+        }
+      }
+      VT vv[LP][8 / V];
+#pragma unroll
+      for (int t = 0; t < LP; ++t)
+#pragma unroll
+        for (int u = 0; u < 8 / V; ++u) vv[t][u] = *(const VT*)(vb + of[t] + u * V);
+#pragma unroll
+      for (int t = 0; t < LP; ++t) {
+        const float aw = lg[t] * inv_den;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) acc[k] = fmaf((float)vv[t][k / V][k % V], aw, acc[k]);
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) sA[r * LDH + head * 32 + c8 * 8 + k] = acc[k];
+  }
+}
+
+
 // Self-attention of the block's 16 query rows (HF:v2.py:246-336, no mask), one head per wave, exact fp32 MFMA.
 // Computed TRANSPOSED so nothing crosses LDS: per 16-key tile  S^T = K Q^T  (keys on accumulator rows, the
 // lane's query on the column), so the softmax reductions over keys are 4 registers + two xor-shuffles (16, 32),
@@ -559,7 +620,9 @@ __device__ __forceinline__ void touch_weights(const DecLin& L, int part, int npa
 // struct is copied to scratch at kernel entry: round 4 read that as register spilling ("256 registers + 704 B of scratch"); it is an
 // inlining artefact, and __forceinline__ on the phase functions removes it.  They are NOT force-inlined in this build: with the attribute
 // hipcc schedules the same code 2.5 % slower (0.770 vs 0.747 ms per step for the nine launches, same box, round 5).)
-template <int SPLIT>
+// DISCRETE = 1: the cross attention samples with sample_rows_discrete (DecArgs::method == DEC_DISCRETE).  A template argument, not a
+// branch on the argument: the kernels of the default sampler stay the code they were.
+template <int SPLIT, int DISCRETE>
 __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
   // LDS (floats).  Row strides are (cols + 4): ds_read_b128 of 16 rows x 4 k-groups is conflict-free.
   constexpr int LDH = 260, LDF = 1028, LDQ = 516, LDO = 292, LDR = 68;
@@ -675,8 +738,13 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
     linear(ACT_NONE, {sA, LDH}, a.offaw, {sO, LDO}, false, a.fc1);
     __syncthreads();
     // ---- MS-deformable sampling (HF:v2.py:44-115,203-221): 32 lanes = one (row, head) ---------------
-    if (a.value_f32) sample_rows<float>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
-    else sample_rows<bf16>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
+    if (DISCRETE) {
+      if (a.value_f32) sample_rows_discrete<float>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
+      else sample_rows_discrete<bf16>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
+    } else {
+      if (a.value_f32) sample_rows<float>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
+      else sample_rows<bf16>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
+    }
     __syncthreads();
     // ---- output projection + residual + LN2 (HF:v2.py:221,418-421) ----------------------------------
     const LNRegs ln2 = ln_fetch(a.ln2, D, lane);
@@ -953,8 +1021,15 @@ void launch_dec_layer(const DecArgs& a, hipStream_t s) {
   RTD_CHECK(a.D == 256 && a.D / a.heads == 32 && a.ffn <= 1024 && a.C <= 512, 1, "fused decoder: d_model 256, head dim 32, ffn <= 1024");
   RTD_CHECK(a.n_levels == 3 && a.n_points == 4 && a.heads == NW, 1, "fused decoder: 3 levels x 4 points, one head per wave");
   const int tiles = (a.Q + DR - 1) / DR;
-  if (a.split) rtd_launch(dec_layer_kernel<1>, dim3(a.B * tiles), dim3(NT), 0, s, a);
-  else rtd_launch(dec_layer_kernel<0>, dim3(a.B * tiles), dim3(NT), 0, s, a);
+  RTD_CHECK(a.method == DEC_DEFAULT || a.method == DEC_DISCRETE, 1, "fused decoder: unknown sampling method");
+  const dim3 grid(a.B * tiles), blk(NT);
+  if (a.method == DEC_DISCRETE) {
+    if (a.split) rtd_launch((dec_layer_kernel<1, 1>), grid, blk, 0, s, a);
+    else rtd_launch((dec_layer_kernel<0, 1>), grid, blk, 0, s, a);
+  } else {
+    if (a.split) rtd_launch((dec_layer_kernel<1, 0>), grid, blk, 0, s, a);
+    else rtd_launch((dec_layer_kernel<0, 0>), grid, blk, 0, s, a);
+  }
   HIP_CHECK(hipGetLastError());
 }
 

@@ -947,7 +947,7 @@ Tensor Builder::decoder_fused(Flow& F, const Queries& q, const Tensor& vall, flo
   base.split = P != F32;
   base.attn_split = (e->opts.attn_split >> 1) & 1;
   base.B = n; base.Q = Q; base.D = dm; base.heads = c.dec_heads; base.S = S; base.n_levels = c.n_levels;
-  base.n_points = c.n_points; base.ffn = c.dec_ffn; base.C = C; base.offset_scale = c.offset_scale;
+  base.n_points = c.n_points; base.ffn = c.dec_ffn; base.C = C; base.offset_scale = c.offset_scale; base.method = c.dec_method;
   base.ref8 = ref8; base.ref_unact8 = ref_unact8; base.anchors = e->anchors_dev; base.tk_idx = q.tk;
   base.value = vall.p; base.value_ld = (int)vall.ld; base.value_f32 = vall.dt == F32; base.lvl = e->lvl_dev;
   base.qpos_in = (const float*)qpos.p; base.qpos_out = (float*)qpos.p;
@@ -989,7 +989,7 @@ Tensor Builder::decoder_fused(Flow& F, const Queries& q, const Tensor& vall, flo
     if (last) a.cls = dec_lin("dec.cls", C, dm);
     else { a.qk = dec_lin(nm("dec.l%d.sa.qk", i + 1), 2 * dm, dm); a.v = dec_lin(nm("dec.l%d.sa.v", i + 1), dm, dm); }
     const double fl = 4.0 * n * (double)Q * Q * dm + 2.0 * n * Q * ((double)dm * dm * 2 + 3.0 * npts * dm + 2.0 * dm * c.dec_ffn + 2.0 * dm * dm + 4.0 * dm) +
-                      2.0 * n * Q * dm * c.n_levels * c.n_points * 4 + (last ? 2.0 * n * Q * dm * C : row_flops_next);
+                      2.0 * n * Q * dm * c.n_levels * c.n_points * (c.dec_method == RTD_DEC_DISCRETE ? 1 : 4) + (last ? 2.0 * n * Q * dm * C : row_flops_next);
     push(p + ".fused", "dec_layer", fl, (double)n * Q * dm * 4 * 8, [a](hipStream_t s) { launch_dec_layer(a, s); });
     hs = hs_out;
   }
@@ -1004,7 +1004,7 @@ Tensor Builder::decoder_by_op(const Queries& q, const Tensor& vall, const Tensor
   Tensor b0 = linear("dec.enc_bbox.0", q.target, dm, F32, ACT_RELU);
   Tensor b1 = linear("dec.enc_bbox.1", b0, dm, F32, ACT_RELU);
   Tensor b2 = linear("dec.enc_bbox.2", b1, 4, F32, ACT_NONE);
-  const float* anchors = e->anchors_dev; const int32_t* lvl = e->lvl_dev; const float osc = c.offset_scale;
+  const float* anchors = e->anchors_dev; const int32_t* lvl = e->lvl_dev; const float osc = c.offset_scale; const int method = c.dec_method;
   const int heads = c.dec_heads, hd = dm / c.dec_heads, nl = c.n_levels, np = c.n_points;
   push("dec.ref_init", "ref_init", 0.0, (double)n * Q * 64, [b2, anchors, tk, S, ref_unact8, ref8](hipStream_t s) { launch_ref_init(b2, anchors, tk, S, ref_unact8, ref8, s); });
   Tensor hs = q.target;
@@ -1026,8 +1026,9 @@ Tensor Builder::decoder_by_op(const Queries& q, const Tensor& vall, const Tensor
     Tensor offaw = linear(p + ".ca.offaw", hp2, 3 * npts, F32, ACT_NONE);
     Tensor samp = act(F32, n, Q, 1, dm);
     const int coff = i * dm;
-    push(p + ".ca.sample", "msdeform", 2.0 * n * Q * dm * nl * np * 4, (double)n * Q * heads * nl * np * 4 * hd * dtype_size(P),
-         [vall, coff, offaw, ref8, samp, heads, hd, nl, np, lvl, osc](hipStream_t s) { launch_msdeform(vall, coff, offaw, ref8, samp, heads, hd, nl, np, lvl, osc, s); });
+    const int taps = method == DEC_DISCRETE ? 1 : 4;                         // value rows read per sampling point
+    push(p + ".ca.sample", "msdeform", 2.0 * n * Q * dm * nl * np * taps, (double)n * Q * heads * nl * np * taps * hd * dtype_size(P),
+         [vall, coff, offaw, ref8, samp, heads, hd, nl, np, lvl, osc, method](hipStream_t s) { launch_msdeform(vall, coff, offaw, ref8, samp, heads, hd, nl, np, lvl, osc, method, s); });
     Tensor co = linear(p + ".ca.op", samp, dm, F32, ACT_NONE, &hs1);
     Tensor hs2 = layernorm(p + ".ln2", co, F32);
     Tensor g1 = linear(p + ".fc1", hs2, c.dec_ffn, F32, ACT_RELU);
@@ -1332,6 +1333,10 @@ int rtd_create(const rtd_config* cfg, rtd_handle* out) {
     for (int i = 0; i < 4; ++i) RTD_CHECK(cfg->depths[i] >= 1 && cfg->hidden_sizes[i] % 32 == 0, RTD_E_INVALID, "stage config");
     RTD_CHECK(cfg->num_queries >= 1 && cfg->num_queries <= 1024 && cfg->num_classes % 4 == 0, RTD_E_INVALID, "num_queries <= 1024, num_classes % 4 == 0");
     RTD_CHECK((cfg->dec_heads * cfg->n_levels * cfg->n_points * 3) % 4 == 0, RTD_E_INVALID, "sampling head width");
+    RTD_CHECK(cfg->dec_method == RTD_DEC_DEFAULT || cfg->dec_method == RTD_DEC_DISCRETE, RTD_E_INVALID, "dec_method must be RTD_DEC_DEFAULT or RTD_DEC_DISCRETE");
+    // a bf16 sampling offset carries 2^-9 relative: at a map 80 wide that moves the nearest tap of a large share of the points
+    RTD_CHECK(!(cfg->dec_method == RTD_DEC_DISCRETE && cfg->precision == RTD_PREC_BF16), RTD_E_INVALID,
+              "precision bf16 is refused with the discrete sampler (dec_method = RTD_DEC_DISCRETE): bf16 offsets move the taps; use f16x3 or fp32");
     e->cfg = *cfg;
     e->device = cfg->device;
     e->opts = g_opts;

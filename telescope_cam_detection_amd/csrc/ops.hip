@@ -1105,9 +1105,50 @@ __global__ __launch_bounds__(256) void k_msdeform(const TV* __restrict__ value, 
   }
   out[bq * ldo + head * 32 + ch] = (TO)acc;
 }
+// HF:v2.py method "discrete" (cross_attn_method: discrete, the dsp checkpoints): the same softmax and locations, but each sampling
+// point reads ONE value row - the tap discrete_tap() names, clamped into the map - instead of four zero-padded bilinear ones.
+// Same item-to-lane mapping as k_msdeform; any n_levels / n_points.
+template <typename TV, typename TO>
+__global__ __launch_bounds__(256) void k_msdeform_discrete(const TV* __restrict__ value, int64_t ldv, int64_t v_bstride,
+                                                            const float* __restrict__ offaw, int64_t ldoa,
+                                                            const float* __restrict__ ref8, TO* __restrict__ out, int64_t ldo,
+                                                            int Q, int heads, int n_levels, int n_points,
+                                                            const int32_t* __restrict__ lvl, float offset_scale, int64_t items) {
+  const int64_t item = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);   // (b, q, head)
+  const int ch = threadIdx.x & 31;
+  if (item >= items) return;
+  const int head = (int)(item % heads);
+  const int64_t bq = item / heads;
+  const int b = (int)(bq / Q);
+  const int LP = n_levels * n_points;
+  const float* oa = offaw + bq * ldoa;
+  const float* offs = oa + (int64_t)head * LP * 2;
+  const float* awl = oa + (int64_t)heads * LP * 2 + (int64_t)head * LP;
+  float mx = -INFINITY;
+  for (int i = 0; i < LP; ++i) mx = fmaxf(mx, awl[i]);
+  float den = 0.f;
+  for (int i = 0; i < LP; ++i) den += __expf(awl[i] - mx);
+  const float inv_den = 1.f / den;
+  const float rx = ref8[bq * 8 + 0], ry = ref8[bq * 8 + 1], rw = ref8[bq * 8 + 2], rh = ref8[bq * 8 + 3];
+  const float pscale = 1.f / (float)n_points;
+  const TV* vb = value + (int64_t)b * v_bstride + head * 32 + ch;
+  float acc = 0.f;
+  for (int l = 0; l < n_levels; ++l) {
+    const int H = lvl[l * 3 + 0], W = lvl[l * 3 + 1], start = lvl[l * 3 + 2];
+    for (int p = 0; p < n_points; ++p) {
+      const int i = l * n_points + p;
+      const float aw = __expf(awl[i] - mx) * inv_den;
+      const int cx = discrete_tap(rx, offs[i * 2 + 0], pscale, rw, offset_scale, W);     // in [0, W - 1]
+      const int cy = discrete_tap(ry, offs[i * 2 + 1], pscale, rh, offset_scale, H);     // in [0, H - 1]
+      acc += (float)vb[(int64_t)(start + cy * W + cx) * ldv] * aw;
+    }
+  }
+  out[bq * ldo + head * 32 + ch] = (TO)acc;
+}
 void launch_msdeform(const Tensor& value, int value_coff, const Tensor& offaw, const float* ref8, const Tensor& out, int heads,
-                     int hd, int n_levels, int n_points, const int32_t* level_hw_start, float offset_scale, hipStream_t s) {
+                     int hd, int n_levels, int n_points, const int32_t* level_hw_start, float offset_scale, int method, hipStream_t s) {
   RTD_CHECK(hd == 32, 1, "msdeform: head dim must be 32");
+  RTD_CHECK(method == DEC_DEFAULT || method == DEC_DISCRETE, 1, "msdeform: unknown sampling method");
   RTD_CHECK(offaw.dt == F32 && offaw.c == heads * n_levels * n_points * 3, 1, "msdeform: offsets|weights layout");
   RTD_CHECK(out.c == heads * hd && out.pixels() == offaw.pixels(), 1, "msdeform: output shape");
   const int B = out.n, Q = out.h * out.w;
@@ -1116,8 +1157,12 @@ void launch_msdeform(const Tensor& value, int value_coff, const Tensor& offaw, c
   const char* vp = (const char*)value.p + (size_t)value_coff * dtype_size(value.dt);
   with_dtype(value.dt, [&](auto tv) { with_dtype(out.dt, [&](auto to) {
     typedef type_of<decltype(tv)> TV; typedef type_of<decltype(to)> TO;
-    rtd_launch((k_msdeform<TV, TO>), grid, blk, 0, s, (const TV*)vp, value.ld, value.bstride, (const float*)offaw.p, offaw.ld, ref8, (TO*)out.p, out.ld, Q,
-               heads, n_levels, n_points, level_hw_start, offset_scale, items);
+    if (method == DEC_DISCRETE)
+      rtd_launch((k_msdeform_discrete<TV, TO>), grid, blk, 0, s, (const TV*)vp, value.ld, value.bstride, (const float*)offaw.p, offaw.ld, ref8, (TO*)out.p,
+                 out.ld, Q, heads, n_levels, n_points, level_hw_start, offset_scale, items);
+    else
+      rtd_launch((k_msdeform<TV, TO>), grid, blk, 0, s, (const TV*)vp, value.ld, value.bstride, (const float*)offaw.p, offaw.ld, ref8, (TO*)out.p, out.ld, Q,
+                 heads, n_levels, n_points, level_hw_start, offset_scale, items);
   }); });
   HIP_CHECK(hipGetLastError());
 }

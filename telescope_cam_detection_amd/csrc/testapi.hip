@@ -463,7 +463,7 @@ int rtd_op_attention(int dtype, const void* qk, const void* v, void* o, int B, i
 // the body both msdeform entry points share (each keeps its own argument checks): the level table [n_levels][3] h, w, start on the
 // device, the reference boxes widened to 8-float rows, the launch
 static void op_msdeform_body(int dtype, const void* value, int value_ld, int value_coff, const float* offaw, const float* ref, float* out, int B, int Q,
-                             int heads, int hd, int n_levels, int n_points, const int32_t* level_hw, float offset_scale) {
+                             int heads, int hd, int n_levels, int n_points, const int32_t* level_hw, float offset_scale, int method) {
   int32_t lv[24]; int S = 0;
   for (int l = 0; l < n_levels; ++l) { lv[l * 3] = level_hw[2 * l]; lv[l * 3 + 1] = level_hw[2 * l + 1]; lv[l * 3 + 2] = S; S += level_hw[2 * l] * level_hw[2 * l + 1]; }
   OpScratch sc;
@@ -471,7 +471,7 @@ static void op_msdeform_body(int dtype, const void* value, int value_ld, int val
   float* ref8 = sc.zeros<float>((size_t)B * Q * 8);
   HIP_CHECK(hipMemcpy2D(ref8, 32, ref, 16, 16, (size_t)B * Q, hipMemcpyDeviceToDevice));
   launch_msdeform(rows_view(value, dtype, B, S, heads * hd, value_ld), value_coff, mk(offaw, F32, B, Q, 1, heads * n_levels * n_points * 3), ref8,
-                  mk(out, F32, B, Q, 1, heads * hd), heads, hd, n_levels, n_points, lvd, offset_scale, nullptr);
+                  mk(out, F32, B, Q, 1, heads * hd), heads, hd, n_levels, n_points, lvd, offset_scale, method, nullptr);
   HIP_CHECK(hipDeviceSynchronize());
 }
 
@@ -479,20 +479,31 @@ int rtd_op_msdeform(int dtype, const void* value, const float* offaw, const floa
                     int n_levels, int n_points, const int32_t* level_hw, int value_ld, float offset_scale) {
   return op_guard([&] {
     RTD_CHECK(n_levels >= 1 && n_levels <= 8, RTD_E_INVALID, "n_levels");
-    op_msdeform_body(dtype, value, value_ld, 0, offaw, ref, out, B, Q, heads, hd, n_levels, n_points, level_hw, offset_scale);
+    op_msdeform_body(dtype, value, value_ld, 0, offaw, ref, out, B, Q, heads, hd, n_levels, n_points, level_hw, offset_scale, DEC_DEFAULT);
   });
 }
 
-int rtd_op_msdeform_view(int dtype, const void* value, int value_ld, int value_coff, const float* offaw, const float* ref, float* out, int B, int Q,
-                         int heads, int hd, int n_levels, int n_points, const int32_t* level_hw, float offset_scale) {
+// both view entry points: the argument checks, then the shared body with the sampler of `method`
+static int op_msdeform_view(int method, int dtype, const void* value, int value_ld, int value_coff, const float* offaw, const float* ref, float* out,
+                            int B, int Q, int heads, int hd, int n_levels, int n_points, const int32_t* level_hw, float offset_scale) {
   return op_guard([&] {
     RTD_CHECK(value && offaw && ref && out && level_hw && rows_fit_int(B, Q), RTD_E_INVALID, "msdeform view: arguments");
     RTD_CHECK(hd == 32 && heads >= 1, RTD_E_INVALID, "msdeform view: head dim must be 32");
     RTD_CHECK(n_levels >= 1 && n_levels <= 8 && n_points >= 1, RTD_E_INVALID, "msdeform view: 1..8 levels");
     RTD_CHECK(value_coff >= 0 && value_coff + heads * hd <= value_ld, RTD_E_INVALID, "msdeform view: the channel slice leaves the value row");
     for (int l = 0; l < n_levels; ++l) RTD_CHECK(level_hw[2 * l] >= 1 && level_hw[2 * l + 1] >= 1, RTD_E_INVALID, "msdeform view: level extents");
-    op_msdeform_body(dtype, value, value_ld, value_coff, offaw, ref, out, B, Q, heads, hd, n_levels, n_points, level_hw, offset_scale);
+    op_msdeform_body(dtype, value, value_ld, value_coff, offaw, ref, out, B, Q, heads, hd, n_levels, n_points, level_hw, offset_scale, method);
   });
+}
+
+int rtd_op_msdeform_view(int dtype, const void* value, int value_ld, int value_coff, const float* offaw, const float* ref, float* out, int B, int Q,
+                         int heads, int hd, int n_levels, int n_points, const int32_t* level_hw, float offset_scale) {
+  return op_msdeform_view(DEC_DEFAULT, dtype, value, value_ld, value_coff, offaw, ref, out, B, Q, heads, hd, n_levels, n_points, level_hw, offset_scale);
+}
+
+int rtd_op_msdeform_discrete_view(int dtype, const void* value, int value_ld, int value_coff, const float* offaw, const float* ref, float* out, int B,
+                                  int Q, int heads, int hd, int n_levels, int n_points, const int32_t* level_hw, float offset_scale) {
+  return op_msdeform_view(DEC_DISCRETE, dtype, value, value_ld, value_coff, offaw, ref, out, B, Q, heads, hd, n_levels, n_points, level_hw, offset_scale);
 }
 
 int rtd_op_select_score(const float* x, int ldx, const float* w_f32, const float* bias, const float* g, const float* b, float* mx, int B, int S,

@@ -17,7 +17,7 @@ from typing import Any, Dict, List, Optional, Union
 import numpy as np
 
 from . import _capi
-from .arch import ARCHS, Arch, arch_from_config_path
+from .arch import ARCHS, Arch, arch_from_config_path, same_weights
 from .coco_constants import COCO_CLASSES, MAMMAL_CLASS_IDS, WILDLIFE_CLASSES
 from .weights import fold_weights, pack_blob, synth_weights
 
@@ -151,6 +151,11 @@ class RTDETRDetector:
                     engine.close()                            # a retry must not find this attempt's weights, arenas and graphs still resident
                     raise
             except (RuntimeError, OSError) as e:              # the reference retries this set (:190-198); IOError is OSError
+                if isinstance(e, _capi.RtdError) and e.code == _capi.RTD_E_INVALID:
+                    # a configuration the library refuses (bf16 with the discrete sampler, an input size that is no multiple of 32 ...)
+                    # is refused the same way on every attempt: no pause, no retry
+                    logger.error("RT-DETR (MI355X): cannot build the engine for %s: %s", self.config_path, e)
+                    return False
                 if k + 1 == tries:
                     logger.error("RT-DETR (MI355X): giving up on %s after %d attempt(s): %s", self.model_path, tries, e, exc_info=True)
                     return False
@@ -166,9 +171,9 @@ class RTDETRDetector:
             self._engine_input_size = tuple(self.input_size)
             self.model = _DeviceModel(engine, self.device)
             logger.info("RT-DETR (MI355X): %s engine for %s on %s ready in %.1f s - weights %s, input %dx%d, up to %d frames per call, "
-                        "%s arithmetic, score threshold %.2f, 80 COCO classes", arch.name, self.config_path, self.device,
+                        "%s arithmetic, %s cross-attention sampler, score threshold %.2f, 80 COCO classes", arch.name, self.config_path, self.device,
                         time.perf_counter() - t0, self.model_path, self.input_size[0], self.input_size[1], self.max_batch, self.precision,
-                        self.conf_threshold)
+                        "discrete (one clamped tap per point)" if arch.dec_method == "discrete" else "bilinear", self.conf_threshold)
             return True
         return False
 
@@ -194,7 +199,10 @@ class RTDETRDetector:
 
         def make_state():
             state, arch_name = load_state(self.model_path)
-            if arch_name and arch_name != arch.name:          # the file knows better than the config's name (the precedence this class always had)
+            # the file knows better than the config's name (the precedence this class always had) - but not which SAMPLER it was trained
+            # with: a checkpoint that fits the plain variant of a discrete ("dsp") config is that config's checkpoint
+            dsp_of_file = arch.dec_method != "default" and ARCHS[arch_name].dec_method == "default" and same_weights(ARCHS[arch_name], arch) if arch_name else False
+            if arch_name and arch_name != arch.name and not dsp_of_file:
                 other["state"], other["arch"] = state, ARCHS[arch_name]
                 raise LookupError(arch_name)
             return state

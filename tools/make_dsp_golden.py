@@ -1,0 +1,155 @@
+"""Generate the discrete-sampling ("dsp") fixtures tests/golden/d*.npz and tests/golden/dsp_yardstick.json by running HuggingFace
+transformers' RT-DETRv2 with decoder_method="discrete" on the CPU.
+
+    python tools/make_dsp_golden.py            write the fixtures
+    python tools/make_dsp_golden.py --check    recompute them and compare every array with the committed files, exactly
+
+Modelled on oracle/make_golden.py and reusing it: its run_case() writes the file (same keys as the c* / t* fixtures) and asserts, before
+it does, that the restatement agrees with HF per selected token (1e-4 logits, 1e-5 boxes).  Two things are swapped in for the run: the
+model builder (make_golden's build_hf takes no method, so its config call is restated here with decoder_method) and the oracle's
+sampler (tests.dsp_ref.discrete_oracle).  Only data is stored.
+"""
+from __future__ import annotations
+
+import json
+import os
+import sys
+import tempfile
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from oracle import make_golden as mg  # noqa: E402
+from oracle import rtdetr_oracle as orc  # noqa: E402
+from telescope_cam_detection_amd.arch import ARCHS  # noqa: E402
+from telescope_cam_detection_amd.checkpoint import hf_key_map  # noqa: E402
+from telescope_cam_detection_amd.synth import make_frame  # noqa: E402
+from telescope_cam_detection_amd.weights import synth_weights  # noqa: E402
+from tests.dsp_ref import discrete_oracle  # noqa: E402
+from tests.util import match_detections  # noqa: E402
+
+# name -> (arch, weight seed, input_size (H, W), [(frame seed, frame H, frame W)], frame kind): the layout of make_golden.CASES
+DSP_CASES = {
+    # d_model 256, 8 heads, 3 x 4 taps: the fused decoder kernel; 20 x 28 + 10 x 14 + 5 x 7 = 735 memory tokens >= 300 queries; the second
+    # frame goes through the resampler
+    "d1_r18dsp_160x224": ("r18_dsp", 0, (160, 224), [(6000, 160, 224), (6001, 200, 150)], "scene"),
+    # d_model 64, 2 heads: the per-op decoder (k_msdeform_discrete); the frames of t_tinyc_160x224
+    "d2_tinycdsp_160x224": ("tinyc_dsp", 3, (160, 224), [(4006, 160, 224), (4007, 200, 150)], "scene"),
+}
+YARDSTICK = "dsp_yardstick.json"
+
+
+def build_hf_with_method(arch, w):
+    """make_golden.build_hf with the decoder's sampler taken from arch.dec_method"""
+    from transformers import RTDetrV2Config, RTDetrV2ForObjectDetection
+    from transformers.models.rt_detr.configuration_rt_detr_resnet import RTDetrResNetConfig
+
+    bb = RTDetrResNetConfig(depths=list(arch.depths), layer_type=arch.layer_type, hidden_sizes=list(arch.hidden_sizes),
+                            embedding_size=arch.embedding_size, out_indices=[2, 3, 4])
+    cfg = RTDetrV2Config(
+        backbone_config=bb, encoder_in_channels=list(arch.backbone_out_channels), encoder_hidden_dim=arch.enc_dim,
+        encoder_ffn_dim=arch.enc_ffn, encoder_attention_heads=arch.enc_heads, hidden_expansion=arch.expansion,
+        d_model=arch.d_model, decoder_in_channels=[arch.enc_dim] * 3, decoder_ffn_dim=arch.dec_ffn,
+        decoder_attention_heads=arch.dec_heads, decoder_layers=arch.dec_layers, num_queries=arch.num_queries,
+        num_labels=arch.num_classes, anchor_image_size=None, eval_size=None, tie_word_embeddings=False,
+        decoder_method=arch.dec_method)
+    cfg._attn_implementation = "eager"
+    model = RTDetrV2ForObjectDetection(cfg).eval()
+    km = hf_key_map(arch)
+    missing, unexpected = model.load_state_dict({hf: w[mine] for mine, hf in km.items()}, strict=False)
+    ok_missing = ("model.decoder.class_embed", "model.decoder.bbox_embed", "model.denoising_class_embed", "n_points_scale", "num_batches_tracked")
+    bad = [k for k in missing if not any(s in k for s in ok_missing)]
+    assert not bad and not unexpected and set(km) == set(w), (bad[:10], unexpected[:10])
+    methods = {m.method for m in model.modules() if hasattr(m, "method") and hasattr(m, "n_points_list")}
+    assert methods == {arch.dec_method}, methods       # every cross-attention module really samples that way
+    return model
+
+
+def write_case(name, out_dir):
+    """the .npz of one case through make_golden.run_case, HF and the restatement both sampling as arch.dec_method says"""
+    saved = mg.build_hf, mg.GOLDEN_DIR
+    mg.CASES[name] = DSP_CASES[name]
+    mg.build_hf, mg.GOLDEN_DIR = build_hf_with_method, out_dir
+    try:
+        with discrete_oracle():
+            mg.run_case(name)
+    finally:
+        mg.build_hf, mg.GOLDEN_DIR = saved
+        del mg.CASES[name]
+
+
+@torch.no_grad()
+def yardstick_of(name, g):
+    """what the tests may ask of an implementation on this case, measured on the restatement itself"""
+    arch_name, wseed, input_size, frames, kind = DSP_CASES[name]
+    arch = ARCHS[arch_name]
+    w = synth_weights(arch, wseed)
+    xs, sizes = [], []
+    for fs, fh, fw in frames:
+        x, wh = orc.preprocess(make_frame(kind, fs, fh, fw), input_size)
+        xs.append(x)
+        sizes.append(wh)
+    x = torch.cat(xs, 0)
+    col, col_default, col64 = {}, {}, {}
+    with discrete_oracle():
+        l32, b32, s32 = orc.model_forward(arch, w, x, sizes, collect=col)
+        # the same restatement in fp64, on the fp32 run's selection (a near-tie at the rank-Q cut must not count as decoder error)
+        w64 = {k: v.double() for k, v in w.items()}
+        l64, b64, s64 = orc.model_forward(arch, w64, x.double(), sizes, collect=col64, force_topk=col["topk"])
+    orc.model_forward(arch, w, x, sizes, collect=col_default)
+    # HF against the restatement, per selected token (query order is decided by near-ties of the encoder scores)
+    so, sh = torch.sort(col["topk"], 1), torch.sort(torch.as_tensor(g["topk"]).long(), 1)
+    assert torch.equal(so.values, sh.values), name
+    gat = lambda t, idx: t.gather(1, idx.unsqueeze(-1).expand(-1, -1, t.shape[-1]))
+    d_logit = (gat(col["logits"], so.indices) - gat(torch.as_tensor(g["logits"]), sh.indices)).abs().max().item()
+    d_box = (gat(col["pred_boxes"], so.indices) - gat(torch.as_tensor(g["pred_boxes"]), sh.indices)).abs().max().item()
+    rows_off = []
+    for i in range(len(frames)):
+        m, n, _, _ = match_detections(l64[i].numpy(), b64[i].numpy(), s64[i].numpy(), l32[i].numpy(), b32[i].numpy(), s32[i].numpy(), 1e-3, 1e-2)
+        rows_off.append(n - m)
+    return {
+        "hf_vs_restatement": {"max_abs_dlogit": d_logit, "max_abs_dbox": d_box},
+        "fp32_vs_fp64_rows_outside_1e-3_1e-2px": rows_off,          # per frame, of the restatement against its fp64 self
+        "default_vs_discrete_max_abs_dlogit": (col["logits"] - col_default["logits"]).abs().max().item(),
+        "default_vs_discrete_max_abs_dbox": (col["pred_boxes"] - col_default["pred_boxes"]).abs().max().item(),
+    }
+
+
+def main(argv):
+    torch.set_num_threads(os.cpu_count())
+    check = "--check" in argv
+    names = [a for a in argv if not a.startswith("--")] or list(DSP_CASES)
+    out_dir = tempfile.mkdtemp() if check else mg.GOLDEN_DIR
+    ys = {}
+    for name in names:
+        write_case(name, out_dir)
+        g = np.load(os.path.join(out_dir, name + ".npz"))
+        if check:
+            ref = np.load(os.path.join(mg.GOLDEN_DIR, name + ".npz"))
+            assert sorted(g.files) == sorted(ref.files), name
+            for k in g.files:
+                assert np.array_equal(g[k], ref[k]), (name, k)
+            print(f"[{name}] {len(g.files)} arrays equal the committed file")
+        ys[name] = yardstick_of(name, g)
+        print(f"[{name}] {json.dumps(ys[name])}")
+    path = os.path.join(mg.GOLDEN_DIR, YARDSTICK)
+    if check:
+        with open(path) as fh:
+            committed = json.load(fh)
+        for name in names:
+            assert committed[name] == ys[name], (name, committed[name], ys[name])
+        print("yardstick equals the committed file")
+    else:
+        if os.path.exists(path) and set(names) != set(DSP_CASES):
+            with open(path) as fh:
+                ys = {**json.load(fh), **ys}
+        with open(path, "w") as fh:
+            json.dump(ys, fh, indent=1, sort_keys=True)
+            fh.write("\n")
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])
