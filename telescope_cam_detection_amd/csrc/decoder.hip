@@ -1018,7 +1018,8 @@ void launch_gather_ln(const float* x, int64_t ldx, int rows_per_image, const int
 }
 
 void launch_dec_layer(const DecArgs& a, hipStream_t s) {
-  RTD_CHECK(a.D == 256 && a.D / a.heads == 32 && a.ffn <= 1024 && a.C <= 512, 1, "fused decoder: d_model 256, head dim 32, ffn <= 1024");
+  RTD_CHECK(a.D == 256 && a.D / a.heads == 32 && a.ffn <= 1024 && a.ffn % 64 == 0 && a.C <= 512, 1,
+            "fused decoder: d_model 256, head dim 32, ffn <= 1024 in 64-wide steps");
   RTD_CHECK(a.n_levels == 3 && a.n_points == 4 && a.heads == NW, 1, "fused decoder: 3 levels x 4 points, one head per wave");
   const int tiles = (a.Q + DR - 1) / DR;
   RTD_CHECK(a.method == DEC_DEFAULT || a.method == DEC_DISCRETE, 1, "fused decoder: unknown sampling method");

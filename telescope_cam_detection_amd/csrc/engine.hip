@@ -524,7 +524,12 @@ struct Builder {
   Tensor aifi_fused(const Tensor& t0), aifi_by_op(const Tensor& t0);
   Tensor csp(const std::string& pfx, const Tensor& cat, const std::string& oname, const Tensor* up_src = nullptr);
   Tensor encoder(Flow& F);
-  bool dec_fused() const { return e->opts.dec_fused && c.d_model == 256 && c.dec_heads == 8 && c.dec_ffn <= 1024 && c.num_classes <= 512 && c.n_levels == 3 && c.n_points == 4; }
+  // (ffn % 64: the row kernel's GEMMs walk K in 64-wide steps and fc1 leaves the hidden columns past ffn unwritten - get_weight_packed
+  // refuses such a K; the per-op path takes any width)
+  bool dec_fused() const {
+    return e->opts.dec_fused && c.d_model == 256 && c.dec_heads == 8 && c.dec_ffn <= 1024 && c.dec_ffn % 64 == 0 && c.num_classes <= 512 &&
+           c.n_levels == 3 && c.n_points == 4;
+  }
   Queries select_queries(Flow& F, const Tensor& mem);
   Decoded decoder(Flow& F, const Tensor& mem, const Queries& q);
   Tensor decoder_fused(Flow& F, const Queries& q, const Tensor& vall, float* ref8, float* ref_unact8);
@@ -820,7 +825,7 @@ Tensor Builder::encoder(Flow& F) {
   Tensor t0 = act(F32, n, L, 1, d, "aifi_in");
   conv("enc.proj.2", F.feats[2], mk(t0.p, F32, n, lh[2], lw[2], d), {});
   // AIFI in fp32 (0.5 % of the FLOPs; keeps the only global-mixing layer of the encoder exact)
-  const bool fused = e->opts.dec_fused && d == 256 && c.enc_heads == 8 && c.enc_ffn <= 1024;
+  const bool fused = e->opts.dec_fused && d == 256 && c.enc_heads == 8 && c.enc_ffn <= 1024 && c.enc_ffn % 64 == 0;
   Tensor t2 = fused ? aifi_fused(t0) : aifi_by_op(t0);
   t2.h = lh[2]; t2.w = lw[2];
 
@@ -1326,7 +1331,8 @@ int rtd_create(const rtd_config* cfg, rtd_handle* out) {
     // the FPN concatenates a 2x-upsampled map with the next level: every level must halve exactly
     RTD_CHECK(cfg->input_h >= 64 && cfg->input_w >= 64 && cfg->input_h % 32 == 0 && cfg->input_w % 32 == 0 &&
                   cfg->input_h <= 4096 && cfg->input_w <= 4096, RTD_E_INVALID, "input size must be a multiple of 32 in [64,4096]");
-    RTD_CHECK(cfg->n_levels == 3 && cfg->n_points >= 1 && cfg->n_points <= 8, RTD_E_INVALID, "n_levels must be 3");
+    RTD_CHECK(cfg->n_levels == 3, RTD_E_INVALID, "n_levels must be 3");
+    RTD_CHECK(cfg->n_points >= 1 && cfg->n_points <= 8, RTD_E_INVALID, "n_points must be in [1,8]");
     RTD_CHECK(cfg->d_model % cfg->dec_heads == 0 && cfg->d_model / cfg->dec_heads == 32, RTD_E_INVALID, "decoder head dim must be 32");
     RTD_CHECK(cfg->enc_dim % cfg->enc_heads == 0 && cfg->enc_dim % 8 == 0 && cfg->csp_hidden % 8 == 0, RTD_E_INVALID, "encoder dims");
     RTD_CHECK(cfg->embedding_size % 16 == 0, RTD_E_INVALID, "embedding_size must be a multiple of 16");

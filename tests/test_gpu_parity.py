@@ -57,10 +57,15 @@ def fp32_case(name):
     return dict(name=name, arch=arch, w=w, input_size=input_size, frames=frames, g=g, oracle=oracle, col=col)
 
 
-def check_fp32_engine(eng, case):
-    """one infer_raw of an fp32 engine on the case's frames, held stage by stage and on the final rows to the oracle and the HF fixture;
-    returns (labels, boxes, scores)"""
-    name, frames, g, (ol, ob, osc), col = case["name"], case["frames"], case["g"], case["oracle"], case["col"]
+def check_fp32_engine(eng, case, refs=None):
+    """one infer_raw of an fp32 engine on the case's frames, held stage by stage to the oracle's stages (case["col"]) and, on the selection
+    scores and the final rows, to every reference of `refs`: (tag, labels, boxes, scores, enc_cls_max) each.  Without `refs` these are
+    the case's oracle and its HF fixture.  Returns (labels, boxes, scores)"""
+    name, frames, col = case["name"], case["frames"], case["col"]
+    if refs is None:
+        g, (ol, ob, osc) = case["g"], case["oracle"]
+        refs = [("oracle", [t.numpy() for t in ol], [t.numpy() for t in ob], [t.numpy() for t in osc], col["enc_cls_max"].numpy()),
+                ("hf", g["labels"], g["boxes"], g["scores"], g["enc_cls_max"])]
     labels, boxes, scores = eng.infer_raw(frames)
     # stage 0: preprocess is integer/byte work -> bit-exact
     x = nchw(eng.debug_tensor("input"))[:, :3]
@@ -73,13 +78,13 @@ def check_fp32_engine(eng, case):
         e = rel_err(nchw(eng.debug_tensor(f"enc{i}")), col[f"enc{i}"].numpy())
         assert e < 5e-5, (f"enc{i}", e)
     mx = eng.debug_tensor("enc_cls_max")[:, :, 0, 0]
-    np.testing.assert_allclose(mx, col["enc_cls_max"].numpy(), atol=2e-4)
-    np.testing.assert_allclose(mx, g["enc_cls_max"], atol=2e-4)
-    # final outputs vs oracle AND vs the HF fixture: 1e-3 on scores, 1e-2 px on boxes, order-tolerant
+    for tag, _, _, _, ref_mx in refs:
+        np.testing.assert_allclose(mx, ref_mx, atol=2e-4, err_msg=tag)
+    # final outputs vs every reference (oracle AND HF fixture): 1e-3 on scores, 1e-2 px on boxes, order-tolerant
     for b in range(len(frames)):
-        for rl, rb, rs in ((ol[b].numpy(), ob[b].numpy(), osc[b].numpy()), (g["labels"][b], g["boxes"][b], g["scores"][b])):
-            m, n, ws, wb = match_detections(rl, rb, rs, labels[b], boxes[b], scores[b], 1e-3, 1e-2)
-            print(f"{name}[{b}] matched {m}/{n} worst dscore={ws:.2e} dbox={wb:.2e}px")
+        for tag, rl, rb, rs, _ in refs:
+            m, n, ws, wb = match_detections(rl[b], rb[b], rs[b], labels[b], boxes[b], scores[b], 1e-3, 1e-2)
+            print(f"{name}[{b}] vs {tag}: matched {m}/{n} worst dscore={ws:.2e} dbox={wb:.2e}px")
             # measured: every row on every case; ONE row is the allowance for a near-tie at a top-k cut (gap ~1e-5, see make_golden output)
             assert m >= n - 1, (m, n, ws, wb)
         assert (np.diff(scores[b]) <= 0).all(), "scores must be descending"

@@ -95,6 +95,26 @@ def test_library_loads_and_exports_every_declared_symbol():
     assert lib.rtd_debug_option(b"no_such_option", 1) == _capi.RTD_E_INVALID
 
 
+@pytest.mark.parametrize("changes,why", [
+    (dict(num_queries=0), "num_queries <= 1024"), (dict(num_queries=1025), "num_queries <= 1024"), (dict(num_classes=82), r"num_classes % 4 == 0"),
+    (dict(n_points=0), r"n_points must be in \[1,8\]"), (dict(n_points=9), r"n_points must be in \[1,8\]"),
+    (dict(dec_heads=4), "decoder head dim must be 32"), (dict(dec_heads=16), "decoder head dim must be 32"),
+    (dict(dec_heads=3), "decoder head dim must be 32"),
+])
+def test_rtd_create_refuses_head_shapes_outside_its_range(changes, why):
+    """rtd_create validates before any HIP call: the decoder-head shapes next to the accepted range (num_queries 1..1024,
+    num_classes % 4 == 0, n_points 1..8, head dim 32) are RTD_E_INVALID with the reason - and the shapes at the ends of the range pass the
+    same checks (tests/test_gpu_head_configs.py runs them)"""
+    from dataclasses import replace
+    from telescope_cam_detection_amd import _capi
+    lib = _capi.lib()
+    cfg = _capi.cfg_for(replace(ARCHS["r18"], **changes), input_size=(320, 320))
+    h = ctypes.c_void_p()
+    rc = lib.rtd_create(ctypes.byref(cfg), ctypes.byref(h))
+    assert rc == _capi.RTD_E_INVALID and not h.value
+    assert re.search(why, lib.rtd_last_error(None).decode()), lib.rtd_last_error(None)
+
+
 def test_maxpool_refuses_what_its_deleted_kernels_took():
     """bf16 and pair tensors are pooled in 2 x 2 output patches of whole 16-byte chunks only (every plan rtd_create admits has even pooled
     extents and C % 8 == 0): an odd pooled extent or a partial chunk is an RtdError from the launcher's checks, before any launch

@@ -31,10 +31,16 @@ _WCACHE = {}
 
 
 def weights_for(arch, seed):
-    key = (arch.name, seed)
+    key = (arch, seed)          # the frozen Arch itself: two replace() variants may share a name, never their weights
     if key not in _WCACHE:
         _WCACHE[key] = synth_weights(arch, seed)
     return _WCACHE[key]
+
+
+def to64(w, x):
+    """the weight dict and the input cast to double: the oracle then runs end to end in fp64 (integer tensors pass through)"""
+    w64 = {k: (v.double() if torch.is_tensor(v) and v.is_floating_point() else v) for k, v in w.items()}
+    return w64, x.double()
 
 
 def sample(t, n=2048):
@@ -113,13 +119,17 @@ def ulp32(v):
     return float(np.spacing(np.float32(abs(float(v)))))
 
 
-def within(family, name, got, ref64, ref32, factor=FACTOR):
-    """|got - ref64| <= factor * (e_ref + ulp(max |ref64|)) with e_ref = max |ref32 - ref64|; prints the figures first"""
+def error_figures(got, ref64, ref32):
+    """(err, e_ref, ulp) of within(): max |got - ref64|, the fp32 reference's own loss max |ref32 - ref64|, one fp32 ulp of max |ref64|"""
     got, ref64, ref32 = (torch.as_tensor(t).double().reshape(-1) for t in (got, ref64, ref32))
     assert torch.isfinite(ref64).all(), "the reference itself must be finite"
-    e_ref = (ref32 - ref64).abs().max().item()
-    ulp = ulp32(ref64.abs().max().item())
-    err = (got - ref64).abs().max().item()
+    return (got - ref64).abs().max().item(), (ref32 - ref64).abs().max().item(), ulp32(ref64.abs().max().item())
+
+
+def within(family, name, got, ref64, ref32, factor=FACTOR):
+    """|got - ref64| <= factor * (e_ref + ulp(max |ref64|)) with e_ref = max |ref32 - ref64|; prints the figures first"""
+    got = torch.as_tensor(got).double().reshape(-1)
+    err, e_ref, ulp = error_figures(got, ref64, ref32)
     print(f"[{family}] {name}: kernel err {err:.3e}, e_ref {e_ref:.3e}, ulp {ulp:.3e}, ratio {err / (e_ref + ulp):.2f} (allowed {factor})")
     assert torch.isfinite(got).all(), (family, name)
     assert err <= factor * (e_ref + ulp), (family, name, err, e_ref, ulp)
