@@ -92,7 +92,7 @@ int rtd_op_msdeform(int dtype, const void* value, const float* offaw, const floa
  * when hd != 32 or the slice leaves the row */
 int rtd_op_msdeform_view(int dtype, const void* value, int value_ld, int value_coff, const float* offaw, const float* ref, float* out,
                          int B, int Q, int heads, int hd, int n_levels, int n_points, const int32_t* level_hw, float offset_scale);
-/* ... sampled as RTD_DEC_DISCRETE does: one nearest tap per point, clamped into the map (k_msdeform_discrete); same arguments and checks */
+/* ... sampled as RTD_DEC_DISCRETE does: one nearest tap per point, clamped into the map (k_msdeform<DEC_DISCRETE, ...>); same arguments and checks */
 int rtd_op_msdeform_discrete_view(int dtype, const void* value, int value_ld, int value_coff, const float* offaw, const float* ref, float* out,
                                   int B, int Q, int heads, int hd, int n_levels, int n_points, const int32_t* level_hw, float offset_scale);
 /* ---- query selection (decoder.hip).  x = [B * S] fp32 rows of K = 256 channels with row stride ldx; w_f32 = [C][K] row-major and

@@ -67,11 +67,11 @@ struct Tensor {
 // (unless OCML_BASIC_ROUNDED_OPERATIONS is defined), whose operations keep the contract flag wherever they are inlined - a pragma here
 // does not reach into them.  So the arithmetic is written with plain operators INSIDE this function under `fp contract(off)`, which
 // clears the flag of exactly these operations and survives inlining into the kernels.  Checked in the ISA of dec_layer_kernel<., 1>
-// and k_msdeform_discrete: three v_mul_f32, v_add_f32, v_mul_f32, v_add_f32, v_max, v_min feed every v_cvt_i32_f32; no v_fma / v_fmac.
+// and k_msdeform<DEC_DISCRETE, ...>: three v_mul_f32, v_add_f32, v_mul_f32, v_add_f32, v_max, v_min feed every v_cvt_i32_f32; no v_fma / v_fmac.
 // The clamp runs in float BEFORE the conversion - masked-anchor boxes (ref = 1) with large offsets lie far outside and a NaN becomes
 // tap 0; for an integer bound, min(trunc(c), extent - 1) == trunc(min(c, extent - 1)) and truncation toward zero sends every c in
-// (-1, 0) to 0, which the lower clamp does too.  The fused decoder kernel and k_msdeform_discrete both call this, so the same inputs
-// give the same taps on both decoder paths.
+// (-1, 0) to 0, which the lower clamp does too.  The fused decoder kernel (sample_rows<DEC_DISCRETE, ...>) and k_msdeform<DEC_DISCRETE, ...>
+// both call this, so the same inputs give the same taps on both decoder paths.
 __device__ __forceinline__ int discrete_tap(float ref, float offset, float pscale, float wh, float offset_scale, int extent) {
 #pragma clang fp contract(off)
   const float off = ((offset * pscale) * wh) * offset_scale;

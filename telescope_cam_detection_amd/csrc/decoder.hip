@@ -28,6 +28,9 @@ __device__ __forceinline__ float dinv_sig(float x) {
   return __logf(fmaxf(x, 1e-5f) / fmaxf(1.f - x, 1e-5f));
 }
 
+// x = hi + lo as two fp16 (common.h sp16), UN-clamped: not common.h's split2, whose saturation at +-65504 changes results and adds instructions.
+__device__ __forceinline__ void split_raw(float x, sp16& hi, sp16& lo) { hi = (sp16)x; lo = (sp16)(x - (float)hi); }
+
 // A GEMM operand or result: 16 rows in LDS as fp32 (f, ld) and, for the split engines' GEMMs, optionally as fp16 hi / lo rows (h, l, ldb).
 // The split form reads and writes the hi/lo rows where there are some (ldb != 0: the wide FFN and qpos hidden layers), the fp32 rows
 // elsewhere.  (ldb, not h, tells them apart: hipcc cannot prove an LDS pointer non-null, and the test must fold at every call.)
@@ -60,9 +63,7 @@ __device__ __forceinline__ void gemm_epilogue(const f32x4_& acc0, const f32x4_& 
         if (ACT == ACT_RELU) v = fmaxf(v, 0.f);
         if (ACT == ACT_GELU) v = 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
         if (pair) {
-          const sp16 hi = (sp16)v;
-          Y.h[row * Y.ldb + col] = hi;
-          Y.l[row * Y.ldb + col] = (sp16)(v - (float)hi);
+          split_raw(v, Y.h[row * Y.ldb + col], Y.l[row * Y.ldb + col]);
         } else {
           Y.f[row * Y.ld + col] = v;
         }
@@ -147,10 +148,9 @@ __device__ __forceinline__ void split_rows(const float* Xs, int ldx, int K, sp16
     sp16x8 h, l;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float x = j < 4 ? v0[j] : v1[j - 4];
-      const sp16 hi = (sp16)x;
-      h[j] = hi;
-      l[j] = (sp16)(x - (float)hi);
+      sp16 hi, lo;
+      split_raw(j < 4 ? v0[j] : v1[j - 4], hi, lo);
+      h[j] = hi; l[j] = lo;
     }
     *(sp16x8*)(Xh + r * ldb + c) = h;
     *(sp16x8*)(Xl + r * ldb + c) = l;
@@ -285,14 +285,15 @@ __device__ __forceinline__ void row_ln(float* Xs, int ldx, int D, const LNRegs& 
   }
 }
 
-
-// MS-deformable sampling of the block's 16 rows x 8 heads = 128 (row, head) items; 3 levels x 4 points.
-// FOUR lanes own one item, each 8 of its 32 channels (one 16-byte load per tap), so the 256 threads cover 64
-// items per pass (2 passes).  All 16 bilinear taps of a level are loaded UNCONDITIONALLY (clamped address, zero
-// weight when the tap is outside the map = grid_sample's zero padding) so they are in flight together: this phase
-// is pure HBM/MALL latency (random 64-byte rows of a ~200 MB tensor) and was 50 % of the kernel with one
-// 2-byte load per lane and 8 items per pass.
-template <typename TV>
+// MS-deformable sampling of the block's 16 rows x 8 heads = 128 (row, head) items; 3 levels x 4 points.  FOUR lanes own one item, each
+// 8 of its 32 channels (one 16-byte load per tap): the block's 512 threads cover the 128 items in one pass.  METHOD picks the taps:
+//   DEC_DEFAULT  - all 16 bilinear taps of a level are loaded UNCONDITIONALLY (clamped address, zero weight when the tap is outside the map
+//     = grid_sample's zero padding) so they are in flight together: this phase is pure HBM/MALL latency (random 64-byte rows of a ~200 MB
+//     tensor) and was 50 % of the kernel with one 2-byte load per lane and 8 items per pass.
+//   DEC_DISCRETE - (HF:v2.py method "discrete") one clamped nearest tap per point.  The item's 12 row offsets are computed first (discrete_tap,
+//     which k_msdeform<DEC_DISCRETE, ...> calls too), then all 12 taps' loads are issued before the first FMA: 12 (bf16) / 24 (fp32) loads
+//     in flight per lane where the bilinear form has 16 / 32 per level and three dependent rounds of them.
+template <int METHOD, typename TV>
 __device__ void sample_rows(const DecArgs& a, const float* sO, int LDO, const float* sR, int LDR, float* sA, int LDH, int b,
                             int nvalid, int tid) {
   constexpr int NL = 3, NP = 4, LP = NL * NP;
@@ -318,115 +319,80 @@ __device__ void sample_rows(const DecArgs& a, const float* sO, int LDO, const fl
       const float inv_den = 1.f / den;
       const float rx = sR[r * LDR + 0], ry = sR[r * LDR + 1], rw = sR[r * LDR + 2], rh = sR[r * LDR + 3];
       const TV* vb = (const TV*)a.value + (long long)b * a.S * a.value_ld + a.value_coff + head * 32 + c8 * 8;
+      if constexpr (METHOD == DEC_DISCRETE) {
+        int of[LP];
 #pragma unroll
-      for (int l = 0; l < NL; ++l) {
-        const int H = a.lvl[l * 3 + 0], W = a.lvl[l * 3 + 1], start = a.lvl[l * 3 + 2];
-        float wt[NP * 4];
-        int of[NP * 4];
+        for (int l = 0; l < NL; ++l) {
+          const int H = a.lvl[l * 3 + 0], W = a.lvl[l * 3 + 1], start = a.lvl[l * 3 + 2];
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-          const int i = l * NP + p;
-          const float aw = lg[i] * inv_den;
-          const float lx = rx + offs[i * 2 + 0] * pscale * rw * a.offset_scale;
-          const float ly = ry + offs[i * 2 + 1] * pscale * rh * a.offset_scale;
-          const float gx = 2.f * lx - 1.f, gy = 2.f * ly - 1.f;
-          const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f;
-          const float iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
-          const float fx = floorf(ix), fy = floorf(iy);
-          // clamp before the int conversion: masked-anchor boxes (ref = 1) with large offsets can be far outside
-          const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f), y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
-          const int x1 = x0 + 1, y1 = y0 + 1;
-          const float wx1 = ix - fx, wy1 = iy - fy, wx0 = (fx + 1.f) - ix, wy0 = (fy + 1.f) - iy;
-          const bool okx0 = (unsigned)x0 < (unsigned)W, okx1 = (unsigned)x1 < (unsigned)W;
-          const bool oky0 = (unsigned)y0 < (unsigned)H, oky1 = (unsigned)y1 < (unsigned)H;
-          const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x1, 0), W - 1);
-          const int cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y1, 0), H - 1);
-          wt[p * 4 + 0] = (oky0 && okx0) ? wx0 * wy0 * aw : 0.f;
-          wt[p * 4 + 1] = (oky0 && okx1) ? wx1 * wy0 * aw : 0.f;
-          wt[p * 4 + 2] = (oky1 && okx0) ? wx0 * wy1 * aw : 0.f;
-          wt[p * 4 + 3] = (oky1 && okx1) ? wx1 * wy1 * aw : 0.f;
-          of[p * 4 + 0] = (start + cy0 * W + cx0) * a.value_ld;
-          of[p * 4 + 1] = (start + cy0 * W + cx1) * a.value_ld;
-          of[p * 4 + 2] = (start + cy1 * W + cx0) * a.value_ld;
-          of[p * 4 + 3] = (start + cy1 * W + cx1) * a.value_ld;
+          for (int p = 0; p < NP; ++p) {
+            const int i = l * NP + p;
+            const int cx = discrete_tap(rx, offs[i * 2 + 0], pscale, rw, a.offset_scale, W);     // in [0, W - 1]
+            const int cy = discrete_tap(ry, offs[i * 2 + 1], pscale, rh, a.offset_scale, H);     // in [0, H - 1]
+            of[i] = (start + cy * W + cx) * a.value_ld;
+          }
         }
-        VT vv[NP * 4][8 / V];
+        VT vv[LP][8 / V];
 #pragma unroll
-        for (int t = 0; t < NP * 4; ++t)
+        for (int t = 0; t < LP; ++t)
 #pragma unroll
           for (int u = 0; u < 8 / V; ++u) vv[t][u] = *(const VT*)(vb + of[t] + u * V);
 #pragma unroll
-        for (int t = 0; t < NP * 4; ++t)
+        for (int t = 0; t < LP; ++t) {
+          const float aw = lg[t] * inv_den;
 #pragma unroll
-          for (int k = 0; k < 8; ++k) acc[k] = fmaf((float)vv[t][k / V][k % V], wt[t], acc[k]);
-      }
-    }
+          for (int k = 0; k < 8; ++k) acc[k] = fmaf((float)vv[t][k / V][k % V], aw, acc[k]);
+        }
+      } else {
 #pragma unroll
-    for (int k = 0; k < 8; ++k) sA[r * LDH + head * 32 + c8 * 8 + k] = acc[k];
-  }
-}
-
-
-// The discrete sampler (cross_attn_method: discrete, HF:v2.py method "discrete"): one clamped nearest tap per sampling point instead
-// of four zero-padded bilinear ones.  Same item-to-lane mapping as sample_rows (4 lanes per (row, head) item, 8 channels each).  The
-// 12 row offsets of an item are computed first (discrete_tap, the helper k_msdeform_discrete calls too), then all 12 taps' 16-byte
-// loads are issued before the first FMA: 12 (bf16) / 24 (fp32) loads in flight per lane where the bilinear sampler has 16 / 32 per
-// level and three dependent rounds of them.
-template <typename TV>
-__device__ void sample_rows_discrete(const DecArgs& a, const float* sO, int LDO, const float* sR, int LDR, float* sA, int LDH, int b,
-                                     int nvalid, int tid) {
-  constexpr int NL = 3, NP = 4, LP = NL * NP;
-  constexpr int V = 16 / (int)sizeof(TV);                      // channels per 16-byte load: 8 (bf16) / 4 (fp32)
-  typedef TV VT __attribute__((ext_vector_type(V)));
-  const int c8 = tid & 3;
-  const float pscale = 1.f / (float)NP;
-  for (int item = tid >> 2; item < DR * a.heads; item += NT / 4) {
-    const int r = item / a.heads, head = item - r * a.heads;
-    float acc[8];
+        for (int l = 0; l < NL; ++l) {
+          const int H = a.lvl[l * 3 + 0], W = a.lvl[l * 3 + 1], start = a.lvl[l * 3 + 2];
+          float wt[NP * 4];
+          int of[NP * 4];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) acc[k] = 0.f;
-    if (r < nvalid) {
-      const float* offs = sO + r * LDO + head * LP * 2;
-      const float* awl = sO + r * LDO + a.heads * LP * 2 + head * LP;
-      float lg[LP];
-      float mx = -INFINITY;
+          for (int p = 0; p < NP; ++p) {
+            const int i = l * NP + p;
+            const float aw = lg[i] * inv_den;
+            // (the location arithmetic is also written out in ops.hip k_msdeform: a shared helper changes both kernels' fp contraction)
+            const float lx = rx + offs[i * 2 + 0] * pscale * rw * a.offset_scale;
+            const float ly = ry + offs[i * 2 + 1] * pscale * rh * a.offset_scale;
+            const float gx = 2.f * lx - 1.f, gy = 2.f * ly - 1.f;
+            const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f;
+            const float iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
+            const float fx = floorf(ix), fy = floorf(iy);
+            // clamp before the int conversion: masked-anchor boxes (ref = 1) with large offsets can be far outside
+            const int x0 = (int)fminf(fmaxf(fx, -2.f), (float)W + 1.f), y0 = (int)fminf(fmaxf(fy, -2.f), (float)H + 1.f);
+            const int x1 = x0 + 1, y1 = y0 + 1;
+            const float wx1 = ix - fx, wy1 = iy - fy, wx0 = (fx + 1.f) - ix, wy0 = (fy + 1.f) - iy;
+            const bool okx0 = (unsigned)x0 < (unsigned)W, okx1 = (unsigned)x1 < (unsigned)W;
+            const bool oky0 = (unsigned)y0 < (unsigned)H, oky1 = (unsigned)y1 < (unsigned)H;
+            const int cx0 = min(max(x0, 0), W - 1), cx1 = min(max(x1, 0), W - 1);
+            const int cy0 = min(max(y0, 0), H - 1), cy1 = min(max(y1, 0), H - 1);
+            wt[p * 4 + 0] = (oky0 && okx0) ? wx0 * wy0 * aw : 0.f;
+            wt[p * 4 + 1] = (oky0 && okx1) ? wx1 * wy0 * aw : 0.f;
+            wt[p * 4 + 2] = (oky1 && okx0) ? wx0 * wy1 * aw : 0.f;
+            wt[p * 4 + 3] = (oky1 && okx1) ? wx1 * wy1 * aw : 0.f;
+            of[p * 4 + 0] = (start + cy0 * W + cx0) * a.value_ld;
+            of[p * 4 + 1] = (start + cy0 * W + cx1) * a.value_ld;
+            of[p * 4 + 2] = (start + cy1 * W + cx0) * a.value_ld;
+            of[p * 4 + 3] = (start + cy1 * W + cx1) * a.value_ld;
+          }
+          VT vv[NP * 4][8 / V];
 #pragma unroll
-      for (int i = 0; i < LP; ++i) { lg[i] = awl[i]; mx = fmaxf(mx, lg[i]); }
-      float den = 0.f;
+          for (int t = 0; t < NP * 4; ++t)
 #pragma unroll
-      for (int i = 0; i < LP; ++i) { lg[i] = __expf(lg[i] - mx); den += lg[i]; }
-      const float inv_den = 1.f / den;
-      const float rx = sR[r * LDR + 0], ry = sR[r * LDR + 1], rw = sR[r * LDR + 2], rh = sR[r * LDR + 3];
-      const TV* vb = (const TV*)a.value + (long long)b * a.S * a.value_ld + a.value_coff + head * 32 + c8 * 8;
-      int of[LP];
+            for (int u = 0; u < 8 / V; ++u) vv[t][u] = *(const VT*)(vb + of[t] + u * V);
 #pragma unroll
-      for (int l = 0; l < NL; ++l) {
-        const int H = a.lvl[l * 3 + 0], W = a.lvl[l * 3 + 1], start = a.lvl[l * 3 + 2];
+          for (int t = 0; t < NP * 4; ++t)
 #pragma unroll
-        for (int p = 0; p < NP; ++p) {
-          const int i = l * NP + p;
-          const int cx = discrete_tap(rx, offs[i * 2 + 0], pscale, rw, a.offset_scale, W);     // in [0, W - 1]
-          const int cy = discrete_tap(ry, offs[i * 2 + 1], pscale, rh, a.offset_scale, H);     // in [0, H - 1]
-          of[i] = (start + cy * W + cx) * a.value_ld;
+            for (int k = 0; k < 8; ++k) acc[k] = fmaf((float)vv[t][k / V][k % V], wt[t], acc[k]);
         }
       }
-      VT vv[LP][8 / V];
-#pragma unroll
-      for (int t = 0; t < LP; ++t)
-#pragma unroll
-        for (int u = 0; u < 8 / V; ++u) vv[t][u] = *(const VT*)(vb + of[t] + u * V);
-#pragma unroll
-      for (int t = 0; t < LP; ++t) {
-        const float aw = lg[t] * inv_den;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) acc[k] = fmaf((float)vv[t][k / V][k % V], aw, acc[k]);
-      }
     }
 #pragma unroll
     for (int k = 0; k < 8; ++k) sA[r * LDH + head * 32 + c8 * 8 + k] = acc[k];
   }
 }
-
 
 // Self-attention of the block's 16 query rows (HF:v2.py:246-336, no mask), one head per wave, exact fp32 MFMA.
 // Computed TRANSPOSED so nothing crosses LDS: per 16-key tile  S^T = K Q^T  (keys on accumulator rows, the
@@ -515,10 +481,9 @@ __device__ void self_attention_rows_split(const DecArgs& a, const float* sQ, int
     const f32x4_ q0 = *(const f32x4_*)(sQ + r16 * ldq + head * 32 + 8 * q), q1 = *(const f32x4_*)(sQ + r16 * ldq + head * 32 + 8 * q + 4);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float x = (j < 4 ? q0[j] : q1[j - 4]) * scale;
-      const sp16 hi = (sp16)x;
-      qh[j] = hi;
-      ql[j] = (sp16)(x - (float)hi);
+      sp16 hi, lo;
+      split_raw((j < 4 ? q0[j] : q1[j - 4]) * scale, hi, lo);
+      qh[j] = hi; ql[j] = lo;
     }
   }
   float m = -INFINITY, l = 0.f;
@@ -569,9 +534,9 @@ __device__ void self_attention_rows_split(const DecArgs& a, const float* sQ, int
       for (int r = 0; r < 4; ++r) {
         const float pv = __expf(sv[e][r] - mn);
         rs += pv;
-        const sp16 hi = (sp16)pv;
-        ph[4 * e + r] = hi;
-        pl[4 * e + r] = (sp16)(pv - (float)hi);
+        sp16 hi, lo;
+        split_raw(pv, hi, lo);
+        ph[4 * e + r] = hi; pl[4 * e + r] = lo;
       }
     rs = rows4_sum(rs);
     l = l * alpha + rs;
@@ -620,8 +585,8 @@ __device__ __forceinline__ void touch_weights(const DecLin& L, int part, int npa
 // struct is copied to scratch at kernel entry: round 4 read that as register spilling ("256 registers + 704 B of scratch"); it is an
 // inlining artefact, and __forceinline__ on the phase functions removes it.  They are NOT force-inlined in this build: with the attribute
 // hipcc schedules the same code 2.5 % slower (0.770 vs 0.747 ms per step for the nine launches, same box, round 5).)
-// DISCRETE = 1: the cross attention samples with sample_rows_discrete (DecArgs::method == DEC_DISCRETE).  A template argument, not a
-// branch on the argument: the kernels of the default sampler stay the code they were.
+// DISCRETE = DecArgs::method (DEC_DEFAULT = 0 | DEC_DISCRETE = 1), handed to sample_rows.  A template argument, not a branch on the
+// argument: the kernels of the default sampler stay the code they were.
 template <int SPLIT, int DISCRETE>
 __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
   // LDS (floats).  Row strides are (cols + 4): ds_read_b128 of 16 rows x 4 k-groups is conflict-free.
@@ -737,14 +702,9 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
     __syncthreads();
     linear(ACT_NONE, {sA, LDH}, a.offaw, {sO, LDO}, false, a.fc1);
     __syncthreads();
-    // ---- MS-deformable sampling (HF:v2.py:44-115,203-221): 32 lanes = one (row, head) ---------------
-    if (DISCRETE) {
-      if (a.value_f32) sample_rows_discrete<float>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
-      else sample_rows_discrete<bf16>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
-    } else {
-      if (a.value_f32) sample_rows<float>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
-      else sample_rows<bf16>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
-    }
+    // ---- MS-deformable sampling (HF:v2.py:44-115,203-221): 4 lanes = one (row, head) ----------------
+    if (a.value_f32) sample_rows<DISCRETE, float>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
+    else sample_rows<DISCRETE, bf16>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
     __syncthreads();
     // ---- output projection + residual + LN2 (HF:v2.py:221,418-421) ----------------------------------
     const LNRegs ln2 = ln_fetch(a.ln2, D, lane);
@@ -858,9 +818,9 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
       sp16x8 o;
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
-        const float x = kr < nvalid ? sT[kr * LDQ + D + h * 32 + 8 * (ln >> 4) + j] : 0.f;
-        const sp16 hi = (sp16)x;
-        o[j] = hl ? (sp16)(x - (float)hi) : hi;
+        sp16 hi, lo;
+        split_raw(kr < nvalid ? sT[kr * LDQ + D + h * 32 + 8 * (ln >> 4) + j] : 0.f, hi, lo);
+        o[j] = hl ? lo : hi;
       }
       *(sp16x8*)((char*)a.kfrag_out + ((size_t)(b * a.heads + h) * tp + tile) * 2048 + hl * 1024 + ln * 16) = o;
     }
@@ -870,9 +830,9 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int vr = 4 * (ln >> 4) + r;
-        const float x = vr < nvalid ? sO[vr * LDO + h * 32 + 16 * d + (ln & 15)] : 0.f;
-        const sp16 hi = (sp16)x;
-        o[r] = hl ? (sp16)(x - (float)hi) : hi;
+        sp16 hi, lo;
+        split_raw(vr < nvalid ? sO[vr * LDO + h * 32 + 16 * d + (ln & 15)] : 0.f, hi, lo);
+        o[r] = hl ? lo : hi;
       }
       char* dst = (char*)a.vfrag_out + ((size_t)(b * a.heads + h) * tp + 2 * pr) * 2048 + (d * 2 + hl) * 1024 + ln * 16;
       *(sp16x4*)(dst + eh * 8) = o;
@@ -890,6 +850,19 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
       a.vfrag_out[dst] = vr < nvalid ? sO[vr * LDO + h * 32 + 16 * c + (ln & 15)] : 0.f;
     }
   }
+}
+
+// LayerNorm of one 256-wide row held four columns per lane (v = columns 4 lane .. +3; g4 / b4 the affine parameters of those columns)
+__device__ __forceinline__ f32x4_ ln_row256(f32x4_ v, f32x4_ g4, f32x4_ b4) {
+  const float mean = wave_sum64(v[0] + v[1] + v[2] + v[3]) / 256.f;
+  float sq = 0.f;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) sq += (v[j] - mean) * (v[j] - mean);
+  const float rstd = rsqrtf(wave_sum64(sq) / 256.f + 1e-5f);
+  f32x4_ o4;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) o4[j] = (v[j] - mean) * rstd * g4[j] + b4[j];
+  return o4;
 }
 
 // ---- query selection scores: LayerNorm + enc_score_head + class max in one launch (exact fp32 MFMA) ----------------------------
@@ -914,19 +887,7 @@ __global__ __launch_bounds__(64 * SEL_WAVES, 2) void select_score_kernel(const S
     for (int i = 0; i < DR; ++i) v[i] = *(const f32x4_*)(a.x + (row0 + min(i, nvalid - 1)) * a.ldx + lane * 4);
     const f32x4_ g4 = *(const f32x4_*)(a.ln.g + lane * 4), b4 = *(const f32x4_*)(a.ln.b + lane * 4);
 #pragma unroll
-    for (int i = 0; i < DR; ++i) {
-      const float s = wave_sum64(v[i][0] + v[i][1] + v[i][2] + v[i][3]);
-      const float mean = s / 256.f;
-      float sq = 0.f;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) sq += (v[i][j] - mean) * (v[i][j] - mean);
-      sq = wave_sum64(sq);
-      const float rstd = rsqrtf(sq / 256.f + 1e-5f);
-      f32x4_ o4;
-#pragma unroll
-      for (int j = 0; j < 4; ++j) o4[j] = (v[i][j] - mean) * rstd * g4[j] + b4[j];
-      *(f32x4_*)(xs + i * LDH + lane * 4) = o4;
-    }
+    for (int i = 0; i < DR; ++i) *(f32x4_*)(xs + i * LDH + lane * 4) = ln_row256(v[i], g4, b4);
   }
   __builtin_amdgcn_wave_barrier();
   constexpr int MAXT = 5;                                         // <= 80 classes per pass; more classes: further passes
@@ -998,17 +959,9 @@ __global__ void k_gather_ln(const float* __restrict__ x, long long ldx, int rows
   int r = idx[t];
   r = min(max(r, 0), rows_per_image - 1);
   const f32x4_ v = *(const f32x4_*)(x + ((long long)b * rows_per_image + r) * ldx + lane * 4);
-  const float s = wave_sum64(v[0] + v[1] + v[2] + v[3]);
-  const float mean = s / 256.f;
-  float sq = 0.f;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) sq += (v[j] - mean) * (v[j] - mean);
-  sq = wave_sum64(sq);
-  const float rstd = rsqrtf(sq / 256.f + 1e-5f);
-  f32x4_ o4;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o4[j] = (v[j] - mean) * rstd * ln.g[lane * 4 + j] + ln.b[lane * 4 + j];
-  *(f32x4_*)(dst + (long long)t * ldd + lane * 4) = o4;
+  const f32x4_ g4 = {ln.g[lane * 4 + 0], ln.g[lane * 4 + 1], ln.g[lane * 4 + 2], ln.g[lane * 4 + 3]};
+  const f32x4_ b4 = {ln.b[lane * 4 + 0], ln.b[lane * 4 + 1], ln.b[lane * 4 + 2], ln.b[lane * 4 + 3]};
+  *(f32x4_*)(dst + (long long)t * ldd + lane * 4) = ln_row256(v, g4, b4);
 }
 void launch_gather_ln(const float* x, int64_t ldx, int rows_per_image, const int32_t* idx, int B, int Q, const DecLN& ln, float* dst, int64_t ldd,
                       hipStream_t s) {
@@ -1023,14 +976,10 @@ void launch_dec_layer(const DecArgs& a, hipStream_t s) {
   RTD_CHECK(a.n_levels == 3 && a.n_points == 4 && a.heads == NW, 1, "fused decoder: 3 levels x 4 points, one head per wave");
   const int tiles = (a.Q + DR - 1) / DR;
   RTD_CHECK(a.method == DEC_DEFAULT || a.method == DEC_DISCRETE, 1, "fused decoder: unknown sampling method");
-  const dim3 grid(a.B * tiles), blk(NT);
-  if (a.method == DEC_DISCRETE) {
-    if (a.split) rtd_launch((dec_layer_kernel<1, 1>), grid, blk, 0, s, a);
-    else rtd_launch((dec_layer_kernel<0, 1>), grid, blk, 0, s, a);
-  } else {
-    if (a.split) rtd_launch((dec_layer_kernel<1, 0>), grid, blk, 0, s, a);
-    else rtd_launch((dec_layer_kernel<0, 0>), grid, blk, 0, s, a);
-  }
+  static_assert(DEC_DEFAULT == 0 && DEC_DISCRETE == 1, "kernel table index");
+  static void (*const kernel[2][2])(const DecArgs) = {{dec_layer_kernel<0, DEC_DEFAULT>, dec_layer_kernel<0, DEC_DISCRETE>},
+                                                      {dec_layer_kernel<1, DEC_DEFAULT>, dec_layer_kernel<1, DEC_DISCRETE>}};   // [split][method]
+  rtd_launch(kernel[a.split ? 1 : 0][a.method], dim3(a.B * tiles), dim3(NT), 0, s, a);
   HIP_CHECK(hipGetLastError());
 }
 

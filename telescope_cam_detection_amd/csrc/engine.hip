@@ -935,6 +935,9 @@ Decoded Builder::decoder(Flow& F, const Tensor& mem, const Queries& q) {
   return out;
 }
 
+// value rows read per sampling point of the cross attention (the flop / byte counts of both decoder paths)
+static int sample_taps(int method) { return method == DEC_DISCRETE ? 1 : 4; }
+
 // ---- fused decoder: 1 prologue + per layer (self-attention kernel + one fused kernel), decoder.hip -----
 Tensor Builder::decoder_fused(Flow& F, const Queries& q, const Tensor& vall, float* ref8, float* ref_unact8) {
   const int dm = c.d_model, S = e->S, Q = c.num_queries, C = c.num_classes, NL = c.dec_layers;
@@ -994,7 +997,7 @@ Tensor Builder::decoder_fused(Flow& F, const Queries& q, const Tensor& vall, flo
     if (last) a.cls = dec_lin("dec.cls", C, dm);
     else { a.qk = dec_lin(nm("dec.l%d.sa.qk", i + 1), 2 * dm, dm); a.v = dec_lin(nm("dec.l%d.sa.v", i + 1), dm, dm); }
     const double fl = 4.0 * n * (double)Q * Q * dm + 2.0 * n * Q * ((double)dm * dm * 2 + 3.0 * npts * dm + 2.0 * dm * c.dec_ffn + 2.0 * dm * dm + 4.0 * dm) +
-                      2.0 * n * Q * dm * c.n_levels * c.n_points * (c.dec_method == RTD_DEC_DISCRETE ? 1 : 4) + (last ? 2.0 * n * Q * dm * C : row_flops_next);
+                      2.0 * n * Q * dm * c.n_levels * c.n_points * sample_taps(c.dec_method) + (last ? 2.0 * n * Q * dm * C : row_flops_next);
     push(p + ".fused", "dec_layer", fl, (double)n * Q * dm * 4 * 8, [a](hipStream_t s) { launch_dec_layer(a, s); });
     hs = hs_out;
   }
@@ -1031,7 +1034,7 @@ Tensor Builder::decoder_by_op(const Queries& q, const Tensor& vall, const Tensor
     Tensor offaw = linear(p + ".ca.offaw", hp2, 3 * npts, F32, ACT_NONE);
     Tensor samp = act(F32, n, Q, 1, dm);
     const int coff = i * dm;
-    const int taps = method == DEC_DISCRETE ? 1 : 4;                         // value rows read per sampling point
+    const int taps = sample_taps(method);
     push(p + ".ca.sample", "msdeform", 2.0 * n * Q * dm * nl * np * taps, (double)n * Q * heads * nl * np * taps * hd * dtype_size(P),
          [vall, coff, offaw, ref8, samp, heads, hd, nl, np, lvl, osc, method](hipStream_t s) { launch_msdeform(vall, coff, offaw, ref8, samp, heads, hd, nl, np, lvl, osc, method, s); });
     Tensor co = linear(p + ".ca.op", samp, dm, F32, ACT_NONE, &hs1);

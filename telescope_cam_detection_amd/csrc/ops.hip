@@ -1051,11 +1051,12 @@ void launch_box_refine(const Tensor& delta, float* ref8, hipStream_t s) {
 }
 
 // ------------------------------------------------------------------------------------------ MS-deformable sampling
-// HF:v2.py:44-115,186-221 (method "default"): for each (b, query, head): softmax over the
-// n_levels*n_points attention logits, sampling location = ref_xy + off/n_points * ref_wh * offset_scale,
-// grid_sample(bilinear, padding zeros, align_corners=False) of that head's 32-channel value rows.
-// 32 lanes = the 32 channels of one (b, q, head): each bilinear tap is one coalesced 64/128-byte row read.
-template <typename TV, typename TO>
+// HF:v2.py:44-115,186-221: for each (b, query, head): softmax over the n_levels*n_points attention logits, sampling location =
+// ref_xy + off/n_points * ref_wh * offset_scale, then per point, of that head's 32-channel value rows, DEC_DEFAULT (method "default"):
+// grid_sample(bilinear, padding zeros, align_corners=False); DEC_DISCRETE (method "discrete", the dsp checkpoints): ONE row - the tap
+// discrete_tap() names, clamped into the map.  32 lanes = the 32 channels of one (b, q, head): each tap is one coalesced 64/128-byte
+// row read.  Any n_levels / n_points.
+template <int METHOD, typename TV, typename TO>
 __global__ __launch_bounds__(256) void k_msdeform(const TV* __restrict__ value, int64_t ldv, int64_t v_bstride,
                                                    const float* __restrict__ offaw, int64_t ldoa,
                                                    const float* __restrict__ ref8, TO* __restrict__ out, int64_t ldo,
@@ -1085,62 +1086,29 @@ __global__ __launch_bounds__(256) void k_msdeform(const TV* __restrict__ value, 
     for (int p = 0; p < n_points; ++p) {
       const int i = l * n_points + p;
       const float aw = __expf(awl[i] - mx) * inv_den;
-      const float lx = rx + offs[i * 2 + 0] * pscale * rw * offset_scale;
-      const float ly = ry + offs[i * 2 + 1] * pscale * rh * offset_scale;
-      const float gx = 2.f * lx - 1.f, gy = 2.f * ly - 1.f;                 // sampling_grids = 2*loc - 1
-      const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f;                // align_corners=False unnormalise
-      const float iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
-      const float fx = floorf(ix), fy = floorf(iy);
-      const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
-      const float wx1 = ix - fx, wy1 = iy - fy, wx0 = (fx + 1.f) - ix, wy0 = (fy + 1.f) - iy;
-      float sv = 0.f;
-      const bool okx0 = (unsigned)x0 < (unsigned)W, okx1 = (unsigned)x1 < (unsigned)W;
-      const bool oky0 = (unsigned)y0 < (unsigned)H, oky1 = (unsigned)y1 < (unsigned)H;
-      if (oky0 && okx0) sv += (float)vb[(int64_t)(start + y0 * W + x0) * ldv] * (wx0 * wy0);
-      if (oky0 && okx1) sv += (float)vb[(int64_t)(start + y0 * W + x1) * ldv] * (wx1 * wy0);
-      if (oky1 && okx0) sv += (float)vb[(int64_t)(start + y1 * W + x0) * ldv] * (wx0 * wy1);
-      if (oky1 && okx1) sv += (float)vb[(int64_t)(start + y1 * W + x1) * ldv] * (wx1 * wy1);
-      acc += sv * aw;
-    }
-  }
-  out[bq * ldo + head * 32 + ch] = (TO)acc;
-}
-// HF:v2.py method "discrete" (cross_attn_method: discrete, the dsp checkpoints): the same softmax and locations, but each sampling
-// point reads ONE value row - the tap discrete_tap() names, clamped into the map - instead of four zero-padded bilinear ones.
-// Same item-to-lane mapping as k_msdeform; any n_levels / n_points.
-template <typename TV, typename TO>
-__global__ __launch_bounds__(256) void k_msdeform_discrete(const TV* __restrict__ value, int64_t ldv, int64_t v_bstride,
-                                                            const float* __restrict__ offaw, int64_t ldoa,
-                                                            const float* __restrict__ ref8, TO* __restrict__ out, int64_t ldo,
-                                                            int Q, int heads, int n_levels, int n_points,
-                                                            const int32_t* __restrict__ lvl, float offset_scale, int64_t items) {
-  const int64_t item = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);   // (b, q, head)
-  const int ch = threadIdx.x & 31;
-  if (item >= items) return;
-  const int head = (int)(item % heads);
-  const int64_t bq = item / heads;
-  const int b = (int)(bq / Q);
-  const int LP = n_levels * n_points;
-  const float* oa = offaw + bq * ldoa;
-  const float* offs = oa + (int64_t)head * LP * 2;
-  const float* awl = oa + (int64_t)heads * LP * 2 + (int64_t)head * LP;
-  float mx = -INFINITY;
-  for (int i = 0; i < LP; ++i) mx = fmaxf(mx, awl[i]);
-  float den = 0.f;
-  for (int i = 0; i < LP; ++i) den += __expf(awl[i] - mx);
-  const float inv_den = 1.f / den;
-  const float rx = ref8[bq * 8 + 0], ry = ref8[bq * 8 + 1], rw = ref8[bq * 8 + 2], rh = ref8[bq * 8 + 3];
-  const float pscale = 1.f / (float)n_points;
-  const TV* vb = value + (int64_t)b * v_bstride + head * 32 + ch;
-  float acc = 0.f;
-  for (int l = 0; l < n_levels; ++l) {
-    const int H = lvl[l * 3 + 0], W = lvl[l * 3 + 1], start = lvl[l * 3 + 2];
-    for (int p = 0; p < n_points; ++p) {
-      const int i = l * n_points + p;
-      const float aw = __expf(awl[i] - mx) * inv_den;
-      const int cx = discrete_tap(rx, offs[i * 2 + 0], pscale, rw, offset_scale, W);     // in [0, W - 1]
-      const int cy = discrete_tap(ry, offs[i * 2 + 1], pscale, rh, offset_scale, H);     // in [0, H - 1]
-      acc += (float)vb[(int64_t)(start + cy * W + cx) * ldv] * aw;
+      if constexpr (METHOD == DEC_DISCRETE) {
+        const int cx = discrete_tap(rx, offs[i * 2 + 0], pscale, rw, offset_scale, W);     // in [0, W - 1]
+        const int cy = discrete_tap(ry, offs[i * 2 + 1], pscale, rh, offset_scale, H);     // in [0, H - 1]
+        acc += (float)vb[(int64_t)(start + cy * W + cx) * ldv] * aw;
+      } else {
+        // (the location arithmetic is also written out in decoder.hip sample_rows: a shared helper changes both kernels' fp contraction)
+        const float lx = rx + offs[i * 2 + 0] * pscale * rw * offset_scale;
+        const float ly = ry + offs[i * 2 + 1] * pscale * rh * offset_scale;
+        const float gx = 2.f * lx - 1.f, gy = 2.f * ly - 1.f;                 // sampling_grids = 2*loc - 1
+        const float ix = ((gx + 1.f) * (float)W - 1.f) * 0.5f;                // align_corners=False unnormalise
+        const float iy = ((gy + 1.f) * (float)H - 1.f) * 0.5f;
+        const float fx = floorf(ix), fy = floorf(iy);
+        const int x0 = (int)fx, y0 = (int)fy, x1 = x0 + 1, y1 = y0 + 1;
+        const float wx1 = ix - fx, wy1 = iy - fy, wx0 = (fx + 1.f) - ix, wy0 = (fy + 1.f) - iy;
+        float sv = 0.f;
+        const bool okx0 = (unsigned)x0 < (unsigned)W, okx1 = (unsigned)x1 < (unsigned)W;
+        const bool oky0 = (unsigned)y0 < (unsigned)H, oky1 = (unsigned)y1 < (unsigned)H;
+        if (oky0 && okx0) sv += (float)vb[(int64_t)(start + y0 * W + x0) * ldv] * (wx0 * wy0);
+        if (oky0 && okx1) sv += (float)vb[(int64_t)(start + y0 * W + x1) * ldv] * (wx1 * wy0);
+        if (oky1 && okx0) sv += (float)vb[(int64_t)(start + y1 * W + x0) * ldv] * (wx0 * wy1);
+        if (oky1 && okx1) sv += (float)vb[(int64_t)(start + y1 * W + x1) * ldv] * (wx1 * wy1);
+        acc += sv * aw;
+      }
     }
   }
   out[bq * ldo + head * 32 + ch] = (TO)acc;
@@ -1157,12 +1125,9 @@ void launch_msdeform(const Tensor& value, int value_coff, const Tensor& offaw, c
   const char* vp = (const char*)value.p + (size_t)value_coff * dtype_size(value.dt);
   with_dtype(value.dt, [&](auto tv) { with_dtype(out.dt, [&](auto to) {
     typedef type_of<decltype(tv)> TV; typedef type_of<decltype(to)> TO;
-    if (method == DEC_DISCRETE)
-      rtd_launch((k_msdeform_discrete<TV, TO>), grid, blk, 0, s, (const TV*)vp, value.ld, value.bstride, (const float*)offaw.p, offaw.ld, ref8, (TO*)out.p,
-                 out.ld, Q, heads, n_levels, n_points, level_hw_start, offset_scale, items);
-    else
-      rtd_launch((k_msdeform<TV, TO>), grid, blk, 0, s, (const TV*)vp, value.ld, value.bstride, (const float*)offaw.p, offaw.ld, ref8, (TO*)out.p, out.ld, Q,
-                 heads, n_levels, n_points, level_hw_start, offset_scale, items);
+    const auto kernel = method == DEC_DISCRETE ? k_msdeform<DEC_DISCRETE, TV, TO> : k_msdeform<DEC_DEFAULT, TV, TO>;
+    rtd_launch(kernel, grid, blk, 0, s, (const TV*)vp, value.ld, value.bstride, (const float*)offaw.p, offaw.ld, ref8, (TO*)out.p, out.ld, Q, heads,
+               n_levels, n_points, level_hw_start, offset_scale, items);
   }); });
   HIP_CHECK(hipGetLastError());
 }

@@ -484,7 +484,7 @@ MSD_CASES = [
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 @pytest.mark.parametrize("case", MSD_CASES)
 def test_msdeform_on_a_channel_slice_of_the_value_buffer(L, dt, case):
-    """k_msdeform as the engine calls it: the layer's channels at offset value_coff of 768-wide value rows (the other slices hold 1e4),
+    """k_msdeform<DEC_DEFAULT, ...> as the engine calls it: the layer's channels at offset value_coff of 768-wide value rows (the other slices hold 1e4),
     batch stride S * 768; levels x points 3 x 4, 1 x 1, 2 x 3, 4 x 2 with 1 x 1, 1 x 7 and 5 x 1 maps; a grid of locations with zero
     offsets (grid_locations) next to random ones with large offsets; attention logits all equal and with one +40 entry."""
     B, Q, heads, shapes, n_points, coff = case

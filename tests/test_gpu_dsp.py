@@ -1,4 +1,4 @@
-"""GPU: the discrete-sampling ("dsp") variants - k_msdeform_discrete against an fp64 restatement, the per-op and the fused decoder
+"""GPU: the discrete-sampling ("dsp") variants - k_msdeform<DEC_DISCRETE, ...> against an fp64 restatement, the per-op and the fused decoder
 against the HF fixtures d1 / d2 and the patched oracle (tests/dsp_ref.py), fused against per-op, graph replay, the detector class on a
 dsp config and the refusal of bf16.
 
@@ -34,7 +34,7 @@ D1, D2 = "d1_r18dsp_160x224", "d2_tinycdsp_160x224"
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
 @pytest.mark.parametrize("case", MSD_CASES)
 def test_msdeform_discrete_on_a_channel_slice_of_the_value_buffer(case, dt):
-    """k_msdeform_discrete as the engine calls it, on the inputs of tests/test_gpu_decoder_ops.py's bilinear twin with power-of-two maps
+    """k_msdeform<DEC_DISCRETE, ...> as the engine calls it, on the inputs of tests/test_gpu_decoder_ops.py's bilinear twin with power-of-two maps
     and the exact-boundary grid (dsp_ref.msd_inputs).  Items with a coordinate within 1e-4 px of a boundary (not on it) are left out
     of the comparison - tests/test_dsp_oracle.py caps their share at 2 % - and must still be finite."""
     from telescope_cam_detection_amd import _capi

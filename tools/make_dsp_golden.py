@@ -36,7 +36,7 @@ DSP_CASES = {
     # d_model 256, 8 heads, 3 x 4 taps: the fused decoder kernel; 20 x 28 + 10 x 14 + 5 x 7 = 735 memory tokens >= 300 queries; the second
     # frame goes through the resampler
     "d1_r18dsp_160x224": ("r18_dsp", 0, (160, 224), [(6000, 160, 224), (6001, 200, 150)], "scene"),
-    # d_model 64, 2 heads: the per-op decoder (k_msdeform_discrete); the frames of t_tinyc_160x224
+    # d_model 64, 2 heads: the per-op decoder (k_msdeform<DEC_DISCRETE, ...>); the frames of t_tinyc_160x224
     "d2_tinycdsp_160x224": ("tinyc_dsp", 3, (160, 224), [(4006, 160, 224), (4007, 200, 150)], "scene"),
 }
 YARDSTICK = "dsp_yardstick.json"
