@@ -91,6 +91,17 @@ ARCHS = {
 # They come AFTER the plain entries: a checkpoint's shapes cannot tell the two apart and checkpoint.guess_arch takes the first fit.
 DSP_SUFFIX = "_dsp"
 ARCHS.update({n + DSP_SUFFIX: replace(ARCHS[n], name=n + DSP_SUFFIX, dec_method="discrete") for n in ("r18", "r34", "r50", "r101", "tinyc")})
+# Upstream's speed-tuned members, AFTER every entry above (guess_arch's first fit stays what it was for every checkpoint that fitted before;
+# these differ from their base in tensor shapes, so the file tells them apart):
+# * rtdetrv2_r50vd_m_7x_coco.yml: the R50 trunk with the half-width CSP blocks (expansion 0.5).  The file trains 6 decoder layers and sets
+#   `eval_idx: 2`: inference runs layers 0..2 and reads the heads of index 2, which is a 3-layer decoder; the converters pick only the
+#   keys they map, so the stored layers 3..5 are ignored.  (Restated from upstream's public config, unverifiable offline: DESIGN.md §8.)
+# * rtdetrv2_r18vd_sp1 / sp2 / sp3_120e_coco.yml: R18 with `num_points: [k, k, k]`, k sampling points per level instead of 4.  Upstream
+#   publishes no sp twins of other backbones and no sp + dsp files, so there are no such entries.
+ARCHS["r50_m"] = replace(ARCHS["r50"], name="r50_m", expansion=0.5, dec_layers=3)
+ARCHS["r50_m" + DSP_SUFFIX] = replace(ARCHS["r50_m"], name="r50_m" + DSP_SUFFIX, dec_method="discrete")
+SP_POINTS = (1, 2, 3)
+ARCHS.update({f"r18_sp{k}": replace(ARCHS["r18"], name=f"r18_sp{k}", n_points=k) for k in SP_POINTS})
 
 
 def same_weights(a: Arch, b: Arch) -> bool:
@@ -116,16 +127,67 @@ def _config_is_discrete(config_path: str) -> bool:
     return "dsp" in stem.split("_")
 
 
+class UnsupportedVariant(ValueError):
+    """a config that names a network this build has no description of (arch_from_config_path): a refusal, where a plain ValueError
+    only says that the path names no variant at all and the checkpoint's shapes may decide"""
+
+
+_NUM_POINTS_LINE = re.compile(r"^\s*num_points\s*:\s*\[([^\]\n]*)\]\s*(#.*)?$", re.MULTILINE)
+_SP_TOKEN = re.compile(r"^sp(\d+)$")
+
+
+def _config_points(config_path: str, tokens) -> "int | None":
+    """the sampling points per level a config asks for, None when it says nothing.  Upstream's sp configs set `num_points: [k, k, k]` on the
+    decoder and carry the token `sp<k>` in their file name (rtdetrv2_r18vd_sp2_120e_coco.yml).  As for the sampler, the YAML decides when it
+    can be read (a plain text scan), otherwise the name does.  A list that is not uniform raises: per-level counts are not built, and
+    serving such a checkpoint with one count for every level must not be silent."""
+    try:
+        if os.path.isfile(config_path):
+            with open(config_path, "r", errors="replace") as fh:
+                m = _NUM_POINTS_LINE.search(fh.read())
+            if m:
+                try:
+                    pts = [int(v) for v in m.group(1).split(",") if v.strip()]
+                except ValueError:
+                    pts = []
+                if not pts or len(set(pts)) != 1:
+                    raise UnsupportedVariant(f"{config_path!r}: num_points: [{m.group(1).strip()}] - one point count for every level is all this build "
+                                     f"serves (per-level counts are not built)")
+                return pts[0]
+    except OSError:
+        pass
+    sp = [int(_SP_TOKEN.match(t).group(1)) for t in tokens if _SP_TOKEN.match(t)]
+    return sp[0] if sp else None
+
+
 def arch_from_config_path(config_path: str) -> Arch:
     """Map the reference's `config_path` argument (src/rtdetr_detector.py:31) to a variant.
 
     The reference passes e.g. "RT-DETR/rtdetrv2_pytorch/configs/rtdetrv2/rtdetrv2_r18vd_120e_coco.yml";
-    upstream's file names carry the backbone tag; beside it this build needs the decoder's sampler (`_config_is_discrete`).
+    upstream's file names carry the backbone tag; beside it this build needs the decoder's sampler (`_config_is_discrete`), its point
+    count (`_config_points`: the sp1 / sp2 / sp3 files of R18) and the mid-size marker `m` of rtdetrv2_r50vd_m_7x_coco.yml, each one of
+    the `_`-delimited tokens of the file stem.  A marker on a backbone upstream publishes no such model for raises: the name asks for a
+    network this build has no description of.
     """
     s = str(config_path).lower()
+    tokens = os.path.basename(s).split(".")[0].split("_")
     for tag in ("r101", "r50", "r34", "r18", "tinyc", "tinyb", "tiny"):
         if tag in s:
-            if tag + DSP_SUFFIX in ARCHS and _config_is_discrete(str(config_path)):
-                return ARCHS[tag + DSP_SUFFIX]
-            return ARCHS[tag]
+            name = tag
+            if "m" in tokens:
+                if tag != "r50":
+                    raise UnsupportedVariant(f"config_path={config_path!r}: the mid-size variant `m` exists for r50 only")
+                name = "r50_m"
+            points = _config_points(str(config_path), tokens)
+            if points is not None and points != ARCHS[name].n_points:
+                if name != "r18" or points not in SP_POINTS:
+                    raise UnsupportedVariant(f"config_path={config_path!r}: {points} sampling point(s) per level - the sp variants are "
+                                     f"r18 with {', '.join(map(str, SP_POINTS))} points")
+                name = f"r18_sp{points}"
+            if _config_is_discrete(str(config_path)):
+                if points is not None and points != ARCHS[tag].n_points:
+                    raise UnsupportedVariant(f"config_path={config_path!r}: no variant has both {points} sampling points and the discrete sampler")
+                if name + DSP_SUFFIX in ARCHS:
+                    name += DSP_SUFFIX
+            return ARCHS[name]
     raise ValueError(f"cannot infer RT-DETR variant from config_path={config_path!r}")

@@ -261,7 +261,8 @@ def sniff_layout(state: Mapping[str, "object"]) -> str:
 
 
 def guess_arch(state: Mapping[str, "object"], layout: str) -> Optional[str]:
-    """pick the ARCHS entry whose shapes fit (r18 / r34 / r50 / r101 differ in block counts and widths)"""
+    """pick the first ARCHS entry whose shapes fit (r18 / r34 / r50 / r101 differ in block counts and widths, r50_m in its CSP width,
+    r18_sp1 / sp2 / sp3 in their sampling heads; a file with more decoder layers than the entry runs - r50_m stores 6 - still fits)"""
     conv = {"hf": convert_hf_state, "upstream": convert_upstream_state}.get(layout)
     for name, arch in ARCHS.items():
         try:
@@ -297,7 +298,7 @@ def load_foreign_state(path: str, arch_name: Optional[str] = None):
     layout = sniff_layout(state)
     name = arch_name or hint or guess_arch(state, layout)
     if name is None:
-        raise ValueError("could not match the checkpoint to r18 / r34 / r50 / r101; pass the arch explicitly")
+        raise ValueError("could not match the checkpoint to one of %s; pass the arch explicitly" % ", ".join(ARCHS))
     arch = ARCHS[name]
     if layout == "hf":
         return convert_hf_state(state, arch), name

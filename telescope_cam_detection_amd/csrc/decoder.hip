@@ -285,18 +285,24 @@ __device__ __forceinline__ void row_ln(float* Xs, int ldx, int D, const LNRegs& 
   }
 }
 
-// MS-deformable sampling of the block's 16 rows x 8 heads = 128 (row, head) items; 3 levels x 4 points.  FOUR lanes own one item, each
-// 8 of its 32 channels (one 16-byte load per tap): the block's 512 threads cover the 128 items in one pass.  METHOD picks the taps:
-//   DEC_DEFAULT  - all 16 bilinear taps of a level are loaded UNCONDITIONALLY (clamped address, zero weight when the tap is outside the map
-//     = grid_sample's zero padding) so they are in flight together: this phase is pure HBM/MALL latency (random 64-byte rows of a ~200 MB
-//     tensor) and was 50 % of the kernel with one 2-byte load per lane and 8 items per pass.
-//   DEC_DISCRETE - (HF:v2.py method "discrete") one clamped nearest tap per point.  The item's 12 row offsets are computed first (discrete_tap,
-//     which k_msdeform<DEC_DISCRETE, ...> calls too), then all 12 taps' loads are issued before the first FMA: 12 (bf16) / 24 (fp32) loads
-//     in flight per lane where the bilinear form has 16 / 32 per level and three dependent rounds of them.
-template <int METHOD, typename TV>
+// MS-deformable sampling of the block's 16 rows x 8 heads = 128 (row, head) items; 3 levels x NP points (NP = 2, 3 or 4: upstream's sp2 / sp3
+// checkpoints and the base models).  FOUR lanes own one item, each 8 of its 32 channels (one 16-byte load per tap): the block's 512
+// threads cover the 128 items in one pass.  METHOD picks the taps:
+//   DEC_DEFAULT  - the bilinear taps of a ROUND of points are loaded UNCONDITIONALLY (clamped address, zero weight when the tap is outside the
+//     map = grid_sample's zero padding) so they are in flight together: this phase is pure HBM/MALL latency (random 64-byte rows of a ~200 MB
+//     tensor) and was 50 % of the kernel with one 2-byte load per lane and 8 items per pass.  A round is PR consecutive points of the item's
+//     3 NP (level-major), the fewest rounds of at most 4 points = 16 taps (128 VGPRs of an fp32 value map): NP = 4: 3 rounds of 4 points =
+//     one level each; NP = 3: 3 rounds of 3 = one level each, 12 taps; NP = 2: 2 rounds of 3 points, 12 taps - a round spans a level and
+//     a half, where one level per round would leave 8 taps in flight and take a third dependent round.
+//   DEC_DISCRETE - (HF:v2.py method "discrete") one clamped nearest tap per point.  The item's 3 NP row offsets are computed first (discrete_tap,
+//     which k_msdeform<DEC_DISCRETE, ...> calls too), then all taps' loads are issued before the first FMA: 12 (bf16) / 24 (fp32) loads
+//     in flight per lane at NP = 4 where the bilinear form has 16 / 32 per round and three dependent rounds of them.
+template <int METHOD, typename TV, int NP>
 __device__ void sample_rows(const DecArgs& a, const float* sO, int LDO, const float* sR, int LDR, float* sA, int LDH, int b,
                             int nvalid, int tid) {
-  constexpr int NL = 3, NP = 4, LP = NL * NP;
+  constexpr int NL = 3, LP = NL * NP;
+  constexpr int NR = (LP + 3) / 4, PR = LP / NR;                // bilinear rounds, points per round
+  static_assert(NP >= 2 && NP <= 4 && NR * PR == LP, "rounds of equal size, at most 16 bilinear taps each");
   constexpr int V = 16 / (int)sizeof(TV);                      // channels per 16-byte load: 8 (bf16) / 4 (fp32)
   typedef TV VT __attribute__((ext_vector_type(V)));
   const int c8 = tid & 3;
@@ -345,13 +351,13 @@ __device__ void sample_rows(const DecArgs& a, const float* sO, int LDO, const fl
         }
       } else {
 #pragma unroll
-        for (int l = 0; l < NL; ++l) {
-          const int H = a.lvl[l * 3 + 0], W = a.lvl[l * 3 + 1], start = a.lvl[l * 3 + 2];
-          float wt[NP * 4];
-          int of[NP * 4];
+        for (int rd = 0; rd < NR; ++rd) {
+          float wt[PR * 4];
+          int of[PR * 4];
 #pragma unroll
-          for (int p = 0; p < NP; ++p) {
-            const int i = l * NP + p;
+          for (int p = 0; p < PR; ++p) {
+            const int i = rd * PR + p, l = i / NP;               // (constants once unrolled: a level's extents are read once)
+            const int H = a.lvl[l * 3 + 0], W = a.lvl[l * 3 + 1], start = a.lvl[l * 3 + 2];
             const float aw = lg[i] * inv_den;
             // (the location arithmetic is also written out in ops.hip k_msdeform: a shared helper changes both kernels' fp contraction)
             const float lx = rx + offs[i * 2 + 0] * pscale * rw * a.offset_scale;
@@ -377,13 +383,13 @@ __device__ void sample_rows(const DecArgs& a, const float* sO, int LDO, const fl
             of[p * 4 + 2] = (start + cy1 * W + cx0) * a.value_ld;
             of[p * 4 + 3] = (start + cy1 * W + cx1) * a.value_ld;
           }
-          VT vv[NP * 4][8 / V];
+          VT vv[PR * 4][8 / V];
 #pragma unroll
-          for (int t = 0; t < NP * 4; ++t)
+          for (int t = 0; t < PR * 4; ++t)
 #pragma unroll
             for (int u = 0; u < 8 / V; ++u) vv[t][u] = *(const VT*)(vb + of[t] + u * V);
 #pragma unroll
-          for (int t = 0; t < NP * 4; ++t)
+          for (int t = 0; t < PR * 4; ++t)
 #pragma unroll
             for (int k = 0; k < 8; ++k) acc[k] = fmaf((float)vv[t][k / V][k % V], wt[t], acc[k]);
         }
@@ -587,7 +593,11 @@ __device__ __forceinline__ void touch_weights(const DecLin& L, int part, int npa
 // hipcc schedules the same code 2.5 % slower (0.770 vs 0.747 ms per step for the nine launches, same box, round 5).)
 // DISCRETE = DecArgs::method (DEC_DEFAULT = 0 | DEC_DISCRETE = 1), handed to sample_rows.  A template argument, not a branch on the
 // argument: the kernels of the default sampler stay the code they were.
-template <int SPLIT, int DISCRETE>
+// NP = sampling points per level (DecArgs::n_points), handed to sample_rows in the same way.  NP = 4 is the kernel of every mode; NP = 2 and 3
+// are launched for the modes with cross attention only (launch_dec_layer): the kernel tells the compiler so (__builtin_assume, inside an
+// `if constexpr` that the 4-point kernels never see - their code is instruction for instruction what it was), and the prologue and AIFI
+// code is dropped from them.
+template <int SPLIT, int DISCRETE, int NP>
 __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
   // LDS (floats).  Row strides are (cols + 4): ds_read_b128 of 16 rows x 4 k-groups is conflict-free.
   constexpr int LDH = 260, LDF = 1028, LDQ = 516, LDO = 292, LDR = 68;
@@ -610,6 +620,7 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
   const LdsRows ffn_hidden = {sF, LDF, sFh, sFl, LDFB}, qpos_hidden = {sT, LDQ, sQh, sQl, LDQB};
 
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if constexpr (NP != 4) __builtin_assume(a.mode == 1 || a.mode == 2);
   const int tiles = (a.Q + DR - 1) / DR;
   const int b = blockIdx.x / tiles;
   const int q0 = (blockIdx.x - b * tiles) * DR;
@@ -703,8 +714,8 @@ __global__ __launch_bounds__(NT, 1) void dec_layer_kernel(const DecArgs a) {
     linear(ACT_NONE, {sA, LDH}, a.offaw, {sO, LDO}, false, a.fc1);
     __syncthreads();
     // ---- MS-deformable sampling (HF:v2.py:44-115,203-221): 4 lanes = one (row, head) ----------------
-    if (a.value_f32) sample_rows<DISCRETE, float>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
-    else sample_rows<DISCRETE, bf16>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
+    if (a.value_f32) sample_rows<DISCRETE, float, NP>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
+    else sample_rows<DISCRETE, bf16, NP>(a, sO, LDO, sR, LDR, sA, LDH, b, nvalid, tid);
     __syncthreads();
     // ---- output projection + residual + LN2 (HF:v2.py:221,418-421) ----------------------------------
     const LNRegs ln2 = ln_fetch(a.ln2, D, lane);
@@ -973,13 +984,18 @@ void launch_gather_ln(const float* x, int64_t ldx, int rows_per_image, const int
 void launch_dec_layer(const DecArgs& a, hipStream_t s) {
   RTD_CHECK(a.D == 256 && a.D / a.heads == 32 && a.ffn <= 1024 && a.ffn % 64 == 0 && a.C <= 512, 1,
             "fused decoder: d_model 256, head dim 32, ffn <= 1024 in 64-wide steps");
-  RTD_CHECK(a.n_levels == 3 && a.n_points == 4 && a.heads == NW, 1, "fused decoder: 3 levels x 4 points, one head per wave");
+  RTD_CHECK(a.n_levels == 3 && a.n_points >= 2 && a.n_points <= 4 && a.heads == NW, 1, "fused decoder: 3 levels x 2, 3 or 4 points, one head per wave");
   const int tiles = (a.Q + DR - 1) / DR;
   RTD_CHECK(a.method == DEC_DEFAULT || a.method == DEC_DISCRETE, 1, "fused decoder: unknown sampling method");
   static_assert(DEC_DEFAULT == 0 && DEC_DISCRETE == 1, "kernel table index");
-  static void (*const kernel[2][2])(const DecArgs) = {{dec_layer_kernel<0, DEC_DEFAULT>, dec_layer_kernel<0, DEC_DISCRETE>},
-                                                      {dec_layer_kernel<1, DEC_DEFAULT>, dec_layer_kernel<1, DEC_DISCRETE>}};   // [split][method]
-  rtd_launch(kernel[a.split ? 1 : 0][a.method], dim3(a.B * tiles), dim3(NT), 0, s, a);
+#define RTD_DEC_KERNELS(NP) {{dec_layer_kernel<0, DEC_DEFAULT, NP>, dec_layer_kernel<0, DEC_DISCRETE, NP>}, \
+                             {dec_layer_kernel<1, DEC_DEFAULT, NP>, dec_layer_kernel<1, DEC_DISCRETE, NP>}}
+  static void (*const kernel[3][2][2])(const DecArgs) = {RTD_DEC_KERNELS(4), RTD_DEC_KERNELS(2), RTD_DEC_KERNELS(3)};   // [points][split][method]
+#undef RTD_DEC_KERNELS
+  // only the sampler depends on the point count: the prologue and the AIFI modes run the 4-point kernel whatever a.n_points says
+  const bool has_cross = a.mode == 1 || a.mode == 2;
+  const int np = has_cross ? (a.n_points == 4 ? 0 : a.n_points - 1) : 0;
+  rtd_launch(kernel[np][a.split ? 1 : 0][a.method], dim3(a.B * tiles), dim3(NT), 0, s, a);
   HIP_CHECK(hipGetLastError());
 }
 

@@ -528,7 +528,7 @@ struct Builder {
   // refuses such a K; the per-op path takes any width)
   bool dec_fused() const {
     return e->opts.dec_fused && c.d_model == 256 && c.dec_heads == 8 && c.dec_ffn <= 1024 && c.dec_ffn % 64 == 0 && c.num_classes <= 512 &&
-           c.n_levels == 3 && c.n_points == 4;
+           c.n_levels == 3 && c.n_points >= 2 && c.n_points <= 4;   // (1 and 5..8 points: the per-op decoder)
   }
   Queries select_queries(Flow& F, const Tensor& mem);
   Decoded decoder(Flow& F, const Tensor& mem, const Queries& q);

@@ -17,7 +17,7 @@ from typing import Any, Dict, List, Optional, Union
 import numpy as np
 
 from . import _capi
-from .arch import ARCHS, Arch, arch_from_config_path, same_weights
+from .arch import ARCHS, Arch, UnsupportedVariant, arch_from_config_path, same_weights
 from .coco_constants import COCO_CLASSES, MAMMAL_CLASS_IDS, WILDLIFE_CLASSES
 from .weights import fold_weights, pack_blob, synth_weights
 
@@ -171,9 +171,10 @@ class RTDETRDetector:
             self._engine_input_size = tuple(self.input_size)
             self.model = _DeviceModel(engine, self.device)
             logger.info("RT-DETR (MI355X): %s engine for %s on %s ready in %.1f s - weights %s, input %dx%d, up to %d frames per call, "
-                        "%s arithmetic, %s cross-attention sampler, score threshold %.2f, 80 COCO classes", arch.name, self.config_path, self.device,
-                        time.perf_counter() - t0, self.model_path, self.input_size[0], self.input_size[1], self.max_batch, self.precision,
-                        "discrete (one clamped tap per point)" if arch.dec_method == "discrete" else "bilinear", self.conf_threshold)
+                        "%s arithmetic, %s cross-attention sampler at %d point(s) per level, score threshold %.2f, 80 COCO classes", arch.name,
+                        self.config_path, self.device, time.perf_counter() - t0, self.model_path, self.input_size[0], self.input_size[1],
+                        self.max_batch, self.precision, "discrete (one clamped tap per point)" if arch.dec_method == "discrete" else "bilinear",
+                        arch.n_points, self.conf_threshold)
             return True
         return False
 
@@ -189,6 +190,8 @@ class RTDETRDetector:
         else:
             try:
                 arch = arch_from_config_path(self.config_path)
+            except UnsupportedVariant:
+                raise                                         # a network this build does not describe: refused, never served as its base
             except ValueError:
                 arch = None
         if arch is None:
