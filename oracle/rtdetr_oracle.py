@@ -213,7 +213,7 @@ def mlp_head(w, pfx, x, n):
     return x
 
 
-def ms_deform_attn(arch, w, pfx, hs, pos, ref, memory, shapes):
+def ms_deform_attn_default(arch, w, pfx, hs, pos, ref, memory, shapes):
     """HF:v2.py:119-225 (module) + :44-115 (sampler, method='default').
 
     ref: [B,Q,4] sigmoid boxes.  loc = ref_xy + off * (1/n_points) * ref_wh * offset_scale ;
@@ -241,6 +241,72 @@ def ms_deform_attn(arch, w, pfx, hs, pos, ref, memory, shapes):
     a = aw.permute(0, 2, 1, 3).reshape(B * H, 1, Q, Lv * P)
     o = (torch.cat(sampled, dim=-1) * a).sum(-1).view(B, H * d, Q).transpose(1, 2).contiguous()
     return linear(w, pfx + ".op", o)
+
+
+# The discrete sampler of the "dsp" checkpoints (`cross_attn_method: discrete`; HF:v2.py:44-115, branch method == "discrete"):
+#   off = ((offset * (1 / n_points)) * ref_wh) * offset_scale        loc = ref_xy + off
+#   cx = int(loc_x * W + 0.5), cy = int(loc_y * H + 0.5)             (conversion truncates toward zero)
+#   then clamped to [0, W - 1] / [0, H - 1]; the output is the attention-weighted sum of value[cy, cx].
+def discrete_coords(off, ref, shapes, n_points, offset_scale):
+    """off [B, Q, heads, LP, 2], ref [B, Q, 4] in one dtype -> the un-truncated tap coordinates loc * (W, H) + 0.5, [B, Q, heads, LP, 2]
+    (x, y), every product and sum rounded on its own in that dtype and in HF's order"""
+    dt = off.dtype
+    scale = torch.tensor(1.0 / n_points, dtype=torch.float32).to(dt)         # the model's fp32 1 / n_points (n_points_scale)
+    r = ref[:, :, None, None, :]
+    loc = r[..., :2] + off * scale * r[..., 2:] * offset_scale
+    wh = torch.tensor([[w, h] for h, w in shapes], dtype=dt).repeat_interleave(n_points, 0)     # [LP, 2]: (W, H) of each tap's level
+    return loc * wh + 0.5
+
+
+def discrete_taps(coords, shapes, n_points):
+    """coordinates -> flat token index [B, Q, heads, LP] into the concatenated level maps: truncate toward zero, clamp into the map"""
+    c = coords.to(torch.int64)                                              # torch truncates toward zero
+    w = torch.tensor([w for _, w in shapes]).repeat_interleave(n_points)
+    h = torch.tensor([h for h, _ in shapes]).repeat_interleave(n_points)
+    start = torch.tensor(np.cumsum([0] + [hh * ww for hh, ww in shapes])[:-1]).repeat_interleave(n_points)
+    cx = torch.minimum(c[..., 0].clamp(min=0), w - 1)
+    cy = torch.minimum(c[..., 1].clamp(min=0), h - 1)
+    return start + cy * w + cx
+
+
+def msdeform_discrete_ref(value, offaw, ref, heads, hd, shapes, n_points, offset_scale, dt):
+    """HF's multi-scale deformable attention with method "discrete", restated in dtype `dt` (also the kernel-level reference of the tests); value [B, S, heads * hd], offaw
+    [B, Q, heads * LP * 3] (offsets | attention logits), ref [B, Q, 4]: the signature of msdeform_ref in tests/test_gpu_decoder_ops.py.
+    Returns (output [B, Q, heads * hd], un-truncated tap coordinates [B, Q, heads, LP, 2])."""
+    value, offaw, ref = value.to(dt), offaw.to(dt), ref.to(dt)
+    B, S, _ = value.shape
+    Q, LP = ref.shape[1], len(shapes) * n_points
+    off = offaw[..., : heads * LP * 2].view(B, Q, heads, LP, 2)
+    aw = torch.softmax(offaw[..., heads * LP * 2:].view(B, Q, heads, LP), -1)
+    coords = discrete_coords(off, ref, shapes, n_points, offset_scale)
+    idx = discrete_taps(coords, shapes, n_points)                           # [B, Q, heads, LP]
+    v = value.view(B, S, heads, hd).permute(0, 2, 1, 3)                     # [B, heads, S, hd]
+    gi = idx.permute(0, 2, 1, 3).reshape(B, heads, Q * LP, 1).expand(-1, -1, -1, hd)
+    taps = v.gather(2, gi).view(B, heads, Q, LP, hd)
+    out = (taps * aw.permute(0, 2, 1, 3)[..., None]).sum(3)                 # [B, heads, Q, hd]
+    return out.permute(0, 2, 1, 3).reshape(B, Q, heads * hd).contiguous(), coords
+
+
+def ms_deform_attn_discrete(arch, w, pfx, hs, pos, ref, memory, shapes):
+    """ms_deform_attn_default with the discrete sampler (same arguments, same projections)"""
+    B, Q, D = hs.shape
+    H, LP = arch.dec_heads, arch.n_levels * arch.n_points
+    q = hs + pos
+    value = linear(w, pfx + ".vp", memory)
+    offaw = torch.cat([linear(w, pfx + ".off", q), linear(w, pfx + ".aw", q)], -1)
+    assert offaw.shape[-1] == H * LP * 3
+    o, _ = msdeform_discrete_ref(value, offaw, ref, H, D // H, shapes, arch.n_points, arch.offset_scale, hs.dtype)
+    return linear(w, pfx + ".op", o)
+
+
+SAMPLERS = {"default": ms_deform_attn_default, "discrete": ms_deform_attn_discrete}
+
+
+def ms_deform_attn(arch, w, pfx, hs, pos, ref, memory, shapes):
+    """the decoder's cross-attention, sampling as arch.dec_method says (HF: decoder_method); any other method is an error"""
+    if arch.dec_method not in SAMPLERS:
+        raise ValueError(f"no sampler for dec_method {arch.dec_method!r}")
+    return SAMPLERS[arch.dec_method](arch, w, pfx, hs, pos, ref, memory, shapes)
 
 
 def decoder_and_heads(arch, w, pan, collect=None, force_topk=None):

@@ -1,105 +1,21 @@
-"""The discrete cross-attention sampler of RT-DETRv2's "dsp" checkpoints (`cross_attn_method: discrete`; HF modeling_rt_detr_v2.py
-multi_scale_deformable_attention_v2, branch method == "discrete", and the module above it), restated for the tests:
-
-  off = ((offset * (1 / n_points)) * ref_wh) * offset_scale        loc = ref_xy + off
-  cx = int(loc_x * W + 0.5), cy = int(loc_y * H + 0.5)             (conversion truncates toward zero)
-  then clamped to [0, W - 1] / [0, H - 1]; the output is the attention-weighted sum of value[cy, cx].
-
-`msdeform_discrete_ref` is the kernel-level reference (any dtype), `discrete_oracle()` turns oracle/rtdetr_oracle.py into the dsp
-yardstick without editing it, `near_boundary_items` names the items whose taps a rounding error may legitimately move.
+"""Test inputs for the discrete cross-attention sampler of RT-DETRv2's "dsp" checkpoints.  The sampler itself is restated in
+oracle/rtdetr_oracle.py (`msdeform_discrete_ref` is the kernel-level reference, any dtype); here are the inputs of the kernel-level
+tests and `near_boundary_items`, which names the items whose taps a rounding error may legitimately move.
 """
-import contextlib
 import json
 import os
 
 import numpy as np
 import torch
 
-from oracle import rtdetr_oracle as orc
-from telescope_cam_detection_amd.arch import ARCHS
-from telescope_cam_detection_amd.synth import make_frame
+from oracle.rtdetr_oracle import discrete_coords, discrete_taps, msdeform_discrete_ref  # noqa: F401  (the tests import them from here)
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-# fixture -> arch (the .npz carries seeds / sizes / frame list itself, as the c* / t* files do)
-DSP_CASE_ARCH = {"d1_r18dsp_160x224": "r18_dsp", "d2_tinycdsp_160x224": "tinyc_dsp"}
-
-
-def load_dsp_case(name):
-    """(arch, weight seed, input size, frames, npz) of a d* fixture: tests.util.load_case for the dsp files"""
-    g = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
-    wseed, ih, iw, n = (int(v) for v in g["meta"])
-    frames = [make_frame(str(g["kind"]), int(s), int(h), int(w)) for s, h, w in g["frames"]]
-    return ARCHS[DSP_CASE_ARCH[name]], wseed, (ih, iw), frames, g
 
 
 def yardstick():
     with open(os.path.join(GOLDEN_DIR, "dsp_yardstick.json")) as fh:
         return json.load(fh)
-
-
-def discrete_coords(off, ref, shapes, n_points, offset_scale):
-    """off [B, Q, heads, LP, 2], ref [B, Q, 4] in one dtype -> the un-truncated tap coordinates loc * (W, H) + 0.5, [B, Q, heads, LP, 2]
-    (x, y), every product and sum rounded on its own in that dtype and in HF's order"""
-    dt = off.dtype
-    scale = torch.tensor(1.0 / n_points, dtype=torch.float32).to(dt)         # the model's fp32 1 / n_points (n_points_scale)
-    r = ref[:, :, None, None, :]
-    loc = r[..., :2] + off * scale * r[..., 2:] * offset_scale
-    wh = torch.tensor([[w, h] for h, w in shapes], dtype=dt).repeat_interleave(n_points, 0)     # [LP, 2]: (W, H) of each tap's level
-    return loc * wh + 0.5
-
-
-def discrete_taps(coords, shapes, n_points):
-    """coordinates -> flat token index [B, Q, heads, LP] into the concatenated level maps: truncate toward zero, clamp into the map"""
-    c = coords.to(torch.int64)                                              # torch truncates toward zero
-    w = torch.tensor([w for _, w in shapes]).repeat_interleave(n_points)
-    h = torch.tensor([h for h, _ in shapes]).repeat_interleave(n_points)
-    start = torch.tensor(np.cumsum([0] + [hh * ww for hh, ww in shapes])[:-1]).repeat_interleave(n_points)
-    cx = torch.minimum(c[..., 0].clamp(min=0), w - 1)
-    cy = torch.minimum(c[..., 1].clamp(min=0), h - 1)
-    return start + cy * w + cx
-
-
-def msdeform_discrete_ref(value, offaw, ref, heads, hd, shapes, n_points, offset_scale, dt):
-    """HF's multi-scale deformable attention with method "discrete", restated in dtype `dt`; value [B, S, heads * hd], offaw
-    [B, Q, heads * LP * 3] (offsets | attention logits), ref [B, Q, 4]: the signature of msdeform_ref in tests/test_gpu_decoder_ops.py.
-    Returns (output [B, Q, heads * hd], un-truncated tap coordinates [B, Q, heads, LP, 2])."""
-    value, offaw, ref = value.to(dt), offaw.to(dt), ref.to(dt)
-    B, S, _ = value.shape
-    Q, LP = ref.shape[1], len(shapes) * n_points
-    off = offaw[..., : heads * LP * 2].view(B, Q, heads, LP, 2)
-    aw = torch.softmax(offaw[..., heads * LP * 2:].view(B, Q, heads, LP), -1)
-    coords = discrete_coords(off, ref, shapes, n_points, offset_scale)
-    idx = discrete_taps(coords, shapes, n_points)                           # [B, Q, heads, LP]
-    v = value.view(B, S, heads, hd).permute(0, 2, 1, 3)                     # [B, heads, S, hd]
-    gi = idx.permute(0, 2, 1, 3).reshape(B, heads, Q * LP, 1).expand(-1, -1, -1, hd)
-    taps = v.gather(2, gi).view(B, heads, Q, LP, hd)
-    out = (taps * aw.permute(0, 2, 1, 3)[..., None]).sum(3)                 # [B, heads, Q, hd]
-    return out.permute(0, 2, 1, 3).reshape(B, Q, heads * hd).contiguous(), coords
-
-
-def ms_deform_attn_discrete(arch, w, pfx, hs, pos, ref, memory, shapes):
-    """oracle.rtdetr_oracle.ms_deform_attn with the discrete sampler (same arguments, same projections)"""
-    B, Q, D = hs.shape
-    H, LP = arch.dec_heads, arch.n_levels * arch.n_points
-    q = hs + pos
-    value = orc.linear(w, pfx + ".vp", memory)
-    offaw = torch.cat([orc.linear(w, pfx + ".off", q), orc.linear(w, pfx + ".aw", q)], -1)
-    assert offaw.shape[-1] == H * LP * 3
-    o, _ = msdeform_discrete_ref(value, offaw, ref, H, D // H, shapes, arch.n_points, arch.offset_scale, hs.dtype)
-    return orc.linear(w, pfx + ".op", o)
-
-
-@contextlib.contextmanager
-def discrete_oracle():
-    """inside the block oracle.rtdetr_oracle samples as the dsp checkpoints do: decoder_and_heads looks ms_deform_attn up in its module,
-    so orc.model_forward and orc.detect_batch become the discrete yardstick; the bilinear function is put back on the way out"""
-    saved = orc.ms_deform_attn
-    orc.ms_deform_attn = ms_deform_attn_discrete
-    try:
-        yield orc
-    finally:
-        orc.ms_deform_attn = saved
 
 
 def near_boundary_items(coords, shapes, delta):

@@ -1,43 +1,39 @@
-"""CPU: the discrete-sampling ("dsp") variants without a GPU - the patched oracle against the HF fixtures tools/make_dsp_golden.py
-wrote, what selects the sampler (config path -> Arch -> rtd_config), the new test entry point's declaration, and the inputs of the
+"""CPU: the discrete-sampling ("dsp") variants without a GPU - the oracle against the HF fixtures oracle/make_golden.py wrote, under
+the arch's own sampler and under the bilinear one ("patched" / "unpatched" in the test names: the oracle once had to be patched to sample
+discretely), what selects the sampler (config path -> Arch -> rtd_config), the new test entry point's declaration, and the inputs of the
 kernel-level GPU test: which items the comparison leaves out, and that the fp32 restatement picks the fp64 taps on all others."""
+import dataclasses
 import os
 import re
 
-import numpy as np
 import pytest
 import torch
 
-from oracle import rtdetr_oracle as orc
 from telescope_cam_detection_amd import _capi
 from telescope_cam_detection_amd.arch import ARCHS, arch_from_config_path
 from tests import dsp_ref
-from tests.dsp_ref import MSD_CASES, MSD_DELTA, discrete_oracle, discrete_taps, load_dsp_case, msd_inputs, msdeform_discrete_ref, near_boundary_items
-from tests.util import weights_for
+from tests.dsp_ref import MSD_CASES, MSD_DELTA, discrete_taps, msd_inputs, msdeform_discrete_ref, near_boundary_items
+from tests.util import load_case, oracle_run, weights_for
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DSP_CASES = ["d1_r18dsp_160x224", "d2_tinycdsp_160x224"]
 
 
-def per_token_deltas(name, patched):
-    """max |dlogit|, max |dbox| between the oracle (discrete when `patched`) and the HF fixture, per selected token: query ORDER is
-    decided by near-ties of the encoder scores (oracle/make_golden.py)"""
-    arch, wseed, input_size, frames, g = load_dsp_case(name)
+def per_token_deltas(name, discrete):
+    """max |dlogit|, max |dbox| between the oracle (with the case's own Arch when `discrete`, else with its bilinear twin) and the HF
+    fixture, per selected token: query ORDER is decided by near-ties of the encoder scores (oracle/make_golden.py)"""
+    arch, wseed, input_size, frames, g = load_case(name)
+    assert arch.dec_method == "discrete"
     w = weights_for(arch, wseed)
-    xs, sizes = zip(*[orc.preprocess(f, input_size) for f in frames])
-    col = {}
-    with torch.no_grad():
-        if patched:
-            with discrete_oracle():
-                orc.model_forward(arch, w, torch.cat(xs, 0), list(sizes), collect=col)
-        else:
-            orc.model_forward(arch, w, torch.cat(xs, 0), list(sizes), collect=col)
+    if not discrete:
+        arch = dataclasses.replace(arch, dec_method="default")
+    _, col = oracle_run(arch, w, frames, input_size)
     so, sh = torch.sort(col["topk"], 1), torch.sort(torch.as_tensor(g["topk"]).long(), 1)
     assert torch.equal(so.values, sh.values)
     gat = lambda t, idx: t.gather(1, idx.unsqueeze(-1).expand(-1, -1, t.shape[-1]))
     d_logit = (gat(col["logits"], so.indices) - gat(torch.as_tensor(g["logits"]), sh.indices)).abs().max().item()
     d_box = (gat(col["pred_boxes"], so.indices) - gat(torch.as_tensor(g["pred_boxes"]), sh.indices)).abs().max().item()
-    print(f"[{name}] {'discrete' if patched else 'bilinear'} oracle vs HF fixture: max|dlogit| {d_logit:.3e}, max|dbox| {d_box:.3e}")
+    print(f"[{name}] {'discrete' if discrete else 'bilinear'} oracle vs HF fixture: max|dlogit| {d_logit:.3e}, max|dbox| {d_box:.3e}")
     return d_logit, d_box
 
 
@@ -53,15 +49,14 @@ def test_unpatched_oracle_misses_the_hf_fixture(name):
     """the fixture tells the two samplers apart"""
     d_logit, _ = per_token_deltas(name, False)
     assert d_logit > 1e-2
-    assert orc.ms_deform_attn.__module__ == "oracle.rtdetr_oracle"          # discrete_oracle() put the bilinear sampler back
 
 
 def test_fixtures_have_the_shapes_the_gpu_tests_rely_on():
-    arch, _, input_size, frames, g = load_dsp_case("d1_r18dsp_160x224")
+    arch, _, input_size, frames, g = load_case("d1_r18dsp_160x224")
     assert arch.d_model == 256 and arch.dec_heads == 8 and (arch.n_levels, arch.n_points) == (3, 4)      # the fused decoder kernel's shape
     assert sum(h * w for h, w in arch.level_shapes(*input_size)) == 735 >= arch.num_queries == 300
     assert [f.shape[:2] for f in frames] == [(160, 224), (200, 150)]
-    arch2, _, _, _, _ = load_dsp_case("d2_tinycdsp_160x224")
+    arch2, _, _, _, _ = load_case("d2_tinycdsp_160x224")
     assert arch2.d_model != 256                                                                          # the per-op decoder
     y = dsp_ref.yardstick()
     for name in DSP_CASES:
@@ -104,7 +99,6 @@ def test_config_path_selects_the_sampler_by_the_yaml_key(tmp_path):
 
 
 def test_dsp_entries_differ_from_their_twins_in_name_and_sampler_only():
-    import dataclasses
     for n in ("r18", "r34", "r50", "r101", "tinyc"):
         assert dataclasses.replace(ARCHS[n + "_dsp"], name=n, dec_method="default") == ARCHS[n]
         assert ARCHS[n].dec_method == "default"

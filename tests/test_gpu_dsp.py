@@ -1,5 +1,5 @@
 """GPU: the discrete-sampling ("dsp") variants - k_msdeform<DEC_DISCRETE, ...> against an fp64 restatement, the per-op and the fused decoder
-against the HF fixtures d1 / d2 and the patched oracle (tests/dsp_ref.py), fused against per-op, graph replay, the detector class on a
+against the HF fixtures d1 / d2 and the oracle, which samples discretely for a dsp Arch ("patched oracle" in names and tags), fused against per-op, graph replay, the detector class on a
 dsp config and the refusal of bf16.
 
 Rows: a case's final rows are matched at the reference tolerance (1e-3 on scores, 1e-2 px on boxes).  Per frame the allowance is what the
@@ -12,7 +12,6 @@ The row is HF's row 245 = query 212: its layer-0 tap of head 6, level 1, point 1
 below 12 and the closest of the frame's coordinates to a boundary; the engine's offset GEMM sums in another order and lands on 12.0."""
 import ctypes as C
 import logging
-import os
 
 import numpy as np
 import pytest
@@ -21,8 +20,9 @@ import torch
 from oracle import rtdetr_oracle as orc
 from telescope_cam_detection_amd.arch import ARCHS
 from tests import dsp_ref
-from tests.dsp_ref import MSD_CASES, MSD_DELTA, MSD_LDV, discrete_oracle, load_dsp_case, msd_inputs, msdeform_discrete_ref, near_boundary_items
-from tests.util import match_detections, weights_for, within
+from tests.dsp_ref import MSD_CASES, MSD_DELTA, MSD_LDV, msd_inputs, msdeform_discrete_ref, near_boundary_items
+from tests.engine_checks import make_engine
+from tests.util import load_case, match_detections, reference_runs, weights_for, within
 
 pytestmark = pytest.mark.gpu
 
@@ -83,30 +83,13 @@ def test_msdeform_discrete_rounds_every_operation_on_its_own():
 
 
 # ------------------------------------------------------------------------------------------ 2 - 5. engines
-def make_engine(arch, w, frames, input_size, precision, use_graph=False):
-    from telescope_cam_detection_amd import _capi
-    from telescope_cam_detection_amd.weights import fold_weights, pack_blob
-    return _capi.Engine(arch, pack_blob(fold_weights(arch, w)), device=0, precision=_capi.precision_code(precision), max_batch=len(frames),
-                        input_size=input_size, use_graph=use_graph)
-
-
-_CASES = {}
-
-
 def dsp_case(name):
-    """a d* fixture's inputs, its HF outputs and the patched oracle's outputs for them (computed once per session)"""
-    if name not in _CASES:
-        arch, wseed, input_size, frames, g = load_dsp_case(name)
-        w = weights_for(arch, wseed)
-        torch.set_num_threads(min(16, len(os.sched_getaffinity(0))))
-        xs, sizes = zip(*[orc.preprocess(f, input_size) for f in frames])
-        col = {}
-        with discrete_oracle():
-            out = orc.model_forward(arch, w, torch.cat(xs, 0), list(sizes), collect=col)
-        allowance = [n + 1 for n in dsp_ref.yardstick()[name]["fp32_vs_fp64_rows_outside_1e-3_1e-2px"]]
-        _CASES[name] = dict(name=name, arch=arch, w=w, input_size=input_size, frames=frames, g=g, oracle=[[t.numpy() for t in o] for o in out],
-                            topk=col["topk"].numpy(), enc=col["enc_cls_max"].numpy(), allowance=allowance)
-    return _CASES[name]
+    """a d* fixture's inputs, its HF outputs and the fp32 oracle's outputs for them"""
+    arch, wseed, input_size, frames, g = load_case(name)
+    d = reference_runs(name, arch, weights_for(arch, wseed), frames, input_size)
+    allowance = [n + 1 for n in dsp_ref.yardstick()[name]["fp32_vs_fp64_rows_outside_1e-3_1e-2px"]]
+    d.update(g=d.get("g", g), oracle=d["out32"], topk=d["col32"]["topk"].numpy(), enc=d["col32"]["enc_cls_max"].numpy(), allowance=allowance)
+    return d
 
 
 def unmatched_rows(refs, b, labels, boxes, scores, cut_tol=5e-5):
@@ -144,8 +127,7 @@ def check_rows(case, eng, tag, score_tol=5e-4):
             print(f"{name}[{b}] {tag}: selection differs in {len(diff) // 2} token(s); farthest from the rank-{Q} score: {worst:.2e}")
             assert worst <= 2 * score_tol, (b, worst)
             xb, sz = orc.preprocess(frames[b], case["input_size"])
-            with discrete_oracle():
-                l2, b2, s2 = orc.model_forward(arch, case["w"], xb, [sz], force_topk=tk[b:b + 1])
+            l2, b2, s2 = orc.model_forward(arch, case["w"], xb, [sz], force_topk=tk[b:b + 1])
             refs = [("patched oracle on the engine's selection", {b: l2[0].numpy()}, {b: b2[0].numpy()}, {b: s2[0].numpy()})]
         for rtag, off_cut, at_cut, m, n, ws, wb in unmatched_rows(refs, b, labels, boxes, scores):
             print(f"{name}[{b}] {tag} vs {rtag}: matched {m}/{n} worst dscore={ws:.2e} dbox={wb:.2e}px; unmatched at the top-{Q} cut: {at_cut}, "
@@ -158,7 +140,7 @@ def check_rows(case, eng, tag, score_tol=5e-4):
 @pytest.mark.parametrize("precision", ["fp32", "f16x3"])
 def test_per_op_decoder_tinyc_dsp_matches_fixture_and_patched_oracle(precision):
     case = dsp_case(D2)
-    eng = make_engine(case["arch"], case["w"], case["frames"], case["input_size"], precision)
+    eng = make_engine(case, precision)
     try:
         check_rows(case, eng, f"tinyc_dsp {precision} per-op")
         assert decoder_path(eng, len(case["frames"])) == "per-op"
@@ -169,7 +151,7 @@ def test_per_op_decoder_tinyc_dsp_matches_fixture_and_patched_oracle(precision):
 @pytest.mark.parametrize("precision", ["fp32", "f16x3"])
 def test_fused_decoder_r18_dsp_matches_fixture_and_patched_oracle(precision):
     case = dsp_case(D1)
-    eng = make_engine(case["arch"], case["w"], case["frames"], case["input_size"], precision)
+    eng = make_engine(case, precision)
     try:
         check_rows(case, eng, f"r18_dsp {precision} fused")
         assert decoder_path(eng, len(case["frames"])) == "fused"
@@ -186,7 +168,7 @@ def test_fused_dsp_decoder_equals_per_op_dsp_decoder():
     try:
         for fused in (0, 1):
             _capi.debug_option("dec_fused", fused)
-            eng = make_engine(arch, case["w"], frames, case["input_size"], "fp32")
+            eng = make_engine(case, "fp32")
             try:
                 outs.append(eng.infer_raw(frames) + (eng.debug_tensor(f"dec{arch.dec_layers - 1}.hs"), eng.debug_tensor("ref")))
                 assert decoder_path(eng, len(frames)) == ("fused" if fused else "per-op")
@@ -206,8 +188,8 @@ def test_fused_dsp_decoder_equals_per_op_dsp_decoder():
 @pytest.mark.parametrize("precision", ["fp32", "f16x3"])
 def test_dsp_graph_replay_is_bit_identical_to_eager(precision):
     case = dsp_case(D1)
-    e1 = make_engine(case["arch"], case["w"], case["frames"], case["input_size"], precision, use_graph=False)
-    e2 = make_engine(case["arch"], case["w"], case["frames"], case["input_size"], precision, use_graph=True)
+    e1 = make_engine(case, precision, use_graph=False)
+    e2 = make_engine(case, precision, use_graph=True)
     try:
         a = e1.infer_raw(case["frames"])
         for _ in range(3):                      # build, then two replays
@@ -222,7 +204,7 @@ def test_default_sampler_with_the_same_weights_does_not_match_the_dsp_fixture():
     """the wrong-sampler guard: what a dsp checkpoint served by the bilinear engine would answer is not what HF answers"""
     case = dsp_case(D1)
     g, frames = case["g"], case["frames"]
-    eng = make_engine(ARCHS["r18"], case["w"], frames, case["input_size"], "fp32")
+    eng = make_engine(dict(arch=ARCHS["r18"], w=case["w"], frames=frames, input_size=case["input_size"]), "fp32")
     try:
         labels, boxes, scores = eng.infer_raw(frames)
     finally:
@@ -255,15 +237,14 @@ def rows_of(dets):
 
 
 def test_detector_follows_the_config_path(tmp_path, caplog):
-    """one upstream-layout checkpoint: under a dsp config name it is served with the discrete sampler (== the patched oracle), under
-    the plain name with the bilinear one (== the unpatched oracle); both pass the load-time self check"""
+    """one upstream-layout checkpoint: under a dsp config name it is served with the discrete sampler (== the oracle of tinyc_dsp), under
+    the plain name with the bilinear one (== the oracle of tinyc); both pass the load-time self check"""
     from telescope_cam_detection_amd.rtdetr_detector import RTDETRDetector
     case = dsp_case(D2)
     arch, w, frames, input_size = ARCHS["tinyc"], case["w"], case["frames"], case["input_size"]
     ckpt = str(tmp_path / "rtdetrv2_tinyc.pth")
     write_upstream_checkpoint(ckpt, arch, w)
-    with discrete_oracle():
-        want_dsp = orc.detect_batch(ARCHS["tinyc_dsp"], w, frames, input_size, 0.2, False)
+    want_dsp = orc.detect_batch(ARCHS["tinyc_dsp"], w, frames, input_size, 0.2, False)
     want_plain = orc.detect_batch(arch, w, frames, input_size, 0.2, False)
     for cfg_name, want, other, arch_name, word in (("rtdetrv2_tinyc_dsp.yml", want_dsp, want_plain, "tinyc_dsp", "discrete"),
                                                    ("rtdetrv2_tinyc.yml", want_plain, want_dsp, "tinyc", "bilinear")):

@@ -12,20 +12,18 @@ own error there.  The seeds of a case were searched on the CPU for those three c
 
 Every tolerance of the GPU tests is one the suite already has (test_gpu_parity.py: check_fp32_engine, x3_check and the stage bounds of
 test_f16x3_engine_matches_oracle_and_golden, test_fused_decoder_equals_per_op_decoder).  Measured figures: DESIGN.md, "Head configurations"."""
-import os
 from dataclasses import dataclass, replace
 
-import numpy as np
 import pytest
-import torch
 
 from oracle import rtdetr_oracle as orc
 from telescope_cam_detection_amd.arch import ARCHS
 from telescope_cam_detection_amd.synth import noise_frame, scene_frame
-from tests.util import error_figures, match_detections, to64, weights_for
+from tests.engine_checks import (FUSED, PER_OP, THREE, assert_same, check_f16x3_stages, check_fused_decoder_equals_per_op,
+                                 check_graph_replay_and_batch_invariance, check_side_stream_equals_serial, make_engine, oracle64_refs, plan_paths)
+from tests.util import error_figures, reference_runs, threads, weights_for, well_posed
 
 SIZE = (320, 320)
-FUSED, PER_OP, THREE = "fused", "per-op", "three-launch"
 
 
 @dataclass(frozen=True)
@@ -78,82 +76,31 @@ NAMES = [c.name for c in CASES]
 FUSED_NAMES = [c.name for c in CASES if c.decoder == FUSED]
 POST_FUSED_NAMES = [c.name for c in CASES if c.post == FUSED]
 
-_DATA = {}
-
-
-def _threads():
-    torch.set_num_threads(min(16, len(os.sched_getaffinity(0))))
-
 
 def head_data(name):
-    """a case's frames and its fp64 and fp32 oracle runs, computed once per session and never changed"""
-    if name not in _DATA:
-        case = BY_NAME[name]
-        arch, (wseed, sseed, nseed) = case.arch, case.seeds
-        w = weights_for(arch, wseed)
-        frames = [scene_frame(sseed, *SIZE), noise_frame(nseed, *SIZE)]
-        _threads()
-        xs, sizes = zip(*[orc.preprocess(f, SIZE) for f in frames])
-        x = torch.cat(xs, 0)
-        col32, col64 = {}, {}
-        out32 = orc.model_forward(arch, w, x, list(sizes), collect=col32)
-        w64, x64 = to64(w, x)
-        out64 = orc.model_forward(arch, w64, x64, list(sizes), collect=col64)
-        col64["input"] = x64
-        _DATA[name] = dict(name=name, case=case, arch=arch, w=w, frames=frames, sizes=list(sizes), x=x, input_size=SIZE,
-                           out32=[t.numpy() for t in out32], out64=[t.numpy() for t in out64], col32=col32, col=col64)
-    return _DATA[name]
+    """a case's frames and its fp64 and fp32 oracle runs"""
+    case = BY_NAME[name]
+    arch, (wseed, sseed, nseed) = case.arch, case.seeds
+    d = reference_runs(name, arch, weights_for(arch, wseed), [scene_frame(sseed, *SIZE), noise_frame(nseed, *SIZE)], SIZE)
+    d["case"] = case
+    return d
 
 
 def forced32(d):
     """the fp32 oracle under the fp64 oracle's selection, in its query order: row for row the e_ref of the chain ratios"""
     if "forced32" not in d:
-        _threads()
+        threads()
         col = {}
         orc.model_forward(d["arch"], d["w"], d["x"], d["sizes"], collect=col, force_topk=d["col"]["topk"].numpy())
         d["forced32"] = col
     return d["forced32"]
 
 
-def cut_gap(values, Q):
-    """the gap between rank Q and rank Q + 1 of one frame's keys"""
-    v = np.sort(np.asarray(values, np.float64).ravel())[::-1]
-    return float(v[Q - 1] - v[Q])
-
-
-def by_token(topk_b, rows_b):
-    """a frame's query rows in token order, so that two runs with one token set line up whatever order their top-k gave"""
-    return np.asarray(rows_b)[np.argsort(np.asarray(topk_b), kind="stable")]
-
-
-def sig(x):
-    return 1.0 / (1.0 + np.exp(-np.asarray(x, np.float64)))
-
-
 # ------------------------------------------------------------------------------------------ CPU: the data is well posed
 @pytest.mark.parametrize("name", NAMES)
 def test_reference_is_well_posed(name):
-    d = head_data(name)
-    Q, c32, c64 = d["arch"].num_queries, d["col32"], d["col"]
-    (l32, b32, s32), (l64, b64, s64) = d["out32"], d["out64"]
-    tk32, tk64 = c32["topk"].numpy(), c64["topk"].numpy()
-    mx32, mx64 = c32["enc_cls_max"].numpy().astype(np.float64), c64["enc_cls_max"].numpy()
-    e_sel = float(np.abs(mx32 - mx64).max())
-    for b in range(len(d["frames"])):
-        # 1. no selection flip inside the reference
-        assert set(tk32[b].tolist()) == set(tk64[b].tolist()), (name, b)
-        # 2. every row of the fp32 oracle at the north-star tolerance: the reference alone spends none of the engines' allowances
-        m, n, ws, wb = match_detections(l64[b], b64[b], s64[b], l32[b], b32[b], s32[b], 1e-3, 1e-2)
-        print(f"{name}[{b}] fp32 oracle vs fp64 oracle: matched {m}/{n} worst dscore={ws:.2e} dbox={wb:.2e}px")
-        assert m == n == Q, (name, b, m, n)
-        # 3. both cuts are at least 10 x the fp32 oracle's own worst error on the quantity that is cut
-        sc32 = sig(by_token(tk32[b], c32["logits"][b].numpy()))
-        sc64 = sig(by_token(tk64[b], c64["logits"][b].numpy()))
-        e_post = float(np.abs(sc32 - sc64).max())
-        g_sel, g_post = cut_gap(mx64[b], Q), cut_gap(sc64, Q)
-        print(f"{name}[{b}] selection cut gap {g_sel:.2e} (fp32 oracle err {e_sel:.2e}), post cut gap {g_post:.2e} (err {e_post:.2e})")
-        assert g_sel >= 10 * e_sel, (name, b, g_sel, e_sel)
-        assert g_post >= 10 * e_post, (name, b, g_post, e_post)
+    ok, reasons = well_posed(head_data(name))
+    assert ok, (name, reasons)
 
 
 def test_case_table_covers_the_paths_it_names():
@@ -162,37 +109,11 @@ def test_case_table_covers_the_paths_it_names():
 
 
 # ------------------------------------------------------------------------------------------ GPU
-def make_engine(d, precision, frames=None, use_graph=False):
-    from telescope_cam_detection_amd import _capi
-    from telescope_cam_detection_amd.weights import fold_weights, pack_blob
-    if "blob" not in d:
-        d["blob"] = pack_blob(fold_weights(d["arch"], d["w"]))
-    return _capi.Engine(d["arch"], d["blob"], device=0, precision=_capi.precision_code(precision), max_batch=len(frames or d["frames"]),
-                        input_size=SIZE, use_graph=use_graph)
-
-
-def plan_paths(eng, n):
-    """(decoder, post-processor, AIFI) paths of the plan of batch size n, read from its launch names"""
-    names = [p["name"] for p in eng.profile(n, 1)]
-    fused = "dec.prologue" in names and "dec.l0.fused" in names
-    per_op = "dec.l0.ca.sample" in names
-    assert fused != per_op, names
-    post_fused = "post.fused" in names
-    three = all(x in names for x in ("post.sigmoid", "post.topk", "post.gather"))
-    assert post_fused != three, names
-    return (FUSED if fused else PER_OP, FUSED if post_fused else THREE, FUSED if "enc.aifi.layer" in names else PER_OP)
-
-
 def assert_paths(eng, d):
     case = d["case"]
     got = plan_paths(eng, len(d["frames"]))
     print(f"{case.name}: decoder {got[0]}, post-processor {got[1]}, AIFI {got[2]}")
     assert got == (case.decoder, case.post, case.aifi), (case.name, got)
-
-
-def oracle64_refs(d):
-    l64, b64, s64 = d["out64"]
-    return [("oracle64", l64, b64, s64)]
 
 
 def print_chain_ratios(eng, d, tag):
@@ -237,24 +158,12 @@ def test_f16x3_engine_matches_the_fp64_oracle(name):
     """the stage bounds of test_gpu_parity.test_f16x3_engine_matches_oracle_and_golden, then x3_check (free-running and with the
     reference's selection) against the fp64 oracle"""
     from telescope_cam_detection_amd import _capi
-    from tests.test_gpu_parity import nchw, rel_err, x3_check
+    from tests.test_gpu_parity import x3_check
     d = head_data(name)
     col, frames = d["col"], d["frames"]
     eng = make_engine(d, "f16x3")
     try:
-        eng.infer_raw(frames)
-        np.testing.assert_array_equal(nchw(eng.debug_tensor("input"))[:, :3], col["input"].numpy())
-        for i in range(3):
-            e = rel_err(nchw(eng.debug_tensor(f"backbone{i}")), col[f"backbone{i}"].numpy())
-            print(f"{name} backbone{i} rel l2 err {e:.2e}")
-            assert e < 4e-5, (f"backbone{i}", e)
-        for i in range(3):
-            e = rel_err(nchw(eng.debug_tensor(f"enc{i}")), col[f"enc{i}"].numpy())
-            print(f"{name} enc{i} rel l2 err {e:.2e}")
-            assert e < 1e-4, (f"enc{i}", e)
-        mx = eng.debug_tensor("enc_cls_max")[:, :, 0, 0]
-        print(f"{name} enc score max abs err {np.abs(mx - col['enc_cls_max'].numpy()).max():.2e}")
-        np.testing.assert_allclose(mx, col["enc_cls_max"].numpy(), atol=5e-4)
+        check_f16x3_stages(eng, d)
         x3_check(name, d["arch"], d["w"], SIZE, eng, frames, col["topk"].numpy(), col["enc_cls_max"].numpy(), oracle64_refs(d), 5e-4)
         assert_paths(eng, d)
         print_chain_ratios(eng, d, "f16x3")
@@ -275,54 +184,7 @@ def test_fused_decoder_equals_per_op_decoder(name, precision):
     q1024 and c512_ffn512).  The pass asserts exactly that - both engines select one token set on every frame - and compares hs and ref
     token by token (by_token) and the final rows order-tolerantly.  Then both engines run on the reference's selection in its order, and
     hs and ref are compared row by row as the original test does."""
-    from telescope_cam_detection_amd import _capi
-    d = head_data(name)
-    arch, frames = d["arch"], d["frames"]
-    last = f"dec{arch.dec_layers - 1}.hs"
-    free, forced = [], []
-    try:
-        for fused in (0, 1):
-            _capi.debug_option("dec_fused", fused)
-            eng = make_engine(d, precision)
-            try:
-                rows = eng.infer_raw(frames)
-                free.append(rows + (eng.debug_tensor(last)[:, :, 0, :], eng.debug_tensor("ref")[:, :, 0, :4],
-                                    eng.debug_tensor("topk")[:, :, 0, 0].astype(np.int64)))
-                eng.force_topk(d["col"]["topk"].numpy())
-                forced.append(eng.infer_raw(frames) + (eng.debug_tensor(last), eng.debug_tensor("ref")))
-                eng.force_topk(None)
-                np.testing.assert_array_equal(eng.debug_tensor("topk")[:, :, 0, 0].astype(np.int64), d["col"]["topk"].numpy())
-                assert plan_paths(eng, len(frames))[0] == (FUSED if fused else PER_OP)
-            finally:
-                eng.close()
-    finally:
-        _capi.debug_option("reset", 0)
-
-    def rows_match(tag, l0, b0, s0, l1, b1, s1):
-        for b in range(len(frames)):
-            m, n, ws, wb = match_detections(l0[b], b0[b], s0[b], l1[b], b1[b], s1[b], 1e-5, 2e-3)
-            print(f"{name} {precision} fused vs per-op, {tag} [{b}]: matched {m}/{n} worst dscore={ws:.2e} dbox={wb:.2e}px")
-            assert m == n, (tag, b, m, n, ws, wb)
-
-    (l0, b0, s0, h0, r0, t0), (l1, b1, s1, h1, r1, t1) = free
-    for b in range(len(frames)):
-        assert set(t0[b].tolist()) == set(t1[b].tolist()), (name, b, "the two selection chains chose different token sets")
-        print(f"{name} {precision} free-running [{b}]: {int((t0[b] != t1[b]).sum())} of {t0.shape[1]} ranks hold another token")
-        ha, hb, ra, rb = by_token(t0[b], h0[b]), by_token(t1[b], h1[b]), by_token(t0[b], r0[b]), by_token(t1[b], r1[b])
-        print(f"{name} {precision} free-running [{b}]: max |dhs| {np.abs(hb - ha).max():.3e}, max |dref| {np.abs(rb - ra).max():.3e}")
-        np.testing.assert_allclose(hb, ha, atol=5e-5, rtol=1e-4)
-        np.testing.assert_allclose(rb, ra, atol=2e-6)
-    rows_match("free-running", l0, b0, s0, l1, b1, s1)
-    (l0, b0, s0, h0, r0), (l1, b1, s1, h1, r1) = forced
-    print(f"{name} {precision} fused vs per-op: max |dhs| {np.abs(h1 - h0).max():.3e}, max |dref| {np.abs(r1[..., :4] - r0[..., :4]).max():.3e}")
-    np.testing.assert_allclose(h1, h0, atol=5e-5, rtol=1e-4)
-    np.testing.assert_allclose(r1[..., :4], r0[..., :4], atol=2e-6)
-    rows_match("reference selection", l0, b0, s0, l1, b1, s1)
-
-
-def assert_same(a, b, what):
-    for x, y in zip(a, b):
-        np.testing.assert_array_equal(x, y, err_msg=what)
+    check_fused_decoder_equals_per_op(head_data(name), precision)
 
 
 @pytest.mark.gpu
@@ -330,22 +192,7 @@ def assert_same(a, b, what):
 def test_f16x3_graph_replay_and_batch_invariance(name):
     """graph replay equals eager, and frame i of the bs-2 call equals its bs-1 call, bit for bit: a block's GEMM rotation depends on its
     row tile inside its image only, at every tile count"""
-    from telescope_cam_detection_amd import _capi
-    d = head_data(name)
-    frames = d["frames"]
-    e1, e2 = make_engine(d, "f16x3", use_graph=False), make_engine(d, "f16x3", use_graph=True)
-    try:
-        a = e1.infer_raw(frames)
-        for _ in range(3):                      # build, then two replays
-            g = e2.infer_raw(frames)
-        assert_same(a, g, "graph replay vs eager")
-        for eng in (e1, e2):
-            for i, f in enumerate(frames):
-                one = eng.infer_raw([f])
-                assert_same([t[i:i + 1] for t in a], one, f"frame {i} of the bs-2 call vs its bs-1 call")
-    finally:
-        e1.close(); e2.close()
-        _capi.debug_option("reset", 0)
+    check_graph_replay_and_batch_invariance(head_data(name))
 
 
 @pytest.mark.gpu
@@ -372,21 +219,7 @@ def test_f16x3_one_launch_post_processor_equals_three_launches(name):
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", NAMES)
 def test_f16x3_side_stream_plan_equals_the_serial_plan(name):
-    from telescope_cam_detection_amd import _capi
-    d = head_data(name)
-    frames, got = d["frames"], {}
-    try:
-        for v in (0, 7):
-            _capi.debug_option("side_stream", v)
-            eng = make_engine(d, "f16x3", use_graph=True)
-            try:
-                for _ in range(3):
-                    got[v] = eng.infer_raw(frames)
-            finally:
-                eng.close()
-    finally:
-        _capi.debug_option("reset", 0)
-    assert_same(got[0], got[7], "side_stream 0 vs 7")
+    check_side_stream_equals_serial(head_data(name))
 
 
 @pytest.mark.gpu

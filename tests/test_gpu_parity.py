@@ -13,27 +13,15 @@ import pytest
 import torch
 
 from oracle import rtdetr_oracle as orc
-from tests.util import load_case, match_detections, weights_for
+from tests import engine_checks
+from tests.util import load_case, match_detections, oracle_run, threads, weights_for
 
 pytestmark = pytest.mark.gpu
 
 
 def make_engine(arch, w, frames, input_size, precision, use_graph=False, profile=0):
-    from telescope_cam_detection_amd import _capi
-    from telescope_cam_detection_amd.weights import fold_weights, pack_blob
-    blob = pack_blob(fold_weights(arch, w))
-    prec = _capi.precision_code(precision)
-    return _capi.Engine(arch, blob, device=0, precision=prec, max_batch=len(frames), input_size=input_size, use_graph=use_graph,
-                        profile=profile)
-
-
-def oracle_run(arch, w, frames, input_size):
-    torch.set_num_threads(min(16, len(__import__('os').sched_getaffinity(0))))
-    xs, sizes = zip(*[orc.preprocess(f, input_size) for f in frames])
-    col = {}
-    out = orc.model_forward(arch, w, torch.cat(xs, 0), list(sizes), collect=col)
-    col["input"] = torch.cat(xs, 0)
-    return out, col
+    """tests.engine_checks.make_engine for call sites that hold a case's parts, not its dict"""
+    return engine_checks.make_engine(dict(arch=arch, w=w, frames=frames, input_size=input_size), precision, use_graph=use_graph, profile=profile)
 
 
 def rel_err(a, b):
@@ -159,7 +147,7 @@ def x3_check(name, arch, w, input_size, eng, frames, ref_topk, ref_scores_all, r
             print(f"{name}[{b}] selection differs in {len(diff) // 2} token(s); farthest from the rank-{Q} score: {worst:.2e}")
             assert worst <= 2 * score_tol, (b, worst)
             # the oracle on THIS selection (frame b alone: frames are independent units)
-            torch.set_num_threads(min(16, len(__import__('os').sched_getaffinity(0))))
+            threads()
             xb, sz = orc.preprocess(frames[b], input_size)
             with torch.no_grad():
                 l2, b2, s2 = orc.model_forward(arch, w, xb, [sz], force_topk=tk[b:b + 1])

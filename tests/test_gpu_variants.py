@@ -17,7 +17,8 @@ import torch
 from oracle import rtdetr_oracle as orc
 from telescope_cam_detection_amd.arch import ARCHS
 from tests import variants_ref as vr
-from tests.test_gpu_head_configs import assert_same, by_token, plan_paths
+from tests.engine_checks import (check_f16x3_stages, check_fused_decoder_equals_per_op, check_graph_replay_and_batch_invariance,
+                                 check_side_stream_equals_serial, make_engine, oracle64_refs, plan_paths)
 from tests.util import match_detections
 
 pytestmark = pytest.mark.gpu
@@ -31,24 +32,10 @@ def data(name):
     return vr.fixture_data(name) if name in vr.POINTS_CASES else vr.engine_data(name)
 
 
-def make_engine(d, precision, frames=None, use_graph=False):
-    from telescope_cam_detection_amd import _capi
-    from telescope_cam_detection_amd.weights import fold_weights, pack_blob
-    if "blob" not in d:
-        d["blob"] = pack_blob(fold_weights(d["arch"], d["w"]))
-    return _capi.Engine(d["arch"], d["blob"], device=0, precision=_capi.precision_code(precision), max_batch=len(frames or d["frames"]),
-                        input_size=d["input_size"], use_graph=use_graph)
-
-
 def assert_decoder_path(eng, d):
     got = plan_paths(eng, len(d["frames"]))[0]
     print(f"{d['name']}: decoder {got}")
     assert got == d["decoder"], (d["name"], got)
-
-
-def oracle64_refs(d):
-    l64, b64, s64 = d["out64"]
-    return [("oracle64", l64, b64, s64)]
 
 
 def dsp_case_of(d):
@@ -81,24 +68,12 @@ def test_f16x3_engine_matches_the_fp64_oracle(name):
     discrete sampler test_gpu_dsp.check_rows with its allowance instead"""
     from telescope_cam_detection_amd import _capi
     from tests.test_gpu_dsp import check_rows
-    from tests.test_gpu_parity import nchw, rel_err, x3_check
+    from tests.test_gpu_parity import x3_check
     d = data(name)
     col, frames, arch = d["col"], d["frames"], d["arch"]
     eng = make_engine(d, "f16x3")
     try:
-        eng.infer_raw(frames)
-        np.testing.assert_array_equal(nchw(eng.debug_tensor("input"))[:, :3], col["input"].numpy())
-        for i in range(3):
-            e = rel_err(nchw(eng.debug_tensor(f"backbone{i}")), col[f"backbone{i}"].numpy())
-            print(f"{name} backbone{i} rel l2 err {e:.2e}")
-            assert e < 4e-5, (f"backbone{i}", e)
-        for i in range(3):
-            e = rel_err(nchw(eng.debug_tensor(f"enc{i}")), col[f"enc{i}"].numpy())
-            print(f"{name} enc{i} rel l2 err {e:.2e}")
-            assert e < 1e-4, (f"enc{i}", e)
-        mx = eng.debug_tensor("enc_cls_max")[:, :, 0, 0]
-        print(f"{name} enc score max abs err {np.abs(mx - col['enc_cls_max'].numpy()).max():.2e}")
-        np.testing.assert_allclose(mx, col["enc_cls_max"].numpy(), atol=5e-4)
+        check_f16x3_stages(eng, d)
         if arch.dec_method == "discrete":
             check_rows(dsp_case_of(d), eng, f"{name} f16x3")
         else:
@@ -115,93 +90,23 @@ def test_f16x3_engine_matches_the_fp64_oracle(name):
 def test_fused_decoder_equals_per_op_decoder(name, precision):
     """dec_fused 1 against 0 at 2 and 3 points, both samplers: tests.test_gpu_head_configs.test_fused_decoder_equals_per_op_decoder on
     these cases, same bounds, same two passes (free-running by token, then under the reference's selection row by row)"""
-    from telescope_cam_detection_amd import _capi
-    d = data(name)
-    arch, frames = d["arch"], d["frames"]
-    last = f"dec{arch.dec_layers - 1}.hs"
-    free, forced = [], []
-    try:
-        for fused in (0, 1):
-            _capi.debug_option("dec_fused", fused)
-            eng = make_engine(d, precision)
-            try:
-                rows = eng.infer_raw(frames)
-                free.append(rows + (eng.debug_tensor(last)[:, :, 0, :], eng.debug_tensor("ref")[:, :, 0, :4],
-                                    eng.debug_tensor("topk")[:, :, 0, 0].astype(np.int64)))
-                eng.force_topk(d["col"]["topk"].numpy())
-                forced.append(eng.infer_raw(frames) + (eng.debug_tensor(last), eng.debug_tensor("ref")))
-                eng.force_topk(None)
-                np.testing.assert_array_equal(eng.debug_tensor("topk")[:, :, 0, 0].astype(np.int64), d["col"]["topk"].numpy())
-                assert plan_paths(eng, len(frames))[0] == (vr.FUSED if fused else vr.PER_OP)
-            finally:
-                eng.close()
-    finally:
-        _capi.debug_option("reset", 0)
-
-    def rows_match(tag, l0, b0, s0, l1, b1, s1):
-        for b in range(len(frames)):
-            m, n, ws, wb = match_detections(l0[b], b0[b], s0[b], l1[b], b1[b], s1[b], 1e-5, 2e-3)
-            print(f"{name} {precision} fused vs per-op, {tag} [{b}]: matched {m}/{n} worst dscore={ws:.2e} dbox={wb:.2e}px")
-            assert m == n, (tag, b, m, n, ws, wb)
-
-    (l0, b0, s0, h0, r0, t0), (l1, b1, s1, h1, r1, t1) = free
-    for b in range(len(frames)):
-        assert set(t0[b].tolist()) == set(t1[b].tolist()), (name, b, "the two selection chains chose different token sets")
-        ha, hb, ra, rb = by_token(t0[b], h0[b]), by_token(t1[b], h1[b]), by_token(t0[b], r0[b]), by_token(t1[b], r1[b])
-        print(f"{name} {precision} free-running [{b}]: max |dhs| {np.abs(hb - ha).max():.3e}, max |dref| {np.abs(rb - ra).max():.3e}")
-        np.testing.assert_allclose(hb, ha, atol=5e-5, rtol=1e-4)
-        np.testing.assert_allclose(rb, ra, atol=2e-6)
-    rows_match("free-running", l0, b0, s0, l1, b1, s1)
-    (l0, b0, s0, h0, r0), (l1, b1, s1, h1, r1) = forced
-    print(f"{name} {precision} fused vs per-op: max |dhs| {np.abs(h1 - h0).max():.3e}, max |dref| {np.abs(r1[..., :4] - r0[..., :4]).max():.3e}")
-    np.testing.assert_allclose(h1, h0, atol=5e-5, rtol=1e-4)
-    np.testing.assert_allclose(r1[..., :4], r0[..., :4], atol=2e-6)
-    rows_match("reference selection", l0, b0, s0, l1, b1, s1)
+    check_fused_decoder_equals_per_op(data(name), precision)
 
 
 # ------------------------------------------------------------------------------------------ 3. bit-exact equalities
 @pytest.mark.parametrize("name", ALL_CASES)
 def test_f16x3_graph_replay_and_batch_invariance(name):
-    from telescope_cam_detection_amd import _capi
-    d = data(name)
-    frames = d["frames"]
-    e1, e2 = make_engine(d, "f16x3", use_graph=False), make_engine(d, "f16x3", use_graph=True)
-    try:
-        a = e1.infer_raw(frames)
-        for _ in range(3):                      # build, then two replays
-            g = e2.infer_raw(frames)
-        assert_same(a, g, "graph replay vs eager")
-        for eng in (e1, e2):
-            for i, f in enumerate(frames):
-                one = eng.infer_raw([f])
-                assert_same([t[i:i + 1] for t in a], one, f"frame {i} of the bs-2 call vs its bs-1 call")
-    finally:
-        e1.close(); e2.close()
-        _capi.debug_option("reset", 0)
+    check_graph_replay_and_batch_invariance(data(name))
 
 
 @pytest.mark.parametrize("name", ALL_CASES)
 def test_f16x3_side_stream_plan_equals_the_serial_plan(name):
-    from telescope_cam_detection_amd import _capi
-    d = data(name)
-    frames, got = d["frames"], {}
-    try:
-        for v in (0, 7):
-            _capi.debug_option("side_stream", v)
-            eng = make_engine(d, "f16x3", use_graph=True)
-            try:
-                for _ in range(3):
-                    got[v] = eng.infer_raw(frames)
-            finally:
-                eng.close()
-    finally:
-        _capi.debug_option("reset", 0)
-    assert_same(got[0], got[7], "side_stream 0 vs 7")
+    check_side_stream_equals_serial(data(name))
 
 
 # ------------------------------------------------------------------------------------------ 4. against the HF rows
 @pytest.mark.parametrize("precision", ["fp32", "f16x3"])
-@pytest.mark.parametrize("name", list(vr.POINTS_CASES))
+@pytest.mark.parametrize("name", vr.POINTS_CASES)
 def test_engine_matches_the_hf_fixture_rows(name, precision):
     """1e-3 / 1e-2 px against HF's rows; the allowance is the yardstick's, which is zero on every frame by the choice of seeds"""
     d = data(name)

@@ -1,6 +1,6 @@
 """CPU: the r50vd_m and sp1 / sp2 / sp3 variants without a GPU - what selects them (config path and YAML -> Arch, checkpoint shapes -> Arch),
-the oracle against the HF fixtures tools/make_points_golden.py wrote, and that the data of every GPU case of tests/test_gpu_variants.py
-is well posed before an engine is judged on it (tests/variants_ref.py)."""
+the oracle against the HF fixtures oracle/make_golden.py wrote, and that the data of every GPU case of tests/test_gpu_variants.py
+is well posed before an engine is judged on it (tests.util.well_posed)."""
 import dataclasses
 
 import numpy as np
@@ -13,7 +13,7 @@ from telescope_cam_detection_amd import checkpoint as ck
 from telescope_cam_detection_amd.arch import ARCHS, UnsupportedVariant, arch_from_config_path
 from telescope_cam_detection_amd.weights import synth_weights
 from tests import variants_ref as vr
-from tests.util import match_detections, sample, weights_for
+from tests.util import match_detections, sample, weights_for, well_posed
 
 UPSTREAM = "RT-DETR/rtdetrv2_pytorch/configs/rtdetrv2/"
 NEW_ARCHS = ["r50_m", "r50_m_dsp", "r18_sp1", "r18_sp2", "r18_sp3"]
@@ -202,7 +202,7 @@ def test_synthetic_model_paths_name_the_new_variants():
 
 
 # ------------------------------------------------------------------------------------------ oracle against the HF fixtures
-@pytest.mark.parametrize("name", list(vr.POINTS_CASES))
+@pytest.mark.parametrize("name", vr.POINTS_CASES)
 def test_oracle_matches_the_hf_fixture(name):
     """tests/test_oracle_golden.py's test_oracle_matches_golden on the new files, same bounds"""
     d = vr.fixture_data(name)
@@ -247,11 +247,11 @@ def test_the_point_count_shows_in_the_fixtures():
 def test_engine_case_is_well_posed(name):
     d = vr.engine_data(name)
     assert sum(h * w for h, w in d["arch"].level_shapes(*vr.SIZE)) == 2100 and d["arch"].num_queries == 300 == 18 * 16 + 12
-    ok, bad = vr.well_posed(d)
+    ok, bad = well_posed(d)
     assert ok, bad
 
 
-@pytest.mark.parametrize("name", list(vr.POINTS_CASES))
+@pytest.mark.parametrize("name", vr.POINTS_CASES)
 def test_fixture_case_is_well_posed(name):
-    ok, bad = vr.well_posed(vr.fixture_data(name))
+    ok, bad = well_posed(vr.fixture_data(name))
     assert ok, bad

@@ -1,30 +1,27 @@
-"""Shared helpers for the parity tests (fixtures -> inputs, order-tolerant comparators)."""
+"""Shared helpers for the parity tests (fixtures -> inputs, a case's oracle runs and whether they are well posed, order-tolerant
+comparators)."""
 import os
 
 import numpy as np
 import torch
 
+from oracle import rtdetr_oracle as orc
+from oracle.make_golden import CASES
 from telescope_cam_detection_amd.arch import ARCHS
 from telescope_cam_detection_amd.synth import make_frame
 from telescope_cam_detection_amd.weights import synth_weights
 
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
-# fixture name -> arch (the .npz carries seeds / sizes / frame list itself)
-CASE_ARCH = {
-    "c1_r18_640_bs1": "r18", "c1_r18_640_scene": "r18", "c1_r18_640_resize": "r18",
-    "c2_r50_640_bs8": "r50", "c2_r50_640_scene_bs2": "r50", "c3_r101_1280_bs1": "r101", "c3_r101_1280_bs4": "r101", "c4_r18_1920_bs1": "r18",
-    "t_tiny_160": "tiny", "t_tiny_160x224": "tiny", "t_tinyb_192x128": "tinyb", "t_tinyc_160x224": "tinyc",
-}
-
 
 def load_case(name):
+    """(arch, weight seed, input size, frames, npz) of a fixture; the arch comes from the generator's table, and the seeds, sizes and
+    frame list the file carries must be that table's row"""
     g = np.load(os.path.join(GOLDEN_DIR, name + ".npz"))
-    arch = ARCHS[CASE_ARCH[name]]
-    wseed, ih, iw, n = (int(v) for v in g["meta"])
-    kind = str(g["kind"])
-    frames = [make_frame(kind, int(s), int(h), int(w)) for s, h, w in g["frames"]]
-    return arch, wseed, (ih, iw), frames, g
+    arch_name, wseed, input_size, frame_specs, kind = CASES[name]
+    assert ([int(v) for v in g["meta"]], [tuple(int(v) for v in f) for f in g["frames"]], str(g["kind"])) == \
+        ([wseed, *input_size, len(frame_specs)], frame_specs, kind), name
+    return ARCHS[arch_name], wseed, input_size, [make_frame(kind, *f) for f in frame_specs], g
 
 
 _WCACHE = {}
@@ -47,6 +44,82 @@ def sample(t, n=2048):
     f = torch.as_tensor(t).detach().float().flatten()
     step = max(1, f.numel() // n)
     return f[::step][:n].numpy()
+
+
+def threads():
+    torch.set_num_threads(min(16, len(os.sched_getaffinity(0))))
+
+
+def oracle_run(arch, w, frames, input_size, double=False):
+    """one oracle run on a case's frames, in fp32 or with weights and input cast to double -> ((labels, boxes, scores), the collected
+    stages with the network input under "input")"""
+    threads()
+    x = torch.cat([orc.preprocess(f, input_size)[0] for f in frames], 0)
+    if double:
+        w, x = to64(w, x)
+    col = {}
+    out = orc.model_forward(arch, w, x, [(f.shape[1], f.shape[0]) for f in frames], collect=col)
+    col["input"] = x
+    return out, col
+
+
+_RUNS = {}
+
+
+def reference_runs(name, arch, w, frames, input_size):
+    """a case's frames and its fp32 and fp64 oracle runs, computed once per session and never changed (check_fp32_engine and x3_check of
+    tests/test_gpu_parity.py read this layout: "col" is the fp64 run's stages)"""
+    if (name, arch) not in _RUNS:
+        out32, col32 = oracle_run(arch, w, frames, input_size)
+        out64, col64 = oracle_run(arch, w, frames, input_size, double=True)
+        _RUNS[name, arch] = dict(name=name, arch=arch, w=w, frames=frames, sizes=[(f.shape[1], f.shape[0]) for f in frames], x=col32["input"],
+                                 input_size=input_size, out32=[t.numpy() for t in out32], out64=[t.numpy() for t in out64], col32=col32, col=col64)
+    return _RUNS[name, arch]
+
+
+def cut_gap(values, Q):
+    """the gap between rank Q and rank Q + 1 of one frame's keys"""
+    v = np.sort(np.asarray(values, np.float64).ravel())[::-1]
+    return float(v[Q - 1] - v[Q])
+
+
+def by_token(topk_b, rows_b):
+    """a frame's query rows in token order, so that two runs with one token set line up whatever order their top-k gave"""
+    return np.asarray(rows_b)[np.argsort(np.asarray(topk_b), kind="stable")]
+
+
+def sig(x):
+    return 1.0 / (1.0 + np.exp(-np.asarray(x, np.float64)))
+
+
+def well_posed(d):
+    """the three conditions under which a case's reference_runs may judge an engine -> (ok, [reason, ...]); prints every figure"""
+    name, Q, c32, c64 = d["name"], d["arch"].num_queries, d["col32"], d["col"]
+    (l32, b32, s32), (l64, b64, s64) = d["out32"], d["out64"]
+    tk32, tk64 = c32["topk"].numpy(), c64["topk"].numpy()
+    mx32, mx64 = c32["enc_cls_max"].numpy().astype(np.float64), c64["enc_cls_max"].numpy()
+    e_sel = float(np.abs(mx32 - mx64).max())
+    bad = []
+    for b in range(len(d["frames"])):
+        # 1. no selection flip inside the reference
+        if set(tk32[b].tolist()) != set(tk64[b].tolist()):
+            bad.append(f"[{b}] the fp32 oracle selects other tokens than the fp64 oracle")
+            continue
+        # 2. every row of the fp32 oracle at the north-star tolerance: the reference alone spends none of the engines' allowances
+        m, n, ws, wb = match_detections(l64[b], b64[b], s64[b], l32[b], b32[b], s32[b], 1e-3, 1e-2)
+        print(f"{name}[{b}] fp32 oracle vs fp64 oracle: matched {m}/{n} worst dscore={ws:.2e} dbox={wb:.2e}px")
+        if not m == n == Q:
+            bad.append(f"[{b}] fp32 oracle rows matched {m}/{n}")
+        # 3. both cuts are at least 10 x the fp32 oracle's own worst error on the quantity that is cut
+        sc32, sc64 = sig(by_token(tk32[b], c32["logits"][b].numpy())), sig(by_token(tk64[b], c64["logits"][b].numpy()))
+        e_post = float(np.abs(sc32 - sc64).max())
+        g_sel, g_post = cut_gap(mx64[b], Q), cut_gap(sc64, Q)
+        print(f"{name}[{b}] selection cut gap {g_sel:.2e} (fp32 oracle err {e_sel:.2e}), post cut gap {g_post:.2e} (err {e_post:.2e})")
+        if g_sel < 10 * e_sel:
+            bad.append(f"[{b}] selection cut gap {g_sel:.2e} < 10 x {e_sel:.2e}")
+        if g_post < 10 * e_post:
+            bad.append(f"[{b}] post cut gap {g_post:.2e} < 10 x {e_post:.2e}")
+    return not bad, bad
 
 
 def match_detections(ref_labels, ref_boxes, ref_scores, labels, boxes, scores, score_tol, box_tol, return_unmatched=False):
