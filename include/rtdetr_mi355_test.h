@@ -81,6 +81,39 @@ int rtd_op_conv_dual(int dtype, const void* x, const void* x2, const void* w_f32
 int rtd_op_conv_next(int dtype, const void* x, const void* x2, const void* w_f32, const float* bias, const void* res, void* y,
                      const void* w1_f32, const float* bias1, void* y1, int B, int H, int W, int Cin, int C2, int Cout, int Cnext,
                      int act, int res_mode, int next_act);
+/* ... on F16X2 operands, with the 2 x 2 / stride-2 average of y written by the same launch: avg_y [B, H/2, W/2, Cout] (how the plan ends a
+ * stage of a vd net: ConvArgs::avg_y).  Cnext = 0: no follower (w1_f32, bias1, y1 may be NULL).  y_dead = 1 (with a follower): the
+ * launch drops the stores of y - the call still takes a y buffer and leaves it untouched.  RTD_E_INVALID before any launch, with
+ * nothing written, for what conv_avg_supported() refuses (odd H, W % 16 != 0, no residual, other channel counts than 64 -> 256 + a
+ * 128-channel follower or 128 -> N alone, maps below 80 x 80). */
+int rtd_op_conv_avg(const void* x, const void* w_f32, const float* bias, const void* res, void* y, const void* w1_f32, const float* bias1,
+                    void* y1, void* avg_y, int B, int H, int W, int Cin, int Cout, int Cnext, int act, int res_mode, int next_act,
+                    int y_dead);
+/* stem.2 and the max-pool in one pass (launch_conv_pool): x [B, H, W, 32] F16X2, w_ohwi_f32 [64][3][3][32], ReLU, then 3x3 / stride 2 /
+ * pad 1 max -> pooled [B, H/2, W/2, 64] F16X2; the conv rows are never written.  RTD_E_INVALID before any launch for what
+ * conv_pool_supported() refuses (odd extents, fewer than 32 tiles of 8 x 32 pixels per image, conv_reg 0). */
+int rtd_op_conv_pool(const void* x, const void* w_ohwi_f32, const float* bias, void* pooled, int B, int H, int W);
+
+/* ---- which conv kernel: the choice behind launch_conv, readable.  Host arithmetic only: no device call, usable without a GPU.
+ * A choice is a text key naming ONE instantiation plus info[12] = family, stages, bn, mt, bm, smallc, wsq, sx, cog, S, grid, ntn
+ * (family: 0 tile, 1 ws, 2 sx, 3 reg3x3, 4 reg3x3_64, 5 wsf, 6 wsq, 7 wsx; S = slices of the two-pass split-K, > 1: k_splitk_reduce
+ * follows; grid in blocks; fields a family does not use are 0, wsq / sx -1).  Keys:
+ *   tile.<bf16|f32>.<BM>x<BN>.smallc<0|1>   conv_igemm_kernel          ws.<bf16|f32>.s<stages>.bn<BN>   conv_igemm_ws_kernel
+ *   wsx.s<stages>.bn<BN>                    conv_igemm_wsx_kernel      wsf.s<stages>.bn<BN>.mt<MT>      conv_igemm_wsf_kernel
+ *   wsq.<MTA>x<MTB>                         conv_igemm_wsq_kernel      reg3x3_64                        conv3x3_reg_split64_kernel
+ *   reg3x3.cog<1|2>[.pool]                  conv3x3_reg_split_kernel (.pool: <2, true> + k_pool_fixup)
+ *   sx.x<NGX>.x2_<NG2>.res<0|1>.next<N>.f32_<0|1>.avg<0|1>             conv1x1_sx_kernel
+ * rtd_debug_conv_choice: what launch_conv would launch NOW (the rtd_debug_option template as it stands) for the launch rtd_op_conv /
+ *   _dual / _next / _avg / _pool would describe: dense tensors, res and x2 in `dtype`, H and W the input extents (x_up2: the output
+ *   extents), Cnext = 0 no follower, avg / pool 0 or 1 (pool: the launch_conv_pool form).  It runs the launchers' own checks and choice
+ *   functions: a launch they refuse is refused here with the same error (rtd_last_error(NULL)).
+ * rtd_debug_last_conv: what the calling thread's last launch_conv / launch_conv_pool did launch (RTD_E_STATE before the first).
+ * rtd_debug_conv_instantiations: the keys of every instantiation the launchers can name, one per line, generated from the tables the
+ *   launchers instantiate from; *needed = bytes including the final NUL (out may be NULL to ask). */
+int rtd_debug_conv_choice(int dtype, int B, int H, int W, int Cin, int C2, int Cout, int KH, int stride, int pad, int res_mode, int out_f32,
+                          int x_up2, int Cnext, int avg, int pool, char* key, int key_capacity, int32_t* info);
+int rtd_debug_last_conv(char* key, int key_capacity, int32_t* info);
+int rtd_debug_conv_instantiations(char* out, int64_t capacity, int64_t* needed);
 int rtd_op_layernorm(int dtype, const void* x, const void* res, const float* g, const float* b,
                      void* y, int rows, int dim, int out_f32);
 int rtd_op_attention(int dtype, const void* qk, const void* v, void* o, int B, int L, int heads, int hd);

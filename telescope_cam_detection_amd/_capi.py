@@ -132,7 +132,9 @@ TEST_EXPORTS = [
     "rtd_op_conv_view", "rtd_bench_conv_act", "rtd_debug_esrgan_tensor",
     "rtd_op_msdeform_view", "rtd_op_select_score", "rtd_op_gather_ln", "rtd_op_split_convert", "rtd_op_set_rows", "rtd_op_rowmax",
     "rtd_op_gather_rows", "rtd_op_boxes", "rtd_op_add", "rtd_op_postprocess", "rtd_op_msdeform_discrete_view",
+    "rtd_op_conv_avg", "rtd_op_conv_pool", "rtd_debug_conv_choice", "rtd_debug_last_conv", "rtd_debug_conv_instantiations",
 ]
+CONV_INFO_FIELDS = ("family", "stages", "bn", "mt", "bm", "smallc", "wsq", "sx", "cog", "S", "grid", "ntn")   # info[12] of the conv-choice calls
 
 
 def lib() -> C.CDLL:
@@ -280,6 +282,12 @@ def lib() -> C.CDLL:
         L.rtd_op_postprocess.argtypes = [vp, vp, vp, i32, i32, i32, i32, i32, vp]
     if hasattr(L, "rtd_op_msdeform_discrete_view"):      # (absent from older builds loaded through RTD_LIB_PATH)
         L.rtd_op_msdeform_discrete_view.argtypes = L.rtd_op_msdeform_view.argtypes
+    if hasattr(L, "rtd_debug_conv_choice"):
+        L.rtd_op_conv_avg.argtypes = [vp] * 9 + [i32] * 10
+        L.rtd_op_conv_pool.argtypes = [vp, vp, vp, vp, i32, i32, i32]
+        L.rtd_debug_conv_choice.argtypes = [i32] * 16 + [C.c_char_p, i32, C.POINTER(i32)]
+        L.rtd_debug_last_conv.argtypes = [C.c_char_p, i32, C.POINTER(i32)]
+        L.rtd_debug_conv_instantiations.argtypes = [C.c_char_p, i64, C.POINTER(i64)]
     _lib = L
     return L
 
@@ -288,6 +296,36 @@ def debug_option(name: str, value: int) -> None:
     rc = lib().rtd_debug_option(name.encode(), int(value))
     if rc != RTD_OK:
         raise ValueError(f"unknown debug option {name!r}")
+
+
+def _conv_report(call, *args):
+    key, info = C.create_string_buffer(64), (C.c_int32 * 12)()
+    rc = call(*args, key, 64, info)
+    if rc != RTD_OK:
+        return None
+    return dict(zip(CONV_INFO_FIELDS, info), key=key.value.decode())
+
+
+def conv_choice(dtype: int, B: int, H: int, W: int, Cin: int, Cout: int, k: int = 1, stride: int = 1, pad: int = 0, res_mode: int = 0,
+                out_f32: int = 0, C2: int = 0, x_up2: int = 0, Cnext: int = 0, avg: int = 0, pool: int = 0):
+    """What launch_conv would launch for this launch under the debug options as they stand (rtd_debug_conv_choice: no GPU needed):
+    {'key': ..., 'family': ..., 'S': ..., 'grid': ...}, or None when the launchers refuse it."""
+    return _conv_report(lib().rtd_debug_conv_choice, dtype, B, H, W, Cin, C2, Cout, k, stride, pad, res_mode, out_f32, x_up2, Cnext, avg, pool)
+
+
+def last_conv():
+    """What this thread's last launch_conv / launch_conv_pool launched (rtd_debug_last_conv); None before the first."""
+    return _conv_report(lib().rtd_debug_last_conv)
+
+
+def conv_instantiations() -> list:
+    """The key of every conv kernel instantiation the launchers can name (rtd_debug_conv_instantiations)."""
+    need = C.c_int64(0)
+    lib().rtd_debug_conv_instantiations(None, 0, C.byref(need))
+    buf = C.create_string_buffer(need.value)
+    rc = lib().rtd_debug_conv_instantiations(buf, need.value, None)
+    assert rc == RTD_OK, rc
+    return buf.value.decode().split()
 
 
 class RtdError(RuntimeError):

@@ -234,6 +234,18 @@ bool conv_pool_supported(const ConvArgs& a, const Tensor& pooled);
 size_t conv_pool_side_bytes(const ConvArgs& a);
 void launch_conv_pool(const ConvArgs& a, const Tensor& pooled, void* side, hipStream_t s);
 size_t conv_split_slab_bytes(const ConvArgs& a);   // workspace the launch would use for its two-pass split-K (0 = it does not split)
+// ---- the kernel choice, readable (tests only; rtd_debug_conv_choice / rtd_debug_last_conv / rtd_debug_conv_instantiations).
+// key names one instantiation ("wsf.s3.bn128.mt11", "wsq.7x6", "tile.bf16.128x64.smallc1", "reg3x3.cog2.pool", ...); fields a family
+// does not use keep ConvChoice's defaults (0, wsq / sx -1).  S = slices of the two-pass split-K (> 1: k_splitk_reduce follows).
+struct ConvChoiceReport {
+  char key[64];
+  int family, stages, bn, mt, bm, smallc, wsq, sx, cog, S, grid, ntn;
+};
+// what launch_conv(a) - with `pooled`, launch_conv_pool(a, *pooled) - would launch: the launchers' own checks (throws rtd::Error as
+// they do) and choice functions, host arithmetic only
+ConvChoiceReport conv_predict(const ConvArgs& a, const Tensor* pooled);
+bool conv_last_choice(ConvChoiceReport* out);        // the calling thread's last launch_conv / launch_conv_pool; false = none yet
+std::vector<std::string> conv_instantiation_keys();  // every key the launchers can name, from their constexpr tables
 
 void launch_layernorm(const Tensor& x, const Tensor* res, const float* g, const float* b, const Tensor& y,
                       float eps, hipStream_t s);

@@ -2051,6 +2051,8 @@ enum class ConvFamily {
 };
 struct ConvChoice {
   ConvFamily family = ConvFamily::Tile;
+  int dt = F32;              // operand type: Tile, Ws are instantiated per type (bf16 / fp32); every other family reads pairs
+  bool pool = false;         // Reg3x3 behind launch_conv_pool(): conv3x3_reg_split_kernel<2, true> + k_pool_fixup
   int stages = 0, bn = 0;    // Ws, Wsf, Wsx; Tile: bn
   int mt = 0;                // Wsf
   int bm = 0;                // Tile
@@ -2094,6 +2096,7 @@ static bool glds_takes(const ConvOpts& o, const ConvArgs& a, const ConvGeom& g, 
 static ConvChoice choose_plain(const ConvArgs& a, const ConvGeom& g, const ConvOpts& o, long long w_bytes) {
   const int N = a.y.c;
   ConvChoice c;
+  c.dt = a.x.dt;
   if (a.y.dt != F16X2 && !(o.conv_mode == 1 && !g.dual) && glds_takes(o, a, g, w_bytes)) {
     const long long mt = (g.M + 127) / 128, ntn = (N + 127) / 128;
     c.family = ConvFamily::Ws;
@@ -2247,6 +2250,7 @@ static ConvChoice choose_pair(const ConvArgs& a, const ConvGeom& g, const ConvOp
   const Tensor& x = a.x;
   const Tensor& y = a.y;
   ConvChoice c;
+  c.dt = F16X2;
   const int S = c.S = split_k2_slices(o, a, g);
   // thin 1x1 expand convs on wide grids (stage-0 / stage-1 c3): the streaming kernel, with the next block's reduce conv riding on it
   if (choose_sx(a, c)) return c;
@@ -2331,6 +2335,74 @@ static ConvChoice choose_pair(const ConvArgs& a, const ConvGeom& g, const ConvOp
 
 // ---- the launch: instantiates what the choice names ---------------------------------------------------------------------------------
 static constexpr int TILE_BMN[3][2] = {{128, 128}, {128, 64}, {64, 64}};   // the instantiated conv_igemm_kernel<T, BM, BN, smallc>
+
+// ---- the choice as text (tests): one key per instantiation the launchers below can name.  The slice count S is not part of the key
+// (k_splitk_reduce follows the same tile kernel); conv_report() carries it beside the key.
+static std::string sx_key(int i) {
+  const SxVariant& v = SX_VARIANTS[i];
+  char b[64];
+  snprintf(b, sizeof b, "sx.x%d.x2_%d.res%d.next%d.f32_%d.avg%d", v.ngx, v.ng2, (int)v.res, v.nextn, (int)v.f32out, (int)v.avg);
+  return b;
+}
+static std::string choice_key(const ConvChoice& c) {
+  const char* T = c.dt == BF16 ? "bf16" : "f32";
+  char b[64];
+  switch (c.family) {
+    case ConvFamily::Tile: snprintf(b, sizeof b, "tile.%s.%dx%d.smallc%d", T, c.bm, c.bn, (int)c.smallc); break;
+    case ConvFamily::Ws: snprintf(b, sizeof b, "ws.%s.s%d.bn%d", T, c.stages, c.bn); break;
+    case ConvFamily::Sx: return sx_key(c.sx);
+    case ConvFamily::Reg3x3: snprintf(b, sizeof b, "reg3x3.cog%d%s", c.cog, c.pool ? ".pool" : ""); break;
+    case ConvFamily::Reg3x3_64: return "reg3x3_64";
+    case ConvFamily::Wsf: snprintf(b, sizeof b, "wsf.s%d.bn%d.mt%d", c.stages, c.bn, c.mt); break;
+    case ConvFamily::Wsq: snprintf(b, sizeof b, "wsq.%dx%d", WSQ_TILES[c.wsq][0], WSQ_TILES[c.wsq][1]); break;
+    case ConvFamily::Wsx: snprintf(b, sizeof b, "wsx.s%d.bn%d", c.stages, c.bn); break;
+  }
+  return b;
+}
+static ConvChoiceReport conv_report(const ConvChoice& c) {
+  ConvChoiceReport r{};
+  snprintf(r.key, sizeof r.key, "%s", choice_key(c).c_str());
+  r.family = (int)c.family; r.stages = c.stages; r.bn = c.bn; r.mt = c.mt; r.bm = c.bm; r.smallc = c.smallc; r.wsq = c.wsq; r.sx = c.sx;
+  r.cog = c.cog; r.S = c.S; r.grid = (int)c.grid; r.ntn = c.ntn;
+  return r;
+}
+// every key launch_choice() / launch_conv_pool() can name, from the tables and ranges their with_int<> calls instantiate
+std::vector<std::string> conv_instantiation_keys() {
+  std::vector<std::string> keys;
+  ConvChoice c;
+  for (int dt : {BF16, F32}) {
+    c = ConvChoice(); c.dt = dt;
+    c.family = ConvFamily::Tile;
+    for (const auto& t : TILE_BMN)
+      for (int sc = 0; sc < 2; ++sc) { c.bm = t[0]; c.bn = t[1]; c.smallc = sc != 0; keys.push_back(choice_key(c)); }
+    c.family = ConvFamily::Ws;   // launch_plain(): <T, 4, 64>, <T, 4>, <T, 2>
+    for (const auto& sb : {std::pair<int, int>{4, 64}, {4, 128}, {2, 128}}) { c.stages = sb.first; c.bn = sb.second; keys.push_back(choice_key(c)); }
+  }
+  c = ConvChoice(); c.dt = F16X2;
+  c.family = ConvFamily::Sx;
+  for (int i = 0; i < 16; ++i) { c.sx = i; keys.push_back(choice_key(c)); }
+  c.family = ConvFamily::Reg3x3;
+  for (int cog = 1; cog <= 2; ++cog) { c.cog = cog; keys.push_back(choice_key(c)); }
+  c.pool = true; keys.push_back(choice_key(c)); c.pool = false;
+  c.family = ConvFamily::Reg3x3_64; keys.push_back(choice_key(c));
+  c.family = ConvFamily::Wsf;
+  for (const auto& sb : {std::pair<int, int>{2, 128}, {3, 64}, {3, 128}})
+    for (int mt = 4; mt <= wsf_max_mt(sb.first, sb.second); ++mt) { c.stages = sb.first; c.bn = sb.second; c.mt = mt; keys.push_back(choice_key(c)); }
+  c.family = ConvFamily::Wsq;
+  for (int i = 0; i < 7; ++i) { c.wsq = i; keys.push_back(choice_key(c)); }
+  c.family = ConvFamily::Wsx;
+  for (int st : {2, 4})
+    for (int bn : {64, 128}) { c.stages = st; c.bn = bn; keys.push_back(choice_key(c)); }
+  return keys;
+}
+// what this thread's last launch_conv() / launch_conv_pool() launched: one host-side struct store per launch (tests read it back)
+static thread_local ConvChoice t_last_choice;
+static thread_local bool t_have_last_choice = false;
+bool conv_last_choice(ConvChoiceReport* out) {
+  if (t_have_last_choice && out) *out = conv_report(t_last_choice);
+  return t_have_last_choice;
+}
+
 template <typename T>   // bf16 / fp32 operands: the register-staged kernel or the LDS-DMA tile
 static void launch_plain(const ConvChoice& c, const ConvK& k, const ConvArgs& a, hipStream_t s) {
   if (c.family == ConvFamily::Tile) {
@@ -2384,6 +2456,7 @@ static void launch_reg3x3(const ConvChoice& c, const ConvK& k, const ConvArgs& a
 
 // the chosen kernel and, behind a split-K first pass, the reduction that finishes the layer
 static void launch_choice(const ConvChoice& c, ConvK k, const ConvArgs& a, hipStream_t s) {
+  t_last_choice = c; t_have_last_choice = true;
   k.ntn = c.ntn;
   const ConvK whole = k;
   if (c.S > 1) k = splitk_partial(k, a.ws.slab);
@@ -2442,7 +2515,10 @@ size_t conv_split_slab_bytes(const ConvArgs& a) {
 }
 
 // ---- launchers ------------------------------------------------------------------------------------------------------------------------
-static void launch_conv_split(const ConvArgs& a, hipStream_t s) {
+// A launch's refusals and its choice, in one place: launch_conv() launches what this returns, conv_predict() (tests) reports it.
+// Host arithmetic on extents, types, alignment and the options only - no device call.
+struct CheckedConv { ConvGeom g; ConvChoice c; };
+static CheckedConv check_and_choose_split(const ConvArgs& a) {
   const ConvOpts& o = opts_of(a);
   const Tensor& x = a.x;
   const Tensor& y = a.y;
@@ -2460,50 +2536,12 @@ static void launch_conv_split(const ConvArgs& a, hipStream_t s) {
     RTD_CHECK(a.next_y.p == nullptr, 1, "conv (f16x3): a fused following conv exists in the streaming kernel only");
     RTD_CHECK(a.avg_y.p == nullptr, 1, "conv (f16x3): the fused vd-shortcut average exists in the streaming kernel only (the plan must fall back to the avg-pool launch)");
   }
-  if (c.S > 1) RTD_CHECK(a.ws.slab && (size_t)c.S * (size_t)g.M * (size_t)y.c * 4 <= a.ws.slab_bytes, 1,
-                         "conv (f16x3): the launch needs a split-K workspace of conv_split_slab_bytes() bytes (ConvArgs::ws)");
-  launch_choice(c, make_convk(a, g, o), a, s);
+  return {g, c};
 }
-
-// ---- stem.2 -> max-pool in one pass (conv3x3_reg_split_kernel<2, true> + k_pool_fixup) ----------------------------------------------
-// a = the 3x3 / stride 1 / pad 1 conv 32 -> 64 channels with ReLU whose output a.y would be pooled 3x3 / stride 2 / pad 1 into `pooled`;
-// a.y.p is not touched (the plan does not allocate it).  `side` = conv_pool_side_bytes(a) bytes of scratch.
-bool conv_pool_supported(const ConvArgs& a, const Tensor& pooled) {
+static CheckedConv check_and_choose(const ConvArgs& a) {
   const Tensor& x = a.x;
   const Tensor& y = a.y;
-  if (x.dt != F16X2 || y.dt != F16X2 || pooled.dt != F16X2) return false;
-  if (!(a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && !a.x2.p && !a.next_y.p && a.res_mode == RES_NONE && a.act == ACT_RELU)) return false;
-  if (x.c != 32 || y.c != 64 || pooled.c != 64 || x.ld % SPLIT_GROUP || pooled.ld % SPLIT_GROUP) return false;
-  if (y.h != x.h || y.w != x.w || (y.h & 1) || (y.w & 1) || pooled.h != y.h / 2 || pooled.w != y.w / 2 || pooled.n != x.n) return false;
-  if (((uintptr_t)x.p & 15) || ((uintptr_t)pooled.p & 15) || ((uintptr_t)a.w & 15)) return false;
-  const RegTiles t(x, 32);
-  return t.tx * t.ty >= 32 && opts_of(a).conv_reg != 0;
-}
-size_t conv_pool_side_bytes(const ConvArgs& a) { return (size_t)RegTiles(a.x, 32).n * (8192 + 1024) + 256; }
-void launch_conv_pool(const ConvArgs& a, const Tensor& pooled, void* side, hipStream_t s) {
-  RTD_CHECK(conv_pool_supported(a, pooled) && side, 1, "conv + max-pool: shape not supported");
-  ConvK k = make_convk(a, ConvGeom(a), opts_of(a));
-  k.y = nullptr; k.N = 64; k.pf = nullptr; k.pf_bytes = 0;       // the conv rows are never written; the launch carries no prefetch
-  const long long x_bytes = span_bytes(a.x, 4), p_bytes = span_bytes(pooled, 4);
-  const RegTiles t(a.x, 32);
-  const long long ntiles = t.n;   // over the batch
-  RTD_CHECK(x_bytes < (1ll << 31) && p_bytes < (1ll << 31) && ntiles * 8192 < (1ll << 31), 1, "conv + max-pool: operand larger than a buffer descriptor");
-  PoolOut po;
-  po.y = (sp16*)pooled.p; po.ldy = pooled.ld; po.bstride = pooled.bstride; po.OH = pooled.h; po.OW = pooled.w; po.y_bytes = (unsigned)p_bytes;
-  po.side_row = (sp16*)side; po.row_bytes = (unsigned)(ntiles * 8192);
-  po.side_col = (sp16*)((char*)side + ntiles * 8192); po.col_bytes = (unsigned)(ntiles * 1024);
-  const unsigned gx = (unsigned)std::min<long long>(ntiles, 256);
-  rtd_launch((conv3x3_reg_split_kernel<2, true>), dim3(gx), dim3(512), 0, s, k, (unsigned)x_bytes, 0u, t.tx, t.ty, (int)ntiles, po);
-  HIP_CHECK(hipGetLastError());
-  const long long items = ntiles * 19 * (64 / 8);
-  rtd_launch(k_pool_fixup, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, po, t.tx, t.ty, (int)ntiles, 64);
-  HIP_CHECK(hipGetLastError());
-}
-
-void launch_conv(const ConvArgs& a, hipStream_t s) {
-  const Tensor& x = a.x;
-  const Tensor& y = a.y;
-  if (x.dt == F16X2) { launch_conv_split(a, s); return; }
+  if (x.dt == F16X2) return check_and_choose_split(a);
   const ConvOpts& o = opts_of(a);
   RTD_CHECK(x.dt == BF16 || x.dt == F32, 1, "conv: input dtype");
   RTD_CHECK(y.dt == BF16 || y.dt == F32 || (y.dt == F16X2 && x.dt == F32), 1, "conv: output dtype");
@@ -2528,7 +2566,65 @@ void launch_conv(const ConvArgs& a, hipStream_t s) {
   RTD_CHECK(!a.next_y.p, 1, "conv: a fused following conv exists on F16X2 operands only (see conv_next_supported)");
   const ConvChoice c = choose_plain(a, g, o, (long long)a.Npad * a.Kpad * (long long)dtype_size(x.dt));
   RTD_CHECK(c.family == ConvFamily::Ws || !g.dual, 1, "conv: no kernel took the dual-input launch");
-  launch_choice(c, make_convk(a, g, o), a, s);
+  return {g, c};
+}
+
+// ---- stem.2 -> max-pool in one pass (conv3x3_reg_split_kernel<2, true> + k_pool_fixup) ----------------------------------------------
+// a = the 3x3 / stride 1 / pad 1 conv 32 -> 64 channels with ReLU whose output a.y would be pooled 3x3 / stride 2 / pad 1 into `pooled`;
+// a.y.p is not touched (the plan does not allocate it).  `side` = conv_pool_side_bytes(a) bytes of scratch.
+bool conv_pool_supported(const ConvArgs& a, const Tensor& pooled) {
+  const Tensor& x = a.x;
+  const Tensor& y = a.y;
+  if (x.dt != F16X2 || y.dt != F16X2 || pooled.dt != F16X2) return false;
+  if (!(a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && !a.x2.p && !a.next_y.p && a.res_mode == RES_NONE && a.act == ACT_RELU)) return false;
+  if (x.c != 32 || y.c != 64 || pooled.c != 64 || x.ld % SPLIT_GROUP || pooled.ld % SPLIT_GROUP) return false;
+  if (y.h != x.h || y.w != x.w || (y.h & 1) || (y.w & 1) || pooled.h != y.h / 2 || pooled.w != y.w / 2 || pooled.n != x.n) return false;
+  if (((uintptr_t)x.p & 15) || ((uintptr_t)pooled.p & 15) || ((uintptr_t)a.w & 15)) return false;
+  const RegTiles t(x, 32);
+  return t.tx * t.ty >= 32 && opts_of(a).conv_reg != 0;
+}
+size_t conv_pool_side_bytes(const ConvArgs& a) { return (size_t)RegTiles(a.x, 32).n * (8192 + 1024) + 256; }
+// the refusals of launch_conv_pool() and what it launches (the grid: persistent, one block per CU)
+static ConvChoice check_and_choose_pool(const ConvArgs& a, const Tensor& pooled) {
+  RTD_CHECK(conv_pool_supported(a, pooled), 1, "conv + max-pool: shape not supported");
+  const long long x_bytes = span_bytes(a.x, 4), p_bytes = span_bytes(pooled, 4), ntiles = RegTiles(a.x, 32).n;
+  RTD_CHECK(x_bytes < (1ll << 31) && p_bytes < (1ll << 31) && ntiles * 8192 < (1ll << 31), 1, "conv + max-pool: operand larger than a buffer descriptor");
+  ConvChoice c;
+  c.dt = F16X2; c.family = ConvFamily::Reg3x3; c.cog = 2; c.pool = true;
+  c.grid = (unsigned)std::min<long long>(ntiles, 256);
+  return c;
+}
+void launch_conv_pool(const ConvArgs& a, const Tensor& pooled, void* side, hipStream_t s) {
+  const ConvChoice c = check_and_choose_pool(a, pooled);
+  RTD_CHECK(side, 1, "conv + max-pool: no side buffer");
+  t_last_choice = c; t_have_last_choice = true;
+  ConvK k = make_convk(a, ConvGeom(a), opts_of(a));
+  k.y = nullptr; k.N = 64; k.pf = nullptr; k.pf_bytes = 0;       // the conv rows are never written; the launch carries no prefetch
+  const long long x_bytes = span_bytes(a.x, 4), p_bytes = span_bytes(pooled, 4);
+  const RegTiles t(a.x, 32);
+  const long long ntiles = t.n;   // over the batch
+  PoolOut po;
+  po.y = (sp16*)pooled.p; po.ldy = pooled.ld; po.bstride = pooled.bstride; po.OH = pooled.h; po.OW = pooled.w; po.y_bytes = (unsigned)p_bytes;
+  po.side_row = (sp16*)side; po.row_bytes = (unsigned)(ntiles * 8192);
+  po.side_col = (sp16*)((char*)side + ntiles * 8192); po.col_bytes = (unsigned)(ntiles * 1024);
+  rtd_launch((conv3x3_reg_split_kernel<2, true>), dim3(c.grid), dim3(512), 0, s, k, (unsigned)x_bytes, 0u, t.tx, t.ty, (int)ntiles, po);
+  HIP_CHECK(hipGetLastError());
+  const long long items = ntiles * 19 * (64 / 8);
+  rtd_launch(k_pool_fixup, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, po, t.tx, t.ty, (int)ntiles, 64);
+  HIP_CHECK(hipGetLastError());
+}
+
+void launch_conv(const ConvArgs& a, hipStream_t s) {
+  const CheckedConv cc = check_and_choose(a);
+  if (cc.c.S > 1) RTD_CHECK(a.ws.slab && (size_t)cc.c.S * (size_t)cc.g.M * (size_t)a.y.c * 4 <= a.ws.slab_bytes, 1,
+                            "conv (f16x3): the launch needs a split-K workspace of conv_split_slab_bytes() bytes (ConvArgs::ws)");
+  launch_choice(cc.c, make_convk(a, cc.g, opts_of(a)), a, s);
+}
+
+// what launch_conv(a), or launch_conv_pool(a, *pooled), would launch: the same refusals (an rtd::Error), the same choice, nothing launched.
+// The workspace and side-buffer pointers are the launchers' own business and are not looked at.
+ConvChoiceReport conv_predict(const ConvArgs& a, const Tensor* pooled) {
+  return conv_report(pooled ? check_and_choose_pool(a, *pooled) : check_and_choose(a).c);
 }
 
 }  // namespace rtd

@@ -290,6 +290,102 @@ int rtd_op_conv_next(int dtype, const void* x, const void* x2, const void* w_f32
   return op_conv_impl(dtype, x, x2, x2 ? C2 : 0, w_f32, bias, res, y, B, H, W, Cin, Cout, 1, 1, 1, 0, act, res_mode, 0, 0, w1_f32, bias1, y1, Cnext, next_act);
 }
 
+// ... plus the fused 2 x 2 average of y (ConvArgs::avg_y) and, with y_dead, without the stores of y.  Cnext = 0: no follower.
+int rtd_op_conv_avg(const void* x, const void* w_f32, const float* bias, const void* res, void* y, const void* w1_f32, const float* bias1, void* y1,
+                    void* avg_y, int B, int H, int W, int Cin, int Cout, int Cnext, int act, int res_mode, int next_act, int y_dead) {
+  if (!x || !w_f32 || !bias || !y || !avg_y || (Cnext != 0 && (!w1_f32 || !bias1 || !y1))) return RTD_E_INVALID;
+  return op_guard([&] {
+    RTD_CHECK(B >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1 && Cnext >= 0, RTD_E_INVALID, "conv + average: extents");
+    OpScratch sc;
+    const ConvFilter f = dev_filter(sc, F16X2, w_f32, bias, Cout, Cin);
+    ConvArgs a = conv_args(mk(x, F16X2, B, H, W, Cin), mk(y, F16X2, B, H, W, Cout), f, 1, 1, 0, act);
+    a.res_mode = res ? res_mode : RES_NONE;
+    if (res) a.res = mk(res, F16X2, B, H, W, Cout);
+    if (Cnext) {
+      const ConvFilter f1 = dev_filter(sc, F16X2, w1_f32, bias1, Cnext, Cout);
+      a.next_w = f1.w; a.next_bias = f1.bias; a.next_y = mk(y1, F16X2, B, H, W, Cnext); a.next_kpad = f1.Kpad; a.next_act = next_act;
+    }
+    a.avg_y = mk(avg_y, F16X2, B, H / 2, W / 2, Cout);
+    a.y_dead = y_dead;
+    RTD_CHECK(conv_avg_supported(a) && conv_sx_batch_fits(a), RTD_E_INVALID, "conv + average: shape not taken by the streaming kernel");
+    give_slab(sc, a);
+    launch_conv(a, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+  });
+}
+
+// stem.2 (3x3, 32 -> 64 channels, ReLU) and the 3x3 / stride-2 max-pool in one pass: x [B, H, W, 32] -> pooled [B, H / 2, W / 2, 64], pairs
+int rtd_op_conv_pool(const void* x, const void* w_ohwi_f32, const float* bias, void* pooled, int B, int H, int W) {
+  if (!x || !w_ohwi_f32 || !bias || !pooled) return RTD_E_INVALID;
+  return op_guard([&] {
+    RTD_CHECK(B >= 1 && H >= 1 && W >= 1, RTD_E_INVALID, "conv + max-pool: extents");
+    OpScratch sc;
+    const ConvFilter f = dev_filter(sc, F16X2, w_ohwi_f32, bias, 64, 9 * 32);
+    const ConvArgs a = conv_args(mk(x, F16X2, B, H, W, 32), mk(nullptr, F16X2, B, H, W, 64), f, 3, 1, 1, ACT_RELU);   // y is never written
+    const Tensor p = mk(pooled, F16X2, B, H / 2, W / 2, 64);
+    RTD_CHECK(conv_pool_supported(a, p), RTD_E_INVALID, "conv + max-pool: shape not supported (even extents, >= 32 tiles of 8 x 32 per image, conv_reg)");
+    launch_conv_pool(a, p, sc.get<char>(conv_pool_side_bytes(a)), nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+  });
+}
+
+// ---- the conv choice, readable: host arithmetic only, no device call (they work on a machine without a GPU) ----
+static void report_out(const ConvChoiceReport& r, char* key, int key_capacity, int32_t* info) {
+  RTD_CHECK(key && info && key_capacity > (int)strlen(r.key), RTD_E_INVALID, "conv choice: key buffer too small");
+  strcpy(key, r.key);
+  const int v[12] = {r.family, r.stages, r.bn, r.mt, r.bm, r.smallc, r.wsq, r.sx, r.cog, r.S, r.grid, r.ntn};
+  for (int i = 0; i < 12; ++i) info[i] = v[i];
+}
+int rtd_debug_conv_choice(int dtype, int B, int H, int W, int Cin, int C2, int Cout, int KH, int stride, int pad, int res_mode, int out_f32,
+                          int x_up2, int Cnext, int avg, int pool, char* key, int key_capacity, int32_t* info) {
+  return backend::caught(create_error(), [&] {
+    RTD_CHECK(dtype == BF16 || dtype == F32 || dtype == F16X2, RTD_E_INVALID, "conv choice: dtype");
+    RTD_CHECK(B >= 1 && H >= 1 && W >= 1 && Cin >= 1 && C2 >= 0 && Cout >= 1 && KH >= 1 && stride >= 1 && pad >= 0 && Cnext >= 0, RTD_E_INVALID, "conv choice: extents");
+    RTD_CHECK(!x_up2 || !((H | W) & 1), RTD_E_INVALID, "conv choice: x_up2 needs even output extents");
+    // the launch as op_conv_impl / rtd_op_conv_avg / rtd_op_conv_pool describe it: dense tensors behind a dummy 16-byte aligned address
+    const void* const P = (const void*)(uintptr_t)4096;
+    const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KH) / stride + 1;
+    ConvFilter f = conv_filter_extents(dtype, Cout, KH * KH * Cin + C2);
+    f.w = (void*)P; f.bias = (float*)P;
+    ConvArgs a = conv_args(x_up2 ? mk(P, dtype, B, H / 2, W / 2, Cin) : mk(P, dtype, B, H, W, Cin), mk(P, out_f32 ? F32 : dtype, B, OH, OW, Cout), f, KH, stride, pad,
+                           ACT_RELU);
+    a.x_up2 = x_up2;
+    a.res_mode = res_mode;
+    if (res_mode != RES_NONE) a.res = mk(P, dtype, B, OH, OW, Cout);
+    if (C2) a.x2 = mk(P, dtype, B, OH, OW, C2);
+    if (Cnext) {
+      a.next_w = P; a.next_bias = (const float*)P; a.next_y = mk(P, dtype, B, OH, OW, Cnext);
+      a.next_kpad = conv_filter_extents(dtype, Cnext, Cout).Kpad; a.next_act = ACT_RELU;
+    }
+    if (avg) a.avg_y = mk(P, dtype, B, OH / 2, OW / 2, Cout);
+    ConvChoiceReport r;
+    if (pool) {
+      const Tensor p = mk(P, dtype, B, OH / 2, OW / 2, Cout);
+      r = conv_predict(a, &p);
+    } else {
+      r = conv_predict(a, nullptr);
+    }
+    report_out(r, key, key_capacity, info);
+  });
+}
+int rtd_debug_last_conv(char* key, int key_capacity, int32_t* info) {
+  return backend::caught(create_error(), [&] {
+    ConvChoiceReport r;
+    RTD_CHECK(conv_last_choice(&r), RTD_E_STATE, "no conv launch on this thread yet");
+    report_out(r, key, key_capacity, info);
+  });
+}
+int rtd_debug_conv_instantiations(char* out, int64_t capacity, int64_t* needed) {
+  return backend::caught(create_error(), [&] {
+    std::string all;
+    for (const std::string& k : conv_instantiation_keys()) all += k + "\n";
+    if (needed) *needed = (int64_t)all.size() + 1;
+    if (!out) return;
+    RTD_CHECK(capacity > (int64_t)all.size(), RTD_E_INVALID, "conv instantiations: buffer too small");
+    memcpy(out, all.c_str(), all.size() + 1);
+  });
+}
+
 // operands of one benchmarked conv in the call's scratch: zero-filled input, filter, bias and residual, the output, the split-K workspace
 struct BenchConv {
   ConvArgs a;

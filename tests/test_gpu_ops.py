@@ -279,16 +279,16 @@ SPLIT_CONV_CASES = [
     (4, 60, 264, 32, 32, 3, 1, 1, "relu", 0, 0),        # stem.1: the direct (filter-in-registers) split kernel, ragged tiles both ways
     (4, 68, 232, 32, 64, 3, 1, 1, "silu", 0, 0),        # stem.2: two channel groups per block
     (2, 40, 40, 32, 32, 3, 1, 1, "relu", 0, 0),         # small map: stays on the tiled kernel (half-empty 64-channel tile)
-    (4, 80, 80, 128, 128, 3, 1, 1, "silu", 1, 0),       # 2-stage kernel (>= 257 blocks)
+    (4, 80, 80, 128, 128, 3, 1, 1, "silu", 1, 0),       # 200 tiles of 128 px: flexible height (wsf<3, 128, 7>, 229 blocks); 2-stage fixed tile in the "tiled 1" pass
     (4, 100, 97, 128, 192, 3, 1, 1, "silu", 2, 0),      # ragged M, partial last N tile, post residual
     (2, 160, 160, 64, 256, 1, 1, 0, "relu", 1, 0),      # stage-0 c3
     (1, 8400, 1, 256, 1536, 1, 1, 0, "none", 0, 1),     # value projection: fp32 output
-    (1, 400, 1, 2048, 256, 1, 1, 0, "none", 0, 1),      # enc.proj.2: long K, fp32 output, 4-stage kernel
+    (1, 400, 1, 2048, 256, 1, 1, 0, "none", 0, 1),      # enc.proj.2: long K, fp32 output (auto: wsf<3, 64, 4>; the 4-stage fixed tile in the "tiled 1 << 30" pass)
     (2, 20, 20, 512, 512, 3, 1, 1, "relu", 0, 0),       # stage-3 c2: K = 4608 real channels x taps (two-pass split-K, 2 slices, F16X2 out)
     (1, 70, 50, 256, 64, 1, 1, 0, "gelu", 0, 0),
     (2, 40, 41, 256, 1024, 1, 1, 0, "relu", 1, 1),      # fp32 output with a F16X2 residual
     (8, 40, 40, 256, 256, 3, 1, 1, "silu", 2, 0),       # 40^2 x 8 maps: flexible tile height (112 px -> 230 blocks), post residual
-    (8, 80, 80, 64, 256, 3, 1, 1, "relu", 0, 0),        # 80^2 x 8 maps: 208-pixel tiles, 3 stages, one block per CU
+    (8, 80, 80, 64, 256, 3, 1, 1, "relu", 0, 0),        # 80^2 x 8 maps, 18 K-steps: auto = the 2-stage fixed tile (800 blocks; below split_wsq_min_nk); quad tiles in the "quad" pass
     (8, 20, 20, 256, 512, 3, 1, 1, "relu", 1, 0),       # 20^2 x 8 maps: 64-pixel tiles
     (3, 37, 29, 512, 192, 1, 1, 0, "none", 0, 1),       # ragged M and N, fp32 output, K = 512 (16 K-steps: flexible tiles)
     (1, 81, 80, 64, 256, 1, 1, 0, "silu", 2, 0),        # streaming split kernel (>= 6400 pixels per image): ragged last 32-pixel tile, post residual
