@@ -381,6 +381,46 @@ int64_t rtd_esrgan_arena_bytes(rtd_esrgan_handle e);
 const char* rtd_esrgan_last_error(rtd_esrgan_handle e);                    /* e may be NULL: last error of a failed create / layout */
 void rtd_esrgan_destroy(rtd_esrgan_handle e);
 
+/* ---- Frame ingest: 4:2:0 camera frames (NV12, NV21, I420) -> the BGR device frames every other entry point takes (in place of the
+ * swscale conversion behind the reference's cv2.VideoCapture and behind `-pix_fmt bgr24` in src/stream_capture_gpu_ffmpeg.py) ----------
+ * All frames of a call in one launch (csrc/ingest.hip).  The arithmetic is OpenCV's COLOR_YUV2BGR_NV12 / _NV21 / _I420 fixed-point
+ * path, integers only (restated in tests/yuv_ref.py and matched bit for bit): the chroma plane has ceil(H/2) rows of ceil(W/2) samples,
+ * pixel (y, x) takes sample (y >> 1, x >> 1) without interpolation, and with u = U - 128, v = V - 128, y' = max(Y - 16, 0) (limited
+ * range) or Y (full range), in int32:
+ *   B = clip8((y' CY + 2^19 + CUB u) >> 20),  G = clip8((y' CY + 2^19 + CVG v + CUG u) >> 20),  R = clip8((y' CY + 2^19 + CVR v) >> 20)
+ * with the five constants floor(c 2^20 + 0.5) of the matrix's decimal coefficients (BT.601 limited: OpenCV's own 1220542, 1673527,
+ * -852492, -409993, 2116026).  Odd widths and heights are accepted by the rule above (OpenCV refuses them; ffmpeg writes them so).
+ * A plane is a pointer and a pitch in bytes, so a padded decoder surface is read where it lies; tightly packed rawvideo is
+ * y_pitch = width, c_pitch = 2 ceil(W/2) (NV12 / NV21) or ceil(W/2) (I420), the planes back to back.  Frames of one call may differ in
+ * size, layout, matrix and range.  Own handle with a non-blocking stream and a pinned staging buffer with its device twin, grown on
+ * demand: no device or pinned allocation on the steady path.  Calls on one handle are serialised by the handle.
+ * Limits: 1..RTD_INGEST_MAX_FRAMES frames per call, 1..65535 pixels per side, pitches of at least the row's bytes, known layout / matrix /
+ * range values, no null plane or output.  Beyond a limit: RTD_E_INVALID with the frame's index in the message, and nothing is copied or
+ * launched. */
+enum { RTD_YUV_NV12 = 0, RTD_YUV_NV21 = 1, RTD_YUV_I420 = 2 };
+enum { RTD_YUV_BT601 = 0, RTD_YUV_BT709 = 1 };
+enum { RTD_INGEST_MAX_FRAMES = 64 };
+typedef struct rtd_yuv_frame { /* 56 bytes */
+  const uint8_t* y; /* luma: height rows of width bytes, y_pitch apart */
+  const uint8_t* u; /* NV12: the interleaved U V plane; NV21: the interleaved V U plane; I420: the U plane.  ceil(H/2) rows, c_pitch apart */
+  const uint8_t* v; /* I420: the V plane (c_pitch apart as well); unused for NV12 / NV21 */
+  int32_t width, height;
+  int32_t y_pitch, c_pitch;
+  int32_t layout;     /* RTD_YUV_NV12 | _NV21 | _I420 */
+  int32_t matrix;     /* RTD_YUV_BT601 | _BT709 */
+  int32_t full_range; /* 0: limited (16..235 luma), 1: full */
+  int32_t reserved0;
+} rtd_yuv_frame;
+typedef struct rtd_ingest* rtd_ingest_handle;
+int rtd_ingest_create(int32_t device, rtd_ingest_handle* out);
+/* n frames whose planes are all host memory (frames_on_device = 0: packed into the staging buffer and uploaded in ONE copy) or all
+ * device memory; out_dev[i] is device memory of the caller with room for height x width x 3 bytes and receives the frame as tight HWC
+ * BGR.  Two frames of a call must not share out_dev memory.  Synchronous: returns when every out_dev[i] is complete. */
+int rtd_ingest_convert(rtd_ingest_handle g, int32_t n, const rtd_yuv_frame* frames, int32_t frames_on_device, uint8_t* const* out_dev /* [n] */);
+int rtd_ingest_wait_stream(rtd_ingest_handle g, void* producer_stream);   /* as rtd_wait_stream */
+const char* rtd_ingest_last_error(rtd_ingest_handle g);                  /* g may be NULL: last error of a failed rtd_ingest_create */
+void rtd_ingest_destroy(rtd_ingest_handle g);
+
 #ifdef __cplusplus
 }
 #endif

@@ -207,6 +207,13 @@ int rtd_debug_enhance_stage(rtd_enhance_handle e, int32_t crop, int32_t stage, u
  * be alive).  out may be NULL to ask for the shape.  csrc/esrgan.hip. */
 int rtd_debug_esrgan_tensor(rtd_esrgan_handle e, const char* name, float* out, int64_t capacity, int64_t shape[4]);
 
+/* what the ingest kernel works with, pure host arithmetic (no GPU, no handle): the five constants CY, CVR, CVG, CUG, CUB of a matrix and
+ * range as the one host function computes them, the tile of one workgroup (pixels), and the number of tiles a call on the n frames
+ * would launch (the planes are not looked at).  Any pointer may be NULL (frames: n is then ignored).  RTD_E_INVALID for an unknown
+ * matrix or range, or a frame rtd_ingest_convert would refuse for its size.  csrc/ingest.hip. */
+int rtd_debug_ingest_info(int32_t matrix, int32_t full_range, int32_t coeffs[5], int32_t* tile_h, int32_t* tile_w, int32_t n,
+                          const rtd_yuv_frame* frames, int64_t* tiles);
+
 #ifdef __cplusplus
 }
 #endif

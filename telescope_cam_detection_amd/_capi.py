@@ -107,6 +107,12 @@ class RtdEsrganConfig(C.Structure):
                 ("num_grow_ch", C.c_int32), ("num_block", C.c_int32), ("tile", C.c_int32), ("tile_pad", C.c_int32)]
 
 
+class RtdYuvFrame(C.Structure):
+    _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
+                ("y_pitch", C.c_int32), ("c_pitch", C.c_int32), ("layout", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
 DET_DTYPE = np.dtype([("class_id", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 
 _lib: Optional[C.CDLL] = None
@@ -122,6 +128,7 @@ EXPORTS = [
     "rtd_overlay_create", "rtd_overlay_draw", "rtd_overlay_wait_stream", "rtd_overlay_last_error", "rtd_overlay_destroy",
     "rtd_enhance_create", "rtd_enhance_layout", "rtd_enhance_crops", "rtd_enhance_last_error", "rtd_enhance_destroy",
     "rtd_esrgan_create", "rtd_esrgan_layout", "rtd_esrgan_upscale", "rtd_esrgan_arena_bytes", "rtd_esrgan_last_error", "rtd_esrgan_destroy",
+    "rtd_ingest_create", "rtd_ingest_convert", "rtd_ingest_wait_stream", "rtd_ingest_last_error", "rtd_ingest_destroy",
 ]
 # every symbol include/rtdetr_mi355_test.h declares: kernel-level test / bench / debug entry points (csrc/testapi.hip)
 TEST_EXPORTS = [
@@ -133,6 +140,7 @@ TEST_EXPORTS = [
     "rtd_op_msdeform_view", "rtd_op_select_score", "rtd_op_gather_ln", "rtd_op_split_convert", "rtd_op_set_rows", "rtd_op_rowmax",
     "rtd_op_gather_rows", "rtd_op_boxes", "rtd_op_add", "rtd_op_postprocess", "rtd_op_msdeform_discrete_view",
     "rtd_op_conv_avg", "rtd_op_conv_pool", "rtd_debug_conv_choice", "rtd_debug_last_conv", "rtd_debug_conv_instantiations",
+    "rtd_debug_ingest_info",
 ]
 CONV_INFO_FIELDS = ("family", "stages", "bn", "mt", "bm", "smallc", "wsq", "sx", "cog", "S", "grid", "ntn")   # info[12] of the conv-choice calls
 
@@ -288,6 +296,15 @@ def lib() -> C.CDLL:
         L.rtd_debug_conv_choice.argtypes = [i32] * 16 + [C.c_char_p, i32, C.POINTER(i32)]
         L.rtd_debug_last_conv.argtypes = [C.c_char_p, i32, C.POINTER(i32)]
         L.rtd_debug_conv_instantiations.argtypes = [C.c_char_p, i64, C.POINTER(i64)]
+    if hasattr(L, "rtd_ingest_create"):        # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_ingest_create.argtypes = [i32, C.POINTER(vp)]
+        L.rtd_ingest_convert.argtypes = [vp, i32, C.POINTER(RtdYuvFrame), i32, C.POINTER(vp)]
+        L.rtd_ingest_wait_stream.argtypes = [vp, vp]
+        L.rtd_ingest_last_error.argtypes = [vp]
+        L.rtd_ingest_last_error.restype = C.c_char_p
+        L.rtd_ingest_destroy.argtypes = [vp]
+        L.rtd_ingest_destroy.restype = None
+        L.rtd_debug_ingest_info.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(RtdYuvFrame), C.POINTER(i64)]
     _lib = L
     return L
 
@@ -357,7 +374,7 @@ def _raise(code: int, handle=None) -> None:
     _raise_msg(code, Engine._what, lib().rtd_last_error(None))
 
 
-# ---- the seven handles (the engine; motion, mog2, jpeg, overlay, enhance, esrgan) ------------------------------------------------------
+# ---- the eight handles (the engine; motion, mog2, jpeg, overlay, enhance, esrgan, ingest) ------------------------------------------------------
 def device_index(device) -> int:
     """an int, None (torch's current device), a torch.device or a string like 'cuda:1' -> the device's index"""
     if isinstance(device, int):
