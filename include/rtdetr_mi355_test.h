@@ -93,6 +93,12 @@ int rtd_op_conv_avg(const void* x, const void* w_f32, const float* bias, const v
  * pad 1 max -> pooled [B, H/2, W/2, 64] F16X2; the conv rows are never written.  RTD_E_INVALID before any launch for what
  * conv_pool_supported() refuses (odd extents, fewer than 32 tiles of 8 x 32 pixels per image, conv_reg 0). */
 int rtd_op_conv_pool(const void* x, const void* w_ohwi_f32, const float* bias, void* pooled, int B, int H, int W);
+/* backbone.stem.0 of the f16x3 engine straight from uint8 frames (stem0_u8_kernel: 3x3 / stride 2 / pad 1, BGR byte cb -> model channel
+ * 2 - cb, pixel = (float)v / 255.0f as a hi / lo pair).  frames_dev: a HOST array of n device pointers, each an [H][W][3] BGR frame at ANY
+ * byte address; w_ohwi_f32 [32][3][3][8] (device; channels = RGB + 5 pad the kernel never reads) and bias [32] (device) are staged as the
+ * engine stages backbone.stem.0; y = F16X2 [n][OH][OW][32] dense, OH = (H - 1) / 2 + 1.  act: 0 none, 1 ReLU, 2 SiLU.  RTD_E_INVALID before
+ * any launch, with nothing written, for n outside 1..64 (RTD_MAX_BATCH), a null pointer (a frame's included), extents < 1 or another act. */
+int rtd_op_stem0_u8(const uint8_t* const* frames_dev, int n, int H, int W, const void* w_ohwi_f32, const float* bias, void* y, int act);
 
 /* ---- which conv kernel: the choice behind launch_conv, readable.  Host arithmetic only: no device call, usable without a GPU.
  * A choice is a text key naming ONE instantiation plus info[12] = family, stages, bn, mt, bm, smallc, wsq, sx, cog, S, grid, ntn

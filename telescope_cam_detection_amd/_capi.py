@@ -140,7 +140,7 @@ TEST_EXPORTS = [
     "rtd_op_msdeform_view", "rtd_op_select_score", "rtd_op_gather_ln", "rtd_op_split_convert", "rtd_op_set_rows", "rtd_op_rowmax",
     "rtd_op_gather_rows", "rtd_op_boxes", "rtd_op_add", "rtd_op_postprocess", "rtd_op_msdeform_discrete_view",
     "rtd_op_conv_avg", "rtd_op_conv_pool", "rtd_debug_conv_choice", "rtd_debug_last_conv", "rtd_debug_conv_instantiations",
-    "rtd_debug_ingest_info",
+    "rtd_debug_ingest_info", "rtd_op_stem0_u8",
 ]
 CONV_INFO_FIELDS = ("family", "stages", "bn", "mt", "bm", "smallc", "wsq", "sx", "cog", "S", "grid", "ntn")   # info[12] of the conv-choice calls
 
@@ -305,6 +305,8 @@ def lib() -> C.CDLL:
         L.rtd_ingest_destroy.argtypes = [vp]
         L.rtd_ingest_destroy.restype = None
         L.rtd_debug_ingest_info.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(RtdYuvFrame), C.POINTER(i64)]
+    if hasattr(L, "rtd_op_stem0_u8"):          # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_op_stem0_u8.argtypes = [C.POINTER(vp), i32, i32, i32, vp, vp, vp, i32]
     _lib = L
     return L
 

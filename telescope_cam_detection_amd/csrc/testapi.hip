@@ -329,6 +329,22 @@ int rtd_op_conv_pool(const void* x, const void* w_ohwi_f32, const float* bias, v
   });
 }
 
+// backbone.stem.0 straight from the uint8 frames (launch_stem0_u8), the filter staged as the engine's get_weight({{"backbone.stem.0", 72}},
+// F16X2, 32) packs it; frames_dev: a HOST array of n device pointers ([H][W][3] BGR bytes at any address), y [n, OH, OW, 32] pairs, dense
+int rtd_op_stem0_u8(const uint8_t* const* frames_dev, int n, int H, int W, const void* w_ohwi_f32, const float* bias, void* y, int act) {
+  if (!frames_dev || !w_ohwi_f32 || !bias || !y || n < 1 || n > RTD_MAX_BATCH || H < 1 || W < 1) return RTD_E_INVALID;
+  if (act != ACT_NONE && act != ACT_RELU && act != ACT_SILU) return RTD_E_INVALID;      // (what the launcher refuses, before any device work)
+  for (int i = 0; i < n; ++i)
+    if (!frames_dev[i]) return RTD_E_INVALID;
+  return op_guard([&] {
+    OpScratch sc;
+    const ConvFilter f = dev_filter(sc, F16X2, w_ohwi_f32, bias, 32, 9 * 8);
+    const uint8_t* const* table = sc.upload(frames_dev, (size_t)n);
+    launch_stem0_u8(table, n, H, W, f.w, f.Kpad, f.bias, mk(y, F16X2, n, (H - 1) / 2 + 1, (W - 1) / 2 + 1, 32), act, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+  });
+}
+
 // ---- the conv choice, readable: host arithmetic only, no device call (they work on a machine without a GPU) ----
 static void report_out(const ConvChoiceReport& r, char* key, int key_capacity, int32_t* info) {
   RTD_CHECK(key && info && key_capacity > (int)strlen(r.key), RTD_E_INVALID, "conv choice: key buffer too small");

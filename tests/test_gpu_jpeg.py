@@ -1,5 +1,5 @@
 """The JPEG encoder on the MI355X (csrc/jpeg.hip): files byte-identical to Pillow's (tests/golden/jpeg_small.npz, jpeg_large.json) for host
-and device frames, alone and batched; the bench layout of 8 x 1080p; capacity and argument handling of rtd_jpeg_encode; stream ordering
+and device frames, alone and batched, device frames also as views at odd byte offsets of a shared buffer; the bench layout of 8 x 1080p; capacity and argument handling of rtd_jpeg_encode; stream ordering
 of device frames; the installed snapshot-saver path.  On a mismatch the first differing coefficient block is reported
 (rtd_debug_jpeg_coefficients against tests/jpeg_ref.py)."""
 import hashlib
@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from tests import jpeg_ref as ref
+from tests.frontend_ref import Placed
 from tests.test_jpeg_host import QUALITIES, large_entries, reference_bookkeeping, small_cases, stand_in_module
 from telescope_cam_detection_amd import _capi, jpeg
 from telescope_cam_detection_amd.synth import make_frame, scene_frame
@@ -61,6 +62,27 @@ def test_every_small_fixture_is_byte_identical_in_one_batch_per_quality(be):
         want = [z[f"jpg_{n}_q{q}"].tobytes() for n in names]
         for dev in (False, True):
             check(be, frames, q, want, dev)
+
+
+def test_device_frames_at_any_byte_address_are_byte_identical(be):
+    """transform_kernel stages a tile's rows as aligned dwords and puts a dword that leaves the frame together from bytes: every small
+    fixture at every quality from device frames that are views 1, 2, 3 and 0 bytes past a 16-byte boundary of one 0xFF-filled buffer
+    (>= 4 KiB of filler around each: a stray read neither faults nor goes unseen), alone and then all in one batch at mixed offsets."""
+    z, names = small_cases()
+    frames = [z["in_" + n] for n in names]
+    same = [Placed(frames, [off] * len(frames), 0xFF) for off in (1, 2, 3, 0)]
+    mixed = Placed(frames, [(1, 2, 3, 0)[i % 4] for i in range(len(frames))], 0xFF)
+    assert {p % 16 for p in mixed.ptrs} == {0, 1, 2, 3}
+    for q in QUALITIES:
+        want = [z[f"jpg_{n}_q{q}"].tobytes() for n in names]
+        for placed in same:
+            for i, f in enumerate(frames):
+                got = be.encode([placed.views[i]], True, q)
+                assert got == [want[i]], (names[i], q, placed.ptrs[i] % 16, len(got[0]), len(want[i]), explain(be, [f], q))
+        got = be.encode(mixed.views, True, q)
+        for i, (g, w) in enumerate(zip(got, want)):
+            assert g == w, (names[i], q, mixed.ptrs[i] % 16, len(g), len(w), explain(be, frames, q))
+        assert len(got) == len(want)
 
 
 def test_large_fixtures_match_length_and_sha256(be):

@@ -835,6 +835,13 @@ def test_resize_matches_pil_bit_exactly(L, size):
     got = out.cpu().numpy()
     assert (got[:, :, 3:] == 0).all()
     np.testing.assert_array_equal(got[:, :, :3], want.astype(np.float32) / np.float32(255.0))
+    # dtype 0: the bf16 NHWC-8 rows every bf16 engine reads for a frame of another size - the same quotient rounded once to bf16
+    out16 = torch.full((dh, dw, 8), float("nan"), dtype=torch.bfloat16, device="cuda")
+    ck(L, L.rtd_op_resize(sd.data_ptr(), sh, sw, out16.data_ptr(), dh, dw, 0))
+    got16 = out16.cpu().view(torch.int16).numpy()
+    want16 = torch.from_numpy(want.astype(np.float32) / np.float32(255.0)).to(torch.bfloat16).view(torch.int16).numpy()
+    assert (got16[:, :, 3:] == 0).all()
+    np.testing.assert_array_equal(got16[:, :, :3], want16)
 
 
 POOL_KIND = {"max": 0, "avg": 1, "up": 2}
