@@ -421,6 +421,48 @@ int rtd_ingest_wait_stream(rtd_ingest_handle g, void* producer_stream);   /* as 
 const char* rtd_ingest_last_error(rtd_ingest_handle g);                  /* g may be NULL: last error of a failed rtd_ingest_create */
 void rtd_ingest_destroy(rtd_ingest_handle g);
 
+/* ---- Privacy face masks on device-resident frames (the reference's FaceMasker.apply_mask in src/face_masker.py: cv2.GaussianBlur,
+ * cv2.resize and cv2.rectangle on the padded face rectangle) ---------------------------------------------------------------------------
+ * Faces are masked where the frame lies (csrc/facemask.hip), all in integers, byte for byte what the reference does to the numpy frame
+ * (restated in tests/face_ref.py).  With p = int(w * 0.2) the padded rectangle of a face (x, y, w, h) on an H x W frame is
+ * x1 = max(0, x - p), y1 = max(0, y - p), x2 = min(W, x + w + p), y2 = min(H, y + h + p), and the region is frame[y1:y2, x1:x2]:
+ *   BLUR       GaussianBlur(region, (k, k), 0) on OpenCV's fixed-point path: taps in 1/256 (getGaussianKernelBitExact), a row pass to
+ *              16-bit sums, a column pass (sum + 32768) >> 16, BORDER_REFLECT_101 at the REGION's edges, each channel on its own.  The
+ *              reference's adaptive_blur is BLUR with the k its caller works out per face.
+ *   PIXELATE   small = resize(region, (max(1, rw / blocks), max(1, rh / blocks)), INTER_LINEAR), then resize(small, (rw, rh),
+ *              INTER_NEAREST): OpenCV's portable 8-bit code, the index and weight tables made on the host.
+ *   BLACK_BOX  zero over x1..min(x2, W - 1), y1..min(y2, H - 1) INCLUSIVE (cv2.rectangle fills both corners).
+ * Faces apply in list order: where the rectangles of two faces of a frame overlap, the later one works on the earlier one's output.
+ * The host sorts the faces of a call into layers (a face goes after every earlier face of its frame that it meets); a layer is one
+ * launch pair per style present, over all its faces.  A face whose padded rectangle is empty is skipped (cv2 would raise).
+ * Own handle with a non-blocking stream, a pinned staging buffer with its device twin and a scratch plane, all grown on demand: no
+ * device or pinned allocation on the steady path.  Calls on one handle are serialised by the handle.
+ * Limits: 1..RTD_FACEMASK_MAX_FRAMES frames per call, 1..65535 pixels per side and less than 2 GiB, at most RTD_FACEMASK_MAX_FACES faces, a frame index
+ * inside the call, a known style, k odd in 1..99, blocks >= 1, no null pointer.  Beyond a limit: RTD_E_INVALID with the face's (or
+ * frame's) index in the message, and nothing is copied or launched. */
+enum { RTD_FACE_BLUR = 0, RTD_FACE_PIXELATE = 1, RTD_FACE_BLACK_BOX = 2 };
+enum { RTD_FACEMASK_MAX_FRAMES = 64, RTD_FACEMASK_MAX_FACES = 1024, RTD_FACEMASK_MAX_K = 99 };
+typedef struct rtd_face_rect { /* 32 bytes */
+  int32_t frame;       /* which frame of the call */
+  int32_t x, y, w, h;  /* the detector's box; may leave the frame */
+  int32_t style;       /* RTD_FACE_* */
+  int32_t k_or_blocks; /* BLUR: the kernel size k; PIXELATE: blocks; BLACK_BOX: ignored */
+  int32_t reserved0;
+} rtd_face_rect;
+typedef struct rtd_facemask* rtd_facemask_handle;
+int rtd_facemask_create(int32_t device, rtd_facemask_handle* out);
+/* n frames (HWC uint8 BGR, tightly packed, hw = [n][2] rows, cols), all device memory (masked in place) or all host memory
+ * (frames_on_device = 0: the frames that have a face are uploaded, masked and written back over the host frame).  Synchronous: returns
+ * when every frame holds its masked pixels.  Bytes outside the padded rectangles are never written. */
+int rtd_facemask_apply(rtd_facemask_handle m, int32_t n, uint8_t* const* frames, const int32_t* hw /* [n][2] */, int32_t frames_on_device,
+                       int32_t n_faces, const rtd_face_rect* faces);
+/* the gray plane a face detector takes, (1868 B + 9617 G + 4899 R + 8192) >> 14 (cv2.cvtColor BGR2GRAY) of one DEVICE frame, written by
+ * the kernel into pinned host memory and copied to gray_out (HOST, rows x cols bytes): a third of the frame's bytes cross.  Synchronous. */
+int rtd_facemask_gray(rtd_facemask_handle m, const uint8_t* frame_dev, int32_t rows, int32_t cols, uint8_t* gray_out);
+int rtd_facemask_wait_stream(rtd_facemask_handle m, void* producer_stream);   /* as rtd_wait_stream */
+const char* rtd_facemask_last_error(rtd_facemask_handle m);                  /* m may be NULL: last error of a failed rtd_facemask_create */
+void rtd_facemask_destroy(rtd_facemask_handle m);
+
 #ifdef __cplusplus
 }
 #endif

@@ -220,6 +220,15 @@ int rtd_debug_esrgan_tensor(rtd_esrgan_handle e, const char* name, float* out, i
 int rtd_debug_ingest_info(int32_t matrix, int32_t full_range, int32_t coeffs[5], int32_t* tile_h, int32_t* tile_w, int32_t n,
                           const rtd_yuv_frame* frames, int64_t* tiles);
 
+/* what rtd_facemask_apply would do with a call, pure host arithmetic (no GPU, no handle; the frames themselves are not looked at): the
+ * number of layers, per face its layer (-1: skipped, its padded rectangle is empty) and its padded rectangle x1, y1, x2, y2 (the blur /
+ * pixelate region, exclusive ends), the tile of one workgroup (pixels) and per launch kind the tiles of the whole call (tiles[5]: blur
+ * rows, blur columns, pixelate small, pixelate nearest, black box).  With taps_k >= 1 the taps of a k-tap blur go to taps[taps_k]
+ * (the shared rule of csrc/gauss_taps.h).  Any output pointer may be NULL.  RTD_E_INVALID for what rtd_facemask_apply would refuse
+ * (the message: rtd_facemask_last_error(NULL)).  csrc/facemask.hip. */
+int rtd_debug_facemask_plan(int32_t n, const int32_t* hw, int32_t n_faces, const rtd_face_rect* faces, int32_t* layers, int32_t* layer_of,
+                            int32_t* rects, int32_t* tile_h, int32_t* tile_w, int64_t* tiles, int32_t taps_k, uint16_t* taps);
+
 #ifdef __cplusplus
 }
 #endif

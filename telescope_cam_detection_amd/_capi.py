@@ -113,6 +113,11 @@ class RtdYuvFrame(C.Structure):
                 ("reserved0", C.c_int32)]
 
 
+class RtdFaceRect(C.Structure):
+    _fields_ = [("frame", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("style", C.c_int32),
+                ("k_or_blocks", C.c_int32), ("reserved0", C.c_int32)]
+
+
 DET_DTYPE = np.dtype([("class_id", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 
 _lib: Optional[C.CDLL] = None
@@ -129,6 +134,7 @@ EXPORTS = [
     "rtd_enhance_create", "rtd_enhance_layout", "rtd_enhance_crops", "rtd_enhance_last_error", "rtd_enhance_destroy",
     "rtd_esrgan_create", "rtd_esrgan_layout", "rtd_esrgan_upscale", "rtd_esrgan_arena_bytes", "rtd_esrgan_last_error", "rtd_esrgan_destroy",
     "rtd_ingest_create", "rtd_ingest_convert", "rtd_ingest_wait_stream", "rtd_ingest_last_error", "rtd_ingest_destroy",
+    "rtd_facemask_create", "rtd_facemask_apply", "rtd_facemask_gray", "rtd_facemask_wait_stream", "rtd_facemask_last_error", "rtd_facemask_destroy",
 ]
 # every symbol include/rtdetr_mi355_test.h declares: kernel-level test / bench / debug entry points (csrc/testapi.hip)
 TEST_EXPORTS = [
@@ -140,7 +146,7 @@ TEST_EXPORTS = [
     "rtd_op_msdeform_view", "rtd_op_select_score", "rtd_op_gather_ln", "rtd_op_split_convert", "rtd_op_set_rows", "rtd_op_rowmax",
     "rtd_op_gather_rows", "rtd_op_boxes", "rtd_op_add", "rtd_op_postprocess", "rtd_op_msdeform_discrete_view",
     "rtd_op_conv_avg", "rtd_op_conv_pool", "rtd_debug_conv_choice", "rtd_debug_last_conv", "rtd_debug_conv_instantiations",
-    "rtd_debug_ingest_info", "rtd_op_stem0_u8",
+    "rtd_debug_ingest_info", "rtd_op_stem0_u8", "rtd_debug_facemask_plan",
 ]
 CONV_INFO_FIELDS = ("family", "stages", "bn", "mt", "bm", "smallc", "wsq", "sx", "cog", "S", "grid", "ntn")   # info[12] of the conv-choice calls
 
@@ -307,6 +313,17 @@ def lib() -> C.CDLL:
         L.rtd_debug_ingest_info.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(RtdYuvFrame), C.POINTER(i64)]
     if hasattr(L, "rtd_op_stem0_u8"):          # (absent from older builds loaded through RTD_LIB_PATH)
         L.rtd_op_stem0_u8.argtypes = [C.POINTER(vp), i32, i32, i32, vp, vp, vp, i32]
+    if hasattr(L, "rtd_facemask_create"):      # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_facemask_create.argtypes = [i32, C.POINTER(vp)]
+        L.rtd_facemask_apply.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), i32, i32, C.POINTER(RtdFaceRect)]
+        L.rtd_facemask_gray.argtypes = [vp, vp, i32, i32, vp]
+        L.rtd_facemask_wait_stream.argtypes = [vp, vp]
+        L.rtd_facemask_last_error.argtypes = [vp]
+        L.rtd_facemask_last_error.restype = C.c_char_p
+        L.rtd_facemask_destroy.argtypes = [vp]
+        L.rtd_facemask_destroy.restype = None
+        L.rtd_debug_facemask_plan.argtypes = [i32, C.POINTER(i32), i32, C.POINTER(RtdFaceRect), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
+                                              C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), i32, C.POINTER(C.c_uint16)]
     _lib = L
     return L
 
@@ -376,7 +393,7 @@ def _raise(code: int, handle=None) -> None:
     _raise_msg(code, Engine._what, lib().rtd_last_error(None))
 
 
-# ---- the eight handles (the engine; motion, mog2, jpeg, overlay, enhance, esrgan, ingest) ------------------------------------------------------
+# ---- the nine handles (the engine; motion, mog2, jpeg, overlay, enhance, esrgan, ingest, facemask) ------------------------------------------------------
 def device_index(device) -> int:
     """an int, None (torch's current device), a torch.device or a string like 'cuda:1' -> the device's index"""
     if isinstance(device, int):

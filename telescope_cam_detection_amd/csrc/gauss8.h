@@ -11,6 +11,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "gauss_taps.h"
+
 namespace gauss8 {
 
 constexpr int MAX_R = 31;                  // k <= 63
@@ -20,32 +22,10 @@ struct Taps {
   uint16_t c[2 * MAX_R + 1];
 };
 
-// taps of GaussianBlur(k, sigma = 0) on 8-bit input (tests/motion_ref.py taps(): fixed tables up to k = 7, error-diffused rounding above)
+// taps of GaussianBlur(k, sigma = 0) on 8-bit input: the rule is gauss_taps.h's (tests/motion_ref.py taps())
 static inline void make_taps(int k, Taps& t) {
-  static const uint16_t fixed[4][7] = {{256}, {64, 128, 64}, {16, 64, 96, 64, 16}, {8, 28, 56, 72, 56, 28, 8}};
   t.radius = k / 2;
-  if (k <= 7) {
-    for (int i = 0; i < k; ++i) t.c[i] = fixed[k / 2][i];
-    return;
-  }
-  const double sigma = 0.15 * k + 0.35;
-  std::vector<double> g(k);
-  double sum = 0;
-  for (int i = 0; i < k; ++i) {
-    const double xx = i - (k - 1) / 2.0;
-    g[i] = std::exp(-(xx * xx) / (2.0 * sigma * sigma));
-    sum += g[i];
-  }
-  double e = 0;
-  int off = 0;
-  for (int i = 0; i < k / 2; ++i) {
-    const double adj = 256.0 * (g[i] / sum) + e;
-    const int v = (int)std::nearbyint(adj);         // round half to even (the default rounding mode), like cvRound
-    e = adj - v;
-    t.c[i] = t.c[k - 1 - i] = (uint16_t)v;
-    off += v;
-  }
-  t.c[k / 2] = (uint16_t)(256 - 2 * off);
+  tap_rule(k, t.c);
 }
 
 // borderInterpolate(p, n, BORDER_REFLECT_101), reflecting repeatedly (a frame shorter than the radius)
