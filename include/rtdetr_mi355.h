@@ -463,6 +463,50 @@ int rtd_facemask_wait_stream(rtd_facemask_handle m, void* producer_stream);   /*
 const char* rtd_facemask_last_error(rtd_facemask_handle m);                  /* m may be NULL: last error of a failed rtd_facemask_create */
 void rtd_facemask_destroy(rtd_facemask_handle m);
 
+/* ---- Stage-2 species classifier: timm's `Eva` vision transformer (the reference's config names
+ * timm/eva02_large_patch14_clip_336.merged2b_ft_inat21: ViT-L/14 at 336 px, 24 blocks, 1024 channels, 16 heads of 64, 577 tokens) ------
+ * Patch embed (patch x patch conv, stride patch, bias), cls token, learned pos_embed; per block
+ *   x += proj(attn_norm?(attention(rope(q), rope(k), v)));  x += fc2(mlp_norm?(silu(fc1_g y) * fc1_x y)), y = norm2(x)
+ * with interleaved RoPE on the patch tokens of q and k (never the cls token), LayerNorm eps 1e-6, then norm -> cls row (RTD_EVA_POOL_TOKEN)
+ * or mean of the patch tokens -> fc_norm (RTD_EVA_POOL_AVG), then the head.  Restated in tests/eva_ref.py.  csrc/classifier.hip.
+ * blob = the container rtd_load_weights reads, holding what eva_checkpoint.fold_state writes (csrc/classifier_host.h lists names and
+ * shapes): filters as [out][in] fp32 rows, 1 / 8 folded into the q rows, qkv as one [3 dim][dim] filter with a zero k bias, fc1_g | fc1_x
+ * as one filter, hidden / 3 patch^2 / classes zero-padded to whole 32-channel groups, and the RoPE sin / cos tables [L - 1][64] as data
+ * (the kernels hold no frequency rule).  A missing or mis-shaped tensor, a NaN / Inf and - pair engine - a value beyond 65504 return
+ * RTD_E_WEIGHTS with the tensor's name, before the device is touched.
+ * The GEMMs run on the library's conv kernels in the handle's precision, RTD_PREC_F16X3 (fp16 hi + lo pairs, attention on pair MFMAs
+ * too) or RTD_PREC_FP32.  The handle owns the filters and one arena (one plan per batch size; a repeated batch size allocates nothing)
+ * and NO stream: rtd_eva_forward is ASYNCHRONOUS on the caller's `stream`; calls on one handle go on ONE stream.
+ * Limits: head dim 64, dim and hidden at most 4096, 1..max_batch images per call (max_batch at most 64).  Anything else: RTD_E_INVALID
+ * before anything is launched, logits_dev untouched. */
+enum { RTD_EVA_POOL_TOKEN = 0, RTD_EVA_POOL_AVG = 1 };
+typedef struct rtd_eva_config {
+  int32_t struct_size; /* = sizeof(rtd_eva_config) */
+  int32_t device;
+  int32_t precision;   /* RTD_PREC_F16X3 | RTD_PREC_FP32 */
+  int32_t max_batch;   /* 1..64 */
+  int32_t img, patch;  /* 336, 14 */
+  int32_t dim, depth, heads; /* 1024, 24, 16 (dim = 64 heads) */
+  int32_t hidden;      /* the SwiGLU width before padding: int(dim * 8 / 3) = 2730 */
+  int32_t classes;     /* 10000 */
+  int32_t ref_feat;    /* the RoPE table's ref_feat_shape (16): recorded only, the table arrives in the blob */
+  int32_t scale_attn_inner; /* 1: LayerNorm between attention and proj (`attn.norm`) */
+  int32_t scale_mlp;   /* 1: LayerNorm between SwiGLU and fc2 (`mlp.norm`) */
+  int32_t pool;        /* RTD_EVA_POOL_* */
+  int32_t reserved0;
+} rtd_eva_config;
+typedef struct rtd_eva* rtd_eva_handle;
+int rtd_eva_create(const rtd_eva_config* cfg, const void* blob, size_t nbytes, rtd_eva_handle* out);
+/* x_dev: [n][3][img][img] fp32 NCHW, normalised (what rtd_crop_resize_batch writes); logits_dev: [n][classes] fp32 */
+int rtd_eva_forward(rtd_eva_handle e, const float* x_dev, int32_t n, float* logits_dev, void* stream);
+/* the pair format's one hazard on ViT outlier channels is fp16's range: *saturated = the values of the last call's final residual stream
+ * found AT +-65504, plus its logits at or beyond 65504 or not finite (0 = healthy).  Waits for the last call's stream.  RTD_E_STATE
+ * before the first successful forward. */
+int rtd_eva_self_check(rtd_eva_handle e, int64_t* saturated);
+int64_t rtd_eva_arena_bytes(rtd_eva_handle e);
+const char* rtd_eva_last_error(rtd_eva_handle e);                          /* e may be NULL: last error of a failed rtd_eva_create */
+void rtd_eva_close(rtd_eva_handle e);
+
 #ifdef __cplusplus
 }
 #endif

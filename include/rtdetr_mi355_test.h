@@ -229,6 +229,27 @@ int rtd_debug_ingest_info(int32_t matrix, int32_t full_range, int32_t coeffs[5],
 int rtd_debug_facemask_plan(int32_t n, const int32_t* hw, int32_t n_faces, const rtd_face_rect* faces, int32_t* layers, int32_t* layer_of,
                             int32_t* rects, int32_t* tile_h, int32_t* tile_w, int64_t* tiles, int32_t taps_k, uint16_t* taps);
 
+/* the classifier's own kernels (csrc/classifier.hip), device pointers, dense tensors, dtype 1 (fp32) or 4 (F16X2 pair storage):
+ * patchify:  x [n][3][img][img] fp32 NCHW -> rows [n G G][pad32(3 patch^2)], k = (c patch + i) patch + j as the conv filter flattens, zeros above
+ * rope:      in place on q and k of qkv [n L][3 * 64 heads] (q | k | v): out = x * cos + stack(-x[1::2], x[0::2]) * sin per head with the
+ *            tables sin, cos [L - 1][64] fp32; token 0 of every image and v stay as they are
+ * layernorm: y [rows][c] = LayerNorm over the first c_valid channels (gain, bias [c] fp32; channels from c_valid on are written as zero);
+ *            swiglu = 1: the input is [rows][2 c] = g | x and the normalised value is silu(g) * x; norm = 0: no normalisation (gain, bias unused).
+ *            c <= 4096, a multiple of 8 (pair storage: of 32)
+ * attention: o [n L][64 heads] = softmax(q k^T) v per head from qkv [n L][3 * 64 heads].  Pair storage: eva_attention, NO scale (the handle
+ *            folds 1 / 8 into q).  fp32: the library's launch_attention on the [q | k] view, which multiplies the scores by 1 / 8 itself
+ *            (the fp32 handle uploads the blob's folded q rows and q bias times 8, which undoes the fold exactly): pass q times 8 for the
+ *            same result */
+int rtd_op_eva_patchify(int dtype, const float* x, void* rows, int n, int img, int patch);
+int rtd_op_eva_rope(int dtype, void* qkv, const float* sin_t, const float* cos_t, int n, int L, int heads);
+int rtd_op_eva_layernorm(int dtype, const void* x, void* y, const float* gain, const float* bias, int rows, int c, int c_valid, int swiglu,
+                         int norm, float eps);
+int rtd_op_eva_attention(int dtype, const void* qkv, void* o, int n, int L, int heads);
+/* a float stage output of the last rtd_eva_forward, [n, 1, rows per image, c] fp32: `patch_embed`, `tokens`, `blocks.<k>.attn` (the
+ * residual stream after the attention branch), `blocks.<k>`, `pool` (after its LayerNorm), `logits`.  The plan reuses its buffers, so
+ * the call is run again up to that stage on its stream (the input must still be alive).  out may be NULL to ask for the shape. */
+int rtd_debug_eva_tensor(rtd_eva_handle e, const char* name, float* out, int64_t capacity, int64_t shape[4]);
+
 #ifdef __cplusplus
 }
 #endif

@@ -107,6 +107,11 @@ class RtdEsrganConfig(C.Structure):
                 ("num_grow_ch", C.c_int32), ("num_block", C.c_int32), ("tile", C.c_int32), ("tile_pad", C.c_int32)]
 
 
+class RtdEvaConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "device", "precision", "max_batch", "img", "patch", "dim", "depth", "heads", "hidden",
+                                         "classes", "ref_feat", "scale_attn_inner", "scale_mlp", "pool", "reserved0")]
+
+
 class RtdYuvFrame(C.Structure):
     _fields_ = [("y", C.c_void_p), ("u", C.c_void_p), ("v", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32),
                 ("y_pitch", C.c_int32), ("c_pitch", C.c_int32), ("layout", C.c_int32), ("matrix", C.c_int32), ("full_range", C.c_int32),
@@ -135,6 +140,7 @@ EXPORTS = [
     "rtd_esrgan_create", "rtd_esrgan_layout", "rtd_esrgan_upscale", "rtd_esrgan_arena_bytes", "rtd_esrgan_last_error", "rtd_esrgan_destroy",
     "rtd_ingest_create", "rtd_ingest_convert", "rtd_ingest_wait_stream", "rtd_ingest_last_error", "rtd_ingest_destroy",
     "rtd_facemask_create", "rtd_facemask_apply", "rtd_facemask_gray", "rtd_facemask_wait_stream", "rtd_facemask_last_error", "rtd_facemask_destroy",
+    "rtd_eva_create", "rtd_eva_forward", "rtd_eva_self_check", "rtd_eva_arena_bytes", "rtd_eva_last_error", "rtd_eva_close",
 ]
 # every symbol include/rtdetr_mi355_test.h declares: kernel-level test / bench / debug entry points (csrc/testapi.hip)
 TEST_EXPORTS = [
@@ -147,6 +153,7 @@ TEST_EXPORTS = [
     "rtd_op_gather_rows", "rtd_op_boxes", "rtd_op_add", "rtd_op_postprocess", "rtd_op_msdeform_discrete_view",
     "rtd_op_conv_avg", "rtd_op_conv_pool", "rtd_debug_conv_choice", "rtd_debug_last_conv", "rtd_debug_conv_instantiations",
     "rtd_debug_ingest_info", "rtd_op_stem0_u8", "rtd_debug_facemask_plan",
+    "rtd_op_eva_patchify", "rtd_op_eva_rope", "rtd_op_eva_layernorm", "rtd_op_eva_attention", "rtd_debug_eva_tensor",
 ]
 CONV_INFO_FIELDS = ("family", "stages", "bn", "mt", "bm", "smallc", "wsq", "sx", "cog", "S", "grid", "ntn")   # info[12] of the conv-choice calls
 
@@ -324,6 +331,21 @@ def lib() -> C.CDLL:
         L.rtd_facemask_destroy.restype = None
         L.rtd_debug_facemask_plan.argtypes = [i32, C.POINTER(i32), i32, C.POINTER(RtdFaceRect), C.POINTER(i32), C.POINTER(i32), C.POINTER(i32),
                                               C.POINTER(i32), C.POINTER(i32), C.POINTER(i64), i32, C.POINTER(C.c_uint16)]
+    if hasattr(L, "rtd_eva_create"):           # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_eva_create.argtypes = [C.POINTER(RtdEvaConfig), vp, C.c_size_t, C.POINTER(vp)]
+        L.rtd_eva_forward.argtypes = [vp, vp, i32, vp, vp]
+        L.rtd_eva_self_check.argtypes = [vp, C.POINTER(i64)]
+        L.rtd_eva_arena_bytes.argtypes = [vp]
+        L.rtd_eva_arena_bytes.restype = i64
+        L.rtd_eva_last_error.argtypes = [vp]
+        L.rtd_eva_last_error.restype = C.c_char_p
+        L.rtd_eva_close.argtypes = [vp]
+        L.rtd_eva_close.restype = None
+        L.rtd_debug_eva_tensor.argtypes = [vp, C.c_char_p, vp, i64, C.POINTER(i64)]
+        L.rtd_op_eva_patchify.argtypes = [i32, vp, vp, i32, i32, i32]
+        L.rtd_op_eva_rope.argtypes = [i32, vp, vp, vp, i32, i32, i32]
+        L.rtd_op_eva_layernorm.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32]
+        L.rtd_op_eva_attention.argtypes = [i32, vp, vp, i32, i32, i32]
     _lib = L
     return L
 
@@ -393,7 +415,7 @@ def _raise(code: int, handle=None) -> None:
     _raise_msg(code, Engine._what, lib().rtd_last_error(None))
 
 
-# ---- the nine handles (the engine; motion, mog2, jpeg, overlay, enhance, esrgan, ingest, facemask) ------------------------------------------------------
+# ---- the ten handles (the engine; motion, mog2, jpeg, overlay, enhance, esrgan, ingest, facemask, eva) ------------------------------------------------------
 def device_index(device) -> int:
     """an int, None (torch's current device), a torch.device or a string like 'cuda:1' -> the device's index"""
     if isinstance(device, int):
