@@ -417,6 +417,28 @@ int rtd_ingest_create(int32_t device, rtd_ingest_handle* out);
  * device memory; out_dev[i] is device memory of the caller with room for height x width x 3 bytes and receives the frame as tight HWC
  * BGR.  Two frames of a call must not share out_dev memory.  Synchronous: returns when every out_dev[i] is complete. */
 int rtd_ingest_convert(rtd_ingest_handle g, int32_t n, const rtd_yuv_frame* frames, int32_t frames_on_device, uint8_t* const* out_dev /* [n] */);
+/* The resize stage: camera frames at their native sizes in, BGR device frames of the requested sizes out, byte for byte OpenCV's
+ * resize(frame, (w, h)) with INTER_LINEAR on 8-bit data (restated in tests/face_ref.py resize_linear, composed with the conversion in
+ * tests/resize_ref.py): the 2 x 2 mean (a + b + c + d + 2) >> 2 where both scale factors are exactly 2, otherwise cv2's index and
+ * weight tables (weights in 1/2048, built on the host by csrc/resize_taps.h) and
+ *   out = (((b0 (H0 >> 4)) >> 16) + ((b1 (H1 >> 4)) >> 16) + 2) >> 2,  H = p[i0] w0 + p[i1] w1.
+ * A 4:2:0 frame is converted per source pixel first (the conversion clamps) and blended after.  Both calls are synchronous, use the
+ * handle's stream and staging buffer (descriptors, tiles, tables and host frames go up in ONE copy) and check every limit before
+ * anything is copied or launched: 1..RTD_INGEST_MAX_FRAMES frames, 1..65535 pixels per side for source and output, pitches of at
+ * least a row, no null source or output, at most 2^24 tiles of 128 x 8 output pixels per call, and no two outputs of a call
+ * (native ones included) sharing a byte.  Beyond a limit: RTD_E_INVALID with the frame's index in the message. */
+typedef struct rtd_bgr_frame { /* 24 bytes */
+  const uint8_t* data; /* height rows of width BGR pixels, pitch bytes apart */
+  int32_t width, height, pitch, reserved0;
+} rtd_bgr_frame;
+/* as rtd_ingest_convert, but out_dev[i] (out_hw[2i] x out_hw[2i+1] x 3 bytes) receives the frame resized to out_hw[2i] rows of
+ * out_hw[2i+1] pixels; native_out_dev may be NULL, and so may any of its entries: a non-null entry (height x width x 3 bytes) receives
+ * the frame at its own size as rtd_ingest_convert would write it */
+int rtd_ingest_convert_resize(rtd_ingest_handle g, int32_t n, const rtd_yuv_frame* frames, int32_t frames_on_device,
+                              const int32_t* out_hw /* [n][2] */, uint8_t* const* out_dev /* [n] */, uint8_t* const* native_out_dev /* [n] or NULL */);
+/* n BGR frames, all host memory (packed row by row into the staging buffer) or all device memory (read where they lie) */
+int rtd_ingest_resize(rtd_ingest_handle g, int32_t n, const rtd_bgr_frame* frames, int32_t frames_on_device,
+                      const int32_t* out_hw /* [n][2] */, uint8_t* const* out_dev /* [n] */);
 int rtd_ingest_wait_stream(rtd_ingest_handle g, void* producer_stream);   /* as rtd_wait_stream */
 const char* rtd_ingest_last_error(rtd_ingest_handle g);                  /* g may be NULL: last error of a failed rtd_ingest_create */
 void rtd_ingest_destroy(rtd_ingest_handle g);

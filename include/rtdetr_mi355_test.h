@@ -220,6 +220,14 @@ int rtd_debug_esrgan_tensor(rtd_esrgan_handle e, const char* name, float* out, i
 int rtd_debug_ingest_info(int32_t matrix, int32_t full_range, int32_t coeffs[5], int32_t* tile_h, int32_t* tile_w, int32_t n,
                           const rtd_yuv_frame* frames, int64_t* tiles);
 
+/* the tables of the ingest's resize stage, pure host arithmetic (no GPU, no handle): out receives the dsize entries i0, i1, w0, w1 of
+ * the INTER_LINEAR pass from ssize to dsize samples (columns != 0: the column rule, else the row rule) as csrc/resize_taps.h builds
+ * them; *is_area2 whether a resize of ssize x ssize2 (width x height) to dsize x dsize2 is the 2 x 2 mean instead; tile_hw the output
+ * pixels (rows, columns) of one workgroup of the resize kernel.  out, is_area2 and tile_hw may be NULL.  RTD_E_INVALID for a size
+ * outside 1..65535.  csrc/ingest.hip. */
+int rtd_debug_resize_table(int32_t ssize, int32_t dsize, int32_t columns, int32_t* out /* [4 * dsize] */, int32_t ssize2, int32_t dsize2,
+                           int32_t* is_area2, int32_t tile_hw[2]);
+
 /* what rtd_facemask_apply would do with a call, pure host arithmetic (no GPU, no handle; the frames themselves are not looked at): the
  * number of layers, per face its layer (-1: skipped, its padded rectangle is empty) and its padded rectangle x1, y1, x2, y2 (the blur /
  * pixelate region, exclusive ends), the tile of one workgroup (pixels) and per launch kind the tiles of the whole call (tiles[5]: blur

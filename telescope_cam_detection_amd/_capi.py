@@ -118,6 +118,10 @@ class RtdYuvFrame(C.Structure):
                 ("reserved0", C.c_int32)]
 
 
+class RtdBgrFrame(C.Structure):
+    _fields_ = [("data", C.c_void_p), ("width", C.c_int32), ("height", C.c_int32), ("pitch", C.c_int32), ("reserved0", C.c_int32)]
+
+
 class RtdFaceRect(C.Structure):
     _fields_ = [("frame", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("w", C.c_int32), ("h", C.c_int32), ("style", C.c_int32),
                 ("k_or_blocks", C.c_int32), ("reserved0", C.c_int32)]
@@ -138,7 +142,7 @@ EXPORTS = [
     "rtd_overlay_create", "rtd_overlay_draw", "rtd_overlay_wait_stream", "rtd_overlay_last_error", "rtd_overlay_destroy",
     "rtd_enhance_create", "rtd_enhance_layout", "rtd_enhance_crops", "rtd_enhance_last_error", "rtd_enhance_destroy",
     "rtd_esrgan_create", "rtd_esrgan_layout", "rtd_esrgan_upscale", "rtd_esrgan_arena_bytes", "rtd_esrgan_last_error", "rtd_esrgan_destroy",
-    "rtd_ingest_create", "rtd_ingest_convert", "rtd_ingest_wait_stream", "rtd_ingest_last_error", "rtd_ingest_destroy",
+    "rtd_ingest_create", "rtd_ingest_convert", "rtd_ingest_convert_resize", "rtd_ingest_resize", "rtd_ingest_wait_stream", "rtd_ingest_last_error", "rtd_ingest_destroy",
     "rtd_facemask_create", "rtd_facemask_apply", "rtd_facemask_gray", "rtd_facemask_wait_stream", "rtd_facemask_last_error", "rtd_facemask_destroy",
     "rtd_eva_create", "rtd_eva_forward", "rtd_eva_self_check", "rtd_eva_arena_bytes", "rtd_eva_last_error", "rtd_eva_close",
 ]
@@ -152,7 +156,7 @@ TEST_EXPORTS = [
     "rtd_op_msdeform_view", "rtd_op_select_score", "rtd_op_gather_ln", "rtd_op_split_convert", "rtd_op_set_rows", "rtd_op_rowmax",
     "rtd_op_gather_rows", "rtd_op_boxes", "rtd_op_add", "rtd_op_postprocess", "rtd_op_msdeform_discrete_view",
     "rtd_op_conv_avg", "rtd_op_conv_pool", "rtd_debug_conv_choice", "rtd_debug_last_conv", "rtd_debug_conv_instantiations",
-    "rtd_debug_ingest_info", "rtd_op_stem0_u8", "rtd_debug_facemask_plan",
+    "rtd_debug_ingest_info", "rtd_debug_resize_table", "rtd_op_stem0_u8", "rtd_debug_facemask_plan",
     "rtd_op_eva_patchify", "rtd_op_eva_rope", "rtd_op_eva_layernorm", "rtd_op_eva_attention", "rtd_debug_eva_tensor",
 ]
 CONV_INFO_FIELDS = ("family", "stages", "bn", "mt", "bm", "smallc", "wsq", "sx", "cog", "S", "grid", "ntn")   # info[12] of the conv-choice calls
@@ -318,6 +322,10 @@ def lib() -> C.CDLL:
         L.rtd_ingest_destroy.argtypes = [vp]
         L.rtd_ingest_destroy.restype = None
         L.rtd_debug_ingest_info.argtypes = [i32, i32, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), i32, C.POINTER(RtdYuvFrame), C.POINTER(i64)]
+    if hasattr(L, "rtd_ingest_resize"):        # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_ingest_convert_resize.argtypes = [vp, i32, C.POINTER(RtdYuvFrame), i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(vp)]
+        L.rtd_ingest_resize.argtypes = [vp, i32, C.POINTER(RtdBgrFrame), i32, C.POINTER(i32), C.POINTER(vp)]
+        L.rtd_debug_resize_table.argtypes = [i32, i32, i32, C.POINTER(i32), i32, i32, C.POINTER(i32), C.POINTER(i32)]
     if hasattr(L, "rtd_op_stem0_u8"):          # (absent from older builds loaded through RTD_LIB_PATH)
         L.rtd_op_stem0_u8.argtypes = [C.POINTER(vp), i32, i32, i32, vp, vp, vp, i32]
     if hasattr(L, "rtd_facemask_create"):      # (absent from older builds loaded through RTD_LIB_PATH)

@@ -8,6 +8,9 @@ loop semantics and the queue item are the reference class's; what differs:
 
 * `decoder_args` (default none) goes in front of `-i`: a site names its hardware decoder there, e.g. ("-hwaccel", "vaapi").
 * `matrix` / `full_range` choose the conversion (BT.601 limited by default: swscale's own choice for a stream without colour tags).
+* `source_size=(w, h)` states the stream's native size: ffmpeg is then asked for no `-s` (no swscale resize on a CPU core), the thread
+  reads native frames and the ingest resizes them to the target size on the GPU (`cv2.resize`'s bytes, not swscale's); with
+  `keep_native` the native BGR frame stays on the device beside it (`latest_native_frame`, the queue item's `native_frame`) for Stage 2.
 * `popen` and `ingest` are seams for tests: a stand-in for subprocess.Popen, and an object with `to_bgr` as FrameIngest.
 
 `install(main_module)` lets the reference's main.py build this class in place of its `RTSPStreamCapture` without editing it.
@@ -19,7 +22,7 @@ import subprocess
 import time
 from queue import Full, Queue
 from threading import Event, Lock, Thread
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 from .ingest import frame_bytes
 
@@ -40,7 +43,8 @@ class RTSPStreamCaptureGPU:
     def __init__(self, rtsp_url: str, frame_queue: Queue, target_width: int = 1280, target_height: int = 720, camera_id: str = "default",
                  camera_name: str = "Default Camera", use_tcp: bool = False, buffer_size: Optional[int] = None, max_failures: int = 30,
                  retry_delay: float = 5.0, keep_frames_on_gpu: bool = True, device="cuda:0", decoder_args: Sequence[str] = (),
-                 matrix: str = "bt601", full_range: bool = False, popen=subprocess.Popen, ingest=None):
+                 matrix: str = "bt601", full_range: bool = False, popen=subprocess.Popen, ingest=None,
+                 source_size: Optional[Tuple[int, int]] = None, keep_native: bool = False):
         import torch
 
         self.rtsp_url = rtsp_url
@@ -60,6 +64,11 @@ class RTSPStreamCaptureGPU:
         self.full_range = bool(full_range)
         self._popen = popen
         self._ingest = ingest
+        # (w, h) of the stream as the camera sends it: the operator's statement, nothing probes it
+        self.source_size = None if source_size is None else (int(source_size[0]), int(source_size[1]))
+        self.keep_native = bool(keep_native)
+        if self.keep_native and self.source_size is None:
+            raise ValueError("keep_native needs source_size")
         if buffer_size is not None:
             logger.warning(f"[{camera_id}] buffer_size={buffer_size} is ignored: ffmpeg buffers the stream itself")
 
@@ -68,6 +77,7 @@ class RTSPStreamCaptureGPU:
         self.capture_thread: Optional[Thread] = None
         self.is_connected = False
         self.latest_frame = None              # a device tensor, or a numpy array with keep_frames_on_gpu = False
+        self.latest_native_frame = None       # with keep_native: the same frame at the source size
         self.frame_lock = Lock()
 
         self.frame_count = 0                  # frames since the last FPS reading
@@ -82,6 +92,8 @@ class RTSPStreamCaptureGPU:
         cmd = ["ffmpeg", *self.decoder_args]
         if self.use_tcp:
             cmd += ["-rtsp_transport", "tcp"]
+        if self.source_size is not None:      # native frames over the pipe: the resize is the ingest's
+            return cmd + ["-i", self.rtsp_url, "-f", "rawvideo", "-pix_fmt", "nv12", "pipe:1"]
         cmd += ["-i", self.rtsp_url, "-f", "rawvideo", "-pix_fmt", "nv12", "-s", f"{self.target_width}x{self.target_height}", "pipe:1"]
         return cmd
 
@@ -151,6 +163,19 @@ class RTSPStreamCaptureGPU:
         return self.connect()
 
     # ---- the loop -----------------------------------------------------------------------------------------------------------------------
+    def _convert_native(self, raw: bytes):
+        """one native NV12 frame off the pipe -> (the target-size BGR frame, the native BGR frame or None)"""
+        sw, sh = self.source_size
+        kw = dict(layout="nv12", matrix=self.matrix, full_range=self.full_range, out_sizes=(self.target_height, self.target_width))
+        if self.keep_native:
+            imgs, natives = self._ingest.to_bgr([raw], [(sh, sw)], native_out=True, **kw)
+            img, native = imgs[0], natives[0]
+        else:
+            img, native = self._ingest.to_bgr([raw], [(sh, sw)], **kw)[0], None
+        if not self.keep_frames_on_gpu:
+            img, native = img.cpu().numpy(), None if native is None else native.cpu().numpy()
+        return img, native
+
     def _convert(self, raw: bytes):
         """one NV12 frame off the pipe -> a BGR device tensor, or its numpy copy"""
         size = (self.target_height, self.target_width)
@@ -167,7 +192,7 @@ class RTSPStreamCaptureGPU:
 
     def _capture_loop(self) -> None:
         failures = 0
-        need = frame_bytes(self.target_height, self.target_width)
+        need = frame_bytes(self.target_height, self.target_width) if self.source_size is None else frame_bytes(self.source_size[1], self.source_size[0])
         while not self.stop_event.is_set():
             try:
                 if not self.is_connected or self.ffmpeg_process is None:
@@ -183,15 +208,23 @@ class RTSPStreamCaptureGPU:
                     logger.warning(f"[{self.camera_id}] short read: {len(raw)} of {need} bytes ({failures}/{self.max_failures})")
                     failures = self._failed(failures)
                     continue
-                img = self._convert(raw)
+                native = None
+                if self.source_size is None:
+                    img = self._convert(raw)
+                else:
+                    img, native = self._convert_native(raw)
                 with self.frame_lock:
                     self.latest_frame = img
+                    if self.keep_native:
+                        self.latest_native_frame = native
                 # the queue gets a tensor of its own: its consumer and the readers of latest_frame never share memory
-                queued = img.clone() if self.keep_frames_on_gpu else img.copy()
+                own = (lambda t: t.clone()) if self.keep_frames_on_gpu else (lambda a: a.copy())
+                item = {"frame": own(img), "timestamp": time.time(), "frame_id": self.frame_id_counter, "camera_id": self.camera_id,
+                        "camera_name": self.camera_name, "is_gpu_tensor": self.keep_frames_on_gpu}
+                if self.keep_native:
+                    item["native_frame"] = own(native)
                 try:
-                    self.frame_queue.put_nowait({"frame": queued, "timestamp": time.time(), "frame_id": self.frame_id_counter,
-                                                 "camera_id": self.camera_id, "camera_name": self.camera_name,
-                                                 "is_gpu_tensor": self.keep_frames_on_gpu})
+                    self.frame_queue.put_nowait(item)
                     self.frame_count += 1
                     self.frame_id_counter += 1
                 except Full:
@@ -221,6 +254,10 @@ class RTSPStreamCaptureGPU:
         with self.frame_lock:
             return self.latest_frame
 
+    def get_latest_native_frame(self):
+        with self.frame_lock:
+            return self.latest_native_frame
+
     def get_latest_frame_as_numpy(self):
         frame = self.get_latest_frame()
         if frame is not None and hasattr(frame, "cpu"):
@@ -232,7 +269,7 @@ class RTSPStreamCaptureGPU:
                 "queue_size": self.frame_queue.qsize()}
 
 
-def install(main_module, **defaults) -> None:
+def install(main_module, source_size=None, **defaults) -> None:
     """Let the reference's main.py capture through this class without editing it:
 
         import main, telescope_cam_detection_amd.capture as cap
@@ -240,10 +277,18 @@ def install(main_module, **defaults) -> None:
 
     `main._create_stream_capture` builds `RTSPStreamCapture(rtsp_url=..., frame_queue=..., target_width=..., target_height=...,
     camera_id=..., camera_name=..., use_tcp=..., buffer_size=..., max_failures=..., retry_delay=...)`; the name is rebound to a subclass of
-    RTSPStreamCaptureGPU that takes those keywords and adds `defaults` (decoder_args, device, keep_frames_on_gpu, matrix, full_range)."""
+    RTSPStreamCaptureGPU that takes those keywords and adds `defaults` (decoder_args, device, keep_frames_on_gpu, matrix, full_range,
+    keep_native).  `source_size` is one (w, h) for all cameras, or a dict keyed by camera_id: a camera that is absent from it keeps the
+    `-s` command (and gets no keep_native)."""
     class RTSPStreamCapture(RTSPStreamCaptureGPU):
         def __init__(self, *args, **kwargs):
-            super().__init__(*args, **{**defaults, **kwargs})
+            kw = {**defaults, **kwargs}
+            if source_size is not None and "source_size" not in kwargs:
+                cam = kw.get("camera_id", "default")
+                kw["source_size"] = source_size.get(cam) if isinstance(source_size, dict) else source_size
+                if kw["source_size"] is None:
+                    kw.pop("keep_native", None)
+            super().__init__(*args, **kw)
 
     if not hasattr(main_module, "_rtd_original_RTSPStreamCapture"):
         main_module._rtd_original_RTSPStreamCapture = getattr(main_module, "RTSPStreamCapture", None)

@@ -15,6 +15,7 @@
 #include "../../include/rtdetr_mi355.h"
 #include "error.h"
 #include "gauss_taps.h"
+#include "resize_taps.h"
 
 namespace facemask_host {
 
@@ -43,11 +44,6 @@ struct FaceDesc {            // 80 bytes; what the kernels read, the same for ev
 
 struct TileRef {
   int32_t face, tile;        // face: index into the descriptors; tile = ty * tiles_x + tx (K_PIX_SMALL: the SMALL_TILE chunk)
-};
-
-struct LinEntry {            // one column (or row) of the INTER_LINEAR pass: S[i0] * w0 + S[i1] * w1
-  int32_t i0, i1;
-  int16_t w0, w1;
 };
 
 struct Rect {                // x2, y2 exclusive
@@ -98,53 +94,14 @@ inline void validate_frames(int64_t n, uint8_t* const* frames) {
   for (int64_t i = 0; i < n; ++i) RTD_CHECK(frames[i], RTD_E_INVALID, "frame " + std::to_string(i) + " is a null pointer");
 }
 
-// ---- OpenCV's resize tables (imgproc/src/resize.cpp), in its own double / float arithmetic ---------------------------------------------
+// ---- OpenCV's resize tables (imgproc/src/resize.cpp): the INTER_LINEAR index and weight tables and the 2 x 2 area rule are resize_taps.h,
+// shared with the frame ingest's resize stage ------------------------------------------------------------------------------------------
 
-inline int cv_round(double v) { return (int)nearbyint(v); }     // cvRound: half to even (the default rounding mode)
-
-// cv::resize: inv_scale = (double)dsize / ssize; hal::resize: scale = 1. / inv_scale
-inline double resize_scale(int ssize, int dsize) {
-  const double inv_scale = (double)dsize / ssize;
-  return 1. / inv_scale;
-}
-
-// hal::resize: INTER_LINEAR becomes the 2 x 2 INTER_AREA mean when both scale factors are exactly 2 (is_area_fast && iscale == 2)
-inline bool area2(int rw, int rh, int sw, int sh) {
-  const double scale_x = resize_scale(rw, sw), scale_y = resize_scale(rh, sh);
-  const int iscale_x = cv_round(scale_x), iscale_y = cv_round(scale_y);      // saturate_cast<int>(double)
-  const bool is_area_fast = fabs(scale_x - iscale_x) < DBL_EPSILON && fabs(scale_y - iscale_y) < DBL_EPSILON;
-  return is_area_fast && iscale_x == 2 && iscale_y == 2;
-}
-
-// resizeGeneric_'s table loops for INTER_LINEAR on 8-bit input: entry d of a pass from ssize to dsize samples.
-// Columns: the fraction becomes 0 where the left sample is the first or the last column (so HResizeLinear's S[sx] * ONE beyond xmax
-// is S[i0] * 2048 + S[i1] * 0 here).  Rows: the table keeps the fraction and resizeGeneric_Invoker clips the two row indices; a
-// down-scale reaches the last row only with the fraction 0, so both rules give the same bytes for every pixelate call.
-inline void linear_table(int ssize, int dsize, bool columns, LinEntry* out) {
-#if defined(__clang__)
-#pragma clang fp contract(off)
-#endif
-  const double scale = resize_scale(ssize, dsize);
-  for (int d = 0; d < dsize; ++d) {
-    double pos = (d + 0.5) * scale;                 // fx = (float)((dx + 0.5) * scale_x - 0.5), the product and the difference rounded
-    pos -= 0.5;                                     // one after the other (two statements: never a fused multiply-add)
-    float f = (float)pos;
-    int s = (int)floorf(f);                         // cvFloor
-    f -= (float)s;
-    int s1;
-    if (columns) {
-      if (s < 0) f = 0, s = 0;
-      if (s >= ssize - 1) f = 0, s = ssize - 1;
-      s1 = std::min(s + 1, ssize - 1);
-    } else {
-      s1 = std::min(std::max(s + 1, 0), ssize - 1);                          // clip(sy0 + k, 0, ssize.height)
-      s = std::min(std::max(s, 0), ssize - 1);
-    }
-    const float c0 = 1.f - f, c1 = f;
-    out[d].i0 = s, out[d].i1 = s1;
-    out[d].w0 = (int16_t)lrintf(c0 * 2048), out[d].w1 = (int16_t)lrintf(c1 * 2048);   // saturate_cast<short>(cbuf[k] * INTER_RESIZE_COEF_SCALE)
-  }
-}
+using resize_taps::LinEntry;
+using resize_taps::area2;
+using resize_taps::cv_round;
+using resize_taps::linear_table;
+using resize_taps::resize_scale;
 
 // resizeNN from ssize samples up to dsize: x_ofs[x] = min(cvFloor(x * ifx), ssize - 1) with ifx = 1. / ((double)dsize / ssize)
 inline void nearest_table(int ssize, int dsize, int32_t* out) {

@@ -143,6 +143,180 @@ __global__ void __launch_bounds__(THREADS) ingest_kernel(const FrameDesc* __rest
   else strip_bytes(d, x0, y0);
 }
 
+// ---- the resize stage: OpenCV's resize(frame, (w, h)) with INTER_LINEAR on the converted (or BGR) frame, tests/resize_ref.py -----------
+// One workgroup per listed 128 x 8 tile of OUTPUT pixels; a thread makes four output pixels of one row (12 bytes: three dwords where
+// the output rows start on a dword, bytes otherwise and for a row's short tail; only ever its own bytes).  Two paths, chosen per frame
+// on the host (resize_taps.h area2): the 2 x 2 mean, whose four output pixels are the convert kernel's strip of 8 source pixels in two
+// rows, loaded the same way (dwords where the source rows allow it) with one chroma sample per block; and the linear path, which reads
+// its four taps per output pixel from the per-frame column and row tables and converts every tap in registers (no LDS: the taps of a
+// tile span a source region whose size depends on the scale, from a fraction of a pixel to 65535, and one code path serves them all).
+
+enum { SRC_YUV = 0, SRC_BGR = 1 };
+typedef const RTD_GLOBAL LinEntry* GLin;
+
+__device__ inline Chroma chroma_at(const FrameDesc& d, int cx, int cy) {
+  const GBytes pu = (GBytes)d.u, pv = (GBytes)d.v;
+  const size_t crow = (size_t)cy * d.c_pitch;
+  uint32_t U, V;
+  if (d.flags & F_INTERLEAVED) {
+    const uint32_t a = pu[crow + 2 * cx], b = pu[crow + 2 * cx + 1];
+    U = (d.flags & F_SWAP) ? b : a;
+    V = (d.flags & F_SWAP) ? a : b;
+  } else {
+    U = pu[crow + cx];
+    V = pv[crow + cx];
+  }
+  return chroma_terms(d, U, V);
+}
+__device__ inline uint32_t luma_at(const FrameDesc& d, int x, int y) { return ((GBytes)d.y)[(size_t)y * d.y_pitch + x]; }
+__device__ inline uint32_t bgr_at(const FrameDesc& d, int x, int y) {
+  const GBytes p = (GBytes)d.y + (size_t)y * d.y_pitch + (size_t)x * 3;
+  return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16;
+}
+
+// the source pixels (x0, y0), (x1, y0), (x0, y1), (x1, y1) as b | g << 8 | r << 16; a chroma sample two taps share is read once
+template <int SRC>
+__device__ inline void taps4(const FrameDesc& s, int x0, int x1, int y0, int y1, uint32_t p[4]) {
+  if (SRC == SRC_BGR) {
+    p[0] = bgr_at(s, x0, y0), p[1] = bgr_at(s, x1, y0), p[2] = bgr_at(s, x0, y1), p[3] = bgr_at(s, x1, y1);
+  } else {
+    const int cx0 = x0 >> 1, cx1 = x1 >> 1, cy0 = y0 >> 1, cy1 = y1 >> 1;
+    const Chroma c00 = chroma_at(s, cx0, cy0);
+    Chroma c01 = c00, c10 = c00;
+    if (cx1 != cx0) c01 = chroma_at(s, cx1, cy0);
+    if (cy1 != cy0) c10 = chroma_at(s, cx0, cy1);
+    Chroma c11 = cy1 == cy0 ? c01 : c10;
+    if (cy1 != cy0 && cx1 != cx0) c11 = chroma_at(s, cx1, cy1);
+    p[0] = pixel(s, luma_at(s, x0, y0), c00), p[1] = pixel(s, luma_at(s, x1, y0), c01);
+    p[2] = pixel(s, luma_at(s, x0, y1), c10), p[3] = pixel(s, luma_at(s, x1, y1), c11);
+  }
+}
+
+// HResizeLinear then VResizeLinear on one output pixel, per channel; every value is non-negative and every product below 2^27
+__device__ inline uint32_t blend(const uint32_t p[4], int w0, int w1, int b0, int b1) {
+  uint32_t o = 0;
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) {
+    const int h0 = __mul24((int)((p[0] >> (8 * ch)) & 0xffu), w0) + __mul24((int)((p[1] >> (8 * ch)) & 0xffu), w1);
+    const int h1 = __mul24((int)((p[2] >> (8 * ch)) & 0xffu), w0) + __mul24((int)((p[3] >> (8 * ch)) & 0xffu), w1);
+    const int v = ((__mul24(b0, h0 >> 4) >> 16) + (__mul24(b1, h1 >> 4) >> 16) + 2) >> 2;                // at most 255 (w0 + w1 and b0 + b1 are at most 2049)
+    o |= (uint32_t)v << (8 * ch);
+  }
+  return o;
+}
+
+// (a + b + c + d + 2) >> 2 per channel of four packed pixels: blue and red in one sum (16 bits apart), green in another
+__device__ inline uint32_t mean4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
+  const uint32_t m = 0x00ff00ffu;
+  const uint32_t br = (((a & m) + (b & m) + (c & m) + (d & m) + 0x00020002u) >> 2) & m;
+  const uint32_t g = (((a >> 8) & 0xffu) + ((b >> 8) & 0xffu) + ((c >> 8) & 0xffu) + ((d >> 8) & 0xffu) + 2u) >> 2;
+  return br | g << 8;
+}
+
+// the area path where the source rows start on dwords: the output pixels ox .. ox + 3 (ox a multiple of 4, all inside the row) of row oy
+template <int SRC>
+__device__ inline void area_wide(const FrameDesc& s, int ox, int oy, uint32_t px[RPX]) {
+  const int x0 = 2 * ox, y0 = 2 * oy;
+  if (SRC == SRC_BGR) {
+    const GWord r0 = (GWord)((GBytes)s.y + (size_t)y0 * s.y_pitch + (size_t)x0 * 3), r1 = (GWord)((GBytes)r0 + s.y_pitch);
+    uint32_t a[6], b[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) a[k] = r0[k], b[k] = r1[k];
+#pragma unroll
+    for (int k = 0; k < RPX; ++k) {
+      uint32_t q[4];
+#pragma unroll
+      for (int j = 0; j < 2; ++j) {
+        const int at = 3 * (2 * k + j);
+        q[j] = byte_of(a, at) | byte_of(a, at + 1) << 8 | byte_of(a, at + 2) << 16;
+        q[2 + j] = byte_of(b, at) | byte_of(b, at + 1) << 8 | byte_of(b, at + 2) << 16;
+      }
+      px[k] = mean4(q[0], q[1], q[2], q[3]);
+    }
+  } else {
+    const GBytes yrow = (GBytes)s.y + (size_t)y0 * s.y_pitch + x0, pu = (GBytes)s.u, pv = (GBytes)s.v;
+    const Words2 l0 = load2(yrow), l1 = load2(yrow + s.y_pitch);
+    const size_t crow = (size_t)oy * s.c_pitch;
+    uint32_t cu[RPX], cv[RPX];
+    if (s.flags & F_INTERLEAVED) {
+      const Words2 c = load2(pu + crow + x0);
+#pragma unroll
+      for (int k = 0; k < RPX; ++k) {
+        const uint32_t a = byte_of(c.w, 2 * k), b = byte_of(c.w, 2 * k + 1);
+        cu[k] = (s.flags & F_SWAP) ? b : a;
+        cv[k] = (s.flags & F_SWAP) ? a : b;
+      }
+    } else {
+      const uint32_t wu = *(GWord)(pu + crow + ox), wv = *(GWord)(pv + crow + ox);
+#pragma unroll
+      for (int k = 0; k < RPX; ++k) cu[k] = byte_of(&wu, k), cv[k] = byte_of(&wv, k);
+    }
+#pragma unroll
+    for (int k = 0; k < RPX; ++k) {
+      const Chroma c = chroma_terms(s, cu[k], cv[k]);
+      px[k] = mean4(pixel(s, byte_of(l0.w, 2 * k), c), pixel(s, byte_of(l0.w, 2 * k + 1), c), pixel(s, byte_of(l1.w, 2 * k), c),
+                    pixel(s, byte_of(l1.w, 2 * k + 1), c));
+    }
+  }
+}
+
+// the area path of any frame, byte by byte: the first cnt of the four output pixels
+template <int SRC>
+__device__ inline void area_bytes(const FrameDesc& s, int ox, int oy, int cnt, uint32_t px[RPX]) {
+#pragma unroll
+  for (int k = 0; k < RPX; ++k) {
+    if (k >= cnt) break;
+    const int x = 2 * (ox + k), y = 2 * oy;
+    if (SRC == SRC_BGR) {
+      px[k] = mean4(bgr_at(s, x, y), bgr_at(s, x + 1, y), bgr_at(s, x, y + 1), bgr_at(s, x + 1, y + 1));
+    } else {
+      const Chroma c = chroma_at(s, ox + k, oy);
+      px[k] = mean4(pixel(s, luma_at(s, x, y), c), pixel(s, luma_at(s, x + 1, y), c), pixel(s, luma_at(s, x, y + 1), c),
+                    pixel(s, luma_at(s, x + 1, y + 1), c));
+    }
+  }
+}
+
+template <int SRC>
+__global__ void __launch_bounds__(THREADS) resize_kernel(const ResizeDesc* __restrict__ descs, const TileRef* __restrict__ tiles) {
+  const TileRef t = tiles[blockIdx.x];
+  const ResizeDesc d = descs[t.frame];
+  const int tx = t.tile % d.tiles_x, ty = t.tile / d.tiles_x;
+  const int ox = tx * RTILE_W + (int)(threadIdx.x % TX) * RPX, oy = ty * RTILE_H + (int)(threadIdx.x / TX);
+  if (ox >= d.OW || oy >= d.OH) return;
+  const int cnt = min(RPX, d.OW - ox);
+  uint32_t px[RPX] = {0u, 0u, 0u, 0u};
+  if (d.rflags & R_AREA) {
+    if ((d.rflags & R_SRC_WIDE) && cnt == RPX) area_wide<SRC>(d.src, ox, oy, px);
+    else area_bytes<SRC>(d.src, ox, oy, cnt, px);
+  } else {
+    const GLin tab = (GLin)d.tab;
+    const GLin r = tab + d.OW + oy;                        // (members one by one: a struct in the global address space is not copyable)
+    const int j0 = r->i0, j1 = r->i1, b0 = r->w0, b1 = r->w1;
+#pragma unroll
+    for (int k = 0; k < RPX; ++k) {
+      if (k >= cnt) break;
+      const GLin e = tab + ox + k;
+      uint32_t p[4];
+      taps4<SRC>(d.src, e->i0, e->i1, j0, j1, p);
+      px[k] = blend(p, e->w0, e->w1, b0, b1);
+    }
+  }
+  const GOut o = (GOut)d.out + ((size_t)oy * d.OW + ox) * 3;
+  if ((d.rflags & R_DST_WIDE) && cnt == RPX) {
+    const GOutWord q = (GOutWord)o;
+    q[0] = px[0] | px[1] << 24;
+    q[1] = px[1] >> 8 | px[2] << 16;
+    q[2] = px[2] >> 16 | px[3] << 8;
+  } else {
+#pragma unroll
+    for (int k = 0; k < RPX; ++k) {
+      if (k >= cnt) break;
+      o[3 * k] = (uint8_t)px[k], o[3 * k + 1] = (uint8_t)(px[k] >> 8), o[3 * k + 2] = (uint8_t)(px[k] >> 16);
+    }
+  }
+}
+
 }  // namespace ingest
 
 using namespace ingest;
@@ -169,6 +343,39 @@ static void convert(rtd_ingest* g, int n, const rtd_yuv_frame* frames, bool on_d
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
+// either resize call: up to three launches on the handle's stream after the one staging copy - the convert kernel for the frames
+// whose native BGR frame is wanted, the fused kernel for the other 4:2:0 frames, the BGR kernel for BGR sources and for the native
+// frames the convert kernel has just written
+static void resize(rtd_ingest* g, const ResizeCall& c) {
+  hipStream_t s = g->q.stream;
+  const ResizePlan p = plan_resize(c);
+  g->pin.reserve(p.total);
+  g->dev.reserve(p.total);
+  fill_resize(g->pin.p, p, c, g->dev.p);
+  if (!c.on_device) pack_sources(g->pin.p, p, c);
+  HIP_CHECK(hipMemcpyAsync(g->dev.p, g->pin.p, p.total, hipMemcpyHostToDevice, s));       // tables and frames: one DMA
+  const ResizeDesc* descs = (const ResizeDesc*)g->dev.p;
+  const TileRef* tiles = (const TileRef*)(g->dev.p + p.tile_off);
+  if (p.conv_tiles) rtd::rtd_launch(ingest_kernel, dim3((unsigned)p.conv_tiles), dim3(THREADS), 0, s, (const FrameDesc*)(g->dev.p + p.fdesc_off), tiles);
+  if (p.fused_tiles) rtd::rtd_launch(resize_kernel<SRC_YUV>, dim3((unsigned)p.fused_tiles), dim3(THREADS), 0, s, descs, tiles + p.conv_tiles);
+  if (p.bgr_tiles) rtd::rtd_launch(resize_kernel<SRC_BGR>, dim3((unsigned)p.bgr_tiles), dim3(THREADS), 0, s, descs, tiles + p.conv_tiles + p.fused_tiles);
+  HIP_CHECK(hipGetLastError());
+  HIP_CHECK(hipStreamSynchronize(s));
+}
+
+static int resize_call(rtd_ingest* g, const ResizeCall& c) {
+  return guarded(g, [&] {
+    validate_resize(c);
+    HIP_CHECK(hipSetDevice(g->device));
+    try {
+      resize(g, c);
+    } catch (...) {
+      g->q.drain();                                        // nothing of a failed call may still read the staging buffers
+      throw;
+    }
+  });
+}
+
 }  // namespace ingest
 
 extern "C" {
@@ -192,6 +399,16 @@ int rtd_ingest_convert(rtd_ingest_handle g, int32_t n, const rtd_yuv_frame* fram
       throw;
     }
   });
+}
+
+int rtd_ingest_convert_resize(rtd_ingest_handle g, int32_t n, const rtd_yuv_frame* frames, int32_t frames_on_device, const int32_t* out_hw,
+                              uint8_t* const* out_dev, uint8_t* const* native_out_dev) {
+  return resize_call(g, ResizeCall{n, frames, nullptr, frames_on_device != 0, out_hw, out_dev, native_out_dev});
+}
+
+int rtd_ingest_resize(rtd_ingest_handle g, int32_t n, const rtd_bgr_frame* frames, int32_t frames_on_device, const int32_t* out_hw,
+                      uint8_t* const* out_dev) {
+  return resize_call(g, ResizeCall{n, nullptr, frames, frames_on_device != 0, out_hw, out_dev, nullptr});
 }
 
 int rtd_ingest_wait_stream(rtd_ingest_handle g, void* producer_stream) {
@@ -230,6 +447,25 @@ int rtd_debug_ingest_info(int32_t matrix, int32_t full_range, int32_t coeffs_out
         *tiles += tiles_of(frames[i]);
       }
     }
+  });
+}
+
+int rtd_debug_resize_table(int32_t ssize, int32_t dsize, int32_t columns, int32_t* out, int32_t ssize2, int32_t dsize2, int32_t* is_area2,
+                           int32_t tile_hw[2]) {
+  static thread_local std::string err;
+  return bk::caught(err, [&] {
+    auto ok = [](int32_t v) { return v >= 1 && v <= 65535; };
+    if (out) {
+      RTD_CHECK(ok(ssize) && ok(dsize), RTD_E_INVALID, "bad size (1..65535)");
+      std::vector<LinEntry> t((size_t)dsize);
+      resize_taps::linear_table(ssize, dsize, columns != 0, t.data());
+      for (int32_t d = 0; d < dsize; ++d) out[4 * d] = t[(size_t)d].i0, out[4 * d + 1] = t[(size_t)d].i1, out[4 * d + 2] = t[(size_t)d].w0, out[4 * d + 3] = t[(size_t)d].w1;
+    }
+    if (is_area2) {
+      RTD_CHECK(ok(ssize) && ok(dsize) && ok(ssize2) && ok(dsize2), RTD_E_INVALID, "bad size (1..65535)");
+      *is_area2 = resize_taps::area2(ssize, ssize2, dsize, dsize2) ? 1 : 0;
+    }
+    if (tile_hw) tile_hw[0] = RTILE_H, tile_hw[1] = RTILE_W;
   });
 }
 

@@ -1,6 +1,7 @@
 // ingest_host.h - the pure host parts of the frame ingest (ingest.hip): the conversion constants, the argument checks of a call, the
-// descriptors and tile list the kernel reads, and where host frames lie in the staging buffer.  No HIP here, so that
-// tools/ingest_host_check.cpp can run all of it under the sanitizers on a CPU.
+// descriptors and tile list the kernel reads, and where host frames lie in the staging buffer; for the resize stage also the tap
+// tables (resize_taps.h) and the check that no two outputs share a byte.  No HIP here, so that tools/ingest_host_check.cpp and
+// tools/resize_host_check.cpp can run all of it under the sanitizers on a CPU.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -10,6 +11,7 @@
 
 #include "../../include/rtdetr_mi355.h"
 #include "error.h"
+#include "resize_taps.h"
 
 namespace ingest_host {
 
@@ -160,6 +162,194 @@ inline void fill_tables(uint8_t* stage, const Plan& p, int n, const rtd_yuv_fram
   for (int i = 0; i < n; ++i) {
     descs[i] = describe(on_device ? frames[i] : packed_at(frames[i], dev_base + p.foff[(size_t)i]), out_dev[i]);
     const int32_t cnt = (int32_t)tiles_of(frames[i]);
+    for (int32_t t = 0; t < cnt; ++t) tiles[k++] = {i, t};
+  }
+}
+
+// ---- the resize stage: rtd_ingest_convert_resize and rtd_ingest_resize -------------------------------------------------------------------
+
+using resize_taps::LinEntry;
+
+// a thread makes RPX output pixels of one row; a workgroup of TX x TY threads one tile of RTILE_W x RTILE_H output pixels.  On the 2 x 2
+// area path that is the convert kernel's source strip (8 pixels of two rows) and tile (256 x 16)
+constexpr int RPX = 4;
+constexpr int RTILE_W = TX * RPX, RTILE_H = TY;                 // 128 x 8 output pixels
+constexpr int64_t MAX_RTILES = 1 << 24;                         // of all launches of a call together (the tile list is pinned memory)
+
+enum : int32_t { R_AREA = 1, R_SRC_WIDE = 2, R_DST_WIDE = 4 };  // ResizeDesc::rflags
+
+struct ResizeDesc {          // 112 bytes; what the resize kernel reads, the same for every thread of a workgroup
+  FrameDesc src;             // the source: 4:2:0 planes as the convert kernel reads them, or BGR (y: first byte, y_pitch: bytes per row); dst unused
+  uint8_t* out;
+  const LinEntry* tab;       // the linear path: OW column entries, then OH row entries (null on the area path)
+  int32_t OW, OH, tiles_x, rflags;
+};
+
+// the arguments of either call in one shape: exactly one of yuv / bgr is set
+struct ResizeCall {
+  int n;
+  const rtd_yuv_frame* yuv;
+  const rtd_bgr_frame* bgr;
+  bool on_device;
+  const int32_t* out_hw;
+  uint8_t* const* out;
+  uint8_t* const* native;    // may be null, and so may its entries
+  int sw(int i) const { return yuv ? yuv[i].width : bgr[i].width; }
+  int sh(int i) const { return yuv ? yuv[i].height : bgr[i].height; }
+  int oh(int i) const { return out_hw[2 * i]; }
+  int ow(int i) const { return out_hw[2 * i + 1]; }
+  uint8_t* native_of(int i) const { return native ? native[i] : nullptr; }
+  // the fused kernel reads frame i's planes; otherwise the BGR kernel reads the frame, or the native frame the convert kernel wrote
+  bool fused(int i) const { return yuv && !native_of(i); }
+  size_t host_bytes(int i) const { return yuv ? (size_t)frame_bytes(sh(i), sw(i)) : (size_t)sh(i) * (size_t)sw(i) * 3; }
+};
+
+inline int64_t rtiles_of(int oh, int ow) { return (int64_t)((ow + RTILE_W - 1) / RTILE_W) * ((oh + RTILE_H - 1) / RTILE_H); }
+
+inline void check_bgr(int i, const rtd_bgr_frame& f) {
+  const std::string fi = "frame " + std::to_string(i);
+  RTD_CHECK(f.width >= 1 && f.height >= 1 && f.width <= 65535 && f.height <= 65535, RTD_E_INVALID, fi + " has a bad size (1..65535 per side)");
+  RTD_CHECK((int64_t)f.pitch >= 3 * (int64_t)f.width, RTD_E_INVALID, fi + ": pitch is less than a row of BGR pixels");
+  RTD_CHECK(f.data, RTD_E_INVALID, fi + " has a null source");
+}
+
+// checks every argument of a resize call; nothing is copied or launched before the whole call has passed
+inline void validate_resize(const ResizeCall& c) {
+  RTD_CHECK(c.n >= 1 && c.n <= RTD_INGEST_MAX_FRAMES, RTD_E_INVALID, "1..RTD_INGEST_MAX_FRAMES frames per call");
+  RTD_CHECK((c.yuv || c.bgr) && c.out_hw && c.out, RTD_E_INVALID, "null argument");
+  int64_t tiles = 0;
+  struct Range { uintptr_t a, b; int frame; const char* what; };
+  std::vector<Range> ranges;
+  for (int i = 0; i < c.n; ++i) {
+    const std::string fi = "frame " + std::to_string(i);
+    if (c.yuv) {
+      const rtd_yuv_frame& f = c.yuv[i];
+      check_shape(i, f);
+      RTD_CHECK(f.y && f.u && (interleaved(f.layout) || f.v), RTD_E_INVALID, fi + " has a null plane");
+    } else {
+      check_bgr(i, c.bgr[i]);
+    }
+    RTD_CHECK(c.oh(i) >= 1 && c.ow(i) >= 1 && c.oh(i) <= 65535 && c.ow(i) <= 65535, RTD_E_INVALID, fi + " has a bad output size (1..65535 per side)");
+    RTD_CHECK(c.out[i], RTD_E_INVALID, fi + " has a null output");
+    tiles += rtiles_of(c.oh(i), c.ow(i));
+    ranges.push_back({(uintptr_t)c.out[i], (uintptr_t)c.out[i] + (uintptr_t)c.oh(i) * (uintptr_t)c.ow(i) * 3, i, "output"});
+    if (c.native_of(i)) {
+      tiles += tiles_of(c.yuv[i]);
+      ranges.push_back({(uintptr_t)c.native_of(i), (uintptr_t)c.native_of(i) + (uintptr_t)c.sh(i) * (uintptr_t)c.sw(i) * 3, i, "native output"});
+    }
+    RTD_CHECK(tiles <= MAX_RTILES, RTD_E_INVALID, fi + ": the call has more than 2^24 tiles");
+  }
+  for (size_t k = 1; k < ranges.size(); ++k)
+    for (size_t j = 0; j < k; ++j)
+      RTD_CHECK(ranges[k].b <= ranges[j].a || ranges[j].b <= ranges[k].a, RTD_E_INVALID,
+                "frame " + std::to_string(ranges[k].frame) + ": its " + ranges[k].what + " shares memory with the " + ranges[j].what + " of frame " +
+                    std::to_string(ranges[j].frame));
+}
+
+// the staging buffer of a resize call: [resize descriptors | convert descriptors (native outputs) | tiles: convert, fused, BGR |
+// tap tables | host frames, tightly packed, each on a 256-byte boundary]
+struct ResizePlan {
+  size_t fdesc_off = 0, tile_off = 0, table_off = 0, tables_end = 0, total = 0;
+  int64_t conv_tiles = 0, fused_tiles = 0, bgr_tiles = 0;       // the three launches' slices of the tile list, in this order
+  std::vector<uint8_t> area;                                    // per frame: the 2 x 2 mean
+  std::vector<size_t> toff;                                     // per frame: where its tables lie (linear frames)
+  std::vector<uint8_t> shared;                                  // per frame: its tables are those of an earlier frame of the same sizes
+  std::vector<size_t> foff;                                     // host frames: where frame i goes
+};
+
+inline ResizePlan plan_resize(const ResizeCall& c) {
+  ResizePlan p;
+  const size_t n = (size_t)c.n;
+  p.area.resize(n), p.toff.assign(n, 0), p.shared.assign(n, 0), p.foff.assign(n, 0);
+  bool any_native = false;
+  for (int i = 0; i < c.n; ++i) {
+    p.area[(size_t)i] = resize_taps::area2(c.sw(i), c.sh(i), c.ow(i), c.oh(i)) ? 1 : 0;
+    const int64_t t = rtiles_of(c.oh(i), c.ow(i));
+    if (c.fused(i)) p.fused_tiles += t;
+    else p.bgr_tiles += t;
+    if (c.native_of(i)) p.conv_tiles += tiles_of(c.yuv[i]), any_native = true;
+  }
+  p.fdesc_off = align_up(sizeof(ResizeDesc) * n, 256);
+  p.tile_off = align_up(p.fdesc_off + (any_native ? sizeof(FrameDesc) * n : 0), 256);
+  p.table_off = align_up(p.tile_off + sizeof(TileRef) * (size_t)(p.conv_tiles + p.fused_tiles + p.bgr_tiles), 256);
+  size_t at = p.table_off;
+  for (int i = 0; i < c.n; ++i) {
+    p.toff[(size_t)i] = at;
+    if (p.area[(size_t)i]) continue;
+    for (int j = 0; j < i && !p.shared[(size_t)i]; ++j)         // the cameras of a site mostly share one size: one pair of tables for them
+      if (!p.area[(size_t)j] && c.sw(j) == c.sw(i) && c.sh(j) == c.sh(i) && c.ow(j) == c.ow(i) && c.oh(j) == c.oh(i))
+        p.toff[(size_t)i] = p.toff[(size_t)j], p.shared[(size_t)i] = 1;
+    if (!p.shared[(size_t)i]) at = align_up(at + sizeof(LinEntry) * ((size_t)c.ow(i) + (size_t)c.oh(i)), 16);
+  }
+  p.tables_end = at = align_up(at, 256);
+  for (int i = 0; i < c.n; ++i) {
+    p.foff[(size_t)i] = at;
+    if (!c.on_device) at = align_up(at + c.host_bytes(i), 256);
+  }
+  p.total = at;
+  return p;
+}
+
+// a host BGR frame, row by row, into 3 H W bytes at dst
+inline void pack_bgr(uint8_t* dst, const rtd_bgr_frame& f) {
+  const size_t row = 3 * (size_t)f.width;
+  for (size_t r = 0; r < (size_t)f.height; ++r) memcpy(dst + r * row, f.data + r * (size_t)f.pitch, row);
+}
+
+// the host frames of a call into stage + foff[i]
+inline void pack_sources(uint8_t* stage, const ResizePlan& p, const ResizeCall& c) {
+  for (int i = 0; i < c.n; ++i) {
+    if (c.yuv) pack_frame(stage + p.foff[(size_t)i], c.yuv[i]);
+    else pack_bgr(stage + p.foff[(size_t)i], c.bgr[i]);
+  }
+}
+
+// writes the tables of a resize call into `stage` (p.tables_end bytes); the staging buffer's twin on the device starts at dev_base
+inline void fill_resize(uint8_t* stage, const ResizePlan& p, const ResizeCall& c, const uint8_t* dev_base) {
+  ResizeDesc* descs = (ResizeDesc*)stage;
+  FrameDesc* conv = (FrameDesc*)(stage + p.fdesc_off);
+  TileRef* tiles = (TileRef*)(stage + p.tile_off);
+  int64_t kc = 0, kf = p.conv_tiles, kb = p.conv_tiles + p.fused_tiles;
+  for (int i = 0; i < c.n; ++i) {
+    const size_t si = (size_t)i;
+    ResizeDesc d;
+    memset(&d, 0, sizeof d);
+    uintptr_t bits = 0;                                         // every address and pitch the source rows start from
+    if (c.yuv) {
+      const rtd_yuv_frame f = c.on_device ? c.yuv[i] : packed_at(c.yuv[i], dev_base + p.foff[si]);
+      if (c.native_of(i)) {
+        conv[i] = describe(f, c.native_of(i));
+        const int32_t cnt = (int32_t)tiles_of(f);
+        for (int32_t t = 0; t < cnt; ++t) tiles[kc++] = {i, t};
+      } else if (p.conv_tiles) {
+        memset(&conv[i], 0, sizeof(FrameDesc));
+      }
+      d.src = describe(f, nullptr);
+      bits = (uintptr_t)d.src.y | (uintptr_t)d.src.u | (uintptr_t)d.src.v | (uintptr_t)f.y_pitch | (uintptr_t)f.c_pitch;
+    }
+    if (!c.fused(i)) {                                          // a BGR source: the caller's frame, its packed copy, or the native output
+      const uint8_t* data = c.yuv ? c.native_of(i) : c.on_device ? c.bgr[i].data : dev_base + p.foff[si];
+      const int32_t pitch = c.yuv || !c.on_device ? 3 * c.sw(i) : c.bgr[i].pitch;
+      memset(&d.src, 0, sizeof d.src);
+      d.src.y = data, d.src.y_pitch = pitch, d.src.W = c.sw(i), d.src.H = c.sh(i);
+      bits = (uintptr_t)data | (uintptr_t)pitch;
+    }
+    d.out = c.out[i];
+    d.OW = c.ow(i), d.OH = c.oh(i);
+    d.tiles_x = (d.OW + RTILE_W - 1) / RTILE_W;
+    const bool dst_wide = (((uintptr_t)d.out | (uintptr_t)(3 * (int64_t)d.OW)) & 3) == 0;
+    d.rflags = (p.area[si] ? R_AREA : 0) | ((bits & 3) == 0 ? R_SRC_WIDE : 0) | (dst_wide ? R_DST_WIDE : 0);
+    if (!p.area[si]) {
+      LinEntry* tab = (LinEntry*)(stage + p.toff[si]);
+      if (!p.shared[si]) {
+        resize_taps::linear_table(c.sw(i), d.OW, true, tab);
+        resize_taps::linear_table(c.sh(i), d.OH, false, tab + d.OW);
+      }
+      d.tab = (const LinEntry*)(dev_base + p.toff[si]);
+    }
+    descs[i] = d;
+    const int32_t cnt = (int32_t)rtiles_of(d.OH, d.OW);
+    int64_t& k = c.fused(i) ? kf : kb;
     for (int32_t t = 0; t < cnt; ++t) tiles[k++] = {i, t};
   }
 }

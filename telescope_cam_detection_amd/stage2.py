@@ -53,6 +53,14 @@ def crop_rect(bbox: Dict[str, float], frame_hw: Tuple[int, int], min_crop_size: 
     return xa, ya, xb, yb
 
 
+def scaled_bbox(bbox: Dict[str, float], frame_hw: Tuple[int, int], source_hw: Tuple[int, int]) -> Dict[str, float]:
+    """A box in the detector frame's pixels -> the same box in the native frame's: each corner times source_w / frame_w and
+    source_h / frame_h (Python floats).  `crop_rect` then runs on it with frame_hw = source_hw, so min_crop_size is compared in
+    native pixels."""
+    fx, fy = source_hw[1] / frame_hw[1], source_hw[0] / frame_hw[0]
+    return {"x1": bbox["x1"] * fx, "y1": bbox["y1"] * fy, "x2": bbox["x2"] * fx, "y2": bbox["y2"] * fy}
+
+
 class CropBatcher:
     """Builds the classifier input batch on the GPU.  Frames must be HWC uint8 BGR torch tensors on the device."""
 
@@ -65,10 +73,15 @@ class CropBatcher:
         self.min_crop_size = min_crop_size
         self.crop_padding_percent = crop_padding_percent
 
-    def rects_for(self, detections: List[Dict], frame_hw) -> Tuple[List[int], List[Tuple[int, int, int, int]]]:
+    def rects_for(self, detections: List[Dict], frame_hw, source_hw=None) -> Tuple[List[int], List[Tuple[int, int, int, int]]]:
+        """the detections Stage 2 keeps and their crop rectangles; with source_hw the rectangles are in the native frame's pixels
+        (`scaled_bbox`), for crops taken from the frame the camera delivered instead of the detector's resized one"""
         kept, rects = [], []
         for i, det in enumerate(detections):
-            r = crop_rect(det["bbox"], frame_hw, self.min_crop_size, self.crop_padding_percent)
+            if source_hw is None:
+                r = crop_rect(det["bbox"], frame_hw, self.min_crop_size, self.crop_padding_percent)
+            else:
+                r = crop_rect(scaled_bbox(det["bbox"], frame_hw, source_hw), source_hw, self.min_crop_size, self.crop_padding_percent)
             if r is not None:
                 kept.append(i)
                 rects.append(r)
@@ -209,9 +222,11 @@ class BatchedStage2:
         else:
             self._set(det, top["species"], top["confidence"], category, level)
 
-    def process_batch(self, frames, detections_per_frame):
+    def process_batch(self, frames, detections_per_frame, native_frames=None):
         """frames: device-resident HWC uint8 BGR tensors; detections_per_frame: Stage-1 dict lists (mutated in place and returned,
-        order kept).  One crop launch for every eligible detection of every frame, one forward per category."""
+        order kept).  One crop launch for every eligible detection of every frame, one forward per category.
+        native_frames: per frame the same picture at the camera's own size (capture's `native_frame`), or None for a camera without
+        one: rectangles, crops and the enhancer's input then come from it, the detection dicts keep their detector-frame boxes."""
         import torch
 
         p = self.pipeline
@@ -223,9 +238,16 @@ class BatchedStage2:
             return detections_per_frame
         if getattr(p, "enhancer", None) is not None and self.enhancer is None:
             return [p.process_detections(f, dets) for f, dets in zip(frames, detections_per_frame)]
+        if native_frames is not None:
+            if len(native_frames) != len(frames):
+                raise ValueError(f"{len(frames)} frames but {len(native_frames)} native frames")
+            sources = [f if nf is None else nf for f, nf in zip(frames, native_frames)]
+        else:
+            sources = frames
         jobs = []                                                  # (frame index, detection, category, rect)
         for fi, (f, dets) in enumerate(zip(frames, detections_per_frame)):
             hw = (int(f.shape[0]), int(f.shape[1]))
+            src_hw = (int(sources[fi].shape[0]), int(sources[fi].shape[1]))
             for d in dets:
                 bbox = normalised_bbox(d.get("bbox", {}))
                 d["bbox"] = bbox
@@ -234,7 +256,10 @@ class BatchedStage2:
                     d["species"] = None
                     d["species_confidence"] = 0.0
                     continue
-                rect = crop_rect(bbox, hw, p.min_crop_size, p.crop_padding_percent)
+                if sources[fi] is f:
+                    rect = crop_rect(bbox, hw, p.min_crop_size, p.crop_padding_percent)
+                else:
+                    rect = crop_rect(scaled_bbox(bbox, hw, src_hw), src_hw, p.min_crop_size, p.crop_padding_percent)
                 if rect is None:                                   # too small / empty crop (:256-259, :281-285)
                     self._set(d, None, 0.0, category, None)
                     continue
@@ -247,9 +272,9 @@ class BatchedStage2:
             rects_per_frame[fi].append(rect)
             order[fi].append(j)
         if self.enhancer is not None:
-            batch = self.batcher.preprocess_batch(frames, rects_per_frame, enhancer=self.enhancer)
+            batch = self.batcher.preprocess_batch(sources, rects_per_frame, enhancer=self.enhancer)
         else:
-            batch = self.batcher.preprocess_batch(frames, rects_per_frame)      # [N,3,S,S], crops in frame-major order
+            batch = self.batcher.preprocess_batch(sources, rects_per_frame)      # [N,3,S,S], crops in frame-major order
         row_of = {j: r for r, j in enumerate(j for per in order for j in per)}
         by_cat: Dict[str, List[int]] = {}
         for j, (_, _, category, _) in enumerate(jobs):
@@ -288,10 +313,14 @@ class BatchedStage2:
                     etimes.append(ms / len(jobs))
         return detections_per_frame
 
-    def process_detections(self, frame, detections):
-        """Drop-in for `TwoStageDetectionPipeline.process_detections(frame, detections)` (one frame)."""
+    def process_detections(self, frame, detections, native_frame=None):
+        """Drop-in for `TwoStageDetectionPipeline.process_detections(frame, detections)` (one frame); native_frame as process_batch's."""
         import torch
 
         if isinstance(frame, np.ndarray):
             frame = torch.from_numpy(np.ascontiguousarray(frame)).cuda()
-        return self.process_batch([frame.contiguous()], [detections])[0]
+        if native_frame is None:
+            return self.process_batch([frame.contiguous()], [detections])[0]
+        if isinstance(native_frame, np.ndarray):
+            native_frame = torch.from_numpy(np.ascontiguousarray(native_frame)).cuda()
+        return self.process_batch([frame.contiguous()], [detections], native_frames=[native_frame.contiguous()])[0]

@@ -10,6 +10,16 @@
         the run to profile (a run of its own: tracing slows the host); device frames, so nothing but the kernel and the table upload
     python tools/ingest_bench.py kernels --stats DIR/ing_kernel_stats.csv [--out profiles/ingest_bench.json]
         kernel time from that file against the bytes of the shapes: 1.5 read + 3 written per pixel
+
+The resize stage (rtd_ingest_convert_resize), 8 NV12 frames to 1280 x 720, `--case area` (2560 x 1440, the 2 x 2 mean) or `--case linear`
+(1920 x 1080, the tables); written to profiles/ingest_resize_bench.json:
+
+    python tools/ingest_bench.py resize-calls [--calls 100]
+        per case the fused call from device and from host frames, the call that also writes the native frames (convert kernel, then
+        the BGR resize kernel), and alternating with them the yardstick: rtd_ingest_convert of the same native frames
+    rocprofv3 --kernel-trace --stats -d DIR -o rs --output-format csv -- python tools/ingest_bench.py resize-run --case area --calls 20
+        the run to profile, one case per run: yardstick, fused and native calls on device frames
+    python tools/ingest_bench.py resize-kernels --case area --stats DIR/rs_kernel_stats.csv
 """
 import argparse
 import csv
@@ -163,14 +173,117 @@ def cmd_kernels(a):
     merge(a.out, {"kernels": rows})
 
 
+# ---- the resize stage ---------------------------------------------------------------------------------------------------------------------
+RESIZE_CASES = {"area": (1440, 2560), "linear": (1080, 1920)}
+OUT_HW = (720, 1280)
+RESIZE_OUT = os.path.join("profiles", "ingest_resize_bench.json")
+
+
+def resize_setup(case, check=True):
+    import torch
+
+    from telescope_cam_detection_amd import ingest
+    from tests import resize_ref, yuv_ref
+    h, w = RESIZE_CASES[case]
+    frames = [yuv_ref.pack(*yuv_ref.planes(60 + i, h, w), "nv12")[0] for i in range(N)]
+    be = ingest.FrameIngest(0)
+    dev = [torch.from_numpy(f).cuda() for f in frames]
+    outs = [torch.empty((*OUT_HW, 3), dtype=torch.uint8, device="cuda") for _ in range(N)]
+    native = [torch.empty((h, w, 3), dtype=torch.uint8, device="cuda") for _ in range(N)]
+    hdesc = [ingest.tight_frame(f.ctypes.data, h, w, 0) for f in frames]
+    ddesc = [ingest.tight_frame(d.data_ptr(), h, w, 0) for d in dev]
+    hw = list(OUT_HW) * N
+    optrs, nptrs = [o.data_ptr() for o in outs], [o.data_ptr() for o in native]
+
+    def ok(rc):
+        assert rc == 0, (rc, be._fn("last_error")(be._h))
+
+    calls = {"fused_from_device": lambda: ok(be.resize_raw(ddesc, True, hw, optrs)),
+             "fused_from_host": lambda: ok(be.resize_raw(hdesc, False, hw, optrs)),
+             "with_native_from_device": lambda: ok(be.resize_raw(ddesc, True, hw, optrs, nptrs)),
+             "yardstick_convert_from_device": lambda: ok(be.convert_raw(ddesc, True, nptrs)),
+             "yardstick_convert_from_host": lambda: ok(be.convert_raw(hdesc, False, nptrs))}
+    if check:                                 # one frame of each call against the restatement (the tests hold the rest)
+        want = resize_ref.to_bgr_resized(frames[N - 1], h, w, *OUT_HW)
+        for name in ("fused_from_device", "fused_from_host", "with_native_from_device"):
+            outs[N - 1].zero_()
+            calls[name]()
+            assert (outs[N - 1].cpu().numpy() == want).all(), f"{name} does not compute the restatement"
+        assert (native[N - 1].cpu().numpy() == yuv_ref.to_bgr(frames[N - 1], h, w)).all()
+    torch.cuda.synchronize()
+    return be, calls, (h, w)
+
+
+def cmd_resize_calls(a):
+    import torch
+
+    from telescope_cam_detection_amd import ingest
+    if not torch.cuda.is_available():
+        raise SystemExit("no GPU: nothing is measured")
+    res = {"frames": N, "out_hw": list(OUT_HW), "layout": "nv12", "tile_out_hw": list(ingest.resize_tile_hw()),
+           "method": "host clock around the synchronous call; medians of five rounds after warm-up, the calls of a case alternating in one process"}
+    for case in ([a.case] if a.case else list(RESIZE_CASES)):
+        be, calls, (h, w) = resize_setup(case)
+        for _ in range(3):
+            for fn in calls.values():
+                fn()
+        rounds, per = 5, max(a.calls // 5, 1)
+        t = {k: [] for k in calls}
+        for _ in range(rounds):               # the sides alternate so that all see the same machine load
+            for k, fn in calls.items():
+                t[k].append(timed(fn, per if "host" not in k else max(per // 4, 1)))
+        res[case] = {"source_hw": [h, w], "area2": ingest.resize_is_area2(w, h, OUT_HW[1], OUT_HW[0]), "nv12_bytes": N * h * w * 3 // 2,
+                     "out_bytes": N * OUT_HW[0] * OUT_HW[1] * 3, "native_bytes": N * h * w * 3}
+        for k, v in t.items():
+            res[case][k + "_ms"] = med(v)
+            res[case][k + "_ms_rounds"] = [round(x, 3) for x in v]
+        be.close()
+    print(json.dumps(res), flush=True)
+    merge(a.out if a.out != os.path.join("profiles", "ingest_bench.json") else RESIZE_OUT, {"calls": res})
+
+
+def cmd_resize_run(a):
+    be, calls, _ = resize_setup(a.case or "area", check=False)
+    try:
+        for name in ("yardstick_convert_from_device", "fused_from_device", "with_native_from_device"):
+            for _ in range(a.calls):
+                calls[name]()
+        print(json.dumps({"case": a.case or "area", "calls": a.calls}))
+    finally:
+        be.close()
+
+
+def cmd_resize_kernels(a):
+    import re
+    case = a.case or "area"
+    h, w = RESIZE_CASES[case]
+    src, out, nat = N * h * w * 3 // 2, N * OUT_HW[0] * OUT_HW[1] * 3, N * h * w * 3
+    moved = {"ingest_kernel": src + nat, "resize_kernel_yuv": src + out, "resize_kernel_bgr": nat + out}
+    rows = {}
+    with open(a.stats) as f:
+        for r in csv.DictReader(f):
+            name = r.get("Name", "")
+            m = re.search(r"resize_kernel(?:ILi|<\D*)(\d)", name)
+            key = "ingest_kernel" if "ingest_kernel" in name else (("resize_kernel_yuv", "resize_kernel_bgr")[int(m.group(1))] if m else None)
+            if key:
+                avg_us = float(r["AverageNs"]) / 1e3
+                rows[key] = {"calls": int(r["Calls"]), "avg_us": round(avg_us, 2), "min_us": round(float(r["MinNs"]) / 1e3, 2),
+                             "max_us": round(float(r["MaxNs"]) / 1e3, 2), "stddev_us": round(float(r.get("StdDev", 0) or 0) / 1e3, 2),
+                             "bytes_read_plus_written": moved[key], "gbytes_per_s": round(moved[key] / avg_us / 1e3, 1)}
+    print(json.dumps(rows, indent=1))
+    merge(a.out if a.out != os.path.join("profiles", "ingest_bench.json") else RESIZE_OUT, {"kernels_" + case: rows})
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("cmd", choices=["calls", "run", "kernels"])
+    ap.add_argument("cmd", choices=["calls", "run", "kernels", "resize-calls", "resize-run", "resize-kernels"])
+    ap.add_argument("--case", choices=sorted(RESIZE_CASES))
     ap.add_argument("--calls", type=int, default=100)
     ap.add_argument("--stats")
     ap.add_argument("--out", default=os.path.join("profiles", "ingest_bench.json"))
     a = ap.parse_args()
-    {"calls": cmd_calls, "run": cmd_run, "kernels": cmd_kernels}[a.cmd](a)
+    {"calls": cmd_calls, "run": cmd_run, "kernels": cmd_kernels, "resize-calls": cmd_resize_calls, "resize-run": cmd_resize_run,
+     "resize-kernels": cmd_resize_kernels}[a.cmd](a)
 
 
 if __name__ == "__main__":
