@@ -10,12 +10,13 @@
 #include <vector>
 
 #include "../../include/rtdetr_mi355.h"
+#include "call_parts.h"
 #include "common.h"
 
 namespace rtd {
 namespace backend {
 
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
+// (align_up, TileRef and sides_ok are call_parts.h's: the HIP-free headers share them)
 
 // runs f; an exception becomes its return code, its message goes into `err`
 template <typename F>
@@ -200,7 +201,7 @@ inline void check_crop_frame(int i, const uint8_t* const* frames, const int32_t*
   const std::string ci = "crop " + std::to_string(i);
   const int64_t fh = frame_hw[2 * i], fw = frame_hw[2 * i + 1];
   RTD_CHECK(frames[i], RTD_E_INVALID, ci + " has a null frame");
-  RTD_CHECK(fh >= 1 && fw >= 1 && fh <= 65535 && fw <= 65535, RTD_E_INVALID, ci + ": bad frame size (1..65535 per side)");
+  RTD_CHECK(sides_ok(fh, fw), RTD_E_INVALID, ci + ": bad frame size (1..65535 per side)");
   RTD_CHECK(rects[4 * i + 2] <= fw && rects[4 * i + 3] <= fh, RTD_E_INVALID, ci + " leaves its frame");
 }
 

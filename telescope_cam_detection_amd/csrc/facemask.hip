@@ -18,6 +18,7 @@
 #include "backend.h"
 #include "facemask_host.h"
 #include "gauss8.h"
+#include "global_bytes.h"
 
 namespace facemask {
 
@@ -26,17 +27,7 @@ namespace bk = rtd::backend;
 using bk::guarded;
 using namespace facemask_host;
 
-// the descriptor's pointers are global memory: said so, the loads and stores are global_* instead of flat_* instructions
-#define RTD_GLOBAL __attribute__((address_space(1)))
-typedef const RTD_GLOBAL uint8_t* GBytes;
-typedef const RTD_GLOBAL uint16_t* GHalf;
-typedef const RTD_GLOBAL uint32_t* GWord;
-typedef const RTD_GLOBAL int32_t* GInt;
-typedef const RTD_GLOBAL LinEntry* GLin;
-typedef RTD_GLOBAL uint8_t* GOut;
-typedef RTD_GLOBAL uint16_t* GOutHalf;
-typedef RTD_GLOBAL uint32_t* GOutWord;
-
+// (the descriptors' pointers are read through global_bytes.h's address_space(1) types: global_* instead of flat_* instructions)
 constexpr int ROW_LDS = (TILE_W + 2 * MAX_R) * 3;       // bytes of one staged row of the row pass
 constexpr int COL_LDS = TILE_W * 3;                     // values of one staged row of the column pass
 
@@ -58,7 +49,7 @@ __global__ void __launch_bounds__(THREADS) facemask_blur_rows(const FaceDesc* __
   __shared__ uint8_t src[TILE_H * ROW_LDS];
   __shared__ uint16_t taps[MAX_K + 1];
   const TileRef tr = tiles[blockIdx.x];
-  const FaceDesc d = descs[tr.face];
+  const FaceDesc d = descs[tr.owner];
   const Tile t = tile_of(d, tr.tile);
   const int tid = threadIdx.x, r = d.radius, k = 2 * r + 1;
   if (tid < k) taps[tid] = ((GHalf)(tables + d.table_off))[tid];
@@ -88,7 +79,7 @@ __global__ void __launch_bounds__(THREADS) facemask_blur_cols(const FaceDesc* __
   __shared__ uint16_t rows[(TILE_H + 2 * MAX_R) * COL_LDS];
   __shared__ uint16_t taps[MAX_K + 1];
   const TileRef tr = tiles[blockIdx.x];
-  const FaceDesc d = descs[tr.face];
+  const FaceDesc d = descs[tr.owner];
   const Tile t = tile_of(d, tr.tile);
   const int tid = threadIdx.x, r = d.radius, k = 2 * r + 1;
   if (tid < k) taps[tid] = ((GHalf)(tables + d.table_off))[tid];
@@ -109,11 +100,12 @@ __global__ void __launch_bounds__(THREADS) facemask_blur_cols(const FaceDesc* __
   }
 }
 
-// resize(region, (sw, sh), INTER_LINEAR) on 8-bit input, the tables from the host: a thread makes four bytes of `small`
+// resize(region, (sw, sh), INTER_LINEAR) on 8-bit input, the tables from the host and the pixel rule resize_taps.h's (area8, linear8):
+// a thread makes four bytes of `small`
 __global__ void __launch_bounds__(THREADS) facemask_pix_small(const FaceDesc* __restrict__ descs, const TileRef* __restrict__ tiles,
                                                               const uint8_t* __restrict__ tables, uint8_t* __restrict__ scratch) {
   const TileRef tr = tiles[blockIdx.x];
-  const FaceDesc d = descs[tr.face];
+  const FaceDesc d = descs[tr.owner];
   const GBytes frame = (GBytes)d.frame;
   const GLin xs = (GLin)(tables + d.table_off), ys = xs + d.sw;
   const GOut small = (GOut)(scratch + d.scratch_off);
@@ -125,18 +117,13 @@ __global__ void __launch_bounds__(THREADS) facemask_pix_small(const FaceDesc* __
     const int c = (int)(idx % 3), px = (int)(idx / 3), dx = px % d.sw, dy = px / d.sw;
     int v;
     if (d.flags & F_AREA2) {
-      // ResizeAreaFastVec / ResizeAreaFast_Invoker at scale 2: (a + b + c + d + 2) >> 2
       const GBytes p = frame + frame_at(d, 2 * dy, 2 * dx) + c;
-      v = ((int)p[0] + p[3] + p[pitch] + p[pitch + 3] + 2) >> 2;
+      v = resize_taps::area8(p[0], p[3], p[pitch], p[pitch + 3]);
     } else {
       const int xi0 = xs[dx].i0, xi1 = xs[dx].i1, a0 = xs[dx].w0, a1 = xs[dx].w1;
       const int b0 = ys[dy].w0, b1 = ys[dy].w1;
       const GBytes r0 = frame + frame_at(d, ys[dy].i0, 0) + c, r1 = frame + frame_at(d, ys[dy].i1, 0) + c;
-      // HResizeLinear<uchar, int, short, 2048>: int32 sums of two 11-bit weights
-      const int S0 = (int)r0[3 * xi0] * a0 + (int)r0[3 * xi1] * a1;
-      const int S1 = (int)r1[3 * xi0] * a0 + (int)r1[3 * xi1] * a1;
-      // VResizeLinear<uchar, int, short, FixedPtCast<int, uchar, 22>>
-      v = (((b0 * (S0 >> 4)) >> 16) + ((b1 * (S1 >> 4)) >> 16) + 2) >> 2;
+      v = resize_taps::linear8(r0[3 * xi0], r0[3 * xi1], r1[3 * xi0], r1[3 * xi1], a0, a1, b0, b1);
     }
     small[idx] = (uint8_t)v;
   }
@@ -146,7 +133,7 @@ __global__ void __launch_bounds__(THREADS) facemask_pix_small(const FaceDesc* __
 __global__ void __launch_bounds__(THREADS) facemask_pix_nearest(const FaceDesc* __restrict__ descs, const TileRef* __restrict__ tiles,
                                                                 const uint8_t* __restrict__ tables, const uint8_t* __restrict__ scratch) {
   const TileRef tr = tiles[blockIdx.x];
-  const FaceDesc d = descs[tr.face];
+  const FaceDesc d = descs[tr.owner];
   const Tile t = tile_of(d, tr.tile);
   const GInt xmap = (GInt)(tables + d.table_off + sizeof(LinEntry) * ((size_t)d.sw + d.sh)), ymap = xmap + d.rw;
   const GBytes small = (GBytes)(scratch + d.scratch_off);
@@ -161,7 +148,7 @@ __global__ void __launch_bounds__(THREADS) facemask_pix_nearest(const FaceDesc* 
 // cv2.rectangle(frame, (x1, y1), (x2, y2), (0, 0, 0), -1): the host has made the inclusive box a region
 __global__ void __launch_bounds__(THREADS) facemask_box(const FaceDesc* __restrict__ descs, const TileRef* __restrict__ tiles) {
   const TileRef tr = tiles[blockIdx.x];
-  const FaceDesc d = descs[tr.face];
+  const FaceDesc d = descs[tr.owner];
   const Tile t = tile_of(d, tr.tile);
   const GOut frame = (GOut)d.frame;
   const int ew = t.tw * 3;
@@ -195,7 +182,7 @@ __global__ void __launch_bounds__(THREADS) facemask_gray(const uint8_t* __restri
     for (int p = 0; p < 4; ++p) {
       uint32_t ch[3];
 #pragma unroll
-      for (int c = 0; c < 3; ++c) ch[c] = (w[(3 * p + c) >> 2] >> (8 * ((3 * p + c) & 3))) & 0xffu;
+      for (int c = 0; c < 3; ++c) ch[c] = byte_of(w, 3 * p + c);
       out |= gray_of(ch[0], ch[1], ch[2]) << (8 * p);
     }
     *(GOutWord)(gray + p0) = out;                               // (the plane starts on a dword and p0 is a multiple of 4)
@@ -296,7 +283,7 @@ int rtd_facemask_apply(rtd_facemask_handle m, int32_t n, uint8_t* const* frames,
 int rtd_facemask_gray(rtd_facemask_handle m, const uint8_t* frame_dev, int32_t rows, int32_t cols, uint8_t* gray_out) {
   return guarded(m, [&] {
     RTD_CHECK(frame_dev && gray_out, RTD_E_INVALID, "null argument");
-    RTD_CHECK(rows >= 1 && cols >= 1 && rows <= 65535 && cols <= 65535, RTD_E_INVALID, "the frame has a bad size (1..65535 per side)");
+    RTD_CHECK(sides_ok(rows, cols), RTD_E_INVALID, "the frame has a bad size (1..65535 per side)");
     HIP_CHECK(hipSetDevice(m->device));
     try {
       gray_plane(m, frame_dev, rows, cols, gray_out);

@@ -13,11 +13,16 @@
 #include <vector>
 
 #include "../../include/rtdetr_mi355.h"
+#include "call_parts.h"
 #include "error.h"
 #include "gauss_taps.h"
 #include "resize_taps.h"
 
 namespace facemask_host {
+
+using rtd::backend::TileRef;         // owner: the face, an index into the descriptors; tile: K_PIX_SMALL's is the SMALL_TILE chunk
+using rtd::backend::align_up;
+using rtd::backend::sides_ok;
 
 // a workgroup of THREADS threads takes one TILE_W x TILE_H pixel tile of a face's region (blur, nearest, box), or SMALL_TILE bytes of
 // a pixelate face's `small` image
@@ -42,17 +47,11 @@ struct FaceDesc {            // 80 bytes; what the kernels read, the same for ev
   int32_t frame_index, reserved0;
 };
 
-struct TileRef {
-  int32_t face, tile;        // face: index into the descriptors; tile = ty * tiles_x + tx (K_PIX_SMALL: the SMALL_TILE chunk)
-};
-
 struct Rect {                // x2, y2 exclusive
   int64_t x1, y1, x2, y2;
   bool empty() const { return x2 <= x1 || y2 <= y1; }
   bool meets(const Rect& o) const { return x1 < o.x2 && o.x1 < x2 && y1 < o.y2 && o.y1 < y2; }
 };
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // the reference's padded rectangle: p = int(w * 0.2) in Python's arithmetic (a double product, truncated towards zero)
 inline Rect padded(const rtd_face_rect& f, int64_t W, int64_t H) {
@@ -75,7 +74,7 @@ inline void validate(int64_t n, const int32_t* hw, int64_t n_faces, const rtd_fa
   RTD_CHECK(hw && (faces || n_faces == 0), RTD_E_INVALID, "null argument");
   for (int64_t i = 0; i < n; ++i) {
     const int64_t H = hw[2 * i], W = hw[2 * i + 1];
-    RTD_CHECK(H >= 1 && W >= 1 && H <= 65535 && W <= 65535, RTD_E_INVALID, "frame " + std::to_string(i) + " has a bad size (1..65535 per side)");
+    RTD_CHECK(sides_ok(H, W), RTD_E_INVALID, "frame " + std::to_string(i) + " has a bad size (1..65535 per side)");
     RTD_CHECK(H * W * 3 < (1ll << 31), RTD_E_INVALID, "frame " + std::to_string(i) + " has 2 GiB or more");
   }
   for (int64_t k = 0; k < n_faces; ++k) {

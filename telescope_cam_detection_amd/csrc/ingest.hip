@@ -1,6 +1,6 @@
 // ingest.hip - 4:2:0 camera frames (NV12, NV21, I420) to tight HWC BGR device frames: OpenCV's COLOR_YUV2BGR_* fixed-point path, all in
 // integers.  The restatement the bytes must equal is tests/yuv_ref.py; the host side (constants, checks, staging layout) is
-// ingest_host.h.
+// ingest_host.h, and all three calls go through one path on it (run() below): a convert call is a resize call without resized outputs.
 //
 // One launch covers the whole call.  The host lists the 256 x 16 pixel tiles of every frame; one workgroup per listed tile, and its
 // frame's descriptor (planes, pitches, layout, constants) is the same for all its threads.  A thread owns 8 pixels of two rows: four
@@ -11,6 +11,7 @@
 #include "../../include/rtdetr_mi355.h"
 #include "../../include/rtdetr_mi355_test.h"
 #include "backend.h"
+#include "global_bytes.h"
 #include "ingest_host.h"
 
 namespace ingest {
@@ -23,17 +24,21 @@ using namespace ingest_host;
 struct Words2 { uint32_t w[2]; };
 struct Words6 { uint32_t w[6]; };
 
-// the descriptor's pointers are global memory: said so, the loads and stores are global_* instead of flat_* instructions
-#define RTD_GLOBAL __attribute__((address_space(1)))
-typedef const RTD_GLOBAL uint8_t* GBytes;
-typedef const RTD_GLOBAL uint32_t* GWord;
-typedef RTD_GLOBAL uint8_t* GOut;
-typedef RTD_GLOBAL uint32_t* GOutWord;
-
+// (the descriptors' pointers are read through global_bytes.h's address_space(1) types: global_* instead of flat_* instructions)
 // dword-aligned rows are all a wide frame guarantees: adjacent dword accesses, which the compiler merges into dwordx2 / dwordx4 ones
 __device__ inline Words2 load2(GBytes p) {
   const GWord q = (GWord)p;
   return {{q[0], q[1]}};
+}
+// four pixels (b | g << 8 | r << 16 each) as the three dwords of their 12 bytes
+__device__ inline void pack4(const uint32_t px[4], uint32_t w[3]) {
+  w[0] = px[0] | px[1] << 24;
+  w[1] = px[1] >> 8 | px[2] << 16;
+  w[2] = px[2] >> 16 | px[3] << 8;
+}
+__device__ inline void store3(GOut p, const uint32_t w[3]) {
+  const GOutWord q = (GOutWord)p;
+  q[0] = w[0], q[1] = w[1], q[2] = w[2];
 }
 __device__ inline void store6(GOut p, const Words6& v) {
   const GOutWord q = (GOutWord)p;
@@ -62,43 +67,65 @@ __device__ inline uint32_t pixel(const FrameDesc& d, uint32_t Y, const Chroma& c
   return clip8_shr20(yc + c.b) | clip8_shr20(yc + c.g) << 8 | clip8_shr20(yc + c.r) << 16;
 }
 
-__device__ inline uint32_t byte_of(const uint32_t* w, int i) { return (w[i >> 2] >> (8 * (i & 3))) & 0xffu; }
+// the chroma sample (cx, cy), byte by byte, as what it adds to its pixels
+__device__ inline Chroma chroma_at(const FrameDesc& d, int cx, int cy) {
+  const GBytes pu = (GBytes)d.u, pv = (GBytes)d.v;
+  const size_t crow = (size_t)cy * d.c_pitch;
+  uint32_t U, V;
+  if (d.flags & F_INTERLEAVED) {
+    const uint32_t a = pu[crow + 2 * cx], b = pu[crow + 2 * cx + 1];
+    U = (d.flags & F_SWAP) ? b : a;
+    V = (d.flags & F_SWAP) ? a : b;
+  } else {
+    U = pu[crow + cx];
+    V = pv[crow + cx];
+  }
+  return chroma_terms(d, U, V);
+}
 
-// a whole strip of a wide frame: x0 is a multiple of 8 and x0 + 8 <= W
-__device__ inline void strip_wide(const FrameDesc& d, int x0, int y0) {
-  const bool two = y0 + 1 < d.H;
-  const GBytes yrow = (GBytes)d.y + (size_t)y0 * d.y_pitch + x0, pu = (GBytes)d.u, pv = (GBytes)d.v;
-  const Words2 l0 = load2(yrow);
-  Words2 l1 = l0;
-  if (two) l1 = load2(yrow + d.y_pitch);
+// THE strip of a wide frame, as dwords: the 8 source pixels from x0 (a multiple of 8, x0 + 8 <= W) of the rows y0 (even) and y0 + 1, and
+// their four chroma samples.  two: the row y0 + 1 exists (it is not loaded otherwise, and l1 is l0)
+struct Strip {
+  Words2 l0, l1;
   uint32_t cu[PX / 2], cv[PX / 2];
+};
+__device__ inline Strip load_strip(const FrameDesc& d, int x0, int y0, bool two) {
+  Strip s;
+  const GBytes yrow = (GBytes)d.y + (size_t)y0 * d.y_pitch + x0, pu = (GBytes)d.u, pv = (GBytes)d.v;
+  s.l0 = load2(yrow);
+  s.l1 = s.l0;
+  if (two) s.l1 = load2(yrow + d.y_pitch);
   const size_t crow = (size_t)(y0 >> 1) * d.c_pitch;
   if (d.flags & F_INTERLEAVED) {
     const Words2 c = load2(pu + crow + x0);
 #pragma unroll
     for (int k = 0; k < PX / 2; ++k) {
       const uint32_t a = byte_of(c.w, 2 * k), b = byte_of(c.w, 2 * k + 1);
-      cu[k] = (d.flags & F_SWAP) ? b : a;
-      cv[k] = (d.flags & F_SWAP) ? a : b;
+      s.cu[k] = (d.flags & F_SWAP) ? b : a;
+      s.cv[k] = (d.flags & F_SWAP) ? a : b;
     }
   } else {
     const uint32_t wu = *(GWord)(pu + crow + (x0 >> 1)), wv = *(GWord)(pv + crow + (x0 >> 1));
 #pragma unroll
-    for (int k = 0; k < PX / 2; ++k) cu[k] = byte_of(&wu, k), cv[k] = byte_of(&wv, k);
+    for (int k = 0; k < PX / 2; ++k) s.cu[k] = byte_of(&wu, k), s.cv[k] = byte_of(&wv, k);
   }
+  return s;
+}
+
+// a whole strip of a wide frame: x0 is a multiple of 8 and x0 + 8 <= W
+__device__ inline void strip_wide(const FrameDesc& d, int x0, int y0) {
+  const bool two = y0 + 1 < d.H;
+  const Strip s = load_strip(d, x0, y0, two);
   Words6 o0, o1;
 #pragma unroll
-  for (int k = 0; k < 6; ++k) o0.w[k] = o1.w[k] = 0u;
+  for (int h = 0; h < PX / 4; ++h) {                              // four pixels of each row are three dwords
+    uint32_t a[4], b[4];
 #pragma unroll
-  for (int p = 0; p < PX; ++p) {
-    const Chroma c = chroma_terms(d, cu[p >> 1], cv[p >> 1]);
-    const uint32_t a = pixel(d, byte_of(l0.w, p), c), b = pixel(d, byte_of(l1.w, p), c);
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) {
-      const int i = 3 * p + ch;
-      o0.w[i >> 2] |= ((a >> (8 * ch)) & 0xffu) << (8 * (i & 3));
-      o1.w[i >> 2] |= ((b >> (8 * ch)) & 0xffu) << (8 * (i & 3));
+    for (int p = 0; p < 4; ++p) {
+      const Chroma c = chroma_terms(d, s.cu[(4 * h + p) >> 1], s.cv[(4 * h + p) >> 1]);
+      a[p] = pixel(d, byte_of(s.l0.w, 4 * h + p), c), b[p] = pixel(d, byte_of(s.l1.w, 4 * h + p), c);
     }
+    pack4(a, o0.w + 3 * h), pack4(b, o1.w + 3 * h);
   }
   const GOut orow = (GOut)d.dst + ((size_t)y0 * d.W + x0) * 3;
   store6(orow, o0);
@@ -107,22 +134,12 @@ __device__ inline void strip_wide(const FrameDesc& d, int x0, int y0) {
 
 // any strip of any frame, byte by byte: the pixels [x0, min(x0 + 8, W)) of the rows y0 and, inside the frame, y0 + 1
 __device__ inline void strip_bytes(const FrameDesc& d, int x0, int y0) {
-  const GBytes py = (GBytes)d.y, pu = (GBytes)d.u, pv = (GBytes)d.v;
+  const GBytes py = (GBytes)d.y;
   const int rows = min(2, d.H - y0);
-  const size_t crow = (size_t)(y0 >> 1) * d.c_pitch;
   for (int k = 0; k < PX / 2; ++k) {
     const int xb = x0 + 2 * k;
     if (xb >= d.W) break;
-    uint32_t U, V;
-    if (d.flags & F_INTERLEAVED) {
-      const uint32_t a = pu[crow + xb], b = pu[crow + xb + 1];         // (xb is even: the pair of chroma sample xb / 2)
-      U = (d.flags & F_SWAP) ? b : a;
-      V = (d.flags & F_SWAP) ? a : b;
-    } else {
-      U = pu[crow + (xb >> 1)];
-      V = pv[crow + (xb >> 1)];
-    }
-    const Chroma c = chroma_terms(d, U, V);
+    const Chroma c = chroma_at(d, xb >> 1, y0 >> 1);                  // (xb and y0 are even)
     const int cols = min(2, d.W - xb);
     for (int r = 0; r < rows; ++r)
       for (int j = 0; j < cols; ++j) {
@@ -135,7 +152,7 @@ __device__ inline void strip_bytes(const FrameDesc& d, int x0, int y0) {
 
 __global__ void __launch_bounds__(THREADS) ingest_kernel(const FrameDesc* __restrict__ descs, const TileRef* __restrict__ tiles) {
   const TileRef t = tiles[blockIdx.x];
-  const FrameDesc d = descs[t.frame];
+  const FrameDesc d = descs[t.owner];
   const int tx = t.tile % d.tiles_x, ty = t.tile / d.tiles_x;
   const int x0 = tx * TILE_W + (int)(threadIdx.x % TX) * PX, y0 = ty * TILE_H + (int)(threadIdx.x / TX) * 2;
   if (x0 >= d.W || y0 >= d.H) return;
@@ -152,22 +169,7 @@ __global__ void __launch_bounds__(THREADS) ingest_kernel(const FrameDesc* __rest
 // tile span a source region whose size depends on the scale, from a fraction of a pixel to 65535, and one code path serves them all).
 
 enum { SRC_YUV = 0, SRC_BGR = 1 };
-typedef const RTD_GLOBAL LinEntry* GLin;
 
-__device__ inline Chroma chroma_at(const FrameDesc& d, int cx, int cy) {
-  const GBytes pu = (GBytes)d.u, pv = (GBytes)d.v;
-  const size_t crow = (size_t)cy * d.c_pitch;
-  uint32_t U, V;
-  if (d.flags & F_INTERLEAVED) {
-    const uint32_t a = pu[crow + 2 * cx], b = pu[crow + 2 * cx + 1];
-    U = (d.flags & F_SWAP) ? b : a;
-    V = (d.flags & F_SWAP) ? a : b;
-  } else {
-    U = pu[crow + cx];
-    V = pv[crow + cx];
-  }
-  return chroma_terms(d, U, V);
-}
 __device__ inline uint32_t luma_at(const FrameDesc& d, int x, int y) { return ((GBytes)d.y)[(size_t)y * d.y_pitch + x]; }
 __device__ inline uint32_t bgr_at(const FrameDesc& d, int x, int y) {
   const GBytes p = (GBytes)d.y + (size_t)y * d.y_pitch + (size_t)x * 3;
@@ -192,20 +194,17 @@ __device__ inline void taps4(const FrameDesc& s, int x0, int x1, int y0, int y1,
   }
 }
 
-// HResizeLinear then VResizeLinear on one output pixel, per channel; every value is non-negative and every product below 2^27
+// one output pixel of the linear path from its four taps: resize_taps.h's linear8 on each channel
 __device__ inline uint32_t blend(const uint32_t p[4], int w0, int w1, int b0, int b1) {
   uint32_t o = 0;
 #pragma unroll
-  for (int ch = 0; ch < 3; ++ch) {
-    const int h0 = __mul24((int)((p[0] >> (8 * ch)) & 0xffu), w0) + __mul24((int)((p[1] >> (8 * ch)) & 0xffu), w1);
-    const int h1 = __mul24((int)((p[2] >> (8 * ch)) & 0xffu), w0) + __mul24((int)((p[3] >> (8 * ch)) & 0xffu), w1);
-    const int v = ((__mul24(b0, h0 >> 4) >> 16) + (__mul24(b1, h1 >> 4) >> 16) + 2) >> 2;                // at most 255 (w0 + w1 and b0 + b1 are at most 2049)
-    o |= (uint32_t)v << (8 * ch);
-  }
+  for (int ch = 0; ch < 3; ++ch)
+    o |= (uint32_t)resize_taps::linear8(byte_of(&p[0], ch), byte_of(&p[1], ch), byte_of(&p[2], ch), byte_of(&p[3], ch), w0, w1, b0, b1) << (8 * ch);
   return o;
 }
 
-// (a + b + c + d + 2) >> 2 per channel of four packed pixels: blue and red in one sum (16 bits apart), green in another
+// resize_taps.h's area8 on each channel of four packed pixels, two channels at a time: blue and red in one sum (16 bits apart, and a
+// sum of four bytes and 2 stays below 2^16), green in another.  An optimisation of area8 for packed pixels, not a second definition
 __device__ inline uint32_t mean4(uint32_t a, uint32_t b, uint32_t c, uint32_t d) {
   const uint32_t m = 0x00ff00ffu;
   const uint32_t br = (((a & m) + (b & m) + (c & m) + (d & m) + 0x00020002u) >> 2) & m;
@@ -234,28 +233,12 @@ __device__ inline void area_wide(const FrameDesc& s, int ox, int oy, uint32_t px
       px[k] = mean4(q[0], q[1], q[2], q[3]);
     }
   } else {
-    const GBytes yrow = (GBytes)s.y + (size_t)y0 * s.y_pitch + x0, pu = (GBytes)s.u, pv = (GBytes)s.v;
-    const Words2 l0 = load2(yrow), l1 = load2(yrow + s.y_pitch);
-    const size_t crow = (size_t)oy * s.c_pitch;
-    uint32_t cu[RPX], cv[RPX];
-    if (s.flags & F_INTERLEAVED) {
-      const Words2 c = load2(pu + crow + x0);
-#pragma unroll
-      for (int k = 0; k < RPX; ++k) {
-        const uint32_t a = byte_of(c.w, 2 * k), b = byte_of(c.w, 2 * k + 1);
-        cu[k] = (s.flags & F_SWAP) ? b : a;
-        cv[k] = (s.flags & F_SWAP) ? a : b;
-      }
-    } else {
-      const uint32_t wu = *(GWord)(pu + crow + ox), wv = *(GWord)(pv + crow + ox);
-#pragma unroll
-      for (int k = 0; k < RPX; ++k) cu[k] = byte_of(&wu, k), cv[k] = byte_of(&wv, k);
-    }
+    const Strip t = load_strip(s, x0, y0, true);                   // (both rows exist: 2 OH == H; RPX output pixels are PX source pixels)
 #pragma unroll
     for (int k = 0; k < RPX; ++k) {
-      const Chroma c = chroma_terms(s, cu[k], cv[k]);
-      px[k] = mean4(pixel(s, byte_of(l0.w, 2 * k), c), pixel(s, byte_of(l0.w, 2 * k + 1), c), pixel(s, byte_of(l1.w, 2 * k), c),
-                    pixel(s, byte_of(l1.w, 2 * k + 1), c));
+      const Chroma c = chroma_terms(s, t.cu[k], t.cv[k]);
+      px[k] = mean4(pixel(s, byte_of(t.l0.w, 2 * k), c), pixel(s, byte_of(t.l0.w, 2 * k + 1), c), pixel(s, byte_of(t.l1.w, 2 * k), c),
+                    pixel(s, byte_of(t.l1.w, 2 * k + 1), c));
     }
   }
 }
@@ -280,7 +263,7 @@ __device__ inline void area_bytes(const FrameDesc& s, int ox, int oy, int cnt, u
 template <int SRC>
 __global__ void __launch_bounds__(THREADS) resize_kernel(const ResizeDesc* __restrict__ descs, const TileRef* __restrict__ tiles) {
   const TileRef t = tiles[blockIdx.x];
-  const ResizeDesc d = descs[t.frame];
+  const ResizeDesc d = descs[t.owner];
   const int tx = t.tile % d.tiles_x, ty = t.tile / d.tiles_x;
   const int ox = tx * RTILE_W + (int)(threadIdx.x % TX) * RPX, oy = ty * RTILE_H + (int)(threadIdx.x / TX);
   if (ox >= d.OW || oy >= d.OH) return;
@@ -304,10 +287,9 @@ __global__ void __launch_bounds__(THREADS) resize_kernel(const ResizeDesc* __res
   }
   const GOut o = (GOut)d.out + ((size_t)oy * d.OW + ox) * 3;
   if ((d.rflags & R_DST_WIDE) && cnt == RPX) {
-    const GOutWord q = (GOutWord)o;
-    q[0] = px[0] | px[1] << 24;
-    q[1] = px[1] >> 8 | px[2] << 16;
-    q[2] = px[2] >> 16 | px[3] << 8;
+    uint32_t w[3];
+    pack4(px, w);
+    store3(o, w);
   } else {
 #pragma unroll
     for (int k = 0; k < RPX; ++k) {
@@ -329,24 +311,10 @@ struct rtd_ingest : bk::Base {
 
 namespace ingest {
 
-static void convert(rtd_ingest* g, int n, const rtd_yuv_frame* frames, bool on_device, uint8_t* const* out_dev) {
-  hipStream_t s = g->q.stream;
-  const Plan p = plan(n, frames, on_device);
-  g->pin.reserve(p.total);
-  g->dev.reserve(p.total);
-  fill_tables(g->pin.p, p, n, frames, on_device, g->dev.p, out_dev);
-  if (!on_device)
-    for (int i = 0; i < n; ++i) pack_frame(g->pin.p + p.foff[i], frames[i]);
-  HIP_CHECK(hipMemcpyAsync(g->dev.p, g->pin.p, p.total, hipMemcpyHostToDevice, s));       // tables and frames: one DMA
-  rtd::rtd_launch(ingest_kernel, dim3((unsigned)p.tiles), dim3(THREADS), 0, s, (const FrameDesc*)g->dev.p, (const TileRef*)(g->dev.p + p.tile_off));
-  HIP_CHECK(hipGetLastError());
-  HIP_CHECK(hipStreamSynchronize(s));
-}
-
-// either resize call: up to three launches on the handle's stream after the one staging copy - the convert kernel for the frames
-// whose native BGR frame is wanted, the fused kernel for the other 4:2:0 frames, the BGR kernel for BGR sources and for the native
-// frames the convert kernel has just written
-static void resize(rtd_ingest* g, const ResizeCall& c) {
+// any of the three calls: up to three launches on the handle's stream after the one staging copy - the convert kernel for the frames
+// whose native BGR frame is wanted (all frames of rtd_ingest_convert), the fused kernel for the other 4:2:0 frames, the BGR kernel for
+// BGR sources and for the native frames the convert kernel has just written
+static void run(rtd_ingest* g, const ResizeCall& c) {
   hipStream_t s = g->q.stream;
   const ResizePlan p = plan_resize(c);
   g->pin.reserve(p.total);
@@ -363,12 +331,13 @@ static void resize(rtd_ingest* g, const ResizeCall& c) {
   HIP_CHECK(hipStreamSynchronize(s));
 }
 
-static int resize_call(rtd_ingest* g, const ResizeCall& c) {
+// what every call does around run(): nothing is copied or launched before the whole call has passed its checks
+static int call(rtd_ingest* g, const ResizeCall& c) {
   return guarded(g, [&] {
     validate_resize(c);
     HIP_CHECK(hipSetDevice(g->device));
     try {
-      resize(g, c);
+      run(g, c);
     } catch (...) {
       g->q.drain();                                        // nothing of a failed call may still read the staging buffers
       throw;
@@ -389,26 +358,17 @@ int rtd_ingest_create(int32_t device, rtd_ingest_handle* out) {
 }
 
 int rtd_ingest_convert(rtd_ingest_handle g, int32_t n, const rtd_yuv_frame* frames, int32_t frames_on_device, uint8_t* const* out_dev) {
-  return guarded(g, [&] {
-    validate(n, frames, out_dev);
-    HIP_CHECK(hipSetDevice(g->device));
-    try {
-      convert(g, n, frames, frames_on_device != 0, out_dev);
-    } catch (...) {
-      g->q.drain();                                        // nothing of a failed call may still read the staging buffers
-      throw;
-    }
-  });
+  return call(g, ResizeCall::convert(n, frames, frames_on_device != 0, out_dev));
 }
 
 int rtd_ingest_convert_resize(rtd_ingest_handle g, int32_t n, const rtd_yuv_frame* frames, int32_t frames_on_device, const int32_t* out_hw,
                               uint8_t* const* out_dev, uint8_t* const* native_out_dev) {
-  return resize_call(g, ResizeCall{n, frames, nullptr, frames_on_device != 0, out_hw, out_dev, native_out_dev});
+  return call(g, ResizeCall{n, frames, nullptr, frames_on_device != 0, out_hw, out_dev, native_out_dev});
 }
 
 int rtd_ingest_resize(rtd_ingest_handle g, int32_t n, const rtd_bgr_frame* frames, int32_t frames_on_device, const int32_t* out_hw,
                       uint8_t* const* out_dev) {
-  return resize_call(g, ResizeCall{n, nullptr, frames, frames_on_device != 0, out_hw, out_dev, nullptr});
+  return call(g, ResizeCall{n, nullptr, frames, frames_on_device != 0, out_hw, out_dev, nullptr});
 }
 
 int rtd_ingest_wait_stream(rtd_ingest_handle g, void* producer_stream) {
@@ -454,15 +414,14 @@ int rtd_debug_resize_table(int32_t ssize, int32_t dsize, int32_t columns, int32_
                            int32_t tile_hw[2]) {
   static thread_local std::string err;
   return bk::caught(err, [&] {
-    auto ok = [](int32_t v) { return v >= 1 && v <= 65535; };
     if (out) {
-      RTD_CHECK(ok(ssize) && ok(dsize), RTD_E_INVALID, "bad size (1..65535)");
+      RTD_CHECK(sides_ok(ssize, dsize), RTD_E_INVALID, "bad size (1..65535)");
       std::vector<LinEntry> t((size_t)dsize);
       resize_taps::linear_table(ssize, dsize, columns != 0, t.data());
       for (int32_t d = 0; d < dsize; ++d) out[4 * d] = t[(size_t)d].i0, out[4 * d + 1] = t[(size_t)d].i1, out[4 * d + 2] = t[(size_t)d].w0, out[4 * d + 3] = t[(size_t)d].w1;
     }
     if (is_area2) {
-      RTD_CHECK(ok(ssize) && ok(dsize) && ok(ssize2) && ok(dsize2), RTD_E_INVALID, "bad size (1..65535)");
+      RTD_CHECK(sides_ok(ssize, dsize) && sides_ok(ssize2, dsize2), RTD_E_INVALID, "bad size (1..65535)");
       *is_area2 = resize_taps::area2(ssize, ssize2, dsize, dsize2) ? 1 : 0;
     }
     if (tile_hw) tile_hw[0] = RTILE_H, tile_hw[1] = RTILE_W;

@@ -1,7 +1,7 @@
-// ingest_host.h - the pure host parts of the frame ingest (ingest.hip): the conversion constants, the argument checks of a call, the
-// descriptors and tile list the kernel reads, and where host frames lie in the staging buffer; for the resize stage also the tap
-// tables (resize_taps.h) and the check that no two outputs share a byte.  No HIP here, so that tools/ingest_host_check.cpp and
-// tools/resize_host_check.cpp can run all of it under the sanitizers on a CPU.
+// ingest_host.h - the pure host parts of the frame ingest (ingest.hip): the conversion constants, and ONE call path for its three
+// calls (a convert call is a resize call whose frames have only a native output): the argument checks, the plan of the staging buffer,
+// the descriptors, tile lists and tap tables (resize_taps.h) the kernels read, and where host frames lie.  No HIP here, so that
+// tools/ingest_host_check.cpp can run all of it under the sanitizers on a CPU.
 #pragma once
 #include <stdint.h>
 #include <string.h>
@@ -10,10 +10,15 @@
 #include <vector>
 
 #include "../../include/rtdetr_mi355.h"
+#include "call_parts.h"
 #include "error.h"
 #include "resize_taps.h"
 
 namespace ingest_host {
+
+using rtd::backend::TileRef;         // owner: the frame
+using rtd::backend::align_up;
+using rtd::backend::sides_ok;
 
 // a thread converts PX pixels of two rows (PX / 2 chroma samples); a workgroup of TX x TY threads one tile
 constexpr int PX = 8;
@@ -32,12 +37,6 @@ struct FrameDesc {           // 80 bytes; what the kernel reads, the same for ev
   int32_t tiles_x, flags, ybias;
   int32_t cy, cvr, cvg, cug, cub;
 };
-
-struct TileRef {
-  int32_t frame, tile;       // tile = ty * tiles_x + tx
-};
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 // THE constants: floor(c 2^20 + 0.5) of the decimal coefficients, order CY, CVR, CVG, CUG, CUB
 inline void coeffs(int32_t matrix, int32_t full_range, int32_t out[5]) {
@@ -68,48 +67,13 @@ inline void check_shape(int i, const rtd_yuv_frame& f) {
   RTD_CHECK(f.layout == RTD_YUV_NV12 || f.layout == RTD_YUV_NV21 || f.layout == RTD_YUV_I420, RTD_E_INVALID, fi + " has an unknown layout");
   RTD_CHECK(f.matrix == RTD_YUV_BT601 || f.matrix == RTD_YUV_BT709, RTD_E_INVALID, fi + " has an unknown matrix");
   RTD_CHECK(f.full_range == 0 || f.full_range == 1, RTD_E_INVALID, fi + " has an unknown range (0 limited, 1 full)");
-  RTD_CHECK(f.width >= 1 && f.height >= 1 && f.width <= 65535 && f.height <= 65535, RTD_E_INVALID, fi + " has a bad size (1..65535 per side)");
+  RTD_CHECK(sides_ok(f.width, f.height), RTD_E_INVALID, fi + " has a bad size (1..65535 per side)");
   RTD_CHECK(f.y_pitch >= f.width, RTD_E_INVALID, fi + ": y_pitch is less than a luma row");
   RTD_CHECK(f.c_pitch >= chroma_row(f.layout, f.width), RTD_E_INVALID, fi + ": c_pitch is less than a chroma row");
 }
 
-// checks every argument of a call; nothing is copied or launched before the whole call has passed
-inline void validate(int n, const rtd_yuv_frame* frames, uint8_t* const* out_dev) {
-  RTD_CHECK(n >= 1 && n <= RTD_INGEST_MAX_FRAMES, RTD_E_INVALID, "1..RTD_INGEST_MAX_FRAMES frames per call");
-  RTD_CHECK(frames && out_dev, RTD_E_INVALID, "null argument");
-  for (int i = 0; i < n; ++i) {
-    const rtd_yuv_frame& f = frames[i];
-    const std::string fi = "frame " + std::to_string(i);
-    check_shape(i, f);
-    RTD_CHECK(f.y && f.u && (interleaved(f.layout) || f.v), RTD_E_INVALID, fi + " has a null plane");
-    RTD_CHECK(out_dev[i], RTD_E_INVALID, fi + " has a null output");
-  }
-}
-
 inline int64_t tiles_of(const rtd_yuv_frame& f) {
   return (int64_t)((f.width + TILE_W - 1) / TILE_W) * ((f.height + TILE_H - 1) / TILE_H);
-}
-
-// the staging buffer of a call: [descriptors | tiles | host frames, tightly packed, each on a 256-byte boundary]
-struct Plan {
-  size_t tile_off = 0, tables = 0, total = 0;   // tables: what the kernel's tables take; total: with the host frames
-  int64_t tiles = 0;
-  std::vector<size_t> foff;                     // host frames: where frame i's luma goes
-};
-
-inline Plan plan(int n, const rtd_yuv_frame* frames, bool on_device) {
-  Plan p;
-  for (int i = 0; i < n; ++i) p.tiles += tiles_of(frames[i]);
-  p.tile_off = align_up(sizeof(FrameDesc) * (size_t)n, 256);
-  p.tables = align_up(p.tile_off + sizeof(TileRef) * (size_t)p.tiles, 256);
-  p.foff.resize((size_t)n);
-  size_t at = p.tables;
-  for (int i = 0; i < n; ++i) {
-    p.foff[(size_t)i] = at;
-    if (!on_device) at = align_up(at + (size_t)frame_bytes(frames[i].height, frames[i].width), 256);
-  }
-  p.total = at;
-  return p;
 }
 
 // a host frame, row by row, into frame_bytes(H, W) bytes at dst: luma, then the chroma plane(s)
@@ -152,21 +116,7 @@ inline rtd_yuv_frame packed_at(const rtd_yuv_frame& f, const uint8_t* base) {
   return t;
 }
 
-// writes the tables of a call into `stage` (plan().tables bytes): frame i's planes are frames[i]'s (device frames) or its packed copy at
-// dev_base + foff[i] (host frames, which are packed into stage + foff[i] by the caller)
-inline void fill_tables(uint8_t* stage, const Plan& p, int n, const rtd_yuv_frame* frames, bool on_device, const uint8_t* dev_base,
-                        uint8_t* const* out_dev) {
-  FrameDesc* descs = (FrameDesc*)stage;
-  TileRef* tiles = (TileRef*)(stage + p.tile_off);
-  int64_t k = 0;
-  for (int i = 0; i < n; ++i) {
-    descs[i] = describe(on_device ? frames[i] : packed_at(frames[i], dev_base + p.foff[(size_t)i]), out_dev[i]);
-    const int32_t cnt = (int32_t)tiles_of(frames[i]);
-    for (int32_t t = 0; t < cnt; ++t) tiles[k++] = {i, t};
-  }
-}
-
-// ---- the resize stage: rtd_ingest_convert_resize and rtd_ingest_resize -------------------------------------------------------------------
+// ---- a call: rtd_ingest_convert, rtd_ingest_convert_resize or rtd_ingest_resize ----------------------------------------------------------
 
 using resize_taps::LinEntry;
 
@@ -185,7 +135,8 @@ struct ResizeDesc {          // 112 bytes; what the resize kernel reads, the sam
   int32_t OW, OH, tiles_x, rflags;
 };
 
-// the arguments of either call in one shape: exactly one of yuv / bgr is set
+// the arguments of any of the three calls in one shape: exactly one of yuv / bgr is set.  rtd_ingest_convert is the call without
+// resized outputs (`resizes` false, out_hw and out unused): its out_dev are the native outputs, and each frame must have one
 struct ResizeCall {
   int n;
   const rtd_yuv_frame* yuv;
@@ -193,14 +144,18 @@ struct ResizeCall {
   bool on_device;
   const int32_t* out_hw;
   uint8_t* const* out;
-  uint8_t* const* native;    // may be null, and so may its entries
+  uint8_t* const* native;    // a resize call: may be null, and so may its entries
+  bool resizes = true;
+  static ResizeCall convert(int n, const rtd_yuv_frame* frames, bool on_device, uint8_t* const* out_dev) {
+    return {n, frames, nullptr, on_device, nullptr, nullptr, out_dev, false};
+  }
   int sw(int i) const { return yuv ? yuv[i].width : bgr[i].width; }
   int sh(int i) const { return yuv ? yuv[i].height : bgr[i].height; }
   int oh(int i) const { return out_hw[2 * i]; }
   int ow(int i) const { return out_hw[2 * i + 1]; }
   uint8_t* native_of(int i) const { return native ? native[i] : nullptr; }
   // the fused kernel reads frame i's planes; otherwise the BGR kernel reads the frame, or the native frame the convert kernel wrote
-  bool fused(int i) const { return yuv && !native_of(i); }
+  bool fused(int i) const { return resizes && yuv && !native_of(i); }
   size_t host_bytes(int i) const { return yuv ? (size_t)frame_bytes(sh(i), sw(i)) : (size_t)sh(i) * (size_t)sw(i) * 3; }
 };
 
@@ -208,15 +163,16 @@ inline int64_t rtiles_of(int oh, int ow) { return (int64_t)((ow + RTILE_W - 1) /
 
 inline void check_bgr(int i, const rtd_bgr_frame& f) {
   const std::string fi = "frame " + std::to_string(i);
-  RTD_CHECK(f.width >= 1 && f.height >= 1 && f.width <= 65535 && f.height <= 65535, RTD_E_INVALID, fi + " has a bad size (1..65535 per side)");
+  RTD_CHECK(sides_ok(f.width, f.height), RTD_E_INVALID, fi + " has a bad size (1..65535 per side)");
   RTD_CHECK((int64_t)f.pitch >= 3 * (int64_t)f.width, RTD_E_INVALID, fi + ": pitch is less than a row of BGR pixels");
   RTD_CHECK(f.data, RTD_E_INVALID, fi + " has a null source");
 }
 
-// checks every argument of a resize call; nothing is copied or launched before the whole call has passed
+// checks every argument of a call; nothing is copied or launched before the whole call has passed.  The limit of 2^24 tiles and the
+// rule that no two outputs share a byte are the resize calls' alone: a convert call is accepted as it always was
 inline void validate_resize(const ResizeCall& c) {
   RTD_CHECK(c.n >= 1 && c.n <= RTD_INGEST_MAX_FRAMES, RTD_E_INVALID, "1..RTD_INGEST_MAX_FRAMES frames per call");
-  RTD_CHECK((c.yuv || c.bgr) && c.out_hw && c.out, RTD_E_INVALID, "null argument");
+  RTD_CHECK((c.yuv || c.bgr) && (c.resizes ? c.out_hw && c.out : c.native != nullptr), RTD_E_INVALID, "null argument");
   int64_t tiles = 0;
   struct Range { uintptr_t a, b; int frame; const char* what; };
   std::vector<Range> ranges;
@@ -229,7 +185,11 @@ inline void validate_resize(const ResizeCall& c) {
     } else {
       check_bgr(i, c.bgr[i]);
     }
-    RTD_CHECK(c.oh(i) >= 1 && c.ow(i) >= 1 && c.oh(i) <= 65535 && c.ow(i) <= 65535, RTD_E_INVALID, fi + " has a bad output size (1..65535 per side)");
+    if (!c.resizes) {
+      RTD_CHECK(c.native[i], RTD_E_INVALID, fi + " has a null output");
+      continue;
+    }
+    RTD_CHECK(sides_ok(c.oh(i), c.ow(i)), RTD_E_INVALID, fi + " has a bad output size (1..65535 per side)");
     RTD_CHECK(c.out[i], RTD_E_INVALID, fi + " has a null output");
     tiles += rtiles_of(c.oh(i), c.ow(i));
     ranges.push_back({(uintptr_t)c.out[i], (uintptr_t)c.out[i] + (uintptr_t)c.oh(i) * (uintptr_t)c.ow(i) * 3, i, "output"});
@@ -246,8 +206,9 @@ inline void validate_resize(const ResizeCall& c) {
                     std::to_string(ranges[j].frame));
 }
 
-// the staging buffer of a resize call: [resize descriptors | convert descriptors (native outputs) | tiles: convert, fused, BGR |
-// tap tables | host frames, tightly packed, each on a 256-byte boundary]
+// the staging buffer of a call: [resize descriptors | convert descriptors (native outputs) | tiles: convert, fused, BGR | tap tables |
+// host frames, tightly packed, each on a 256-byte boundary], each part on a 256-byte boundary.  A part nothing reads takes no room:
+// a convert call is [convert descriptors | tiles | host frames]
 struct ResizePlan {
   size_t fdesc_off = 0, tile_off = 0, table_off = 0, tables_end = 0, total = 0;
   int64_t conv_tiles = 0, fused_tiles = 0, bgr_tiles = 0;       // the three launches' slices of the tile list, in this order
@@ -263,19 +224,20 @@ inline ResizePlan plan_resize(const ResizeCall& c) {
   p.area.resize(n), p.toff.assign(n, 0), p.shared.assign(n, 0), p.foff.assign(n, 0);
   bool any_native = false;
   for (int i = 0; i < c.n; ++i) {
+    if (c.native_of(i)) p.conv_tiles += tiles_of(c.yuv[i]), any_native = true;
+    if (!c.resizes) continue;
     p.area[(size_t)i] = resize_taps::area2(c.sw(i), c.sh(i), c.ow(i), c.oh(i)) ? 1 : 0;
     const int64_t t = rtiles_of(c.oh(i), c.ow(i));
     if (c.fused(i)) p.fused_tiles += t;
     else p.bgr_tiles += t;
-    if (c.native_of(i)) p.conv_tiles += tiles_of(c.yuv[i]), any_native = true;
   }
-  p.fdesc_off = align_up(sizeof(ResizeDesc) * n, 256);
+  p.fdesc_off = align_up(c.resizes ? sizeof(ResizeDesc) * n : 0, 256);
   p.tile_off = align_up(p.fdesc_off + (any_native ? sizeof(FrameDesc) * n : 0), 256);
   p.table_off = align_up(p.tile_off + sizeof(TileRef) * (size_t)(p.conv_tiles + p.fused_tiles + p.bgr_tiles), 256);
   size_t at = p.table_off;
   for (int i = 0; i < c.n; ++i) {
     p.toff[(size_t)i] = at;
-    if (p.area[(size_t)i]) continue;
+    if (!c.resizes || p.area[(size_t)i]) continue;
     for (int j = 0; j < i && !p.shared[(size_t)i]; ++j)         // the cameras of a site mostly share one size: one pair of tables for them
       if (!p.area[(size_t)j] && c.sw(j) == c.sw(i) && c.sh(j) == c.sh(i) && c.ow(j) == c.ow(i) && c.oh(j) == c.oh(i))
         p.toff[(size_t)i] = p.toff[(size_t)j], p.shared[(size_t)i] = 1;
@@ -304,7 +266,8 @@ inline void pack_sources(uint8_t* stage, const ResizePlan& p, const ResizeCall& 
   }
 }
 
-// writes the tables of a resize call into `stage` (p.tables_end bytes); the staging buffer's twin on the device starts at dev_base
+// writes the tables of a call into `stage` (p.tables_end bytes); the staging buffer's twin on the device starts at dev_base.  Frame i's
+// planes are the caller's (device frames) or its packed copy at dev_base + foff[i] (host frames: pack_sources)
 inline void fill_resize(uint8_t* stage, const ResizePlan& p, const ResizeCall& c, const uint8_t* dev_base) {
   ResizeDesc* descs = (ResizeDesc*)stage;
   FrameDesc* conv = (FrameDesc*)(stage + p.fdesc_off);
@@ -324,6 +287,7 @@ inline void fill_resize(uint8_t* stage, const ResizePlan& p, const ResizeCall& c
       } else if (p.conv_tiles) {
         memset(&conv[i], 0, sizeof(FrameDesc));
       }
+      if (!c.resizes) continue;
       d.src = describe(f, nullptr);
       bits = (uintptr_t)d.src.y | (uintptr_t)d.src.u | (uintptr_t)d.src.v | (uintptr_t)f.y_pitch | (uintptr_t)f.c_pitch;
     }

@@ -19,8 +19,10 @@ namespace overlay {
 
 using rtd::Error;
 namespace bk = rtd::backend;
+using bk::TileRef;           // owner: the frame
 using bk::align_up;
 using bk::guarded;
+using bk::sides_ok;
 
 constexpr int TILE_W = 64, TILE_H = 16;
 constexpr int THREADS = 256;
@@ -41,10 +43,6 @@ struct FrameDesc {
   int rows, cols, ch;
   int prim0, nprims;         // this frame's primitives in the flattened table
   int tiles_x;
-};
-
-struct TileRef {
-  int frame, tile;           // tile = ty * tiles_x + tx
 };
 
 __device__ inline bool meets_tile(const DevPrim& p, int X0, int Y0, int X1, int Y1) {
@@ -131,7 +129,7 @@ __global__ void __launch_bounds__(THREADS) overlay_kernel(const FrameDesc* __res
   __shared__ DevPrim kept[CHUNK];
   __shared__ int wave_cnt[THREADS / 64];
   const TileRef t = tiles[blockIdx.x];
-  const FrameDesc d = descs[t.frame];
+  const FrameDesc d = descs[t.owner];
   if (d.ch == 3) draw_tile<3>(d, prims, masks, t.tile, kept, wave_cnt);
   else draw_tile<1>(d, prims, masks, t.tile, kept, wave_cnt);
 }
@@ -176,7 +174,7 @@ static void validate(int n, const uint8_t* const* frames, const int32_t* hwc, co
     const std::string fi = "frame " + std::to_string(i);
     RTD_CHECK(frames[i] && out_dev[i], RTD_E_INVALID, fi + " has a null pointer");
     const int64_t H = hwc[3 * i], W = hwc[3 * i + 1], C = hwc[3 * i + 2];
-    RTD_CHECK(H >= 1 && W >= 1 && H <= 65535 && W <= 65535, RTD_E_INVALID, fi + " has a bad size (1..65535 per side)");
+    RTD_CHECK(sides_ok(H, W), RTD_E_INVALID, fi + " has a bad size (1..65535 per side)");
     RTD_CHECK(C == 1 || C == 3, RTD_E_INVALID, "frames must have 1 or 3 channels");
     RTD_CHECK(H * W * C < (1ll << 31), RTD_E_INVALID, fi + " has 2 GiB or more");
     RTD_CHECK(prim_counts[i] >= 0 && prim_counts[i] <= RTD_OVERLAY_MAX_PRIMS, RTD_E_INVALID,

@@ -1,6 +1,8 @@
-// resize_taps.h - OpenCV's resize tables for 8-bit INTER_LINEAR (imgproc/src/resize.cpp), made in its own double / float arithmetic:
-// THE tap rule of the pixelate face mask (facemask_host.h) and of the frame ingest's resize stage (ingest_host.h), as gauss_taps.h is
-// the blur's.  The restatement both must equal is tests/face_ref.py (linear_table, is_area2).  No HIP here.
+// resize_taps.h - OpenCV's resize for 8-bit INTER_LINEAR (imgproc/src/resize.cpp): the tables, made in its own double / float
+// arithmetic, and the integer rule that turns four taps into one output value.  THE rule of the pixelate face mask (facemask_host.h,
+// facemask.hip) and of the frame ingest's resize stage (ingest_host.h, ingest.hip), as gauss_taps.h is the blur's.  The restatement both
+// must equal is tests/face_ref.py (linear_table, is_area2, resize_linear).  The tables are host code; the pixel rule (linear8, area8)
+// compiles for the device too, and as plain C++ where there is no HIP (tools/ingest_host_check.cpp holds it to hand-worked values).
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -60,5 +62,32 @@ inline void linear_table(int ssize, int dsize, bool columns, LinEntry* out) {
     out[d].w0 = (int16_t)lrintf(c0 * 2048), out[d].w1 = (int16_t)lrintf(c1 * 2048);   // saturate_cast<short>(cbuf[k] * INTER_RESIZE_COEF_SCALE)
   }
 }
+
+// ---- the pixel rule: one channel of one output pixel from its four source values (0..255) ----------------------------------------------
+#if defined(__HIPCC__)
+#define RTD_TAPS_FN __host__ __device__ inline
+#else
+#define RTD_TAPS_FN inline
+#endif
+
+// a product of two values that fit 24 bits: on the device the full-rate multiply (a 32-bit one issues at a quarter of that rate)
+RTD_TAPS_FN int mul24(int a, int b) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return __mul24(a, b);
+#else
+  return a * b;
+#endif
+}
+
+// HResizeLinear<uchar, int, short, 2048> on the rows of p00 p01 and of p10 p11 with the column weights w0, w1, then
+// VResizeLinear<uchar, int, short, FixedPtCast<int, uchar, 22>> with the row weights b0, b1.  Every value is non-negative, every
+// product below 2^27 and the result at most 255: w0 + w1 and b0 + b1 are at most 2049 (linear_table)
+RTD_TAPS_FN int linear8(int p00, int p01, int p10, int p11, int w0, int w1, int b0, int b1) {
+  const int h0 = mul24(p00, w0) + mul24(p01, w1), h1 = mul24(p10, w0) + mul24(p11, w1);
+  return ((mul24(b0, h0 >> 4) >> 16) + (mul24(b1, h1 >> 4) >> 16) + 2) >> 2;
+}
+
+// ResizeAreaFastVec / ResizeAreaFast_Invoker at scale 2: the rounded mean of a 2 x 2 block
+RTD_TAPS_FN int area8(int a, int b, int c, int d) { return (a + b + c + d + 2) >> 2; }
 
 }  // namespace resize_taps

@@ -120,7 +120,7 @@ int main() {
         CHECK(l.tile0 == tiles && l.ntiles > 0);
         tiles += l.ntiles;
         for (size_t t = l.tile0; t < l.tile0 + l.ntiles; ++t) {
-          const fh::FaceDesc& d = p.descs[(size_t)p.tiles[t].face];
+          const fh::FaceDesc& d = p.descs[(size_t)p.tiles[t].owner];
           const int64_t cnt = l.kind == fh::K_PIX_SMALL ? ((int64_t)d.sh * d.sw * 3 + fh::SMALL_TILE - 1) / fh::SMALL_TILE : fh::region_tiles(d);
           CHECK(p.tiles[t].tile >= 0 && p.tiles[t].tile < cnt);
         }
