@@ -529,6 +529,54 @@ int64_t rtd_eva_arena_bytes(rtd_eva_handle e);
 const char* rtd_eva_last_error(rtd_eva_handle e);                          /* e may be NULL: last error of a failed rtd_eva_create */
 void rtd_eva_close(rtd_eva_handle e);
 
+/* ---- YOLOX post-processing: upstream's yolox.utils.postprocess(prediction, num_classes, conf_thre, nms_thre, class_agnostic=False)
+ * with torchvision's batched_nms in its per-class form (_batched_nms_vanilla), and optionally the head's grid decode ------------------
+ * Per image, on prediction[A][5 + C] fp32 rows (cx, cy, w, h, obj, C class scores):
+ *   corners      x1 = cx - w / 2, y1 = cy - h / 2, x2 = cx + w / 2, y2 = cy + h / 2
+ *   class        class_conf = the largest class score, class_id = the LOWEST index that holds it (a NaN class score makes class_conf NaN)
+ *   candidates   the rows with obj * class_conf >= conf_threshold (NaN never passes) whose class has its class_keep bit set
+ *   order        score = obj * class_conf descending; equal scores by lower anchor index first
+ *   suppression  greedy in that order: a row is dropped when an earlier KEPT row of the SAME class has
+ *                inter / (area_a + area_b - inter) > nms_threshold, with inter = max(0, min(x2) - max(x1)) * max(0, min(y2) - max(y1)) and
+ *                area = (x2 - x1) * (y2 - y1), every operation one fp32 operation in this order.  The comparison is strict, and 0 / 0 is
+ *                NaN, which is not greater: the row stays.
+ *   rows         x1, y1, x2, y2, obj, class_conf, class_id (as a float), score descending; rows past `kept` are not written.
+ * decode = 1: the rows are the head's undecoded output (upstream's YOLOXHead with decode_in_inference = False: raw box terms, obj and class
+ * scores already sigmoided), levels of stride 8, 16, 32 in that order, row-major over (y, x) within a level, and
+ *   cx = (t0 + x) * s, cy = (t1 + y) * s, w = exp(t2) * s, h = exp(t3) * s                     before the steps above.
+ * When more rows pass than max_candidates, the best max_candidates by (score descending, anchor ascending) enter the suppression;
+ * counts[i][1] still reports every row that passed (upstream has no such cap).
+ * The handle owns NO stream: rtd_yolox_post_run is ASYNCHRONOUS on the caller's `stream` (as rtd_enhance_crops), one memset and four
+ * launches whatever n is, and nothing crosses to the host between them.  Its scratch (candidate lists, ranked rows, the suppression bit
+ * matrix: n * max_candidates^2 / 8 bytes) is grown on demand and belongs to the call in flight: calls on one handle go on ONE stream.
+ * Refused with RTD_E_INVALID before anything is launched, outputs untouched: n outside 1..max_batch, n_anchors outside 1..max_anchors,
+ * decode = 1 with n_anchors != rtd_yolox_anchors(in_h, in_w), a null pointer, a threshold outside [0, 1] or not finite, a wrong
+ * struct_size.  csrc/yolox_post.hip, csrc/yolox_post_host.h; restated in tests/yolox_ref.py. */
+typedef struct rtd_yolox_post_config {
+  int32_t struct_size; /* = sizeof(rtd_yolox_post_config) */
+  int32_t device;
+  int32_t num_classes;    /* 1..1024 */
+  int32_t max_batch;      /* 1..64 */
+  int32_t max_anchors;    /* 1..2^20 */
+  int32_t max_candidates; /* 64..8192, a multiple of 64 */
+} rtd_yolox_post_config;
+typedef struct rtd_yolox_post_params {
+  int32_t struct_size; /* = sizeof(rtd_yolox_post_params) */
+  float conf_threshold, nms_threshold; /* each in [0, 1], finite */
+  int32_t decode;      /* 0: rows are cx, cy, w, h; 1: the head's output, see above */
+  int32_t in_h, in_w;  /* read when decode = 1: multiples of 32 */
+  const uint32_t* class_keep; /* HOST, NULL (every class) or ceil(num_classes / 32) words: a class whose bit is 0 never passes */
+} rtd_yolox_post_params;
+typedef struct rtd_yolox_post* rtd_yolox_post_handle;
+/* pure host: the anchors of an in_h x in_w input (multiples of 32, 32..16384), (h/8)(w/8) + (h/16)(w/16) + (h/32)(w/32); 640 x 640 -> 8400 */
+int rtd_yolox_anchors(int32_t in_h, int32_t in_w, int32_t* n_anchors);
+int rtd_yolox_post_create(const rtd_yolox_post_config* cfg, rtd_yolox_post_handle* out);
+/* pred_dev: [n][n_anchors][5 + num_classes] fp32 at any 4-byte address; rows_dev: [n][max_candidates][7]; counts_dev: [n][2] kept, passed */
+int rtd_yolox_post_run(rtd_yolox_post_handle y, int32_t n, const float* pred_dev, int32_t n_anchors, const rtd_yolox_post_params* params,
+                       float* rows_dev, int32_t* counts_dev, void* stream);
+const char* rtd_yolox_post_last_error(rtd_yolox_post_handle y);            /* y may be NULL: the last refused create / anchors call */
+void rtd_yolox_post_destroy(rtd_yolox_post_handle y);
+
 #ifdef __cplusplus
 }
 #endif

@@ -127,6 +127,15 @@ class RtdFaceRect(C.Structure):
                 ("k_or_blocks", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class RtdYoloxPostConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "device", "num_classes", "max_batch", "max_anchors", "max_candidates")]
+
+
+class RtdYoloxPostParams(C.Structure):
+    _fields_ = [("struct_size", C.c_int32), ("conf_threshold", C.c_float), ("nms_threshold", C.c_float), ("decode", C.c_int32),
+                ("in_h", C.c_int32), ("in_w", C.c_int32), ("class_keep", C.POINTER(C.c_uint32))]
+
+
 DET_DTYPE = np.dtype([("class_id", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 
 _lib: Optional[C.CDLL] = None
@@ -145,6 +154,7 @@ EXPORTS = [
     "rtd_ingest_create", "rtd_ingest_convert", "rtd_ingest_convert_resize", "rtd_ingest_resize", "rtd_ingest_wait_stream", "rtd_ingest_last_error", "rtd_ingest_destroy",
     "rtd_facemask_create", "rtd_facemask_apply", "rtd_facemask_gray", "rtd_facemask_wait_stream", "rtd_facemask_last_error", "rtd_facemask_destroy",
     "rtd_eva_create", "rtd_eva_forward", "rtd_eva_self_check", "rtd_eva_arena_bytes", "rtd_eva_last_error", "rtd_eva_close",
+    "rtd_yolox_anchors", "rtd_yolox_post_create", "rtd_yolox_post_run", "rtd_yolox_post_last_error", "rtd_yolox_post_destroy",
 ]
 # every symbol include/rtdetr_mi355_test.h declares: kernel-level test / bench / debug entry points (csrc/testapi.hip)
 TEST_EXPORTS = [
@@ -354,6 +364,14 @@ def lib() -> C.CDLL:
         L.rtd_op_eva_rope.argtypes = [i32, vp, vp, vp, i32, i32, i32]
         L.rtd_op_eva_layernorm.argtypes = [i32, vp, vp, vp, vp, i32, i32, i32, i32, i32, f32]
         L.rtd_op_eva_attention.argtypes = [i32, vp, vp, i32, i32, i32]
+    if hasattr(L, "rtd_yolox_post_create"):    # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_yolox_anchors.argtypes = [i32, i32, C.POINTER(i32)]
+        L.rtd_yolox_post_create.argtypes = [C.POINTER(RtdYoloxPostConfig), C.POINTER(vp)]
+        L.rtd_yolox_post_run.argtypes = [vp, i32, vp, i32, C.POINTER(RtdYoloxPostParams), vp, vp, vp]
+        L.rtd_yolox_post_last_error.argtypes = [vp]
+        L.rtd_yolox_post_last_error.restype = C.c_char_p
+        L.rtd_yolox_post_destroy.argtypes = [vp]
+        L.rtd_yolox_post_destroy.restype = None
     _lib = L
     return L
 
@@ -423,7 +441,7 @@ def _raise(code: int, handle=None) -> None:
     _raise_msg(code, Engine._what, lib().rtd_last_error(None))
 
 
-# ---- the ten handles (the engine; motion, mog2, jpeg, overlay, enhance, esrgan, ingest, facemask, eva) ------------------------------------------------------
+# ---- the eleven handles (the engine; motion, mog2, jpeg, overlay, enhance, esrgan, ingest, facemask, eva, yolox_post) ------------------------------------------------------
 def device_index(device) -> int:
     """an int, None (torch's current device), a torch.device or a string like 'cuda:1' -> the device's index"""
     if isinstance(device, int):
