@@ -577,6 +577,39 @@ int rtd_yolox_post_run(rtd_yolox_post_handle y, int32_t n, const float* pred_dev
 const char* rtd_yolox_post_last_error(rtd_yolox_post_handle y);            /* y may be NULL: the last refused create / anchors call */
 void rtd_yolox_post_destroy(rtd_yolox_post_handle y);
 
+/* ---- The YOLOX network (upstream's YOLOX(YOLOPAFPN(CSPDarknet), YOLOXHead) in eval mode with decode_in_inference = False) on the
+ * library's conv kernels: Focus, CSPDarknet with SPP, PAFPN and the decoupled head, every BaseConv as conv + folded BatchNorm (eps
+ * 1e-3) + SiLU.  Input: the reference's `preprocess` output, fp32 [n][3][in_h][in_w] BGR in 0..255 (no mean, no std).  Output: the
+ * head's undecoded rows fp32 [n][A][5 + num_classes] - 4 raw box terms, sigmoid(obj), sigmoid(class scores); levels of stride 8, 16, 32
+ * in that order, row-major over (y, x) - which is what rtd_yolox_post_run reads with decode = 1.  Restated in tests/yolox_net_ref.py.
+ * Variants: base_channels = int(64 * width) must be a multiple of 32 (yolox-s: 32 with depth 1, yolox-l: 64 with depth 3; m, x, tiny
+ * and the depthwise nano are refused).  precision: RTD_PREC_F16X3 (fp16 hi + lo pairs, three MFMAs per product) or RTD_PREC_FP32.
+ * blob: the packed container of yolox_network.fold_state - per convolution `name`.weight [cout][k][k][cin] with the BatchNorm folded in
+ * and `name`.bias [cout]; a table that is not this variant's is RTD_E_INVALID, a NaN, an infinity or (pair engine) |w| > 65504 is
+ * RTD_E_WEIGHTS with the tensor's name.
+ * The handle owns the filters, one cached plan per (n, in_h, in_w) and ONE arena that holds the largest plan seen (a repeated shape
+ * allocates nothing).  It owns NO stream and captures nothing: rtd_yolox_net_run is ASYNCHRONOUS on the caller's `stream`, and the arena
+ * belongs to the call in flight: calls on one handle go on ONE stream.  Refused with RTD_E_INVALID before anything is launched: a null
+ * pointer, a wrong struct_size, n outside 1..max_batch, a side that is no multiple of 32, in_dev off a 16-byte boundary, pred_dev off a
+ * 4-byte boundary, and any shape the conv launchers refuse (with their message).  csrc/yolox_net.hip, csrc/yolox_net_host.h. */
+typedef struct rtd_yolox_net_config {
+  int32_t struct_size;   /* = sizeof(rtd_yolox_net_config) */
+  int32_t device;
+  int32_t precision;     /* RTD_PREC_F16X3 | RTD_PREC_FP32 */
+  int32_t num_classes;   /* 1..1024 */
+  int32_t base_channels; /* int(64 * width): 32 (yolox-s) or 64 (yolox-l) */
+  int32_t depth;         /* max(round(3 * depth), 1): 1 (yolox-s), 3 (yolox-l) */
+  int32_t max_batch;     /* 1..64 */
+  int32_t reserved0;
+} rtd_yolox_net_config;
+typedef struct rtd_yolox_net* rtd_yolox_net_handle;
+int rtd_yolox_net_create(const rtd_yolox_net_config* cfg, const void* blob, size_t nbytes, rtd_yolox_net_handle* out);
+int rtd_yolox_net_run(rtd_yolox_net_handle y, int32_t n, const float* in_dev /* [n][3][in_h][in_w] */, int32_t in_h, int32_t in_w,
+                      float* pred_dev /* [n][rtd_yolox_anchors(in_h, in_w)][5 + num_classes] */, void* stream);
+int64_t rtd_yolox_net_arena_bytes(rtd_yolox_net_handle y);
+const char* rtd_yolox_net_last_error(rtd_yolox_net_handle y);              /* y may be NULL: the last refused create / rtd_op_yolox_* call */
+void rtd_yolox_net_destroy(rtd_yolox_net_handle y);
+
 #ifdef __cplusplus
 }
 #endif

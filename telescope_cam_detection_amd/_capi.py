@@ -136,6 +136,10 @@ class RtdYoloxPostParams(C.Structure):
                 ("in_h", C.c_int32), ("in_w", C.c_int32), ("class_keep", C.POINTER(C.c_uint32))]
 
 
+class RtdYoloxNetConfig(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("struct_size", "device", "precision", "num_classes", "base_channels", "depth", "max_batch", "reserved0")]
+
+
 DET_DTYPE = np.dtype([("class_id", "<i4"), ("score", "<f4"), ("x1", "<f4"), ("y1", "<f4"), ("x2", "<f4"), ("y2", "<f4")])
 
 _lib: Optional[C.CDLL] = None
@@ -155,6 +159,7 @@ EXPORTS = [
     "rtd_facemask_create", "rtd_facemask_apply", "rtd_facemask_gray", "rtd_facemask_wait_stream", "rtd_facemask_last_error", "rtd_facemask_destroy",
     "rtd_eva_create", "rtd_eva_forward", "rtd_eva_self_check", "rtd_eva_arena_bytes", "rtd_eva_last_error", "rtd_eva_close",
     "rtd_yolox_anchors", "rtd_yolox_post_create", "rtd_yolox_post_run", "rtd_yolox_post_last_error", "rtd_yolox_post_destroy",
+    "rtd_yolox_net_create", "rtd_yolox_net_run", "rtd_yolox_net_arena_bytes", "rtd_yolox_net_last_error", "rtd_yolox_net_destroy",
 ]
 # every symbol include/rtdetr_mi355_test.h declares: kernel-level test / bench / debug entry points (csrc/testapi.hip)
 TEST_EXPORTS = [
@@ -168,6 +173,7 @@ TEST_EXPORTS = [
     "rtd_op_conv_avg", "rtd_op_conv_pool", "rtd_debug_conv_choice", "rtd_debug_last_conv", "rtd_debug_conv_instantiations",
     "rtd_debug_ingest_info", "rtd_debug_resize_table", "rtd_op_stem0_u8", "rtd_debug_facemask_plan",
     "rtd_op_eva_patchify", "rtd_op_eva_rope", "rtd_op_eva_layernorm", "rtd_op_eva_attention", "rtd_debug_eva_tensor",
+    "rtd_op_yolox_focus", "rtd_op_yolox_spp", "rtd_op_yolox_head_emit", "rtd_debug_yolox_tensor",
 ]
 CONV_INFO_FIELDS = ("family", "stages", "bn", "mt", "bm", "smallc", "wsq", "sx", "cog", "S", "grid", "ntn")   # info[12] of the conv-choice calls
 
@@ -372,6 +378,19 @@ def lib() -> C.CDLL:
         L.rtd_yolox_post_last_error.restype = C.c_char_p
         L.rtd_yolox_post_destroy.argtypes = [vp]
         L.rtd_yolox_post_destroy.restype = None
+    if hasattr(L, "rtd_yolox_net_create"):     # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_yolox_net_create.argtypes = [C.POINTER(RtdYoloxNetConfig), vp, C.c_size_t, C.POINTER(vp)]
+        L.rtd_yolox_net_run.argtypes = [vp, i32, vp, i32, i32, vp, vp]
+        L.rtd_yolox_net_arena_bytes.argtypes = [vp]
+        L.rtd_yolox_net_arena_bytes.restype = i64
+        L.rtd_yolox_net_last_error.argtypes = [vp]
+        L.rtd_yolox_net_last_error.restype = C.c_char_p
+        L.rtd_yolox_net_destroy.argtypes = [vp]
+        L.rtd_yolox_net_destroy.restype = None
+        L.rtd_debug_yolox_tensor.argtypes = [vp, C.c_char_p, vp, i64, C.POINTER(i64)]
+        L.rtd_op_yolox_focus.argtypes = [i32, vp, vp, i32, i32, i32]
+        L.rtd_op_yolox_spp.argtypes = [i32, vp, i32, i32, i32, i32]
+        L.rtd_op_yolox_head_emit.argtypes = [C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, i32, vp]
     _lib = L
     return L
 
@@ -441,7 +460,7 @@ def _raise(code: int, handle=None) -> None:
     _raise_msg(code, Engine._what, lib().rtd_last_error(None))
 
 
-# ---- the eleven handles (the engine; motion, mog2, jpeg, overlay, enhance, esrgan, ingest, facemask, eva, yolox_post) ------------------------------------------------------
+# ---- the twelve handles (the engine; motion, mog2, jpeg, overlay, enhance, esrgan, ingest, facemask, eva, yolox_post, yolox_net) ------------------------------------------------------
 def device_index(device) -> int:
     """an int, None (torch's current device), a torch.device or a string like 'cuda:1' -> the device's index"""
     if isinstance(device, int):

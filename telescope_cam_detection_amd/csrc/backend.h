@@ -1,5 +1,5 @@
-// backend.h - the host-side scaffold of all eleven handles (eleven handles, one scaffold): the detector engine (engine_internal.h) and the
-// stand-alone back ends (motion, mog2, jpeg, overlay, enhance, esrgan, ingest, facemask, eva, yolox_post).  What a handle holds, how a C entry point turns exceptions into a
+// backend.h - the host-side scaffold of all twelve handles (twelve handles, one scaffold): the detector engine (engine_internal.h) and the
+// stand-alone back ends (motion, mog2, jpeg, overlay, enhance, esrgan, ingest, facemask, eva, yolox_post, yolox_net).  What a handle holds, how a C entry point turns exceptions into a
 // return code and a message, how a handle is created, the buffers it grows on demand, and the scratch of one call (OpScratch).
 // A back end writes its kernels, its argument checks and its extern "C" functions; nothing here generates an entry point.  Host only.
 #pragma once

@@ -1,6 +1,6 @@
 // engine_internal.h - what engine.hip (the product C ABI) and testapi.hip (kernel-level test / bench / debug entry points) share:
 // the handle, its plans and the few host helpers both translation units call.  Not installed, not part of the ABI.
-// The handle is one of the eleven on the one scaffold of backend.h (eleven handles, one scaffold): Base, caught, create, OwnStream, GrowBuf.
+// The handle is one of the twelve on the one scaffold of backend.h (twelve handles, one scaffold): Base, caught, create, OwnStream, GrowBuf.
 #pragma once
 #include <math.h>
 #include <string.h>

@@ -10,9 +10,11 @@ restated in tests/yolox_ref.py.
   class_conf, class_id; only the first counts[i][0] of image i are written), counts [n][2] (kept, passed).
 * `YOLOXDetector`: the reference's constructor keywords, attributes and methods, plus `model=None, backend=None, decode=False`.  The
   NETWORK is a pluggable callable from a [B, 3, H, W] float batch to [B, A, 5 + C] (with `decode=True`: the head's undecoded output);
-  the YOLOX network on this library's conv engine is the next step and will write its head maps straight into the back end's
-  `decode = 1` input.  Without an injected model, load_model() builds upstream's PyTorch model through `yolox.exp.get_exp` as the
-  reference does, where that package is importable; where it is not, load_model() logs one error and returns False.
+  without an injected model it is chosen by `network`: "auto" builds upstream's PyTorch model through `yolox.exp.get_exp` as the
+  reference does where that package is importable, and otherwise this library's network (yolox_network.YoloxNetwork, csrc/yolox_net.hip)
+  from the checkpoint at `model_path`; "mi355" always takes this library's network.  With it load_model() sets `decode = True` and
+  `num_classes` from the checkpoint.  A checkpoint that does not exist, cannot be read or is refused makes load_model() log one error
+  and return False before any device call.
 * `install()`: sets this class on the module `src.yolox_detector` (the reference imports it function-locally).
 """
 from __future__ import annotations
@@ -119,7 +121,9 @@ class YOLOXDetector:
     def __init__(self, model_name: str = "yolox-s", model_path: str = "models/yolox/yolox_s.pth", device: str = "cuda:0",
                  conf_threshold: float = 0.25, nms_threshold: float = 0.45, input_size: tuple = (640, 640), wildlife_only: bool = True,
                  use_tensorrt: bool = False, model=None, backend=None, decode: bool = False, num_classes: int = 80, max_batch: int = 8,
-                 max_candidates: int = 2048):
+                 max_candidates: int = 2048, network: str = "auto"):
+        if network not in ("auto", "mi355"):
+            raise ValueError(f"network must be 'auto' or 'mi355', not {network!r}")
         self.model_name = model_name
         self.model_path = model_path
         self.device = device
@@ -137,6 +141,7 @@ class YOLOXDetector:
         self.num_classes = int(num_classes)
         self.max_batch = int(max_batch)
         self.max_candidates = int(max_candidates)
+        self.network = network
         self._injected_model = model
         self._backend = backend
         self._warned_cap = False
@@ -149,7 +154,12 @@ class YOLOXDetector:
             logger.error("YOLOX (MI355X): device %r - the post-processing runs on the GPU only", self.device)
             return False
         try:
-            model = self._injected_model if self._injected_model is not None else self._load_pytorch_model()
+            if self._injected_model is not None:
+                model = self._injected_model
+            elif self._wants_own_network():
+                model = self._load_own_network()
+            else:
+                model = self._load_pytorch_model()
             if model is None:
                 return False
             if self._backend is None:
@@ -161,6 +171,37 @@ class YOLOXDetector:
         logger.info("YOLOX (MI355X): %s ready on %s - input %dx%d, %d classes, confidence threshold %.2f, NMS threshold %.2f", self.model_name,
                     self.device, self.input_size[0], self.input_size[1], self.num_classes, self.conf_threshold, self.nms_threshold)
         return True
+
+    def _wants_own_network(self) -> bool:
+        if self.network == "mi355":
+            return True
+        if self.use_tensorrt:
+            return False
+        try:
+            import yolox  # noqa: F401
+        except ImportError:
+            return True
+        return False
+
+    def _load_own_network(self):
+        """this library's network from the checkpoint at model_path; the file and its tensor table are checked on the host first"""
+        import os
+
+        from . import yolox_network as yn
+        if not self.model_path or not os.path.isfile(self.model_path) or not os.access(self.model_path, os.R_OK):
+            logger.error("YOLOX (MI355X): no network - the checkpoint %r does not exist or cannot be read (and no model=... was given)", self.model_path)
+            return None
+        try:
+            state = yn.state_dict_of(self.model_path)
+            variant = yn.variant_of(self.model_name, state)
+            yn.fold_tensors(state, variant)                      # every tensor present and of its shape
+        except Exception as e:
+            logger.error("YOLOX (MI355X): the checkpoint %r is refused: %s", self.model_path, e)
+            return None
+        net = yn.YoloxNetwork(state, self.model_name, device=self.device, input_size=self.input_size, max_batch=self.max_batch)
+        self.decode = True
+        self.num_classes = net.num_classes
+        return net
 
     def _load_pytorch_model(self):
         """upstream's model as src/yolox_detector.py:_load_pytorch_model builds it (not exercised where `yolox` is absent)"""
@@ -303,6 +344,9 @@ class YOLOXDetector:
     def close(self) -> None:
         if self._backend is not None and hasattr(self._backend, "close"):
             self._backend.close()
+        if self._injected_model is None and hasattr(self.model, "close"):
+            self.model.close()
+            self.model = None
 
 
 def install() -> None:
