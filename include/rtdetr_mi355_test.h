@@ -75,6 +75,13 @@ int rtd_op_conv_view(int dtype, const void* x, int ldx, const void* w_ohwi_f32, 
 int rtd_op_conv_dual(int dtype, const void* x, const void* x2, const void* w_f32, const float* bias, const void* res,
                      void* y, int B, int H, int W, int Cin, int C2, int Cout, int KH, int stride, int pad,
                      int act, int res_mode, int out_f32, int x_up2);
+/* rtd_op_conv_dual on channel-slice views: x, x2, res and y are [B, ., ., .] with pixel strides ldx >= Cin, ldx2 >= C2, ldres >= Cout,
+ * ldy >= Cout (in channels), images dense inside each buffer (batch stride = h * w * ld) - how the networks write the halves of a concat
+ * buffer and read a slice of one (Tensor::slice_c).  x2 may be NULL (C2, ldx2 ignored; x_up2 then refused), res may be NULL.  H and W are
+ * the input extents (x_up2 = 1: the output extents), out_f32 = 1 writes fp32 rows (ldy in fp32 channels). */
+int rtd_op_conv_views(int dtype, const void* x, int ldx, const void* x2, int C2, int ldx2, const void* w_f32, const float* bias,
+                      const void* res, int ldres, void* y, int ldy, int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad,
+                      int act, int res_mode, int out_f32, int x_up2);
 /* 1x1 conv (optionally with a second input, as rtd_op_conv_dual) with the FOLLOWING 1x1 conv Cout -> Cnext fused into the launch
  * (how the plan runs a bottleneck's reduce conv inside the previous block's expand conv): y = act(W [x | x2] + b (+ res)),
  * y1 = next_act(W1 y + b1), both written.  dtype 1 (bf16) / 4 (f16x2); RTD_E_INVALID for shapes the streaming kernels do not take. */
@@ -118,6 +125,10 @@ int rtd_op_stem0_u8(const uint8_t* const* frames_dev, int n, int H, int W, const
  *   launchers instantiate from; *needed = bytes including the final NUL (out may be NULL to ask). */
 int rtd_debug_conv_choice(int dtype, int B, int H, int W, int Cin, int C2, int Cout, int KH, int stride, int pad, int res_mode, int out_f32,
                           int x_up2, int Cnext, int avg, int pool, char* key, int key_capacity, int32_t* info);
+/* ... for the launch rtd_op_conv_views would describe: the same views (C2 = 0: no second input, res_mode = 0: no residual) behind 16-byte
+ * aligned probe addresses; same outputs, same refusals. */
+int rtd_debug_conv_choice_views(int dtype, int ldx, int C2, int ldx2, int ldres, int ldy, int B, int H, int W, int Cin, int Cout, int KH,
+                                int stride, int pad, int res_mode, int out_f32, int x_up2, char* key, int key_capacity, int32_t* info);
 int rtd_debug_last_conv(char* key, int key_capacity, int32_t* info);
 int rtd_debug_conv_instantiations(char* out, int64_t capacity, int64_t* needed);
 int rtd_op_layernorm(int dtype, const void* x, const void* res, const float* g, const float* b,

@@ -174,6 +174,7 @@ TEST_EXPORTS = [
     "rtd_debug_ingest_info", "rtd_debug_resize_table", "rtd_op_stem0_u8", "rtd_debug_facemask_plan",
     "rtd_op_eva_patchify", "rtd_op_eva_rope", "rtd_op_eva_layernorm", "rtd_op_eva_attention", "rtd_debug_eva_tensor",
     "rtd_op_yolox_focus", "rtd_op_yolox_spp", "rtd_op_yolox_head_emit", "rtd_debug_yolox_tensor",
+    "rtd_op_conv_views", "rtd_debug_conv_choice_views",
 ]
 CONV_INFO_FIELDS = ("family", "stages", "bn", "mt", "bm", "smallc", "wsq", "sx", "cog", "S", "grid", "ntn")   # info[12] of the conv-choice calls
 
@@ -329,6 +330,9 @@ def lib() -> C.CDLL:
         L.rtd_debug_conv_choice.argtypes = [i32] * 16 + [C.c_char_p, i32, C.POINTER(i32)]
         L.rtd_debug_last_conv.argtypes = [C.c_char_p, i32, C.POINTER(i32)]
         L.rtd_debug_conv_instantiations.argtypes = [C.c_char_p, i64, C.POINTER(i64)]
+    if hasattr(L, "rtd_op_conv_views"):        # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_op_conv_views.argtypes = [i32, vp, i32, vp, i32, i32, vp, vp, vp, i32, vp, i32] + [i32] * 12
+        L.rtd_debug_conv_choice_views.argtypes = [i32] * 17 + [C.c_char_p, i32, C.POINTER(i32)]
     if hasattr(L, "rtd_ingest_create"):        # (absent from older builds loaded through RTD_LIB_PATH)
         L.rtd_ingest_create.argtypes = [i32, C.POINTER(vp)]
         L.rtd_ingest_convert.argtypes = [vp, i32, C.POINTER(RtdYuvFrame), i32, C.POINTER(vp)]
@@ -414,6 +418,12 @@ def conv_choice(dtype: int, B: int, H: int, W: int, Cin: int, Cout: int, k: int 
     """What launch_conv would launch for this launch under the debug options as they stand (rtd_debug_conv_choice: no GPU needed):
     {'key': ..., 'family': ..., 'S': ..., 'grid': ...}, or None when the launchers refuse it."""
     return _conv_report(lib().rtd_debug_conv_choice, dtype, B, H, W, Cin, C2, Cout, k, stride, pad, res_mode, out_f32, x_up2, Cnext, avg, pool)
+
+
+def conv_choice_views(dtype: int, B: int, H: int, W: int, Cin: int, Cout: int, ldx: int, ldy: int, k: int = 1, stride: int = 1, pad: int = 0,
+                      res_mode: int = 0, ldres: int = 0, out_f32: int = 0, C2: int = 0, ldx2: int = 0, x_up2: int = 0):
+    """conv_choice for the launch rtd_op_conv_views describes (rtd_debug_conv_choice_views): channel-slice views with pixel strides ld*."""
+    return _conv_report(lib().rtd_debug_conv_choice_views, dtype, ldx, C2, ldx2, ldres, ldy, B, H, W, Cin, Cout, k, stride, pad, res_mode, out_f32, x_up2)
 
 
 def last_conv():

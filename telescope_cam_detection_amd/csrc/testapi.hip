@@ -278,6 +278,39 @@ int rtd_op_conv_view(int dtype, const void* x, int ldx, const void* w_ohwi_f32, 
   });
 }
 
+// the launch rtd_op_conv_views / rtd_debug_conv_choice_views describe: rtd_op_conv_dual's (x2 optional) on channel-slice views, images
+// dense inside each buffer (bstride = h * w * ld) as Tensor::slice_c makes them; the filter's pointers are the caller's business
+static ConvArgs views_args(int dtype, const void* x, int ldx, const void* x2, int C2, int ldx2, const ConvFilter& f, const void* res, int ldres, void* y,
+                           int ldy, int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad, int act, int res_mode, int out_f32, int x_up2) {
+  RTD_CHECK(dtype == BF16 || dtype == F32 || dtype == F16X2, RTD_E_INVALID, "conv views: dtype");
+  RTD_CHECK(B >= 1 && H >= 1 && W >= 1 && Cin >= 1 && Cout >= 1 && KH >= 1 && stride >= 1 && pad >= 0, RTD_E_INVALID, "conv views: extents");
+  RTD_CHECK(ldx >= Cin && ldy >= Cout && (!x2 || (C2 >= 1 && ldx2 >= C2)) && (!res || ldres >= Cout), RTD_E_INVALID, "conv views: pixel strides");
+  RTD_CHECK(!x_up2 || (x2 && !((H | W) & 1)), RTD_E_INVALID, "conv views: x_up2 needs a second input and even output extents");
+  const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KH) / stride + 1;
+  auto view = [&](const void* p, int dt, int h, int w, int c, int ld) { Tensor t = mk(p, dt, B, h, w, c); t.ld = ld; t.bstride = (int64_t)h * w * ld; return t; };
+  ConvArgs a = conv_args(x_up2 ? view(x, dtype, H / 2, W / 2, Cin, ldx) : view(x, dtype, H, W, Cin, ldx), view(y, out_f32 ? F32 : dtype, OH, OW, Cout, ldy), f, KH,
+                         stride, pad, act);
+  a.x_up2 = x_up2;
+  a.res_mode = res ? res_mode : RES_NONE;
+  if (res) a.res = view(res, dtype, OH, OW, Cout, ldres);
+  if (x2) a.x2 = view(x2, dtype, OH, OW, C2, ldx2);
+  return a;
+}
+
+int rtd_op_conv_views(int dtype, const void* x, int ldx, const void* x2, int C2, int ldx2, const void* w_f32, const float* bias, const void* res, int ldres,
+                      void* y, int ldy, int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad, int act, int res_mode, int out_f32, int x_up2) {
+  if (!x || !y || !w_f32 || !bias) return RTD_E_INVALID;
+  return op_guard([&] {
+    RTD_CHECK((dtype == BF16 || dtype == F32 || dtype == F16X2) && Cin >= 1 && Cout >= 1 && KH >= 1 && (!x2 || C2 >= 1), RTD_E_INVALID, "conv views: arguments");
+    OpScratch sc;
+    const ConvFilter f = dev_filter(sc, dtype, w_f32, bias, Cout, KH * KH * Cin + (x2 ? C2 : 0));
+    ConvArgs a = views_args(dtype, x, ldx, x2, C2, ldx2, f, res, ldres, y, ldy, B, H, W, Cin, Cout, KH, stride, pad, act, res_mode, out_f32, x_up2);
+    give_slab(sc, a);
+    launch_conv(a, nullptr);
+    HIP_CHECK(hipDeviceSynchronize());
+  });
+}
+
 int rtd_op_conv_dual(int dtype, const void* x, const void* x2, const void* w_f32, const float* bias, const void* res, void* y, int B,
                      int H, int W, int Cin, int C2, int Cout, int KH, int stride, int pad, int act, int res_mode, int out_f32, int x_up2) {
   if (!x2 || (x_up2 && ((H | W) & 1))) return RTD_E_INVALID;
@@ -382,6 +415,20 @@ int rtd_debug_conv_choice(int dtype, int B, int H, int W, int Cin, int C2, int C
       r = conv_predict(a, nullptr);
     }
     report_out(r, key, key_capacity, info);
+  });
+}
+// ... for the launch rtd_op_conv_views describes: the same views (pixel strides ld*, images dense inside each buffer) behind 16-byte aligned
+// probe addresses, as yolox_net.hip's builder puts its launches to conv_predict
+int rtd_debug_conv_choice_views(int dtype, int ldx, int C2, int ldx2, int ldres, int ldy, int B, int H, int W, int Cin, int Cout, int KH, int stride, int pad,
+                                int res_mode, int out_f32, int x_up2, char* key, int key_capacity, int32_t* info) {
+  return backend::caught(create_error(), [&] {
+    RTD_CHECK((dtype == BF16 || dtype == F32 || dtype == F16X2) && Cin >= 1 && Cout >= 1 && KH >= 1 && C2 >= 0, RTD_E_INVALID, "conv choice (views): arguments");
+    void* const P = (void*)(uintptr_t)4096;
+    ConvFilter f = conv_filter_extents(dtype, Cout, KH * KH * Cin + C2);
+    f.w = P; f.bias = (float*)P;
+    const ConvArgs a = views_args(dtype, P, ldx, C2 ? P : nullptr, C2, ldx2, f, res_mode != RES_NONE ? P : nullptr, ldres, P, ldy, B, H, W, Cin, Cout, KH, stride,
+                                  pad, ACT_RELU, res_mode, out_f32, x_up2);
+    report_out(conv_predict(a, nullptr), key, key_capacity, info);
   });
 }
 int rtd_debug_last_conv(char* key, int key_capacity, int32_t* info) {

@@ -102,16 +102,19 @@ class Guarded:
         return v.double()
 
 
-def conv_ref(xv, wmat, bias, k, pad, x2v=None):
-    """fp64 [B, OH, OW, N]: unfold + matmul.  xv [B, H, W, Cin], wmat [N, k*k*Cin (+ C2)] with tap-major / channel-minor columns."""
+def conv_ref(xv, wmat, bias, k, pad, x2v=None, stride=1, x_up2=0):
+    """fp64 [B, OH, OW, N]: unfold + matmul.  xv [B, H, W, Cin], wmat [N, k*k*Cin (+ C2)] with tap-major / channel-minor columns.
+    x_up2: xv is read through a nearest 2x upsampling (the seen values, repeated)."""
+    if x_up2:
+        xv = xv.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
     B, H, W, Cin = xv.shape
     N = wmat.shape[0]
-    if k == 1:
+    if k == 1 and stride == 1:
         cols = xv.reshape(B, H * W, Cin).double()
         OH, OW = H, W
     else:
-        OH, OW = H + 2 * pad - k + 1, W + 2 * pad - k + 1
-        u = F.unfold(xv.permute(0, 3, 1, 2).double(), k, padding=pad)                         # [B, Cin * k * k, L], channel-major
+        OH, OW = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
+        u = F.unfold(xv.permute(0, 3, 1, 2).double(), k, padding=pad, stride=stride)          # [B, Cin * k * k, L], channel-major
         cols = u.reshape(B, Cin, k * k, OH * OW).permute(0, 3, 2, 1).reshape(B, OH * OW, k * k * Cin)
     if x2v is not None:
         cols = torch.cat([cols, x2v.reshape(B, OH * OW, -1).double()], dim=-1)
@@ -142,9 +145,9 @@ class Operands:
         g = torch.Generator().manual_seed(zlib.crc32(r["name"].encode()))
         B, H, W, Cin, Cout, k, C2, Cn = r["B"], r["H"], r["W"], r["Cin"], r["Cout"], r["k"], r["C2"], r["Cnext"]
         self.pair = r["dtype"] == "f16x2"
-        self.OH, self.OW = H + 2 * r["pad"] - k + 1, W + 2 * r["pad"] - k + 1
+        self.OH, self.OW = (H + 2 * r["pad"] - k) // r["stride"] + 1, (W + 2 * r["pad"] - k) // r["stride"] + 1
         K = k * k * Cin + C2
-        x = torch.randn(B, H, W, Cin, generator=g)
+        x = torch.randn(B, H // 2, W // 2, Cin, generator=g) if r["x_up2"] else torch.randn(B, H, W, Cin, generator=g)   # x_up2: H, W are the output extents
         w = torch.randn(Cout, K, generator=g) * (1.0 / K) ** 0.5                                   # [tap-major x | x2] columns (OHWI rows)
         self.b = torch.randn(Cout, generator=g) * 0.1
         x2 = torch.randn(B, self.OH, self.OW, C2, generator=g) if C2 else None
@@ -177,7 +180,7 @@ class Operands:
 
     def reference(self):
         r = self.row
-        y = conv_ref(self.xv, self.wv, self.b, r["k"], r["pad"], self.x2v)
+        y = conv_ref(self.xv, self.wv, self.b, r["k"], r["pad"], self.x2v, r["stride"], r["x_up2"])
         return epilogue_ref(y, r["act"], r["res_mode"], self.rv)
 
     def out_kind(self):
