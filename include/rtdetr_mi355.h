@@ -606,6 +606,16 @@ typedef struct rtd_yolox_net* rtd_yolox_net_handle;
 int rtd_yolox_net_create(const rtd_yolox_net_config* cfg, const void* blob, size_t nbytes, rtd_yolox_net_handle* out);
 int rtd_yolox_net_run(rtd_yolox_net_handle y, int32_t n, const float* in_dev /* [n][3][in_h][in_w] */, int32_t in_h, int32_t in_w,
                       float* pred_dev /* [n][rtd_yolox_anchors(in_h, in_w)][5 + num_classes] */, void* stream);
+/* The same call from the camera frames themselves (in place of src/yolox_detector.py:186-220 `preprocess` + the call above): frame i is a
+ * contiguous uint8 HWC BGR device buffer of frame_hw[i] = (h, w), sides 1..16384, at ANY byte address; frames of one call may differ in
+ * size.  One kernel resizes them as F.interpolate(mode = "bilinear", align_corners = False) does on the float frame - fp32, source
+ * coordinate max(scale * (d + 0.5) - 0.5, 0) with scale = (float)src / (float)dst, every operation rounded on its own - and writes the
+ * Focus map; no float frame and no resized image exists.  A frame already in_h x in_w passes as its integers.  Same plan cache, arena,
+ * stream rule and refusals as rtd_yolox_net_run but for the input's alignment; also refused before anything is allocated or launched: a
+ * null array, a null frame pointer, a side outside 1..16384.  frames_dev and frame_hw are HOST arrays, read before the call returns.
+ * Restated in tests/yolox_frames_ref.py. */
+int rtd_yolox_net_run_frames(rtd_yolox_net_handle y, int32_t n, const uint8_t* const* frames_dev /* host array of n device pointers */,
+                             const int32_t* frame_hw /* host [n][2]: h, w */, int32_t in_h, int32_t in_w, float* pred_dev, void* stream);
 int64_t rtd_yolox_net_arena_bytes(rtd_yolox_net_handle y);
 const char* rtd_yolox_net_last_error(rtd_yolox_net_handle y);              /* y may be NULL: the last refused create / rtd_op_yolox_* call */
 void rtd_yolox_net_destroy(rtd_yolox_net_handle y);

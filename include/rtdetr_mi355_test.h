@@ -272,15 +272,19 @@ int rtd_debug_eva_tensor(rtd_eva_handle e, const char* name, float* out, int64_t
 /* the YOLOX network's own kernels (csrc/yolox_net.hip), device pointers, dtype 1 (fp32) or 4 (F16X2 pair storage):
  * focus:     x [n][3][h][w] fp32 (16-byte aligned, h and w even) -> y [n][h/2][w/2][32]: channel 3 k + c = x[c][2 oy + (k & 1)][2 ox + (k >> 1)]
  *            (quadrants top-left, bottom-left, top-right, bottom-right), channels 12..31 zero
+ * focus_u8:  frames: a host array of n (1..64) device pointers to contiguous uint8 HWC BGR frames of frame_hw[i] = (h, w), sides
+ *            1..16384, at any byte address -> y [n][in_h/2][in_w/2][32] (16-byte aligned, in_h and in_w even): focus of the frames
+ *            resized to in_h x in_w by rtd_yolox_net_run_frames' rule
  * spp:       buf [n][h][w][4 c]: reads channel slice 0 (c channels, a multiple of 8; pair storage: of 32) and writes the stride-1 max
  *            pools 5, 9, 13 (padding never wins) into slices 1, 2, 3
  * head_emit: the three levels' fp32 pred-conv rows - cls [n][h_l w_l][cls_ld], regobj [n][h_l w_l][regobj_ld] (4 box terms, obj) - ->
  *            pred [n][A][5 + num_classes] at any 4-byte address: box terms as they are, sigmoid(obj), sigmoid(cls) */
 int rtd_op_yolox_focus(int dtype, const float* x, void* y, int n, int h, int w);
+int rtd_op_yolox_focus_u8(int dtype, const uint8_t* const* frames, const int32_t* frame_hw, int n, int in_h, int in_w, void* y);
 int rtd_op_yolox_spp(int dtype, void* buf, int n, int h, int w, int c);
 int rtd_op_yolox_head_emit(const float* const cls[3], const float* const regobj[3], int cls_ld, int regobj_ld, int n, int in_h, int in_w,
                            int num_classes, float* pred);
-/* a float stage output of the last rtd_yolox_net_run, [n, h, w, c] fp32 (read after that call's stream has drained): `focus`, `stem`,
+/* a float stage output of the last rtd_yolox_net_run or rtd_yolox_net_run_frames, [n, h, w, c] fp32 (read after that call's stream has drained): `focus`, `stem`,
  * `dark2` .. `dark5`, `spp`, `fpn_out0`, `fpn_out1`, `pan_out2`, `pan_out1`, `pan_out0` and per level l = 0..2 `stem_<l>`,
  * `cls_feat_<l>`, `reg_feat_<l>`, `cls_rows_<l>`, `regobj_rows_<l>`.  out may be NULL to ask for the shape. */
 int rtd_debug_yolox_tensor(rtd_yolox_net_handle y, const char* name, float* out, int64_t capacity, int64_t shape[4]);

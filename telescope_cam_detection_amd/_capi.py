@@ -159,7 +159,7 @@ EXPORTS = [
     "rtd_facemask_create", "rtd_facemask_apply", "rtd_facemask_gray", "rtd_facemask_wait_stream", "rtd_facemask_last_error", "rtd_facemask_destroy",
     "rtd_eva_create", "rtd_eva_forward", "rtd_eva_self_check", "rtd_eva_arena_bytes", "rtd_eva_last_error", "rtd_eva_close",
     "rtd_yolox_anchors", "rtd_yolox_post_create", "rtd_yolox_post_run", "rtd_yolox_post_last_error", "rtd_yolox_post_destroy",
-    "rtd_yolox_net_create", "rtd_yolox_net_run", "rtd_yolox_net_arena_bytes", "rtd_yolox_net_last_error", "rtd_yolox_net_destroy",
+    "rtd_yolox_net_create", "rtd_yolox_net_run", "rtd_yolox_net_run_frames", "rtd_yolox_net_arena_bytes", "rtd_yolox_net_last_error", "rtd_yolox_net_destroy",
 ]
 # every symbol include/rtdetr_mi355_test.h declares: kernel-level test / bench / debug entry points (csrc/testapi.hip)
 TEST_EXPORTS = [
@@ -173,7 +173,7 @@ TEST_EXPORTS = [
     "rtd_op_conv_avg", "rtd_op_conv_pool", "rtd_debug_conv_choice", "rtd_debug_last_conv", "rtd_debug_conv_instantiations",
     "rtd_debug_ingest_info", "rtd_debug_resize_table", "rtd_op_stem0_u8", "rtd_debug_facemask_plan",
     "rtd_op_eva_patchify", "rtd_op_eva_rope", "rtd_op_eva_layernorm", "rtd_op_eva_attention", "rtd_debug_eva_tensor",
-    "rtd_op_yolox_focus", "rtd_op_yolox_spp", "rtd_op_yolox_head_emit", "rtd_debug_yolox_tensor",
+    "rtd_op_yolox_focus", "rtd_op_yolox_focus_u8", "rtd_op_yolox_spp", "rtd_op_yolox_head_emit", "rtd_debug_yolox_tensor",
     "rtd_op_conv_views", "rtd_debug_conv_choice_views",
 ]
 CONV_INFO_FIELDS = ("family", "stages", "bn", "mt", "bm", "smallc", "wsq", "sx", "cog", "S", "grid", "ntn")   # info[12] of the conv-choice calls
@@ -395,6 +395,9 @@ def lib() -> C.CDLL:
         L.rtd_op_yolox_focus.argtypes = [i32, vp, vp, i32, i32, i32]
         L.rtd_op_yolox_spp.argtypes = [i32, vp, i32, i32, i32, i32]
         L.rtd_op_yolox_head_emit.argtypes = [C.POINTER(vp), C.POINTER(vp), i32, i32, i32, i32, i32, i32, vp]
+    if hasattr(L, "rtd_yolox_net_run_frames"):    # (absent from older builds loaded through RTD_LIB_PATH)
+        L.rtd_yolox_net_run_frames.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), i32, i32, vp, vp]
+        L.rtd_op_yolox_focus_u8.argtypes = [i32, C.POINTER(vp), C.POINTER(i32), i32, i32, i32, vp]
     _lib = L
     return L
 

@@ -10,7 +10,8 @@
 //   * a Bottleneck's shortcut is the 3x3 conv's RES_POST residual;
 //   * cls_pred is one conv, reg_pred and obj_pred (one input) are ONE conv of N = 5; both write fp32 rows at N padded to 32;
 //   * every launch is put to conv_predict while the plan is built: a shape the launchers refuse is a refused call, never a launch.
-// Three kernels are this file's own: yolox_focus (space to depth from the planar input into the trunk's storage), yolox_spp (the
+// Four kernels are this file's own: yolox_focus (space to depth from the planar input into the trunk's storage), yolox_focus_u8 (the same
+// map straight from uint8 HWC frames of any size, resized as the reference's F.interpolate does: rtd_yolox_net_run_frames), yolox_spp (the
 // stride-1 max pools 5 / 9 / 13 of SPPBottleneck as three 5 x 5 passes in LDS, one launch) and yolox_head_emit (the three levels' pred
 // rows -> [A][5 + C] rows with the sigmoids).  Everything is enqueued on the caller's stream; the handle owns no stream and captures nothing.
 #include <math.h>
@@ -35,26 +36,10 @@ namespace bk = rtd::backend;
 using bk::guarded;
 
 // ---------------------------------------------------------------------------------------------------------------- kernels
-// Focus: one thread per OUTPUT pixel.  The two pixels (2 ox, 2 ox + 1) of an input row are one 8-byte load, so a wave reads 512
-// consecutive bytes of each of the six rows (3 channels x 2 rows) it touches; the thread then writes its pixel's whole 128-byte channel
-// group: channel 3 k + c from quadrant k (top-left, bottom-left, top-right, bottom-right), zeros in 12..31.
+// the store of one Focus output pixel: v[0..11] and zeros above into its 32-channel group, fp32 or hi + lo pairs.  yolox_focus and
+// yolox_focus_u8 both end here, so equal values are equal storage bits.
 template <bool PAIR>
-__global__ void __launch_bounds__(256) yolox_focus(const float* __restrict__ x, int n, int H, int W, void* __restrict__ y) {
-  const int OH = H >> 1, OW = W >> 1;
-  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= (int64_t)n * OH * OW) return;
-  const int ox = (int)(i % OW);
-  const int64_t t = i / OW;
-  const int oy = (int)(t % OH), b = (int)(t / OH);
-  float v[16];
-#pragma unroll
-  for (int k = 12; k < 16; ++k) v[k] = 0.f;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    const float* p = x + (((int64_t)b * 3 + c) * H + 2 * oy) * W + 2 * ox;
-    const float2 top = *(const float2*)p, bot = *(const float2*)(p + W);
-    v[c] = top.x; v[3 + c] = bot.x; v[6 + c] = top.y; v[9 + c] = bot.y;
-  }
+__device__ __forceinline__ void focus_store(void* __restrict__ y, int64_t i, const float (&v)[16]) {
   if (PAIR) {
     sp16* q = (sp16*)y + i * (2 * yh::FOCUS_C);
     const sp16x8 zero = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -75,6 +60,71 @@ __global__ void __launch_bounds__(256) yolox_focus(const float* __restrict__ x, 
 #pragma unroll
     for (int g = 4; g < 8; ++g) *(f32x4*)(q + 4 * g) = f32x4{0.f, 0.f, 0.f, 0.f};
   }
+}
+
+// Focus: one thread per OUTPUT pixel.  The two pixels (2 ox, 2 ox + 1) of an input row are one 8-byte load, so a wave reads 512
+// consecutive bytes of each of the six rows (3 channels x 2 rows) it touches; the thread then writes its pixel's whole 128-byte channel
+// group: channel 3 k + c from quadrant k (top-left, bottom-left, top-right, bottom-right), zeros in 12..31.
+template <bool PAIR>
+__global__ void __launch_bounds__(256) yolox_focus(const float* __restrict__ x, int n, int H, int W, void* __restrict__ y) {
+  const int OH = H >> 1, OW = W >> 1;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)n * OH * OW) return;
+  const int ox = (int)(i % OW);
+  const int64_t t = i / OW;
+  const int oy = (int)(t % OH), b = (int)(t / OH);
+  float v[16];
+#pragma unroll
+  for (int k = 12; k < 16; ++k) v[k] = 0.f;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    const float* p = x + (((int64_t)b * 3 + c) * H + 2 * oy) * W + 2 * ox;
+    const float2 top = *(const float2*)p, bot = *(const float2*)(p + W);
+    v[c] = top.x; v[3 + c] = bot.x; v[6 + c] = top.y; v[9 + c] = bot.y;
+  }
+  focus_store<PAIR>(y, i, v);
+}
+
+// The uint8 front end: Focus of the resized frame, from the frames themselves.  One thread per OUTPUT pixel, as yolox_focus: it resamples the
+// 2 x 2 block of resized pixels (2 oy + r, 2 ox + q) x 3 channels with the rule of yolox_net_host.h (frame_tap, frame_blend: bilinear,
+// align_corners = False, each operation one fp32 rounding) and stores its whole 128-byte group.  Frames lie at any byte address and a
+// pixel is 3 bytes, so no wider load is ever aligned: every tap is a byte load.  Neighbouring threads read neighbouring spans of the same
+// source rows, which the vector L1 serves from the same lines; the kernel's traffic is the Focus map it writes (128 bytes per thread
+// against at most 48 source bytes).  Per-frame descriptors travel as the kernel's argument, as CropBatch does.
+struct FrameBatch {
+  const uint8_t* p[yh::MAX_BATCH];   // contiguous HWC uint8 BGR frames on the device
+  int h[yh::MAX_BATCH], w[yh::MAX_BATCH];
+  float sy[yh::MAX_BATCH], sx[yh::MAX_BATCH];   // frame_scale(h, in_h), frame_scale(w, in_w)
+};
+template <bool PAIR>
+__global__ void __launch_bounds__(256) yolox_focus_u8(const FrameBatch fb, int n, int H, int W, void* __restrict__ y) {
+  const int OH = H >> 1, OW = W >> 1;
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= (int64_t)n * OH * OW) return;
+  const int ox = (int)(i % OW);
+  const int64_t t = i / OW;
+  const int oy = (int)(t % OH), b = (int)(t / OH);
+  const uint8_t* __restrict__ f = fb.p[b];
+  const int h = fb.h[b], w = fb.w[b];
+  const float sy = fb.sy[b], sx = fb.sx[b];
+  yh::FrameTap ty[2], tx[2];
+#pragma unroll
+  for (int r = 0; r < 2; ++r) ty[r] = yh::frame_tap(sy, 2 * oy + r, h), tx[r] = yh::frame_tap(sx, 2 * ox + r, w);
+  float v[16];
+#pragma unroll
+  for (int k = 12; k < 16; ++k) v[k] = 0.f;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {                    // quadrant k: row 2 oy + (k & 1), column 2 ox + (k >> 1)
+    const yh::FrameTap& ry = ty[k & 1];
+    const yh::FrameTap& cx = tx[k >> 1];
+    const uint8_t* r0 = f + (int64_t)ry.i0 * w * 3;
+    const uint8_t* r1 = f + (int64_t)ry.i1 * w * 3;
+    const int x0 = cx.i0 * 3, x1 = cx.i1 * 3;      // (at most 3 * 16383)
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+      v[3 * k + c] = yh::frame_blend(ry, cx, (float)r0[x0 + c], (float)r0[x1 + c], (float)r1[x0 + c], (float)r1[x1 + c]);
+  }
+  focus_store<PAIR>(y, i, v);
 }
 
 // SPP: MaxPool2d(k, stride 1, padding k / 2) for k = 5, 9, 13 of channel slice 0 of the [n][h][w][4 cs] concat buffer into slices 1, 2, 3.
@@ -200,6 +250,20 @@ static void launch_focus(int dt, const float* x, void* y, int n, int H, int W, h
   const dim3 grid((unsigned)((total + 255) / 256)), blk(256);
   if (dt == F16X2) rtd_launch(yolox_focus<true>, grid, blk, 0, s, x, n, H, W, y);
   else rtd_launch(yolox_focus<false>, grid, blk, 0, s, x, n, H, W, y);
+  HIP_CHECK(hipGetLastError());
+}
+// frames / frame_hw: the caller's host arrays, already through yh::check_frames
+static void launch_focus_u8(int dt, const uint8_t* const* frames, const int32_t* frame_hw, void* y, int n, int H, int W, hipStream_t s) {
+  FrameBatch fb;
+  memset(&fb, 0, sizeof fb);
+  for (int i = 0; i < n; ++i) {
+    fb.p[i] = frames[i], fb.h[i] = frame_hw[2 * i], fb.w[i] = frame_hw[2 * i + 1];
+    fb.sy[i] = yh::frame_scale(fb.h[i], H), fb.sx[i] = yh::frame_scale(fb.w[i], W);
+  }
+  const int64_t total = (int64_t)n * (H / 2) * (W / 2);
+  const dim3 grid((unsigned)((total + 255) / 256)), blk(256);
+  if (dt == F16X2) rtd_launch(yolox_focus_u8<true>, grid, blk, 0, s, fb, n, H, W, y);
+  else rtd_launch(yolox_focus_u8<false>, grid, blk, 0, s, fb, n, H, W, y);
   HIP_CHECK(hipGetLastError());
 }
 // t: the concat buffer's slice 0 view (c = the slice's channels, ld = 4 c)
@@ -466,20 +530,30 @@ static EmitArgs emit_args(const float* const cls[3], const float* const regobj[3
   return a;
 }
 
-static void run(rtd_yolox_net* e, int n, const float* in, int in_h, int in_w, float* pred, hipStream_t s) {
-  yh::check_run(e->cfg, n, in, in_h, in_w, pred);                  // every argument is checked before anything is allocated or launched
+// the checked call, whichever front end: `fill(focus)` launches the kernel that writes the plan's `in` tensor, the rest is the plan
+template <typename Fill>
+static void run_plan(rtd_yolox_net* e, int n, int in_h, int in_w, float* pred, hipStream_t s, Fill&& fill) {
   HIP_CHECK(hipSetDevice(e->device));
   Plan* p = get_plan(e, n, in_h, in_w);                            // (a shape the conv launchers refuse throws here)
   e->last_plan = nullptr;
   e->arena.reserve(p->bytes);
   char* base = (char*)e->arena.p;
-  launch_focus(e->P, in, base + (size_t)p->in.p, n, in_h, in_w, s);
+  fill((void*)(base + (size_t)p->in.p));
   for (const Op& op : p->ops) run_op(e, p, op, s);
   const float* cls[yh::LEVELS];
   const float* ro[yh::LEVELS];
   for (int l = 0; l < yh::LEVELS; ++l) cls[l] = (const float*)(base + (size_t)p->cls_rows[l].p), ro[l] = (const float*)(base + (size_t)p->regobj_rows[l].p);
   launch_emit(emit_args(cls, ro, (int)p->cls_rows[0].ld, (int)p->regobj_rows[0].ld, n, in_h, in_w, e->cfg.num_classes, pred), s);
   e->last_plan = p, e->last_stream = s;
+}
+// every argument is checked before anything is allocated or launched
+static void run(rtd_yolox_net* e, int n, const float* in, int in_h, int in_w, float* pred, hipStream_t s) {
+  yh::check_run(e->cfg, n, in, in_h, in_w, pred);
+  run_plan(e, n, in_h, in_w, pred, s, [&](void* focus) { launch_focus(e->P, in, focus, n, in_h, in_w, s); });
+}
+static void run_frames(rtd_yolox_net* e, int n, const uint8_t* const* frames, const int32_t* frame_hw, int in_h, int in_w, float* pred, hipStream_t s) {
+  yh::check_run_frames(e->cfg, n, frames, frame_hw, in_h, in_w, pred);
+  run_plan(e, n, in_h, in_w, pred, s, [&](void* focus) { launch_focus_u8(e->P, frames, frame_hw, focus, n, in_h, in_w, s); });
 }
 
 // Filters and biases through the upload path of the handle's precision: the blob's rows [cout][k k cin] -> zero-padded fp32 rows
@@ -556,6 +630,11 @@ int rtd_yolox_net_run(rtd_yolox_net_handle e, int32_t n, const float* in_dev, in
   return guarded(e, [&] { run(e, n, in_dev, in_h, in_w, pred_dev, (hipStream_t)stream); });
 }
 
+int rtd_yolox_net_run_frames(rtd_yolox_net_handle e, int32_t n, const uint8_t* const* frames_dev, const int32_t* frame_hw, int32_t in_h, int32_t in_w,
+                             float* pred_dev, void* stream) {
+  return guarded(e, [&] { run_frames(e, n, frames_dev, frame_hw, in_h, in_w, pred_dev, (hipStream_t)stream); });
+}
+
 int64_t rtd_yolox_net_arena_bytes(rtd_yolox_net_handle e) {
   if (!e) return 0;
   std::lock_guard<std::mutex> lk(e->mu);
@@ -603,6 +682,16 @@ int rtd_op_yolox_focus(int dtype, const float* x, void* y, int n, int h, int w) 
               "yolox_focus: arguments (even sides of 2..16384)");
     RTD_CHECK(aligned16(x, y), RTD_E_INVALID, "yolox_focus: alignment");
     launch_focus(op_dtype(dtype), x, y, n, h, w, nullptr);
+  });
+}
+
+int rtd_op_yolox_focus_u8(int dtype, const uint8_t* const* frames, const int32_t* frame_hw, int n, int in_h, int in_w, void* y) {
+  return op_guard([&] {
+    yh::check_frames(n, yh::MAX_BATCH, frames, frame_hw);
+    RTD_CHECK(y && in_h >= 2 && in_w >= 2 && in_h % 2 == 0 && in_w % 2 == 0 && in_h <= 16384 && in_w <= 16384, RTD_E_INVALID,
+              "yolox_focus_u8: arguments (even output sides of 2..16384)");
+    RTD_CHECK(aligned16(y), RTD_E_INVALID, "yolox_focus_u8: alignment");
+    launch_focus_u8(op_dtype(dtype), frames, frame_hw, y, n, in_h, in_w, nullptr);
   });
 }
 

@@ -53,6 +53,74 @@ inline void check_run(const rtd_yolox_net_config& c, int64_t n, const void* in, 
   need(((uintptr_t)pred & 3) == 0, RTD_E_INVALID, "pred_dev must lie on a 4-byte boundary");
 }
 
+// ---- the uint8 front end (yolox_focus_u8): frames at their own sizes -> the resized image the Focus map is cut from.  The rule is
+// F.interpolate(mode = "bilinear", align_corners = False) in fp32, every operation rounded on its own (no contraction into an FMA), so a
+// numpy float32 restatement in the same order (tests/yolox_frames_ref.py) has the kernel's bits.  frame_scale runs on the host, frame_tap
+// and frame_blend on both sides, as resize_taps.h shares cv2's rule.
+constexpr int MAX_FRAME_SIDE = 16384;
+
+#if defined(__HIPCC__)
+#define YOLOX_FRAME_FN __host__ __device__ inline
+#else
+#define YOLOX_FRAME_FN inline
+#endif
+
+struct FrameTap {
+  int i0, i1;        // the two source rows (or columns), clamped into the frame
+  float l0, l1;      // their weights: l1 = the source coordinate's fraction, l0 = 1 - l1
+};
+
+inline float frame_scale(int src, int dst) { return (float)src / (float)dst; }
+
+// area_pixel_compute_source_index(scale, d, align_corners = False, cubic = False) and the index / weight rule of upsample_bilinear2d
+YOLOX_FRAME_FN FrameTap frame_tap(float scale, int d, int extent) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float centre = (float)d + 0.5f;
+  const float scaled = scale * centre;
+  float f = scaled - 0.5f;
+  f = f < 0.f ? 0.f : f;
+  FrameTap t;
+  const int i = (int)f;
+  t.i0 = i < extent - 1 ? i : extent - 1;
+  t.i1 = t.i0 + 1 < extent - 1 ? t.i0 + 1 : extent - 1;
+  t.l1 = f - (float)t.i0;
+  t.l0 = 1.f - t.l1;
+  return t;
+}
+
+// one channel of one resized pixel from its four source values: nine operations, each one IEEE fp32
+YOLOX_FRAME_FN float frame_blend(const FrameTap& ty, const FrameTap& tx, float p00, float p01, float p10, float p11) {
+#if defined(__clang__)
+#pragma clang fp contract(off)
+#endif
+  const float a = tx.l0 * p00, b = tx.l1 * p01, c = tx.l0 * p10, d = tx.l1 * p11;
+  const float top = a + b, bot = c + d;
+  const float u = ty.l0 * top, v = ty.l1 * bot;
+  return u + v;
+}
+
+// rtd_yolox_net_run_frames: what rtd_yolox_net_run refuses but for the input's alignment (a frame lies at any byte address), a null
+// array or frame, a side outside 1..16384.  check_frames alone is what rtd_op_yolox_focus_u8 shares.
+inline void check_frames(int64_t n, int64_t max_batch, const uint8_t* const* frames, const int32_t* frame_hw) {
+  need(frames && frame_hw, RTD_E_INVALID, "null argument");
+  need(n >= 1 && n <= max_batch, RTD_E_INVALID, "1..max_batch (" + std::to_string(max_batch) + ") images per call, not " + std::to_string(n));
+  for (int64_t i = 0; i < n; ++i) {
+    need(frames[i], RTD_E_INVALID, "frame " + std::to_string(i) + ": null pointer");
+    const int32_t h = frame_hw[2 * i], w = frame_hw[2 * i + 1];
+    need(h >= 1 && h <= MAX_FRAME_SIDE && w >= 1 && w <= MAX_FRAME_SIDE, RTD_E_INVALID,
+         "frame " + std::to_string(i) + ": sides must be 1..16384, not " + std::to_string(h) + " x " + std::to_string(w));
+  }
+}
+inline void check_run_frames(const rtd_yolox_net_config& c, int64_t n, const uint8_t* const* frames, const int32_t* frame_hw, int64_t in_h, int64_t in_w,
+                             const void* pred) {
+  need(pred, RTD_E_INVALID, "null argument");
+  check_frames(n, c.max_batch, frames, frame_hw);
+  (void)yolox_post_host::anchors(in_h, in_w);   // a multiple of 32 in 32..16384 per side
+  need(((uintptr_t)pred & 3) == 0, RTD_E_INVALID, "pred_dev must lie on a 4-byte boundary");
+}
+
 // first head row of each level (stride order, row-major over (y, x) within a level) and, in [LEVELS], the rows of an image
 inline void level_offsets(int in_h, int in_w, int64_t off[LEVELS + 1], int lh[LEVELS], int lw[LEVELS]) {
   off[0] = 0;

@@ -15,6 +15,10 @@ restated in tests/yolox_ref.py.
   from the checkpoint at `model_path`; "mi355" always takes this library's network.  With it load_model() sets `decode = True` and
   `num_classes` from the checkpoint.  A checkpoint that does not exist, cannot be read or is refused makes load_model() log one error
   and return False before any device call.
+  `frontend`: "auto" (default) hands uint8 [h][w][3] frames - numpy or device tensors, at their native sizes - to this library's network as
+  they are (YoloxNetwork.run_frames: the resize happens inside the kernel that writes the Focus map); float, CHW and 4-d frames, an
+  injected `model=` and upstream's torch model go through `preprocess()` as in the reference.  "torch" always takes `preprocess()`;
+  "mi355" always takes the fused path, refuses an injected model at construction and raises for a frame the kernel cannot read.
 * `install()`: sets this class on the module `src.yolox_detector` (the reference imports it function-locally).
 """
 from __future__ import annotations
@@ -121,9 +125,13 @@ class YOLOXDetector:
     def __init__(self, model_name: str = "yolox-s", model_path: str = "models/yolox/yolox_s.pth", device: str = "cuda:0",
                  conf_threshold: float = 0.25, nms_threshold: float = 0.45, input_size: tuple = (640, 640), wildlife_only: bool = True,
                  use_tensorrt: bool = False, model=None, backend=None, decode: bool = False, num_classes: int = 80, max_batch: int = 8,
-                 max_candidates: int = 2048, network: str = "auto"):
+                 max_candidates: int = 2048, network: str = "auto", frontend: str = "auto"):
         if network not in ("auto", "mi355"):
             raise ValueError(f"network must be 'auto' or 'mi355', not {network!r}")
+        if frontend not in ("auto", "torch", "mi355"):
+            raise ValueError(f"frontend must be 'auto', 'torch' or 'mi355', not {frontend!r}")
+        if frontend == "mi355" and model is not None:
+            raise ValueError("frontend='mi355' needs this library's network (rtd_yolox_net_run_frames): it cannot be combined with an injected model=")
         self.model_name = model_name
         self.model_path = model_path
         self.device = device
@@ -142,6 +150,7 @@ class YOLOXDetector:
         self.max_batch = int(max_batch)
         self.max_candidates = int(max_candidates)
         self.network = network
+        self.frontend = frontend
         self._injected_model = model
         self._backend = backend
         self._warned_cap = False
@@ -173,7 +182,7 @@ class YOLOXDetector:
         return True
 
     def _wants_own_network(self) -> bool:
-        if self.network == "mi355":
+        if self.network == "mi355" or self.frontend == "mi355":
             return True
         if self.use_tensorrt:
             return False
@@ -284,12 +293,34 @@ class YOLOXDetector:
             out = self.model(batch)
         return out.float().contiguous() if hasattr(out, "contiguous") else out
 
+    # ------------------------------------------------------------------ the fused front end (YoloxNetwork.run_frames)
+    def _takes_fused_path(self, frames) -> bool:
+        """True: these frames go to the network as their uint8 bytes (one kernel resizes them and writes the Focus map); False: through
+        preprocess().  "auto" asks for this library's own network (not an injected model) and uint8 [h][w][3] frames throughout; "mi355"
+        raises for anything else instead of falling back."""
+        if self.frontend == "torch":
+            return False
+        from .yolox_network import YoloxNetwork, is_u8_frame
+        own = self._injected_model is None and isinstance(self.model, YoloxNetwork)
+        fits = all(is_u8_frame(f) for f in frames)
+        if self.frontend == "mi355" and not (own and fits):
+            raise ValueError("frontend='mi355' takes uint8 [h][w][3] frames and this library's network; use frontend='auto' for float or CHW frames")
+        return own and fits
+
+    def _run_frames(self, frames):
+        import torch
+        with torch.no_grad():
+            return self.model.run_frames(frames, self.input_size)
+
     def detect(self, frame) -> List[Dict[str, Any]]:
         if self.model is None:
             logger.error("Model not loaded")
             return []
         orig_h, orig_w = frame.shape[:2]
-        output = self._postprocess(self._run_model(self.preprocess(frame)))[0]
+        if self._takes_fused_path([frame]):
+            output = self._postprocess(self._run_frames([frame]))[0]
+        else:
+            output = self._postprocess(self._run_model(self.preprocess(frame)))[0]
         return self._format_model_output_to_detections(output, orig_h, orig_w)
 
     def detect_batch(self, frames: List) -> List[List[Dict[str, Any]]]:
@@ -317,11 +348,12 @@ class YOLOXDetector:
             else:
                 h, w = frame.shape[0], frame.shape[1]
             orig_sizes.append((h, w))
-        batch_tensor = torch.cat([self.preprocess(frame) for frame in frames], dim=0)
+        fused = self._takes_fused_path(frames)
+        batch_tensor = None if fused else torch.cat([self.preprocess(frame) for frame in frames], dim=0)
         all_detections: List[List[Dict[str, Any]]] = []
         step = max(1, int(getattr(self._backend, "max_batch", len(frames))))
         for i0 in range(0, len(frames), step):                 # larger lists run as several device batches
-            outputs = self._postprocess(self._run_model(batch_tensor[i0:i0 + step]))
+            outputs = self._postprocess(self._run_frames(frames[i0:i0 + step]) if fused else self._run_model(batch_tensor[i0:i0 + step]))
             for k, output in enumerate(outputs):
                 orig_h, orig_w = orig_sizes[i0 + k]
                 all_detections.append(self._format_model_output_to_detections(output, orig_h, orig_w))

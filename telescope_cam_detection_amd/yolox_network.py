@@ -3,7 +3,9 @@
 
 `YoloxNetwork` owns one rtd_yolox_net handle and is the callable `YOLOXDetector` wants as its model: a [B, 3, H, W] float batch (BGR,
 0..255, the reference's `preprocess` output) -> the head's undecoded rows [B, A, 5 + C] on torch's current stream, which the
-post-processing back end reads with `decode=True`.  The architecture, the state-dict keys and BatchNorm's eps of 1e-3 (upstream's
+post-processing back end reads with `decode=True`.  `run_frames` takes the camera frames themselves - uint8 HWC, each at its own size -
+and does the reference's resize inside the kernel that writes the Focus map (rtd_yolox_net_run_frames).  The architecture, the
+state-dict keys and BatchNorm's eps of 1e-3 (upstream's
 `Exp.get_model` sets it; a checkpoint does not carry it) are restated from upstream's public source in tests/yolox_net_ref.py.
 
 Served: yolox-s and yolox-l (every channel count a multiple of 32).  yolox-m, -x, -tiny (widths 48, 80, 24) and the depthwise nano are
@@ -169,6 +171,19 @@ def anchors(in_h: int, in_w: int) -> int:
     return sum((int(in_h) // s) * (int(in_w) // s) for s in STRIDES)
 
 
+def is_u8_frame(f) -> bool:
+    """a uint8 [h][w][3] numpy array or torch tensor: what run_frames (and YOLOXDetector's fused front end) takes"""
+    shape = getattr(f, "shape", None)
+    return shape is not None and len(shape) == 3 and int(shape[2]) == 3 and str(getattr(f, "dtype", "")) in ("uint8", "torch.uint8")
+
+
+def frame_arrays(ptrs, hw):
+    """the two host arrays of rtd_yolox_net_run_frames / rtd_op_yolox_focus_u8: device addresses and (h, w) pairs (None stays a null array)"""
+    frames = None if ptrs is None else (C.c_void_p * max(len(ptrs), 1))(*[C.c_void_p(int(p) or None) for p in ptrs])
+    sizes = None if hw is None else (C.c_int32 * max(2 * len(hw), 1))(*[int(v) for s in hw for v in s])
+    return frames, sizes
+
+
 class YoloxNetwork(_capi.Handle):
     """One rtd_yolox_net handle.  state_or_path: a checkpoint path or a state dict.  Calls are asynchronous on torch's current stream; the
     handle's arena belongs to the call in flight, so use one network from one stream at a time."""
@@ -211,6 +226,35 @@ class YoloxNetwork(_capi.Handle):
         for i0 in range(0, B, self.max_batch):
             k = min(self.max_batch, B - i0)
             self._check(self.run_raw(k, x[i0].data_ptr(), H, W, pred[i0].data_ptr(), stream))
+        return pred
+
+    def run_frames_raw(self, n: int, ptrs, hw, in_h: int, in_w: int, pred_ptr, stream: int) -> int:
+        """rtd_yolox_net_run_frames as it is: the return code.  ptrs: the frames' device addresses, hw: their (h, w); None: a null array"""
+        frames, sizes = frame_arrays(ptrs, hw)
+        return self._L.rtd_yolox_net_run_frames(self._h, int(n), frames, sizes, int(in_h), int(in_w), C.c_void_p(pred_ptr), C.c_void_p(int(stream) or None))
+
+    def run_frames(self, frames, input_size=None):
+        """frames: uint8 [h][w][3] BGR numpy arrays or tensors, each at its own size -> a fresh contiguous fp32 [B, A, 5 + C] device tensor
+        for `input_size` (default: the network's), enqueued on torch's current stream: the reference's `preprocess` (bilinear,
+        align_corners=False) and the Focus map in one kernel, from the bytes.  A numpy frame is uploaded as uint8, one copy; a tensor on the
+        network's device is read in place.  Lists above max_batch run as several calls."""
+        import torch
+
+        H, W = (int(v) for v in (input_size if input_size is not None else self.input_size))
+        dev = torch.device("cuda", self.device)
+        held = []
+        for f in frames:
+            if not is_u8_frame(f):
+                raise TypeError(f"run_frames takes uint8 [h][w][3] arrays or tensors, not {type(f).__name__} {getattr(f, 'dtype', '')} {tuple(getattr(f, 'shape', ()))}")
+            t = f if isinstance(f, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(f))
+            held.append(t.to(dev).contiguous())
+        B = len(held)
+        pred = torch.empty((B, anchors(H, W), 5 + self.num_classes), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        for i0 in range(0, B, self.max_batch):
+            part = held[i0:i0 + self.max_batch]
+            self._check(self.run_frames_raw(len(part), [t.data_ptr() for t in part], [(int(t.shape[0]), int(t.shape[1])) for t in part], H, W,
+                                            pred[i0].data_ptr(), stream))
         return pred
 
     def arena_bytes(self) -> int:

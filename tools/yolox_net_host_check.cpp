@@ -1,5 +1,5 @@
 // Stand-alone check of the pure host parts of the YOLOX network (csrc/yolox_net_host.h): the variants served and refused, the conv table
-// and its channel counts, the per-level anchor offsets, the blob's table (parsing, missing and mis-shaped tensors, NaN and range checks)
+// and its channel counts, the checks of a call (float input and uint8 frames), the front end's index and weight rule, the per-level anchor offsets, the blob's table (parsing, missing and mis-shaped tensors, NaN and range checks)
 // and the SPP kernel's tiling.
 //   c++ -std=c++17 -g -fsanitize=address,undefined -fno-sanitize-recover=all -I. tools/yolox_net_host_check.cpp -o yolox_net_host_check && ./yolox_net_host_check
 #include <stdio.h>
@@ -97,6 +97,58 @@ int main() {
   CHECK(run_refusal(1, nullptr, 640, 640, in).find("null") == 0 && run_refusal(1, in, 640, 640, nullptr).find("null") == 0);
   CHECK(run_refusal(1, in, 640, 650, in).find("the input size") == 0 && run_refusal(1, in, 0, 640, in).find("the input size") == 0 && !run_refusal(1, in, 16416, 64, in).empty());
   CHECK(run_refusal(1, in + 1, 640, 640, in).find("in_dev") == 0 && run_refusal(1, in, 640, 640, (const char*)in + 2).find("pred_dev") == 0);
+
+  // ---- the checks of a call from frames: no alignment rule for a frame, null arrays and frames, sides 1..16384, then what check_run asks
+  {
+    const uint8_t bytes[16] = {0};
+    const uint8_t* two[2] = {bytes + 1, bytes + 3};                       // (odd addresses are fine)
+    const uint8_t* holed[2] = {bytes, nullptr};
+    const int32_t hw[4] = {1080, 1920, 1, 16384};
+    auto frames_refusal = [&](int64_t n, const uint8_t* const* f, const int32_t* s, int64_t h, int64_t w, const void* pred) {
+      return refusal([&] { yh::check_run_frames(c, n, f, s, h, w, pred); });
+    };
+    CHECK(frames_refusal(2, two, hw, 640, 640, in).empty() && frames_refusal(1, two, hw, 32, 64, in + 1).empty());
+    CHECK(frames_refusal(2, nullptr, hw, 640, 640, in).find("null") == 0 && frames_refusal(2, two, nullptr, 640, 640, in).find("null") == 0 &&
+          frames_refusal(2, two, hw, 640, 640, nullptr).find("null") == 0);
+    CHECK(frames_refusal(0, two, hw, 640, 640, in).find("1..max_batch") == 0 && frames_refusal(9, two, hw, 640, 640, in).find("1..max_batch") == 0);
+    CHECK(frames_refusal(2, holed, hw, 640, 640, in).find("frame 1: null") == 0 && frames_refusal(1, holed, hw, 640, 640, in).empty());   // (only the n frames of the call are read)
+    for (int32_t bad : {0, -1, 16385}) {
+      const int32_t bh[4] = {1080, 1920, bad, 8}, bw[4] = {8, bad, 1080, 1920};
+      CHECK(frames_refusal(2, two, bh, 640, 640, in).find("frame 1: sides") == 0 && frames_refusal(2, two, bw, 640, 640, in).find("frame 0: sides") == 0);
+    }
+    CHECK(frames_refusal(2, two, hw, 640, 650, in).find("the input size") == 0 && frames_refusal(2, two, hw, 640, 640, (const char*)in + 2).find("pred_dev") == 0);
+    CHECK(refusal([&] { yh::check_frames(65, yh::MAX_BATCH, two, hw); }).find("1..max_batch") == 0);
+  }
+
+  // ---- the front end's index and weight rule: bilinear, align_corners = False, each operation one fp32 rounding
+  {
+    CHECK(yh::frame_scale(1080, 640) == 1.6875f && yh::frame_scale(1920, 640) == 3.f && yh::frame_scale(64, 64) == 1.f);
+    // 2 -> 4: f = 0, 0.25, 0.75, 1.25
+    const int want_i0[4] = {0, 0, 0, 1}, want_i1[4] = {1, 1, 1, 1};
+    const float want_l1[4] = {0.f, 0.25f, 0.75f, 0.25f};
+    for (int d = 0; d < 4; ++d) {
+      const yh::FrameTap t = yh::frame_tap(yh::frame_scale(2, 4), d, 2);
+      CHECK(t.i0 == want_i0[d] && t.i1 == want_i1[d] && t.l1 == want_l1[d] && t.l0 == 1.f - want_l1[d]);
+    }
+    // the identity size: every tap is the pixel itself with weight 1, and the blend returns the integer
+    for (int d : {0, 1, 63, 16383}) {
+      const yh::FrameTap t = yh::frame_tap(1.f, d, 16384);
+      CHECK(t.i0 == d && t.l1 == 0.f && t.l0 == 1.f && t.i1 == (d < 16383 ? d + 1 : d));
+      CHECK(yh::frame_blend(t, t, 255.f, 7.f, 9.f, 11.f) == 255.f);
+    }
+    // every tap of every size stays inside the frame, weights in [0, 1]; a 1-pixel side reads pixel 0 only
+    for (int src : {1, 2, 3, 37, 1080, 2047, 16384})
+      for (int dst : {2, 32, 96, 640, 16384})
+        for (int d : {0, 1, dst / 2, dst - 2, dst - 1}) {
+          const yh::FrameTap t = yh::frame_tap(yh::frame_scale(src, dst), d, src);
+          CHECK(t.i0 >= 0 && t.i0 <= t.i1 && t.i1 <= src - 1 && t.i1 - t.i0 <= 1 && t.l1 >= 0.f && t.l1 <= 1.f && t.l0 >= 0.f && t.l0 <= 1.f);
+          if (src == 1) CHECK(t.i0 == 0 && t.i1 == 0);
+        }
+    // 3 x downscale (1920 -> 640): f = 3 d + 1, exact; the blend of a 2 x 2 block with l1 = 0.5 on both axes is its mean
+    const yh::FrameTap t3 = yh::frame_tap(3.f, 5, 1920), half = yh::frame_tap(2.f, 0, 4);
+    CHECK(t3.i0 == 16 && t3.i1 == 17 && t3.l1 == 0.f && half.i0 == 0 && half.i1 == 1 && half.l1 == 0.5f);
+    CHECK(yh::frame_blend(half, half, 0.f, 3.f, 12.f, 15.f) == 7.5f);
+  }
 
   // ---- anchor offsets: levels in stride order, row-major within a level; the total is rtd_yolox_anchors
   for (auto hw : {std::pair<int, int>{640, 640}, {64, 96}, {160, 160}, {32, 32}, {416, 672}}) {
