@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG, "csrc")
 LIB_DIR = os.path.join(PKG, "lib")
 LIB_PATH = os.path.join(LIB_DIR, "libmi355rtdetr.so")
 SOURCES = ["conv_igemm.hip", "ops.hip", "decoder.hip", "engine.hip", "testapi.hip", "motion.hip", "mog2.hip", "jpeg.hip", "overlay.hip", "enhance.hip", "esrgan.hip", "ingest.hip", "facemask.hip", "classifier.hip", "yolox_post.hip", "yolox_net.hip"]
-HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "error.h"), os.path.join(CSRC, "backend.h"), os.path.join(CSRC, "call_parts.h"), os.path.join(CSRC, "global_bytes.h"), os.path.join(CSRC, "engine_internal.h"), os.path.join(CSRC, "gauss8.h"), os.path.join(CSRC, "gauss_taps.h"), os.path.join(CSRC, "enhance_tables.h"), os.path.join(CSRC, "esrgan_host.h"), os.path.join(CSRC, "ingest_host.h"), os.path.join(CSRC, "resize_taps.h"), os.path.join(CSRC, "facemask_host.h"), os.path.join(CSRC, "classifier_host.h"), os.path.join(CSRC, "yolox_post_host.h"), os.path.join(CSRC, "yolox_net_host.h"), os.path.join(os.path.dirname(PKG), "include", "rtdetr_mi355.h"),
+HEADERS = [os.path.join(CSRC, "common.h"), os.path.join(CSRC, "error.h"), os.path.join(CSRC, "backend.h"), os.path.join(CSRC, "call_parts.h"), os.path.join(CSRC, "global_bytes.h"), os.path.join(CSRC, "engine_internal.h"), os.path.join(CSRC, "gauss8.h"), os.path.join(CSRC, "gauss_taps.h"), os.path.join(CSRC, "enhance_tables.h"), os.path.join(CSRC, "weight_blob.h"), os.path.join(CSRC, "net_plan.h"), os.path.join(CSRC, "esrgan_host.h"), os.path.join(CSRC, "ingest_host.h"), os.path.join(CSRC, "resize_taps.h"), os.path.join(CSRC, "facemask_host.h"), os.path.join(CSRC, "classifier_host.h"), os.path.join(CSRC, "yolox_post_host.h"), os.path.join(CSRC, "yolox_net_host.h"), os.path.join(os.path.dirname(PKG), "include", "rtdetr_mi355.h"),
            os.path.join(os.path.dirname(PKG), "include", "rtdetr_mi355_test.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-fno-gpu-rdc", "-Wall", "-Wno-unused-function"]
 

@@ -2,6 +2,7 @@
 // stand-alone back ends (motion, mog2, jpeg, overlay, enhance, esrgan, ingest, facemask, eva, yolox_post, yolox_net).  What a handle holds, how a C entry point turns exceptions into a
 // return code and a message, how a handle is created, the buffers it grows on demand, and the scratch of one call (OpScratch).
 // A back end writes its kernels, its argument checks and its extern "C" functions; nothing here generates an entry point.  Host only.
+// The three that run a whole network on launch_conv (esrgan, eva, yolox_net) share more: net_plan.h, on top of this header.
 #pragma once
 #include <algorithm>
 #include <mutex>

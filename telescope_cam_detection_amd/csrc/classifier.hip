@@ -21,13 +21,16 @@
 #include "../../include/rtdetr_mi355_test.h"
 #include "backend.h"
 #include "classifier_host.h"
+#include "net_plan.h"
 
 namespace eva {
 
 using namespace rtd;
 namespace vh = eva_host;
 namespace bk = rtd::backend;
+namespace np = rtd::netplan;
 using bk::guarded;
+using np::op_dtype;
 
 constexpr int HD = vh::HEAD_DIM;
 
@@ -437,8 +440,7 @@ static void launch_pool(int P, const void* x, void* y, int n, int L, int D, int 
 
 // ---------------------------------------------------------------------------------------------------------------- plan
 enum OpKind { OP_PATCHIFY, OP_CONV, OP_TOKENS, OP_LN, OP_ROPE, OP_ATTN, OP_POOL };
-// tensors of an op hold their byte OFFSET inside the arena; run_op() adds the arena's base (the arena may be replaced by a larger one
-// between calls, the plans stay)
+// (tensors of an op are arena offsets: net_plan.h)
 struct Op {
   int kind = OP_CONV;
   ConvArgs conv;                       // OP_CONV (x, y, res as offsets)
@@ -452,30 +454,23 @@ struct Op {
   size_t stage_off = 0;
   int stage_dt = F32, stage_rows = 0, stage_c = 0, stage_ld = 0;   // rows per image
 };
-struct Plan {
+struct Plan : np::PlanBase {
   int n = 0;
-  size_t bytes = 0, slab_off = 0, slab_bytes = 0;
   vh::Layout lay;
   std::vector<Op> ops;
 };
 
 }  // namespace eva
 
-struct rtd_eva : rtd::backend::Base {
+struct rtd_eva : rtd::netplan::NetBase {
   rtd_eva_config cfg;
   eva_host::Dims dm;
-  int P = rtd::F16X2;
   std::vector<char> blob;
-  std::map<std::string, rtd::ConvFilter> filters;
   std::map<std::string, const float*> vecs;     // LayerNorm gains and biases, cls_token, pos_embed, the RoPE tables: fp32 on the device
-  std::vector<void*> allocs;
   std::map<int, std::unique_ptr<eva::Plan>> plans;
-  rtd::backend::DevBuf arena;                   // holds the largest plan seen (a repeated batch size allocates nothing)
-  rtd::ConvOpts conv_opts;
   // the last call (rtd_debug_eva_tensor re-runs it up to the stage asked for; rtd_eva_self_check scans what it left)
   const float* last_x = nullptr;
   eva::Plan* last_plan = nullptr;
-  hipStream_t last_stream = nullptr;
 };
 
 namespace eva {
@@ -498,10 +493,7 @@ static std::unique_ptr<Plan> build_plan(rtd_eva* e, int n) {
     op.kind = OP_CONV;
     ConvArgs& ca = op.conv;
     ca = conv_args(x, y, e->filters.at(name), 1, 1, 0, ACT_NONE);
-    ca.opts = &e->conv_opts;
-    if (res) { ca.res = *res; ca.res_mode = RES_PRE; }
-    (void)conv_predict(ca, nullptr);                             // the launcher's own checks, now: a shape it refuses fails the plan, not a later launch
-    slab = std::max(slab, conv_split_slab_bytes(ca));
+    np::plan_conv(ca, &e->conv_opts, res, RES_PRE, slab, name);
     p->ops.push_back(op);
     return p->ops.back();
   };
@@ -538,33 +530,17 @@ static std::unique_ptr<Plan> build_plan(rtd_eva* e, int n) {
   stage(ln("final_norm", a.pool, 0, D, a.pooln, n, D, D, false, true), "pool", a.pooln, P, 1, D, D);
   stage(conv("head", rows_at(a.pooln, P, n, D, D), rows_at(a.logits, F32, n, d.Cp, d.Cp), nullptr), "logits", a.logits, F32, 1, c.classes, d.Cp);
 
-  p->slab_off = a.top;
-  p->slab_bytes = slab;
-  p->bytes = a.top + (slab + 255) / 256 * 256;
+  p->seal(a.top, slab);
   return p;
-}
-
-static Plan* get_plan(rtd_eva* e, int n) {
-  auto it = e->plans.find(n);
-  if (it != e->plans.end()) return it->second.get();
-  return (e->plans[n] = build_plan(e, n)).get();
 }
 
 static void run_op(rtd_eva* e, const Plan* p, const Op& op, const float* x, hipStream_t s) {
   char* base = (char*)e->arena.p;
   const rtd_eva_config& c = e->cfg;
   const vh::Dims& d = e->dm;
-  auto based = [&](Tensor t) { t.p = base + (size_t)t.p; return t; };
   switch (op.kind) {
     case OP_PATCHIFY: launch_patchify(e->P, x, base + op.y, p->n, c.img, c.patch, s); break;
-    case OP_CONV: {
-      ConvArgs a = op.conv;
-      a.x = based(a.x), a.y = based(a.y);
-      if (a.res_mode != RES_NONE) a.res = based(a.res);
-      if (p->slab_bytes) { a.ws.slab = (float*)(base + p->slab_off); a.ws.slab_bytes = p->slab_bytes; }
-      launch_conv(a, s);
-      break;
-    }
+    case OP_CONV: np::run_conv(op.conv, base, *p, s); break;
     case OP_TOKENS: launch_tokens(e->P, base + op.a, e->vecs.at("cls_token"), e->vecs.at("pos_embed"), base + op.y, p->n, d.L, c.dim, s); break;
     case OP_LN: {
       LnArgs a;
@@ -585,7 +561,7 @@ static void run(rtd_eva* e, const float* x, int n, float* logits, hipStream_t s)
   RTD_CHECK(n >= 1 && n <= e->cfg.max_batch, RTD_E_INVALID, "1..max_batch (" + std::to_string(e->cfg.max_batch) + ") images per call");
   HIP_CHECK(hipSetDevice(e->device));
   e->last_plan = nullptr;
-  Plan* p = get_plan(e, n);
+  Plan* p = np::get_or_build(e->plans, n, vh::MAX_BATCH, [&] { return build_plan(e, n); });   // (n <= 64: the cache never outgrows its cap)
   e->arena.reserve(p->bytes);
   for (const Op& op : p->ops) run_op(e, p, op, x, s);
   HIP_CHECK(hipMemcpy2DAsync(logits, (size_t)e->cfg.classes * 4, e->arena.p + p->lay.logits, (size_t)e->dm.Cp * 4, (size_t)e->cfg.classes * 4, (size_t)n,
@@ -593,25 +569,17 @@ static void run(rtd_eva* e, const float* x, int n, float* logits, hipStream_t s)
   e->last_x = x, e->last_plan = p, e->last_stream = s;
 }
 
-// Filters through the upload path of the handle's precision (common.h: conv_filter_extents / _rows / _convert, as the ESRGAN back end's),
-// every fp32 vector into one pool.  The blob's q rows carry 1 / 8; the fp32 engine's attention (launch_attention) scales by 1 / 8 itself,
-// so its q rows and q bias are uploaded times 8 - exact, a power of two.
+// Every 2-d `.weight` of the table is a filter, uploaded with its `.bias` (net_plan.h: upload_filters); every other tensor is an fp32
+// vector in one pool.  The blob's q rows carry 1 / 8; the fp32 engine's attention (launch_attention) scales by 1 / 8 itself, so its q rows
+// and q bias are uploaded times 8 - exact, a power of two.
 static void upload_weights(rtd_eva* e, const std::map<std::string, vh::HostTensor>& host, const std::vector<vh::TensorDesc>& table) {
-  struct Item { std::string name; ConvFilter f; size_t w_off, b_off; };
-  std::vector<Item> items;
+  std::vector<np::FilterSpec> specs;
   std::vector<std::pair<std::string, size_t>> vec_items;
-  size_t w_bytes = 0, b_bytes = 0, v_bytes = 0;
+  size_t v_bytes = 0;
   for (const vh::TensorDesc& d : table) {
     const bool is_w = d.shape.size() == 2 && d.name.size() > 7 && d.name.compare(d.name.size() - 7, 7, ".weight") == 0;
-    const std::string stem = is_w ? d.name.substr(0, d.name.size() - 7) : "";
     if (is_w) {
-      Item it;
-      it.name = stem;
-      it.f = conv_filter_extents(e->P, (int)d.shape[0], (int)d.shape[1]);
-      it.w_off = w_bytes, it.b_off = b_bytes;
-      w_bytes += bk::align_up(it.f.bytes(), 256);
-      b_bytes += (size_t)it.f.Npad * 4;
-      items.push_back(it);
+      specs.push_back({d.name.substr(0, d.name.size() - 7), conv_filter_extents(e->P, (int)d.shape[0], (int)d.shape[1])});
     } else {
       const size_t dot = d.name.rfind('.');
       const bool is_filter_bias = dot != std::string::npos && d.name.substr(dot) == ".bias" && host.count(d.name.substr(0, dot) + ".weight") &&
@@ -621,26 +589,19 @@ static void upload_weights(rtd_eva* e, const std::map<std::string, vh::HostTenso
       v_bytes += bk::align_up((size_t)host.at(d.name).numel() * 4, 256);
     }
   }
-  auto dmalloc = [&](size_t bytes) { void* q = nullptr; HIP_CHECK(hipMalloc(&q, bytes ? bytes : 256)); e->allocs.push_back(q); return (char*)q; };
-  char* wpool = dmalloc(w_bytes);
-  char* bpool = dmalloc(b_bytes);
-  char* vpool = dmalloc(v_bytes);
+  char* vpool = e->dmalloc(v_bytes);
   for (const auto& v : vec_items) {
     const vh::HostTensor& t = host.at(v.first);
     HIP_CHECK(hipMemcpy(vpool + v.second, t.data, (size_t)t.numel() * 4, hipMemcpyHostToDevice));
     e->vecs[v.first] = (const float*)(vpool + v.second);
   }
-  bk::OpScratch staging;
-  char* stage = e->P == F16X2 ? staging.get<char>(w_bytes) : wpool;
   const int D = e->cfg.dim;
-  for (Item& it : items) {
-    ConvFilter& f = it.f;
-    const vh::HostTensor& w = host.at(it.name + ".weight");
-    const vh::HostTensor& b = host.at(it.name + ".bias");
-    std::vector<float> rows = conv_filter_rows(f, {{w.data, f.K}});
-    std::vector<float> bias(f.Npad, 0.f);
-    for (int o = 0; o < f.N; ++o) bias[o] = b.data[o];
-    const bool qkv = it.name.size() > 9 && it.name.compare(it.name.size() - 9, 9, ".attn.qkv") == 0;
+  np::upload_filters(*e, specs, [&](size_t i, std::vector<float>& rows, std::vector<float>& bias) {
+    const std::string& name = specs[i].name;
+    const ConvFilter& f = specs[i].f;
+    rows = conv_filter_rows(f, {{host.at(name + ".weight").data, f.K}});
+    memcpy(bias.data(), host.at(name + ".bias").data, (size_t)f.N * 4);
+    const bool qkv = name.size() > 9 && name.compare(name.size() - 9, 9, ".attn.qkv") == 0;
     if (qkv && e->P == F32) {
       const int kc = f.kcols();
       for (int o = 0; o < D; ++o) {
@@ -648,26 +609,12 @@ static void upload_weights(rtd_eva* e, const std::map<std::string, vh::HostTenso
         for (int k = 0; k < f.K; ++k) rows[(size_t)o * kc + k] *= 8.f;
       }
     }
-    f.bias = (float*)(bpool + it.b_off);
-    f.w = wpool + it.w_off;
-    float* dev_rows = (float*)(stage + it.w_off);
-    HIP_CHECK(hipMemcpy(f.bias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dev_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
-    conv_filter_convert(f, dev_rows, nullptr);
-    e->filters[it.name] = f;
-  }
-  HIP_CHECK(hipDeviceSynchronize());
+  });
 }
 
-// the test entry points' guard: the message goes where rtd_last_error(NULL) reads it, and the call returns when the device is done
+// (the kernel-level entry points report where rtd_last_error(NULL) reads)
 template <typename F>
-static int op_guard(F&& f) {
-  return bk::caught(bk::create_error<rtd_engine>(), [&] { f(); HIP_CHECK(hipDeviceSynchronize()); });
-}
-static int op_dtype(int dtype) {
-  RTD_CHECK(dtype == F32 || dtype == F16X2, RTD_E_INVALID, "dtype must be 1 (fp32) or 4 (F16X2)");
-  return dtype;
-}
+static int op_guard(F&& f) { return np::op_guard<rtd_engine>(f); }
 
 }  // namespace eva
 
@@ -721,20 +668,13 @@ int rtd_eva_self_check(rtd_eva_handle e, int64_t* saturated) {
   });
 }
 
-int64_t rtd_eva_arena_bytes(rtd_eva_handle e) {
-  if (!e) return 0;
-  std::lock_guard<std::mutex> lk(e->mu);
-  return (int64_t)e->arena.cap;
-}
+int64_t rtd_eva_arena_bytes(rtd_eva_handle e) { return e ? e->arena_bytes() : 0; }
 
 const char* rtd_eva_last_error(rtd_eva_handle e) { return bk::last_error(e); }
 
 void rtd_eva_close(rtd_eva_handle e) {
   if (!e) return;
-  (void)hipSetDevice(e->device);
-  e->arena.release();                           // (hipFree waits for the device: nothing enqueued still uses the arena or the filters)
-  for (void* q : e->allocs) (void)hipFree(q);
-  (void)hipGetLastError();
+  e->release_device();
   delete e;
 }
 
@@ -755,13 +695,7 @@ int rtd_debug_eva_tensor(rtd_eva_handle e, const char* name, float* out, int64_t
     HIP_CHECK(hipSetDevice(e->device));
     hipStream_t s = e->last_stream;
     for (size_t i = 0; i < upto; ++i) run_op(e, p, p->ops[i], e->last_x, s);
-    const void* src = e->arena.p + st->stage_off;
-    bk::OpScratch sc;
-    float* f32 = sc.get<float>((size_t)numel);
-    if (st->stage_dt == F16X2) launch_split_to_f32(src, st->stage_ld, f32, st->stage_c, rows, st->stage_c, s);
-    else HIP_CHECK(hipMemcpy2DAsync(f32, (size_t)st->stage_c * 4, src, (size_t)st->stage_ld * 4, (size_t)st->stage_c * 4, (size_t)rows, hipMemcpyDeviceToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(out, f32, (size_t)numel * 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
+    np::read_tensor(rows_tensor(e->arena.p + st->stage_off, st->stage_dt, p->n, st->stage_rows, st->stage_c, st->stage_ld), rows, out, s);
   });
 }
 

@@ -1,6 +1,6 @@
 // classifier_host.h - the pure host parts of the EVA02 species classifier (classifier.hip): config checks, the derived extents, the weight
 // blob's tensor table and the arena layout of one batch size.  No HIP, no device: this header compiles on its own
-// (tools/eva_host_check.cpp runs it under -fsanitize=address,undefined).  The blob is the container of esrgan_host.h (weights.pack_blob),
+// (tools/eva_host_check.cpp runs it under -fsanitize=address,undefined).  The blob is the container of weight_blob.h (weights.pack_blob),
 // holding the tensors eva_checkpoint.fold_state wrote: already folded and zero-padded, so the table below is a plain shape check.
 #pragma once
 #include <math.h>
@@ -12,13 +12,13 @@
 
 #include "../../include/rtdetr_mi355.h"
 #include "error.h"
-#include "esrgan_host.h"   // need(), HostTensor, parse_blob: one blob format for every back end that reads weights
+#include "weight_blob.h"   // need(), HostTensor, parse_blob, check_values: one blob format for every back end that reads weights
 
 namespace eva_host {
 
-using esrgan_host::HostTensor;
-using esrgan_host::need;
-using esrgan_host::parse_blob;
+using rtd::blob::HostTensor;
+using rtd::blob::need;
+using rtd::blob::parse_blob;
 
 constexpr int HEAD_DIM = 64, MAX_BATCH = 64, MAX_LN_C = 4096, MAX_IMG = 1024, MAX_DEPTH = 64;
 
@@ -95,13 +95,7 @@ inline void check_tensors(const std::map<std::string, HostTensor>& host, const s
     const auto it = host.find(d.name);
     need(it != host.end(), RTD_E_WEIGHTS, "weight blob: missing tensor " + d.name);
     need(it->second.shape == d.shape, RTD_E_WEIGHTS, "weight shape mismatch: " + d.name);
-    const int64_t n = it->second.numel();
-    for (int64_t i = 0; i < n; ++i) {
-      const float v = it->second.data[i];
-      need(isfinite(v), RTD_E_WEIGHTS, "weight blob: tensor " + d.name + " holds a NaN or an infinity");
-      need(!pair || fabsf(v) <= 65504.f, RTD_E_WEIGHTS,
-           "weight blob: tensor " + d.name + " reaches " + std::to_string(v) + ", beyond the fp16 pair format's range (65504): use precision fp32");
-    }
+    rtd::blob::check_values(d.name, it->second, pair);
   }
 }
 

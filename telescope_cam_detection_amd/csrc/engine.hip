@@ -23,40 +23,7 @@ PlanOpts g_opts;
 
 namespace rtd_eng {
 
-// ------------------------------------------------------------------------------------------ blob
-void parse_blob(rtd_engine* e) {
-  const char* b = e->blob.data();
-  const size_t n = e->blob.size();
-  RTD_CHECK(n >= 12 && memcmp(b, "RTDW", 4) == 0, RTD_E_WEIGHTS, "weight blob: bad magic");
-  uint32_t ver, count;
-  memcpy(&ver, b + 4, 4);
-  memcpy(&count, b + 8, 4);
-  RTD_CHECK(ver == 1, RTD_E_WEIGHTS, "weight blob: unsupported version");
-  size_t p = 12;
-  for (uint32_t i = 0; i < count; ++i) {
-    RTD_CHECK(p + 2 <= n, RTD_E_WEIGHTS, "weight blob: truncated table");
-    uint16_t nl;
-    memcpy(&nl, b + p, 2); p += 2;
-    RTD_CHECK(p + nl + 4 <= n, RTD_E_WEIGHTS, "weight blob: truncated table");
-    std::string name(b + p, nl); p += nl;
-    uint32_t nd;
-    memcpy(&nd, b + p, 4); p += 4;
-    RTD_CHECK(nd <= 8 && p + 4 * nd + 16 <= n, RTD_E_WEIGHTS, "weight blob: truncated table");
-    HostTensor t;
-    for (uint32_t d = 0; d < nd; ++d) {
-      uint32_t v;
-      memcpy(&v, b + p, 4); p += 4;
-      t.shape.push_back(v);
-    }
-    uint64_t off, nb;
-    memcpy(&off, b + p, 8); p += 8;
-    memcpy(&nb, b + p, 8); p += 8;
-    RTD_CHECK(off % 4 == 0 && off + nb <= n && (int64_t)nb == t.numel() * 4, RTD_E_WEIGHTS, "weight blob: bad tensor extent: " + name);
-    t.data = (const float*)(b + off);
-    e->host[name] = t;
-  }
-}
-
+// ------------------------------------------------------------------------------------------ blob (the table: weight_blob.h)
 // Real-weights guard, part 1: a checkpoint is refused at load time when a tensor holds a NaN / Inf, or - on the pair
 // engine, whose operands are fp16 hi/lo halves that SATURATE at +-65504 (common.h split2, f2h_rne below) - when a folded filter value does
 // not fit that range: the result would be finite, plausible and wrong.  (BN folding multiplies a filter row by gamma / sqrt(var + eps):
@@ -1371,7 +1338,7 @@ int rtd_load_weights(rtd_handle h, const void* blob, size_t nbytes) {
     if (!e->ev_fork) HIP_CHECK(hipEventCreateWithFlags(&e->ev_fork, hipEventDisableTiming));
     if (!e->ev_join) HIP_CHECK(hipEventCreateWithFlags(&e->ev_join, hipEventDisableTiming));
     e->blob.assign((const char*)blob, (const char*)blob + nbytes);
-    parse_blob(e);
+    blob::parse_blob(e->blob.data(), e->blob.size(), e->host);
     check_weight_range(e);
     const rtd_config& c = e->cfg;
     // level geometry (strides 8/16/32)

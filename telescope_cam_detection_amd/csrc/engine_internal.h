@@ -15,6 +15,7 @@
 
 #include "../../include/rtdetr_mi355_test.h"
 #include "backend.h"
+#include "weight_blob.h"
 
 namespace rtd_eng {
 using namespace rtd;
@@ -46,15 +47,7 @@ struct PlanOpts {
                         // grids and row kernels leave CUs idle (0: one stream)
 };
 
-struct HostTensor {
-  const float* data = nullptr;
-  std::vector<int64_t> shape;
-  int64_t numel() const {
-    int64_t n = 1;
-    for (auto d : shape) n *= d;
-    return n;
-  }
-};
+using blob::HostTensor;   // a tensor of the weight blob (weight_blob.h)
 
 struct Op {
   std::string name;

@@ -29,13 +29,17 @@
 #include "../../include/rtdetr_mi355_test.h"
 #include "backend.h"
 #include "esrgan_host.h"
+#include "net_plan.h"
 
 namespace esrgan {
 
 using namespace rtd;
 namespace eh = esrgan_host;
 namespace bk = rtd::backend;
+namespace np = rtd::netplan;
 using bk::guarded;
+using np::at;
+using np::based;
 
 constexpr int IN_C = 32, FEAT = 64, GROW = 32, DENSE_C = 192, LAST_C = 32;
 
@@ -88,8 +92,7 @@ __global__ void __launch_bounds__(256) esrgan_emit(EmitArgs a) {
 
 // ---------------------------------------------------------------------------------------------------------------- plan
 enum OpKind { OP_CONV, OP_UPSAMPLE, OP_AXPBY, OP_COPY };
-// tensors of an op hold their byte OFFSET inside the arena in `p`; run() adds the arena's base (the arena may be replaced by a larger one
-// between calls, the plans stay)
+// (tensors of an op are arena offsets: net_plan.h)
 struct Op {
   int kind = OP_CONV;
   ConvArgs conv;          // OP_CONV (x, y, res as offsets)
@@ -97,59 +100,37 @@ struct Op {
   std::string stage;      // the debug name of the tensor this op completes ("" = none)
   Tensor stage_t;
 };
-struct Plan {
+struct Plan : np::PlanBase {
   int h = 0, w = 0;
-  size_t bytes = 0;       // arena bytes, the split-K workspace included
-  size_t slab_off = 0, slab_bytes = 0;
   Tensor in, last;
   std::vector<Op> ops;
 };
 
 }  // namespace esrgan
 
-struct rtd_esrgan : rtd::backend::Base {
+struct rtd_esrgan : rtd::netplan::NetBase {
   rtd_esrgan_config cfg;
-  int P = rtd::F16X2;
   std::vector<char> blob;
-  std::map<std::string, rtd::ConvFilter> weights;
-  std::vector<void*> allocs;
   std::map<std::pair<int, int>, std::unique_ptr<esrgan::Plan>> plans;
-  rtd::backend::DevBuf arena;   // holds the largest plan seen (a repeated shape allocates nothing)
-  rtd::ConvOpts conv_opts;
   // the last tile of the last call (rtd_debug_esrgan_tensor re-runs it up to the stage asked for)
   const uint8_t* last_src = nullptr;
   int last_pitch = 0;
   esrgan::Plan* last_plan = nullptr;
-  hipStream_t last_stream = nullptr;
 };
 
 namespace esrgan {
-
-static Tensor at(size_t off, int dt, int h, int w, int c, int ld) {
-  Tensor t;
-  t.p = (void*)off; t.dt = dt; t.n = 1; t.h = h; t.w = w; t.c = c; t.ld = ld; t.bstride = (int64_t)h * w * ld;
-  return t;
-}
-static Tensor based(Tensor t, char* base) {
-  t.p = base + (size_t)t.p;
-  return t;
-}
 
 static std::unique_ptr<Plan> build_plan(rtd_esrgan* e, int h, int w) {
   auto p = std::make_unique<Plan>();
   p->h = h, p->w = w;
   const int P = e->P, B = e->cfg.num_block;
-  size_t top = 0;
-  auto alloc = [&](int hh, int ww, int c, int dt) {
-    const size_t off = top;
-    top += ((size_t)hh * ww * c * 4 + 255) / 256 * 256;
-    return at(off, dt, hh, ww, c, c);
-  };
+  np::Arena arena;
+  auto alloc = [&](int hh, int ww, int c, int dt) { return arena.tensor(dt, 1, hh, ww, c); };
   const Tensor in = alloc(h, w, IN_C, P), feat = alloc(h, w, FEAT, P);
   const Tensor d[3] = {alloc(h, w, DENSE_C, P), alloc(h, w, DENSE_C, P), alloc(h, w, DENSE_C, P)};
   const Tensor u1 = alloc(2 * h, 2 * w, FEAT, P), c1 = alloc(2 * h, 2 * w, FEAT, P);
   const Tensor u2 = alloc(4 * h, 4 * w, FEAT, P), c2 = alloc(4 * h, 4 * w, FEAT, P);
-  Tensor last = at((size_t)c2.p, F32, 4 * h, 4 * w, LAST_C, LAST_C);
+  Tensor last = at((size_t)c2.p, F32, 1, 4 * h, 4 * w, LAST_C);
   p->in = in, p->last = last;
 
   size_t slab = 0;
@@ -157,10 +138,8 @@ static std::unique_ptr<Plan> build_plan(rtd_esrgan* e, int h, int w) {
     Op op;
     op.kind = OP_CONV;
     ConvArgs& a = op.conv;
-    a = conv_args(x, y, e->weights.at(name), 3, 1, 1, act);
-    a.opts = &e->conv_opts;
-    if (res) { a.res = *res; a.res_mode = RES_PRE; }
-    slab = std::max(slab, conv_split_slab_bytes(a));
+    a = conv_args(x, y, e->filters.at(name), 3, 1, 1, act);
+    np::plan_conv(a, &e->conv_opts, res, RES_PRE, slab, name);
     op.stage = stage; op.stage_t = y;
     p->ops.push_back(op);
   };
@@ -192,30 +171,14 @@ static std::unique_ptr<Plan> build_plan(rtd_esrgan* e, int h, int w) {
   conv("conv_hr", c2, u2, ACT_LRELU, nullptr, "hr");
   conv("conv_last", u2, last, ACT_NONE, nullptr, "last");
 
-  p->slab_off = top;
-  p->slab_bytes = slab;
-  p->bytes = top + (slab + 255) / 256 * 256;
-  return p;
-}
-
-static Plan* get_plan(rtd_esrgan* e, int h, int w) {
-  auto it = e->plans.find({h, w});
-  if (it != e->plans.end()) return it->second.get();
-  Plan* p = (e->plans[{h, w}] = build_plan(e, h, w)).get();
+  p->seal(arena.top, slab);
   return p;
 }
 
 static void run_op(rtd_esrgan* e, const Plan* p, const Op& op, hipStream_t s) {
   char* base = (char*)e->arena.p;
   switch (op.kind) {
-    case OP_CONV: {
-      ConvArgs a = op.conv;
-      a.x = based(a.x, base), a.y = based(a.y, base);
-      if (a.res_mode != RES_NONE) a.res = based(a.res, base);
-      if (p->slab_bytes) { a.ws.slab = (float*)(base + p->slab_off); a.ws.slab_bytes = p->slab_bytes; }
-      launch_conv(a, s);
-      break;
-    }
+    case OP_CONV: np::run_conv(op.conv, base, *p, s); break;
     case OP_UPSAMPLE: launch_upsample2x(based(op.a, base), based(op.y, base), s); break;
     case OP_AXPBY: launch_axpby(0.2f, based(op.a, base), based(op.b, base), based(op.y, base), s); break;
     default: {
@@ -255,11 +218,13 @@ static void run(rtd_esrgan* e, int n, const uint8_t* const* frames, const int32_
   std::vector<Job> jobs;
   size_t need = 0;
   e->last_plan = nullptr;
-  if (e->plans.size() > 256) e->plans.clear();                    // (a plan is a host-side op list: cheap to rebuild)
+  // (the cache is trimmed here and not while the jobs are collected: they hold pointers to its plans)
+  if (e->plans.size() > 256) e->plans.clear();
   for (int i = 0; i < n; ++i) {
     const int W = rects[4 * i + 2] - rects[4 * i], H = rects[4 * i + 3] - rects[4 * i + 1];
     for (const eh::TileRect& t : eh::tile_rects(H, W, tile, pad)) {
-      Plan* p = get_plan(e, t.iy1 - t.iy0, t.ix1 - t.ix0);
+      const int h = t.iy1 - t.iy0, w = t.ix1 - t.ix0;
+      Plan* p = np::get_or_build(e->plans, std::make_pair(h, w), (size_t)-1, [&] { return build_plan(e, h, w); });
       need = std::max(need, p->bytes);
       jobs.push_back(Job{p, t, i});
     }
@@ -286,46 +251,20 @@ static void run(rtd_esrgan* e, int n, const uint8_t* const* frames, const int32_
   }
 }
 
-// Filters and biases through the upload path of the handle's precision: host fp32 rows [Npad][kcols] -> device, then conv_filter_convert
-// (common.h: the conversion rtd_op_conv and the detection engine use).  Two pools (filters, biases) and, on the pair engine, one
-// staging pool that is freed when every conversion has run: three allocations and one wait for the whole network.
+// The filters (net_plan.h: upload_filters): OIHW -> tap-major rows, conv_first's 3 input channels padded to the `in` tensor's 32 and
+// conv_last's 3 outputs to 32 rows; `x5 * 0.2 + x`: the 0.2 lives in conv5's filter and bias
 static void upload_weights(rtd_esrgan* e, const std::map<std::string, eh::HostTensor>& host, const std::vector<eh::ConvDesc>& table) {
-  struct Item { ConvFilter f; int cin_pad; size_t w_off, b_off; float scale; };
-  std::vector<Item> items;
-  size_t w_bytes = 0, b_bytes = 0;
-  for (const eh::ConvDesc& d : table) {
-    Item it;
-    it.cin_pad = d.cin == 3 ? IN_C : d.cin;
-    it.f = conv_filter_extents(e->P, d.cout == 3 ? LAST_C : d.cout, 9 * it.cin_pad);
-    const bool conv5 = d.name.size() > 6 && d.name.compare(d.name.size() - 6, 6, ".conv5") == 0;
-    it.scale = conv5 ? 0.2f : 1.f;                                // `x5 * 0.2 + x`: the 0.2 lives in conv5's filter and bias
-    it.w_off = w_bytes, it.b_off = b_bytes;
-    w_bytes += it.f.bytes();                                      // (= the bytes of its fp32 rows; multiples of 512: every filter stays 256-byte aligned)
-    b_bytes += (size_t)it.f.Npad * 4;
-    items.push_back(it);
-  }
-  auto dmalloc = [&](size_t bytes) { void* q = nullptr; HIP_CHECK(hipMalloc(&q, bytes)); e->allocs.push_back(q); return (char*)q; };
-  char* wpool = dmalloc(w_bytes);
-  char* bpool = dmalloc(b_bytes);
-  bk::OpScratch staging;
-  char* stage = e->P == F16X2 ? staging.get<char>(w_bytes) : wpool;
-  for (size_t i = 0; i < table.size(); ++i) {
+  std::vector<np::FilterSpec> specs;
+  for (const eh::ConvDesc& d : table) specs.push_back({d.name, conv_filter_extents(e->P, d.cout == 3 ? LAST_C : d.cout, 9 * (d.cin == 3 ? IN_C : d.cin))});
+  np::upload_filters(*e, specs, [&](size_t i, std::vector<float>& rows, std::vector<float>& bias) {
     const eh::ConvDesc& d = table[i];
-    ConvFilter& f = items[i].f;
-    const float scale = items[i].scale;
-    const std::vector<float> rows = eh::filter_rows(host.at(d.name + ".weight"), d.cout, d.cin, items[i].cin_pad, f.Npad, f.kcols(), scale);
-    std::vector<float> bias(f.Npad, 0.f);
+    const ConvFilter& f = specs[i].f;
+    const bool conv5 = d.name.size() > 6 && d.name.compare(d.name.size() - 6, 6, ".conv5") == 0;
+    const float scale = conv5 ? 0.2f : 1.f;
+    rows = eh::filter_rows(host.at(d.name + ".weight"), d.cout, d.cin, d.cin == 3 ? IN_C : d.cin, f.Npad, f.kcols(), scale);
     const eh::HostTensor& b = host.at(d.name + ".bias");
     for (int o = 0; o < d.cout; ++o) bias[o] = b.data[o] * scale;
-    f.bias = (float*)(bpool + items[i].b_off);
-    f.w = wpool + items[i].w_off;
-    float* dev_rows = (float*)(stage + items[i].w_off);
-    HIP_CHECK(hipMemcpy(f.bias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dev_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
-    conv_filter_convert(f, dev_rows, nullptr);
-    e->weights[d.name] = f;
-  }
-  HIP_CHECK(hipDeviceSynchronize());
+  });
 }
 
 }  // namespace esrgan
@@ -363,20 +302,13 @@ int rtd_esrgan_upscale(rtd_esrgan_handle e, int32_t n, const uint8_t* const* fra
   return guarded(e, [&] { run(e, n, frames_dev, frame_hw, rects, out_dev, out_cap, (hipStream_t)stream); });
 }
 
-int64_t rtd_esrgan_arena_bytes(rtd_esrgan_handle e) {
-  if (!e) return 0;
-  std::lock_guard<std::mutex> lk(e->mu);
-  return (int64_t)e->arena.cap;
-}
+int64_t rtd_esrgan_arena_bytes(rtd_esrgan_handle e) { return e ? e->arena_bytes() : 0; }
 
 const char* rtd_esrgan_last_error(rtd_esrgan_handle e) { return bk::last_error(e); }
 
 void rtd_esrgan_destroy(rtd_esrgan_handle e) {
   if (!e) return;
-  (void)hipSetDevice(e->device);
-  e->arena.release();                           // (hipFree waits for the device: nothing enqueued still uses the arena or the filters)
-  for (void* q : e->allocs) (void)hipFree(q);
-  (void)hipGetLastError();
+  e->release_device();
   delete e;
 }
 
@@ -402,13 +334,7 @@ int rtd_debug_esrgan_tensor(rtd_esrgan_handle e, const char* name, float* out, i
     hipStream_t s = e->last_stream;
     run_ingest(e, p, e->last_src, e->last_pitch, s);
     for (size_t i = 0; i < upto; ++i) run_op(e, p, p->ops[i], s);
-    t = based(t, (char*)e->arena.p);
-    bk::OpScratch sc;
-    float* f32 = sc.get<float>((size_t)numel);
-    if (t.dt == F16X2) launch_split_to_f32(t.p, t.ld, f32, t.c, t.pixels(), t.c, s);
-    else HIP_CHECK(hipMemcpy2DAsync(f32, (size_t)t.c * 4, t.p, (size_t)t.ld * 4, (size_t)t.c * 4, (size_t)t.pixels(), hipMemcpyDeviceToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(out, f32, (size_t)numel * 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
+    np::read_tensor(based(t, (char*)e->arena.p), t.pixels(), out, s);
   });
 }
 

@@ -1,5 +1,6 @@
 // esrgan_host.h - the pure host parts of the Real-ESRGAN x4 crop upscaler (esrgan.hip): config checks, the output layout, the tile
-// rectangles of RealESRGANer.tile_process, the weight blob's table and the list of RRDBNet's convolutions.  No HIP, no device: this
+// rectangles of RealESRGANer.tile_process and the list of RRDBNet's convolutions with the blob tensors they need (the blob itself:
+// weight_blob.h).  No HIP, no device: this
 // header compiles on its own (tools/esrgan_host_check.cpp runs it under -fsanitize=address,undefined).
 #pragma once
 #include <math.h>
@@ -12,12 +13,13 @@
 
 #include "../../include/rtdetr_mi355.h"
 #include "error.h"
+#include "weight_blob.h"
 
 namespace esrgan_host {
 
-inline void need(bool ok, int code, const std::string& msg) {   // (the plain message: callers match on it)
-  if (!ok) throw rtd::Error(code, msg);
-}
+using rtd::blob::HostTensor;   // the packed blob (weight_blob.h)
+using rtd::blob::need;
+using rtd::blob::parse_blob;
 
 constexpr int SCALE = 4;
 constexpr int MIN_SIDE = 8, MAX_SIDE = 4096, MAX_ONE_PASS_SIDE = 576, MAX_CROPS = 64;
@@ -76,51 +78,6 @@ inline std::vector<TileRect> tile_rects(int H, int W, int tile, int pad) {
   return out;
 }
 
-// ---- the weight blob (weights.pack_blob of the state dict: OIHW fp32 `.weight`, `.bias`)
-struct HostTensor {
-  const float* data = nullptr;
-  std::vector<int64_t> shape;
-  int64_t numel() const {
-    int64_t n = 1;
-    for (auto d : shape) n *= d;
-    return n;
-  }
-};
-inline void parse_blob(const char* b, size_t n, std::map<std::string, HostTensor>& out) {
-  need(b && n >= 12 && memcmp(b, "RTDW", 4) == 0, RTD_E_WEIGHTS, "weight blob: bad magic");
-  need(((uintptr_t)b & 3) == 0, RTD_E_WEIGHTS, "weight blob: not 4-byte aligned");
-  uint32_t ver, count;
-  memcpy(&ver, b + 4, 4);
-  memcpy(&count, b + 8, 4);
-  need(ver == 1, RTD_E_WEIGHTS, "weight blob: unsupported version");
-  size_t p = 12;
-  for (uint32_t i = 0; i < count; ++i) {
-    need(n - p >= 2, RTD_E_WEIGHTS, "weight blob: truncated table");
-    uint16_t nl;
-    memcpy(&nl, b + p, 2); p += 2;
-    need(n - p >= (size_t)nl + 4, RTD_E_WEIGHTS, "weight blob: truncated table");
-    const std::string name(b + p, nl); p += nl;
-    uint32_t nd;
-    memcpy(&nd, b + p, 4); p += 4;
-    need(nd <= 8 && n - p >= 4 * (size_t)nd + 16, RTD_E_WEIGHTS, "weight blob: truncated table");
-    HostTensor t;
-    uint64_t numel = 1;
-    for (uint32_t d = 0; d < nd; ++d) {
-      uint32_t v;
-      memcpy(&v, b + p, 4); p += 4;
-      t.shape.push_back(v);
-      numel *= v;
-      need(numel <= (uint64_t)1 << 40, RTD_E_WEIGHTS, "weight blob: bad tensor extent: " + name);
-    }
-    uint64_t off, nb;
-    memcpy(&off, b + p, 8); p += 8;
-    memcpy(&nb, b + p, 8); p += 8;
-    need(off % 4 == 0 && off <= n && nb <= n - off && nb == numel * 4, RTD_E_WEIGHTS, "weight blob: bad tensor extent: " + name);
-    t.data = (const float*)(b + off);
-    out[name] = t;
-  }
-}
-
 // ---- RRDBNet(3, 3, 64, B, 32, scale 4): its convolutions in execution order (all 3x3, stride 1, pad 1, with bias)
 struct ConvDesc {
   std::string name;   // state-dict prefix: `name`.weight [cout][cin][3][3], `name`.bias [cout]
@@ -149,16 +106,8 @@ inline void check_conv_tensors(const std::map<std::string, HostTensor>& host, co
   const std::vector<int64_t> ws{d.cout, d.cin, 3, 3}, bs{d.cout};
   need(w->second.shape == ws, RTD_E_WEIGHTS, "weight shape mismatch: " + d.name + ".weight");
   need(b->second.shape == bs, RTD_E_WEIGHTS, "bias shape mismatch: " + d.name + ".bias");
-  for (const auto* t : {&w->second, &b->second}) {
-    const std::string nm = d.name + (t == &w->second ? ".weight" : ".bias");
-    const int64_t n = t->numel();
-    for (int64_t i = 0; i < n; ++i) {
-      const float v = t->data[i];
-      need(isfinite(v), RTD_E_WEIGHTS, "weight blob: tensor " + nm + " holds a NaN or an infinity");
-      need(!pair || fabsf(v) <= 65504.f, RTD_E_WEIGHTS,
-           "weight blob: tensor " + nm + " reaches " + std::to_string(v) + ", beyond the fp16 pair format's range (65504): use precision fp32");
-    }
-  }
+  rtd::blob::check_values(d.name + ".weight", w->second, pair);
+  rtd::blob::check_values(d.name + ".bias", b->second, pair);
 }
 
 // OIHW fp32 -> the conv kernels' filter rows [npad][kcols]: k = tap * cin_pad + channel (tap-major, channel-minor), zero padded;

@@ -26,6 +26,7 @@
 #include "../../include/rtdetr_mi355.h"
 #include "../../include/rtdetr_mi355_test.h"
 #include "backend.h"
+#include "net_plan.h"
 #include "yolox_net_host.h"
 
 namespace yolox_net {
@@ -33,7 +34,11 @@ namespace yolox_net {
 using namespace rtd;
 namespace yh = yolox_net_host;
 namespace bk = rtd::backend;
+namespace np = rtd::netplan;
 using bk::guarded;
+using np::at;
+using np::based;
+using np::op_dtype;
 
 // ---------------------------------------------------------------------------------------------------------------- kernels
 // the store of one Focus output pixel: v[0..11] and zeros above into its 32-channel group, fp32 or hi + lo pairs.  yolox_focus and
@@ -286,17 +291,14 @@ static void launch_emit(const EmitArgs& a, hipStream_t s) {
 
 // ---------------------------------------------------------------------------------------------------------------- plan
 enum OpKind { OP_CONV, OP_UPSAMPLE, OP_SPP };
-// tensors of an op hold their byte OFFSET inside the arena in `p`; run() adds the arena's base (the arena may be replaced by a larger one
-// between calls, the plans stay)
+// (tensors of an op are arena offsets: net_plan.h)
 struct Op {
   int kind = OP_CONV;
   ConvArgs conv;          // OP_CONV (x, y, res as offsets)
   Tensor a, y;            // OP_UPSAMPLE: a -> y; OP_SPP: a = slice 0 of the concat buffer
 };
-struct Plan {
+struct Plan : np::PlanBase {
   int n = 0, h = 0, w = 0;
-  size_t bytes = 0;       // arena bytes, the split-K workspace included
-  size_t slab_off = 0, slab_bytes = 0;
   Tensor in;              // the Focus output
   Tensor cls_rows[yh::LEVELS], regobj_rows[yh::LEVELS];
   std::vector<Op> ops;
@@ -305,34 +307,13 @@ struct Plan {
 
 }  // namespace yolox_net
 
-struct rtd_yolox_net : rtd::backend::Base {
+struct rtd_yolox_net : rtd::netplan::NetBase {
   rtd_yolox_net_config cfg;
-  int P = rtd::F16X2;
-  std::map<std::string, rtd::ConvFilter> weights;
-  std::vector<void*> allocs;
   std::map<std::tuple<int, int, int>, std::unique_ptr<yolox_net::Plan>> plans;
-  rtd::backend::DevBuf arena;   // holds the largest plan seen (a repeated shape allocates nothing)
-  rtd::ConvOpts conv_opts;
   yolox_net::Plan* last_plan = nullptr;   // rtd_debug_yolox_tensor reads its stages
-  hipStream_t last_stream = nullptr;
 };
 
 namespace yolox_net {
-
-static Tensor at(size_t off, int dt, int n, int h, int w, int c) {
-  Tensor t;
-  t.p = (void*)off; t.dt = dt; t.n = n; t.h = h; t.w = w; t.c = c; t.ld = c; t.bstride = (int64_t)h * w * c;
-  return t;
-}
-static Tensor based(Tensor t, char* base) {
-  t.p = base + (size_t)t.p;
-  return t;
-}
-static ConvArgs based(ConvArgs a, char* base) {
-  a.x = based(a.x, base), a.y = based(a.y, base);
-  if (a.res_mode != RES_NONE) a.res = based(a.res, base);
-  return a;
-}
 
 // One pass over the network.  Named stage outputs and everything a later layer reads live in the persistent part of the arena; a CSP
 // layer's and a head branch's temporaries come from a scratch region at the arena's start that every such unit uses again.  The scratch
@@ -341,28 +322,20 @@ struct Builder {
   rtd_yolox_net* e;
   Plan* p;
   int n, P;
-  size_t scratch, top = 0, s_top = 0, s_max = 0, slab = 0;
+  np::Arena keep;            // the persistent part: it starts where the scratch region ends
+  np::Arena scratch;         // reset by every unit that uses it
+  size_t s_max = 0, slab = 0;
 
-  static size_t room(int n, int h, int w, int c) { return ((size_t)n * h * w * c * 4 + 255) / 256 * 256; }
-  Tensor alloc(int h, int w, int c, int dt) { const size_t off = scratch + top; top += room(n, h, w, c); return at(off, dt, n, h, w, c); }
-  Tensor salloc(int h, int w, int c) { const size_t off = s_top; s_top += room(n, h, w, c); s_max = std::max(s_max, s_top); return at(off, P, n, h, w, c); }
+  Tensor alloc(int h, int w, int c, int dt) { return keep.tensor(dt, n, h, w, c); }
+  Tensor salloc(int h, int w, int c) { const Tensor t = scratch.tensor(P, n, h, w, c); s_max = std::max(s_max, scratch.top); return t; }
   void stage(const std::string& name, const Tensor& t) { p->stages[name] = t; }
 
   void conv(const yh::ConvDesc& d, const Tensor& x, const Tensor& y, int act, const Tensor* res) {
     Op op;
     op.kind = OP_CONV;
     ConvArgs& a = op.conv;
-    a = conv_args(x, y, e->weights.at(d.name), d.k, d.stride, (d.k - 1) / 2, act);
-    a.opts = &e->conv_opts;
-    if (res) { a.res = *res; a.res_mode = RES_POST; }
-    // the launchers' own checks, on addresses as aligned as the arena's (offset 0 would read as a null pointer)
-    const ConvArgs probe = based(a, (char*)(uintptr_t)4096);
-    try {
-      (void)conv_predict(probe, nullptr);
-    } catch (const Error& er) {
-      throw Error(RTD_E_INVALID, d.name + " at " + std::to_string(n) + " x " + std::to_string(x.h) + " x " + std::to_string(x.w) + ": " + er.what());
-    }
-    slab = std::max(slab, conv_split_slab_bytes(probe));
+    a = conv_args(x, y, e->filters.at(d.name), d.k, d.stride, (d.k - 1) / 2, act);
+    np::plan_conv(a, &e->conv_opts, res, RES_POST, slab, d.name + " at " + std::to_string(n) + " x " + std::to_string(x.h) + " x " + std::to_string(x.w));
     p->ops.push_back(op);
   }
 };
@@ -383,7 +356,7 @@ struct Net {
   // CSPLayer: y = conv3(cat(m(conv1(x)), conv2(x))), m = n Bottlenecks (1x1, then 3x3 with the shortcut as its RES_POST residual)
   void csp(const std::string& tail, const Tensor& x, const Tensor& y, int n, bool shortcut) {
     const int h = y.c / 2;
-    b.s_top = 0;
+    b.scratch.top = 0;
     const Tensor cat = b.salloc(x.h, x.w, 2 * h), A = b.salloc(x.h, x.w, h), B = b.salloc(x.h, x.w, h), T = b.salloc(x.h, x.w, h);
     base_conv(tail + ".conv1", x, A);
     base_conv(tail + ".conv2", x, cat.slice_c(h, h));
@@ -461,7 +434,7 @@ struct Net {
       const Tensor st = b.alloc(lh, lw, hc, P), cf = b.alloc(lh, lw, hc, P), rf = b.alloc(lh, lw, hc, P);
       p->cls_rows[l] = b.alloc(lh, lw, cls_c, F32);
       p->regobj_rows[l] = b.alloc(lh, lw, ro_c, F32);
-      b.s_top = 0;
+      b.scratch.top = 0;
       const Tensor t = b.salloc(lh, lw, hc);
       base_conv("stems." + s, lv[l], st);
       base_conv("cls_convs." + s + ".0", st, t);
@@ -484,35 +457,23 @@ static std::unique_ptr<Plan> build_plan(rtd_yolox_net* e, int n, int h, int w) {
   for (int pass = 0; pass < 2; ++pass) {
     p = std::make_unique<Plan>();
     p->n = n, p->h = h, p->w = w;
-    Builder b{e, p.get(), n, e->P, scratch};
+    Builder b{e, p.get(), n, e->P, np::Arena{scratch}};
     Net net{b, table};
     net.build(h, w);
     scratch = b.s_max;
-    p->slab_off = b.scratch + b.top;
-    p->slab_bytes = b.slab;
-    p->bytes = p->slab_off + (b.slab + 255) / 256 * 256;
+    p->seal(b.keep.top, b.slab);
   }
   return p;
 }
 
 static Plan* get_plan(rtd_yolox_net* e, int n, int h, int w) {
-  const auto key = std::make_tuple(n, h, w);
-  auto it = e->plans.find(key);
-  if (it != e->plans.end()) return it->second.get();
-  if (e->plans.size() > 64) e->plans.clear();                     // (a plan is a host-side op list: cheap to rebuild)
-  e->last_plan = nullptr;
-  return (e->plans[key] = build_plan(e, n, h, w)).get();
+  return np::get_or_build(e->plans, std::make_tuple(n, h, w), 64, [&] { return build_plan(e, n, h, w); });
 }
 
 static void run_op(rtd_yolox_net* e, const Plan* p, const Op& op, hipStream_t s) {
   char* base = (char*)e->arena.p;
   switch (op.kind) {
-    case OP_CONV: {
-      ConvArgs a = based(op.conv, base);
-      if (p->slab_bytes) { a.ws.slab = (float*)(base + p->slab_off); a.ws.slab_bytes = p->slab_bytes; }
-      launch_conv(a, s);
-      break;
-    }
+    case OP_CONV: np::run_conv(op.conv, base, *p, s); break;
     case OP_UPSAMPLE: launch_upsample2x(based(op.a, base), based(op.y, base), s); break;
     default: launch_spp(based(op.a, base), s);
   }
@@ -534,8 +495,8 @@ static EmitArgs emit_args(const float* const cls[3], const float* const regobj[3
 template <typename Fill>
 static void run_plan(rtd_yolox_net* e, int n, int in_h, int in_w, float* pred, hipStream_t s, Fill&& fill) {
   HIP_CHECK(hipSetDevice(e->device));
+  e->last_plan = nullptr;                                          // (get_plan may empty the cache it points into)
   Plan* p = get_plan(e, n, in_h, in_w);                            // (a shape the conv launchers refuse throws here)
-  e->last_plan = nullptr;
   e->arena.reserve(p->bytes);
   char* base = (char*)e->arena.p;
   fill((void*)(base + (size_t)p->in.p));
@@ -556,51 +517,19 @@ static void run_frames(rtd_yolox_net* e, int n, const uint8_t* const* frames, co
   run_plan(e, n, in_h, in_w, pred, s, [&](void* focus) { launch_focus_u8(e->P, frames, frame_hw, focus, n, in_h, in_w, s); });
 }
 
-// Filters and biases through the upload path of the handle's precision: the blob's rows [cout][k k cin] -> zero-padded fp32 rows
-// [Npad][kcols] on the device, then conv_filter_convert (common.h).  Two pools (filters, biases) and, on the pair engine, one staging
-// pool that is freed when every conversion has run: three allocations and one wait for the whole network.
+// The filters (net_plan.h: upload_filters): the blob's rows [cout][k k cin] are launch_conv's filter rows as they are
 static void upload_weights(rtd_yolox_net* e, const std::map<std::string, yh::HostTensor>& host, const std::vector<yh::ConvDesc>& table) {
-  struct Item { ConvFilter f; size_t w_off, b_off; };
-  std::vector<Item> items;
-  size_t w_bytes = 0, b_bytes = 0;
-  for (const yh::ConvDesc& d : table) {
-    Item it;
-    it.f = conv_filter_extents(e->P, d.cout, d.k * d.k * d.cin);
-    it.w_off = w_bytes, it.b_off = b_bytes;
-    w_bytes += ((size_t)it.f.Npad * it.f.kcols() * 4 + 255) / 256 * 256;   // (>= f.bytes(): the fp32 rows are staged at the same offsets)
-    b_bytes += (size_t)it.f.Npad * 4;
-    items.push_back(it);
-  }
-  auto dmalloc = [&](size_t bytes) { void* q = nullptr; HIP_CHECK(hipMalloc(&q, bytes)); e->allocs.push_back(q); return (char*)q; };
-  char* wpool = dmalloc(w_bytes);
-  char* bpool = dmalloc(b_bytes);
-  bk::OpScratch staging;
-  char* stage = e->P == F16X2 ? staging.get<char>(w_bytes) : wpool;
-  for (size_t i = 0; i < table.size(); ++i) {
-    const yh::ConvDesc& d = table[i];
-    ConvFilter& f = items[i].f;
-    const std::vector<float> rows = conv_filter_rows(f, {{host.at(d.name + ".weight").data, f.K}});
-    std::vector<float> bias(f.Npad, 0.f);
-    memcpy(bias.data(), host.at(d.name + ".bias").data, (size_t)d.cout * 4);
-    f.bias = (float*)(bpool + items[i].b_off);
-    f.w = wpool + items[i].w_off;
-    float* dev_rows = (float*)(stage + items[i].w_off);
-    HIP_CHECK(hipMemcpy(f.bias, bias.data(), bias.size() * 4, hipMemcpyHostToDevice));
-    HIP_CHECK(hipMemcpy(dev_rows, rows.data(), rows.size() * 4, hipMemcpyHostToDevice));
-    conv_filter_convert(f, dev_rows, nullptr);
-    e->weights[d.name] = f;
-  }
-  HIP_CHECK(hipDeviceSynchronize());
+  std::vector<np::FilterSpec> specs;
+  for (const yh::ConvDesc& d : table) specs.push_back({d.name, conv_filter_extents(e->P, d.cout, d.k * d.k * d.cin)});
+  np::upload_filters(*e, specs, [&](size_t i, std::vector<float>& rows, std::vector<float>& bias) {
+    const ConvFilter& f = specs[i].f;
+    rows = conv_filter_rows(f, {{host.at(table[i].name + ".weight").data, f.K}});
+    memcpy(bias.data(), host.at(table[i].name + ".bias").data, (size_t)f.N * 4);
+  });
 }
 
 template <typename F>
-static int op_guard(F&& f) {
-  return bk::caught(bk::create_error<rtd_yolox_net>(), [&] { f(); HIP_CHECK(hipDeviceSynchronize()); });
-}
-static int op_dtype(int dtype) {
-  RTD_CHECK(dtype == F32 || dtype == F16X2, RTD_E_INVALID, "dtype must be 1 (fp32) or 4 (F16X2)");
-  return dtype;
-}
+static int op_guard(F&& f) { return np::op_guard<rtd_yolox_net>(f); }
 
 }  // namespace yolox_net
 
@@ -635,20 +564,13 @@ int rtd_yolox_net_run_frames(rtd_yolox_net_handle e, int32_t n, const uint8_t* c
   return guarded(e, [&] { run_frames(e, n, frames_dev, frame_hw, in_h, in_w, pred_dev, (hipStream_t)stream); });
 }
 
-int64_t rtd_yolox_net_arena_bytes(rtd_yolox_net_handle e) {
-  if (!e) return 0;
-  std::lock_guard<std::mutex> lk(e->mu);
-  return (int64_t)e->arena.cap;
-}
+int64_t rtd_yolox_net_arena_bytes(rtd_yolox_net_handle e) { return e ? e->arena_bytes() : 0; }
 
 const char* rtd_yolox_net_last_error(rtd_yolox_net_handle e) { return bk::last_error(e); }
 
 void rtd_yolox_net_destroy(rtd_yolox_net_handle e) {
   if (!e) return;
-  (void)hipSetDevice(e->device);
-  e->arena.release();                           // (hipFree waits for the device: nothing enqueued still uses the arena or the filters)
-  for (void* q : e->allocs) (void)hipFree(q);
-  (void)hipGetLastError();
+  e->release_device();
   delete e;
 }
 
@@ -666,13 +588,7 @@ int rtd_debug_yolox_tensor(rtd_yolox_net_handle e, const char* name, float* out,
     RTD_CHECK(capacity >= numel, RTD_E_INVALID, "debug tensor: output capacity too small");
     HIP_CHECK(hipSetDevice(e->device));
     hipStream_t s = e->last_stream;
-    t = based(t, (char*)e->arena.p);
-    bk::OpScratch sc;
-    float* f32 = sc.get<float>((size_t)numel);
-    if (t.dt == F16X2) launch_split_to_f32(t.p, t.ld, f32, t.c, t.pixels(), t.c, s);
-    else HIP_CHECK(hipMemcpy2DAsync(f32, (size_t)t.c * 4, t.p, (size_t)t.ld * 4, (size_t)t.c * 4, (size_t)t.pixels(), hipMemcpyDeviceToDevice, s));
-    HIP_CHECK(hipMemcpyAsync(out, f32, (size_t)numel * 4, hipMemcpyDeviceToHost, s));
-    HIP_CHECK(hipStreamSynchronize(s));
+    np::read_tensor(based(t, (char*)e->arena.p), t.pixels(), out, s);
   });
 }
 

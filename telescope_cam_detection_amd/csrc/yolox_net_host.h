@@ -12,14 +12,14 @@
 
 #include "../../include/rtdetr_mi355.h"
 #include "error.h"
-#include "esrgan_host.h"   // the packed blob: HostTensor, parse_blob
+#include "weight_blob.h"   // the packed blob: HostTensor, parse_blob, check_values
 #include "yolox_post_host.h"   // anchors(): the input sizes served
 
 namespace yolox_net_host {
 
-using esrgan_host::HostTensor;
-using esrgan_host::need;
-using esrgan_host::parse_blob;
+using rtd::blob::HostTensor;
+using rtd::blob::need;
+using rtd::blob::parse_blob;
 
 constexpr int MAX_BATCH = 64, MAX_CLASSES = 1024, MAX_DEPTH = 8, MAX_BASE = 128;
 constexpr int FOCUS_C = 32;              // the Focus output: 12 channels in a whole 32-channel group, zeros above
@@ -194,16 +194,8 @@ inline void check_conv_tensors(const std::map<std::string, HostTensor>& host, co
   const std::vector<int64_t> ws{d.cout, d.k, d.k, d.cin}, bs{d.cout};
   need(w->second.shape == ws, RTD_E_INVALID, "weight shape mismatch: " + d.name + ".weight (not this variant's table)");
   need(b->second.shape == bs, RTD_E_INVALID, "bias shape mismatch: " + d.name + ".bias (not this variant's table)");
-  for (const auto* t : {&w->second, &b->second}) {
-    const std::string nm = d.name + (t == &w->second ? ".weight" : ".bias");
-    const int64_t n = t->numel();
-    for (int64_t i = 0; i < n; ++i) {
-      const float v = t->data[i];
-      need(isfinite(v), RTD_E_WEIGHTS, "weight blob: tensor " + nm + " holds a NaN or an infinity");
-      need(!pair || fabsf(v) <= 65504.f, RTD_E_WEIGHTS,
-           "weight blob: tensor " + nm + " reaches " + std::to_string(v) + ", beyond the fp16 pair format's range (65504): use precision fp32");
-    }
-  }
+  rtd::blob::check_values(d.name + ".weight", w->second, pair);
+  rtd::blob::check_values(d.name + ".bias", b->second, pair);
 }
 
 // the SPP launch: one workgroup per (image, tile, chunk of SPP_CH channels)
