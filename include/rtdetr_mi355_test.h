@@ -289,6 +289,15 @@ int rtd_op_yolox_head_emit(const float* const cls[3], const float* const regobj[
  * `cls_feat_<l>`, `reg_feat_<l>`, `cls_rows_<l>`, `regobj_rows_<l>`.  out may be NULL to ask for the shape. */
 int rtd_debug_yolox_tensor(rtd_yolox_net_handle y, const char* name, float* out, int64_t capacity, int64_t shape[4]);
 
+/* the conv launches of a handle's LAST plan (the last successful run / forward / upscale: its last tile), in execution order, as text:
+ * one line per launch, `name dtype B H W Cin Cout k stride pad act res_mode out_f32 ldx ldy ldres key S grid` - geometry (H, W: the
+ * input's), pixel strides and epilogue as the plan holds them, key / S / grid from the function rtd_debug_conv_choice_views answers from,
+ * under the handle's own options.  name: the conv table's (YOLOX, ESRGAN) or the launch's index (EVA).  Host arithmetic only.  out may
+ * be NULL to ask for the size (*needed, with the terminating 0).  RTD_E_STATE before the first successful call. */
+int rtd_debug_yolox_plan_convs(rtd_yolox_net_handle y, char* out, int64_t capacity, int64_t* needed);
+int rtd_debug_eva_plan_convs(rtd_eva_handle e, char* out, int64_t capacity, int64_t* needed);
+int rtd_debug_esrgan_plan_convs(rtd_esrgan_handle e, char* out, int64_t capacity, int64_t* needed);
+
 #ifdef __cplusplus
 }
 #endif

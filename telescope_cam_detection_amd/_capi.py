@@ -175,6 +175,7 @@ TEST_EXPORTS = [
     "rtd_op_eva_patchify", "rtd_op_eva_rope", "rtd_op_eva_layernorm", "rtd_op_eva_attention", "rtd_debug_eva_tensor",
     "rtd_op_yolox_focus", "rtd_op_yolox_focus_u8", "rtd_op_yolox_spp", "rtd_op_yolox_head_emit", "rtd_debug_yolox_tensor",
     "rtd_op_conv_views", "rtd_debug_conv_choice_views",
+    "rtd_debug_yolox_plan_convs", "rtd_debug_eva_plan_convs", "rtd_debug_esrgan_plan_convs",
 ]
 CONV_INFO_FIELDS = ("family", "stages", "bn", "mt", "bm", "smallc", "wsq", "sx", "cog", "S", "grid", "ntn")   # info[12] of the conv-choice calls
 
@@ -398,6 +399,9 @@ def lib() -> C.CDLL:
     if hasattr(L, "rtd_yolox_net_run_frames"):    # (absent from older builds loaded through RTD_LIB_PATH)
         L.rtd_yolox_net_run_frames.argtypes = [vp, i32, C.POINTER(vp), C.POINTER(i32), i32, i32, vp, vp]
         L.rtd_op_yolox_focus_u8.argtypes = [i32, C.POINTER(vp), C.POINTER(i32), i32, i32, i32, vp]
+    if hasattr(L, "rtd_debug_yolox_plan_convs"):  # (absent from older builds loaded through RTD_LIB_PATH)
+        for fn in (L.rtd_debug_yolox_plan_convs, L.rtd_debug_eva_plan_convs, L.rtd_debug_esrgan_plan_convs):
+            fn.argtypes = [vp, C.c_char_p, i64, C.POINTER(i64)]
     _lib = L
     return L
 
@@ -432,6 +436,26 @@ def conv_choice_views(dtype: int, B: int, H: int, W: int, Cin: int, Cout: int, l
 def last_conv():
     """What this thread's last launch_conv / launch_conv_pool launched (rtd_debug_last_conv); None before the first."""
     return _conv_report(lib().rtd_debug_last_conv)
+
+
+PLAN_CONV_FIELDS = ("dtype", "B", "H", "W", "Cin", "Cout", "k", "stride", "pad", "act", "res_mode", "out_f32", "ldx", "ldy", "ldres")
+
+
+def plan_convs(prefix: str, handle) -> list:
+    """The conv launches of a network handle's last plan (rtd_debug_<yolox|eva|esrgan>_plan_convs; prefix: "yolox", "eva" or "esrgan"),
+    in execution order: dicts of name, PLAN_CONV_FIELDS (codes as the C ABI has them), key, S and grid.  Raises RtdError before the first run."""
+    call = getattr(lib(), f"rtd_debug_{prefix}_plan_convs")
+    need = C.c_int64(0)
+    rc = call(handle, None, 0, C.byref(need))
+    buf = C.create_string_buffer(max(int(need.value), 1))
+    rc = rc or call(handle, buf, need.value, None)
+    if rc != RTD_OK:
+        raise RtdError(rc, f"rtd_debug_{prefix}_plan_convs failed")
+    out = []
+    for line in buf.value.decode().splitlines():
+        w = line.split()
+        out.append(dict(zip(PLAN_CONV_FIELDS, (int(v) for v in w[1:16])), name=w[0], key=w[16], S=int(w[17]), grid=int(w[18])))
+    return out
 
 
 def conv_instantiations() -> list:

@@ -699,6 +699,13 @@ int rtd_debug_eva_tensor(rtd_eva_handle e, const char* name, float* out, int64_t
   });
 }
 
+int rtd_debug_eva_plan_convs(rtd_eva_handle e, char* out, int64_t capacity, int64_t* needed) {
+  return guarded(e, [&] {
+    RTD_CHECK(e->last_plan, RTD_E_STATE, "no successful rtd_eva_forward call yet");
+    np::text_out(np::plan_convs_text(*e->last_plan, OP_CONV, {}), out, capacity, needed);
+  });
+}
+
 // ---- kernel-level test entry points (include/rtdetr_mi355_test.h)
 int rtd_op_eva_patchify(int dtype, const float* x, void* rows, int n, int img, int patch) {
   return op_guard([&] {

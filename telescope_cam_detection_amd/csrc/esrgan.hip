@@ -338,4 +338,13 @@ int rtd_debug_esrgan_tensor(rtd_esrgan_handle e, const char* name, float* out, i
   });
 }
 
+int rtd_debug_esrgan_plan_convs(rtd_esrgan_handle e, char* out, int64_t capacity, int64_t* needed) {
+  return guarded(e, [&] {
+    RTD_CHECK(e->last_plan, RTD_E_STATE, "no successful rtd_esrgan_upscale call yet");
+    std::vector<std::string> names;      // (build_plan's convs follow the table's order)
+    for (const eh::ConvDesc& d : eh::conv_table(e->cfg.num_block)) names.push_back(d.name);
+    np::text_out(np::plan_convs_text(*e->last_plan, OP_CONV, names), out, capacity, needed);
+  });
+}
+
 }  // extern "C"

@@ -3,6 +3,8 @@
 // memory, the filter upload and the read-back of a debug tensor.  A back end keeps its own Op struct and op kinds, its network walk, its
 // `run` and its stage bookkeeping: nothing here interprets an op list.  Host only.
 #pragma once
+#include <string.h>
+
 #include <map>
 #include <memory>
 #include <string>
@@ -162,6 +164,39 @@ inline void read_tensor(const Tensor& t, int64_t rows, float* out, hipStream_t s
   else HIP_CHECK(hipMemcpy2DAsync(f32, (size_t)t.c * 4, t.p, (size_t)t.ld * 4, (size_t)t.c * 4, (size_t)rows, hipMemcpyDeviceToDevice, s));
   HIP_CHECK(hipMemcpyAsync(out, f32, (size_t)numel * 4, hipMemcpyDeviceToHost, s));
   HIP_CHECK(hipStreamSynchronize(s));
+}
+
+// ---- tests only (rtd_debug_yolox_plan_convs, rtd_debug_eva_plan_convs, rtd_debug_esrgan_plan_convs): the conv launches of a plan in
+// execution order, one text line each -
+//   name dtype B H W Cin Cout k stride pad act res_mode out_f32 ldx ldy ldres key S grid
+// geometry, pixel strides and epilogue as the plan's ConvArgs hold them (H, W: the input's; out_f32: fp32 rows out of other operands;
+// ldres 0 without a residual), key / S / grid from conv_predict on the probe addresses plan_conv used - the function
+// rtd_debug_conv_choice_views answers from.  names: one per OP_CONV in order, or empty (the line's name is then the launch's index).
+template <typename Plan>
+std::string plan_convs_text(const Plan& p, int conv_kind, const std::vector<std::string>& names) {
+  std::string out;
+  size_t i = 0;
+  for (const auto& op : p.ops) {
+    if (op.kind != conv_kind) continue;
+    const ConvArgs& a = op.conv;
+    RTD_CHECK(names.empty() || i < names.size(), RTD_E_STATE, "plan convs: the plan has more convs than its table has names");
+    const ConvChoiceReport r = conv_predict(based(a, (char*)(uintptr_t)4096), nullptr);
+    const int v[15] = {a.x.dt, a.x.n, a.x.h, a.x.w, a.x.c, a.y.c, a.KH, a.stride, a.pad, a.act, a.res_mode, a.y.dt == F32 && a.x.dt != F32,
+                       (int)a.x.ld, (int)a.y.ld, a.res_mode != RES_NONE ? (int)a.res.ld : 0};
+    out += names.empty() ? std::to_string(i) : names[i];
+    for (int k = 0; k < 15; ++k) out += " " + std::to_string(v[k]);
+    out += std::string(" ") + r.key + " " + std::to_string(r.S) + " " + std::to_string(r.grid) + "\n";
+    ++i;
+  }
+  RTD_CHECK(names.empty() || i == names.size(), RTD_E_STATE, "plan convs: the table has names the plan did not use");
+  return out;
+}
+// the size-then-fill convention of rtd_debug_conv_instantiations
+inline void text_out(const std::string& text, char* out, int64_t capacity, int64_t* needed) {
+  if (needed) *needed = (int64_t)text.size() + 1;
+  if (!out) return;
+  RTD_CHECK(capacity > (int64_t)text.size(), RTD_E_INVALID, "text output: buffer too small");
+  memcpy(out, text.c_str(), text.size() + 1);
 }
 
 // the kernel-level test entry points' guard: the message goes where rtd_X_last_error(NULL) of handle type H reads it, and the call

@@ -592,6 +592,15 @@ int rtd_debug_yolox_tensor(rtd_yolox_net_handle e, const char* name, float* out,
   });
 }
 
+int rtd_debug_yolox_plan_convs(rtd_yolox_net_handle e, char* out, int64_t capacity, int64_t* needed) {
+  return guarded(e, [&] {
+    RTD_CHECK(e->last_plan, RTD_E_STATE, "no successful rtd_yolox_net_run call yet");
+    std::vector<std::string> names;      // (Net::take walks the same table: the i-th conv of a plan is its i-th entry)
+    for (const yh::ConvDesc& d : yh::conv_table(e->cfg.base_channels, e->cfg.depth, e->cfg.num_classes)) names.push_back(d.name);
+    np::text_out(np::plan_convs_text(*e->last_plan, OP_CONV, names), out, capacity, needed);
+  });
+}
+
 int rtd_op_yolox_focus(int dtype, const float* x, void* y, int n, int h, int w) {
   return op_guard([&] {
     RTD_CHECK(x && y && n >= 1 && n <= yh::MAX_BATCH && h >= 2 && w >= 2 && h % 2 == 0 && w % 2 == 0 && h <= 16384 && w <= 16384, RTD_E_INVALID,

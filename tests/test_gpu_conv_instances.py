@@ -15,8 +15,8 @@ from tests.conv_cases import CASES
 
 pytestmark = pytest.mark.gpu
 
-ACT_FN = {"none": lambda t: t, "relu": F.relu, "silu": F.silu, "gelu": F.gelu}
-ACT_CODE = {"none": 0, "relu": 1, "silu": 2, "gelu": 3}
+ACT_FN = {"none": lambda t: t, "relu": F.relu, "silu": F.silu, "gelu": F.gelu, "lrelu": lambda t: F.leaky_relu(t, 0.2)}
+ACT_CODE = {"none": 0, "relu": 1, "silu": 2, "gelu": 3, "lrelu": 4}
 TORCH_DT = {"bf16": torch.bfloat16, "f32": torch.float32}
 GUARD_PIXELS = 256            # the tallest tile of any conv kernel (conv_igemm_wsq_kernel<8, 8>: 16 * (8 + 8) pixels)
 SENTINEL = 0x5A5A
