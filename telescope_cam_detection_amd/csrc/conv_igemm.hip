@@ -82,7 +82,7 @@ __device__ __forceinline__ void prefetch_share(const ConvK& a, unsigned block, u
 // it was 4.5 us of a 20 us launch (in-kernel s_memtime stamps, EXPERIMENTS.md "Timing probes")
 template <int A> struct ActC { static constexpr int value = A; };
 template <int ACT> __device__ __forceinline__ float act_c(float v) {
-  if (ACT == ACT_RELU) return fmaxf(v, 0.f);
+  if (ACT == ACT_RELU) return (v <= 0.f) ? 0.f : v;   // not fmaxf: a NaN stays a NaN (split2)
   if (ACT == ACT_SILU) return v / (1.f + __expf(-v));
   if (ACT == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
   if (ACT == ACT_LRELU) return v >= 0.f ? v : v * 0.2f;
@@ -98,7 +98,7 @@ template <typename F> __device__ __forceinline__ void dispatch_act(int act, F&& 
   }
 }
 __device__ __forceinline__ float act_fn(float v, int act) {
-  if (act == ACT_RELU) return fmaxf(v, 0.f);
+  if (act == ACT_RELU) return (v <= 0.f) ? 0.f : v;
   if (act == ACT_SILU) return v / (1.f + __expf(-v));
   if (act == ACT_GELU) return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
   if (act == ACT_LRELU) return v >= 0.f ? v : v * 0.2f;
@@ -1869,7 +1869,7 @@ __global__ __launch_bounds__(512, 2) void conv1x1_sx_kernel(const ConvK a, unsig
 #pragma unroll
           for (int e = 0; e < 4; ++e) {
             float v = c[e] + b1v[e];
-            if (a.next_act == ACT_RELU) v = fmaxf(v, 0.f);
+            if (a.next_act == ACT_RELU) v = (v <= 0.f) ? 0.f : v;
             sp16 hi, lo;
             split2(v, hi, lo);
             vh[e] = hi; vl[e] = lo;

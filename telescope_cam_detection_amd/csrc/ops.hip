@@ -1410,7 +1410,7 @@ __global__ __launch_bounds__(256) void stem0_u8_kernel(const uint8_t* const* __r
 #pragma unroll
       for (int e = 0; e < 4; ++e) {
         float v = acc[4 * q + e] + bv[e];
-        if (act == ACT_RELU) v = fmaxf(v, 0.f);
+        if (act == ACT_RELU) v = (v <= 0.f) ? 0.f : v;   // not fmaxf: a NaN stays a NaN
         else if (act == ACT_SILU) v = v / (1.f + __expf(-v));
         if constexpr (SPLIT) { sp16 hh, ll; split2(v, hh, ll); o[e] = hh; ol[e] = ll; }
         else o[e] = (E)v;

@@ -12,10 +12,10 @@ import torch.nn.functional as F
 
 from telescope_cam_detection_amd import _capi
 from tests.conv_cases import CASES
+from tests.conv_reference import ACT_FN, conv_ref, epilogue_ref, pooled_ref  # noqa: F401 (the other conv tests import them from here)
 
 pytestmark = pytest.mark.gpu
 
-ACT_FN = {"none": lambda t: t, "relu": F.relu, "silu": F.silu, "gelu": F.gelu, "lrelu": lambda t: F.leaky_relu(t, 0.2)}
 ACT_CODE = {"none": 0, "relu": 1, "silu": 2, "gelu": 3, "lrelu": 4}
 TORCH_DT = {"bf16": torch.bfloat16, "f32": torch.float32}
 GUARD_PIXELS = 256            # the tallest tile of any conv kernel (conv_igemm_wsq_kernel<8, 8>: 16 * (8 + 8) pixels)
@@ -93,41 +93,14 @@ class Guarded:
     def bits(self):
         return self.raw(self.view).cpu().numpy().copy()
 
-    def values(self):
-        """fp64 [B, H, W, C] on the host; asserts the guards and that every element was written and is finite."""
+    def values(self, finite=True):
+        """fp64 [B, H, W, C] on the host; asserts the guards and that every element was written and is finite (finite=False: the
+        caller holds the non-finite elements to a reference of its own)."""
         assert self.guards_intact(), "a guard band was written"
         v = self.view.cpu()
         v = pair_values(v) if self.kind == "pair" else v.float()
-        assert torch.isfinite(v).all(), "unwritten or non-finite output elements"
+        assert not finite or torch.isfinite(v).all(), "unwritten or non-finite output elements"
         return v.double()
-
-
-def conv_ref(xv, wmat, bias, k, pad, x2v=None, stride=1, x_up2=0):
-    """fp64 [B, OH, OW, N]: unfold + matmul.  xv [B, H, W, Cin], wmat [N, k*k*Cin (+ C2)] with tap-major / channel-minor columns.
-    x_up2: xv is read through a nearest 2x upsampling (the seen values, repeated)."""
-    if x_up2:
-        xv = xv.repeat_interleave(2, dim=1).repeat_interleave(2, dim=2)
-    B, H, W, Cin = xv.shape
-    N = wmat.shape[0]
-    if k == 1 and stride == 1:
-        cols = xv.reshape(B, H * W, Cin).double()
-        OH, OW = H, W
-    else:
-        OH, OW = (H + 2 * pad - k) // stride + 1, (W + 2 * pad - k) // stride + 1
-        u = F.unfold(xv.permute(0, 3, 1, 2).double(), k, padding=pad, stride=stride)          # [B, Cin * k * k, L], channel-major
-        cols = u.reshape(B, Cin, k * k, OH * OW).permute(0, 3, 2, 1).reshape(B, OH * OW, k * k * Cin)
-    if x2v is not None:
-        cols = torch.cat([cols, x2v.reshape(B, OH * OW, -1).double()], dim=-1)
-    return (cols @ wmat.double().t() + bias.double()).reshape(B, OH, OW, N)
-
-
-def epilogue_ref(y, act, res_mode, rv):
-    if res_mode == 1:
-        y = y + rv.double()
-    y = ACT_FN[act](y)
-    if res_mode == 2:
-        y = y + rv.double()
-    return y
 
 
 def assert_pair_bound(got, want, what):
@@ -138,9 +111,14 @@ def assert_pair_bound(got, want, what):
 
 
 class Operands:
-    """Operands of one table row, seeded by its name: fp32 draws, their storage on the device, and the values the kernel sees."""
+    """Operands of one table row, seeded by its name: fp32 draws, their storage on the device, and the values the kernel sees.
+    scales: None, or a hook (generator, row) -> dict(e=[Cin], e2=[C2] or None, f=[Cout]) of integer exponents, called after the draws
+    (which it therefore leaves as they are): input channel c is multiplied by 2^e_c (second input: 2^e2_c), filter column (tap, c) of
+    row n by 2^(f_n - e_c), bias and residual channel n by 2^f_n, the follower filter's column n by 2^-f_n; b1 stays.  Powers of two,
+    applied before the storage rounding: the pre-activation of channel n is the unscaled one times 2^f_n, term by term.
+    device: where the storage goes ("cpu": the seen values alone are wanted, tools/conv_f32_order.py)."""
 
-    def __init__(self, row):
+    def __init__(self, row, scales=None, device="cuda"):
         self.row = r = row
         g = torch.Generator().manual_seed(zlib.crc32(r["name"].encode()))
         B, H, W, Cin, Cout, k, C2, Cn = r["B"], r["H"], r["W"], r["Cin"], r["Cout"], r["k"], r["C2"], r["Cnext"]
@@ -154,6 +132,20 @@ class Operands:
         res = torch.randn(B, self.OH, self.OW, Cout, generator=g) if r["res_mode"] else None
         w1 = torch.randn(Cn, Cout, generator=g) * (1.0 / Cout) ** 0.5 if Cn else None
         self.b1 = torch.randn(Cn, generator=g) * 0.1 if Cn else None
+        self.scales = scales(g, r) if scales is not None else None
+        if self.scales is not None:
+            p2 = lambda e: torch.ldexp(torch.ones(e.shape), e)            # exact powers of two
+            e, e2, f = self.scales["e"], self.scales["e2"], self.scales["f"]
+            x *= p2(e)
+            w[:, : k * k * Cin] *= p2(f[:, None, None] - e[None, None, :]).expand(Cout, k * k, Cin).reshape(Cout, k * k * Cin)
+            self.b *= p2(f)
+            if C2:
+                x2 *= p2(e2)
+                w[:, k * k * Cin:] *= p2(f[:, None] - e2[None, :])
+            if res is not None:
+                res *= p2(f)
+            if Cn:
+                w1 *= p2(-f)[None, :]
         if self.pair:
             store = lambda t: pair_words(t)
             seen = lambda s: pair_values(s)
@@ -166,17 +158,17 @@ class Operands:
             self.wv = w.to(tdt).float()
             self.w1v = None
         xs = store(x)
-        self.xv, self.xd = seen(xs), xs.cuda()
+        self.xv, self.xd = seen(xs), xs.to(device)
         del x, xs
         self.x2v = self.x2d = self.rv = self.rd = None
         if C2:
             s = store(x2)
-            self.x2v, self.x2d = seen(s), s.cuda()
+            self.x2v, self.x2d = seen(s), s.to(device)
         if res is not None:
             s = store(res)
-            self.rv, self.rd = seen(s), s.cuda()
-        self.wd, self.bd = w.contiguous().cuda(), self.b.cuda()
-        self.w1d, self.b1d = (w1.contiguous().cuda(), self.b1.cuda()) if Cn else (None, None)
+            self.rv, self.rd = seen(s), s.to(device)
+        self.wd, self.bd = w.contiguous().to(device), self.b.to(device)
+        self.w1d, self.b1d = (w1.contiguous().to(device), self.b1.to(device)) if Cn else (None, None)
 
     def reference(self):
         r = self.row
@@ -213,11 +205,6 @@ def pool_avg_bits(L, y, B, H, W, C):
     ck(L, L.rtd_op_pool(1, _capi.DT_F16X2, y.ptr(), out.ptr(), B, H, W, C, C, C))
     out.values()
     return out.bits()
-
-
-def pooled_ref(y):
-    """3x3 / stride 2 / pad 1 max of fp64 [B, H, W, C]."""
-    return F.max_pool2d(y.permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1)
 
 
 @pytest.mark.parametrize("row", CASES, ids=[r["name"] for r in CASES])

@@ -412,8 +412,9 @@ def test_conv_split_f16x3(L, case):
 @pytest.mark.parametrize("shape", [(1, 40, 40, 64, 128, 1), (1, 160, 160, 64, 256, 1), (1, 24, 24, 64, 64, 3)])
 def test_a_nan_stays_a_nan_through_the_pair_format(L, shape):
     """split2 saturates at +-65504 instead of producing inf - but a NaN must stay a NaN, on the device (epilogue of every
-    pair kernel: tiled, streaming, direct 3x3 paths) as in the host mirror `_capi.to_split`: otherwise an upstream fault would be
-    laundered into a finite bound and no isfinite check could see it.  An overflow still saturates."""
+    pair kernel: tiled, streaming, direct 3x3 paths, without an activation and through ReLU) as in the host mirror `_capi.to_split`:
+    otherwise an upstream fault would be laundered into a finite bound and no isfinite check could see it.  An overflow still saturates.
+    (Every kernel family, with its receptive field held to fp64: tests/test_gpu_conv_range.py.)"""
     from telescope_cam_detection_amd import _capi
     B, H, W, Cin, Cout, k = shape
     x = torch.ones(B, H, W, Cin) * 0.5
@@ -428,14 +429,15 @@ def test_a_nan_stays_a_nan_through_the_pair_format(L, shape):
     wd = w.permute(0, 2, 3, 1).contiguous().cuda()
     bd = torch.zeros(Cout).cuda()
     xd = torch.from_numpy(xs.view(np.int16)).cuda()
-    yd = torch.full((B, H, W, 2 * Cout), -1, dtype=torch.int16, device="cuda")
-    ck(L, L.rtd_op_conv(_capi.DT_F16X2, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), None, yd.data_ptr(), B, H, W, Cin, Cout, k, k, 1, k // 2, 0, 0, 0))
-    got = _capi.from_split(yd.cpu().numpy().view(np.uint16))
-    nan_at = np.argwhere(np.isnan(got))
-    assert len(nan_at) > 0 and all(tuple(i[:3]) == (0, 3, 5) or k == 3 for i in nan_at)        # visible where it was put (3x3: also its window)
-    assert np.isnan(got[0, 3, 5, 7])
-    assert got[0, 9, 2, 1] == 65504.0                          # overflow saturates, finite
-    assert got[0, 20, 20, 3] == 0.5
+    for act in (0, 1):                                         # none, relu: max(NaN, 0) is 0 in fmaxf - the ReLU epilogues select instead
+        yd = torch.full((B, H, W, 2 * Cout), -1, dtype=torch.int16, device="cuda")
+        ck(L, L.rtd_op_conv(_capi.DT_F16X2, xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), None, yd.data_ptr(), B, H, W, Cin, Cout, k, k, 1, k // 2, act, 0, 0))
+        got = _capi.from_split(yd.cpu().numpy().view(np.uint16))
+        nan_at = np.argwhere(np.isnan(got))
+        assert len(nan_at) > 0 and all(tuple(i[:3]) == (0, 3, 5) or k == 3 for i in nan_at), act   # visible where it was put (3x3: also its window)
+        assert np.isnan(got[0, 3, 5, 7]), act
+        assert got[0, 9, 2, 1] == 65504.0, act                 # overflow saturates, finite
+        assert got[0, 20, 20, 3] == 0.5, act
 
 
 SX_NEXT_CASES = [
